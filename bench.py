@@ -13,6 +13,10 @@ configs[1]).  Inputs (processed waveform, start noise) are resident in HBM befor
 With N > 1 every rank processes its own B clips (weak scaling, no data-path collective) and one
 RCCL all-gather assembles the (N*B, 600, 32) result, inside the timed region.
 
+--dump-outputs DIR writes what the last timed step returned, (N*B, 600, 32) blendshape coefficients, as DIR/result.npy (float32;
+above 64 MB a fixed seeded sample of the clips).  The inputs, the eta > 0 noise seed included, are the same in every pass and every
+run with the same arguments, so two builds can be compared output for output.
+
 Prints ONE JSON line (rank 0).  Extra objects:
   roofline      dominant UNet kernel: algorithmic bytes per launch / HIP-event-timed launch duration
   cpu_baseline  the CPU oracle (a port of the reference path, oracle/) timed on this host's cores on a
@@ -65,6 +69,8 @@ def parse():
     p.add_argument("--tm_acts", type=int, nargs="?", const=1, default=-1, choices=[-1, 0, 1],
                    help="large-batch schedule with token-major activations between the UNet kernels and the normalisations inside the consuming "
                         "GEMMs (41 launches per step): -1 (default) = on in bf16 mode, off in fp32 mode; 0 / 1 force it (said_debug_option tm_acts)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the result of the last one as DIR/result.npy (float32; at most 64 MB: a seeded sample of the clips above that)")
     p.add_argument("--no_cpu_baseline", action="store_true")
     p.add_argument("--no_secondary", action="store_true",
                    help="skip the secondary configurations (BASELINE configs[2], [3] per GPU, [4], and the headline with eta = 1) that the "
@@ -77,6 +83,30 @@ def parse():
     p.add_argument("--dry_run_gloo", action="store_true",
                    help="no GPU: run the launch / shard / all-gather / timing plumbing on CPU over gloo with a stand-in path")
     return p.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each (clips, ...) tensor of `arrays` as out_dir/<name>.npy in float32.  One above its share of `limit` keeps a sample of
+    its clips drawn by numpy's default_rng(0), in clip order: the same rows in every run at the same shape.  Returns what was written."""
+    fresh = not os.path.isdir(out_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    if fresh:   # a directory this creates ignores itself in git, wherever it is put (as .pytest_cache does)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:
+            f.write("*\n")
+    info = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        n, cap = a.shape[0], max(1, limit // len(arrays) // (a[:1].nbytes or 1))
+        rows = "all"
+        if n > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(n, cap, replace=False))]
+            rows = f"{cap} of {n} clips, sampled by numpy default_rng(0)"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = {"shape": list(a.shape), "dtype": "float32", "rows": rows}
+    return info
 
 
 def cpu_info():
@@ -509,9 +539,12 @@ def run(args):
                                        dist=dist, device=torch.device("cpu"))
         if rank == 0:
             want = sum(float(c) * T * 32 for c in range(world * B))
-            print(json.dumps({"dry_run": "gloo/cpu stand-in path: NOT a measurement", "n_gpus": world, "steps": args.steps,
-                              "warmup": args.warmup, "clip_ranges": r.clip_ranges, "gathered_shape": list(r.gathered.shape),
-                              "gathered_checksum": r.checksum, "checksum_ok": r.checksum == want}), flush=True)
+            line = {"dry_run": "gloo/cpu stand-in path: NOT a measurement", "n_gpus": world, "steps": args.steps,
+                    "warmup": args.warmup, "clip_ranges": r.clip_ranges, "gathered_shape": list(r.gathered.shape),
+                    "gathered_checksum": r.checksum, "checksum_ok": r.checksum == want}
+            if args.dump_outputs:
+                line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, {"result": r.gathered})}
+            print(json.dumps(line), flush=True)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -559,6 +592,7 @@ def run(args):
     proc, lat0, edit_kw, T, Ta = make_inputs(model, dev, clips, args.seconds, args.edit)
 
     def path_fn(_clips):
+        torch.default_generator.manual_seed(0)   # SAID.inference draws the eta > 0 noise seed on torch's CPU generator: the same one in every pass and run
         return model.inference(proc, num_inference_steps=args.num_steps, guidance_scale=args.guidance_scale, eta=args.eta,
                                init_latents=lat0, **edit_kw).result
 
@@ -577,6 +611,8 @@ def run(args):
                                    dist=dist, device=dev)
     elapsed = r.elapsed_s
     assert torch.isfinite(r.gathered).all()
+    # copied out before anything below runs the model again
+    dumped = dump_outputs(args.dump_outputs, {"result": r.gathered}) if (args.dump_outputs and rank == 0) else None
 
     if rank == 0:
         frames = world * B * T * args.steps
@@ -600,6 +636,8 @@ def run(args):
                        "clip_ranges": r.clip_ranges, "gathered_checksum": r.checksum,
                        "graph_nodes_per_step": model._eng.graph_num_nodes()},
         }
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if args.ab_lib or args.debug_option:
             line["development_build"] = {"ab_lib": args.ab_lib, "debug_option": args.debug_option}   # not the shipped defaults: an A/B run
         if not args.no_roofline:
@@ -637,6 +675,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit(f"--gpus {args.gpus}: need at least one GPU")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps {args.steps} --warmup {args.warmup}: need at least one timed step and no negative warm-up")
     if not args.dry_run_gloo:
         # fail fast, before any rank is spawned: one process per GPU, HIP_VISIBLE_DEVICES (if set) already narrowed the
         # devices this process sees, and rank r uses visible device LOCAL_RANK = r

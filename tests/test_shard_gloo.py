@@ -127,19 +127,42 @@ def test_clip_range_partitions_without_overlap():
         assert ids == list(range(world * B))
 
 
-def test_bench_self_launches_ranks_dry_run():
+def test_bench_self_launches_ranks_dry_run(tmp_path):
     """`python bench.py --gpus 2` without torchrun must spawn its two ranks itself; on CPU this is
-    exercised through the gloo dry-run flag, which shares launch, shard, gather and timing code with the RCCL run."""
+    exercised through the gloo dry-run flag, which shares launch, shard, gather and timing code with the RCCL run.
+    --dump-outputs writes the gathered result of the last pass (rank 0 only) into a directory that git ignores."""
+    import numpy as np
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
+    dump = tmp_path / "outputs"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "2", "--steps", "2", "--warmup", "1",
-                          "--seconds", "0.5", "--dry_run_gloo"], capture_output=True, text=True, timeout=300, env=env)
+                          "--seconds", "0.5", "--dry_run_gloo", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                               # ONE JSON line, from rank 0
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["clip_ranges"] == [[0, 1], [2, 3]] and j["gathered_shape"] == [4, 30, 32] and j["checksum_ok"]
+    res = np.load(dump / "result.npy")
+    assert res.dtype == np.float32 and np.array_equal(res, np.broadcast_to(np.arange(4, dtype=np.float32)[:, None, None], (4, 30, 32)))
+    assert j["dump_outputs"]["arrays"]["result"] == {"shape": [4, 30, 32], "dtype": "float32", "rows": "all"}
+    assert sorted(os.listdir(dump)) == [".gitignore", "result.npy"] and (dump / ".gitignore").read_text() == "*\n"
+
+
+def test_bench_dump_outputs_samples_clips_above_the_limit(tmp_path):
+    """Above the byte limit bench.dump_outputs keeps a seeded sample of whole clips in clip order, the same in every run; an existing
+    directory gets no .gitignore."""
+    import numpy as np
+    import bench
+    x = torch.arange(10, dtype=torch.float64)[:, None, None].expand(10, 6, 32)      # 768 bytes per clip in float32
+    a = bench.dump_outputs(str(tmp_path), {"result": x}, limit=3 * 768 + 100)
+    b = bench.dump_outputs(str(tmp_path / "again"), {"result": x}, limit=3 * 768 + 100)
+    assert a == b and a["result"]["shape"] == [3, 6, 32] and a["result"]["rows"].startswith("3 of 10 clips")
+    got = np.load(tmp_path / "result.npy")
+    ids = got[:, 0, 0]
+    assert got.dtype == np.float32 and len(set(ids)) == 3 and list(ids) == sorted(ids) and np.array_equal(got, x.float().numpy()[ids.astype(int)])
+    assert np.array_equal(got, np.load(tmp_path / "again" / "result.npy"))
+    assert not (tmp_path / ".gitignore").exists()
 
 
 # ---------------------------------------------------------------- round 4: the product entry point, uneven shards
