@@ -205,20 +205,19 @@ double said_unet_algorithmic_flops(int batch_eff, int frames);
 int said_profile_unet(said_ctx* ctx, int batch_eff, int frames, int cfg_clips, int reps, int max_stages, float* us_out, double* bytes_out,
                       double* flops_out, int* kind_out, int* epi_out, int* nb_out, int* ks_out, int* n_stages_out, void* stream);
 
-/* ---- VAE encoder ----------------------------------------------
- * Replaces the device work of BCVAE.encode -> BCEncoder.forward (said/model/vae.py:26-83,
- * 228-243) as driven by generate_latents_info (script/test_evaluate.py:53-106): sliding
- * windows of 120 frames of (T, 32) coefficients -> the 64-d latent mean used by the FD /
- * WInD / multimodality metrics.  Eval-mode only: BatchNorm1d layers use their running
- * statistics and are folded into the preceding Conv1d / Linear on the host.  The decoder
- * (vae.py:115-178) is not on this path; its state-dict keys are accepted and ignored. */
+/* ---- VAE -------------------------------------------------------
+ * Encoder: the device work of BCVAE.encode -> BCEncoder.forward (said/model/vae.py:26-83, 228-243) as driven by
+ * generate_latents_info (script/test_evaluate.py:53-106): windows of 120 frames -> the 64-d latent.  Decoder: BCVAE.decode
+ * (vae.py:115-170, 258-272), optionally fused with the reparametrisation (vae.py:106-110).  Eval-mode only: BatchNorm1d
+ * layers use their running statistics and are folded into the preceding layer on the host. */
 typedef struct said_vae said_vae;
 /* BCVAE(channels=32, seq_len=120, z_dim=64) (vae.py:181-207); other sizes are refused. */
 int said_vae_create(said_vae** out, int device, int in_channels, int seq_len, int z_dim);
 int said_vae_destroy(said_vae* vae);
 const char* said_vae_last_error(const said_vae* vae);
 /* `name` is the BCVAE state-dict key ("encoder.conv_layers.0.weight", ..., "encoder.fc_mu.bias", BatchNorm "running_mean"/"running_var" included;
- * "num_batches_tracked" may be passed as a float scalar or omitted).  Replaces said_vae.load_state_dict(...) + .to(device) (test_evaluate.py:551-553). */
+ * "num_batches_tracked" may be passed as a float scalar or omitted).  Replaces said_vae.load_state_dict(...) + .to(device) (test_evaluate.py:551-553).
+ * The 24 decoder.* tensors are optional, all or none: with them the context can decode, a partial set fails finalize. */
 int said_vae_set_weight(said_vae* vae, const char* name, const float* data_host, const int64_t* shape, int ndim);
 int said_vae_finalize_weights(said_vae* vae);
 /* encode `n_windows` windows of (120, 32) fp32 coefficients.  Window w starts at coeffs_dev + w * window_stride_floats: 120*32 for a (N, 120, 32) batch of
@@ -226,6 +225,12 @@ int said_vae_finalize_weights(said_vae* vae);
  * logvar_dev (nullable) are (n_windows, 64) row-major: BCLatent.mean / .log_var (vae.py:79-83). */
 int said_vae_encode(said_vae* vae, const float* coeffs_dev, long long window_stride_floats, int n_windows, float* mean_dev,
                     float* logvar_dev, void* stream);
+/* 1 if the context was finalized with the decoder.* weights (said_vae_decode can run), else 0. */
+int said_vae_has_decoder(const said_vae* vae);
+/* n latents (n, 64) -> (n, 120, 32) coefficients (BCDecoder.forward, vae.py:158-170; BCVAE.decode, vae.py:258-272), one launch, no workspace.  eps_dev
+ * nullable: given, z = mean + exp(0.5 log_var) eps (BCEncoder.reparametrize, vae.py:106-110, with the caller's eps), else z = mean, log_var ignored.
+ * Row-major device buffers, coeffs_out_dev 16-byte aligned.  Fails without decoder weights. */
+int said_vae_decode(said_vae* vae, const float* mean_dev, const float* logvar_dev, const float* eps_dev, int n, float* coeffs_out_dev, void* stream);
 
 #ifdef __cplusplus
 }

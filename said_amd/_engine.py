@@ -86,7 +86,12 @@ EXPORTS = {
     "said_vae_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
     "said_vae_finalize_weights": (c_int, [c_void_p]),
     "said_vae_encode": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p]),
+    "said_vae_has_decoder": (c_int, [c_void_p]),
+    "said_vae_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
 }
+# Added without an ABI version bump: a library built before them still loads (everything else works) and the decoder
+# entry points raise "rebuild" when called (VaeEngine.decode).
+LATE_EXPORTS = frozenset({"said_vae_has_decoder", "said_vae_decode"})
 
 
 def library_path() -> str:
@@ -104,6 +109,8 @@ def load_library():
             "said_amd has no CPU fallback.")
     lib = ctypes.CDLL(_LIB_PATH)
     for name, (res, args) in EXPORTS.items():
+        if name in LATE_EXPORTS and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -446,8 +453,12 @@ class Engine:
         return a.value, bool(b.value)
 
 
+class NoCpuPathError(EngineError, NotImplementedError):
+    """A model method called on a CPU-resident model: said_amd computes on the MI355X only."""
+
+
 class VaeEngine:
-    """BCVAE encoder context on one GPU (include/said_hip.h, "VAE encoder")."""
+    """BCVAE context on one GPU (include/said_hip.h, "VAE"): the encoder always, the decoder when its weights were loaded."""
 
     def __init__(self, device: torch.device, in_channels: int = 32, seq_len: int = 120, z_dim: int = 64):
         self.lib = load_library()
@@ -500,6 +511,40 @@ class VaeEngine:
             self._chk(self.lib.said_vae_encode(self.h, _ptr(coeffs), int(window_stride), int(n_windows), _ptr(mean), _ptr(logvar), _stream()),
                       "said_vae_encode")
         return mean, logvar
+
+    def _decode_entry(self, name: str):
+        if not hasattr(self.lib, name):
+            raise EngineError(f"{_LIB_PATH} predates the VAE decoder ({name} is not exported): rebuild it with `python -m said_amd.build --force`")
+        return getattr(self.lib, name)
+
+    @property
+    def has_decoder(self) -> bool:
+        return bool(self._decode_entry("said_vae_has_decoder")(self.h))
+
+    def decode(self, mean: torch.Tensor, log_var: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(n, z_dim) latents -> (n, seq_len, in_channels) coefficients.  With `eps`, the latent is mean + exp(0.5 log_var) eps,
+        computed in the decoder launch's prologue."""
+        fn = self._decode_entry("said_vae_decode")
+        z = self.z_dim
+        if eps is not None and log_var is None:
+            raise ValueError("eps needs log_var")
+        args = {"mean": mean, "log_var": log_var, "eps": eps}
+        for k, t in args.items():
+            if t is None:
+                continue
+            if t.dim() != 2 or t.shape[1] != z or t.shape[0] != mean.shape[0]:
+                raise ValueError(f"{k} must be (n, {z}) like mean {tuple(mean.shape)}, got {tuple(t.shape)}")
+            args[k] = _check_dev(t, k)
+            if t.device.index != self.index:
+                raise EngineError(f"{k} lives on cuda:{t.device.index}, this VAE engine on cuda:{self.index}")
+        n = int(mean.shape[0])
+        out = torch.empty(n, self.seq_len, self.in_channels, device=self.device if n == 0 else args["mean"].device, dtype=torch.float32)
+        if n == 0:
+            return out
+        lv = args["log_var"] if eps is not None else None
+        with torch.cuda.device(self.index):
+            self._chk(fn(self.h, _ptr(args["mean"]), _ptr(lv), _ptr(args["eps"]), n, _ptr(out), _stream()), "said_vae_decode")
+        return out
 
 
 def unet_algorithmic_bytes(batch_eff: int, frames: int, bytes_per_elem: int = 4) -> float:

@@ -3423,6 +3423,9 @@ struct said_vae {
     // workspace for `cap` windows at a time
     int cap = 0;
     float *X0 = nullptr, *Y[4] = {nullptr, nullptr, nullptr, nullptr}, *F = nullptr, *G1 = nullptr, *G2 = nullptr, *G3 = nullptr, *G4 = nullptr;
+    // decoder (vae.py:115-170): present when the state dict held the decoder.* keys; one fused launch, no workspace (vae_dec.hip)
+    bool has_dec = false;
+    VaeDecWeights dec{};
 };
 
 namespace {
@@ -3449,6 +3452,94 @@ int fold_bn(said_ctx* ctx, const std::string& wname, const std::string& bname, c
     ctx->host_w[out_w] = std::move(W);
     ctx->host_w[out_b] = std::move(B);
     return 0;
+}
+
+// The decoder half of the state dict (vae.py:135-156): the 24 decoder.* tensors (+3 optional num_batches_tracked), all or none.
+const char* const kDecKeys[] = {
+    "fc_layers.0.weight", "fc_layers.0.bias", "fc_layers.1.weight", "fc_layers.1.bias", "fc_layers.1.running_mean", "fc_layers.1.running_var",
+    "fc_layers.3.weight", "fc_layers.3.bias", "conv_layers.0.weight", "conv_layers.0.bias", "conv_layers.1.weight", "conv_layers.1.bias",
+    "conv_layers.1.running_mean", "conv_layers.1.running_var", "conv_layers.3.weight", "conv_layers.3.bias", "conv_layers.4.weight",
+    "conv_layers.4.bias", "conv_layers.4.running_mean", "conv_layers.4.running_var", "conv_layers.6.weight", "conv_layers.6.bias",
+    "conv_layers.7.weight", "conv_layers.7.bias"};
+const char* const kDecCounters[] = {"fc_layers.1.num_batches_tracked", "conv_layers.1.num_batches_tracked", "conv_layers.4.num_batches_tracked"};
+
+// 0: no decoder.* key (encoder-only state dict), 1: decoder folded and uploaded to v->dec, -1: error (partial or mis-shaped decoder)
+int load_vae_decoder(said_vae* v) {
+    said_ctx* ctx = &v->c;
+    const std::string D = "decoder.";
+    size_t present = 0;
+    for (auto& kv : ctx->host_w) {
+        const std::string& k = kv.first;
+        if (k.rfind(D, 0) != 0) continue;
+        const std::string leaf = k.substr(D.size());
+        bool known = false;
+        for (const char* e : kDecKeys) known = known || leaf == e;
+        if (known) ++present;
+        else {
+            bool counter = false;
+            for (const char* e : kDecCounters) counter = counter || leaf == e;
+            if (!counter) return fail(ctx, "unexpected key(s) in state dict: %s", k.c_str());
+        }
+    }
+    if (present == 0) return 0;
+    const size_t expect = sizeof(kDecKeys) / sizeof(kDecKeys[0]);
+    if (present != expect) {
+        for (const char* e : kDecKeys)
+            if (!ctx->host_w.count(D + e))
+                return fail(ctx, "partial decoder state dict: %zu of %zu decoder.* tensors, missing %s%s (pass all of them or none)", present, expect, D.c_str(), e);
+    }
+    const int Z = v->zdim, H1 = 2 * v->seq_len, H2 = 4 * v->seq_len;   // 64, 240, 480
+    if (!getw(ctx, D + "fc_layers.0.weight", {H1, Z}) || !getw(ctx, D + "fc_layers.0.bias", {H1}) || !getw(ctx, D + "fc_layers.3.weight", {H2, H1}) ||
+        !getw(ctx, D + "fc_layers.3.bias", {H2}))
+        return -1;
+    if (fold_bn(ctx, D + "fc_layers.0.weight", D + "fc_layers.0.bias", D + "fc_layers.1", "__vdfc1.w", "__vdfc1.b")) return -1;
+    // ConvTranspose1d (stride 1, no padding) weight (cin, cout, k) -> Conv1d weight (cout, cin, k) with the taps flipped, applied
+    // to the input zero-padded by k-1 on each side: y[co][t] = sum_ci sum_j xpad[ci][t + j] * W[ci][co][k-1-j]
+    const int ct_cin[2] = {4, 32}, conv_cin[4] = {4, 32, 32, 32};
+    const char* conv_idx[4] = {"0", "3", "6", "7"};
+    const char* conv_bn[4] = {"1", "4", "", ""};
+    for (int l = 0; l < 4; ++l) {
+        const std::string w = D + "conv_layers." + conv_idx[l];
+        const int cin = conv_cin[l];
+        const HostTensor* W = l < 2 ? getw(ctx, w + ".weight", {ct_cin[l], 32, 3}) : getw(ctx, w + ".weight", {32, cin, 3});
+        if (!W || !getw(ctx, w + ".bias", {32})) return -1;
+        std::string wname = w + ".weight";
+        if (l < 2) {
+            HostTensor C;
+            C.shape = {32, cin, 3};
+            C.data.resize((size_t)32 * cin * 3);
+            for (int ci = 0; ci < cin; ++ci)
+                for (int co = 0; co < 32; ++co)
+                    for (int j = 0; j < 3; ++j) C.data[((size_t)co * cin + ci) * 3 + j] = W->data[((size_t)ci * 32 + co) * 3 + (2 - j)];
+            wname = "__vdconv" + std::to_string(l) + ".flip";
+            ctx->host_w[wname] = std::move(C);
+        }
+        const std::string bn = conv_bn[l][0] ? D + "conv_layers." + conv_bn[l] : "";
+        const std::string ow = "__vdconv" + std::to_string(l) + ".w", ob = "__vdconv" + std::to_string(l) + ".b";
+        if (fold_bn(ctx, wname, w + ".bias", bn, ow, ob)) return -1;
+        // kernel order [cin][32][3]: one wave's 8 output channels x 3 taps for one cin are contiguous (vae_dec.hip)
+        const HostTensor& F = ctx->host_w[ow];
+        std::vector<float> P((size_t)cin * 32 * 3);
+        for (int co = 0; co < 32; ++co)
+            for (int ci = 0; ci < cin; ++ci)
+                for (int j = 0; j < 3; ++j) P[((size_t)ci * 32 + co) * 3 + j] = F.data[((size_t)co * cin + ci) * 3 + j];
+        if (upload(ctx, const_cast<float**>(&v->dec.conv_w[l]), P.data(), P.size())) return -1;
+        if (upload(ctx, const_cast<float**>(&v->dec.conv_b[l]), ctx->host_w[ob].data.data(), 32)) return -1;
+    }
+    {   // the linears input-major: [in][out]
+        auto transpose_up = [&](const std::string& name, int N, int K, const float** dst) {
+            const HostTensor& T = ctx->host_w[name];
+            std::vector<float> P((size_t)K * N);
+            for (int o = 0; o < N; ++o)
+                for (int i = 0; i < K; ++i) P[(size_t)i * N + o] = T.data[(size_t)o * K + i];
+            return upload(ctx, const_cast<float**>(dst), P.data(), P.size());
+        };
+        if (transpose_up("__vdfc1.w", H1, Z, &v->dec.fc1_w) || transpose_up(D + "fc_layers.3.weight", H2, H1, &v->dec.fc2_w)) return -1;
+        if (upload(ctx, const_cast<float**>(&v->dec.fc1_b), ctx->host_w["__vdfc1.b"].data.data(), H1) ||
+            upload(ctx, const_cast<float**>(&v->dec.fc2_b), ctx->host_w[D + "fc_layers.3.bias"].data.data(), H2))
+            return -1;
+    }
+    return 1;
 }
 }  // namespace
 
@@ -3541,8 +3632,8 @@ int said_vae_finalize_weights(said_vae* v) {
         ctx->host_w["__vhead.b"] = std::move(B);
         if (make_pw(ctx, &v->head, "__vhead.w", "__vhead.b", 2 * v->zdim, v->zdim, 0)) return -1;
     }
-    // strict key check, like load_state_dict(strict=True) of the encoder half; decoder.* keys are accepted and ignored
-    // (the decoder is not on this path), num_batches_tracked counters are metadata
+    // strict key check, like load_state_dict(strict=True) of the encoder half; the decoder.* keys are checked by load_vae_decoder
+    // (all or none), num_batches_tracked counters are metadata
     size_t enc = 0;
     for (auto& kv : ctx->host_w) {
         const std::string& k = kv.first;
@@ -3552,6 +3643,9 @@ int said_vae_finalize_weights(said_vae* v) {
     }
     const size_t expect_min = 4 * 2 + 3 * 4 + 3 * 2 + 2 * 4 + 4;   // convs, conv BNs, fcs, fc BNs, mu/logvar (+ optional num_batches_tracked)
     if (enc < expect_min || enc > expect_min + 5) return fail(ctx, "unexpected key(s) in state dict: %zu encoder.* tensors, expected %zu (+5 num_batches_tracked)", enc, expect_min);
+    const int dec = load_vae_decoder(v);
+    if (dec < 0) return -1;
+    v->has_dec = dec == 1;
     ctx->host_w.clear();
     v->finalized = true;
     return 0;
@@ -3616,6 +3710,33 @@ int said_vae_encode(said_vae* v, const float* coeffs_dev, long long window_strid
         fc(v->head, v->G3, Z, v->G4, 2 * Z, false, 4, 4);
         launch_cm_to_tm(v->G4, mean_dev + (long long)w0 * Z, 1, nb, Z, np, 0, s);
         if (logvar_dev) launch_cm_to_tm(v->G4 + (long long)Z * np, logvar_dev + (long long)w0 * Z, 1, nb, Z, np, 0, s);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int said_vae_has_decoder(const said_vae* v) { return v && v->finalized && v->has_dec ? 1 : 0; }
+
+// BCVAE.decode (vae.py:158-170, 258-272) of n latents, fused with BCVAE.reparametrize (vae.py:106-110) when eps_dev is given.
+int said_vae_decode(said_vae* v, const float* mean_dev, const float* logvar_dev, const float* eps_dev, int n, float* coeffs_out_dev, void* stream) {
+    if (!v) return -1;
+    said_ctx* ctx = &v->c;
+    if (!v->finalized) return fail(ctx, "weights not finalized: call said_vae_finalize_weights first");
+    if (!v->has_dec)
+        return fail(ctx, "said_vae_decode: this context holds no decoder weights (its state dict had no decoder.* keys): load the full BCVAE state dict");
+    if (n < 0 || (n > 0 && (!mean_dev || !coeffs_out_dev))) return fail(ctx, "said_vae_decode: bad arguments");
+    if (eps_dev && !logvar_dev) return fail(ctx, "said_vae_decode: eps_dev given without logvar_dev");
+    if (reinterpret_cast<uintptr_t>(coeffs_out_dev) & 15) return fail(ctx, "said_vae_decode: coeffs_out_dev must be 16-byte aligned");
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int Z = v->zdim, out_w = v->seq_len * v->cin;
+    const int chunk = 16384;   // windows per launch: keeps every in-kernel index far from int range
+    for (int w0 = 0; w0 < n; w0 += chunk) {
+        const int nb = std::min(chunk, n - w0);
+        const long long o = (long long)w0 * Z;
+        launch_vae_decode(v->dec, mean_dev + o, logvar_dev ? logvar_dev + o : nullptr, eps_dev ? eps_dev + o : nullptr, nb,
+                          coeffs_out_dev + (long long)w0 * out_w, s);
     }
     HIPCHK(hipGetLastError());
     return 0;

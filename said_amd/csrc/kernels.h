@@ -296,6 +296,17 @@ void launch_windows_to_cm(const float* src, long long win_stride, float* dst, in
 // nn.Flatten of the conv stack's (n, C, T) output into the feature-major FC operand: dst[c * T + t][w] = src[w][c][t]
 void launch_flatten_cm(const float* src, long long src_bstride, int src_pitch, float* dst, int dst_pitch, int n, int C, int T, hipStream_t s);
 
+// ---- VAE decoder (said/model/vae.py:115-170): one fused launch (vae_dec.hip) ----
+// host-packed weights, BatchNorms folded: fc1_w [64][240], fc2_w [240][480], conv_w[l] [cin][32][3] (ConvTranspose layers 0, 1
+// already rewritten as flipped Conv1d over a 2-padded input), conv_b[l] [32]
+struct VaeDecWeights {
+    const float *fc1_w, *fc1_b, *fc2_w, *fc2_b;
+    const float* conv_w[4];
+    const float* conv_b[4];
+};
+// (n, 64) latents -> (n, 120, 32) token-major coefficients; eps non-null: z = mean + exp(0.5 logvar) eps.  out: 16-byte aligned.
+void launch_vae_decode(const VaeDecWeights& w, const float* mean, const float* logvar, const float* eps, int n, float* out, hipStream_t s);
+
 // ---- audio-encoder specific kernels ----
 // conv0: 1 -> C channels, kernel K, stride S, no bias (Wav2Vec2 feature extractor layer 0)
 void launch_conv0(const float* wav, const float* w, float* y, int B, int Ta, int C, int K, int S, int Tout, int pitch,

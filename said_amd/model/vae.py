@@ -1,11 +1,12 @@
-"""BCVAE — encoder half on the MI355X engine.
+"""BCVAE on the MI355X engine.
 
-Drop-in for the slice of /root/reference/said/model/vae.py that the evaluation driver uses
-(script/test_evaluate.py:53-106, 551-554): ``BCVAE()`` with the reference's ``state_dict()`` key layout (70 tensors,
-``encoder.*`` and ``decoder.*``, so ``load_state_dict(torch.load("vae.pth"))`` works strictly), ``.seq_len``,
-``.eval()`` and ``.encode(coeffs) -> BCLatent(mean, log_var)``.  All encoder math runs in HIP (``said_vae_encode``);
-modules only hold parameters.  The decoder / reparametrisation are training-time components and are out of scope
-(SURVEY.md §2 row 8): their parameters are kept so that checkpoints load, calling them raises.
+Drop-in for /root/reference/said/model/vae.py in eval mode: ``BCVAE()`` with the reference's ``state_dict()`` key layout
+(70 tensors, ``encoder.*`` and ``decoder.*``, so ``load_state_dict(torch.load("vae.pth"))`` works strictly), ``.seq_len``,
+``.eval()``, ``.encode(coeffs) -> BCLatent(mean, log_var)``, ``.reparametrize(mean, log_var)``, ``.decode(latent)`` and
+``forward(coeffs, use_noise) -> BCVAEOutput(mean, log_var, latent, coeffs_reconst)`` (script/inference_vae.py).  All
+encoder and decoder math runs in HIP (``said_vae_encode``; ``said_vae_decode``, one fused launch that also applies the
+reparametrisation); modules only hold parameters.  The reparametrisation noise is the reference's own draw,
+``torch.randn(B, z_dim)`` on the CPU generator, so ``torch.manual_seed`` reproduces it.  Training is out of scope.
 
 Extension (not in the reference): ``encode_windows`` runs all sliding windows of a sequence in ONE engine call instead
 of the reference's Python loop over windows (test_evaluate.py:92-95).
@@ -27,6 +28,16 @@ class BCLatent:
 
     mean: torch.FloatTensor
     log_var: torch.FloatTensor
+
+
+@dataclass
+class BCVAEOutput:
+    """Output of the BCVAE"""
+
+    mean: torch.FloatTensor
+    log_var: torch.FloatTensor
+    latent: torch.FloatTensor
+    coeffs_reconst: torch.FloatTensor
 
 
 class _ConvP(nn.Module):
@@ -79,7 +90,8 @@ class BCEncoder(nn.Module):
 
 
 class BCDecoder(nn.Module):
-    """Parameter container of vae.py:115-178 (kept so that vae.pth loads strictly; not computed on this path)."""
+    """Parameter container of vae.py:115-178 (Linear/BatchNorm1d/LeakyReLU, Linear, Unflatten; ConvTranspose1d/BatchNorm1d/
+    LeakyReLU x2, Conv1d x2, ReLU, Tanh), computed by said_vae_decode."""
 
     def __init__(self, out_channels: int = 32, seq_len: int = 120, z_dim: int = 64):
         super().__init__()
@@ -89,7 +101,7 @@ class BCDecoder(nn.Module):
 
 
 class BCVAE(nn.Module):
-    """Autoencoder for the blendshape coefficients — encoder on the HIP engine (vae.py:181-272)."""
+    """Autoencoder for the blendshape coefficients on the HIP engine (vae.py:181-272)."""
 
     def __init__(self, channels: int = 32, seq_len: int = 120, z_dim: int = 64):
         super().__init__()
@@ -124,18 +136,18 @@ class BCVAE(nn.Module):
         ts = list(self.parameters()) + list(self.buffers())
         return (str(ts[0].device), tuple(t._version for t in ts))
 
-    def _get_engine(self) -> _engine.VaeEngine:
+    def _get_engine(self, what: str = "encode") -> _engine.VaeEngine:
         dev = next(self.parameters()).device
         if dev.type != "cuda":
-            raise _engine.EngineError(f"model is on {dev}: said_amd runs on MI355X only — call .to('cuda:N')")
+            raise _engine.NoCpuPathError(f"model is on {dev}: said_amd runs on MI355X only — call .to('cuda:N')")
         if self.training:
-            raise _engine.EngineError("BCVAE.encode on the HIP engine is eval-mode only (BatchNorm uses running statistics): call .eval()")
+            raise _engine.EngineError(f"BCVAE.{what} on the HIP engine is eval-mode only (BatchNorm uses running statistics): call .eval()")
         key = self._weights_key()
         if self._eng is None or self._eng_stale or key != self._eng_key:
             if self._eng is not None:
                 self._eng.close()
             e = _engine.VaeEngine(dev, self.channels, self.seq_len, self.z_dim)
-            e.load_weights({k: v for k, v in self.state_dict().items() if k.startswith("encoder.")})
+            e.load_weights({k: v for k, v in self.state_dict().items() if k.startswith(("encoder.", "decoder."))})
             self._eng, self._eng_key, self._eng_stale = e, key, False
         return self._eng
 
@@ -158,12 +170,37 @@ class BCVAE(nn.Module):
         mean, _ = self._get_engine().encode(coeffs_seq.contiguous(), n, window_step_size * self.channels, want_logvar=False)
         return mean
 
-    def forward(self, coeffs: torch.Tensor, use_noise: bool = True):
-        raise NotImplementedError("BCVAE.forward (reparametrise + decode, vae.py:209-226) is a training-time path: out of scope "
-                                  "(SURVEY.md §2 row 8); use .encode()")
+    def _latents(self, t: torch.Tensor, name: str) -> torch.Tensor:
+        if t.dim() != 2 or t.shape[1] != self.z_dim:
+            raise ValueError(f"{name} must be (B, {self.z_dim}), got {tuple(t.shape)}")
+        return t
 
-    def decode(self, latent: torch.Tensor):
-        raise NotImplementedError("BCVAE.decode (vae.py:258-272) is not on the evaluation path: out of scope (SURVEY.md §2 row 8)")
+    def reparametrize(self, mean: torch.Tensor, log_var: torch.Tensor, *, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mean + exp(0.5 log_var) eps, (B, z_dim)   (vae.py:94-112, 244-256).  `eps` None: the reference's draw,
+        torch.randn(B, z_dim) on the CPU generator, moved to the model's device."""
+        self._get_engine("reparametrize")
+        self._latents(mean, "mean")
+        self._latents(log_var, "log_var")
+        if eps is None:
+            eps = torch.randn(mean.shape[0], self.z_dim).to(mean.device)
+        return mean + torch.exp(0.5 * log_var) * eps
 
-    def reparametrize(self, mean, log_var):
-        raise NotImplementedError("BCVAE.reparametrize (vae.py:244-256) is a training-time path: out of scope")
+    def decode(self, latent: torch.Tensor) -> torch.Tensor:
+        """(B, z_dim) latents -> (B, seq_len, channels) blendshape coefficients   (vae.py:158-170, 258-272)."""
+        eng = self._get_engine("decode")
+        return eng.decode(self._latents(latent, "latent"))
+
+    def forward(self, coeffs: torch.Tensor, use_noise: bool = True, *, eps: Optional[torch.Tensor] = None) -> BCVAEOutput:
+        """encode -> (reparametrize | mean) -> decode   (vae.py:209-226): two engine launches, the reparametrisation runs in
+        the decoder launch.  `eps` replaces the reference's torch.randn draw when use_noise is set."""
+        eng = self._get_engine("forward")
+        lat = self.encode(coeffs)
+        if not use_noise:
+            return BCVAEOutput(mean=lat.mean, log_var=lat.log_var, latent=lat.mean, coeffs_reconst=eng.decode(lat.mean))
+        if eps is None:
+            eps = torch.randn(lat.mean.shape[0], self.z_dim).to(lat.mean.device)
+        elif tuple(eps.shape) != tuple(lat.mean.shape):
+            raise ValueError(f"eps must be {tuple(lat.mean.shape)}, got {tuple(eps.shape)}")
+        eps = eps.to(lat.mean.device)
+        latent = lat.mean + torch.exp(0.5 * lat.log_var) * eps
+        return BCVAEOutput(mean=lat.mean, log_var=lat.log_var, latent=latent, coeffs_reconst=eng.decode(lat.mean, lat.log_var, eps))

@@ -181,6 +181,49 @@ def vae_encoder_state_dict(salt: int = 0) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def vae_decoder_param_shapes() -> Dict[str, Tuple[int, ...]]:
+    """Names/shapes of the ``decoder.*`` half of the reference's BCVAE state dict (said/model/vae.py:135-156), BatchNorm
+    running statistics included (num_batches_tracked counters are not weights and are left out, as above)."""
+    s: Dict[str, Tuple[int, ...]] = {}
+    for idx, (co, ci) in {0: (240, 64), 3: (480, 240)}.items():
+        s[f"decoder.fc_layers.{idx}.weight"] = (co, ci)
+        s[f"decoder.fc_layers.{idx}.bias"] = (co,)
+    for idx, shp in {0: (4, 32, 3), 3: (32, 32, 3), 6: (32, 32, 3), 7: (32, 32, 3)}.items():   # 0, 3: ConvTranspose1d (cin, cout, k)
+        s[f"decoder.conv_layers.{idx}.weight"] = shp
+        s[f"decoder.conv_layers.{idx}.bias"] = (32,)
+    for pre, n in (("decoder.fc_layers.1", 240), ("decoder.conv_layers.1", 32), ("decoder.conv_layers.4", 32)):
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            s[f"{pre}.{leaf}"] = (n,)
+    return s
+
+
+_VAE_DEC_BN = ("decoder.fc_layers.1.", "decoder.conv_layers.1.", "decoder.conv_layers.4.")
+_VAE_DEC_CT = ("decoder.conv_layers.0.weight", "decoder.conv_layers.3.weight")
+
+
+def vae_state_dict(salt: int = 0) -> Dict[str, torch.Tensor]:
+    """The full 70-tensor BCVAE state dict: ``vae_encoder_state_dict(salt)`` plus a deterministic decoder fill.  Decoder
+    BatchNorm statistics are non-trivial (running_mean ~ 0.3 N(0,1), running_var in [0.25, 2.25], gains ~ 1 +- 0.2) so the
+    host folding matters; ConvTranspose1d weights are scaled by their real fan-in (cin * k); num_batches_tracked = 100."""
+    sd = vae_encoder_state_dict(salt)
+    for pre in ("encoder.conv_layers.1", "encoder.conv_layers.4", "encoder.conv_layers.7", "encoder.fc_layers.1", "encoder.fc_layers.4"):
+        sd[pre + ".num_batches_tracked"] = torch.tensor(100, dtype=torch.long)
+    for k, shp in vae_decoder_param_shapes().items():
+        t = fill_tensor(k, shp, salt)
+        if k in _VAE_DEC_CT:
+            t = t * (shp[1] / shp[0]) ** 0.5   # fill_tensor scaled by 1/sqrt(cout * k); a transposed conv's fan-in is cin * k
+        if k.startswith(_VAE_DEC_BN):
+            g = torch.Generator()
+            g.manual_seed((zlib.crc32(k.encode()) + 7919 * salt) & 0x7FFFFFFF)
+            r = torch.randn(shp, generator=g, dtype=torch.float32)
+            leaf = k.split(".")[-1]
+            t = {"weight": 1.0 + 0.2 * r, "bias": 0.2 * r, "running_mean": 0.3 * r, "running_var": 1.25 + torch.tanh(r)}[leaf]
+        sd[k] = t
+    for pre in _VAE_DEC_BN:
+        sd[pre + "num_batches_tracked"] = torch.tensor(100, dtype=torch.long)
+    return sd
+
+
 # ---------------------------------------------------------------------------
 # Deterministic fill
 # ---------------------------------------------------------------------------
