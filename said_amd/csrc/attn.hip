@@ -599,22 +599,10 @@ bool battn_supports(const AttnArgs& a, int head_dim) {
     return head_dim == 32 && a.T >= 1 && a.T <= 640 && a.pitch >= ((a.T + 31) & ~31) && a.rows >= ((a.T + 31) & ~31) && a.v_bstride <= 0x7fffffffLL && a.o_bstride <= 0x7fffffffLL;
 }
 // q / k: bf16 [b][2 heads][rows][32] at a.qk, v: bf16 [b][heads * 32][pitch] at a.v (tokens permuted per 16: TGemmArgs::qkv_bf16), o: bf16 token-major
-void launch_battn(const AttnArgs& a, int batch, hipStream_t s, int qt) {
+void launch_battn(const AttnArgs& a, int batch, hipStream_t s) {
     // K: the key rows actually used; V^T: 81 pieces per row.  T = 600: 80,384 bytes — two workgroups per CU with room to spare (2 x 81,920 is the
     // whole LDS of a CU to the byte, and measured like ONE workgroup per CU)
     const int lds_bytes = ((((a.T + 31) / 32) * 32) * 4 + 32 * 81) * 16;
-    if (qt == 4) {
-        dim3 grid((((a.T + 31) / 32) + 3) / 4, a.heads, batch);
-        hipLaunchKernelGGL(battn_kernel<4>, grid, dim3(256), lds_bytes, s, reinterpret_cast<const unsigned short*>(a.qk), reinterpret_cast<const unsigned short*>(a.v),
-                           reinterpret_cast<unsigned short*>(a.o), (int)a.v_bstride, (int)a.o_bstride, a.pitch, a.T, a.heads, a.rows, a.scale);
-        return;
-    }
-    if (qt == 10) {   // 19 query tiles (T = 600) as two workgroups of ten waves: two K / V copies per head instead of three, one idle wave instead of five
-        dim3 grid((((a.T + 31) / 32) + 9) / 10, a.heads, batch);
-        hipLaunchKernelGGL(battn_kernel<10>, grid, dim3(640), lds_bytes, s, reinterpret_cast<const unsigned short*>(a.qk), reinterpret_cast<const unsigned short*>(a.v),
-                           reinterpret_cast<unsigned short*>(a.o), (int)a.v_bstride, (int)a.o_bstride, a.pitch, a.T, a.heads, a.rows, a.scale);
-        return;
-    }
     dim3 grid((((a.T + 31) / 32) + 7) / 8, a.heads, batch);
     hipLaunchKernelGGL(battn_kernel<8>, grid, dim3(512), lds_bytes, s, reinterpret_cast<const unsigned short*>(a.qk), reinterpret_cast<const unsigned short*>(a.v),
                        reinterpret_cast<unsigned short*>(a.o), (int)a.v_bstride, (int)a.o_bstride, a.pitch, a.T, a.heads, a.rows, a.scale);
@@ -640,9 +628,7 @@ static void configure_attn_modes() {
     configure_attn_one<2, 8, PM>(); configure_attn_one<2, 4, PM>(); configure_attn_one<2, 1, PM>(); configure_attn_one<2, 1, PM, 4>();
 }
 void configure_attn_kernels() {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&battn_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&battn_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&battn_kernel<10>), hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
     configure_attn_modes<0>(); configure_attn_modes<1>(); configure_attn_modes<2>();
     configure_attn_one<1, 8, 3>(); configure_attn_one<1, 4, 3>(); configure_attn_one<1, 1, 3, 4>();
     configure_attn2q_kernel();

@@ -98,7 +98,6 @@ struct said_ctx {
     STW st[NST];
     float* null_cond = nullptr;
     float* c2[NST] = {nullptr, nullptr, nullptr, nullptr};   // attn2 output of the unconditional half: to_out(to_v(null_cond_emb)) + bias, per block
-    bool cfg_share = true;   // exploit the guidance structure (shared prefix, constant unconditional cross-attention); SAID_NO_CFG_SHARE=1 disables
     float* freqs = nullptr;
     bool freqs_set = false;
 
@@ -118,14 +117,10 @@ struct said_ctx {
     bool band_chain_ok = false;  // the alignment band fits stchain's window tile (set_band)
     int kvt_S = -1;              // key count of the key-major copy KVT as run_kv last made it (-1: not made — the fused tail then does not run: ADVICE r5)
     int kvt_bf16 = 0;            // ... and its element type
-    bool st_chain_large = true;  // ... at large batches too, beside the token-major q / k / v GEMM (32 clips: 3.2 -> 2.4 ms per step; said_debug_option "st_chain_large")
-    long long st_chain_max_tiles = 1LL << 40;   // ... while the launch is at most this many workgroups (sample x 32-token tiles; said_debug_option "st_chain_max_tiles")
     int st_chain_bf16 = -1;      // bf16 mode, large batches: the same fused tail on bf16 operands instead of rgemm's five launches; 0: off; -1 / 1: stchain_kernel<true> (one token tile per
                                  // workgroup, two workgroups per CU; said_debug_option "st_chain_bf16").  (Round 5's two-tiles-per-workgroup variant measured slower — 96 vs 83 us,
                                  // profiles/r05p_stchain2_two_tiles_ab.txt — and was removed in round 6.)
-    bool st_chain_dbg = false;   // debug: the fused kernel also writes x1 / x2 to X1 / X2
     int attn_2q = -1;            // fp32 mode, pre-split K / V, four key slices: three query tiles per wave (attn2q_kernel) — -1: launches of >= 512 (sample, head, tile) triples, 0: never, 1: always (said_debug_option "attn_2q")
-    int attn_ks_force = 0;       // development: != 0 forces the self-attention workgroup shape (8 / 4 / 1: key-split waves; -4: four query tiles per workgroup) — said_debug_option "attn_ks"
     int st_chain_slices = -1;    // fp32 mode: -1 / 3: launches of at most CHAIN3_MAX_TILES (sample, token tile) pairs run THREE workgroups per tile, of at most CHAIN2_MAX_TILES two
                                  // (stchain.hip CU<>); 2: two wherever slicing is possible; 1: never
                                  // (said_debug_option "st_chain_slices")
@@ -147,16 +142,11 @@ struct said_ctx {
     float* axpby_coef = nullptr;
     long long* clk_dev = nullptr;  // [64 launches][8 waves][8 slots]
     bool clk_on = false;
-    int cur_b0 = 0;          // batch offset applied to every launch issued by run_unet (parallel graph branches)
-    hipStream_t cap_stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool use_branches = false;  // SAID_BRANCHES=1: capture the two halves of the UNet batch as parallel graph branches
     bool bf16_mode = false;  // said_set_precision(SAID_PREC_BF16): multiply in bf16 wherever the LDS-staged kernel is used
     int prec_mode = 0;       // the SAID_PREC_* mode asked for (said_set_precision)
     bool split_unsafe = false;   // a weight tensor lies outside the split-fp16 representation's range (scan_split_range): SAID_PREC_FP32 then runs as SAID_PREC_FP32_STRICT
     std::string split_note;      // ... which tensor and why (said_precision_note)
     int* status_dev = nullptr;   // [2] sticky numeric status of the last loop / forward call (said_numeric_status)
-    bool use_ugemm = true;   // SAID_NO_UGEMM=1 forces the generic kernel everywhere (A/B testing)
 
     // ---- bf16 audio encoder (tgemm.hip): bf16 weights [N][K] (convs: K = tap-major), token-major workspace ----
     void* bw_conv[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -167,32 +157,20 @@ struct said_ctx {
     float* pos_bias_pad = nullptr; // its bias, 16 zeros appended (the last group's 64-wide tile reads past 768)
     void* bXg = nullptr;          // per-group operand [clips][16][R][48] bf16
     size_t bXg_elems = 0;
-    bool pos_tgemm = true;        // SAID_NO_POSCONV_TGEMM=1: the grouped fp32 channel-major kernel also in bf16 mode
     struct BLayer { void *qkv, *out, *ff1, *ff2; };
     std::vector<BLayer> blayers;
     void *bA0 = nullptr, *bA1 = nullptr, *bX = nullptr, *bHb = nullptr, *bF = nullptr, *bO = nullptr;
     float *bH = nullptr, *bT = nullptr, *bPosT = nullptr;
     size_t b_conv_elems[2] = {0, 0}, b_tok = 0;
-    bool audio_bf16 = true;   // SAID_NO_AUDIO_BF16=1: the fp32 audio encoder also in bf16 mode
     // bf16-mode UNet at large batch: token-major bf16 GEMM operands (tgemm.hip) prepared from the channel-major fp32 activations
-    float* gn_coef = nullptr;   // [2 slots][maxBe][192][2] GroupNorm coefficients for prep_kernel
+    float* gn_coef = nullptr;   // [maxBe][192][2] GroupNorm coefficients of a block input (PrepArgs::coef_out / GemmCommon::gn_coef_out / gn_coef_kernel; room for two)
     void *uPA = nullptr, *uPB = nullptr, *uPL = nullptr, *uPH = nullptr, *uPX = nullptr;   // conv operand [Be][T+2][384], raw cat input
                                                                                             // [Be][T][384], LN'd [Be][T][192], GEGLU out [Be][T][768], raw x2 [Be][T][192]
     int tm_acts = -1;         // bf16 mode, large batches: token-major bf16 activations BETWEEN the UNet kernels, operand transforms inside the GEMMs (-1 / 1: on; 0: the
                               // channel-major schedule with preparation kernels — said_debug_option "tm_acts").  The fp32 twin of this schedule (round 3: 4.78 vs 4.41 ms per
                               // step at 32 clips) was removed in round 6 together with xgemm_kernel's fp32 instantiations.
-    bool mt_mid = true;       // multi-tile workgroups for mid-size launches too (said_debug_option "mt_mid")
-    int mt_wgs = 0;           // > 0: multi-tile workgroups from this many workgroups per token tile on (said_debug_option "mt_wgs"; default 1024)
     int tgemm_direct = -1;    // audio encoder (bf16): the projections on tgemm256d_kernel (256 x 256 tile, operand tiles loaded straight into LDS; -1 / 1: on, 0: tgemm_kernel<128> — said_debug_option "tgemm_direct")
-    int tgemm_sb = 1;         // audio encoder (bf16): the single-LDS-buffer 128 x 128 GEMM variant, three workgroups per CU (said_debug_option "tgemm_sb"; 0: double buffer, two per CU)
-    int unet_nb = 0;          // > 0: forces pick_unet's column tiles per workgroup (said_debug_option "unet_nb")
-    bool unet_nb_model = true; // pick_unet by the busiest-CU model (0: round 2's rule; said_debug_option "unet_nb_model")
-    bool f32_out1_tm = true;  // fp32 large batch: attn1.to_out on the token-major fp32 GEMM (said_debug_option "f32_out1_tm")
-    bool hybrid = true;       // bf16 mode at large batch: SpatialTransformers from the attention output on use round 3's token-major kernels
-    int xgemm_dbg = 0;
     bool xclk_on = false;
-    int battn = -1;           // round 4: bf16-operand self-attention with a head's K / V resident in LDS (attn.hip: battn_kernel) behind rgemm's q/k/v;
-                              // 0: attn_kernel on fp32 operands (said_debug_option "battn")
     int attn_split = -1;      // fp32 mode: both attention products on split-fp16 operands (attn.hip: PM == 2; x = h + 2^-11 l: 22-bit significands, fp32 accumulation,
                               // as close to a float64 evaluation as the fp32 MFMAs: tests/test_gpu_round4.py).  Default (-1) and 1: ON since round 5; 0: v_mfma_f32_32x32x2_f32
                               // on the fp32 operands (said_debug_option "attn_split").  Round 4 shipped it opt-in because runs beside other streams were not bit-stable;
@@ -206,22 +184,16 @@ struct said_ctx {
     int out_split = -1;       // out_sched_kernel's convolution on split-fp16 operands (-1 / 1: on; 0: fp32 matrix instructions — said_debug_option "out_split")
     int kconv = -1;           // fp32 mode, small batch: the K-long ResBlock convolutions of the up path as straight-line two- / three-block waves (gemm_lds.hip kconv_body; -1 / 1: on,
                               // 0: ugemm_body's block loop — said_debug_option "kconv"; bit-identical)
-    long long kconv_max_tiles = 4096;   // launches of at most this many (sample, token tile) pairs run the K-long convolutions as NB = 1 kconv_body workgroups when the chosen NB has no split shape
     int chain_coef = -1;      // fp32 small batch: stchain_kernel takes the block input's GroupNorm coefficients from the q/k/v GEMM (-1 / 1: on; 0: finalises them itself — said_debug_option "chain_coef")
     int ugemm_split = -1;     // fp32 mode: the small-batch channel-major GEMMs (ugemm_kernel) on split-fp16 operands too (gemm_lds.hip: SP; weights pre-split on the host:
                               // Seg::ws).  Default (-1) and 1: ON; 0: fp32 MFMAs (said_debug_option "ugemm_split")
     int pw_split = 0;         // make_pw: also build the split-fp16 packing (1: per-block layout, 2: flat) — set around the UNet weights only
-    int rgemm = -1;           // round 4: register-stationary, wave-specialised persistent GEMMs (rgemm.hip) wherever launch_rgemm serves the shape
-                              // (bf16 mode: 192-wide GEMMs with K <= 576, q/k/v); 0: off (said_debug_option "rgemm")
     long long n_rgemm = 0;
     long long n_stchain = 0;  // launches issued through stchain_kernel (said_debug_get)
     long long n_xgemm = 0;    // launches issued through round 3's xgemm_kernel (said_debug_get; n_rgemm: through rgemm_kernel)
-    int xgemm_ntw = 0;        // test / measurement: column tiles per workgroup of the resident-source GEMMs (0: launch_xgemm decides)
     void *tX1 = nullptr, *tX2 = nullptr, *tO = nullptr, *tF = nullptr;   // token-major x1, x2, attention output [.][192], GEGLU product [.][768]
-    bool unet_tgemm = true;   // SAID_NO_UNET_TGEMM=1 keeps the channel-major kernels in bf16 mode at every batch size
-    bool unet_fgemm = true;   // SAID_NO_UNET_FGEMM=1: the same for the fp32 mode's token-major path (fgemm_kernel)
     // tokens per launch from which the token-major GEMM path is taken (measured crossovers, scripts/gpu_r2_w.sh: bf16 between 4800
-    // and 6000 tokens, fp32 between 9600 and 10800); SAID_UNET_TGEMM_MIN overrides both
+    // and 6000 tokens, fp32 between 9600 and 10800; said_debug_option "unet_tgemm_min_tokens" overrides both)
     // (bf16: 3000 since round 4 — with the persistent kernels the crossover sits between 2400 rows (2 clips x 600 frames under guidance: 21.9 vs 22.6 ms per
     //  50 steps) and 3600 (3 clips: 30.3 vs 22.7 ms); rounds 2-3: 5800)
     long long unet_tgemm_min_tokens = 3000, unet_fgemm_min_tokens = 10000;
@@ -285,7 +257,12 @@ void scan_split_range(said_ctx* ctx, const std::string& name, const float* w, si
     }
 }
 
-static bool trace_on() { static int v = -1; if (v < 0) v = dev_env("SAID_TRACE") ? 1 : 0; return v == 1; }
+// -DSAID_TRACE (SAID_EXTRA_DEFS): every UNet launch is reported on stderr and synchronised
+#ifdef SAID_TRACE
+constexpr bool trace_on() { return true; }
+#else
+constexpr bool trace_on() { return false; }
+#endif
 
 #define TRACE(msg) do { if (trace_on()) { fprintf(stderr, "[said] %s:%d %s\n", __FILE__, __LINE__, msg); fflush(stderr); } } while (0)
 
@@ -300,19 +277,11 @@ static bool trace_on() { static int v = -1; if (v < 0) v = dev_env("SAID_TRACE")
 // side (the clip groups' loops).
 static int ensure_cap_streams(said_ctx* ctx) {
     if (!ctx->cap_stream) HIPCHK(hipStreamCreateWithFlags(&ctx->cap_stream, hipStreamNonBlocking));
-    if (ctx->use_branches) {
-        if (!ctx->cap_stream2) HIPCHK(hipStreamCreateWithFlags(&ctx->cap_stream2, hipStreamNonBlocking));
-        if (!ctx->ev_fork) HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-        if (!ctx->ev_join) HIPCHK(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-    }
     return 0;
 }
 static void release_cap_streams(said_ctx* ctx) {
     if (ctx->cap_stream) (void)hipStreamDestroy(ctx->cap_stream);
-    if (ctx->cap_stream2) (void)hipStreamDestroy(ctx->cap_stream2);
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
-    ctx->cap_stream = ctx->cap_stream2 = nullptr; ctx->ev_fork = ctx->ev_join = nullptr;
+    ctx->cap_stream = nullptr;
 }
 
 // a schedule function's kernel refused its shape (nothing was launched for it): report instead of continuing
@@ -565,8 +534,6 @@ int make_pw(said_ctx* ctx, PW* pw, const std::string& wname, const std::string& 
 }
 
 struct LaunchCfg { int NB, KS; };
-// experiment knob: SAID_BIG=cgemm restores the generic kernel's large-batch tile shapes
-static bool big_cgemm() { static const bool v = dev_env("SAID_BIG") && !strcmp(dev_env("SAID_BIG"), "cgemm"); return v; }
 LaunchCfg pick_cfg(long long t_tiles_total, int ntiles, bool allow6 = true) {
     // small problems: maximise workgroups (split K over 8 waves, one tile each);
     // large problems: amortise the operand transform over more tiles per workgroup.
@@ -584,10 +551,8 @@ LaunchCfg pick_cfg(long long t_tiles_total, int ntiles, bool allow6 = true) {
 // time is that of the busiest CU: ceil(workgroups / 256) workgroups of (F + NB) units each, F = 0.45 the per-workgroup fixed part
 // (GroupNorm finalisation, operand tile; fitted on T = 1800: NB = 1 14.8 us, NB = 2 25.0 us at 342 workgroups each).  Round 2's rule
 // (NB = 2 from 64 tiles) put 342 workgroups on 256 CUs at T = 1800: two rounds of three units where NB = 3 is one round of 3.45.
-LaunchCfg pick_unet(const said_ctx* c, long long t_tiles_total) {
-    if (big_cgemm()) return pick_cfg(t_tiles_total, 6);
-    if (c->unet_nb > 0) return LaunchCfg{c->unet_nb, 8};
-    if (!c->unet_nb_model || t_tiles_total * 6 > 1024) return t_tiles_total * 3 >= 192 ? LaunchCfg{2, 8} : LaunchCfg{1, 8};   // (large launches: multi-tile NB = 2 shapes)
+LaunchCfg pick_unet(long long t_tiles_total) {
+    if (t_tiles_total * 6 > 1024) return t_tiles_total * 3 >= 192 ? LaunchCfg{2, 8} : LaunchCfg{1, 8};   // (large launches: multi-tile NB = 2 shapes)
     int best = 1;
     double cost = 1e30;
     for (int nb = 1; nb <= 3; ++nb) {
@@ -628,7 +593,6 @@ struct UGeo {
     long long sts;     // batch stride of its stats
     const int* step_ptr;
     int emb_b_stride;
-    int b0;            // first sample of this launch range (Be = number of samples in the range)
     int* step_inc;     // if set: the first kernel of the schedule increments this counter
     const OutSchedArgs* out_sched;   // if set: the `out` conv is fused with the scheduler update (loop only)
     int Bc;            // > 0: classifier-free guidance over Bc clips — samples [0, Bc) are the unconditional half (context =
@@ -650,22 +614,20 @@ inline bool dbg_go_peek(const said_ctx* c) { return c->dbg_only >= 0 ? c->dbg_co
 // Multi-tile workgroups (gemm_lds.hip, MT): once a launch would have several thousand workgroups, each workgroup walks
 // over `tt` consecutive token tiles instead, keeping its weights in registers; tt is chosen so that ~4 workgroups per
 // CU remain.  Returns 1 when the launch is not eligible.
-static int pick_tt(said_ctx* c, const GemmArgs& a, int epi, int batch, int& NB, int KS, bool bf) {
-    static const bool mt_off = dev_env("SAID_NO_MT") != nullptr;
-    if (mt_off || !c->use_ugemm || a.step_inc) return 1;
+constexpr long long KCONV_MAX_TILES = 4096;   // do_gemm: launches of at most this many (sample, token tile) pairs may run the K-long convolutions as NB = 1 kconv_body workgroups
+constexpr long long MT_WGS_PER_TILE = 1024;   // workgroups per extra token tile of a large launch
+constexpr long long MT_MID_WGS = 228;         // ... of a mid-size one
+static int pick_tt(const GemmArgs& a, int epi, int batch, int NB, int KS, bool bf) {
+    if (a.step_inc) return 1;
     if (epi == EPI_GEGLU || epi == EPI_BAND) return 1;   // measured slower multi-tile (B=32: GEGLU NB=2 x tt vs NB=4, band)
-    int nb = NB;
     const long long ntt = (a.T + 31) / 32;
-    const long long wgs = ntt * (a.ntiles_per_group / nb) * batch;
-    static const long long wgs_env = dev_env("SAID_MT_WGS") ? std::max(64, atoi(dev_env("SAID_MT_WGS"))) : 1024;   // experiment knob
-    const long long wgs_per_tile = c->mt_wgs > 0 ? c->mt_wgs : wgs_env;
-    long long want = wgs / wgs_per_tile;
+    const long long wgs = ntt * (a.ntiles_per_group / NB) * batch;
+    long long want = wgs / MT_WGS_PER_TILE;
     // mid-size launches (one to four rounds of one workgroup per CU, e.g. q/k/v at T = 1800: 684 workgroups): as many token tiles per
     // workgroup as there would be rounds, so that ONE round of <= 256 workgroups remains (configs[4]: 16.87k -> 17.34k frames/s)
-    if (want <= 1 && c->mt_mid && c->mt_wgs <= 0) want = wgs / 228;
+    if (want <= 1) want = wgs / MT_MID_WGS;
     int tt = (int)std::min<long long>(std::min<long long>(8, want), ntt);
-    if (tt <= 1 || !ugemm_supports(a, epi, nb, KS, bf, tt)) return 1;
-    NB = nb;
+    if (tt <= 1 || !ugemm_supports(a, epi, NB, KS, bf, tt)) return 1;
     return tt;
 }
 
@@ -673,20 +635,19 @@ static int pick_tt(said_ctx* c, const GemmArgs& a, int epi, int batch, int& NB, 
 bool do_gemm(said_ctx* c, const GemmArgs& a, int epi, int batch, int NB, int KS, hipStream_t s) {
     bool on_ugemm = false;
     GemmArgs a2 = a;
-    a2.b0 = c->cur_b0;
     a2.kconv_off = (c->kconv == 0) ? 1 : 0;
     const bool bf = c->bf16_mode;
-    if (NB == 3 && epi == EPI_STORE && c->use_ugemm && !ugemm_supports(a2, epi, 3, KS, bf)) NB = 2;   // (the two-segment fp32 shapes spill at NB = 3: not built)
+    if (NB == 3 && epi == EPI_STORE && !ugemm_supports(a2, epi, 3, KS, bf)) NB = 2;   // (the two-segment fp32 shapes spill at NB = 3: not built)
     // K-long up-path convolutions (two / three K segments): the split-fp16 shapes exist for one column tile per workgroup only (kconv_body; with two the second accumulator
     // set spills).  Where that takes at most 1.5 x the rounds of the chosen shape on the fp32 matrix instructions it wins (a round of NB = 1 split ~11 us, of NB = 2 fp32 ~21 us:
     // configs[4] 24.3k -> 25.5k frames/s, 3 clips +6 %; 76 tiles — 2 rounds against 1 — loses 2 %: profiles/r06g_kconv_ab.txt)
-    if (!bf && epi == EPI_STORE && NB > 1 && a2.nseg >= 2 && c->kconv != 0 && sp_on(c, c->ugemm_split) && c->use_ugemm && !a2.step_inc && !c->clk_on && (!c->cur_concurrent || c->kconv == 2)) {   // (concurrent clip groups share the CUs: fewer workgroups win there — 5 clips -1.9 %; "kconv" = 2: there too)
+    if (!bf && epi == EPI_STORE && NB > 1 && a2.nseg >= 2 && c->kconv != 0 && sp_on(c, c->ugemm_split) && !a2.step_inc && !c->clk_on && (!c->cur_concurrent || c->kconv == 2)) {   // (concurrent clip groups share the CUs: fewer workgroups win there — 5 clips -1.9 %; "kconv" = 2: there too)
         const long long tiles = (long long)batch * ((a2.T + 31) / 32), r1 = (tiles * 6 + 255) / 256, rn = (tiles * (6 / NB) + 255) / 256;
-        if (tiles <= c->kconv_max_tiles && 2 * r1 <= 3 * rn && !ugemm_supports(a2, epi, NB, KS, 2) && ugemm_supports(a2, epi, 1, 8, 2)) { NB = 1; KS = 8; }
+        if (tiles <= KCONV_MAX_TILES && 2 * r1 <= 3 * rn && !ugemm_supports(a2, epi, NB, KS, 2) && ugemm_supports(a2, epi, 1, 8, 2)) { NB = 1; KS = 8; }
     }
-    const int tt = pick_tt(c, a2, epi, batch, NB, KS, bf);
+    const int tt = pick_tt(a2, epi, batch, NB, KS, bf);
     // fp32 mode, single-tile workgroups: split-fp16 products wherever the shape is built for them (gemm_lds.hip SP) and the weights carry the packing
-    const bool sp = !bf && tt <= 1 && sp_on(c, c->ugemm_split) && c->use_ugemm && !a2.step_inc && ugemm_supports(a2, epi, NB, KS, 2);
+    const bool sp = !bf && tt <= 1 && sp_on(c, c->ugemm_split) && !a2.step_inc && ugemm_supports(a2, epi, NB, KS, 2);
     if (c->log_on) {
         double w = 0, in = 0, fl = 0;
         const double nout = (double)a.groups * a.N * (epi == EPI_GEGLU ? 2 : 1);
@@ -699,12 +660,12 @@ bool do_gemm(said_ctx* c, const GemmArgs& a, int epi, int batch, int NB, int KS,
         double out = (double)batch * a.groups * a.N * a.T * 4.0;
         if (a.res_kind != RES_NONE) in += out;
         if (epi == EPI_BAND) in += 2.0 * batch * a.N * a.T * 4.0;  // this block's K and V rows
-        c->stage_log.push_back({(c->use_ugemm && (tt > 1 || ugemm_supports(a, epi, NB, KS, bf) || ugemm_supports(a, epi, NB, KS))) ? 2 : 0, epi, NB, KS, w + in + out, fl});
+        c->stage_log.push_back({((tt > 1 || ugemm_supports(a, epi, NB, KS, bf) || ugemm_supports(a, epi, NB, KS))) ? 2 : 0, epi, NB, KS, w + in + out, fl});
     }
     if (c->clk_on && c->dbg_count < 64) a2.clk = c->clk_dev + (long long)c->dbg_count * 128;
     if (dbg_go(c)) {
         if (trace_on()) { fprintf(stderr, "[said] gemm #%d epi=%d NB=%d KS=%d T=%d N=%d batch=%d tt=%d\n", c->dbg_count - 1, epi, NB, KS, a.T, a.N, batch, tt); fflush(stderr); }
-        const bool ug = c->use_ugemm && !a2.step_inc;
+        const bool ug = !a2.step_inc;
         on_ugemm = true;
         if (tt > 1) launch_ugemm(a2, epi, batch, NB, KS, s, bf, tt);
         else if (sp) launch_ugemm(a2, epi, batch, NB, KS, s, 2);
@@ -725,9 +686,7 @@ void do_attn(said_ctx* c, const AttnArgs& a, int batch, int head_dim, int KS, hi
     }
     if (dbg_go(c)) {
         if (trace_on()) { fprintf(stderr, "[said] attn #%d D=%d KS=%d T=%d batch=%d\n", c->dbg_count - 1, head_dim, KS, a.T, batch); fflush(stderr); }
-        AttnArgs a2 = a;
-        a2.b0 = c->cur_b0;
-        launch_attn(a2, batch, head_dim, KS, s, c->bf16_mode ? 1 : (sp_on(c, c->attn_split) ? (presplit ? 3 : 2) : 0));
+        launch_attn(a, batch, head_dim, KS, s, c->bf16_mode ? 1 : (sp_on(c, c->attn_split) ? (presplit ? 3 : 2) : 0));
         if (trace_on()) { hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[said]   -> %s\n", hipGetErrorString(e)); fflush(stderr); }
     }
 }
@@ -740,7 +699,7 @@ bool use_tg(said_ctx* c, const UGeo& g, int nsamples) {
     // (the token-major kernels address their operands with 32-bit element offsets: beyond that the channel-major kernels run)
     const long long widest = ((long long)nsamples * rup(g.T + 2, 32) + 2) * FFI;
     if (c->band_wmax > 8) return false;   // wide alignment windows: the channel-major schedule (its generic band kernel)
-    return (c->bf16_mode ? c->unet_tgemm : c->unet_fgemm) && !c->clk_on && widest < 0x7fffffffLL &&
+    return !c->clk_on && widest < 0x7fffffffLL &&
            (long long)nsamples * g.T >= (c->bf16_mode ? c->unet_tgemm_min_tokens : (c->cur_concurrent ? std::min(c->unet_fgemm_min_tokens, c->unet_fgemm_min_concurrent) : c->unet_fgemm_min_tokens));
 }
 // weight of the token-major GEMM in the context's precision mode
@@ -780,19 +739,9 @@ PrepArgs mkprep(const UGeo& g, const float* x, int mode, void* dst, long long ds
     p.dst = dst; p.dst_bs = dst_bs; p.ldd = ldd; p.coff = coff;
     return p;
 }
-// GroupNorm coefficients of the operand, once per tensor (slot: one of two coefficient tables, so that the two sources of a
-// concatenated input can be prepared back to back)
-void prep_gn(said_ctx* c, PrepArgs& p, const UGeo& g, const float* part, int cpg, float eps, const float* gamma, const float* beta, int nb,
-             int slot, hipStream_t s) {
-    static const bool separate = dev_env("SAID_PREP_GN_SEPARATE") != nullptr;   // A/B: coefficients by their own launch (gn_coef_kernel)
-    if (!separate) {   // finalised inside the preparation kernel from the producer's partials
-        p.part = part; p.part_bs = g.sts; p.gn_cpg = cpg; p.gn_nparts = g.np; p.gn_eps = eps; p.gn_gamma = gamma; p.gn_beta = beta;
-        return;
-    }
-    float* co = c->gn_coef + (size_t)slot * c->maxBe * 2 * MC;
-    if (c->log_on) c->stage_log.push_back({5, -2, 0, 0, (double)nb * MC * g.np * 8.0, 0.0});
-    if (dbg_go(c)) launch_gn_coef(part, g.sts, cpg, g.np, g.T, eps, gamma, beta, co, 2 * MC, nb, s);
-    p.coef = co; p.coef_bs = 2 * MC;
+// GroupNorm of the operand: its coefficients are finalised inside the preparation kernel from the producer's partials
+void prep_gn(PrepArgs& p, const UGeo& g, const float* part, int cpg, float eps, const float* gamma, const float* beta) {
+    p.part = part; p.part_bs = g.sts; p.gn_cpg = cpg; p.gn_nparts = g.np; p.gn_eps = eps; p.gn_gamma = gamma; p.gn_beta = beta;
 }
 TGemmArgs mktg(const UGeo& g, const void* a, int lda, const void* w, int N, int K) {
     TGemmArgs t;
@@ -809,19 +758,17 @@ inline int tm_seg(const UGeo& g) { return rup(g.T, 64); }   // sample pitch in t
 // (32-bit element offsets inside the kernels: the widest token-major tensor here is the GEGLU product, sample pitch tm_seg — up to 4/3 of
 // the rup(T + 2, 32) pitch use_tg's guard is written for)
 inline bool use_tm(said_ctx* c, const UGeo& g) {
-    return c->bf16_mode && c->tm_acts != 0 && use_tg(c, g, g.Be) && g.b0 == 0 && ((long long)g.Be * tm_seg(g) + 2) * FFI < 0x7fffffffLL;
+    return c->bf16_mode && c->tm_acts != 0 && use_tg(c, g, g.Be) && ((long long)g.Be * tm_seg(g) + 2) * FFI < 0x7fffffffLL;
 }
 // `rows` tokens further into a token-major tensor of row width `ld` (element size by precision mode)
 inline void* tm_at(const said_ctx* c, void* base, long long rows, int ld) { return static_cast<char*>(base) + rows * ld * (c->bf16_mode ? 2 : 4); }
 void do_xgemm(said_ctx* c, const TGemmArgs& a, int batch, hipStream_t s) {
     TGemmArgs a2 = a;
     a2.f32 = c->bf16_mode ? 0 : 1;
-    if (c->xgemm_ntw > 0 && a2.ra[0]) a2.ntw = c->xgemm_ntw;
-    a2.dbg = c->xgemm_dbg;
     if (c->xclk_on && c->dbg_count < 64) a2.clk = c->clk_dev + (long long)c->dbg_count * 128;
     if (a2.f32 && a2.yb) { a2.yf = reinterpret_cast<float*>(a2.yb); a2.yb = nullptr; }
     // kernel family: 7 = rgemm_kernel (round 4: register-stationary weights, helper waves), 6 = round 3's xgemm_kernel
-    const int fam = (c->rgemm != 0 && !a2.f32 && rgemm_supports(a2, batch)) ? 7 : 6;
+    const int fam = (!a2.f32 && rgemm_supports(a2, batch)) ? 7 : 6;
     if (c->log_on) {
         const double eb = c->bf16_mode ? 2.0 : 4.0;
         const double out_n = a.geglu ? a.N / 2 : a.N;
@@ -865,7 +812,7 @@ void run_resblock_tm(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, c
     // rounding of a quantity the next kernel rounds anyway): conv1 = [source 0 -> P] + [source 1 + bias + emb + P], and the 1x1 skip over
     // the raw input becomes the residual of conv2.  The partial / skip tensor lives in tX1 (idle until the block's SpatialTransformer).
     bool split = false;
-    if (in1 && c->rgemm != 0 && c->bf16_mode && rw.has_skip) {
+    if (in1 && c->bf16_mode && rw.has_skip) {
         TGemmArgs t = mkx(g, rw.t_conv1, MC, 3 * MC);
         t.ra[0] = in0.t; t.rmode = 1; t.rtaps = 3; t.gn_part[0] = in0.st; t.gn_cpg = rw.cin / 32; t.gn_eps = 1e-5f; t.gn_gamma = rw.g1; t.gn_beta = rw.b1;
         t.y_tm = c->tX1; t.w_ld = 3 * rw.cin; t.w_seg = rw.cin;
@@ -956,7 +903,7 @@ void run_transformer_tm(said_ctx* c, const UGeo& g, const STW& sw, int blk, cons
         AttnArgs pa;
         pa.qk = c->QK; pa.v = c->VT; pa.o = static_cast<float*>(c->tO); pa.v_bstride = (long long)MC * g.Tp; pa.o_bstride = seg;
         pa.pitch = g.Tp; pa.T = g.T; pa.heads = HEADS; pa.rows = vt_rows; pa.b0 = 0; pa.scale = 0.17677669529663687f;
-        t.qkv_bf16 = (c->battn != 0 && c->bf16_mode && c->rgemm != 0 && battn_supports(pa, HD)) ? 1 : 0;
+        t.qkv_bf16 = (c->bf16_mode && battn_supports(pa, HD)) ? 1 : 0;
         if (t.qkv_bf16 && !rgemm_supports(t, n1)) t.qkv_bf16 = 0;
         battn = t.qkv_bf16 != 0;
         t.q_scale = 0.17677669529663687f * 1.4426950408889634f;   // dim_head ** -0.5 (attention.py:101) x log2(e)
@@ -970,13 +917,13 @@ void run_transformer_tm(said_ctx* c, const UGeo& g, const STW& sw, int blk, cons
         a.scale = 0.17677669529663687f;
         if (battn) {
             if (c->log_on) { const double e = (double)n1 * HEADS * HD * g.T; c->stage_log.push_back({9, -1, 1, 1, 4.0 * e * 2.0, 4.0 * e * g.T}); }
-            if (dbg_go(c)) launch_battn(a, n1, s, c->battn == 4 ? 4 : (c->battn == 10 ? 10 : 8));
+            if (dbg_go(c)) launch_battn(a, n1, s);
         } else {
             do_attn(c, a, n1, HD, -4, s);
         }
     }
     // round 5: everything behind the attention as ONE launch on bf16 operands (stchain_kernel<true>; the token-major bf16 tensors are its operands as they are)
-    if (c->bf16_mode && c->st_chain_bf16 != 0 && !last && sw.chain_wb && sw.chain_vec && c->band_chain_ok && c->kvt_S == g.S && c->kvt_bf16 && c->cur_b0 == 0 && g.S == c->band_S && g.T == c->band_T &&
+    if (c->bf16_mode && c->st_chain_bf16 != 0 && !last && sw.chain_wb && sw.chain_vec && c->band_chain_ok && c->kvt_S == g.S && c->kvt_bf16 && g.S == c->band_S && g.T == c->band_T &&
         (long long)g.Be * seg * MC < 0x7fffffffLL) {
         ChainArgs ca;
         memset(&ca, 0, sizeof ca);
@@ -1036,7 +983,7 @@ void run_transformer_tm(said_ctx* c, const UGeo& g, const STW& sw, int blk, cons
         do_xgemm(c, t, g.Be, s);
     }
     bool split = false;
-    if (!last && c->rgemm != 0 && c->bf16_mode) {   // round 4: as two rgemm launches over column ranges of the folded weight (see run_resblock_tm)
+    if (!last && c->bf16_mode) {   // round 4: as two rgemm launches over column ranges of the folded weight (see run_resblock_tm)
         TGemmArgs t = mkx(g, sw.t_ffproj, MC, FFI);
         t.sa[0] = c->tF; t.sld[0] = FFI; t.sk[0] = FFI; t.w_ld = FFI + MC;
         t.res_tm = in.t; t.y_tm = c->tX1;
@@ -1072,7 +1019,7 @@ void run_transformer_tm(said_ctx* c, const UGeo& g, const STW& sw, int blk, cons
     }
 }
 
-// ---- round 3, bf16 mode at large batch (default): the HYBRID SpatialTransformer.  The ResBlocks and q/k/v keep round 2's kernels
+// ---- round 3, bf16 mode at large batch when the token-major activations are off (tm_acts = 0, or beyond their 32-bit offsets): the HYBRID SpatialTransformer.  The ResBlocks and q/k/v keep round 2's kernels
 // (channel-major fp32 between them, prep_kernel + token-major GEMM), everything from the attention output on runs on round 3's
 // token-major-activation kernels, where they are faster in situ: attention writes token-major bf16, attn1.to_out / band / attn2.to_out /
 // GEGLU / folded proj_out are xgemm launches (no second preparation kernel: GEGLU applies norm3 itself), and the folded proj_out writes
@@ -1087,7 +1034,7 @@ void run_transformer_hybrid(said_ctx* c, const UGeo& g, const STW& sw, int blk, 
     const int vt_rows = rup(g.T, 32);
     {   // q, k, v on round 2's token-major GEMM; the preparation kernel also leaves the raw input token-major (in.t)
         PrepArgs p = mkprep(g, in.p, 1, c->uPL, (long long)tg_rows(g) * MC, MC, 0);
-        prep_gn(c, p, g, in.st, 6, 1e-6f, sw.gn_g, sw.gn_b, g.Be, 0, s);
+        prep_gn(p, g, in.st, 6, 1e-6f, sw.gn_g, sw.gn_b);
         p.ln_gamma = sw.l1g; p.ln_beta = sw.l1b;
         p.dst2 = in.t; p.dst2_bs = seg * MC; p.ldd2 = MC; p.coff2 = 0;
         do_prep(c, p, g.Be, s);   // (all samples: the second half's rows are the residual of proj_out)
@@ -1165,13 +1112,13 @@ void run_resblock(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, cons
         {   // in_layers: GN -> SiLU -> conv3 + emb term   (openaimodel.py:205-225)
             PrepArgs p = mkprep(g, in0.p, 0, c->uPA, T2 * rw.cin, rw.cin, 0);
             p.pack = pk;
-            prep_gn(c, p, g, in0.st, cpg, 1e-5f, rw.g1, rw.b1, nb, 0, s);
+            prep_gn(p, g, in0.st, cpg, 1e-5f, rw.g1, rw.b1);
             if (rw.has_skip) { p.dst2 = c->uPB; p.dst2_bs = T2 * 2 * MC; p.ldd2 = 2 * MC; p.coff2 = 0; }   // raw copy for the 1x1 skip conv
             do_prep(c, p, nb, s);
             if (in1) {
                 PrepArgs q = mkprep(g, in1->p, 0, c->uPA, T2 * rw.cin, rw.cin, MC);
                 q.pack = pk;
-                prep_gn(c, q, g, in1->st, cpg, 1e-5f, rw.g1 + MC, rw.b1 + MC, nb, 1, s);
+                prep_gn(q, g, in1->st, cpg, 1e-5f, rw.g1 + MC, rw.b1 + MC);
                 if (rw.has_skip) { q.dst2 = c->uPB; q.dst2_bs = T2 * 2 * MC; q.ldd2 = 2 * MC; q.coff2 = MC; }
                 do_prep(c, q, nb, s);
             }
@@ -1185,7 +1132,7 @@ void run_resblock(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, cons
         {   // out_layers: GN -> SiLU -> conv3 ; + skip(x)   (openaimodel.py:226-227)
             PrepArgs p = mkprep(g, c->M.p, 0, c->uPA, T2 * MC, MC, 0);
             p.pack = pk;
-            prep_gn(c, p, g, c->M.st, 6, 1e-5f, rw.g2, rw.b2, nb, 0, s);
+            prep_gn(p, g, c->M.st, 6, 1e-5f, rw.g2, rw.b2);
             do_prep(c, p, nb, s);
             TGemmArgs t = mktg(g, c->uPA, MC, pk ? rw.tp_conv2 : tw(c, rw.t_conv2, rw.tf_conv2), MC, 3 * MC);
             t.f32_packed = pk;
@@ -1216,7 +1163,7 @@ void run_resblock(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, cons
         a.emb = c->EO + (long long)rb_index * MC * c->maxNp; a.emb_pitch = c->maxNp; a.step_ptr = g.step_ptr; a.emb_b_stride = g.emb_b_stride;
         a.y = c->M.p; a.y_bstride = g.hs; a.y_pitch = g.Tp;
         a.stats_out = c->M.st; a.stats_bstride = g.sts;
-        const LaunchCfg lc = pick_unet(c, tt);
+        const LaunchCfg lc = pick_unet(tt);
         do_gemm(c, a, EPI_STORE, nb, lc.NB, lc.KS, s);
     }
     {   // out_layers: GN -> SiLU -> conv3 ; + skip(x)   (openaimodel.py:226-227)
@@ -1236,7 +1183,7 @@ void run_resblock(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, cons
         a.y = out.p; a.y_bstride = g.hs; a.y_pitch = g.Tp;
         a.stats_out = out.st; a.stats_bstride = g.sts;
         if (shared) { a.y2 = out.p + (long long)g.Bc * g.hs; a.y2_bstride = g.hs; a.y2_add = nullptr; }
-        const LaunchCfg lc = pick_unet(c, tt);
+        const LaunchCfg lc = pick_unet(tt);
         do_gemm(c, a, EPI_STORE, nb, lc.NB, lc.KS, s);
     }
 }
@@ -1255,26 +1202,24 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
     const int kv_off = g.Bc > 0 ? g.Bc : 0;
     const long long tt1 = (long long)n1 * ((g.T + 31) / 32), tt2 = (long long)n2 * ((g.T + 31) / 32);
     const long long tt = (long long)g.Be * ((g.T + 31) / 32);
-    const bool big = big_cgemm() && tt * 6 > 1536;
-    const bool big_qkv = tt1 * 6 > 1536 && dev_env("SAID_NO_MT") && !c->bf16_mode;   // without multi-tile workgroups the generic NB=6 shape wins in fp32
     const int vt_rows = rup(g.T, 32);
     const long long obs = 2LL * MC * g.Tp;   // batch stride of O (shared with QK so attention uses one stride)
     const bool tg = use_tg(c, g, n1);
-    if (c->hybrid && c->bf16_mode && tg && use_tg(c, g, g.Be) && g.b0 == 0) { run_transformer_hybrid(c, g, sw, blk, in, out, s, shared); return; }
+    if (c->bf16_mode && tg && use_tg(c, g, g.Be)) { run_transformer_hybrid(c, g, sw, blk, in, out, s, shared); return; }
     // fp32 mode: attn1.to_out on the token-major fp32 GEMM too (the attention kernel writes its operand token-major into the free q/k/v
     // operand buffer; the GroupNorm'ed residual uses the coefficients the q/k/v preparation finalised): 59 -> ~30 us per launch at Be = 64
-    // fp32 mode: everything behind the self-attention as ONE launch (stchain.hip) — at small batches beside the channel-major GEMMs, at large ones (st_chain_large)
+    // fp32 mode: everything behind the self-attention as ONE launch (stchain.hip) — at small batches beside the channel-major GEMMs, at large ones
     // beside the token-major GEMMs' q / k / v (the attention kernel then writes channel-major, as the small-batch schedule has it)
-    const bool chain = !c->bf16_mode && sp_on(c, c->st_chain) && c->use_ugemm && sw.chain_w && sw.chain_vec && c->band_chain_ok && c->kvt_S == g.S && !c->kvt_bf16 && c->cur_b0 == 0 && !c->use_branches &&
-                       ((!tg && !use_tg(c, g, g.Be)) || c->st_chain_large) && tt <= c->st_chain_max_tiles && g.S == c->band_S && g.T == c->band_T;
-    const bool out1_tm = tg && !chain && !c->bf16_mode && c->f32_out1_tm && tt1 * HEADS >= 2048 && sw.tf_out1;
+    const bool chain = !c->bf16_mode && sp_on(c, c->st_chain) && sw.chain_w && sw.chain_vec && c->band_chain_ok && c->kvt_S == g.S && !c->kvt_bf16 &&
+                       g.S == c->band_S && g.T == c->band_T;
+    const bool out1_tm = tg && !chain && !c->bf16_mode && tt1 * HEADS >= 2048 && sw.tf_out1;
     bool presplit = false;   // k and v stored as packed split-fp16 pairs for attn_kernel<PM = 3> (see below)
     bool coef_ready = false; // the q/k/v GEMM left the block input's GroupNorm coefficients in gn_coef (small-batch ugemm_kernel only)
     if (tg) {   // q, k, v on the bf16 token-major GEMM: operand = LayerNorm(GroupNorm(x)) prepared once
         const int pk = (!c->bf16_mode && sp_on(c, c->gemm_split) && c->gemm_presplit != 0 && sw.tp_qkv) ? 1 : 0;   // operands arrive split (see run_resblock)
         PrepArgs p = mkprep(g, in.p, 1, c->uPL, (long long)tg_rows(g) * MC, MC, 0);
         p.pack = pk;
-        prep_gn(c, p, g, in.st, 6, 1e-6f, sw.gn_g, sw.gn_b, n1, 0, s);
+        prep_gn(p, g, in.st, 6, 1e-6f, sw.gn_g, sw.gn_b);
         p.ln_gamma = sw.l1g; p.ln_beta = sw.l1b;
         if ((out1_tm || (chain && c->chain_coef != 0)) && p.part) { p.coef_out = c->gn_coef; p.coef_out_bs = 2 * MC; coef_ready = chain; }   // (the fp32 fused tail reads them too: round 6)
         do_prep(c, p, n1, s);
@@ -1283,8 +1228,8 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         t.qk = c->QK; t.vt = c->VT; t.v_bs = (long long)MC * g.Tp; t.qk_n = 2 * MC; t.head_dim = HD; t.rows = vt_rows; t.heads2 = 2 * HEADS; t.v_pitch = g.Tp;
         // round 6: this GEMM's epilogue stores k and v pre-split too (as ugemm_kernel's does at small batch), for every attention shape that unpacks them: the
         // key-split ones and the four-query-tile one of large batches (each wave of which used to split all of K and V for itself)
-        presplit = !c->bf16_mode && sp_on(c, c->attn_split) && c->attn_presplit != 0 && sp_on(c, c->gemm_split) && !c->attn_ks_force && !dev_env("SAID_ATTN_KS") &&
-                   !dev_env("SAID_NO_ATTN_QW") && !c->clk_on;   // (then the attention shape below is -4, 8 or 4: all unpack)
+        presplit = !c->bf16_mode && sp_on(c, c->attn_split) && c->attn_presplit != 0 && sp_on(c, c->gemm_split) &&
+                   !c->clk_on;   // (then the attention shape below is -4, 8 or 4: all unpack)
         t.kv_pack = presplit ? 1 : 0;
         do_tgemm(c, t, n1, s);
     } else
@@ -1301,25 +1246,20 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         a.y = c->VT - (long long)a.tm_tiles * 32 * g.Tp; a.y_bstride = (long long)MC * g.Tp; a.y_pitch = g.Tp;
         // tiles per workgroup: the largest shape that still gives every CU a workgroup in ONE round (at Be=2, T=600:
         // NB=3 -> 228 workgroups, 27.5 -> 13.8 us per launch against NB=1's 684 workgroups in 2.7 rounds)
-        static const int qkv_env = dev_env("SAID_QKV_NB") ? atoi(dev_env("SAID_QKV_NB")) : 0;
-        int qkv_nb = qkv_env ? qkv_env : (tt1 * 6 >= 192 ? 3 : (tt1 * 9 >= 192 ? 2 : 1));
-        if (!qkv_env && c->unet_nb_model && tt1 * 18 <= 1024) {   // pick_unet's busiest-CU model over the 18 column tiles (19 tiles: NB 1 -> 2, 342 -> 171 workgroups)
+        int qkv_nb = tt1 * 6 >= 192 ? 3 : (tt1 * 9 >= 192 ? 2 : 1);
+        if (tt1 * 18 <= 1024) {   // pick_unet's busiest-CU model over the 18 column tiles (19 tiles: NB 1 -> 2, 342 -> 171 workgroups)
             double cost = 1e30;
             for (int nb = 1; nb <= 3; ++nb) {
                 const double k = (double)((tt1 * (18 / nb) + 255) / 256) * (0.45 + nb);
                 if (k < cost - 1e-9) { cost = k; qkv_nb = nb; }
             }
         }
-        const LaunchCfg lc = big_qkv ? LaunchCfg{6, 4} : LaunchCfg{qkv_nb, 8};
+        const LaunchCfg lc{qkv_nb, 8};
         // k and v pre-split for the key-split attention shapes (same rule as below), when this GEMM runs on ugemm_kernel (the only epilogue that packs)
-        {
-            const bool key_split = (c->attn_ks_force == 4 || c->attn_ks_force == 8) || (!(tt1 * HEADS >= 2048) && !(tt1 * HEADS > 8192) && !dev_env("SAID_ATTN_KS") && !dev_env("SAID_NO_ATTN_QW") && !c->attn_ks_force);
-            GemmArgs probe = a;
-            probe.b0 = c->cur_b0;
-            presplit = !c->bf16_mode && sp_on(c, c->attn_split) && c->attn_presplit != 0 && key_split && c->use_ugemm && !big_qkv && !c->clk_on &&
-                       (ugemm_supports(probe, EPI_QKV, lc.NB, lc.KS, 2) || ugemm_supports(probe, EPI_QKV, lc.NB, lc.KS));
-            a.kv_split = presplit ? 1 : 0;
-        }
+        const bool key_split = tt1 * HEADS < 2048;
+        presplit = !c->bf16_mode && sp_on(c, c->attn_split) && c->attn_presplit != 0 && key_split && !c->clk_on &&
+                   (ugemm_supports(a, EPI_QKV, lc.NB, lc.KS, 2) || ugemm_supports(a, EPI_QKV, lc.NB, lc.KS));
+        a.kv_split = presplit ? 1 : 0;
         // round 6: this GEMM finalises the block input's GroupNorm coefficients anyway (its operand is LayerNorm(GroupNorm(x))): the first workgroup of every sample
         // leaves them for stchain_kernel, whose GroupNorm'ed residual then needs 2 loads per wave instead of 23 and no finalisation in front of its first barrier
         if (chain && c->chain_coef != 0 && c->gn_coef) { a.gn_coef_out = c->gn_coef; a.gn_coef_bs = 2 * MC; }
@@ -1332,15 +1272,11 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         a.v_bstride = (long long)MC * g.Tp; a.o_bstride = obs;
         a.pitch = g.Tp; a.T = g.T; a.heads = HEADS; a.rows = vt_rows; a.b0 = 0;
         a.scale = 0.17677669529663687f;  // 32 ** -0.5
-        static const int attn_ks_env0 = dev_env("SAID_ATTN_KS") ? atoi(dev_env("SAID_ATTN_KS")) : 0;   // experiment knob
-        const int attn_ks_env = c->attn_ks_force ? c->attn_ks_force : attn_ks_env0;
         // waves per workgroup = ways the key tiles are split: 8 only pays while a wave would otherwise hold a single
         // tile (T <= 256); from there 4 waves with ~5 tiles each merge half as many partial states (B=1: -0.5 % per step)
         // large batches: four query tiles per workgroup sharing each K / V tile through the CU's L1 (-4), see attn.hip
-        static const bool no_qw = dev_env("SAID_NO_ATTN_QW") != nullptr;
-        const int attn_ks = (!no_qw && tt1 * HEADS >= 2048) ? -4 : ((tt1 * HEADS > 8192) ? 1 : ((g.T <= 256 && tt1 * HEADS <= 2048) ? 8 : 4));
-        if (out1_tm && !attn_ks_env && attn_ks == -4) { a.o = static_cast<float*>(c->uPL); a.o_bstride = tg_rows(g); a.o_mode = 1; }
-        int ks_run = attn_ks_env ? attn_ks_env : attn_ks;
+        int ks_run = tt1 * HEADS >= 2048 ? -4 : (g.T <= 256 ? 8 : 4);
+        if (out1_tm && ks_run == -4) { a.o = static_cast<float*>(c->uPL); a.o_bstride = tg_rows(g); a.o_mode = 1; }
         // long sequences at small batch (configs[4]): three query tiles per wave share every K / V fragment (attn2q.hip; bit-identical) where a third of the
         // launch is most of ONE round of workgroups (101 KB of LDS, 264 registers: one workgroup per CU)
         if (presplit && ks_run == 4 && a.o_mode == 0 && (c->attn_2q > 0 || (c->attn_2q < 0 && tt1 * HEADS >= 512 && (long long)n1 * HEADS * ((((g.T + 31) / 32) + 2) / 3) <= 256))) ks_run = 34;   // (one round of one workgroup per CU)
@@ -1358,7 +1294,7 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         // small launches: three workgroups per token tile, each streaming a third of the GEGLU / folded proj_out weights (38 workgroups on 256 CUs were bound by
         // one CU's L2 port each: 2.36 MB per workgroup) — while the launch still is one round of the chip
         ca.slices = 1;
-        if (c->st_chain_slices != 1 && sw.chain_w3 && sw.chain_w2 && !c->st_chain_dbg) {
+        if (c->st_chain_slices != 1 && sw.chain_w3 && sw.chain_w2) {
             if (tt <= CHAIN3_MAX_TILES && c->st_chain_slices != 2) ca.slices = 3;
             else if (tt <= CHAIN2_MAX_TILES) ca.slices = 2;
         }
@@ -1367,7 +1303,6 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         if (!coef_ready && dbg_go_peek(c)) launch_gn_coef(in.st, g.sts, 6, g.np, g.T, 1e-6f, sw.gn_g, sw.gn_b, c->gn_coef, 2 * MC, n1, s);
         ca.gn_coef = c->gn_coef; ca.coef_bs = 2 * MC;
         if (c->clk_on && c->dbg_count < 64) ca.clk = c->clk_dev + (long long)c->dbg_count * 128;
-        if (c->st_chain_dbg) { ca.dbg_x1 = c->X1; ca.dbg_x2 = c->X2; ca.dbg_o2 = c->X3; }
         if (c->log_on) {
             const double w = 4.0 * ((double)3 * MC * MC + 2.0 * FFI * MC + (double)(FFI + MC) * MC);
             const double io = 4.0 * MC * g.T * ((double)n1 * 2 + g.Be) + 4.0 * 2 * MC * g.T * (double)n2;
@@ -1403,8 +1338,7 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
                           // conditional slots — when this launch covers them — are overwritten by attn2's to_out below)
             a.y2 = c->X2; a.y2_bstride = g.hs; a.y2_add = c->c2[blk];
         }
-        const LaunchCfg lc = big_cgemm() ? pick_unet(c, tt1) : LaunchCfg{1, 8};   // the GroupNorm'ed-residual variant exists for NB = 1
-        do_gemm(c, a, EPI_STORE, n1, lc.NB, lc.KS, s);
+        do_gemm(c, a, EPI_STORE, n1, 1, 8, s);   // the GroupNorm'ed-residual variant exists for NB = 1
     }
     {   // attn2: q = to_q(norm2(x1)); banded softmax over the precomputed audio K/V   (attention.py:170-191)
         GemmArgs a = mkargs(g.T, MC);
@@ -1425,7 +1359,7 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
             if (c->log_on) c->stage_log.push_back({5, -2, 0, 0, 0.0, 0.0});
             if (dbg_go(c)) launch_band_wide(a.y, obs, g.Tp, bd.k, bd.v, bd.kv_bstride, bd.kv_pitch, bd.lo, bd.hi, g.T, HEADS, n2, bd.scale, s);
         } else
-        do_gemm(c, a, EPI_BAND, n2, 1, big ? 4 : 8, s);
+        do_gemm(c, a, EPI_BAND, n2, 1, 8, s);
     }
     {   // x2 = to_out(attn2) + x1   (conditional half only under guidance: its slots are [Bc, 2 Bc) of X2)
         GemmArgs a = mkargs(g.T, MC);
@@ -1434,7 +1368,7 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         a.bias = sw.out2.bias;
         a.res_kind = RES_PLAIN; a.res = c->X1 + (long long)x_off * g.hs; a.res_bstride = g.hs; a.res_pitch = g.Tp;
         a.y = c->X2 + (long long)kv_off * g.hs; a.y_bstride = g.hs; a.y_pitch = g.Tp;
-        const LaunchCfg lc = pick_unet(c, tt2);
+        const LaunchCfg lc = pick_unet(tt2);
         do_gemm(c, a, EPI_STORE, n2, lc.NB, lc.KS, s);
     }
     if (use_tg(c, g, g.Be)) {
@@ -1466,12 +1400,10 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         a.seg[0].ln_gamma = sw.l3g; a.seg[0].ln_beta = sw.l3b; a.seg[0].ln_eps = 1e-5f;
         a.bias = sw.ff1.bias; a.geglu_gate_tiles = FFI / 32;
         a.y = c->F; a.y_bstride = (long long)FFI * g.Tp; a.y_pitch = g.Tp;
-        static const int geglu_env = dev_env("SAID_GEGLU_NB") ? atoi(dev_env("SAID_GEGLU_NB")) : 0;
-        const int geglu_nb = geglu_env ? geglu_env : (tt * 6 >= 192 ? 4 : (tt * 12 >= 192 ? 2 : 1));   // one round of workgroups, as for qkv
-        do_gemm(c, a, EPI_GEGLU, g.Be, big ? 3 : geglu_nb, big ? 4 : 8, s);
+        const int geglu_nb = tt * 6 >= 192 ? 4 : (tt * 12 >= 192 ? 2 : 1);   // one round of workgroups, as for qkv
+        do_gemm(c, a, EPI_GEGLU, g.Be, geglu_nb, 8, s);
     }
-    static const bool no_fold = dev_env("SAID_NO_FFPROJ_FOLD") != nullptr;   // A/B knob: the two unfused launches
-    if (!no_fold) {
+    {
         // x3 = net.2(h) + x2 and out = proj_out(x3) + x_in as ONE GEMM over the K segments [h ; x2] with the host-folded
         // weights (P F2 | P) — both maps are per-token linear, so nothing but rounding order changes
         GemmArgs a = mkargs(g.T, MC);
@@ -1482,41 +1414,17 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         a.res_kind = RES_PLAIN; a.res = in.p; a.res_bstride = g.hs; a.res_pitch = g.Tp;
         a.y = out.p; a.y_bstride = g.hs; a.y_pitch = g.Tp;
         a.stats_out = out.st; a.stats_bstride = g.sts;
-        const LaunchCfg lc = pick_unet(c, tt);
-        do_gemm(c, a, EPI_STORE, g.Be, lc.NB, lc.KS, s);
-        return;
-    }
-    {   // x3 = net.2(h) + x2
-        GemmArgs a = mkargs(g.T, MC);
-        a.nseg = 1;
-        a.seg[0] = with_pw(mkseg(c->F, (long long)FFI * g.Tp, g.Tp, FFI, 1, 0, 1, g.T, XF_NONE, sw.ff2.w[0]), sw.ff2, 0);
-        a.bias = sw.ff2.bias;
-        a.res_kind = RES_PLAIN; a.res = c->X2; a.res_bstride = g.hs; a.res_pitch = g.Tp;
-        a.y = c->X3; a.y_bstride = g.hs; a.y_pitch = g.Tp;
-        const LaunchCfg lc = pick_unet(c, tt);
-        do_gemm(c, a, EPI_STORE, g.Be, lc.NB, lc.KS, s);
-    }
-    {   // proj_out (1x1 conv) + x_in   (attention.py:232-234)
-        GemmArgs a = mkargs(g.T, MC);
-        a.nseg = 1;
-        a.seg[0] = with_pw(mkseg(c->X3, g.hs, g.Tp, MC, 1, 0, 1, g.T, XF_NONE, sw.proj.w[0]), sw.proj, 0);
-        a.bias = sw.proj.bias;
-        a.res_kind = RES_PLAIN; a.res = in.p; a.res_bstride = g.hs; a.res_pitch = g.Tp;
-        a.y = out.p; a.y_bstride = g.hs; a.y_pitch = g.Tp;
-        a.stats_out = out.st; a.stats_bstride = g.sts;
-        const LaunchCfg lc = pick_unet(c, tt);
+        const LaunchCfg lc = pick_unet(tt);
         do_gemm(c, a, EPI_STORE, g.Be, lc.NB, lc.KS, s);
     }
 }
 
 // UNetModel.forward (openaimodel.py:677-709): x_cm (latents) -> eps_cm.  Needs KV, band tables and EO ready.
 void run_unet(said_ctx* c, const UGeo& g, hipStream_t s) {
-    c->cur_b0 = g.b0;
     const long long tt = (long long)g.Be * ((g.T + 31) / 32);
     const int in_copies = (g.B_lat > 0 && g.Be % g.B_lat == 0) ? g.Be / g.B_lat : 0;   // samples sharing one clip's latents
-    static const bool no_conv_in = dev_env("SAID_NO_CONV_IN") != nullptr;
     bool conv_in_tm = false;
-    if (!no_conv_in && g.b0 == 0 && in_copies >= 1 && c->conv_in.w4[0] && !c->clk_on &&
+    if (in_copies >= 1 && c->conv_in.w4[0] && !c->clk_on &&
         conv_in_supports(c->cin, MC, c->conv_in.taps, g.T, g.Tp, in_copies)) {
         // input_blocks.0: Conv1d(32 -> 192, k3), computed once per clip (conv_in.hip)
         // (large batches in bf16 mode: straight into the token-major bf16 layout the persistent GEMMs read — no channel-major copy, no transposition)
@@ -1536,14 +1444,14 @@ void run_unet(said_ctx* c, const UGeo& g, hipStream_t s) {
         a.step_inc = g.step_inc;   // the loop's device step counter is advanced by the first kernel of the step
         a.bias = c->conv_in.bias;
         a.y = c->H0.p; a.y_bstride = g.hs; a.y_pitch = g.Tp; a.stats_out = c->H0.st; a.stats_bstride = g.sts;
-        const LaunchCfg lc = pick_unet(c, tt);
+        const LaunchCfg lc = pick_unet(tt);
         do_gemm(c, a, EPI_STORE, g.Be, lc.NB, lc.KS, s);
     }
     const bool sh = g.Bc > 0;   // guidance-shared prefix: the two halves first differ at input_blocks.1.1's cross-attention
     // round 4: the loop's last kernel reads the token-major bf16 hidden state itself (out_sched.hip: out_sched_tm_kernel)
     OutSchedArgs osa_tm;
     bool out_tm = false;
-    if (g.out_sched && c->out_tm != 0 && c->bf16_mode && c->rgemm != 0 && use_tm(c, g) && c->bw_out) {
+    if (g.out_sched && c->out_tm != 0 && c->bf16_mode && use_tm(c, g) && c->bw_out) {
         osa_tm = *g.out_sched;
         osa_tm.x_tm = c->P.t; osa_tm.wb = c->bw_out; osa_tm.seg = tm_seg(g);
         out_tm = out_sched_tm_supports(osa_tm);
@@ -1679,7 +1587,7 @@ UGeo make_geo(said_ctx* c, int Be, int B_lat, int T, int S) {
     UGeo g;
     g.Be = Be; g.B_lat = B_lat; g.T = T; g.Tp = rup(T, 32); g.np = (T + 31) / 32; g.S = S; g.Sp = rup(S, 32);
     g.hs = (long long)MC * g.Tp; g.sts = (long long)MC * g.np * 2;
-    g.step_ptr = nullptr; g.emb_b_stride = 0; g.b0 = 0; g.step_inc = nullptr; g.out_sched = nullptr; g.Bc = 0;
+    g.step_ptr = nullptr; g.emb_b_stride = 0; g.step_inc = nullptr; g.out_sched = nullptr; g.Bc = 0;
     return g;
 }
 
@@ -1791,14 +1699,6 @@ int said_create(said_ctx** out, int device, int max_batch_eff, int max_frames, i
     configure_stchain_kernel();
     configure_attn_kernels();
     configure_out_sched_kernel();
-    ctx->use_ugemm = dev_env("SAID_NO_UGEMM") == nullptr;
-    ctx->use_branches = dev_env("SAID_BRANCHES") != nullptr;
-    ctx->cfg_share = dev_env("SAID_NO_CFG_SHARE") == nullptr;
-    ctx->audio_bf16 = dev_env("SAID_NO_AUDIO_BF16") == nullptr;
-    ctx->pos_tgemm = dev_env("SAID_NO_POSCONV_TGEMM") == nullptr;
-    ctx->unet_tgemm = dev_env("SAID_NO_UNET_TGEMM") == nullptr;
-    ctx->unet_fgemm = dev_env("SAID_NO_UNET_FGEMM") == nullptr;
-    if (dev_env("SAID_UNET_TGEMM_MIN")) ctx->unet_tgemm_min_tokens = ctx->unet_fgemm_min_tokens = atoll(dev_env("SAID_UNET_TGEMM_MIN"));
     configure_tgemm_kernel();
     configure_xgemm_kernels();
     configure_rgemm_kernels();
@@ -1931,7 +1831,7 @@ int said_clone(said_ctx* parent, said_ctx** out, int max_batch_eff, int max_fram
     c->allocs.clear(); c->ws_allocs.clear(); c->alloc_list = &c->allocs;
     c->is_clone = true;
     c->graph = c->graph_rem = nullptr; c->gexec = c->gexec_rem = nullptr; c->gkey.clear(); c->gnodes = 0;
-    c->cap_stream = c->cap_stream2 = nullptr; c->ev_fork = c->ev_join = nullptr; c->own_stream = nullptr;
+    c->cap_stream = nullptr; c->own_stream = nullptr;
     c->stage_log.clear(); c->log_on = false; c->dbg_stop = -1; c->dbg_only = -1; c->dbg_count = 0; c->clk_on = false; c->xclk_on = false;
     // lazily grown buffers start empty
     c->abufA = c->abufB = nullptr; c->abuf_elems[0] = c->abuf_elems[1] = 0;
@@ -2292,6 +2192,7 @@ int said_finalize_weights(said_ctx* ctx, void* stream) {
         ctx->pw_split = 2;   // GEGLU runs as one output tile per wave over the whole K (NB = 4): flat step layout
         if (make_pw(ctx, &sw.ff1, b + ".ff.net.0.proj.weight", b + ".ff.net.0.proj.bias", 2 * FFI, MC, 0, 1, "", "", b + ".norm3.weight", b + ".norm3.bias")) return -1;
         ctx->pw_split = 1;
+        // (no launch multiplies by ff.net.2 or proj_out alone — only by their fold below — but their packing keeps both in fp32 mode's split-range scan)
         if (make_pw(ctx, &sw.ff2, b + ".ff.net.2.weight", b + ".ff.net.2.bias", MC, FFI, 0)) return -1;
         if (make_pw(ctx, &sw.proj, p + ".proj_out.weight", p + ".proj_out.bias", MC, MC, 1)) return -1;
         {   // proj_out o ff.net.2 folded into ONE GEMM over [h (768) ; x2 (192)]  (attention.py:193 `ff(norm3(x)) + x`, :232-234):
@@ -2530,7 +2431,6 @@ int said_unet_forward(said_ctx* ctx, const float* sample_dev, const int64_t* tim
 // for the FIRST graph of a loop it is not — 1200-1400 nodes (50 steps) in front of a 50- or 100-step loop cost configs[2] / configs[4] 2-6 % where the long loops gain 0.4-0.5 %
 // from five times fewer graph boundaries (profiles/r06l_steps_per_graph.txt).  So: spg_limit (50) from 400 steps on, at most 10 below.
 static int steps_per_graph(const said_ctx* ctx, int N) {
-    if (ctx->use_branches) return 1;
     const int lim = N >= 400 ? ctx->spg_limit : std::min(ctx->spg_limit, 10);
     return std::max(1, std::min(lim, N));
 }
@@ -2571,7 +2471,7 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
     if (set_band(ctx, T, T, s)) return -1;
     UGeo g = make_geo(ctx, Be, cfg ? B : 0, T, T);
     g.step_ptr = ctx->step_dev;
-    if (cfg && ctx->cfg_share && !ctx->use_branches) g.Bc = B;
+    if (cfg) g.Bc = B;
     const long long xs = (long long)C * g.Tp;
 
     TRACE("loop: begin");
@@ -2639,8 +2539,7 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
     osa.prediction_type = p->prediction_type; osa.guidance_scale = p->guidance_scale; osa.guidance_rescale = sa.guidance_rescale;
     osa.latent_scale = p->latent_scale;
     osa.status = ctx->status_dev;
-    static const bool no_fuse = dev_env("SAID_NO_FUSE_SCHED") != nullptr;
-    const bool fused = !no_fuse && !ctx->use_branches && ctx->conv_out.w4[0] && out_sched_supports(osa);
+    const bool fused = ctx->conv_out.w4[0] && out_sched_supports(osa);
     if (fused) g.out_sched = &osa;
 
     if (N > 0) {
@@ -2652,13 +2551,11 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
         const std::vector<long long> key = loop_graph_key(ctx, p, sa.step_noise);
         if (!ctx->gexec || key != ctx->gkey) {
             drop_graphs(ctx);
-            const bool fold_step = !(ctx->use_branches && Be >= 2);   // conv_in advances the step counter itself
             // Eager warm-up of the exact step sequence first: the first launch of a kernel inside a
             // stream capture hangs on ROCm 7.2 (lazy per-kernel initialisation is not capturable).
             // The step is run on step index 0 and its effect on the latents is undone afterwards.
             TRACE("loop: warmup begin");
-            if (fold_step) g.step_inc = ctx->step_dev; else launch_step_advance(ctx->step_dev, s);
-            if (trace_on()) { hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[said] step_advance -> %s\n", hipGetErrorString(e)); fflush(stderr); }
+            g.step_inc = ctx->step_dev;   // the first kernel of the step (conv_in) advances the step counter itself
             run_unet(ctx, g, s);
             TRACE("loop: warmup unet launched");
             if (!fused) {
@@ -2681,22 +2578,7 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
             auto capture_steps = [&](int nsteps, hipGraph_t* gr, hipGraphExec_t* ge) -> int {
                 HIPCHK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
                 for (int rep = 0; rep < nsteps; ++rep) {
-                    if (!fold_step) launch_step_advance(ctx->step_dev, cs);
-                    if (ctx->use_branches && Be >= 2) {
-                        // The two halves of the UNet batch (unconditional / conditional under CFG) are independent until
-                        // the scheduler: capture them as parallel branches so their per-kernel latencies overlap.
-                        UGeo ga = g, gb = g;
-                        ga.Be = Be / 2; ga.b0 = 0;
-                        gb.Be = Be - Be / 2; gb.b0 = Be / 2;
-                        HIPCHK(hipEventRecord(ctx->ev_fork, cs));
-                        HIPCHK(hipStreamWaitEvent(ctx->cap_stream2, ctx->ev_fork, 0));
-                        run_unet(ctx, ga, cs);
-                        run_unet(ctx, gb, ctx->cap_stream2);
-                        HIPCHK(hipEventRecord(ctx->ev_join, ctx->cap_stream2));
-                        HIPCHK(hipStreamWaitEvent(cs, ctx->ev_join, 0));
-                    } else {
-                        run_unet(ctx, g, cs);
-                    }
+                    run_unet(ctx, g, cs);
                     if (!fused) {
                         if (sa.guidance_rescale > 0.f) launch_rescale_partials(sa, ctx->rescale_part, cs);
                         launch_sched_step(sa, cs);
@@ -2791,33 +2673,12 @@ int said_debug_option(said_ctx* ctx, const char* name, long long value) {
     } else if (k == "steps_per_graph") {
         if (value < 1) return fail(ctx, "steps_per_graph must be >= 1");
         ctx->spg_limit = (int)value;
-    } else if (k == "hybrid") {
-        ctx->hybrid = value != 0;
     } else if (k == "out_tm") {
         ctx->out_tm = (int)value;
-    } else if (k == "mt_mid") {
-        ctx->mt_mid = value != 0;
-    } else if (k == "mt_wgs") {
-        ctx->mt_wgs = (int)value;
-    } else if (k == "tgemm_sb") {
-        ctx->tgemm_sb = value != 0;
-    } else if (k == "unet_nb") {
-        ctx->unet_nb = (int)value;
-    } else if (k == "unet_nb_model") {
-        ctx->unet_nb_model = value != 0;
-    } else if (k == "f32_out1_tm") {
-        ctx->f32_out1_tm = value != 0;
     } else if (k == "xgemm_clk") {   // shader-clock stamps of the token-major-activation GEMMs (-DSAID_CLK_STAMPS builds); read with said_debug_clocks
         ctx->xclk_on = value != 0;
-    } else if (k == "xgemm_ntw") {
-        ctx->xgemm_ntw = (int)value;
-    } else if (k == "xgemm_dbg") {   // knock-out timing experiments (1: no epilogue, 2: no k loop, 4: no residual, 8: no source tile): WRONG results,
-        if (!dev_env("SAID_DEV")) return fail(ctx, "xgemm_dbg needs a -DSAID_DEV_KNOBS build with SAID_DEV=1");   // so refused by the shipped library
-        ctx->xgemm_dbg = (int)value;
     } else if (k == "tm_acts") {
         ctx->tm_acts = value < 0 ? -1 : (value != 0);
-    } else if (k == "rgemm") {
-        ctx->rgemm = value < 0 ? -1 : (value != 0);
     } else if (k == "gemm_presplit") {
         ctx->gemm_presplit = value < 0 ? -1 : (value != 0);
     } else if (k == "gemm_split") {
@@ -2836,26 +2697,14 @@ int said_debug_option(said_ctx* ctx, const char* name, long long value) {
         ctx->tgemm_direct = value < 0 ? -1 : (value != 0);
     } else if (k == "kconv") {
         ctx->kconv = value < 0 ? -1 : (value == 2 ? 2 : (value != 0));
-    } else if (k == "kconv_max_tiles") {
-        ctx->kconv_max_tiles = value;
     } else if (k == "st_chain") {
         ctx->st_chain = value < 0 ? -1 : (value != 0);
     } else if (k == "attn_2q") {
         ctx->attn_2q = value < 0 ? -1 : (value != 0);
-    } else if (k == "attn_ks") {
-        ctx->attn_ks_force = (int)value;
     } else if (k == "st_chain_slices") {
         ctx->st_chain_slices = value < 0 ? -1 : ((value == 3 || value == 2) ? (int)value : 1);   // 2: two slices wherever a sliced launch is possible (<= 128 tiles)
-    } else if (k == "st_chain_dbg") {
-        ctx->st_chain_dbg = value != 0;
     } else if (k == "st_chain_bf16") {
         ctx->st_chain_bf16 = value < 0 ? -1 : (value != 0);
-    } else if (k == "st_chain_large") {
-        ctx->st_chain_large = value != 0;
-    } else if (k == "st_chain_max_tiles") {
-        ctx->st_chain_max_tiles = value;
-    } else if (k == "battn") {
-        ctx->battn = value < 0 ? -1 : (int)value;   // 0: off, 4 / 8: query tiles per workgroup (experiments), else on
     } else {
         return fail(ctx, "said_debug_option: unknown option %s", name);
     }
@@ -2878,7 +2727,6 @@ long long said_debug_get(const said_ctx* ctx, const char* name) {
     if (k == "n_stchain") return ctx->n_stchain;
     if (k == "st_chain_bf16") return (ctx->bf16_mode && ctx->st_chain_bf16 != 0) ? 1 : 0;
     if (k == "attn_split") return (!ctx->bf16_mode && sp_on(ctx, ctx->attn_split)) ? 1 : 0;   // 1: fp32-mode attention products run on split-fp16 operands
-    if (k == "rgemm") return ctx->rgemm;
     if (k == "n_rgemm") return ctx->n_rgemm;
     if (k == "n_xgemm") return ctx->n_xgemm;
     if (k == "pool_probed") return (ctx->device >= 0 && ctx->device < POOL_DEVICES) ? g_pool_probed[ctx->device] : -1;
@@ -2974,7 +2822,7 @@ int said_profile_unet(said_ctx* ctx, int Be, int T, int cfg_clips, int reps, int
     if (cfg_clips < 0 || (cfg_clips > 0 && Be != 2 * cfg_clips)) return fail(ctx, "said_profile_unet: cfg_clips must be 0 or batch_eff / 2");
     UGeo g = make_geo(ctx, Be, cfg_clips, T, T);
     g.emb_b_stride = 0;
-    if (cfg_clips > 0 && ctx->cfg_share && !ctx->use_branches) g.Bc = cfg_clips;   // the schedule the guided loop runs
+    if (cfg_clips > 0) g.Bc = cfg_clips;   // the schedule the guided loop runs
     run_unet(ctx, g, s);  // eager warm-up: kernels must not see their first launch inside a capture
     HIPCHK(hipStreamSynchronize(s));
     if (ensure_cap_streams(ctx)) return -1;
@@ -3126,7 +2974,7 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
     }
     // bf16 mode (said_set_precision): token-major bf16 encoder on v_mfma_f32_32x32x16_bf16 (tgemm.hip).  conv0 + its
     // per-channel GroupNorm, the grouped positional convolution and the attention kernel are shared with the fp32 path.
-    const bool bfa = ctx->bf16_mode && ctx->audio_bf16 && (!apply_proj || ctx->ctx_dim % 128 == 0) && (int)ctx->blayers.size() == ctx->w2v_layers;
+    const bool bfa = ctx->bf16_mode && (!apply_proj || ctx->ctx_dim % 128 == 0) && (int)ctx->blayers.size() == ctx->w2v_layers;
     if (bfa) {
         const size_t e0 = (size_t)chunk * L[0] * W2V_CONV, e1 = (size_t)chunk * L[1] * W2V_CONV, tk = (size_t)chunk * Fr;
         const size_t xg = (size_t)chunk * 16 * (size_t)rup(Fr + ctx->posconv.taps, 8) * (W2V_H / 16) + 4096;   // per-group positional-conv operand
@@ -3184,7 +3032,7 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                 if (!launch_tgemm(a, nb, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
             }
             const int PK = ctx->posconv.taps, PG = 16, PCG = W2V_H / PG;
-            if (ctx->pos_tgemm && ctx->bw_pos && PK % 2 == 0) {
+            if (ctx->bw_pos && PK % 2 == 0) {
                 // positional conv embedding (wav2vec2: Conv1d(768, 768, k=128, padding=64, groups=16), last output dropped, GELU) as 16
                 // GEMMs on the bf16 token-major kernel: group g's input channels laid out [R][48] with 64 zero rows in front, so
                 // that output token t is row t's 128 x 48 contiguous elements times W_g (tap-major) — 150 GFLOP per 32 clips that
@@ -3227,7 +3075,7 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                     a.a = ctx->bHb; a.a_bs = hsT; a.lda = W2V_H; a.w = bl.qkv; a.bias = ly.qkv.bias;
                     a.qk = ctx->aQK; a.vt = ctx->aVT; a.v_bs = hs; a.qk_n = 2 * W2V_H; a.head_dim = W2V_HD; a.rows = Fp; a.heads2 = 2 * W2V_HEADS;
                     a.v_pitch = Fp; a.M = Fr; a.N = 3 * W2V_H; a.K = W2V_H;
-                    a.sb = ctx->tgemm_sb; a.direct = ctx->tgemm_direct != 0;
+                    a.sb = 1; a.direct = ctx->tgemm_direct != 0;
                     if (!launch_tgemm(a, nb, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
                 }
                 {
@@ -3249,7 +3097,7 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                     a.a = ctx->bO; a.a_bs = hsT; a.lda = W2V_H; a.w = bl.out; a.bias = ly.out.bias;
                     a.res = ctx->bH; a.res_bs = hsT; a.ldr = W2V_H;
                     a.yf = ctx->bT; a.y_bs = hsT; a.ldy = W2V_H; a.M = nb * Fr; a.N = W2V_H; a.K = W2V_H;
-                    a.sb = ctx->tgemm_sb; a.direct = ctx->tgemm_direct != 0;
+                    a.sb = 1; a.direct = ctx->tgemm_direct != 0;
                     if (!launch_tgemm(a, 1, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
                 }
                 launch_ln_tm(ctx->bT, nullptr, ctx->bH, ctx->bHb, ly.ln1g, ly.ln1b, (long long)nb * Fr, W2V_H, 1e-5f, s);
@@ -3258,7 +3106,7 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                     memset(&a, 0, sizeof a);
                     a.a = ctx->bHb; a.a_bs = hsT; a.lda = W2V_H; a.w = bl.ff1; a.bias = ly.ff1.bias; a.act = 1;
                     a.yb = ctx->bF; a.y_bs = (long long)Fr * W2V_FFN; a.ldy = W2V_FFN; a.M = nb * Fr; a.N = W2V_FFN; a.K = W2V_H;
-                    a.sb = ctx->tgemm_sb; a.direct = ctx->tgemm_direct != 0;
+                    a.sb = 1; a.direct = ctx->tgemm_direct != 0;
                     if (!launch_tgemm(a, 1, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
                 }
                 {   // feed_forward.output_dense + residual, then final_layer_norm
@@ -3267,7 +3115,7 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                     a.a = ctx->bF; a.a_bs = (long long)Fr * W2V_FFN; a.lda = W2V_FFN; a.w = bl.ff2; a.bias = ly.ff2.bias;
                     a.res = ctx->bH; a.res_bs = hsT; a.ldr = W2V_H;
                     a.yf = ctx->bT; a.y_bs = hsT; a.ldy = W2V_H; a.M = nb * Fr; a.N = W2V_H; a.K = W2V_FFN;
-                    a.sb = ctx->tgemm_sb; a.direct = ctx->tgemm_direct != 0;
+                    a.sb = 1; a.direct = ctx->tgemm_direct != 0;
                     if (!launch_tgemm(a, 1, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
                 }
                 const bool last = l + 1 == ctx->w2v_layers && !apply_proj;   // the last LayerNorm writes the (B, frames, 768) result itself

@@ -1438,8 +1438,6 @@ static void ulaunch_one(const GemmArgs& a, int batch, hipStream_t s, int tt) {
         const int ks = kconv_smem_floats(a.seg[0].C, (VAR & UV_GN1) ? a.seg[1].C : 0, (VAR & UV_GN1) ? 2 : 3) * (int)sizeof(float);
         if (ks > smem) smem = ks;
     }
-    static const int min_lds = dev_env("SAID_MIN_LDS") ? atoi(dev_env("SAID_MIN_LDS")) : 0;   // experiment: force one workgroup per CU
-    if (smem < min_lds) smem = min_lds;
     if (smem > kMaxLds) { launch_fault("ugemm needs %d B of LDS", smem); return; }
     const int ntt = (a.T + 31) / 32;
     dim3 grid(((MT ? (ntt + tt - 1) / tt : ntt)) * (a.ntiles_per_group / NB), batch);   // x: decoded XCD-aware in the kernel

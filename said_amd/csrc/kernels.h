@@ -12,18 +12,6 @@
 
 namespace said {
 
-// Development knobs (A/B switches, experiment sizes) are environment variables that ONLY a build compiled with
-// -DSAID_DEV_KNOBS reads (SAID_EXTRA_DEFS=-DSAID_DEV_KNOBS python -m said_amd.build --force; scripts/README.md).  The
-// shipped library ignores the environment: every dev_env() below is a null pointer there.
-inline const char* dev_env(const char* name) {
-#ifdef SAID_DEV_KNOBS
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
-
 // operand transforms applied while loading X (fused producer-side elementwise work)
 enum XForm : int {
     XF_NONE = 0,
@@ -187,7 +175,6 @@ void launch_fill_cm_vec(const float* vec, float* dst, int B, int T, int C, int p
 // sinusoidal timestep embedding, channel-major [dim][pitch], column r <- timesteps[r] (ldm/util.py:66-90)
 // freqs_dev: the context's own [dim/2] frequency table (no process-global state: several contexts may coexist)
 void launch_timestep_embedding(const long long* timesteps_dev, const float* freqs_dev, float* dst, int n, int dim, int pitch, hipStream_t s);
-void launch_step_advance(int* step_ptr, hipStream_t s);
 void launch_spin(long long ticks_100mhz, hipStream_t s);   // one wave busy for that long (stream-concurrency probe)
 void configure_gemm_kernels();   // raise the dynamic-LDS limit of every instantiation (call once, outside capture)
 void configure_attn_kernels();
@@ -199,7 +186,7 @@ void launch_band_wide(float* qo, long long qo_bstride, int pitch, const float* k
 // round 6: pre-split K / V, head_dim 32, four key slices, three query tiles per wave (attn2q.hip: long sequences at small batch); channel-major output
 void launch_attn2q(const AttnArgs& a, int batch, hipStream_t s);
 void configure_attn2q_kernel();
-void launch_battn(const AttnArgs& a, int batch, hipStream_t s, int qt = 8);   // qt: query tiles (waves) per workgroup, 4 or 8
+void launch_battn(const AttnArgs& a, int batch, hipStream_t s);
 
 struct SchedArgs {
     const float* eps;          // channel-major [Be][C][pitch] model output

@@ -149,8 +149,6 @@ void launch_timestep_embedding(const long long* timesteps_dev, const float* freq
     hipLaunchKernelGGL(temb_kernel, grid, dim3(64), 0, s, timesteps_dev, freqs_dev, dst, n, dim / 2, pitch);
 }
 
-__global__ void step_advance_kernel(int* p) { *p = *p + 1; }
-void launch_step_advance(int* step_ptr, hipStream_t s) { hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, step_ptr); }
 
 // Welford partials of e_c and eps_cfg for rescale_noise_cfg: part[b][which][blk] = (n, mean, M2)
 __global__ void rescale_partials_kernel(const SchedArgs a, float* __restrict__ part) {

@@ -12,7 +12,7 @@
 extern "C" {
 #endif
 
-/* Test-only switches of one context (the shipped library reads no environment variables):
+/* Test-only switches of one context (the library reads no environment variables; an unknown name fails):
  *   "unet_tgemm_min_tokens"  tokens per launch from which the UNet takes the token-major GEMM path, both precisions
  *                            (< 0: restore the measured defaults 3000 bf16 / 10000 fp32)
  *   "audio_chunk"            clips per audio-encoder pass (default 32)
@@ -20,22 +20,9 @@ extern "C" {
  *   "tm_acts"                bf16 mode, large batches: token-major bf16 activations between the UNet kernels, GroupNorm / LayerNorm applied inside the consuming
  *                            GEMMs (-1 / 1, default); 0: channel-major fp32 activations with preparation kernels (round 2).  (The fp32 twin of the schedule, measured
  *                            slower in round 3, was removed in round 6.)
- *   "xgemm_ntw"              column tiles per workgroup of the resident-source GEMMs (0: chosen per launch)
- *   "hybrid"                 0: bf16 mode at large batch keeps round 2's SpatialTransformer schedule throughout (default 1: from the
- *                            attention output on, the block runs on round 3's token-major kernels — NOTEBOOK.md 7.3)
- *   "mt_mid"                 0: multi-tile workgroups (several token tiles per workgroup, weights kept in registers) only from 1024 workgroups per
- *                            launch on (round 2); default 1: also for launches of 2-4 rounds of one workgroup per CU (NOTEBOOK.md 7.2)
- *   "mt_wgs"                 > 0: workgroups per token tile from which a launch goes multi-tile (overrides both rules)
- *   "tgemm_sb"               0: the bf16 audio encoder's 128 x 128 GEMM tiles keep two LDS operand buffers (two workgroups per CU; round 2); default 1: one
- *                            buffer, three workgroups per CU (11.12 -> 10.90 ms per 32 clips, bit-identical)
  *   "tgemm_direct"           0: the bf16 audio encoder's projections on tgemm_kernel<128> (rounds 2-5); -1 / 1 (default): on tgemm256d_kernel — 256 x 256 x 64 tile, operand tiles
  *                            loaded global -> LDS directly, XOR-swizzled chunks, one barrier per k-tile (round 6; bit-identical)
- *   "f32_out1_tm"            0: fp32 mode at large batch runs attn1.to_out on the channel-major kernel (round 2); default 1: on the token-major fp32 GEMM
- *   "unet_nb_model"          0: round 2's rule for the column tiles per workgroup of the 192-wide channel-major GEMMs (default 1: busiest-CU model)
- *   "unet_nb"                > 0: forces that number of column tiles per workgroup (1, 2 or 3)
  *   "out_tm"                 0: bf16 large batches end the step with round 3's channel-major out conv + scheduler kernel (default -1: out_sched_tm_kernel)
- *   "rgemm"                  0: bf16 large batches without round 4's persistent register-stationary GEMMs (default -1: on)
- *   "battn"                  0: bf16 large batches with attn_kernel on fp32 operands instead of battn_kernel (default -1: on; 4 / 8: query tiles per workgroup)
  *   "gemm_presplit"          fp32 mode, large batches: 0 = fgemm_kernel splits fp32 operands in its k loop (round 5); -1 / 1 (default): the ResBlock convolutions' and q / k / v's
  *                            operands arrive split (prep_kernel packs h | l pairs, packed weight copies; bit-identical, round 6)
  *   "gemm_split"             fp32 mode, large batches: 0 puts fgemm_kernel back on v_mfma_f32_32x32x2_f32 (default -1 / 1: split-fp16 products)
@@ -51,9 +38,7 @@ extern "C" {
  *   "attn_presplit"          fp32 small batch: 0 = attention splits K / V itself (default -1 / 1: the q/k/v GEMM stores them pre-split, attn_kernel<PM = 3>)
  *   "out_split"              out_sched_kernel's convolution: 0 = fp32 MFMAs (default -1 / 1: split-fp16 products, round 5)
  *   "st_chain"               fp32 mode: 0 runs everything behind a SpatialTransformer's self-attention as five launches (rounds 1-4); default -1 / 1:
- *                            one launch per block (stchain_kernel, round 5).  "st_chain_large" 0: only below the token-major threshold;
- *                            "st_chain_max_tiles" n: only while a launch has at most n (sample, 32-token tile) workgroups; "st_chain_dbg" 1: the fused
- *                            kernel also writes x1 / x2 / the cross-attention input to X1 / X2 / X3 (bring-up)
+ *                            one launch per block (stchain_kernel, round 5)
  *   "st_chain_slices"        fp32 mode, fused tail: 1 = always one workgroup per token tile; -1 / 3 (default) = launches of at most 85 (sample, tile) pairs run three
  *                            workgroups per tile, each with a third of the GEGLU / folded proj_out weight stream, partial sums met in memory in a fixed order (round 6)
  *   "st_chain_bf16"          bf16 mode, large batches: 0 = rgemm's six launches behind self-attention; -1 / 1 (default) = stchain_kernel<bf16>, one token tile per workgroup,

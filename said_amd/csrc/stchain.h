@@ -34,9 +34,6 @@ struct ChainArgs {
     const int* hi;           // [T] one past the last visible key
     float* y;                // block output, channel-major [sample][192][pitch]
     float* stats_out;        // its GroupNorm partials [sample][tile][192][2], or null
-    float* dbg_x1;           // debug (said_debug_option "st_chain_dbg"): x1 and x2 to channel-major buffers [sample][192][pitch]
-    float* dbg_x2;
-    float* dbg_o2;           // ... and the cross-attention output
     long long* clk;          // debug: shader-clock stamps [8 waves][16] of workgroup (8, last sample)
     long long part_bs, kvt_bs, y_bs, stats_bs;   // floats between samples
     int S;                   // keys

@@ -676,13 +676,6 @@ __device__ __forceinline__ void chain_body(const ChainHdr& hd, const ChainArgs& 
             for (int r = 0; r < 16; ++r) x2[r] += bo[r] + x1[r];
         }
         clk_stamp_c(clk, w, l, 6);
-        if (a.dbg_x1) {   // bring-up taps (said_debug_option "st_chain_dbg")
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const long long o = (long long)s_idx * 192 * hd.pitch + (long long)(col0 + (r & 3) + 8 * (r >> 2)) * hd.pitch + t;
-                if (tv) { gstore(a.dbg_x1, o, x1[r]); gstore(a.dbg_x2, o, x2[r]); }
-            }
-        }
         // ---- LayerNorm3 (folded into GEGLU's weights) and the raw x2 (second K segment of the folded proj_out) as B operands ----
         const float2 st3 = ln_stats(x2, lnp, j, lt, lh);
         {

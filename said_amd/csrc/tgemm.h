@@ -70,7 +70,6 @@ struct TGemmArgs {
     int f32_split;         // f32 operands: run the products on split-fp16 operands (fgemm_kernel SP; split_f16.h) — fp32-equivalent results
     int f32_packed;        // ... and A, A2 and W ARRIVE split: every element one dword h | l << 16 (split_f16.h pack_split_f16: prep_kernel PrepArgs::pack, engine.cpp
                            // upload_tm_pair): the k loop unpacks with v_perm instead of splitting (round 6: the loop was VALU-bound on the splits); bit-identical results
-    int dbg;               // timing experiments (SAID_TG_DBG): bit 0 = skip the epilogue, bit 1 = skip the K loop
     // ==== token-major ACTIVATION interface (round 3; xgemm_kernel only; large batches, both precisions) ====================
     // Between the UNet kernels the activations are token-major [sample][token][192] in the context's element type ET (bf16 in
     // bf16 mode, fp32 else), sample pitch seg_rows tokens (a multiple of 64, so a 64-row tile never straddles samples), plus

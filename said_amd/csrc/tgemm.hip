@@ -270,7 +270,7 @@ __global__ __launch_bounds__(512) void tgemm256_kernel(const TGemmArgs a) {
     gload_tile(S1, min(1, nk - 1));
     lds_store(S0, 0);
     __syncthreads();
-    for (int kt = 0; kt < ((a.dbg & 2) ? 0 : nk); kt += 2) {
+    for (int kt = 0; kt < nk; kt += 2) {
         gload_tile(S0, min(kt + 2, nk - 1));
         __builtin_amdgcn_sched_barrier(0);
         compute(0);
@@ -376,7 +376,7 @@ __global__ __launch_bounds__(512) void tgemm256d_kernel(const TGemmArgs a) {
     issue(0, 0);
     __builtin_amdgcn_s_waitcnt(0);   // (vmcnt(0): the tile is in LDS)
     __syncthreads();
-    for (int kt = 0; kt < ((a.dbg & 2) ? 0 : nk); ++kt) {
+    for (int kt = 0; kt < nk; ++kt) {
         // tile kt + 1 goes into the buffer tile kt - 1 was read from: every wave passed the barrier that ended that step
         if (kt + 1 < nk) issue(kt + 1, (kt + 1) & 1);
         __builtin_amdgcn_sched_barrier(0);
@@ -565,13 +565,12 @@ __global__ __launch_bounds__(256, OCC) void fgemm_kernel(const TGemmArgs a) {
     // Every load and LDS store of the loop is unconditional, as in tgemm_kernel (steps past the end re-request the last tile).
     // One k-step: request a later tile -> multiply the tile in LDS -> barrier (all four waves have read it) -> park the next
     // tile -> barrier.
-    const int nloop = (a.dbg & 2) ? 0 : nk;
     gload_tile(ra, rw, 0);
     if constexpr (PF == 2) gload_tile(ra1, rw1, min(1, nk - 1));
     lds_store(ra, rw);
     __syncthreads();
     if constexpr (PF == 2) {
-        for (int kt = 0; kt < nloop; kt += 2) {
+        for (int kt = 0; kt < nk; kt += 2) {
             gload_tile(ra, rw, min(kt + 2, nk - 1));
             __builtin_amdgcn_sched_barrier(0);
             compute();
@@ -591,7 +590,7 @@ __global__ __launch_bounds__(256, OCC) void fgemm_kernel(const TGemmArgs a) {
         // tile kt multiplies from buffer kt & 1 while tile kt + 1 (in registers since the previous step) is parked in the other one — free since every wave passed the
         // previous barrier behind its products on it — and tile kt + 2 is requested: ONE barrier per k-step
         gload_tile(ra, rw, min(1, nk - 1));
-        for (int kt = 0; kt < nloop; ++kt) {
+        for (int kt = 0; kt < nk; ++kt) {
             __builtin_amdgcn_sched_barrier(0);
             compute(kt & 1);
             __builtin_amdgcn_sched_barrier(0);
@@ -600,7 +599,7 @@ __global__ __launch_bounds__(256, OCC) void fgemm_kernel(const TGemmArgs a) {
             __syncthreads();
         }
     } else {
-        for (int kt = 0; kt < nloop; ++kt) {
+        for (int kt = 0; kt < nk; ++kt) {
             gload_tile(ra, rw, min(kt + 1, nk - 1));
             __builtin_amdgcn_sched_barrier(0);
             compute();
@@ -1109,7 +1108,7 @@ __global__ __launch_bounds__(256, OCC) void xgemm_kernel(const TGemmArgs a) {
                     const f32x4t v0 = *reinterpret_cast<const f32x4t*>(sc + row * CP + 8 * cq);
                     const f32x4t v1 = *reinterpret_cast<const f32x4t*>(sc + row * CP + 8 * cq + 4);
                     float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                    if (a.res_tm && !(a.dbg & 4)) {
+                    if (a.res_tm) {
                         if constexpr (BF) {
                             const u32x4 rv = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(a.res_tm) + (R0 + row) * a.ldr_tm + n);
 #pragma unroll
@@ -1197,7 +1196,7 @@ __global__ __launch_bounds__(256, OCC) void xgemm_kernel(const TGemmArgs a) {
         }
         return;
     }
-    if constexpr (RS) { if (!(a.dbg & 8)) load_resident(0); }   // (before anything of the k loop is live in registers)
+    if constexpr (RS) load_resident(0);   // (before anything of the k loop is live in registers)
     setup_offsets();
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
@@ -1206,11 +1205,10 @@ __global__ __launch_bounds__(256, OCC) void xgemm_kernel(const TGemmArgs a) {
     gload_step(0);
     lds_store(ra_, rw);
     __syncthreads();
-    const int nk_loop = (a.dbg & 2) ? 1 : nk;   // (timing experiment: no k loop)
     for (int jn = 0; jn < ntw; ++jn) {
         const int s0 = jn * nk;
         // all k-tiles but the last: request the next tile -> multiply -> barrier -> park the next tile -> barrier
-        for (int kt = 0; kt < nk_loop - 1; ++kt) {
+        for (int kt = 0; kt < nk - 1; ++kt) {
             gload_step(s0 + kt + 1);
             __builtin_amdgcn_sched_barrier(0);
             compute(kt);
@@ -1305,7 +1303,7 @@ __global__ __launch_bounds__(256, OCC) void xgemm_kernel(const TGemmArgs a) {
                 const f32x4t v0 = *reinterpret_cast<const f32x4t*>(sc + row * CP + 8 * cq);
                 const f32x4t v1 = *reinterpret_cast<const f32x4t*>(sc + row * CP + 8 * cq + 4);
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                if (a.res_tm && !(a.dbg & 4)) {
+                if (a.res_tm) {
                     if constexpr (BF) {
                         const u32x4 rv = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(a.res_tm) + (R0 + row) * a.ldr_tm + n);
 #pragma unroll
@@ -1428,7 +1426,6 @@ void configure_tgemm_kernel() {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm_kernel<3, 1, false, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, fgemm_lds_bytes<3>());
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm_kernel<3, 1, false, 2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, FGEMM_PK_LDS3);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm_kernel<4, 1, false, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, fgemm_lds_bytes<4>());
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm_kernel<3, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, fgemm_lds_bytes<3>());
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm_kernel<3, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, fgemm_lds_bytes<3>());
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm_kernel<4, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, fgemm_lds_bytes<4>());
 }
@@ -1436,9 +1433,6 @@ bool launch_tgemm(const TGemmArgs& a, int batch, hipStream_t s) {
     if (!tgemm_supports(a)) return false;
     TGemmArgs a2 = a;
     a2.batch = batch;
-    static const int dbg = dev_env("SAID_TG_DBG") ? atoi(dev_env("SAID_TG_DBG")) : 0;
-    a2.dbg = dbg;
-    static const bool no256 = dev_env("SAID_NO_TGEMM256") != nullptr;
     const long long rows_tot = a.seg_rows > 0 ? (long long)batch * a.seg_rows : a.M;
     const int nb = a.seg_rows > 0 ? 1 : batch;
     if (a.f32) {
@@ -1466,45 +1460,35 @@ bool launch_tgemm(const TGemmArgs& a, int batch, hipStream_t s) {
     // For q/k/v and GEGLU (456 / 912 big workgroups) the isolated replays of said_profile_unet favour the big tile (29.8 vs 32.7,
     // 69.7 vs 75.0 us) but the real step does not: 122.1 vs 120.3 ms per 32 clips x 50 steps, three alternating runs on one box
     // (scripts/gpu_r2_ak.sh) — one 147 KB-LDS workgroup per CU starts and drains badly between neighbours of other shapes.  So
-    // the small tile is the rule; SAID_TGEMM_SMALL=0 restores the 256-row tiles, =1 uses them only where they fill the chip.
-    static const int small_bf = dev_env("SAID_TGEMM_SMALL") ? atoi(dev_env("SAID_TGEMM_SMALL")) : -1;
-    if (a.seg_rows > 0 && small_bf != 0 && a.K % 64 == 0 && (!a.a2 || a.K1 % 64 == 0) && (a.N % 96 == 0 || a.N % 128 == 0)) {
+    // the small tile is the rule.
+    if (a.seg_rows > 0 && a.K % 64 == 0 && (!a.a2 || a.K1 % 64 == 0) && (a.N % 96 == 0 || a.N % 128 == 0)) {
         const bool wide_n = a.N % 128 == 0 && (a.geglu || a.N % 96);
-        const long long big_grid = ((rows_tot + 255) / 256) * (a.N / (wide_n ? 256 : 192));
-        const bool can_big = !no256 && (a.N % 256 == 0 || a.N % 192 == 0) && rows_tot >= 4096;
-        if (small_bf != 1 || big_grid < 256 || !can_big) {
-            const long long mt8 = ((rows_tot + 63) / 64 + 7) / 8 * 8;
-            constexpr int LDS3 = fgemm_lds_bytes<3>(), LDS4 = fgemm_lds_bytes<4>();
-            // (the GEGLU tile squeezed to 128 VGPRs for four per CU spills five registers and measured no better: 121.7 vs 120.1 ms)
-            if (wide_n) hipLaunchKernelGGL((fgemm_kernel<4, 1, true>), dim3((unsigned)(mt8 * (a.N / 128))), dim3(256), LDS4, s, a2);
-            else {
-                // one register set at FIVE workgroups per CU (96 VGPRs): the 1216 workgroups of a 192-wide launch at Be = 64 are all
-                // resident at once instead of 1024 + a tail of 192 — 124.5 -> 121.0 ms per 32 clips x 50 steps, three alternating
-                // runs on one box (scripts/gpu_r2_ar.sh).  SAID_BF_OCC5=0: two register sets at four per CU.
-                static const int occ5 = dev_env("SAID_BF_OCC5") ? atoi(dev_env("SAID_BF_OCC5")) : 1;
-                if (occ5) hipLaunchKernelGGL((fgemm_kernel<3, 1, true>), dim3((unsigned)(mt8 * (a.N / 96))), dim3(256), LDS3, s, a2);
-                else hipLaunchKernelGGL((fgemm_kernel<3, 2, true>), dim3((unsigned)(mt8 * (a.N / 96))), dim3(256), LDS3, s, a2);
-            }
-            return true;
-        }
+        const long long mt8 = ((rows_tot + 63) / 64 + 7) / 8 * 8;
+        constexpr int LDS3 = fgemm_lds_bytes<3>(), LDS4 = fgemm_lds_bytes<4>();
+        // (the GEGLU tile squeezed to 128 VGPRs for four per CU spills five registers and measured no better: 121.7 vs 120.1 ms)
+        if (wide_n) hipLaunchKernelGGL((fgemm_kernel<4, 1, true>), dim3((unsigned)(mt8 * (a.N / 128))), dim3(256), LDS4, s, a2);
+        // one register set at FIVE workgroups per CU (96 VGPRs): the 1216 workgroups of a 192-wide launch at Be = 64 are all
+        // resident at once instead of 1024 + a tail of 192 (two register sets at four per CU) — 124.5 -> 121.0 ms per 32 clips x 50 steps,
+        // three alternating runs on one box (scripts/gpu_r2_ar.sh)
+        else hipLaunchKernelGGL((fgemm_kernel<3, 1, true>), dim3((unsigned)(mt8 * (a.N / 96))), dim3(256), LDS3, s, a2);
+        return true;
     }
     if (a.grp > 1 && (a.seg_rows > 0 || a.a2 || a.n_store < 1 || a.col_gs < a.n_store)) return false;   // grouped launches: tgemm_kernel only
-    const bool big = a.grp <= 1 && !no256 && (a.N % 256 == 0 || a.N % 192 == 0) && rows_tot * nb >= 4096 &&
+    const bool big = a.grp <= 1 && (a.N % 256 == 0 || a.N % 192 == 0) && rows_tot * nb >= 4096 &&
                      (rows_tot + 2) * (long long)std::max(a.lda, a.lda2) < 0x7fffffffLL;
     if (a.geglu && !big) return false;   // the GEGLU epilogue needs the 256-wide tile
     // Per-sample operands (audio encoder): a 256-row tile holds one workgroup per CU, so its grid runs in rounds of 256 — the
     // encoder's 768-wide GEMMs at 32 clips x 600 frames are 288 workgroups = two rounds, the second 12 % full.  Where the
-    // 128 x 128 tile (two per CU, rounds of 512) fills its rounds clearly better, it is used instead (SAID_TGEMM_BALANCE=0: never).
-    static const int balance = dev_env("SAID_TGEMM_BALANCE") ? atoi(dev_env("SAID_TGEMM_BALANCE")) : 15;   // margin in percent; 0: never
+    // 128 x 128 tile (two per CU, rounds of 512) fills its rounds clearly better (by a margin of 0.15), it is used instead.
     bool use_big = big;
-    if (big && balance > 0 && a.seg_rows == 0 && !a.geglu && a.N % 128 == 0) {
+    if (big && a.seg_rows == 0 && !a.geglu && a.N % 128 == 0) {
         const long long mt_big = (rows_tot + 255) / 256, mt_128 = (a.M + TBM - 1) / TBM;
         const long long g_big = (long long)nb * mt_big * (a.N / (a.N % 256 == 0 ? 256 : 192));
         const long long g_128 = (long long)batch * mt_128 * (a.N / 128);
         // efficiency = how full the rounds are x how full the row tiles are (rows past M repeat the last row: wasted work)
         const double e_big = (double)g_big / (double)(((g_big + 255) / 256) * 256) * (double)rows_tot / (double)(mt_big * 256);
         const double e_128 = (double)g_128 / (double)(((g_128 + 511) / 512) * 512) * (double)a.M / (double)(mt_128 * TBM);
-        if (e_128 > e_big + 0.01 * balance) use_big = false;
+        if (e_128 > e_big + 0.15) use_big = false;
     }
     // round 6: per-sample operands with 256-wide outputs (the audio encoder's projections): the direct-to-LDS 256 x 256 tile (a.direct; said_debug_option "tgemm_direct")
     if (a.direct && a.grp <= 1 && a.seg_rows == 0 && !a.geglu && !a.a2 && a.N % 256 == 0 && a.K % TBK == 0 && (long long)a.M * batch >= 4096 &&
@@ -1807,8 +1791,7 @@ __global__ __launch_bounds__(256, 5) void prep_kernel(const PrepArgs a) {   // f
 bool launch_prep(const PrepArgs& a, int batch, hipStream_t s) {
     if (a.C != 192 || a.T < 1 || a.ldd % 8 || a.coff % 8 || a.dst_bs % 8 || (a.dst2 && (a.ldd2 % 8 || a.coff2 % 8 || a.dst2_bs % 8)) || a.pitch % 4) return false;
     dim3 grid(a.T / 32 + 1, batch);   // one tile past ceil(T / 32) when T % 32 == 0: the conv operand's right padding row
-    static const int pad = dev_env("SAID_PREP_PAD_LDS") ? atoi(dev_env("SAID_PREP_PAD_LDS")) : 0;   // occupancy experiment: unused dynamic LDS
-    hipLaunchKernelGGL(prep_kernel, grid, dim3(256), pad, s, a);
+    hipLaunchKernelGGL(prep_kernel, grid, dim3(256), 0, s, a);
     return true;
 }
 

@@ -16,7 +16,7 @@ typedef float f32x4t __attribute__((ext_vector_type(4)));
 // The MFMA result layout is D[row][n]: lane -> output column n (l & 31 within a 32-column tile), register r -> row
 // (r & 3) + 8 (r >> 2) + 4 (l >> 5).  Storing straight from that layout makes every store instruction touch up to 64
 // different cache lines (channel-major results: one 16-byte piece per lane; token-major bf16: 2-byte elements), and the
-// knock-out experiment of round 2 (SAID_TG_DBG, scripts/gpu_r2_j.sh) measured the epilogue at 53-57 % of the kernels' time.
+// knock-out experiment of round 2 (scripts/gpu_r2_j.sh) measured the epilogue at 53-57 % of the kernels' time.
 // So the tile goes through a wave-private LDS scratch [32 rows][32 NJ + 4] first (the operand buffers are free after the K
 // loop) — bias / timestep-embedding term / activation / GEGLU product are applied on the way in, where lane == column —
 // and is read back in the layout the destination wants:
@@ -48,10 +48,6 @@ __device__ __forceinline__ void tg_epilogue(const TGemmArgs& a, f32x16 (&acc)[NJ
     const int b = a.seg_rows > 0 ? rt / a.seg_rows : b_grid;
     const int mt = a.seg_rows > 0 ? rt - b * a.seg_rows : rt;
     if (mt >= a.M) return;
-    if (a.dbg & 1) {   // timing experiment (SAID_TG_DBG=1): no epilogue memory traffic — results are WRONG, never used in tests
-        if (acc[0][0] == 12345.678f && a.yf) a.yf[0] = acc[0][1];
-        return;
-    }
     const int nrows = min(32, a.M - mt);
     const int n_store = n_lim ? n_lim : a.n_store;   // first column NOT stored (grouped launches: the group's own limit)
     const long long R0 = (long long)b * a.seg_rows + mt;   // global row of the tile's first token (token-major activation tensors)
