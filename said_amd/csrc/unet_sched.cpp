@@ -1,0 +1,1065 @@
+// unet_sched.cpp — the UNet1D launch schedules: launch-shape choices, the per-block ResBlock / SpatialTransformer
+// launch sequences of every precision mode and batch size, time embedding, cross-attention K/V and the alignment band.
+#include "engine_internal.h"
+
+namespace said {
+namespace host {
+
+LaunchCfg pick_cfg(long long t_tiles_total, int ntiles, bool allow6) {
+    // small problems: maximise workgroups (split K over 8 waves, one tile each);
+    // large problems: amortise the operand transform over more tiles per workgroup.
+    if (t_tiles_total * ntiles <= 1536 || ntiles % 2) return {1, 8};
+    if (t_tiles_total * ntiles <= 4096) return {2, 8};
+    if (allow6 && ntiles % 6 == 0) return {6, 4};
+    if (ntiles % 4 == 0) return {4, 4};
+    if (ntiles % 3 == 0) return {3, 4};
+    return {2, 8};
+}
+
+namespace {
+
+// UNet GEMMs with 6 output tiles (192 channels): the LDS-staged kernel at every batch size — two tiles per workgroup
+// as soon as that still fills the chip (measured at Be=32: 47 TFLOP/s against 34 for the generic NB=6 shape)
+// Column tiles per workgroup (NB) of the UNet's 192-wide channel-major GEMMs.  A launch is t_tiles x 6 / NB workgroups on 256 CUs; its
+// time is that of the busiest CU: ceil(workgroups / 256) workgroups of (F + NB) units each, F = 0.45 the per-workgroup fixed part
+// (GroupNorm finalisation, operand tile; fitted on T = 1800: NB = 1 14.8 us, NB = 2 25.0 us at 342 workgroups each).  Round 2's rule
+// (NB = 2 from 64 tiles) put 342 workgroups on 256 CUs at T = 1800: two rounds of three units where NB = 3 is one round of 3.45.
+LaunchCfg pick_unet(long long t_tiles_total) {
+    if (t_tiles_total * 6 > 1024) return t_tiles_total * 3 >= 192 ? LaunchCfg{2, 8} : LaunchCfg{1, 8};   // (large launches: multi-tile NB = 2 shapes)
+    int best = 1;
+    double cost = 1e30;
+    for (int nb = 1; nb <= 3; ++nb) {
+        const long long wgs = t_tiles_total * (6 / nb);
+        const double k = (double)((wgs + 255) / 256) * (0.45 + nb);
+        if (k < cost - 1e-9) { cost = k; best = nb; }
+    }
+    return LaunchCfg{best, 8};
+}
+
+}  // namespace
+
+Seg mkseg(const float* x, long long bstride, int pitch, int C, int taps, int pad, int stride, int Tin, int xform, const float* w) {
+    Seg s;
+    memset(&s, 0, sizeof s);
+    s.x = x; s.w = w; s.x_bstride = bstride; s.x_pitch = pitch; s.C = C; s.taps = taps; s.pad = pad; s.stride = stride;
+    s.Tin = Tin; s.xform = xform; s.gn_cpg = 1; s.gn_nparts = 1;
+    return s;
+}
+
+namespace {
+
+inline Seg with_w4(Seg s, const float* w4, bool gn_tail = false, bool ln_tail = false) { s.w4 = w4; s.w4_gn_tail = gn_tail ? 1 : 0; s.w4_ln_tail = ln_tail ? 1 : 0; return s; }
+// attach K-segment k of a packed weight: both packings for the LDS-staged kernel and what follows them
+inline Seg with_pw(Seg s, const PW& pw, int k) {
+    s.w4 = pw.w4[k]; s.w2 = pw.w2[k]; s.ws = pw.ws[k]; s.ws_flat = pw.ws_flat ? 1 : 0; s.w4_gn_tail = pw.gn_tail ? 1 : 0; s.w4_ln_tail = pw.ln_tail ? 1 : 0;
+    return s;
+}
+void seg_gn(Seg& s, const float* part, long long part_bstride, int cpg, int nparts, float eps, const float* g, const float* b) {
+    s.gn_part = part; s.gn_part_bstride = part_bstride; s.gn_cpg = cpg; s.gn_nparts = nparts; s.gn_eps = eps; s.gn_gamma = g; s.gn_beta = b;
+}
+
+}  // namespace
+
+GemmArgs mkargs(int T, int N) {
+    GemmArgs a;
+    memset(&a, 0, sizeof a);
+    a.T = T; a.N = N; a.groups = 1; a.ntiles_per_group = (N + 31) / 32;
+    return a;
+}
+
+namespace {
+
+inline bool dbg_go(said_ctx* c) {
+    const int k = c->dbg_count++;
+    if (c->dbg_only >= 0) return k == c->dbg_only;
+    return c->dbg_stop < 0 || k < c->dbg_stop;
+}
+
+// (a helper launch that is not a node of the counted schedule: runs whenever the NEXT counted launch would)
+inline bool dbg_go_peek(const said_ctx* c) { return c->dbg_only >= 0 ? c->dbg_count == c->dbg_only : (c->dbg_stop < 0 || c->dbg_count < c->dbg_stop); }
+
+// algorithmic HBM bytes / flops of one launch: weights + operands in + residual + result out
+// Multi-tile workgroups (gemm_lds.hip, MT): once a launch would have several thousand workgroups, each workgroup walks
+// over `tt` consecutive token tiles instead, keeping its weights in registers; tt is chosen so that ~4 workgroups per
+// CU remain.  Returns 1 when the launch is not eligible.
+constexpr long long KCONV_MAX_TILES = 4096;   // do_gemm: launches of at most this many (sample, token tile) pairs may run the K-long convolutions as NB = 1 kconv_body workgroups
+constexpr long long MT_WGS_PER_TILE = 1024;   // workgroups per extra token tile of a large launch
+constexpr long long MT_MID_WGS = 228;         // ... of a mid-size one
+static int pick_tt(const GemmArgs& a, int epi, int batch, int NB, int KS, bool bf) {
+    if (a.step_inc) return 1;
+    if (epi == EPI_GEGLU || epi == EPI_BAND) return 1;   // measured slower multi-tile (B=32: GEGLU NB=2 x tt vs NB=4, band)
+    const long long ntt = (a.T + 31) / 32;
+    const long long wgs = ntt * (a.ntiles_per_group / NB) * batch;
+    long long want = wgs / MT_WGS_PER_TILE;
+    // mid-size launches (one to four rounds of one workgroup per CU, e.g. q/k/v at T = 1800: 684 workgroups): as many token tiles per
+    // workgroup as there would be rounds, so that ONE round of <= 256 workgroups remains (configs[4]: 16.87k -> 17.34k frames/s)
+    if (want <= 1) want = wgs / MT_MID_WGS;
+    int tt = (int)std::min<long long>(std::min<long long>(8, want), ntt);
+    if (tt <= 1 || !ugemm_supports(a, epi, NB, KS, bf, tt)) return 1;
+    return tt;
+}
+
+// returns true when the launch went to ugemm_kernel (gemm_lds.hip) — the only kernel that honours GemmCommon::gn_coef_out / kv_split
+bool do_gemm(said_ctx* c, const GemmArgs& a, int epi, int batch, int NB, int KS, hipStream_t s) {
+    bool on_ugemm = false;
+    GemmArgs a2 = a;
+    a2.kconv_off = (c->kconv == 0) ? 1 : 0;
+    const bool bf = c->bf16_mode;
+    if (NB == 3 && epi == EPI_STORE && !ugemm_supports(a2, epi, 3, KS, bf)) NB = 2;   // (the two-segment fp32 shapes spill at NB = 3: not built)
+    // K-long up-path convolutions (two / three K segments): the split-fp16 shapes exist for one column tile per workgroup only (kconv_body; with two the second accumulator
+    // set spills).  Where that takes at most 1.5 x the rounds of the chosen shape on the fp32 matrix instructions it wins (a round of NB = 1 split ~11 us, of NB = 2 fp32 ~21 us:
+    // configs[4] 24.3k -> 25.5k frames/s, 3 clips +6 %; 76 tiles — 2 rounds against 1 — loses 2 %: profiles/r06g_kconv_ab.txt)
+    if (!bf && epi == EPI_STORE && NB > 1 && a2.nseg >= 2 && c->kconv != 0 && sp_on(c, c->ugemm_split) && !a2.step_inc && !c->clk_on && (!c->cur_concurrent || c->kconv == 2)) {   // (concurrent clip groups share the CUs: fewer workgroups win there — 5 clips -1.9 %; "kconv" = 2: there too)
+        const long long tiles = (long long)batch * ((a2.T + 31) / 32), r1 = (tiles * 6 + 255) / 256, rn = (tiles * (6 / NB) + 255) / 256;
+        if (tiles <= KCONV_MAX_TILES && 2 * r1 <= 3 * rn && !ugemm_supports(a2, epi, NB, KS, 2) && ugemm_supports(a2, epi, 1, 8, 2)) { NB = 1; KS = 8; }
+    }
+    const int tt = pick_tt(a2, epi, batch, NB, KS, bf);
+    // fp32 mode, single-tile workgroups: split-fp16 products wherever the shape is built for them (gemm_lds.hip SP) and the weights carry the packing
+    const bool sp = !bf && tt <= 1 && sp_on(c, c->ugemm_split) && !a2.step_inc && ugemm_supports(a2, epi, NB, KS, 2);
+    if (c->log_on) {
+        double w = 0, in = 0, fl = 0;
+        const double nout = (double)a.groups * a.N * (epi == EPI_GEGLU ? 2 : 1);
+        for (int i = 0; i < a.nseg; ++i) {
+            const Seg& sg = a.seg[i];
+            w += nout * sg.C * sg.taps * 4.0;
+            in += (double)batch * a.groups * sg.C * sg.Tin * 4.0;
+            fl += 2.0 * batch * nout * sg.C * sg.taps * a.T;
+        }
+        double out = (double)batch * a.groups * a.N * a.T * 4.0;
+        if (a.res_kind != RES_NONE) in += out;
+        if (epi == EPI_BAND) in += 2.0 * batch * a.N * a.T * 4.0;  // this block's K and V rows
+        c->stage_log.push_back({((tt > 1 || ugemm_supports(a, epi, NB, KS, bf) || ugemm_supports(a, epi, NB, KS))) ? 2 : 0, epi, NB, KS, w + in + out, fl});
+    }
+    if (c->clk_on && c->dbg_count < 64) a2.clk = c->clk_dev + (long long)c->dbg_count * 128;
+    if (dbg_go(c)) {
+        if (trace_on()) { fprintf(stderr, "[said] gemm #%d epi=%d NB=%d KS=%d T=%d N=%d batch=%d tt=%d\n", c->dbg_count - 1, epi, NB, KS, a.T, a.N, batch, tt); fflush(stderr); }
+        const bool ug = !a2.step_inc;
+        on_ugemm = true;
+        if (tt > 1) launch_ugemm(a2, epi, batch, NB, KS, s, bf, tt);
+        else if (sp) launch_ugemm(a2, epi, batch, NB, KS, s, 2);
+        else if (ug && bf && ugemm_supports(a2, epi, NB, KS, true)) launch_ugemm(a2, epi, batch, NB, KS, s, true);
+        else if (ug && ugemm_supports(a2, epi, NB, KS)) launch_ugemm(a2, epi, batch, NB, KS, s);
+        else on_ugemm = false;
+        if (on_ugemm) {}
+        else if (epi == EPI_QKV && a2.kv_split) c->launch_err = "q/k/v GEMM asked for pre-split k / v but does not run on ugemm_kernel";
+        else launch_gemm(a2, epi, batch, NB, KS, s);
+        if (trace_on()) { hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[said]   -> %s\n", hipGetErrorString(e)); fflush(stderr); }
+    }
+    return on_ugemm;
+}
+void do_attn(said_ctx* c, const AttnArgs& a, int batch, int head_dim, int KS, hipStream_t s, bool presplit = false) {
+    if (c->log_on) {
+        const double e = (double)batch * a.heads * head_dim * a.T;
+        c->stage_log.push_back({1, -1, head_dim / 32, KS, 4.0 * e * 4.0, 4.0 * e * a.T});
+    }
+    if (dbg_go(c)) {
+        if (trace_on()) { fprintf(stderr, "[said] attn #%d D=%d KS=%d T=%d batch=%d\n", c->dbg_count - 1, head_dim, KS, a.T, batch); fflush(stderr); }
+        launch_attn(a, batch, head_dim, KS, s, c->bf16_mode ? 1 : (sp_on(c, c->attn_split) ? (presplit ? 3 : 2) : 0));
+        if (trace_on()) { hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[said]   -> %s\n", hipGetErrorString(e)); fflush(stderr); }
+    }
+}
+
+// ---- bf16 mode, large batches: UNet GEMMs on the token-major bf16 kernel (tgemm.hip) ------------------------------------
+// The channel-major fp32 activations stay as they are between kernels (GroupNorm statistics, residuals, attention operands);
+// what changes is the GEMM itself: a prep kernel applies the fused operand transform once and writes the operand token-major
+// in bf16, and the GEMM runs as 128-token tiles on v_mfma_f32_32x32x16_bf16 without any split-K reduction.
+bool use_tg(said_ctx* c, const UGeo& g, int nsamples) {
+    // (the token-major kernels address their operands with 32-bit element offsets: beyond that the channel-major kernels run)
+    const long long widest = ((long long)nsamples * rup(g.T + 2, 32) + 2) * FFI;
+    if (c->band_wmax > 8) return false;   // wide alignment windows: the channel-major schedule (its generic band kernel)
+    return !c->clk_on && widest < 0x7fffffffLL &&
+           (long long)nsamples * g.T >= (c->bf16_mode ? c->unet_tgemm_min_tokens : (c->cur_concurrent ? std::min(c->unet_fgemm_min_tokens, c->unet_fgemm_min_concurrent) : c->unet_fgemm_min_tokens));
+}
+// weight of the token-major GEMM in the context's precision mode
+inline const void* tw(const said_ctx* c, const void* bf, const void* f32) { return c->bf16_mode ? bf : f32; }
+void do_prep(said_ctx* c, const PrepArgs& a, int batch, hipStream_t s) {
+    if (c->log_on) c->stage_log.push_back({5, -2, 0, 0, (double)batch * a.C * a.T * (4.0 + (c->bf16_mode ? 2.0 : 4.0)) * (a.dst2 ? 1.5 : 1.0), 0.0});
+    PrepArgs a2 = a;
+    a2.f32 = c->bf16_mode ? 0 : 1;
+    if (!a2.f32) a2.pack = 0;
+    if (dbg_go(c) && !launch_prep(a2, batch, s)) c->launch_err = "operand preparation kernel: unsupported shape";
+}
+void do_tgemm(said_ctx* c, const TGemmArgs& a, int batch, hipStream_t s) {
+    if (c->log_on) {
+        const double eb = c->bf16_mode ? 2.0 : 4.0;   // operand element size; KS = 32 marks the fp32 kernel (fgemm_kernel) in the log
+        const double out_b = a.geglu ? a.N / 2 * eb : (a.y_cm ? 4.0 * a.N * (a.res_cm ? 2 : 1) : 4.0 * a.N);
+        const int tile_n = c->bf16_mode ? (a.N % 128 == 0 ? 128 : 64) : ((a.N % 128 == 0 && (a.geglu || a.N % 96)) ? 128 : 96);
+        c->stage_log.push_back({4, a.geglu ? EPI_GEGLU : (a.qk ? EPI_QKV : EPI_STORE), tile_n, c->bf16_mode ? 4 : 32,
+                                eb * a.N * a.K + (double)batch * a.M * (eb * a.K + out_b), 2.0 * batch * (double)a.M * a.N * a.K});
+    }
+    TGemmArgs a2 = a;
+    a2.f32 = c->bf16_mode ? 0 : 1;
+    if (a2.f32 && a2.yb) { a2.yf = reinterpret_cast<float*>(a2.yb); a2.yb = nullptr; }   // token-major intermediate (GEGLU product) in fp32
+    a2.f32_split = (a2.f32 && sp_on(c, c->gemm_split)) ? 1 : 0;
+    if (!a2.f32_split) a2.f32_packed = 0;
+    if (dbg_go(c) && !launch_tgemm(a2, batch, s)) {
+        char b[160]; snprintf(b, sizeof b, "token-major GEMM: shape M=%d N=%d K=%d (batch %d) is not served by any kernel", a.M, a.N, a.K, batch);
+        c->launch_err = b;
+    }
+}
+// per-sample row pitch of the token-major operands: a multiple of 32 that holds the T tokens plus the two Conv1d padding rows, so
+// that all samples form ONE row axis for the 256-row GEMM tiles (tgemm.h: seg_rows) and 32-row MFMA tiles never straddle samples
+inline int tg_rows(const UGeo& g) { return rup(g.T + 2, 32); }
+PrepArgs mkprep(const UGeo& g, const float* x, int mode, void* dst, long long dst_bs, int ldd, int coff) {
+    PrepArgs p;
+    memset(&p, 0, sizeof p);
+    p.x = x; p.x_bs = g.hs; p.pitch = g.Tp; p.T = g.T; p.C = MC; p.mode = mode;
+    p.dst = dst; p.dst_bs = dst_bs; p.ldd = ldd; p.coff = coff;
+    return p;
+}
+// GroupNorm of the operand: its coefficients are finalised inside the preparation kernel from the producer's partials
+void prep_gn(PrepArgs& p, const UGeo& g, const float* part, int cpg, float eps, const float* gamma, const float* beta) {
+    p.part = part; p.part_bs = g.sts; p.gn_cpg = cpg; p.gn_nparts = g.np; p.gn_eps = eps; p.gn_gamma = gamma; p.gn_beta = beta;
+}
+TGemmArgs mktg(const UGeo& g, const void* a, int lda, const void* w, int N, int K) {
+    TGemmArgs t;
+    memset(&t, 0, sizeof t);
+    t.a = a; t.a_bs = 0; t.lda = lda; t.w = w; t.M = g.T; t.N = N; t.K = K; t.seg_rows = tg_rows(g);
+    return t;
+}
+void tg_cm_out(TGemmArgs& t, const UGeo& g, const ActBuf& out) {
+    t.y_cm = out.p; t.cm_bs = g.hs; t.cm_pitch = g.Tp; t.stats = out.st; t.stats_bs = g.sts;
+}
+
+// ---- round 3, large batches: token-major activations between the kernels, operand transforms inside the GEMMs (xgemm_kernel) ----
+inline int tm_seg(const UGeo& g) { return rup(g.T, 64); }   // sample pitch in tokens: a 64-row tile never straddles samples
+// (32-bit element offsets inside the kernels: the widest token-major tensor here is the GEGLU product, sample pitch tm_seg — up to 4/3 of
+// the rup(T + 2, 32) pitch use_tg's guard is written for)
+inline bool use_tm(said_ctx* c, const UGeo& g) {
+    return c->bf16_mode && c->tm_acts != 0 && use_tg(c, g, g.Be) && ((long long)g.Be * tm_seg(g) + 2) * FFI < 0x7fffffffLL;
+}
+// `rows` tokens further into a token-major tensor of row width `ld` (element size by precision mode)
+inline void* tm_at(const said_ctx* c, void* base, long long rows, int ld) { return static_cast<char*>(base) + rows * ld * (c->bf16_mode ? 2 : 4); }
+void do_xgemm(said_ctx* c, const TGemmArgs& a, int batch, hipStream_t s) {
+    TGemmArgs a2 = a;
+    a2.f32 = c->bf16_mode ? 0 : 1;
+    if (c->xclk_on && c->dbg_count < 64) a2.clk = c->clk_dev + (long long)c->dbg_count * 128;
+    if (a2.f32 && a2.yb) { a2.yf = reinterpret_cast<float*>(a2.yb); a2.yb = nullptr; }
+    // kernel family: 7 = rgemm_kernel (round 4: register-stationary weights, helper waves), 6 = round 3's xgemm_kernel
+    const int fam = (!a2.f32 && rgemm_supports(a2, batch)) ? 7 : 6;
+    if (c->log_on) {
+        const double eb = c->bf16_mode ? 2.0 : 4.0;
+        const double out_n = a.geglu ? a.N / 2 : a.N;
+        const double out_b = a.y_cm ? 4.0 * out_n : (a.qk ? 4.0 * out_n : eb * out_n * (a.y2_tm ? 2 : 1));
+        const double in_k = (a.ra[0] ? (a.ra[1] ? 384.0 : 192.0) : 0.0) + a.sk[0] + a.sk[1] + a.sk[2];   // source channels read per token (a conv reads its tile once)
+        const double res_b = a.res_tm ? eb * a.N : 0.0;
+        const double band_b = a.band_k ? 2.0 * 4.0 * a.N : 0.0;
+        c->stage_log.push_back({fam, a.geglu ? EPI_GEGLU : (a.qk ? EPI_QKV : (a.band_k ? EPI_BAND : EPI_STORE)), a.N % 128 == 0 && (a.geglu || a.N % 96) ? 128 : 96, c->bf16_mode ? 4 : 32,
+                                eb * a.N * a.K + (double)batch * a.M * (eb * in_k + out_b + res_b + band_b), 2.0 * batch * (double)a.M * a.N * a.K});
+    }
+    if (fam == 7) {
+        if (dbg_go(c)) {
+            if (!launch_rgemm(a2, batch, s)) c->launch_err = "rgemm_kernel refused a launch its own rgemm_supports() had accepted";
+            ++c->n_rgemm;
+        }
+        return;
+    }
+    // a launch over a COLUMN RANGE of the packed weights (the split concatenated-input ResBlocks / folded proj_out probe only their first launch) is
+    // something only rgemm_kernel understands: falling through to xgemm_kernel would silently multiply the wrong columns
+    if (a2.w_k0 != 0 || (a2.w_ld != 0 && a2.w_ld != a2.K) || a2.w_seg != 0) {
+        c->launch_err = "token-major GEMM over a weight column range is not served by rgemm_kernel for this shape";
+        return;
+    }
+    ++c->n_xgemm;
+    if (dbg_go(c) && !launch_xgemm(a2, batch, s)) {
+        char b[160]; snprintf(b, sizeof b, "token-major activation GEMM: shape M=%d N=%d K=%d (batch %d) is not served by any kernel", a.M, a.N, a.K, batch);
+        c->launch_err = b;
+    }
+}
+TGemmArgs mkx(const UGeo& g, const void* w, int N, int K) {
+    TGemmArgs t;
+    memset(&t, 0, sizeof t);
+    t.w = w; t.M = g.T; t.N = N; t.K = K; t.seg_rows = tm_seg(g);
+    t.gn_part_bs = g.sts; t.gn_nparts = g.np; t.stats_bs = g.sts; t.ldy = MC; t.ldr_tm = MC;
+    return t;
+}
+void run_resblock_tm(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, const ActBuf& in0, const ActBuf* in1, const ActBuf& out, hipStream_t s, bool shared) {
+    const int nb = shared ? g.Bc : g.Be;
+    // Round 4 (bf16 mode): a concatenated-input ResBlock (K = 1152 / 576 + 384) runs as launches of rgemm_kernel over COLUMN RANGES of the
+    // same packed weights — its register-stationary weight fragments hold 576 columns per wave — with a bf16 partial sum in between (one extra
+    // rounding of a quantity the next kernel rounds anyway): conv1 = [source 0 -> P] + [source 1 + bias + emb + P], and the 1x1 skip over
+    // the raw input becomes the residual of conv2.  The partial / skip tensor lives in tX1 (idle until the block's SpatialTransformer).
+    bool split = false;
+    if (in1 && c->bf16_mode && rw.has_skip) {
+        TGemmArgs t = mkx(g, rw.t_conv1, MC, 3 * MC);
+        t.ra[0] = in0.t; t.rmode = 1; t.rtaps = 3; t.gn_part[0] = in0.st; t.gn_cpg = rw.cin / 32; t.gn_eps = 1e-5f; t.gn_gamma = rw.g1; t.gn_beta = rw.b1;
+        t.y_tm = c->tX1; t.w_ld = 3 * rw.cin; t.w_seg = rw.cin;
+        split = rgemm_supports(t, nb);
+    }
+    if (split) {
+        {   // in_layers, source 0: GN -> SiLU -> conv3 over the first 192 input channels -> P
+            TGemmArgs t = mkx(g, rw.t_conv1, MC, 3 * MC);
+            t.ra[0] = in0.t; t.rmode = 1; t.rtaps = 3;
+            t.gn_part[0] = in0.st; t.gn_cpg = rw.cin / 32; t.gn_eps = 1e-5f; t.gn_gamma = rw.g1; t.gn_beta = rw.b1;
+            t.w_ld = 3 * rw.cin; t.w_k0 = 0; t.w_seg = rw.cin;
+            t.y_tm = c->tX1;
+            do_xgemm(c, t, nb, s);
+        }
+        {   // in_layers, source 1 (the skip connection's channels) + bias + emb term + P
+            TGemmArgs t = mkx(g, rw.t_conv1, MC, 3 * MC);
+            t.ra[0] = in1->t; t.rmode = 1; t.rtaps = 3;
+            t.gn_part[0] = in1->st; t.gn_cpg = rw.cin / 32; t.gn_eps = 1e-5f; t.gn_gamma = rw.g1 + MC; t.gn_beta = rw.b1 + MC;
+            t.w_ld = 3 * rw.cin; t.w_k0 = MC; t.w_seg = rw.cin;
+            t.bias = rw.conv1.bias;
+            t.emb = c->EO + (long long)rb_index * MC * c->maxNp; t.emb_pitch = c->maxNp; t.step_ptr = g.step_ptr; t.emb_b_stride = g.emb_b_stride;
+            t.res_tm = c->tX1;
+            t.y_tm = c->M.t; t.stats = c->M.st;
+            do_xgemm(c, t, nb, s);
+        }
+        {   // skip_connection: Conv1d 1x1 over the concatenated raw input (openaimodel.py:194) -> tX1
+            TGemmArgs t = mkx(g, rw.t_conv2, MC, 2 * MC);
+            t.sa[0] = in0.t; t.sld[0] = MC; t.sk[0] = MC;
+            t.sa[1] = in1->t; t.sld[1] = MC; t.sk[1] = MC;
+            t.w_ld = 3 * MC + 2 * MC; t.w_k0 = 3 * MC;
+            t.y_tm = c->tX1;
+            do_xgemm(c, t, nb, s);
+        }
+        {   // out_layers: GN -> SiLU -> conv3 + (both biases) + skip(x)
+            TGemmArgs t = mkx(g, rw.t_conv2, MC, 3 * MC);
+            t.ra[0] = c->M.t; t.rmode = 1; t.rtaps = 3;
+            t.gn_part[0] = c->M.st; t.gn_cpg = 6; t.gn_eps = 1e-5f; t.gn_gamma = rw.g2; t.gn_beta = rw.b2;
+            t.w_ld = 3 * MC + 2 * MC; t.w_k0 = 0;
+            t.bias = rw.bias2;
+            t.res_tm = c->tX1;
+            t.y_tm = out.t; t.stats = out.st;
+            do_xgemm(c, t, nb, s);
+        }
+        return;
+    }
+    {   // in_layers: GN -> SiLU -> conv3 + emb term   (openaimodel.py:205-225)
+        TGemmArgs t = mkx(g, tw(c, rw.t_conv1, rw.tf_conv1), MC, 3 * rw.cin);
+        t.ra[0] = in0.t; t.ra[1] = in1 ? in1->t : nullptr; t.rmode = 1; t.rtaps = 3;
+        t.gn_part[0] = in0.st; t.gn_part[1] = in1 ? in1->st : nullptr; t.gn_cpg = rw.cin / 32; t.gn_eps = 1e-5f; t.gn_gamma = rw.g1; t.gn_beta = rw.b1;
+        t.bias = rw.conv1.bias;
+        t.emb = c->EO + (long long)rb_index * MC * c->maxNp; t.emb_pitch = c->maxNp; t.step_ptr = g.step_ptr; t.emb_b_stride = g.emb_b_stride;
+        t.y_tm = c->M.t; t.stats = c->M.st;
+        do_xgemm(c, t, nb, s);
+    }
+    {   // out_layers: GN -> SiLU -> conv3 ; + skip(x)   (openaimodel.py:226-227)
+        TGemmArgs t = mkx(g, tw(c, rw.t_conv2, rw.tf_conv2), MC, 3 * MC + (rw.has_skip ? 2 * MC : 0));
+        t.ra[0] = c->M.t; t.rmode = 1; t.rtaps = 3;
+        t.gn_part[0] = c->M.st; t.gn_cpg = 6; t.gn_eps = 1e-5f; t.gn_gamma = rw.g2; t.gn_beta = rw.b2;
+        if (rw.has_skip) {   // 1x1 conv over the concatenated raw input: two streamed K segments behind the resident one
+            t.sa[0] = in0.t; t.sld[0] = MC; t.sk[0] = MC;
+            t.sa[1] = in1->t; t.sld[1] = MC; t.sk[1] = MC;
+            t.bias = rw.bias2;
+        } else {
+            t.bias = rw.conv2.bias;
+            t.res_tm = in0.t;
+        }
+        t.y_tm = out.t; t.stats = out.st;
+        if (shared) { t.y2_tm = out.t; t.y2_row_off = (long long)g.Bc * tm_seg(g); }
+        do_xgemm(c, t, nb, s);
+    }
+}
+// last: this block feeds the `out` convolution, which reads channel-major fp32 + GroupNorm partials (out_sched.hip)
+void run_transformer_tm(said_ctx* c, const UGeo& g, const STW& sw, int blk, const ActBuf& in, const ActBuf& out, hipStream_t s, bool shared, bool last) {
+    const int n1 = shared ? g.Bc : g.Be;
+    const int n2 = g.Bc > 0 ? g.Bc : g.Be;
+    const int x_off = (g.Bc > 0 && !shared) ? g.Bc : 0;
+    const int kv_off = g.Bc > 0 ? g.Bc : 0;
+    const long long seg = tm_seg(g);
+    const int vt_rows = rup(g.T, 32);
+    bool battn = false;
+    {   // x = norm(x); q, k, v = to_{q,k,v}(norm1(x)) into attn.hip's operand layout   (attention.py:227, 168, 93-97)
+        TGemmArgs t = mkx(g, tw(c, sw.t_qkv, sw.tf_qkv), 3 * MC, MC);
+        t.ra[0] = in.t; t.rmode = 3; t.rtaps = 1;
+        t.gn_part[0] = in.st; t.gn_cpg = 6; t.gn_eps = 1e-6f; t.gn_gamma = sw.gn_g; t.gn_beta = sw.gn_b;
+        t.ln_gamma = sw.l1g; t.ln_beta = sw.l1b;
+        t.qk = c->QK; t.vt = c->VT; t.v_bs = (long long)MC * g.Tp; t.qk_n = 2 * MC; t.head_dim = HD; t.rows = vt_rows; t.heads2 = 2 * HEADS; t.v_pitch = g.Tp;
+        // round 4 (bf16 mode, T <= 640): the projection writes bf16 q / k / v in battn_kernel's operand layout (attn.hip)
+        AttnArgs pa;
+        pa.qk = c->QK; pa.v = c->VT; pa.o = static_cast<float*>(c->tO); pa.v_bstride = (long long)MC * g.Tp; pa.o_bstride = seg;
+        pa.pitch = g.Tp; pa.T = g.T; pa.heads = HEADS; pa.rows = vt_rows; pa.b0 = 0; pa.scale = 0.17677669529663687f;
+        t.qkv_bf16 = (c->bf16_mode && battn_supports(pa, HD)) ? 1 : 0;
+        if (t.qkv_bf16 && !rgemm_supports(t, n1)) t.qkv_bf16 = 0;
+        battn = t.qkv_bf16 != 0;
+        t.q_scale = 0.17677669529663687f * 1.4426950408889634f;   // dim_head ** -0.5 (attention.py:101) x log2(e)
+        do_xgemm(c, t, n1, s);
+    }
+    {   // softmax(q k^T * scale) v -> token-major   (attention.py:99-126)
+        AttnArgs a;
+        a.qk = c->QK; a.v = c->VT; a.o = static_cast<float*>(c->tO);
+        a.v_bstride = (long long)MC * g.Tp; a.o_bstride = seg; a.o_mode = c->bf16_mode ? 2 : 1;
+        a.pitch = g.Tp; a.T = g.T; a.heads = HEADS; a.rows = vt_rows; a.b0 = 0;
+        a.scale = 0.17677669529663687f;
+        if (battn) {
+            if (c->log_on) { const double e = (double)n1 * HEADS * HD * g.T; c->stage_log.push_back({9, -1, 1, 1, 4.0 * e * 2.0, 4.0 * e * g.T}); }
+            if (dbg_go(c)) launch_battn(a, n1, s);
+        } else {
+            do_attn(c, a, n1, HD, -4, s);
+        }
+    }
+    // round 5: everything behind the attention as ONE launch on bf16 operands (stchain_kernel<true>; the token-major bf16 tensors are its operands as they are)
+    if (c->bf16_mode && c->st_chain_bf16 != 0 && !last && sw.chain_wb && sw.chain_vec && c->band_chain_ok && c->kvt_S == g.S && c->kvt_bf16 && g.S == c->band_S && g.T == c->band_T &&
+        (long long)g.Be * seg * MC < 0x7fffffffLL) {
+        ChainArgs ca;
+        memset(&ca, 0, sizeof ca);
+        ca.wstream = static_cast<const float*>(sw.chain_wb); ca.vec = sw.chain_vec;
+        ca.xin_part = in.st; ca.part_bs = g.sts; ca.gn_gamma = sw.gn_g; ca.gn_beta = sw.gn_b;
+        ca.kvt = c->KVT; ca.kvt_bs = (long long)g.S * (NST * 2 * MC); ca.lo = c->band_lo; ca.hi = c->band_hi;
+        ca.y = static_cast<float*>(out.t); ca.y_bs = seg * MC; ca.stats_out = out.st; ca.stats_bs = g.sts;
+        ca.S = g.S; ca.np = g.np; ca.koff = blk * 2 * MC; ca.wmax = c->band_wmax; ca.scale = 0.17677669529663687f;
+        if (c->log_on) {
+            const double w = 2.0 * ((double)3 * MC * MC + 2.0 * FFI * MC + (double)(FFI + MC) * MC);
+            const double io = 2.0 * MC * g.T * ((double)n1 * 2 + g.Be) + 4.0 * 2 * MC * g.T * (double)n2;
+            const double fl = 2.0 * g.T * ((double)n1 * MC * MC + (double)n2 * 2 * MC * MC + (double)g.Be * (2.0 * FFI * MC + (double)(FFI + MC) * MC)) + 4.0 * n2 * MC * g.T * c->band_wmax;
+            c->stage_log.push_back({10, EPI_STORE, 6, 8, w + io, fl});
+        }
+        if (c->xclk_on && c->dbg_count < 64) ca.clk = c->clk_dev + (long long)c->dbg_count * 128;   // (said_debug_option "xgemm_clk": -DSAID_CLK_STAMPS builds)
+        if (dbg_go(c)) {
+            launch_stchain(ca, static_cast<const float*>(c->tO), static_cast<const float*>(in.t), g.T, g.Tp, seg * MC, seg * MC, shared ? g.Bc : 0, g.Bc > 0 ? g.Bc : 0, g.Be, s, true);
+            ++c->n_stchain;
+        }
+        return;
+    }
+    {   // x1 = to_out(attn) + GroupNorm(x_in)   (attention.py:127, 168); under guidance also x2 of the unconditional half = x1 + c2
+        TGemmArgs t = mkx(g, tw(c, sw.t_out1, sw.tf_out1), MC, MC);
+        t.sa[0] = c->tO; t.sld[0] = MC; t.sk[0] = MC;
+        t.bias = sw.out1.bias;
+        t.res_tm = in.t; t.res_gn = 1; t.res_part = in.st; t.res_gamma = sw.gn_g; t.res_beta = sw.gn_b; t.res_eps = 1e-6f; t.gn_cpg = 6;
+        t.y_tm = c->tX1;
+        if (g.Bc > 0) { t.y2_tm = c->tX2; t.y2_row_off = 0; t.y2_add = c->c2[blk]; }
+        do_xgemm(c, t, n1, s);
+    }
+    {   // attn2: q = to_q(norm2(x1)); banded softmax over the precomputed audio K/V   (attention.py:170-191)
+        TGemmArgs t = mkx(g, tw(c, sw.t_q2, sw.tf_q2), MC, MC);
+        t.ra[0] = tm_at(c, c->tX1, x_off * seg, MC); t.rmode = 2; t.rtaps = 1;
+        t.ln_gamma = sw.l2g; t.ln_beta = sw.l2b;
+        const long long kvbs = (long long)NST * 2 * MC * g.Sp;
+        t.band_k = c->KV + (long long)(blk * 2 * MC) * g.Sp + (long long)kv_off * kvbs;
+        t.band_v = c->KV + (long long)(blk * 2 * MC + MC) * g.Sp + (long long)kv_off * kvbs;
+        t.band_kv_bs = kvbs; t.band_kv_pitch = g.Sp; t.band_lo = c->band_lo; t.band_hi = c->band_hi; t.band_wmax = c->band_wmax;
+        t.band_scale = 0.17677669529663687f;
+        t.y_tm = tm_at(c, c->tO, x_off * seg, MC);
+        do_xgemm(c, t, n2, s);
+    }
+    {   // x2 = to_out(attn2) + x1   (conditional half only under guidance: its rows are [Bc, 2 Bc) of X2)
+        TGemmArgs t = mkx(g, tw(c, sw.t_out2, sw.tf_out2), MC, MC);
+        t.sa[0] = tm_at(c, c->tO, x_off * seg, MC); t.sld[0] = MC; t.sk[0] = MC;
+        t.bias = sw.out2.bias;
+        t.res_tm = tm_at(c, c->tX1, x_off * seg, MC);
+        t.y_tm = tm_at(c, c->tX2, kv_off * seg, MC);
+        do_xgemm(c, t, n2, s);
+    }
+    {   // GEGLU: proj(norm3(x2)) -> a * gelu(gate)   (attention.py:25-32)
+        TGemmArgs t = mkx(g, tw(c, sw.t_ff1, sw.tf_ff1), 2 * FFI, MC);
+        t.ra[0] = c->tX2; t.rmode = 2; t.rtaps = 1;
+        t.ln_gamma = sw.l3g; t.ln_beta = sw.l3b;
+        t.bias = sw.t_ff1_bias; t.geglu = 1;
+        t.yb = c->tF; t.y_bs = seg * FFI; t.ldy = FFI;
+        do_xgemm(c, t, g.Be, s);
+    }
+    bool split = false;
+    if (!last && c->bf16_mode) {   // round 4: as two rgemm launches over column ranges of the folded weight (see run_resblock_tm)
+        TGemmArgs t = mkx(g, sw.t_ffproj, MC, FFI);
+        t.sa[0] = c->tF; t.sld[0] = FFI; t.sk[0] = FFI; t.w_ld = FFI + MC;
+        t.res_tm = in.t; t.y_tm = c->tX1;
+        split = rgemm_supports(t, g.Be);
+    }
+    if (split) {
+        {   // (P F2) h + x_in -> tX1 (x1 is dead by now)
+            TGemmArgs t = mkx(g, sw.t_ffproj, MC, FFI);
+            t.sa[0] = c->tF; t.sld[0] = FFI; t.sk[0] = FFI; t.w_ld = FFI + MC; t.w_k0 = 0;
+            t.res_tm = in.t;
+            t.y_tm = c->tX1;
+            do_xgemm(c, t, g.Be, s);
+        }
+        {   // + P x2 + (P b2 + bp)
+            TGemmArgs t = mkx(g, sw.t_ffproj, MC, MC);
+            t.sa[0] = c->tX2; t.sld[0] = MC; t.sk[0] = MC; t.w_ld = FFI + MC; t.w_k0 = FFI;
+            t.bias = sw.ffproj.bias;
+            t.res_tm = c->tX1;
+            t.y_tm = out.t; t.stats = out.st;
+            do_xgemm(c, t, g.Be, s);
+        }
+        return;
+    }
+    {   // proj_out o ff.net.2 over [h ; x2] + x_in   (attention.py:193, 232-234)
+        TGemmArgs t = mkx(g, tw(c, sw.t_ffproj, sw.tf_ffproj), MC, FFI + MC);
+        t.sa[0] = c->tF; t.sld[0] = FFI; t.sk[0] = FFI;
+        t.sa[1] = c->tX2; t.sld[1] = MC; t.sk[1] = MC;
+        t.bias = sw.ffproj.bias;
+        t.res_tm = in.t;
+        if (last) { t.y_cm = out.p; t.cm_bs = g.hs; t.cm_pitch = g.Tp; t.stats = out.st; }
+        else { t.y_tm = out.t; t.stats = out.st; }
+        do_xgemm(c, t, g.Be, s);
+    }
+}
+
+// ---- round 3, bf16 mode at large batch when the token-major activations are off (tm_acts = 0, or beyond their 32-bit offsets): the HYBRID SpatialTransformer.  The ResBlocks and q/k/v keep round 2's kernels
+// (channel-major fp32 between them, prep_kernel + token-major GEMM), everything from the attention output on runs on round 3's
+// token-major-activation kernels, where they are faster in situ: attention writes token-major bf16, attn1.to_out / band / attn2.to_out /
+// GEGLU / folded proj_out are xgemm launches (no second preparation kernel: GEGLU applies norm3 itself), and the folded proj_out writes
+// channel-major fp32 + GroupNorm partials again for the next ResBlock.  The token-major copy of the block's input (the residual of
+// attn1.to_out and of proj_out) is a by-product of the q/k/v operand preparation.  8 launches per block instead of 9.
+void run_transformer_hybrid(said_ctx* c, const UGeo& g, const STW& sw, int blk, const ActBuf& in, const ActBuf& out, hipStream_t s, bool shared) {
+    const int n1 = shared ? g.Bc : g.Be;
+    const int n2 = g.Bc > 0 ? g.Bc : g.Be;
+    const int x_off = (g.Bc > 0 && !shared) ? g.Bc : 0;
+    const int kv_off = g.Bc > 0 ? g.Bc : 0;
+    const long long seg = tm_seg(g);
+    const int vt_rows = rup(g.T, 32);
+    {   // q, k, v on round 2's token-major GEMM; the preparation kernel also leaves the raw input token-major (in.t)
+        PrepArgs p = mkprep(g, in.p, 1, c->uPL, (long long)tg_rows(g) * MC, MC, 0);
+        prep_gn(p, g, in.st, 6, 1e-6f, sw.gn_g, sw.gn_b);
+        p.ln_gamma = sw.l1g; p.ln_beta = sw.l1b;
+        p.dst2 = in.t; p.dst2_bs = seg * MC; p.ldd2 = MC; p.coff2 = 0;
+        do_prep(c, p, g.Be, s);   // (all samples: the second half's rows are the residual of proj_out)
+        TGemmArgs t = mktg(g, c->uPL, MC, tw(c, sw.t_qkv, sw.tf_qkv), 3 * MC, MC);
+        t.qk = c->QK; t.vt = c->VT; t.v_bs = (long long)MC * g.Tp; t.qk_n = 2 * MC; t.head_dim = HD; t.rows = vt_rows; t.heads2 = 2 * HEADS; t.v_pitch = g.Tp;
+        do_tgemm(c, t, n1, s);
+    }
+    {   // softmax(q k^T * scale) v -> token-major   (attention.py:99-126)
+        AttnArgs a;
+        a.qk = c->QK; a.v = c->VT; a.o = static_cast<float*>(c->tO);
+        a.v_bstride = (long long)MC * g.Tp; a.o_bstride = seg; a.o_mode = c->bf16_mode ? 2 : 1;
+        a.pitch = g.Tp; a.T = g.T; a.heads = HEADS; a.rows = vt_rows; a.b0 = 0;
+        a.scale = 0.17677669529663687f;
+        do_attn(c, a, n1, HD, -4, s);
+    }
+    {   // x1 = to_out(attn) + GroupNorm(x_in); under guidance also x2 of the unconditional half = x1 + c2
+        TGemmArgs t = mkx(g, tw(c, sw.t_out1, sw.tf_out1), MC, MC);
+        t.sa[0] = c->tO; t.sld[0] = MC; t.sk[0] = MC;
+        t.bias = sw.out1.bias;
+        t.res_tm = in.t; t.res_gn = 1; t.res_part = in.st; t.res_gamma = sw.gn_g; t.res_beta = sw.gn_b; t.res_eps = 1e-6f; t.gn_cpg = 6;
+        t.y_tm = c->tX1;
+        if (g.Bc > 0) { t.y2_tm = c->tX2; t.y2_row_off = 0; t.y2_add = c->c2[blk]; }
+        do_xgemm(c, t, n1, s);
+    }
+    {   // attn2: q = to_q(norm2(x1)); banded softmax over the precomputed audio K/V
+        TGemmArgs t = mkx(g, tw(c, sw.t_q2, sw.tf_q2), MC, MC);
+        t.ra[0] = tm_at(c, c->tX1, x_off * seg, MC); t.rmode = 2; t.rtaps = 1;
+        t.ln_gamma = sw.l2g; t.ln_beta = sw.l2b;
+        const long long kvbs = (long long)NST * 2 * MC * g.Sp;
+        t.band_k = c->KV + (long long)(blk * 2 * MC) * g.Sp + (long long)kv_off * kvbs;
+        t.band_v = c->KV + (long long)(blk * 2 * MC + MC) * g.Sp + (long long)kv_off * kvbs;
+        t.band_kv_bs = kvbs; t.band_kv_pitch = g.Sp; t.band_lo = c->band_lo; t.band_hi = c->band_hi; t.band_wmax = c->band_wmax;
+        t.band_scale = 0.17677669529663687f;
+        t.y_tm = tm_at(c, c->tO, x_off * seg, MC);
+        do_xgemm(c, t, n2, s);
+    }
+    {   // x2 = to_out(attn2) + x1   (conditional half only under guidance: its rows are [Bc, 2 Bc) of X2)
+        TGemmArgs t = mkx(g, tw(c, sw.t_out2, sw.tf_out2), MC, MC);
+        t.sa[0] = tm_at(c, c->tO, x_off * seg, MC); t.sld[0] = MC; t.sk[0] = MC;
+        t.bias = sw.out2.bias;
+        t.res_tm = tm_at(c, c->tX1, x_off * seg, MC);
+        t.y_tm = tm_at(c, c->tX2, kv_off * seg, MC);
+        do_xgemm(c, t, n2, s);
+    }
+    {   // GEGLU: proj(norm3(x2)) -> a * gelu(gate): the GEMM normalises its operand itself
+        TGemmArgs t = mkx(g, tw(c, sw.t_ff1, sw.tf_ff1), 2 * FFI, MC);
+        t.ra[0] = c->tX2; t.rmode = 2; t.rtaps = 1;
+        t.ln_gamma = sw.l3g; t.ln_beta = sw.l3b;
+        t.bias = sw.t_ff1_bias; t.geglu = 1;
+        t.yb = c->tF; t.y_bs = seg * FFI; t.ldy = FFI;
+        do_xgemm(c, t, g.Be, s);
+    }
+    {   // proj_out o ff.net.2 over [h ; x2] + x_in -> channel-major fp32 + GroupNorm partials for the next ResBlock
+        TGemmArgs t = mkx(g, tw(c, sw.t_ffproj, sw.tf_ffproj), MC, FFI + MC);
+        t.sa[0] = c->tF; t.sld[0] = FFI; t.sk[0] = FFI;
+        t.sa[1] = c->tX2; t.sld[1] = MC; t.sk[1] = MC;
+        t.bias = sw.ffproj.bias;
+        t.res_tm = in.t;
+        t.y_cm = out.p; t.cm_bs = g.hs; t.cm_pitch = g.Tp; t.stats = out.st;
+        do_xgemm(c, t, g.Be, s);
+    }
+}
+
+// shared: guidance-shared prefix — only the first g.Bc samples are computed, and the result is ALSO written into the
+// conditional half's slots (values only; its statistics are consumed by kernels that run on the first half alone)
+void run_resblock(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, const ActBuf& in0, const ActBuf* in1, const ActBuf& out, hipStream_t s,
+                  bool shared = false) {
+    const int cpg = rw.cin / 32;
+    const int nb = shared ? g.Bc : g.Be;
+    const long long tt = (long long)nb * ((g.T + 31) / 32);
+    if (use_tg(c, g, nb)) {
+        const long long T2 = tg_rows(g);
+        // fp32 mode: the operands reach fgemm_kernel already split (packed h | l pairs: prep_kernel's pack mode + the packed weight copies)
+        const int pk = (!c->bf16_mode && sp_on(c, c->gemm_split) && c->gemm_presplit != 0 && rw.tp_conv1 && rw.tp_conv2) ? 1 : 0;
+        {   // in_layers: GN -> SiLU -> conv3 + emb term   (openaimodel.py:205-225)
+            PrepArgs p = mkprep(g, in0.p, 0, c->uPA, T2 * rw.cin, rw.cin, 0);
+            p.pack = pk;
+            prep_gn(p, g, in0.st, cpg, 1e-5f, rw.g1, rw.b1);
+            if (rw.has_skip) { p.dst2 = c->uPB; p.dst2_bs = T2 * 2 * MC; p.ldd2 = 2 * MC; p.coff2 = 0; }   // raw copy for the 1x1 skip conv
+            do_prep(c, p, nb, s);
+            if (in1) {
+                PrepArgs q = mkprep(g, in1->p, 0, c->uPA, T2 * rw.cin, rw.cin, MC);
+                q.pack = pk;
+                prep_gn(q, g, in1->st, cpg, 1e-5f, rw.g1 + MC, rw.b1 + MC);
+                if (rw.has_skip) { q.dst2 = c->uPB; q.dst2_bs = T2 * 2 * MC; q.ldd2 = 2 * MC; q.coff2 = MC; }
+                do_prep(c, q, nb, s);
+            }
+            TGemmArgs t = mktg(g, c->uPA, rw.cin, pk ? rw.tp_conv1 : tw(c, rw.t_conv1, rw.tf_conv1), MC, 3 * rw.cin);
+            t.f32_packed = pk;
+            t.bias = rw.conv1.bias;
+            t.emb = c->EO + (long long)rb_index * MC * c->maxNp; t.emb_pitch = c->maxNp; t.step_ptr = g.step_ptr; t.emb_b_stride = g.emb_b_stride;
+            tg_cm_out(t, g, c->M);
+            do_tgemm(c, t, nb, s);
+        }
+        {   // out_layers: GN -> SiLU -> conv3 ; + skip(x)   (openaimodel.py:226-227)
+            PrepArgs p = mkprep(g, c->M.p, 0, c->uPA, T2 * MC, MC, 0);
+            p.pack = pk;
+            prep_gn(p, g, c->M.st, 6, 1e-5f, rw.g2, rw.b2);
+            do_prep(c, p, nb, s);
+            TGemmArgs t = mktg(g, c->uPA, MC, pk ? rw.tp_conv2 : tw(c, rw.t_conv2, rw.tf_conv2), MC, 3 * MC);
+            t.f32_packed = pk;
+            if (rw.has_skip) {   // 1x1 conv over the concatenated raw input as a second K segment
+                // (the raw copies of the two inputs were written into uPB by the in_layers operand preparation above)
+                t.a2 = c->uPB; t.a2_bs = 0; t.lda2 = 2 * MC; t.K1 = 3 * MC; t.K = 5 * MC;
+                t.bias = rw.bias2;
+            } else {
+                t.bias = rw.conv2.bias;
+                t.res_cm = in0.p; t.res_cm_bs = g.hs;
+            }
+            tg_cm_out(t, g, out);
+            if (shared) { t.y2_cm = out.p + (long long)g.Bc * g.hs; t.y2_bs = g.hs; }
+            do_tgemm(c, t, nb, s);
+        }
+        return;
+    }
+    {   // in_layers: GN -> SiLU -> conv3 ; + emb_layers(emb)   (openaimodel.py:205-225)
+        GemmArgs a = mkargs(g.T, MC);
+        a.nseg = in1 ? 2 : 1;
+        a.seg[0] = with_pw(mkseg(in0.p, g.hs, g.Tp, MC, 3, 1, 1, g.T, XF_GN_SILU, rw.conv1.w[0]), rw.conv1, 0);
+        seg_gn(a.seg[0], in0.st, g.sts, cpg, g.np, 1e-5f, rw.g1, rw.b1);
+        if (in1) {
+            a.seg[1] = with_pw(mkseg(in1->p, g.hs, g.Tp, MC, 3, 1, 1, g.T, XF_GN_SILU, rw.conv1.w[1]), rw.conv1, 1);
+            seg_gn(a.seg[1], in1->st, g.sts, cpg, g.np, 1e-5f, rw.g1 + MC, rw.b1 + MC);
+        }
+        a.bias = rw.conv1.bias;
+        a.emb = c->EO + (long long)rb_index * MC * c->maxNp; a.emb_pitch = c->maxNp; a.step_ptr = g.step_ptr; a.emb_b_stride = g.emb_b_stride;
+        a.y = c->M.p; a.y_bstride = g.hs; a.y_pitch = g.Tp;
+        a.stats_out = c->M.st; a.stats_bstride = g.sts;
+        const LaunchCfg lc = pick_unet(tt);
+        do_gemm(c, a, EPI_STORE, nb, lc.NB, lc.KS, s);
+    }
+    {   // out_layers: GN -> SiLU -> conv3 ; + skip(x)   (openaimodel.py:226-227)
+        GemmArgs a = mkargs(g.T, MC);
+        a.nseg = 1;
+        a.seg[0] = with_pw(mkseg(c->M.p, g.hs, g.Tp, MC, 3, 1, 1, g.T, XF_GN_SILU, rw.conv2.w[0]), rw.conv2, 0);
+        seg_gn(a.seg[0], c->M.st, g.sts, 6, g.np, 1e-5f, rw.g2, rw.b2);
+        if (rw.has_skip) {  // 1x1 conv over the concatenated input folded in as two extra K segments
+            a.seg[1] = with_pw(mkseg(in0.p, g.hs, g.Tp, MC, 1, 0, 1, g.T, XF_NONE, rw.skip.w[0]), rw.skip, 0);
+            a.seg[2] = with_pw(mkseg(in1->p, g.hs, g.Tp, MC, 1, 0, 1, g.T, XF_NONE, rw.skip.w[1]), rw.skip, 1);
+            a.nseg = 3;
+            a.bias = rw.bias2;
+        } else {
+            a.bias = rw.conv2.bias;
+            a.res_kind = RES_PLAIN; a.res = in0.p; a.res_bstride = g.hs; a.res_pitch = g.Tp;
+        }
+        a.y = out.p; a.y_bstride = g.hs; a.y_pitch = g.Tp;
+        a.stats_out = out.st; a.stats_bstride = g.sts;
+        if (shared) { a.y2 = out.p + (long long)g.Bc * g.hs; a.y2_bstride = g.hs; a.y2_add = nullptr; }
+        const LaunchCfg lc = pick_unet(tt);
+        do_gemm(c, a, EPI_STORE, nb, lc.NB, lc.KS, s);
+    }
+}
+
+// shared: guidance-shared prefix (first transformer under classifier-free guidance): self-attention and everything
+// before it run once per clip on samples [0, g.Bc).  With g.Bc > 0 the cross-attention (q projection, band softmax,
+// to_out) runs on the conditional half only — the unconditional half attends to one repeated key/value, so its
+// attn2 output is the per-channel constant c2[blk] and attn1's to_out emits its x2 = x1 + c2 directly.
+void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const ActBuf& in, const ActBuf& out, hipStream_t s,
+                     bool shared = false) {
+    const int n1 = shared ? g.Bc : g.Be;          // samples through self-attention
+    const int n2 = g.Bc > 0 ? g.Bc : g.Be;        // samples through cross-attention
+    // first sample of the cross-attention range in the activations (X1, O): the conditional half, unless the prefix is
+    // shared (then X1 exists once per clip, in slots [0, Bc)); its K/V are always the conditional half's
+    const int x_off = (g.Bc > 0 && !shared) ? g.Bc : 0;
+    const int kv_off = g.Bc > 0 ? g.Bc : 0;
+    const long long tt1 = (long long)n1 * ((g.T + 31) / 32), tt2 = (long long)n2 * ((g.T + 31) / 32);
+    const long long tt = (long long)g.Be * ((g.T + 31) / 32);
+    const int vt_rows = rup(g.T, 32);
+    const long long obs = 2LL * MC * g.Tp;   // batch stride of O (shared with QK so attention uses one stride)
+    const bool tg = use_tg(c, g, n1);
+    if (c->bf16_mode && tg && use_tg(c, g, g.Be)) { run_transformer_hybrid(c, g, sw, blk, in, out, s, shared); return; }
+    // fp32 mode: attn1.to_out on the token-major fp32 GEMM too (the attention kernel writes its operand token-major into the free q/k/v
+    // operand buffer; the GroupNorm'ed residual uses the coefficients the q/k/v preparation finalised): 59 -> ~30 us per launch at Be = 64
+    // fp32 mode: everything behind the self-attention as ONE launch (stchain.hip) — at small batches beside the channel-major GEMMs, at large ones
+    // beside the token-major GEMMs' q / k / v (the attention kernel then writes channel-major, as the small-batch schedule has it)
+    const bool chain = !c->bf16_mode && sp_on(c, c->st_chain) && sw.chain_w && sw.chain_vec && c->band_chain_ok && c->kvt_S == g.S && !c->kvt_bf16 &&
+                       g.S == c->band_S && g.T == c->band_T;
+    const bool out1_tm = tg && !chain && !c->bf16_mode && tt1 * HEADS >= 2048 && sw.tf_out1;
+    bool presplit = false;   // k and v stored as packed split-fp16 pairs for attn_kernel<PM = 3> (see below)
+    bool coef_ready = false; // the q/k/v GEMM left the block input's GroupNorm coefficients in gn_coef (small-batch ugemm_kernel only)
+    if (tg) {   // q, k, v on the bf16 token-major GEMM: operand = LayerNorm(GroupNorm(x)) prepared once
+        const int pk = (!c->bf16_mode && sp_on(c, c->gemm_split) && c->gemm_presplit != 0 && sw.tp_qkv) ? 1 : 0;   // operands arrive split (see run_resblock)
+        PrepArgs p = mkprep(g, in.p, 1, c->uPL, (long long)tg_rows(g) * MC, MC, 0);
+        p.pack = pk;
+        prep_gn(p, g, in.st, 6, 1e-6f, sw.gn_g, sw.gn_b);
+        p.ln_gamma = sw.l1g; p.ln_beta = sw.l1b;
+        if ((out1_tm || (chain && c->chain_coef != 0)) && p.part) { p.coef_out = c->gn_coef; p.coef_out_bs = 2 * MC; coef_ready = chain; }   // (the fp32 fused tail reads them too: round 6)
+        do_prep(c, p, n1, s);
+        TGemmArgs t = mktg(g, c->uPL, MC, pk ? sw.tp_qkv : tw(c, sw.t_qkv, sw.tf_qkv), 3 * MC, MC);
+        t.f32_packed = pk;
+        t.qk = c->QK; t.vt = c->VT; t.v_bs = (long long)MC * g.Tp; t.qk_n = 2 * MC; t.head_dim = HD; t.rows = vt_rows; t.heads2 = 2 * HEADS; t.v_pitch = g.Tp;
+        // round 6: this GEMM's epilogue stores k and v pre-split too (as ugemm_kernel's does at small batch), for every attention shape that unpacks them: the
+        // key-split ones and the four-query-tile one of large batches (each wave of which used to split all of K and V for itself)
+        presplit = !c->bf16_mode && sp_on(c, c->attn_split) && c->attn_presplit != 0 && sp_on(c, c->gemm_split) &&
+                   !c->clk_on;   // (then the attention shape below is -4, 8 or 4: all unpack)
+        t.kv_pack = presplit ? 1 : 0;
+        do_tgemm(c, t, n1, s);
+    } else
+    {   // x = norm(x) (GroupNorm eps 1e-6); q,k,v = to_{q,k,v}(norm1(x))   (attention.py:227, 168, 93-97)
+        GemmArgs a = mkargs(g.T, 3 * MC);
+        a.nseg = 1;
+        a.seg[0] = with_pw(mkseg(in.p, g.hs, g.Tp, MC, 1, 0, 1, g.T, XF_GN_LN, sw.qkv.w[0]), sw.qkv, 0);
+        seg_gn(a.seg[0], in.st, g.sts, 6, g.np, 1e-6f, sw.gn_g, sw.gn_b);
+        a.seg[0].ln_gamma = sw.l1g; a.seg[0].ln_beta = sw.l1b; a.seg[0].ln_eps = 1e-5f;
+        // q and k tiles (0..11) token-major into QK [Be][2*heads][rows][32]; v tiles channel-major into VT [Be][192][Tp]
+        // (y is biased so that output channel n = 384 + c lands on row c)
+        a.tm_tiles = 2 * MC / 32;
+        a.vt = c->QK; a.vt_heads = 2 * HEADS; a.vt_dim = HD; a.vt_rows = vt_rows;
+        a.y = c->VT - (long long)a.tm_tiles * 32 * g.Tp; a.y_bstride = (long long)MC * g.Tp; a.y_pitch = g.Tp;
+        // tiles per workgroup: the largest shape that still gives every CU a workgroup in ONE round (at Be=2, T=600:
+        // NB=3 -> 228 workgroups, 27.5 -> 13.8 us per launch against NB=1's 684 workgroups in 2.7 rounds)
+        int qkv_nb = tt1 * 6 >= 192 ? 3 : (tt1 * 9 >= 192 ? 2 : 1);
+        if (tt1 * 18 <= 1024) {   // pick_unet's busiest-CU model over the 18 column tiles (19 tiles: NB 1 -> 2, 342 -> 171 workgroups)
+            double cost = 1e30;
+            for (int nb = 1; nb <= 3; ++nb) {
+                const double k = (double)((tt1 * (18 / nb) + 255) / 256) * (0.45 + nb);
+                if (k < cost - 1e-9) { cost = k; qkv_nb = nb; }
+            }
+        }
+        const LaunchCfg lc{qkv_nb, 8};
+        // k and v pre-split for the key-split attention shapes (same rule as below), when this GEMM runs on ugemm_kernel (the only epilogue that packs)
+        const bool key_split = tt1 * HEADS < 2048;
+        presplit = !c->bf16_mode && sp_on(c, c->attn_split) && c->attn_presplit != 0 && key_split && !c->clk_on &&
+                   (ugemm_supports(a, EPI_QKV, lc.NB, lc.KS, 2) || ugemm_supports(a, EPI_QKV, lc.NB, lc.KS));
+        a.kv_split = presplit ? 1 : 0;
+        // round 6: this GEMM finalises the block input's GroupNorm coefficients anyway (its operand is LayerNorm(GroupNorm(x))): the first workgroup of every sample
+        // leaves them for stchain_kernel, whose GroupNorm'ed residual then needs 2 loads per wave instead of 23 and no finalisation in front of its first barrier
+        if (chain && c->chain_coef != 0 && c->gn_coef) { a.gn_coef_out = c->gn_coef; a.gn_coef_bs = 2 * MC; }
+        coef_ready = do_gemm(c, a, EPI_QKV, n1, lc.NB, lc.KS, s) && a.gn_coef_out != nullptr;
+    }
+    bool out1_done = false;
+    {   // softmax(q k^T * scale) v   (attention.py:99-126)
+        AttnArgs a;
+        a.qk = c->QK; a.v = c->VT; a.o = c->O;
+        a.v_bstride = (long long)MC * g.Tp; a.o_bstride = obs;
+        a.pitch = g.Tp; a.T = g.T; a.heads = HEADS; a.rows = vt_rows; a.b0 = 0;
+        a.scale = 0.17677669529663687f;  // 32 ** -0.5
+        // waves per workgroup = ways the key tiles are split: 8 only pays while a wave would otherwise hold a single
+        // tile (T <= 256); from there 4 waves with ~5 tiles each merge half as many partial states (B=1: -0.5 % per step)
+        // large batches: four query tiles per workgroup sharing each K / V tile through the CU's L1 (-4), see attn.hip
+        int ks_run = tt1 * HEADS >= 2048 ? -4 : (g.T <= 256 ? 8 : 4);
+        if (out1_tm && ks_run == -4) { a.o = static_cast<float*>(c->uPL); a.o_bstride = tg_rows(g); a.o_mode = 1; }
+        // long sequences at small batch (configs[4]): three query tiles per wave share every K / V fragment (attn2q.hip; bit-identical) where a third of the
+        // launch is most of ONE round of workgroups (101 KB of LDS, 264 registers: one workgroup per CU)
+        if (presplit && ks_run == 4 && a.o_mode == 0 && (c->attn_2q > 0 || (c->attn_2q < 0 && tt1 * HEADS >= 512 && (long long)n1 * HEADS * ((((g.T + 31) / 32) + 2) / 3) <= 256))) ks_run = 34;   // (one round of one workgroup per CU)
+        do_attn(c, a, n1, HD, ks_run, s, presplit && (ks_run == 4 || ks_run == 8 || ks_run == -4 || ks_run == 34));
+        out1_done = a.o_mode == 1;
+    }
+    if (chain && !out1_done) {
+        ChainArgs ca;
+        memset(&ca, 0, sizeof ca);
+        ca.wstream = sw.chain_w; ca.vec = sw.chain_vec;
+        ca.xin_part = in.st; ca.part_bs = g.sts; ca.gn_gamma = sw.gn_g; ca.gn_beta = sw.gn_b;
+        ca.kvt = c->KVT; ca.kvt_bs = (long long)g.S * (NST * 2 * MC); ca.lo = c->band_lo; ca.hi = c->band_hi;
+        ca.y = out.p; ca.y_bs = g.hs; ca.stats_out = out.st; ca.stats_bs = g.sts;
+        ca.S = g.S; ca.np = g.np; ca.koff = blk * 2 * MC; ca.wmax = c->band_wmax; ca.scale = 0.17677669529663687f;
+        // small launches: three workgroups per token tile, each streaming a third of the GEGLU / folded proj_out weights (38 workgroups on 256 CUs were bound by
+        // one CU's L2 port each: 2.36 MB per workgroup) — while the launch still is one round of the chip
+        ca.slices = 1;
+        if (c->st_chain_slices != 1 && sw.chain_w3 && sw.chain_w2) {
+            if (tt <= CHAIN3_MAX_TILES && c->st_chain_slices != 2) ca.slices = 3;
+            else if (tt <= CHAIN2_MAX_TILES) ca.slices = 2;
+        }
+        if (ca.slices > 1) { ca.wstream = ca.slices == 3 ? sw.chain_w3 : sw.chain_w2; ca.part = c->chain_part; ca.ticket = c->chain_ticket; }
+        // the fp32 kernels read the block input's GroupNorm coefficients (round 6): left by the q/k/v GEMM (ugemm_kernel) or its operand preparation (prep_kernel), else made here
+        if (!coef_ready && dbg_go_peek(c)) launch_gn_coef(in.st, g.sts, 6, g.np, g.T, 1e-6f, sw.gn_g, sw.gn_b, c->gn_coef, 2 * MC, n1, s);
+        ca.gn_coef = c->gn_coef; ca.coef_bs = 2 * MC;
+        if (c->clk_on && c->dbg_count < 64) ca.clk = c->clk_dev + (long long)c->dbg_count * 128;
+        if (c->log_on) {
+            const double w = 4.0 * ((double)3 * MC * MC + 2.0 * FFI * MC + (double)(FFI + MC) * MC);
+            const double io = 4.0 * MC * g.T * ((double)n1 * 2 + g.Be) + 4.0 * 2 * MC * g.T * (double)n2;
+            const double fl = 2.0 * g.T * ((double)n1 * MC * MC + (double)n2 * 2 * MC * MC + (double)g.Be * (2.0 * FFI * MC + (double)(FFI + MC) * MC)) + 4.0 * n2 * MC * g.T * c->band_wmax;
+            c->stage_log.push_back({10, EPI_STORE, 6, 8, w + io, fl});
+        }
+        if (dbg_go(c)) {
+            if (trace_on()) { fprintf(stderr, "[said] stchain #%d T=%d samples=%d shared=%d\n", c->dbg_count - 1, g.T, g.Be, (int)shared); fflush(stderr); }
+            launch_stchain(ca, c->O, in.p, g.T, g.Tp, obs, g.hs, shared ? g.Bc : 0, g.Bc > 0 ? g.Bc : 0, g.Be, s, false);
+            ++c->n_stchain;
+            if (trace_on()) { hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[said]   -> %s\n", hipGetErrorString(e)); fflush(stderr); }
+        }
+        return;
+    }
+    if (out1_done) {   // x1 = to_out(attn) + GroupNorm(x_in) on fgemm_kernel; under guidance also x2 of the unconditional half = x1 + c2
+        TGemmArgs t = mktg(g, c->uPL, MC, sw.tf_out1, MC, MC);
+        t.bias = sw.out1.bias;
+        t.res_cm = in.p; t.res_cm_bs = g.hs; t.res_cm_coef = c->gn_coef; t.res_cm_coef_bs = 2 * MC;
+        t.y_cm = c->X1; t.cm_bs = g.hs; t.cm_pitch = g.Tp;
+        if (g.Bc > 0) { t.y2_cm = c->X2; t.y2_bs = g.hs; t.y2_add_cm = c->c2[blk]; }
+        do_tgemm(c, t, n1, s);
+    } else
+    {   // x1 = to_out(attn) + x, with x = GroupNorm(in) recomputed on the fly   (attention.py:127, 168)
+        GemmArgs a = mkargs(g.T, MC);
+        a.nseg = 1;
+        a.seg[0] = with_pw(mkseg(c->O, obs, g.Tp, MC, 1, 0, 1, g.T, XF_NONE, sw.out1.w[0]), sw.out1, 0);
+        a.bias = sw.out1.bias;
+        a.res_kind = RES_GN; a.res = in.p; a.res_bstride = g.hs; a.res_pitch = g.Tp;
+        a.res_gn_part = in.st; a.res_gn_part_bstride = g.sts; a.res_gn_cpg = 6; a.res_gn_nparts = g.np; a.res_gn_eps = 1e-6f;
+        a.res_gn_gamma = sw.gn_g; a.res_gn_beta = sw.gn_b;
+        a.y = c->X1; a.y_bstride = g.hs; a.y_pitch = g.Tp;
+        if (g.Bc > 0) {   // x2 of the unconditional half: x1 + const (written for every sample of this launch; the
+                          // conditional slots — when this launch covers them — are overwritten by attn2's to_out below)
+            a.y2 = c->X2; a.y2_bstride = g.hs; a.y2_add = c->c2[blk];
+        }
+        do_gemm(c, a, EPI_STORE, n1, 1, 8, s);   // the GroupNorm'ed-residual variant exists for NB = 1
+    }
+    {   // attn2: q = to_q(norm2(x1)); banded softmax over the precomputed audio K/V   (attention.py:170-191)
+        GemmArgs a = mkargs(g.T, MC);
+        a.nseg = 1;
+        a.seg[0] = with_pw(mkseg(c->X1 + (long long)x_off * g.hs, g.hs, g.Tp, MC, 1, 0, 1, g.T, XF_LN, sw.q2.w[0]), sw.q2, 0);
+        a.seg[0].ln_gamma = sw.l2g; a.seg[0].ln_beta = sw.l2b; a.seg[0].ln_eps = 1e-5f;
+        a.y = c->O + (long long)x_off * obs; a.y_bstride = obs; a.y_pitch = g.Tp;
+        const long long kvbs = (long long)NST * 2 * MC * g.Sp;
+        a.band.k = c->KV + (long long)(blk * 2 * MC) * g.Sp + (long long)kv_off * kvbs;
+        a.band.v = c->KV + (long long)(blk * 2 * MC + MC) * g.Sp + (long long)kv_off * kvbs;
+        a.band.kv_bstride = kvbs; a.band.kv_pitch = g.Sp;
+        a.band.lo = c->band_lo; a.band.hi = c->band_hi; a.band.wmax = c->band_wmax; a.band.scale = 0.17677669529663687f;
+        if (c->band_wmax > 8) {   // windows wider than the fused epilogue's eight keys (S >> T through SAID.forward): plain q projection, then the
+                                  // generic band kernel in place (misc.hip; never on SAID.inference's path)
+            const BandArgs bd = a.band;
+            memset(&a.band, 0, sizeof a.band);
+            do_gemm(c, a, EPI_STORE, n2, 1, 8, s);
+            if (c->log_on) c->stage_log.push_back({5, -2, 0, 0, 0.0, 0.0});
+            if (dbg_go(c)) launch_band_wide(a.y, obs, g.Tp, bd.k, bd.v, bd.kv_bstride, bd.kv_pitch, bd.lo, bd.hi, g.T, HEADS, n2, bd.scale, s);
+        } else
+        do_gemm(c, a, EPI_BAND, n2, 1, 8, s);
+    }
+    {   // x2 = to_out(attn2) + x1   (conditional half only under guidance: its slots are [Bc, 2 Bc) of X2)
+        GemmArgs a = mkargs(g.T, MC);
+        a.nseg = 1;
+        a.seg[0] = with_pw(mkseg(c->O + (long long)x_off * obs, obs, g.Tp, MC, 1, 0, 1, g.T, XF_NONE, sw.out2.w[0]), sw.out2, 0);
+        a.bias = sw.out2.bias;
+        a.res_kind = RES_PLAIN; a.res = c->X1 + (long long)x_off * g.hs; a.res_bstride = g.hs; a.res_pitch = g.Tp;
+        a.y = c->X2 + (long long)kv_off * g.hs; a.y_bstride = g.hs; a.y_pitch = g.Tp;
+        const LaunchCfg lc = pick_unet(tt2);
+        do_gemm(c, a, EPI_STORE, n2, lc.NB, lc.KS, s);
+    }
+    if (use_tg(c, g, g.Be)) {
+        {   // GEGLU: operand norm3(x2) (and raw x2 for the folded proj_out), value/gate pairs multiplied in the epilogue
+            const long long P = tg_rows(g);
+            PrepArgs p = mkprep(g, c->X2, 2, c->uPL, P * MC, MC, 0);
+            p.ln_gamma = sw.l3g; p.ln_beta = sw.l3b;
+            p.dst2 = c->uPX; p.dst2_bs = P * MC; p.ldd2 = MC; p.coff2 = 0;
+            do_prep(c, p, g.Be, s);
+            TGemmArgs t = mktg(g, c->uPL, MC, tw(c, sw.t_ff1, sw.tf_ff1), 2 * FFI, MC);
+            t.bias = sw.t_ff1_bias; t.geglu = 1;
+            t.yb = c->uPH; t.y_bs = P * FFI; t.ldy = FFI;
+            do_tgemm(c, t, g.Be, s);
+        }
+        {   // proj_out o ff.net.2 over [h ; x2] + x_in, channel-major result + GroupNorm partials
+            TGemmArgs t = mktg(g, c->uPH, FFI, tw(c, sw.t_ffproj, sw.tf_ffproj), MC, FFI + MC);
+            t.a2 = c->uPX; t.a2_bs = 0; t.lda2 = MC; t.K1 = FFI;
+            t.bias = sw.ffproj.bias;
+            t.res_cm = in.p; t.res_cm_bs = g.hs;
+            tg_cm_out(t, g, out);
+            do_tgemm(c, t, g.Be, s);
+        }
+        return;
+    }
+    {   // GEGLU: proj(norm3(x2)) -> a * gelu(gate)   (attention.py:25-32)
+        GemmArgs a = mkargs(g.T, FFI);
+        a.nseg = 1;
+        a.seg[0] = with_pw(mkseg(c->X2, g.hs, g.Tp, MC, 1, 0, 1, g.T, XF_LN, sw.ff1.w[0]), sw.ff1, 0);
+        a.seg[0].ln_gamma = sw.l3g; a.seg[0].ln_beta = sw.l3b; a.seg[0].ln_eps = 1e-5f;
+        a.bias = sw.ff1.bias; a.geglu_gate_tiles = FFI / 32;
+        a.y = c->F; a.y_bstride = (long long)FFI * g.Tp; a.y_pitch = g.Tp;
+        const int geglu_nb = tt * 6 >= 192 ? 4 : (tt * 12 >= 192 ? 2 : 1);   // one round of workgroups, as for qkv
+        do_gemm(c, a, EPI_GEGLU, g.Be, geglu_nb, 8, s);
+    }
+    {
+        // x3 = net.2(h) + x2 and out = proj_out(x3) + x_in as ONE GEMM over the K segments [h ; x2] with the host-folded
+        // weights (P F2 | P) — both maps are per-token linear, so nothing but rounding order changes
+        GemmArgs a = mkargs(g.T, MC);
+        a.nseg = 2;
+        a.seg[0] = with_pw(mkseg(c->F, (long long)FFI * g.Tp, g.Tp, FFI, 1, 0, 1, g.T, XF_NONE, sw.ffproj.w[0]), sw.ffproj, 0);
+        a.seg[1] = with_pw(mkseg(c->X2, g.hs, g.Tp, MC, 1, 0, 1, g.T, XF_NONE, sw.ffproj.w[1]), sw.ffproj, 1);
+        a.bias = sw.ffproj.bias;
+        a.res_kind = RES_PLAIN; a.res = in.p; a.res_bstride = g.hs; a.res_pitch = g.Tp;
+        a.y = out.p; a.y_bstride = g.hs; a.y_pitch = g.Tp;
+        a.stats_out = out.st; a.stats_bstride = g.sts;
+        const LaunchCfg lc = pick_unet(tt);
+        do_gemm(c, a, EPI_STORE, g.Be, lc.NB, lc.KS, s);
+    }
+}
+
+}  // namespace
+
+// UNetModel.forward (openaimodel.py:677-709): x_cm (latents) -> eps_cm.  Needs KV, band tables and EO ready.
+void run_unet(said_ctx* c, const UGeo& g, hipStream_t s) {
+    const long long tt = (long long)g.Be * ((g.T + 31) / 32);
+    const int in_copies = (g.B_lat > 0 && g.Be % g.B_lat == 0) ? g.Be / g.B_lat : 0;   // samples sharing one clip's latents
+    bool conv_in_tm = false;
+    if (in_copies >= 1 && c->conv_in.w4[0] && !c->clk_on &&
+        conv_in_supports(c->cin, MC, c->conv_in.taps, g.T, g.Tp, in_copies)) {
+        // input_blocks.0: Conv1d(32 -> 192, k3), computed once per clip (conv_in.hip)
+        // (large batches in bf16 mode: straight into the token-major bf16 layout the persistent GEMMs read — no channel-major copy, no transposition)
+        conv_in_tm = c->bf16_mode && use_tm(c, g) && tm_seg(g) <= 0xffff;
+        if (dbg_go(c)) {
+            if (conv_in_tm) launch_conv_in_tm(c->x_cm, c->conv_in.w4[0], c->conv_in.bias, c->H0.t, tm_seg(g), c->H0.st, g.step_inc, g.B_lat, in_copies, g.T, g.Tp, s);
+            else launch_conv_in(c->x_cm, c->conv_in.w4[0], c->conv_in.bias, c->H0.p, c->H0.st, g.step_inc, g.B_lat, in_copies, g.T, g.Tp, MC, s);
+        }
+        if (c->log_on)
+            c->stage_log.push_back({11 /* conv_in_kernel */, EPI_STORE, 1, 4, 4.0 * ((double)MC * c->cin * 3 + (double)g.B_lat * c->cin * g.T + (double)g.Be * MC * g.T),
+                                    2.0 * g.B_lat * MC * c->cin * 3 * g.T});
+    } else {   // input_blocks.0: Conv1d(32 -> 192, k3)
+        GemmArgs a = mkargs(g.T, MC);
+        a.nseg = 1;
+        a.seg[0] = with_pw(mkseg(c->x_cm, (long long)c->cin * g.Tp, g.Tp, c->cin, 3, 1, 1, g.T, XF_NONE, c->conv_in.w[0]), c->conv_in, 0);
+        a.seg[0].b_mod = g.B_lat;
+        a.step_inc = g.step_inc;   // the loop's device step counter is advanced by the first kernel of the step
+        a.bias = c->conv_in.bias;
+        a.y = c->H0.p; a.y_bstride = g.hs; a.y_pitch = g.Tp; a.stats_out = c->H0.st; a.stats_bstride = g.sts;
+        const LaunchCfg lc = pick_unet(tt);
+        do_gemm(c, a, EPI_STORE, g.Be, lc.NB, lc.KS, s);
+    }
+    const bool sh = g.Bc > 0;   // guidance-shared prefix: the two halves first differ at input_blocks.1.1's cross-attention
+    // round 4: the loop's last kernel reads the token-major bf16 hidden state itself (out_sched.hip: out_sched_tm_kernel)
+    OutSchedArgs osa_tm;
+    bool out_tm = false;
+    if (g.out_sched && c->out_tm != 0 && c->bf16_mode && use_tm(c, g) && c->bw_out) {
+        osa_tm = *g.out_sched;
+        osa_tm.x_tm = c->P.t; osa_tm.wb = c->bw_out; osa_tm.seg = tm_seg(g);
+        out_tm = out_sched_tm_supports(osa_tm);
+    }
+    if (use_tm(c, g)) {
+        if (!conv_in_tm) {   // conv_in's result (channel-major fp32 + GroupNorm partials) -> token-major, raw
+            PrepArgs p = mkprep(g, c->H0.p, 3, c->H0.t, (long long)tm_seg(g) * MC, MC, 0);
+            do_prep(c, p, g.Be, s);
+        }
+        run_resblock_tm(c, g, c->res[0], 0, c->H0, nullptr, c->P, s, sh);            // input_blocks.1.0
+        run_transformer_tm(c, g, c->st[0], 0, c->P, c->H1, s, sh, false);           // input_blocks.1.1
+        run_resblock_tm(c, g, c->res[1], 1, c->H1, nullptr, c->P, s, false);         // middle_block.0
+        run_transformer_tm(c, g, c->st[1], 1, c->P, c->Q, s, false, false);         // middle_block.1
+        run_resblock_tm(c, g, c->res[2], 2, c->Q, nullptr, c->P, s, false);          // middle_block.2
+        run_resblock_tm(c, g, c->res[3], 3, c->P, &c->H1, c->Q, s, false);           // output_blocks.0.0  cat([h, H1])
+        run_transformer_tm(c, g, c->st[2], 2, c->Q, c->P, s, false, false);         // output_blocks.0.1
+        run_resblock_tm(c, g, c->res[4], 4, c->P, &c->H0, c->Q, s, false);           // output_blocks.1.0  cat([h, H0])
+        run_transformer_tm(c, g, c->st[3], 3, c->Q, c->P, s, false, !out_tm);       // output_blocks.1.1 (-> channel-major for out_sched_kernel unless out_tm)
+    } else {
+    run_resblock(c, g, c->res[0], 0, c->H0, nullptr, c->P, s, sh);   // input_blocks.1.0
+    run_transformer(c, g, c->st[0], 0, c->P, c->H1, s, sh);          // input_blocks.1.1   (hs: H0, H1)
+    run_resblock(c, g, c->res[1], 1, c->H1, nullptr, c->P, s);       // middle_block.0
+    run_transformer(c, g, c->st[1], 1, c->P, c->Q, s);               // middle_block.1
+    run_resblock(c, g, c->res[2], 2, c->Q, nullptr, c->P, s);        // middle_block.2
+    run_resblock(c, g, c->res[3], 3, c->P, &c->H1, c->Q, s);         // output_blocks.0.0  cat([h, H1])
+    run_transformer(c, g, c->st[2], 2, c->Q, c->P, s);               // output_blocks.0.1
+    run_resblock(c, g, c->res[4], 4, c->P, &c->H0, c->Q, s);         // output_blocks.1.0  cat([h, H0])
+    run_transformer(c, g, c->st[3], 3, c->Q, c->P, s);               // output_blocks.1.1
+    }
+    if (g.out_sched) {   // out conv + guidance + DDIM update in one kernel (out_sched.hip)
+        if (dbg_go(c)) { if (out_tm) launch_out_sched_tm(osa_tm, s); else launch_out_sched(*g.out_sched, s); }
+    } else {   // out: GN -> SiLU -> Conv1d(192 -> 32, k3)
+        GemmArgs a = mkargs(g.T, c->cin);
+        a.nseg = 1;
+        a.seg[0] = with_pw(mkseg(c->P.p, g.hs, g.Tp, MC, 3, 1, 1, g.T, XF_GN_SILU, c->conv_out.w[0]), c->conv_out, 0);
+        seg_gn(a.seg[0], c->P.st, g.sts, 6, g.np, 1e-5f, c->out_g, c->out_b);
+        a.bias = c->conv_out.bias;
+        a.y = c->eps_cm; a.y_bstride = (long long)c->cin * g.Tp; a.y_pitch = g.Tp;
+        do_gemm(c, a, EPI_STORE, g.Be, 1, 8, s);
+        if (c->log_on && !c->stage_log.empty()) c->stage_log.back().kind = 12;   // the `out` convolution alone (forward(), profiling): in the loop it is out_sched_kernel's first half
+    }
+}
+
+// time_embed + the five emb_layers for `n` timesteps already in ts_dev -> EO [5*192][Np]
+void run_time_embed(said_ctx* c, int n, hipStream_t s) {
+    const int Np = c->maxNp;
+    launch_timestep_embedding(c->ts_dev, c->freqs, c->E0, n, MC, Np, s);
+    const long long tt = (n + 31) / 32;
+    {
+        GemmArgs a = mkargs(n, TE);
+        a.nseg = 1;
+        a.seg[0] = with_pw(mkseg(c->E0, 0, Np, MC, 1, 0, 1, n, XF_NONE, c->te1.w[0]), c->te1, 0);
+        a.bias = c->te1.bias; a.act = ACT_SILU;
+        a.y = c->E1; a.y_pitch = Np;
+        const LaunchCfg lc = pick_cfg(tt, TE / 32);
+        launch_gemm(a, EPI_STORE, 1, lc.NB, lc.KS, s);
+    }
+    {
+        GemmArgs a = mkargs(n, TE);
+        a.nseg = 1;
+        a.seg[0] = with_pw(mkseg(c->E1, 0, Np, TE, 1, 0, 1, n, XF_NONE, c->te2.w[0]), c->te2, 0);
+        a.bias = c->te2.bias;
+        a.y = c->E2; a.y_pitch = Np;
+        const LaunchCfg lc = pick_cfg(tt, TE / 32);
+        launch_gemm(a, EPI_STORE, 1, lc.NB, lc.KS, s);
+    }
+    {
+        GemmArgs a = mkargs(n, NRES * MC);
+        a.nseg = 1;
+        a.seg[0] = with_pw(mkseg(c->E2, 0, Np, TE, 1, 0, 1, n, XF_SILU, c->emb_all.w[0]), c->emb_all, 0);
+        a.bias = c->emb_all.bias;
+        a.y = c->EO; a.y_pitch = Np;
+        const LaunchCfg lc = pick_cfg(tt, NRES * MC / 32);
+        launch_gemm(a, EPI_STORE, 1, lc.NB, lc.KS, s);
+    }
+}
+
+// cross-attention K/V of all four transformer blocks from the channel-major context (step-invariant)
+// for samples [b0, b0 + nb): under guidance with the shared schedule only the conditional half's are ever read
+void run_kv(said_ctx* c, int b0, int nb, int S, int Sp, hipStream_t s) {
+    GemmArgs a = mkargs(S, NST * 2 * MC);
+    a.nseg = 1;
+    const long long cbs = (long long)c->ctx_dim * Sp, ybs = (long long)NST * 2 * MC * Sp;
+    a.seg[0] = with_pw(mkseg(c->CTX + b0 * cbs, cbs, Sp, c->ctx_dim, 1, 0, 1, S, XF_NONE, c->kv_all.w[0]), c->kv_all, 0);
+    a.y = c->KV + b0 * ybs; a.y_bstride = ybs; a.y_pitch = Sp;
+    const LaunchCfg lc = pick_cfg((long long)nb * ((S + 31) / 32), NST * 2 * MC / 32);
+    launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
+    // the key-major copy the fused SpatialTransformer tail reads its window tiles from (once per loop; fp32 mode's small-batch schedule only)
+    c->kvt_S = -1;
+    if ((c->bf16_mode ? c->st_chain_bf16 != 0 : sp_on(c, c->st_chain)) && (long long)S * NST * 2 * MC <= (long long)NST * 2 * MC * c->maxTp)
+    {
+        c->kvt_S = S; c->kvt_bf16 = c->bf16_mode ? 1 : 0;
+        // (bf16 mode: the copy itself is bf16 — the kernels round the window tiles to bf16 anyway, and at 32 clips the windows are 64 of a launch's 117 MB of HBM traffic in fp32)
+        if (c->bf16_mode) launch_cm_to_tm_bf16(c->KV + b0 * ybs, ybs, Sp, reinterpret_cast<unsigned short*>(c->KVT) + (long long)b0 * S * (NST * 2 * MC), (long long)S * (NST * 2 * MC), nb, S, NST * 2 * MC, s);
+        else launch_cm_to_tm(c->KV + b0 * ybs, c->KVT + (long long)b0 * S * (NST * 2 * MC), nb, S, NST * 2 * MC, Sp, ybs, s);
+    }
+}
+
+// alignment band of ldm/attention.py:170-189 with Python's banker's rounding on doubles
+int set_band(said_ctx* ctx, int T, int S, hipStream_t s) {
+    if (ctx->band_T == T && ctx->band_S == S) return 0;
+    std::vector<int> lo(T), hi(T);
+    const double ratio = (double)S / (double)T, kh = ratio / 2 + 1;
+    int wmax = 0;
+    for (int i = 0; i < T; ++i) {
+        const double mid = (i + 0.5) * ratio;
+        const int a = std::max((int)std::nearbyint(mid - kh), 0);
+        const int b = std::min((int)std::nearbyint(mid + kh), S);
+        lo[i] = a; hi[i] = b;
+        wmax = std::max(wmax, b - a);
+        if (b <= a) return fail(ctx, "empty alignment window at query %d (T=%d, S=%d)", i, T, S);
+    }
+    // work queued earlier on the caller's stream may still read the previous tables: drain it before they change
+    // (only happens when the clip length changes)
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(ctx->band_lo, lo.data(), T * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->band_hi, hi.data(), T * sizeof(int), hipMemcpyHostToDevice));
+    ctx->band_T = T; ctx->band_S = S; ctx->band_wmax = wmax;
+    {   // stchain.hip keeps the windows of a 32-token tile as CHAIN_KW key rows starting at lo[first token]: needs a non-decreasing band of that span
+        bool ok = wmax <= 8;
+        for (int i = 1; i < T && ok; ++i) ok = lo[i] >= lo[i - 1];
+        for (int t0 = 0; t0 < T && ok; t0 += 32) {
+            int hmax = 0;
+            for (int i = t0; i < std::min(T, t0 + 32); ++i) hmax = std::max(hmax, hi[i]);
+            ok = hmax - lo[t0] <= CHAIN_KW;
+        }
+        ctx->band_chain_ok = ok;
+    }
+    return 0;
+}
+
+UGeo make_geo(said_ctx* c, int Be, int B_lat, int T, int S) {
+    UGeo g;
+    g.Be = Be; g.B_lat = B_lat; g.T = T; g.Tp = rup(T, 32); g.np = (T + 31) / 32; g.S = S; g.Sp = rup(S, 32);
+    g.hs = (long long)MC * g.Tp; g.sts = (long long)MC * g.np * 2;
+    g.step_ptr = nullptr; g.emb_b_stride = 0; g.step_inc = nullptr; g.out_sched = nullptr; g.Bc = 0;
+    return g;
+}
+
+}  // namespace host
+}  // namespace said

@@ -94,7 +94,7 @@ def test_decode_chunking_and_edge_cases():
     eng = m._get_engine()
     g = torch.Generator()
     g.manual_seed(77)
-    n_big = 16384 + 3   # one more launch than engine.cpp's 16384-window chunk
+    n_big = 16384 + 3   # one more launch than vae.cpp's 16384-window chunk
     z = torch.randn(n_big, 64, generator=g).to(DEV)
     big = m.decode(z)
     assert big.shape == (n_big, 120, 32)

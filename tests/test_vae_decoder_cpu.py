@@ -1,6 +1,6 @@
 """BCVAE decoder (said/model/vae.py:115-170), CPU side: the synthetic full state dict, a float64 restatement of the decoder
 pinned to golden G11 (the reference's own BCVAE), the ConvTranspose1d -> flipped Conv1d rewrite the host packing uses
-(engine.cpp load_vae_decoder), and the reconstruction CLI's flags.  The GPU tests (test_gpu_vae_decoder.py) compare the
+(vae.cpp load_vae_decoder), and the reconstruction CLI's flags.  The GPU tests (test_gpu_vae_decoder.py) compare the
 engine against the same restatement."""
 import os
 import subprocess
