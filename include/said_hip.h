@@ -50,7 +50,6 @@ const char* said_last_error(const said_ctx* ctx);
 int said_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------ */
-
 /* Replaces `.load_state_dict(...)` + `.to(device)` (script/inference.py:157-158). `name` is the reference state-dict key: "null_cond_emb",
  * "denoiser.model.*", "audio_encoder.*" (transformers-4.30.2 naming, i.e. "...pos_conv_embed.conv.weight_g/weight_v"), optional "audio_proj_layer.*". Data is
  * copied; fp32, C-contiguous. */
@@ -64,7 +63,6 @@ int said_finalize_weights(said_ctx* ctx, void* stream);
 int said_set_timestep_freqs(said_ctx* ctx, const float* freqs_host, int n);
 
 /* ---- audio path (once per clip) ----------------------------------------- */
-
 /* Replaces SAID.get_audio_embedding (diffusion.py:209-230) → ModifiedWav2Vec2Model.forward (said/model/wav2vec2.py:13-82): conv feature extractor, linear
  * interpolation to `num_frames` (<=0: none), projection, positional conv, transformer encoder; with apply_proj != 0 also the audio_proj_layer Linear(768,
  * feature_dim) of diffusion.py:228-229. waveform_dev (B, Ta) → out_dev (B, F, D), D = 768 or feature_dim.  *out_frames receives F. */
@@ -72,7 +70,6 @@ int said_audio_encode(said_ctx* ctx, const float* waveform_dev, int batch, int n
                       int apply_proj, float* out_dev, int* out_frames, void* stream);
 
 /* ---- denoiser: one evaluation ------------------------------------------- */
-
 /* Replaces SAID.forward (diffusion.py:127-155) → UNet1DConditionModel.forward (said/model/unet_1d_condition.py:51-77) → UNetModel.forward
  * (said/model/ldm/openaimodel.py:677-709).  sample_dev (Be, T, C_in), timesteps_host (Be) int64, context_dev (Be, S, ctx_dim) → out_dev (Be, T, C_in). Any (T,
  * S): the cross-attention's alignment windows (ldm/attention.py:170-189) of up to 8 keys — all that SAID.inference produces — run inside the q projection's
@@ -81,7 +78,6 @@ int said_unet_forward(said_ctx* ctx, const float* sample_dev, const int64_t* tim
                       int batch_eff, int frames, int ctx_len, float* out_dev, void* stream);
 
 /* ---- denoising loop (diffusion.py:354-472) ------------------------------ */
-
 typedef struct said_loop_params {
     int batch;               /* B clips (UNet batch is 2*B when guidance_scale > 1) */
     int frames;              /* T = window_size */
@@ -123,6 +119,7 @@ enum {
     SAID_COEF_SIGMA = 4,          /* eta * variance ** 0.5                     */
     SAID_COEF_NEXT_SQRT_ALPHA = 5,/* add_noise coefficient at t_next (mask blend), 1 on the last step */
     SAID_COEF_NEXT_SQRT_BETA = 6, /* add_noise coefficient at t_next, 0 on the last step               */
+    SAID_COEF_SOLVER = 7,         /* per row: 0 DDIM (above), 1 DDPM, 2 / 3 DPM-Solver++ order 1 / 2: cols 0-4 then per INTEGRATION.md */
     SAID_NCOEF = 8
 };
 
@@ -149,7 +146,6 @@ int said_loop_progress_reset(said_ctx* ctx);
 int said_philox_normal(said_ctx* ctx, uint64_t seed, int step0, int nsteps, int64_t n_per_step, float* out_dev, void* stream);
 
 /* ---- scheduler arithmetic on its own (bit-exactness tests) -------------- */
-
 /* One DDIMScheduler.step (+ optional CFG combine and mask blend) as a plain elementwise kernel over n = B*T*C values, using the same device function the loop
  * uses.  eps_uncond_dev may be NULL (no guidance).  coef = one row of coef_host.  Replaces diffusers' DDIMScheduler.step / add_noise as called at
  * diffusion.py:441-443, 451-454. */
@@ -158,6 +154,12 @@ int said_ddim_step(said_ctx* ctx, const float* eps_dev, const float* eps_uncond_
                    const float* step_noise_dev, const float* init_latents_dev, const float* edit_noise_dev,
                    const float* mask_dev, float* prev_sample_dev, int64_t n, void* stream);
 
+/* said_ddim_step for one DDPM / DPM-Solver++ row (SAID_COEF_SOLVER 1-3): DDPMScheduler / DPMSolverMultistepScheduler.step (diffusers 0.19).  x0_hist_dev
+ * (n floats, DPM rows): in the previous step's x0, out this step's.  DPM rows take no step_noise_dev. */
+int said_solver_step(said_ctx* ctx, const float* model_out_dev, const float* uncond_dev, float guidance_scale, const float* sample_dev,
+                     const float* coef_host, int prediction_type, float* x0_hist_dev, const float* step_noise_dev, const float* init_latents_dev,
+                     const float* edit_noise_dev, const float* mask_dev, float* prev_sample_dev, int64_t n, void* stream);
+
 /* out[b, i] = a[b] * x[b, i] + c[b] * y[b, i] with each product and the sum rounded separately (no FMA): DDIMScheduler.add_noise / get_velocity as called at
  * diffusion.py:271-272, 383-385 (velocity: a = sqrt_alpha, x = noise, c = -sqrt_beta, y = sample).  a_host/c_host have `batch` entries; y_dev may be NULL (c
  * ignored). */
@@ -165,7 +167,6 @@ int said_axpby(said_ctx* ctx, const float* a_host, const float* x_dev, const flo
                float* out_dev, int batch, int64_t n_per_batch, void* stream);
 
 /* ---- precision ----------------------------------------------------------- */
-
 /* How the matrix products of the UNet and the audio encoder multiply.  Accumulation, statistics, normalisations, softmax, residual sums and the scheduler are
  * fp32 in every mode.  The reference itself (diffusion.py) only runs fp32.
  * SAID_PREC_FP32 (default): fp32 tensors; products on SPLIT-fp16 operands — x = h + 2^-11 l, h = RN16(x), l = RN16((x - h) 2^11): 22-bit significands, three
@@ -191,7 +192,6 @@ const char* said_precision_note(const said_ctx* ctx);/* "" or which tensor force
 int said_numeric_status(said_ctx* ctx, void* stream, int* first_bad_step, int* result_nonfinite);
 
 /* ---- introspection ------------------------------------------------------- */
-
 /* Number of kernel launches captured in the current per-step graph (0 if none). */
 int said_graph_num_nodes(const said_ctx* ctx);
 /* Algorithmic bytes / flops of one UNet evaluation for (batch_eff, frames), SURVEY.md §8(d) formulas; used by bench.py's roofline block. */

@@ -19,6 +19,8 @@ _lib = None
 PRED = {"epsilon": 0, "sample": 1, "v_prediction": 2}
 PRECISIONS = {"fp32": 0, "bf16": 1, "fp32_strict": 2}   # SAID_PREC_* of include/said_hip.h
 NCOEF = 8
+COEF_SOLVER = 7   # SAID_COEF_SOLVER: column 7 of a coefficient row
+SOLVER = {"ddim": 0, "ddpm": 1, "dpm1": 2, "dpm2": 3}
 ABI_VERSION = 9   # include/said_hip.h as bound below; a stale libsaid_hip.so is refused at load time
 
 
@@ -57,6 +59,8 @@ EXPORTS = {
     "said_denoise_loop": (c_int, [c_void_p, POINTER(LoopParams), c_void_p]),
     "said_ddim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, POINTER(c_float), c_int, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "said_solver_step": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "said_axpby": (c_int, [c_void_p, POINTER(c_float), c_void_p, POINTER(c_float), c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "said_graph_num_nodes": (c_int, [c_void_p]),
     "said_loop_progress": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
@@ -330,6 +334,27 @@ class Engine:
             self._chk(self.lib.said_ddim_step(self.h, _ptr(eps), _ptr(opt[0]), float(guidance_scale), _ptr(sample),
                                               cf.ctypes.data_as(POINTER(c_float)), PRED[prediction_type], _ptr(opt[1]), _ptr(opt[2]),
                                               _ptr(opt[3]), _ptr(opt[4]), _ptr(out), sample.numel(), _stream()), "said_ddim_step")
+            torch.cuda.current_stream().synchronize()  # cf is a temporary
+        return out
+
+    def solver_step(self, model_output: torch.Tensor, sample: torch.Tensor, coef_row: np.ndarray, prediction_type: str,
+                    x0_hist: Optional[torch.Tensor] = None, model_output_uncond: Optional[torch.Tensor] = None, guidance_scale: float = 1.0,
+                    step_noise: Optional[torch.Tensor] = None, init_latents: Optional[torch.Tensor] = None,
+                    edit_noise: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One DDPM / DPM-Solver++ row (said_solver_step).  `x0_hist` (DPM rows): the previous step's x0 in, this step's out (updated in place)."""
+        model_output, sample = _check_dev(model_output, "model_output"), _check_dev(sample, "sample")
+        out = torch.empty_like(sample)
+        cf = np.ascontiguousarray(np.asarray(coef_row, dtype=np.float32).reshape(NCOEF))
+        opt = [None if t is None else _check_dev(t, "tensor") for t in (model_output_uncond, step_noise, init_latents, edit_noise, mask)]
+        for t in [x0_hist] + opt:
+            if t is not None and t.numel() != sample.numel():
+                raise EngineError(f"solver_step: every tensor must hold {sample.numel()} values, got {t.numel()}")
+        if x0_hist is not None and (_check_dev(x0_hist, "x0_hist") is not x0_hist):
+            raise EngineError("x0_hist must be contiguous: it is updated in place")
+        with torch.cuda.device(self.index):
+            self._chk(self.lib.said_solver_step(self.h, _ptr(model_output), _ptr(opt[0]), float(guidance_scale), _ptr(sample),
+                                                cf.ctypes.data_as(POINTER(c_float)), PRED[prediction_type], _ptr(x0_hist), _ptr(opt[1]),
+                                                _ptr(opt[2]), _ptr(opt[3]), _ptr(opt[4]), _ptr(out), sample.numel(), _stream()), "said_solver_step")
             torch.cuda.current_stream().synchronize()  # cf is a temporary
         return out
 

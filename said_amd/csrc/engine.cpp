@@ -91,6 +91,7 @@ int alloc_workspace(said_ctx* ctx, int max_batch_eff, int max_frames) {
         rc |= dalloc(ctx, reinterpret_cast<float**>(&ctx->tO), tm);
         rc |= dalloc(ctx, reinterpret_cast<float**>(&ctx->tF), Be * seg * FFI + 4096);
     }
+    rc |= dalloc(ctx, &ctx->x0h_cm, Be * 32 * Tp);   // (last: the workspace-inspection indices of the buffers above stay)
     ctx->alloc_list = &ctx->allocs;
     ctx->band_T = ctx->band_S = -1;   // the band tables are part of the workspace
     ctx->kvt_S = -1;                  // ... and so is the key-major K / V copy
@@ -355,7 +356,24 @@ static int steps_per_graph(const said_ctx* ctx, int N) {
     const int lim = N >= 400 ? ctx->spg_limit : std::min(ctx->spg_limit, 10);
     return std::max(1, std::min(lim, N));
 }
-static std::vector<long long> loop_graph_key(const said_ctx* ctx, const said_loop_params* p, const float* noise_cm) {
+// Solver family of a coefficient table (column SAID_COEF_SOLVER): 0 = DDIM rows only, 1 = DDPM / DPM-Solver++ rows only, -1 = malformed
+// (the message in *why).  The family picks the kernels the step graph holds; the row's own code picks the update inside them.
+static int table_solver(const said_loop_params* p, std::string* why) {
+    char buf[160];
+    int fam = -1;
+    for (int k = 0; k < p->num_steps; ++k) {
+        const float v = p->coef_host[(size_t)k * 8 + 7];
+        const int code = (v >= 0.f && v <= 3.f) ? (int)v : -1;
+        if (code < 0 || v != (float)code) { snprintf(buf, sizeof buf, "coefficient row %d: unknown solver code %g in column 7", k, (double)v); *why = buf; return -1; }
+        const int f = code != 0;
+        if (fam >= 0 && f != fam) { snprintf(buf, sizeof buf, "coefficient row %d: DDIM and DDPM / DPM-Solver++ rows mixed in one table", k); *why = buf; return -1; }
+        fam = f;
+        if (code == 3 && k == 0) { *why = "coefficient row 0: a loop's first step cannot be second order (no previous x0)"; return -1; }
+        if (code >= 2 && p->use_step_noise) { snprintf(buf, sizeof buf, "coefficient row %d: DPM-Solver++ rows draw no step noise (use_step_noise must be 0)", k); *why = buf; return -1; }
+    }
+    return fam < 0 ? 0 : fam;
+}
+static std::vector<long long> loop_graph_key(const said_ctx* ctx, const said_loop_params* p, const float* noise_cm, int solver) {
     const bool cfg = p->guidance_scale > 1.0f;
     float gs = p->guidance_scale, gr = (cfg && p->guidance_rescale > 0.f) ? p->guidance_rescale : 0.f, ls = p->latent_scale;
     int gsi, gri, lsi;
@@ -363,7 +381,7 @@ static std::vector<long long> loop_graph_key(const said_ctx* ctx, const said_loo
     const int spg = p->num_steps > 0 ? steps_per_graph(ctx, p->num_steps) : 0;
     const int rem = spg > 0 ? p->num_steps % spg : 0;
     return {spg, rem, p->batch, p->frames, cfg, gsi, gri, lsi, p->prediction_type, p->use_mask, p->use_step_noise, ctx->bf16_mode ? 1 : (strict_f32(ctx) ? 2 : 0), p->noise_batch_offset, p->concurrent != 0,
-            (long long)(uintptr_t)(p->save_intermediate ? p->intermediates_dev : nullptr), (long long)(uintptr_t)(p->use_step_noise == 1 ? noise_cm : nullptr)};
+            (long long)(uintptr_t)(p->save_intermediate ? p->intermediates_dev : nullptr), (long long)(uintptr_t)(p->use_step_noise == 1 ? noise_cm : nullptr), solver};
 }
 
 static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, bool prepare_only) {
@@ -384,10 +402,14 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
     if (p->use_step_noise == 1 && !p->step_noise_dev) return fail(ctx, "use_step_noise = 1 needs step_noise_dev");
     if (p->use_step_noise < 0 || p->use_step_noise > 2) return fail(ctx, "bad use_step_noise %d", p->use_step_noise);
     if (p->save_intermediate && !p->intermediates_dev) return fail(ctx, "save_intermediate needs intermediates_dev");
+    if (N > 0 && !p->coef_host) return fail(ctx, "coef_host must not be null");
+    std::string why;
+    const int solver = table_solver(p, &why);
+    if (solver < 0) return fail(ctx, "said_denoise_loop: %s", why.c_str());
     if (prepare_only) {   // nothing to do when the step graph of this configuration exists
         if (N == 0) return 0;
         const bool grow = p->use_step_noise == 1 && (size_t)N * B * C * (size_t)rup(T, 32) > ctx->noise_cm_elems;
-        if (!grow && ctx->gexec && loop_graph_key(ctx, p, ctx->noise_cm) == ctx->gkey) return 0;
+        if (!grow && ctx->gexec && loop_graph_key(ctx, p, ctx->noise_cm, solver) == ctx->gkey) return 0;
     }
     if (set_band(ctx, T, T, s)) return -1;
     UGeo g = make_geo(ctx, Be, cfg ? B : 0, T, T);
@@ -460,6 +482,7 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
     osa.prediction_type = p->prediction_type; osa.guidance_scale = p->guidance_scale; osa.guidance_rescale = sa.guidance_rescale;
     osa.latent_scale = p->latent_scale;
     osa.status = ctx->status_dev;
+    osa.x0h = solver ? ctx->x0h_cm : nullptr; osa.solver = solver;
     const bool fused = ctx->conv_out.w4[0] && out_sched_supports(osa);
     if (fused) g.out_sched = &osa;
 
@@ -469,7 +492,7 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
         // the N % spg remaining steps finishes it (prime N, e.g. 997 = 99 x 10 + 7)
         const int spg = steps_per_graph(ctx, N);   // measured: ~6 us per graph launch boundary; 10 steps per graph recovered 1.2 % at B=1 (round 1), 50 another 0.4-0.5 % of a long loop (round 6)
         const int rem = N % spg;
-        const std::vector<long long> key = loop_graph_key(ctx, p, sa.step_noise);
+        const std::vector<long long> key = loop_graph_key(ctx, p, sa.step_noise, solver);
         if (!ctx->gexec || key != ctx->gkey) {
             drop_graphs(ctx);
             // Eager warm-up of the exact step sequence first: the first launch of a kernel inside a
@@ -481,7 +504,8 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
             TRACE("loop: warmup unet launched");
             if (!fused) {
                 if (sa.guidance_rescale > 0.f) launch_rescale_partials(sa, ctx->rescale_part, s);
-                launch_sched_step(sa, s);
+                launch_sched_step(sa, solver, osa.x0h, s);
+                ++ctx->n_sched_step;
             }
             launch_tm_to_cm(p->latents_dev, ctx->x_cm, B, T, C, g.Tp, xs, s);
             HIPCHK(hipMemsetAsync(ctx->step_dev, 0xFF, sizeof(int), s));
@@ -502,7 +526,8 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
                     run_unet(ctx, g, cs);
                     if (!fused) {
                         if (sa.guidance_rescale > 0.f) launch_rescale_partials(sa, ctx->rescale_part, cs);
-                        launch_sched_step(sa, cs);
+                        launch_sched_step(sa, solver, osa.x0h, cs);
+                        ++ctx->n_sched_step;
                     }
                 }
                 TRACE("loop: capture recorded");
@@ -551,6 +576,29 @@ int said_ddim_step(said_ctx* ctx, const float* eps_dev, const float* eps_uncond_
     if (n > 0)
         launch_ddim_flat(eps_dev, eps_uncond_dev, guidance_scale, sample_dev, ctx->coef1_dev, prediction_type, step_noise_dev,
                          init_latents_dev, edit_noise_dev, mask_dev, prev_sample_dev, n, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int said_solver_step(said_ctx* ctx, const float* model_out_dev, const float* uncond_dev, float guidance_scale, const float* sample_dev,
+                     const float* coef_host, int prediction_type, float* x0_hist_dev, const float* step_noise_dev, const float* init_latents_dev,
+                     const float* edit_noise_dev, const float* mask_dev, float* prev_sample_dev, int64_t n, void* stream) {
+    if (!ctx) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (prediction_type < 0 || prediction_type > 2) return fail(ctx, "bad prediction_type %d", prediction_type);
+    if (!coef_host) return fail(ctx, "said_solver_step: coef_host must not be null");
+    if (mask_dev && !(init_latents_dev && edit_noise_dev)) return fail(ctx, "mask needs init_latents_dev and edit_noise_dev");
+    const float v = coef_host[7];
+    const int code = (v >= 1.f && v <= 3.f) ? (int)v : -1;
+    if (code < 0 || v != (float)code)
+        return fail(ctx, "said_solver_step: solver code %g in column 7 is not DDPM (1) or DPM-Solver++ (2, 3); DDIM rows go to said_ddim_step", (double)v);
+    if (code >= 2 && step_noise_dev) return fail(ctx, "said_solver_step: DPM-Solver++ rows draw no step noise");
+    if (code >= 2 && !x0_hist_dev) return fail(ctx, "said_solver_step: DPM-Solver++ rows need x0_hist_dev");
+    HIPCHK(hipMemcpyAsync(ctx->coef1_dev, coef_host, 8 * sizeof(float), hipMemcpyHostToDevice, s));
+    if (n > 0)
+        launch_solver_flat(model_out_dev, uncond_dev, guidance_scale, sample_dev, ctx->coef1_dev, prediction_type, x0_hist_dev, step_noise_dev,
+                           init_latents_dev, edit_noise_dev, mask_dev, prev_sample_dev, n, s);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -646,6 +694,9 @@ long long said_debug_get(const said_ctx* ctx, const char* name) {
     if (k == "ugemm_split") return (!ctx->bf16_mode && sp_on(ctx, ctx->ugemm_split)) ? 1 : 0;
     if (k == "st_chain") return (!ctx->bf16_mode && sp_on(ctx, ctx->st_chain)) ? 1 : 0;
     if (k == "n_stchain") return ctx->n_stchain;
+    if (k == "n_out_sched") return ctx->n_out_sched;
+    if (k == "n_out_sched_tm") return ctx->n_out_sched_tm;
+    if (k == "n_sched_step") return ctx->n_sched_step;
     if (k == "st_chain_bf16") return (ctx->bf16_mode && ctx->st_chain_bf16 != 0) ? 1 : 0;
     if (k == "attn_split") return (!ctx->bf16_mode && sp_on(ctx, ctx->attn_split)) ? 1 : 0;   // 1: fp32-mode attention products run on split-fp16 operands
     if (k == "n_rgemm") return ctx->n_rgemm;
@@ -700,7 +751,7 @@ static const char* ws_name(const said_ctx* c, const void* p) {
         {c->E0, "E0"}, {c->E1, "E1"}, {c->E2, "E2"}, {c->EO, "EO"}, {c->ts_dev, "ts"}, {c->coef_dev, "coef"}, {c->axpby_coef, "axpby_coef"},
         {c->band_lo, "band_lo"}, {c->band_hi, "band_hi"}, {c->init_cm, "init_cm"}, {c->enoise_cm, "enoise_cm"}, {c->mask_cm, "mask_cm"},
         {c->rescale_part, "rescale_part"}, {c->uPA, "uPA"}, {c->uPB, "uPB"}, {c->uPL, "uPL"}, {c->uPH, "uPH"}, {c->uPX, "uPX"}, {c->gn_coef, "gn_coef"},
-        {c->H0.t, "tH0"}, {c->H1.t, "tH1"}, {c->P.t, "tP"}, {c->Q.t, "tQ"}, {c->M.t, "tM"}, {c->tX1, "tX1"}, {c->tX2, "tX2"}, {c->tO, "tO"}, {c->tF, "tF"}};
+        {c->H0.t, "tH0"}, {c->H1.t, "tH1"}, {c->P.t, "tP"}, {c->Q.t, "tQ"}, {c->M.t, "tM"}, {c->tX1, "tX1"}, {c->tX2, "tX2"}, {c->tO, "tO"}, {c->tF, "tF"}, {c->x0h_cm, "x0h"}};
     for (const auto& e : t) if (e.first == p) return e.second;
     return "?";
 }

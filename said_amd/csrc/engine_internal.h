@@ -144,6 +144,7 @@ struct said_ctx : HostCtx {
     float *init_cm = nullptr, *enoise_cm = nullptr, *mask_cm = nullptr, *rescale_part = nullptr;
     float* noise_cm = nullptr; size_t noise_cm_elems = 0;
     float* coef1_dev = nullptr;  // one row for said_ddim_step
+    float* x0h_cm = nullptr;     // DPM-Solver++: the previous step's x0, x_cm's layout (workspace; each element read and written by the thread that owns it)
     unsigned seed_host[2] = {0, 0};
     unsigned* seed_dev = nullptr;  // [2] Philox key of the loop's eta noise (said_loop_params::noise_seed)
     float* axpby_coef = nullptr;
@@ -197,6 +198,7 @@ struct said_ctx : HostCtx {
     int pw_split = 0;         // make_pw: also build the split-fp16 packing (1: per-block layout, 2: flat) — set around the UNet weights only
     long long n_rgemm = 0;
     long long n_stchain = 0;  // launches issued through stchain_kernel (said_debug_get)
+    long long n_out_sched = 0, n_out_sched_tm = 0, n_sched_step = 0;   // ... through the step's last kernel: out_sched_kernel, out_sched_tm_kernel, sched_step_kernel
     long long n_xgemm = 0;    // launches issued through round 3's xgemm_kernel (said_debug_get; n_rgemm: through rgemm_kernel)
     void *tX1 = nullptr, *tX2 = nullptr, *tO = nullptr, *tF = nullptr;   // token-major x1, x2, attention output [.][192], GEGLU product [.][768]
     // tokens per launch from which the token-major GEMM path is taken (measured crossovers, scripts/gpu_r2_w.sh: bf16 between 4800

@@ -213,7 +213,13 @@ struct SchedArgs {
     unsigned noise_elem0;         // element index of this call's first clip in the whole batch (clip groups on concurrent streams draw the noise of ONE batch)
     int* status;                  // device [2] sticky numeric status (said_numeric_status): [0] <- 1 + the first step whose model output was not finite, or null
 };
-void launch_sched_step(const SchedArgs& a, hipStream_t s);
+// sched_step_kernel<1>'s arguments: DPM-Solver++'s previous-step x0, channel-major like x (read by order-2 rows, written by every DPM row).
+// (A separate type, so that the DDIM kernel's argument block — and its code — stays as it was.)
+struct SolverSchedArgs : SchedArgs {
+    float* x0h;
+};
+// solver: 0 = the table's rows are DDIM (sched_math.h ddim_prev), 1 = DDPM / DPM-Solver++ rows (solver_prev, x0h); a table never mixes the two
+void launch_sched_step(const SchedArgs& a, int solver, float* x0h, hipStream_t s);
 
 // out conv (GN -> SiLU -> Conv1d(192 -> Cout, k3)) + guidance + DDIM update in one kernel (out_sched.hip)
 struct OutSchedArgs {
@@ -244,6 +250,8 @@ struct OutSchedArgs {
     const void* wb;
     int seg;
     int* status;               // see SchedArgs
+    float* x0h;                // see SolverSchedArgs (channel-major like lat)
+    int solver;                // see launch_sched_step
 };
 bool out_sched_supports(const OutSchedArgs& a);
 bool out_sched_tm_supports(const OutSchedArgs& a);
@@ -256,6 +264,9 @@ void launch_rescale_partials(const SchedArgs& a, float* part_out, hipStream_t s)
 void launch_ddim_flat(const float* eps, const float* eps_u, float gs, const float* x, const float* coef_dev, int pred,
                       const float* noise, const float* init, const float* edit_noise, const float* mask, float* out,
                       long long n, hipStream_t s);
+// standalone DDPM / DPM-Solver++ step on token-major buffers (said_solver_step); x0h: in / out x0 history (DPM rows), may be null for DDPM
+void launch_solver_flat(const float* mo, const float* mo_u, float gs, const float* x, const float* coef_dev, int pred, float* x0h,
+                        const float* noise, const float* init, const float* edit_noise, const float* mask, float* out, long long n, hipStream_t s);
 // out[b][i] = a[b]*x[b][i] + c[b]*y[b][i] (explicitly rounded mul, mul, add); coefficients live in device memory
 void launch_axpby(const float* a_dev, const float* x, const float* c_dev, const float* y, float* out, int B, long long n,
                   hipStream_t s);

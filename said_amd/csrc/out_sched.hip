@@ -29,7 +29,8 @@ static_assert(OS_CW == 24, "one 24-channel block per wave");
 // the weights out.2 in engine.cpp's pack_rows_split layout (a.ws: [8 blocks][5 k16 steps][2 planes][64 lanes][8 halfs], GroupNorm affine behind) — 30 v_mfma_f32_32x32x16_f16
 // of 8 passes per wave instead of 72 v_mfma_f32_32x32x2_f32 of 16 (two waves share a SIMD's matrix pipe: 4.6 of the kernel's 12.8 us were this loop).
 // The leading parameters are what the first requests need (preloaded into SGPRs: build.py): with everything inside the by-value struct the kernel began with a scalar-memory round trip.
-template <bool CFG, bool SP>
+// SF (solver family): 0 = DDIM rows (ddim_prev), 1 = DDPM / DPM-Solver++ rows (solver_prev, the x0 history in a.x0h).
+template <bool CFG, bool SP, int SF>
 __global__ __launch_bounds__(64 * OS_KS) void out_sched_kernel(const float* hx, const float* hpart, const float* hw, const int* hstep, int hT_pitch, int hxbs, int hpbs, int hB_np,
                                                                const OutSchedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -94,8 +95,10 @@ __global__ __launch_bounds__(64 * OS_KS) void out_sched_kernel(const float* hx, 
     const rsrc_t rin = make_rsrc(a.mask ? a.init + (long long)b * a.lat_bstride : nullptr, a.mask ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
     const rsrc_t ren = make_rsrc(a.mask ? a.edit_noise + (long long)b * a.lat_bstride : nullptr, a.mask ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
     const rsrc_t rmk = make_rsrc(a.mask ? a.mask + (long long)b * a.lat_bstride : nullptr, a.mask ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
-    float e_x[2], e_nz[2], e_in[2], e_en[2], e_mk[2], e_bias[2];
+    float e_x[2], e_nz[2], e_in[2], e_en[2], e_mk[2], e_bias[2], e_h[2];
     int e_n[2];
+    const bool want_h = SF != 0 && solver_code(cfv) == SOLVER_DPM2;   // (order 2 reads the previous step's x0)
+    const rsrc_t rh = make_rsrc(SF != 0 ? a.x0h + (long long)b * a.lat_bstride : nullptr, SF != 0 ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int r = w + j * OS_KS;
@@ -107,6 +110,7 @@ __global__ __launch_bounds__(64 * OS_KS) void out_sched_kernel(const float* hx, 
         e_in[j] = bload(rin, vo, 0);
         e_en[j] = bload(ren, vo, 0);
         e_mk[j] = bload(rmk, vo, 0);
+        if constexpr (SF != 0) e_h[j] = bload(rh, want_h ? vo : (int)0x80000000, 0);
         e_bias[j] = a.bias[n < a.Cout ? n : 0];
     }
 
@@ -231,7 +235,14 @@ __global__ __launch_bounds__(64 * OS_KS) void out_sched_kernel(const float* hx, 
         const float x = e_x[j];
         note_nonfinite(e, a.status, step);
         if (a.inter) a.inter[(((long long)step * a.B + b) * T + t) * a.Cout + n] = x / a.latent_scale;
-        float prev = ddim_prev(e, x, cfv, a.prediction_type);
+        float prev;
+        if constexpr (SF == 0) {
+            prev = ddim_prev(e, x, cfv, a.prediction_type);
+        } else {
+            float x0n = 0.f;
+            prev = solver_prev(e, x, cfv, a.prediction_type, e_h[j], x0n);
+            if (solver_code(cfv) >= SOLVER_DPM1) a.x0h[(long long)b * a.lat_bstride + (long long)n * a.pitch + t] = x0n;
+        }
         if (a.step_noise) prev = __fadd_rn(prev, __fmul_rn(cfv[4], e_nz[j]));
         else if (a.noise_seed) prev = __fadd_rn(prev, __fmul_rn(cfv[4], philox_normal(a.noise_seed[0], a.noise_seed[1], (unsigned)step, a.noise_elem0 + (unsigned)((b * T + t) * a.Cout + n))));
         if (a.mask) prev = mask_blend(prev, e_in[j], e_en[j], e_mk[j], cfv);
@@ -239,19 +250,21 @@ __global__ __launch_bounds__(64 * OS_KS) void out_sched_kernel(const float* hx, 
     }
 }
 
-template <bool CFG> __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a);   // (below)
+template <bool CFG, int SF> __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a);   // (below)
 static int out_sched_smem(bool cfg) {   // (the split-fp16 tile is the smaller one: 2 x 34 x 24 halfs against 24 x 40 floats)
     const int nh = cfg ? 2 : 1;
     const int stage = OS_KS * nh * OS_CW * OS_XP, red = OS_KS * nh * 16 * 64;
     return (nh * 2 * OS_C + OS_KS * GN_SCRATCH + (stage > red ? stage : red)) * (int)sizeof(float);
 }
 void configure_out_sched_kernel() {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&out_sched_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&out_sched_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&out_sched_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&out_sched_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&out_sched_tm_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&out_sched_tm_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+#define OS_ATTR(K, BYTES) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, BYTES)
+    OS_ATTR((out_sched_kernel<true, false, 0>), 160 * 1024); OS_ATTR((out_sched_kernel<false, false, 0>), 160 * 1024);
+    OS_ATTR((out_sched_kernel<true, true, 0>), 160 * 1024); OS_ATTR((out_sched_kernel<false, true, 0>), 160 * 1024);
+    OS_ATTR((out_sched_kernel<true, false, 1>), 160 * 1024); OS_ATTR((out_sched_kernel<false, false, 1>), 160 * 1024);
+    OS_ATTR((out_sched_kernel<true, true, 1>), 160 * 1024); OS_ATTR((out_sched_kernel<false, true, 1>), 160 * 1024);
+    OS_ATTR((out_sched_tm_kernel<true, 0>), 64 * 1024); OS_ATTR((out_sched_tm_kernel<false, 0>), 64 * 1024);
+    OS_ATTR((out_sched_tm_kernel<true, 1>), 64 * 1024); OS_ATTR((out_sched_tm_kernel<false, 1>), 64 * 1024);
+#undef OS_ATTR
 }
 bool out_sched_supports(const OutSchedArgs& a) {
     return a.Cin == OS_C && a.Cout <= 32 && a.guidance_rescale <= 0.f && a.gn_nparts < 0x7fff && a.T <= 0xffff && a.pitch <= 0xffff && a.B <= 0xffff &&
@@ -261,10 +274,15 @@ void launch_out_sched(const OutSchedArgs& a, hipStream_t s) {
     dim3 grid((a.T + 31) / 32, a.B);
     const int tp = a.T | (a.pitch << 16), bn = a.B | (a.gn_nparts << 16);
     const bool sp = a.ws != nullptr;   // split-fp16 products (engine.cpp: fp32 mode's default; said_debug_option "out_split")
-#define OS_LAUNCH(CFG, SP) hipLaunchKernelGGL((out_sched_kernel<CFG, SP>), grid, dim3(64 * OS_KS), out_sched_smem(CFG), s, a.x, a.gn_part, (SP) ? a.ws : a.w4, a.step_ptr, tp, (int)a.x_bstride, \
+#define OS_LAUNCH(CFG, SP, SF) hipLaunchKernelGGL((out_sched_kernel<CFG, SP, SF>), grid, dim3(64 * OS_KS), out_sched_smem(CFG), s, a.x, a.gn_part, (SP) ? a.ws : a.w4, a.step_ptr, tp, (int)a.x_bstride, \
                                               (int)a.gn_part_bstride, bn, a)
-    if (a.cfg) { if (sp) OS_LAUNCH(true, true); else OS_LAUNCH(true, false); }
-    else { if (sp) OS_LAUNCH(false, true); else OS_LAUNCH(false, false); }
+    if (a.solver == 0) {
+        if (a.cfg) { if (sp) OS_LAUNCH(true, true, 0); else OS_LAUNCH(true, false, 0); }
+        else { if (sp) OS_LAUNCH(false, true, 0); else OS_LAUNCH(false, false, 0); }
+    } else {
+        if (a.cfg) { if (sp) OS_LAUNCH(true, true, 1); else OS_LAUNCH(true, false, 1); }
+        else { if (sp) OS_LAUNCH(false, true, 1); else OS_LAUNCH(false, false, 1); }
+    }
 #undef OS_LAUNCH
 }
 
@@ -282,7 +300,7 @@ typedef __bf16 os_bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int os_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int OT_AP = 200, OT_ROWS = 34, OT_NP = 4;   // tile row pitch (elements), rows, 16-byte pieces per thread and sample (34 x 24 = 816 <= 4 x 256)
 
-template <bool CFG>
+template <bool CFG, int SF>
 __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NH = CFG ? 2 : 1;
@@ -321,8 +339,10 @@ __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a)
     const rsrc_t rin = make_rsrc(a.mask ? a.init + (long long)b * a.lat_bstride : nullptr, a.mask ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
     const rsrc_t ren = make_rsrc(a.mask ? a.edit_noise + (long long)b * a.lat_bstride : nullptr, a.mask ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
     const rsrc_t rmk = make_rsrc(a.mask ? a.mask + (long long)b * a.lat_bstride : nullptr, a.mask ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
-    float e_x[4], e_nz[4], e_in[4], e_en[4], e_mk[4], e_bias[4];
+    float e_x[4], e_nz[4], e_in[4], e_en[4], e_mk[4], e_bias[4], e_h[4];
     int e_n[4];
+    const bool want_h = SF != 0 && solver_code(cfv) == SOLVER_DPM2;   // (order 2 reads the previous step's x0)
+    const rsrc_t rh = make_rsrc(SF != 0 ? a.x0h + (long long)b * a.lat_bstride : nullptr, SF != 0 ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int r = w + 4 * j;
@@ -334,6 +354,7 @@ __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a)
         e_in[j] = bload(rin, vo, 0);
         e_en[j] = bload(ren, vo, 0);
         e_mk[j] = bload(rmk, vo, 0);
+        if constexpr (SF != 0) e_h[j] = bload(rh, want_h ? vo : (int)0x80000000, 0);
         e_bias[j] = a.bias[n < a.Cout ? n : 0];
     }
     // this wave's nine k16 steps of the [32][576] weight matrix (row = output channel, k = tap * 192 + channel); rows past Cout: row 0 again (unused)
@@ -426,7 +447,14 @@ __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a)
         const float x = e_x[j];
         note_nonfinite(e, a.status, step);
         if (a.inter) a.inter[(((long long)step * a.B + b) * T + t) * a.Cout + n] = x / a.latent_scale;
-        float prev = ddim_prev(e, x, cfv, a.prediction_type);
+        float prev;
+        if constexpr (SF == 0) {
+            prev = ddim_prev(e, x, cfv, a.prediction_type);
+        } else {
+            float x0n = 0.f;
+            prev = solver_prev(e, x, cfv, a.prediction_type, e_h[j], x0n);
+            if (solver_code(cfv) >= SOLVER_DPM1) a.x0h[(long long)b * a.lat_bstride + (long long)n * a.pitch + t] = x0n;
+        }
         if (a.step_noise) prev = __fadd_rn(prev, __fmul_rn(cfv[4], e_nz[j]));
         else if (a.noise_seed) prev = __fadd_rn(prev, __fmul_rn(cfv[4], philox_normal(a.noise_seed[0], a.noise_seed[1], (unsigned)step, a.noise_elem0 + (unsigned)((b * T + t) * a.Cout + n))));
         if (a.mask) prev = mask_blend(prev, e_in[j], e_en[j], e_mk[j], cfv);
@@ -443,8 +471,13 @@ bool out_sched_tm_supports(const OutSchedArgs& a) {
 }
 void launch_out_sched_tm(const OutSchedArgs& a, hipStream_t s) {
     dim3 grid((a.T + 31) / 32, a.B);
-    if (a.cfg) hipLaunchKernelGGL(out_sched_tm_kernel<true>, grid, dim3(256), out_sched_tm_smem(true), s, a);
-    else hipLaunchKernelGGL(out_sched_tm_kernel<false>, grid, dim3(256), out_sched_tm_smem(false), s, a);
+    if (a.solver == 0) {
+        if (a.cfg) hipLaunchKernelGGL((out_sched_tm_kernel<true, 0>), grid, dim3(256), out_sched_tm_smem(true), s, a);
+        else hipLaunchKernelGGL((out_sched_tm_kernel<false, 0>), grid, dim3(256), out_sched_tm_smem(false), s, a);
+    } else {
+        if (a.cfg) hipLaunchKernelGGL((out_sched_tm_kernel<true, 1>), grid, dim3(256), out_sched_tm_smem(true), s, a);
+        else hipLaunchKernelGGL((out_sched_tm_kernel<false, 1>), grid, dim3(256), out_sched_tm_smem(false), s, a);
+    }
 }
 
 }  // namespace said

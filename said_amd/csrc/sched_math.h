@@ -1,4 +1,4 @@
-// sched_math.h — the DDIM update as device functions shared by the stand-alone scheduler kernels (misc.hip) and the
+// sched_math.h — the DDIM, DDPM and DPM-Solver++ updates as device functions shared by the stand-alone scheduler kernels (misc.hip) and the
 // fused output-conv + scheduler kernel (out_sched.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,6 +30,36 @@ __device__ __forceinline__ float ddim_prev(float model_out, float x, const float
     x0 = (x0 != x0) ? x0 : fminf(fmaxf(x0, -1.0f), 1.0f);  // clip_sample=True, range 1.0 (torch.clamp keeps a NaN; fminf / fmaxf alone would turn it into -1)
     return __fadd_rn(__fmul_rn(sap, x0), __fmul_rn(dir, e));
 }
+// ------------------------------------------------------------------------------------------
+// DDPM and DPM-Solver++(2M) (diffusers 0.19 DDPMScheduler.step, DPMSolverMultistepScheduler.step).  The solver is per row:
+// coef column 7 (SAID_COEF_SOLVER) holds 1 = DDPM, 2 = DPM-Solver++ first order, 3 = second order (0 = DDIM: ddim_prev).
+// Columns 0 / 1 are the x0 conversion pair (sqrt(alpha_prod_t), sqrt(1 - alpha_prod_t)); then
+//   DDPM:  2 = pred_original_sample_coeff, 3 = current_sample_coeff, 4 = std (the caller adds std * noise, as for DDIM's sigma)
+//   DPM:   2 = sigma_t / sigma_s0, 3 = alpha_t * (exp(-h) - 1), 4 = 1 / r0 (order 2)
+// The previous step's x0 (order 2's m1) lives in `x0_prev`; every DPM row returns its own x0 in `x0_out` for the next step.
+// ------------------------------------------------------------------------------------------
+constexpr int SOLVER_DDIM = 0, SOLVER_DDPM = 1, SOLVER_DPM1 = 2, SOLVER_DPM2 = 3;
+__device__ __forceinline__ int solver_code(const float* cf) { return (int)cf[7]; }
+__device__ __forceinline__ float solver_prev(float model_out, float x, const float* cf, int pred, float x0_prev, float& x0_out) {
+    const float sa = cf[0], sb = cf[1];
+    const int code = solver_code(cf);
+    float x0;
+    if (pred == 0) x0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(sb, model_out)), sa);
+    else if (pred == 1) x0 = model_out;
+    else x0 = __fsub_rn(__fmul_rn(sa, x), __fmul_rn(sb, model_out));
+    if (code == SOLVER_DDPM) {
+        x0 = (x0 != x0) ? x0 : fminf(fmaxf(x0, -1.0f), 1.0f);   // clip_sample=True, range 1.0 (NaN kept, as torch.clamp)
+        return __fadd_rn(__fmul_rn(cf[2], x0), __fmul_rn(cf[3], x));
+    }
+    x0_out = x0;
+    float prev = __fsub_rn(__fmul_rn(cf[2], x), __fmul_rn(cf[3], x0));
+    if (code == SOLVER_DPM2) {   // - 0.5 * (alpha_t * (exp(-h) - 1)) * ((1 / r0) * (m0 - m1)); the halving is exact
+        const float d1 = __fmul_rn(cf[4], __fsub_rn(x0, x0_prev));
+        prev = __fsub_rn(prev, __fmul_rn(0.5f * cf[3], d1));
+    }
+    return prev;
+}
+
 // The model output of a step is not finite: remember the first such step (said_numeric_status).  fp32 mode multiplies on split-fp16 operands
 // (split_f16.h: |x| < 65504); an operand beyond that becomes inf / NaN in its product and reaches this point through every later layer.
 __device__ __forceinline__ void note_nonfinite(float model_out, int* status, int step) {

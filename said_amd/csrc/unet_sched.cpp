@@ -952,7 +952,10 @@ void run_unet(said_ctx* c, const UGeo& g, hipStream_t s) {
     run_transformer(c, g, c->st[3], 3, c->Q, c->P, s);               // output_blocks.1.1
     }
     if (g.out_sched) {   // out conv + guidance + DDIM update in one kernel (out_sched.hip)
-        if (dbg_go(c)) { if (out_tm) launch_out_sched_tm(osa_tm, s); else launch_out_sched(*g.out_sched, s); }
+        if (dbg_go(c)) {
+            if (out_tm) { launch_out_sched_tm(osa_tm, s); ++c->n_out_sched_tm; }
+            else { launch_out_sched(*g.out_sched, s); ++c->n_out_sched; }
+        }
     } else {   // out: GN -> SiLU -> Conv1d(192 -> 32, k3)
         GemmArgs a = mkargs(g.T, c->cin);
         a.nseg = 1;

@@ -27,7 +27,7 @@ import torch
 from torch import nn
 
 from .. import _engine
-from ..scheduler import DDIMScheduler
+from ..scheduler import DDIMScheduler, check_engine_scheduler
 from .processor import AudioProcessor
 from .unet_1d_condition import UNet1DConditionModel
 from .wav2vec2 import AudioConfig, ModifiedWav2Vec2Model
@@ -179,7 +179,6 @@ class SAID(ABC, nn.Module):
             e.load_weights(self.state_dict())
             self._eng, self._eng_key, self._eng_stale = e, self._weights_key(), False
             self._clones = []      # (closed with the old engine)
-            self.noise_scheduler._engine = e
         elif e.max_batch_eff < batch_eff or e.max_frames < frames:
             # a larger batch or a longer clip: only the workspace grows, the packed weights stay where they are
             try:
@@ -193,6 +192,8 @@ class SAID(ABC, nn.Module):
                 self._eng = None
                 raise
         e.set_precision(self.mfma_dtype)
+        if hasattr(self.noise_scheduler, "_need_engine"):   # (also a scheduler swapped in after the engine was built: model.noise_scheduler = ...)
+            self.noise_scheduler._engine = e
         return e
 
     def set_mfma_dtype(self, dtype: str) -> "SAID":
@@ -332,15 +333,24 @@ class SAID(ABC, nn.Module):
                   step_noise: Optional[torch.Tensor] = None,
                   audio_embedding: Optional[torch.Tensor] = None) -> SAIDInferenceOutput:
         """Inference pipeline (diffusion.py:308-472): schedule, start noise, optional init/mask
-        editing, classifier-free guidance, DDIM updates, final clamp to [0, 1]."""
+        editing, classifier-free guidance, scheduler updates (DDIM, DDPM or DPM-Solver++: said_amd.scheduler), final clamp to [0, 1]."""
+        sch = self.noise_scheduler
+        check_engine_scheduler(sch)   # before any GPU work
         batch_size, waveform_len = waveform_processed.shape
         in_channels = self.denoiser.in_channels
         device = waveform_processed.device
         do_cfg = guidance_scale > 1.0
         window_size = int(waveform_len / self.sampling_rate * fps)
-        eng = self._get_engine(2 * batch_size if do_cfg else batch_size, window_size)
-        sch = self.noise_scheduler
         sch.set_timesteps(num_inference_steps)
+        n_sched = len(sch.timesteps)   # DPM-Solver++ drops duplicate timesteps: fewer than num_inference_steps from 1000 steps on
+        init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
+        t_start = num_inference_steps - init_timestep
+        if init_samples is not None and init_timestep > n_sched:   # the reference's timesteps[-init_timestep] (diffusion.py:375)
+            raise ValueError(f"strength {strength} needs timestep {-init_timestep} of a {n_sched}-step schedule ({type(sch).__name__})")
+        if init_samples is not None and mask is not None and t_start < n_sched < num_inference_steps:   # ... and timesteps[tdx_next] (:449-451)
+            raise ValueError(f"masked editing indexes timestep {n_sched} of a {n_sched}-step schedule ({type(sch).__name__}, "
+                             f"num_inference_steps={num_inference_steps})")
+        eng = self._get_engine(2 * batch_size if do_cfg else batch_size, window_size)
 
         if init_samples is None:
             latents = init_latents.to(device) if init_latents is not None else torch.randn(batch_size, window_size, in_channels, device=device)
@@ -350,7 +360,6 @@ class SAID(ABC, nn.Module):
         if scale0 != 1.0:
             latents = eng.axpby([scale0] * batch_size, latents)
         init_lat = latents.clone()
-        init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
 
         noise = None
         if init_samples is not None:
@@ -365,12 +374,11 @@ class SAID(ABC, nn.Module):
             audio_embedding = self._encode_distinct(waveform_processed, window_size) if (batch_size > 1 and self.dedupe_audio) \
                 else self.get_audio_embedding(waveform_processed, window_size)
 
-        t_start = num_inference_steps - init_timestep
         ts = sch.timesteps[t_start:].cpu().numpy().astype(np.int64)
         n_run = len(ts)
         coef = sch.coef_table(ts, float(eta))
         noise_steps, noise_seed = None, None
-        if eta > 0 and n_run > 0:
+        if sch.draws_step_noise(float(eta)) and n_run > 0:   # DDIM: eta > 0; DDPM: always; DPM-Solver++: never
             if step_noise is not None:   # injected by the caller (tests: the CPU oracle is fed the same draws)
                 noise_steps = step_noise.to(device)
             else:

@@ -17,7 +17,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from said_amd.model.diffusion import SAID_UNet1D  # noqa: E402
-from said_amd.scheduler import DDIMScheduler  # noqa: E402
+from said_amd.scheduler import SCHEDULERS, DDIMScheduler  # noqa: E402
 from said_amd.util.audio import fit_audio_unet, load_audio  # noqa: E402
 
 # flag -> (type, default, description).  `bool` flags keep argparse's type=bool behaviour of the reference
@@ -55,6 +55,9 @@ def parser_with(description: str, names: Iterable[str]) -> argparse.ArgumentPars
     for name in names:
         typ, default, text = FLAG_TABLE[name]
         ap.add_argument("--" + name, type=typ, default=default, help=text)
+    # Not a reference flag: the reference selects its sampler in code (the noise_scheduler slot of SAID).  Both drivers get it here.
+    ap.add_argument("--scheduler", choices=sorted(SCHEDULERS), default="ddim",
+                    help="sampler: ddim (default), ddpm or dpmsolver++ (DPM-Solver++(2M)); --eta only affects ddim")
     return ap
 
 
@@ -67,6 +70,9 @@ def make_model(args) -> SAID_UNet1D:
     else:
         state = torch.load(args.weights_path, map_location="cpu")
     net.load_state_dict(state, strict=True)
+    name = getattr(args, "scheduler", "ddim")
+    if name != "ddim":   # SAID_UNet1D does not forward noise_scheduler (as in the reference): set the slot itself
+        net.noise_scheduler = SCHEDULERS[name](num_train_timesteps=1000, beta_schedule="squaredcos_cap_v2", prediction_type=args.prediction_type)
     return net.to(args.device).eval()
 
 
