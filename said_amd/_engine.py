@@ -578,3 +578,159 @@ def unet_algorithmic_bytes(batch_eff: int, frames: int, bytes_per_elem: int = 4)
 
 def unet_algorithmic_flops(batch_eff: int, frames: int) -> float:
     return float(load_library().said_unet_algorithmic_flops(batch_eff, frames))
+
+
+# ---- evaluation metrics (include/said_metrics.h): a table of their own, bound on first use, outside EXPORTS and the ABI version of said_hip.h
+_c_double_p, _c_ll_p = POINTER(c_double), POINTER(ctypes.c_longlong)
+METRICS_EXPORTS = {
+    "said_metrics_create": (c_int, [POINTER(c_void_p), c_int, ctypes.c_longlong]),
+    "said_metrics_destroy": (c_int, [c_void_p]),
+    "said_metrics_last_error": (c_char_p, [c_void_p]),
+    "said_metrics_max_points": (ctypes.c_longlong, [c_void_p]),
+    "said_metrics_weighted_sums": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, _c_double_p, _c_double_p, c_void_p]),
+    "said_metrics_weighted_scatter": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, _c_double_p, _c_double_p, c_void_p]),
+    "said_metrics_gmm_estep": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "said_metrics_kmeans_assign": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, _c_double_p, c_int, _c_ll_p, _c_double_p, c_void_p]),
+    "said_metrics_kmeans_read": (c_int, [c_void_p, ctypes.c_longlong, POINTER(c_int), _c_double_p, c_void_p]),
+    "said_metrics_kmeans_set_labels": (c_int, [c_void_p, ctypes.c_longlong, c_int, POINTER(c_int), c_void_p]),
+    "said_metrics_kmeanspp_first": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_longlong, _c_double_p, c_void_p]),
+    "said_metrics_kmeanspp_step": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, _c_double_p, c_int, _c_ll_p, _c_double_p, c_void_p]),
+}
+METRICS_DIM, METRICS_MAX_K = 64, 8
+W_UNIT, W_LABELS, W_RESP = 0, 1, 2   # SAID_METRICS_W_*
+_metrics_bound = False
+
+
+def load_metrics_library():
+    """The engine library with the said_metrics.h entry points bound."""
+    global _metrics_bound
+    lib = load_library()
+    if not _metrics_bound:
+        for name, (res, args) in METRICS_EXPORTS.items():
+            if not hasattr(lib, name):
+                raise EngineError(f"{_LIB_PATH} predates the metrics passes ({name} is not exported): rebuild it with `python -m said_amd.build --force`")
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _metrics_bound = True
+    return lib
+
+
+def _dp(a: np.ndarray):
+    return a.ctypes.data_as(_c_double_p)
+
+
+class MetricsEngine:
+    """said_metrics context on one GPU (include/said_metrics.h): workspace for up to `max_points` (n, 64) fp32 latents."""
+
+    def __init__(self, device: torch.device, max_points: int):
+        self.lib = load_metrics_library()
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise NoCpuPathError(f"said_amd computes the metrics on MI355X only (device={device}); there is no CPU path")
+        self.device = device
+        self.index = device.index if device.index is not None else torch.cuda.current_device()
+        h = c_void_p()
+        if self.lib.said_metrics_create(ctypes.byref(h), self.index, int(max_points)) != 0:
+            raise EngineError("said_metrics_create: " + (self.lib.said_metrics_last_error(None) or b"?").decode())
+        self.h = h
+        self.max_points = int(max_points)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.said_metrics_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc: int, what: str):
+        if rc != 0:
+            raise EngineError(f"{what}: " + (self.lib.said_metrics_last_error(self.h) or b"?").decode())
+
+    def _x(self, x: torch.Tensor) -> torch.Tensor:
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != METRICS_DIM or not x.is_contiguous():
+            raise EngineError(f"latents must be a contiguous (n, {METRICS_DIM}) float32 device tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
+        if x.device.index != self.index:
+            raise EngineError(f"latents live on cuda:{x.device.index}, this metrics context on cuda:{self.index}")
+        if x.shape[0] > self.max_points:
+            raise EngineError(f"{x.shape[0]} latents exceed this context's max_points {self.max_points}")
+        return x
+
+    def weighted_sums(self, x: torch.Tensor, k: int, wsrc: int):
+        """(n_k (k,), sum r x (k, 64)) in float64."""
+        x = self._x(x)
+        nk, sx = np.zeros(k), np.zeros((k, METRICS_DIM))
+        with torch.cuda.device(self.index):
+            self._chk(self.lib.said_metrics_weighted_sums(self.h, _ptr(x), x.shape[0], k, wsrc, _dp(nk), _dp(sx), _stream()), "said_metrics_weighted_sums")
+        return nk, sx
+
+    def weighted_scatter(self, x: torch.Tensor, k: int, wsrc: int, means: np.ndarray) -> np.ndarray:
+        """sum r (x - mu_k)(x - mu_k)^T, (k, 64, 64) float64."""
+        x = self._x(x)
+        mu = np.ascontiguousarray(means, dtype=np.float64).reshape(k, METRICS_DIM)
+        out = np.zeros((k, METRICS_DIM, METRICS_DIM))
+        with torch.cuda.device(self.index):
+            self._chk(self.lib.said_metrics_weighted_scatter(self.h, _ptr(x), x.shape[0], k, wsrc, _dp(mu), _dp(out), _stream()),
+                      "said_metrics_weighted_scatter")
+        return out
+
+    def gmm_estep(self, x: torch.Tensor, prec_chol: np.ndarray, mean_prec: np.ndarray, log_det: np.ndarray, log_weights: np.ndarray,
+                  want_resp: bool = False):
+        """Mean log_prob_norm (the lower bound); with want_resp also the (n, k) log-responsibilities and (n,) log_prob_norm, float64 device tensors."""
+        x = self._x(x)
+        k = prec_chol.shape[0]
+        args = [np.ascontiguousarray(a, dtype=np.float64) for a in (prec_chol, mean_prec, log_det, log_weights)]
+        lb = np.zeros(1)
+        lr = lpn = None
+        if want_resp:
+            lr = torch.empty(x.shape[0], k, dtype=torch.float64, device=x.device)
+            lpn = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
+        with torch.cuda.device(self.index):
+            self._chk(self.lib.said_metrics_gmm_estep(self.h, _ptr(x), x.shape[0], k, *[_dp(a) for a in args], _dp(lb), _ptr(lr), _ptr(lpn), _stream()),
+                      "said_metrics_gmm_estep")
+        return (float(lb[0]), lr, lpn) if want_resp else float(lb[0])
+
+    def kmeans_assign(self, x: torch.Tensor, centres: np.ndarray, compare: bool):
+        """(labels changed since the previous assignment (n when not compared), inertia)."""
+        x = self._x(x)
+        c = np.ascontiguousarray(centres, dtype=np.float64)
+        changed, inertia = ctypes.c_longlong(0), np.zeros(1)
+        with torch.cuda.device(self.index):
+            self._chk(self.lib.said_metrics_kmeans_assign(self.h, _ptr(x), x.shape[0], c.shape[0], _dp(c), int(bool(compare)), ctypes.byref(changed),
+                                                          _dp(inertia), _stream()), "said_metrics_kmeans_assign")
+        return int(changed.value), float(inertia[0])
+
+    def kmeans_read(self, n: int):
+        """(labels int32 (n,), squared distance to the assigned centre float64 (n,)) of the last assignment."""
+        lab, dist = np.zeros(n, dtype=np.int32), np.zeros(n)
+        with torch.cuda.device(self.index):
+            self._chk(self.lib.said_metrics_kmeans_read(self.h, n, lab.ctypes.data_as(POINTER(c_int)), _dp(dist), _stream()), "said_metrics_kmeans_read")
+        return lab, dist
+
+    def kmeans_set_labels(self, labels: np.ndarray, k: int):
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        with torch.cuda.device(self.index):
+            self._chk(self.lib.said_metrics_kmeans_set_labels(self.h, lab.shape[0], k, lab.ctypes.data_as(POINTER(c_int)), _stream()),
+                      "said_metrics_kmeans_set_labels")
+
+    def kmeanspp_first(self, x: torch.Tensor, centre_id: int) -> float:
+        x = self._x(x)
+        pot = np.zeros(1)
+        with torch.cuda.device(self.index):
+            self._chk(self.lib.said_metrics_kmeanspp_first(self.h, _ptr(x), x.shape[0], int(centre_id), _dp(pot), _stream()), "said_metrics_kmeanspp_first")
+        return float(pot[0])
+
+    def kmeanspp_step(self, x: torch.Tensor, rand_vals: np.ndarray):
+        """(chosen point index, its potential) for candidate values rand_vals (uniform * current potential)."""
+        x = self._x(x)
+        r = np.ascontiguousarray(rand_vals, dtype=np.float64)
+        cid, pot = ctypes.c_longlong(0), np.zeros(1)
+        with torch.cuda.device(self.index):
+            self._chk(self.lib.said_metrics_kmeanspp_step(self.h, _ptr(x), x.shape[0], _dp(r), r.shape[0], ctypes.byref(cid), _dp(pot), _stream()),
+                      "said_metrics_kmeanspp_step")
+        return int(cid.value), float(pot[0])
