@@ -734,3 +734,108 @@ class MetricsEngine:
             self._chk(self.lib.said_metrics_kmeanspp_step(self.h, _ptr(x), x.shape[0], _dp(r), r.shape[0], ctypes.byref(cid), _dp(pot), _stream()),
                       "said_metrics_kmeanspp_step")
         return int(cid.value), float(pot[0])
+
+
+# ---- blendshape-coefficient fit (include/said_optimize.h): a table of its own, bound on first use, outside EXPORTS and the ABI version of said_hip.h
+OPTIMIZE_EXPORTS = {
+    "said_optimize_create": (c_int, [POINTER(c_void_p), c_int]),
+    "said_optimize_destroy": (c_int, [c_void_p]),
+    "said_optimize_last_error": (c_char_p, [c_void_p]),
+    "said_optimize_set_bases": (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong, _c_double_p, _c_double_p, _c_double_p, c_void_p]),
+    "said_optimize_rhs": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "said_optimize_solve": (c_int, [c_void_p, c_int, _c_ll_p, POINTER(c_int), c_void_p, c_double, c_int, c_int, c_double, c_void_p, c_void_p,
+                                    POINTER(c_int), POINTER(c_int), _c_double_p, c_void_p]),
+}
+OPTIMIZE_MAX_K = 64
+OPT_CONVERGED, OPT_MAX_ITER, OPT_NOT_FINITE = 0, 1, 2   # SAID_OPTIMIZE_*
+_optimize_bound = False
+
+
+def load_optimize_library():
+    """The engine library with the said_optimize.h entry points bound."""
+    global _optimize_bound
+    lib = load_library()
+    if not _optimize_bound:
+        for name, (res, args) in OPTIMIZE_EXPORTS.items():
+            if not hasattr(lib, name):
+                raise EngineError(f"{_LIB_PATH} predates the blendshape fit ({name} is not exported): rebuild it with `python -m said_amd.build --force`")
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _optimize_bound = True
+    return lib
+
+
+class OptimizeEngine:
+    """said_optimize context on one GPU (include/said_optimize.h): the bases of a batch, the rhs kernel and the batched QP solver."""
+
+    def __init__(self, device: torch.device):
+        self.lib = load_optimize_library()
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise NoCpuPathError(f"said_amd fits blendshape coefficients on MI355X only (device={device}); there is no CPU path")
+        self.device = device
+        self.index = device.index if device.index is not None else torch.cuda.current_device()
+        h = c_void_p()
+        if self.lib.said_optimize_create(ctypes.byref(h), self.index) != 0:
+            raise EngineError("said_optimize_create: " + (self.lib.said_optimize_last_error(None) or b"?").decode())
+        self.h = h
+        self.k = 0
+        self.n3v = 0
+        self.nbasis = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.said_optimize_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc: int, what: str):
+        if rc != 0:
+            raise EngineError(f"{what}: " + (self.lib.said_optimize_last_error(self.h) or b"?").decode())
+
+    def set_bases(self, neutrals: np.ndarray, bdeltas: np.ndarray, ps: np.ndarray):
+        """neutrals (nb, 3V), bdeltas (nb, 3V, K) = B - n, ps (nb, K, K) = B_delta' B_delta, float64."""
+        n = np.ascontiguousarray(neutrals, dtype=np.float64)
+        b = np.ascontiguousarray(bdeltas, dtype=np.float64)
+        p = np.ascontiguousarray(ps, dtype=np.float64)
+        nb, n3v, k = b.shape
+        with torch.cuda.device(self.index):
+            self._chk(self.lib.said_optimize_set_bases(self.h, nb, k, n3v, _dp(n), _dp(b), _dp(p), _stream()), "said_optimize_set_bases")
+        self.nbasis, self.n3v, self.k = nb, n3v, k
+
+    def rhs(self, basis: int, verts: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """q (frames, K) float64 device tensor for verts, a contiguous (frames, 3V) float64 device tensor."""
+        if not verts.is_cuda or verts.dtype != torch.float64 or verts.dim() != 2 or verts.shape[1] != self.n3v or not verts.is_contiguous():
+            raise EngineError(f"vertices must be a contiguous (frames, {self.n3v}) float64 device tensor, got {tuple(verts.shape)} {verts.dtype}")
+        if out is None:
+            out = torch.empty(verts.shape[0], self.k, dtype=torch.float64, device=verts.device)
+        with torch.cuda.device(self.index):
+            self._chk(self.lib.said_optimize_rhs(self.h, int(basis), _ptr(verts), verts.shape[0], _ptr(out), _stream()), "said_optimize_rhs")
+        return out
+
+    def solve(self, q: torch.Tensor, offsets: np.ndarray, basis: np.ndarray, delta: float, coupled: bool, max_iter: int, tol: float,
+              want_duals: bool = False):
+        """(w (frames, K), z (frames, 4, K) or None, status, iters, resid (nseq, 3)); w and z float64 device tensors."""
+        if not q.is_cuda or q.dtype != torch.float64 or q.dim() != 2 or q.shape[1] != self.k or not q.is_contiguous():
+            raise EngineError(f"q must be a contiguous (frames, {self.k}) float64 device tensor")
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        bas = np.ascontiguousarray(basis, dtype=np.int32)
+        nseq = bas.shape[0]
+        if offs.shape != (nseq + 1,) or offs[-1] != q.shape[0]:
+            raise EngineError(f"offsets must have nseq + 1 = {nseq + 1} entries ending at the {q.shape[0]} frames of q")
+        w = torch.empty_like(q)
+        z = torch.empty(q.shape[0], 4, self.k, dtype=torch.float64, device=q.device) if want_duals else None
+        st, it = np.zeros(nseq, dtype=np.int32), np.zeros(nseq, dtype=np.int32)
+        res = np.zeros((nseq, 3))
+        ip = POINTER(c_int)
+        with torch.cuda.device(self.index):
+            self._chk(self.lib.said_optimize_solve(self.h, nseq, offs.ctypes.data_as(_c_ll_p), bas.ctypes.data_as(ip), _ptr(q), float(delta),
+                                                   int(bool(coupled)), int(max_iter), float(tol), _ptr(w), _ptr(z), st.ctypes.data_as(ip),
+                                                   it.ctypes.data_as(ip), _dp(res), _stream()), "said_optimize_solve")
+        return w, z, st, it, res
