@@ -839,3 +839,156 @@ class OptimizeEngine:
                                                    int(bool(coupled)), int(max_iter), float(tol), _ptr(w), _ptr(z), st.ctypes.data_as(ip),
                                                    it.ctypes.data_as(ip), _dp(res), _stream()), "said_optimize_solve")
         return w, z, st, it, res
+
+
+# ---- BCVAE trainer (include/said_train.h): a table of its own, bound on first use, outside EXPORTS and the ABI version of said_hip.h
+_c_float_p = POINTER(c_float)
+TRAIN_EXPORTS = {
+    "said_train_create": (c_int, [POINTER(c_void_p), c_int, c_int]),
+    "said_train_destroy": (c_int, [c_void_p]),
+    "said_train_last_error": (c_char_p, [c_void_p]),
+    "said_train_tensor_name": (c_char_p, [c_int]),
+    "said_train_tensor_numel": (ctypes.c_longlong, [c_int]),
+    "said_train_tensor_is_counter": (c_int, [c_int]),
+    "said_train_set_tensor": (c_int, [c_void_p, c_int, c_char_p, c_void_p, ctypes.c_longlong]),
+    "said_train_get_tensor": (c_int, [c_void_p, c_int, c_char_p, c_void_p, ctypes.c_longlong]),
+    "said_train_reset_optimizer": (c_int, [c_void_p]),
+    "said_train_set_data": (c_int, [c_void_p, c_int, _c_float_p, ctypes.c_longlong, _c_ll_p, POINTER(c_int), c_int, POINTER(c_int)]),
+    "said_train_gather": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), _c_float_p]),
+    "said_train_step": (c_int, [c_void_p, c_int, POINTER(c_int), _c_float_p, _c_float_p, _c_float_p, c_int]),
+    "said_train_apply_update": (c_int, [c_void_p, _c_float_p]),
+    "said_train_eval_loss": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), _c_float_p, _c_float_p, _c_float_p, c_int]),
+    "said_train_read_losses": (c_int, [c_void_p, c_int, _c_double_p, POINTER(c_int), c_int]),
+    "said_train_last_losses": (c_int, [c_void_p, _c_float_p]),
+    "said_train_bn_stats": (c_int, [c_void_p, c_int, _c_float_p]),
+    "said_train_graph_count": (c_int, [c_void_p]),
+}
+# SAID_TRAIN_* of include/said_train.h
+TRAIN_NSCAL, TRAIN_NACC, TRAIN_ITEM = 16, 8, 4
+(TRAIN_S_LR, TRAIN_S_WD_FACTOR, TRAIN_S_STEP_SIZE, TRAIN_S_BC2_SQRT, TRAIN_S_EMA_OMD, TRAIN_S_BETA, TRAIN_S_WVEL, TRAIN_S_OMB1, TRAIN_S_B2,
+ TRAIN_S_OMB2, TRAIN_S_EPS, TRAIN_S_USE_EMA) = range(12)
+TRAIN_STATE, TRAIN_EMA, TRAIN_GRAD, TRAIN_EXP_AVG, TRAIN_EXP_AVG_SQ = range(5)
+TRAIN_OK, TRAIN_NOT_FINITE = 0, 1
+TRAIN_SET_TRAIN, TRAIN_SET_VAL = 0, 1
+_train_bound = False
+
+
+def load_train_library():
+    """The engine library with the said_train.h entry points bound."""
+    global _train_bound
+    lib = load_library()
+    if not _train_bound:
+        for name, (res, args) in TRAIN_EXPORTS.items():
+            if not hasattr(lib, name):
+                raise EngineError(f"{_LIB_PATH} predates the BCVAE trainer ({name} is not exported): rebuild it with `python -m said_amd.build --force`")
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _train_bound = True
+    return lib
+
+
+def _f32(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _i32(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+class TrainEngine:
+    """said_train context on one GPU (include/said_train.h): the BCVAE's parameters, buffers, gradients, Adam moments and EMA shadow, the
+    window sets, and the captured training step.  Host arrays in and out (numpy); the context keeps its own stream."""
+
+    def __init__(self, device: torch.device, max_batch: int):
+        self.lib = load_train_library()
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise NoCpuPathError(f"said_amd trains the BCVAE on MI355X only (device={device}); there is no CPU path")
+        self.device = device
+        self.index = device.index if device.index is not None else torch.cuda.current_device()
+        h = c_void_p()
+        if self.lib.said_train_create(ctypes.byref(h), self.index, int(max_batch)) != 0:
+            raise EngineError("said_train_create: " + (self.lib.said_train_last_error(None) or b"?").decode())
+        self.h = h
+        self.max_batch = int(max_batch)
+        self.tensors = [(self.lib.said_train_tensor_name(i).decode(), int(self.lib.said_train_tensor_numel(i)),
+                         bool(self.lib.said_train_tensor_is_counter(i))) for i in range(70)]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.said_train_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc: int, what: str):
+        if rc != 0:
+            raise EngineError(f"{what}: " + (self.lib.said_train_last_error(self.h) or b"?").decode())
+
+    def set_tensor(self, which: int, name: str, value) -> None:
+        a = np.ascontiguousarray(value, dtype=np.int64 if name.endswith("num_batches_tracked") else np.float32).reshape(-1)
+        self._chk(self.lib.said_train_set_tensor(self.h, which, name.encode(), a.ctypes.data_as(c_void_p), a.size), "said_train_set_tensor")
+
+    def get_tensor(self, which: int, name: str, numel: int) -> np.ndarray:
+        a = np.empty(numel, dtype=np.int64 if name.endswith("num_batches_tracked") else np.float32)
+        self._chk(self.lib.said_train_get_tensor(self.h, which, name.encode(), a.ctypes.data_as(c_void_p), numel), "said_train_get_tensor")
+        return a
+
+    def reset_optimizer(self) -> None:
+        self._chk(self.lib.said_train_reset_optimizer(self.h), "said_train_reset_optimizer")
+
+    def set_data(self, which_set: int, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, mirror: np.ndarray) -> None:
+        fr, off, ln, mi = _f32(frames), np.ascontiguousarray(offsets, dtype=np.int64), _i32(lengths), _i32(mirror)
+        self._chk(self.lib.said_train_set_data(self.h, which_set, fr.ctypes.data_as(_c_float_p), fr.shape[0], off.ctypes.data_as(_c_ll_p),
+                                               ln.ctypes.data_as(POINTER(c_int)), ln.size, mi.ctypes.data_as(POINTER(c_int))), "said_train_set_data")
+
+    def gather(self, which_set: int, items: np.ndarray) -> np.ndarray:
+        it = _i32(items)
+        x = np.empty((it.shape[0], 120, 32), dtype=np.float32)
+        self._chk(self.lib.said_train_gather(self.h, which_set, it.shape[0], it.ctypes.data_as(POINTER(c_int)), x.ctypes.data_as(_c_float_p)),
+                  "said_train_gather")
+        return x
+
+    @staticmethod
+    def _opt_f32(a):
+        return None if a is None else _f32(a)
+
+    def step(self, items: np.ndarray, eps: np.ndarray, scalars: np.ndarray, std: Optional[np.ndarray], use_graph: bool = True) -> None:
+        it, ep, sc, sd = _i32(items), _f32(eps), _f32(scalars), self._opt_f32(std)
+        self._chk(self.lib.said_train_step(self.h, it.shape[0], it.ctypes.data_as(POINTER(c_int)), ep.ctypes.data_as(_c_float_p),
+                                           sc.ctypes.data_as(_c_float_p), None if sd is None else sd.ctypes.data_as(_c_float_p), int(bool(use_graph))),
+                  "said_train_step")
+
+    def apply_update(self, scalars: np.ndarray) -> None:
+        sc = _f32(scalars)
+        self._chk(self.lib.said_train_apply_update(self.h, sc.ctypes.data_as(_c_float_p)), "said_train_apply_update")
+
+    def eval_loss(self, which_set: int, items: np.ndarray, eps: np.ndarray, scalars: np.ndarray, std: Optional[np.ndarray], ema: bool) -> None:
+        it, ep, sc, sd = _i32(items), _f32(eps), _f32(scalars), self._opt_f32(std)
+        self._chk(self.lib.said_train_eval_loss(self.h, which_set, it.shape[0], it.ctypes.data_as(POINTER(c_int)), ep.ctypes.data_as(_c_float_p),
+                                                sc.ctypes.data_as(_c_float_p), None if sd is None else sd.ctypes.data_as(_c_float_p), int(bool(ema))),
+                  "said_train_eval_loss")
+
+    def read_losses(self, val: bool, reset: bool = True):
+        acc = np.zeros(TRAIN_NACC, dtype=np.float64)
+        st = c_int(0)
+        self._chk(self.lib.said_train_read_losses(self.h, int(bool(val)), _dp(acc), ctypes.byref(st), int(bool(reset))), "said_train_read_losses")
+        return acc, int(st.value)
+
+    def last_losses(self) -> np.ndarray:
+        out = np.zeros(4, dtype=np.float32)
+        self._chk(self.lib.said_train_last_losses(self.h, out.ctypes.data_as(_c_float_p)), "said_train_last_losses")
+        return out
+
+    def bn_stats(self, bn: int, channels: int) -> np.ndarray:
+        out = np.zeros(2 * channels, dtype=np.float32)
+        self._chk(self.lib.said_train_bn_stats(self.h, bn, out.ctypes.data_as(_c_float_p)), "said_train_bn_stats")
+        return out.reshape(2, channels)
+
+    def graph_count(self) -> int:
+        return int(self.lib.said_train_graph_count(self.h))
