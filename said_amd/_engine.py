@@ -1,4 +1,4 @@
-"""ctypes binding of libsaid_hip.so (C ABI: include/said_hip.h).
+"""ctypes binding of libsaid_hip.so (C ABI: include/said_hip.h, said_metrics.h, said_optimize.h, said_train.h).
 
 There is deliberately no fallback: if the library is missing, cannot be loaded,
 or no gfx950 device is visible, every entry point raises.
@@ -26,6 +26,10 @@ ABI_VERSION = 9   # include/said_hip.h as bound below; a stale libsaid_hip.so is
 
 class EngineError(RuntimeError):
     pass
+
+
+class NoCpuPathError(EngineError, NotImplementedError):
+    """A model method called on a CPU-resident model: said_amd computes on the MI355X only."""
 
 
 class LoopParams(ctypes.Structure):
@@ -93,37 +97,94 @@ EXPORTS = {
     "said_vae_has_decoder": (c_int, [c_void_p]),
     "said_vae_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
 }
-# Added without an ABI version bump: a library built before them still loads (everything else works) and the decoder
-# entry points raise "rebuild" when called (VaeEngine.decode).
-LATE_EXPORTS = frozenset({"said_vae_has_decoder", "said_vae_decode"})
+_c_float_p, _c_double_p, _c_ll_p = POINTER(c_float), POINTER(c_double), POINTER(ctypes.c_longlong)
+# Groups bound on first use (load_library(group)), outside the ABI version of said_hip.h: a library built before a group still loads, and only
+# what uses the group raises "rebuild".  group: (what a library without it predates, its table).
+LAZY_EXPORTS = {
+    # said_hip.h entries added without an ABI version bump: part of EXPORTS, but not bound at load
+    "vae_decoder": ("the VAE decoder", {n: EXPORTS[n] for n in ("said_vae_has_decoder", "said_vae_decode")}),
+    "metrics": ("the metrics passes", {   # include/said_metrics.h
+        "said_metrics_create": (c_int, [POINTER(c_void_p), c_int, ctypes.c_longlong]),
+        "said_metrics_destroy": (c_int, [c_void_p]),
+        "said_metrics_last_error": (c_char_p, [c_void_p]),
+        "said_metrics_max_points": (ctypes.c_longlong, [c_void_p]),
+        "said_metrics_weighted_sums": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, _c_double_p, _c_double_p, c_void_p]),
+        "said_metrics_weighted_scatter": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, _c_double_p, _c_double_p, c_void_p]),
+        "said_metrics_gmm_estep": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                           _c_double_p, c_void_p, c_void_p, c_void_p]),
+        "said_metrics_kmeans_assign": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, _c_double_p, c_int, _c_ll_p, _c_double_p, c_void_p]),
+        "said_metrics_kmeans_read": (c_int, [c_void_p, ctypes.c_longlong, POINTER(c_int), _c_double_p, c_void_p]),
+        "said_metrics_kmeans_set_labels": (c_int, [c_void_p, ctypes.c_longlong, c_int, POINTER(c_int), c_void_p]),
+        "said_metrics_kmeanspp_first": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_longlong, _c_double_p, c_void_p]),
+        "said_metrics_kmeanspp_step": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, _c_double_p, c_int, _c_ll_p, _c_double_p, c_void_p]),
+    }),
+    "optimize": ("the blendshape fit", {   # include/said_optimize.h
+        "said_optimize_create": (c_int, [POINTER(c_void_p), c_int]),
+        "said_optimize_destroy": (c_int, [c_void_p]),
+        "said_optimize_last_error": (c_char_p, [c_void_p]),
+        "said_optimize_set_bases": (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong, _c_double_p, _c_double_p, _c_double_p, c_void_p]),
+        "said_optimize_rhs": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+        "said_optimize_solve": (c_int, [c_void_p, c_int, _c_ll_p, POINTER(c_int), c_void_p, c_double, c_int, c_int, c_double, c_void_p, c_void_p,
+                                        POINTER(c_int), POINTER(c_int), _c_double_p, c_void_p]),
+    }),
+    "train": ("the BCVAE trainer", {   # include/said_train.h
+        "said_train_create": (c_int, [POINTER(c_void_p), c_int, c_int]),
+        "said_train_destroy": (c_int, [c_void_p]),
+        "said_train_last_error": (c_char_p, [c_void_p]),
+        "said_train_tensor_name": (c_char_p, [c_int]),
+        "said_train_tensor_numel": (ctypes.c_longlong, [c_int]),
+        "said_train_tensor_is_counter": (c_int, [c_int]),
+        "said_train_set_tensor": (c_int, [c_void_p, c_int, c_char_p, c_void_p, ctypes.c_longlong]),
+        "said_train_get_tensor": (c_int, [c_void_p, c_int, c_char_p, c_void_p, ctypes.c_longlong]),
+        "said_train_reset_optimizer": (c_int, [c_void_p]),
+        "said_train_set_data": (c_int, [c_void_p, c_int, _c_float_p, ctypes.c_longlong, _c_ll_p, POINTER(c_int), c_int, POINTER(c_int)]),
+        "said_train_gather": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), _c_float_p]),
+        "said_train_step": (c_int, [c_void_p, c_int, POINTER(c_int), _c_float_p, _c_float_p, _c_float_p, c_int]),
+        "said_train_apply_update": (c_int, [c_void_p, _c_float_p]),
+        "said_train_eval_loss": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), _c_float_p, _c_float_p, _c_float_p, c_int]),
+        "said_train_read_losses": (c_int, [c_void_p, c_int, _c_double_p, POINTER(c_int), c_int]),
+        "said_train_last_losses": (c_int, [c_void_p, _c_float_p]),
+        "said_train_bn_stats": (c_int, [c_void_p, c_int, _c_float_p]),
+        "said_train_graph_count": (c_int, [c_void_p]),
+    }),
+}
+_bound = set()   # the LAZY_EXPORTS groups bound so far
 
 
 def library_path() -> str:
     return _LIB_PATH
 
 
-def load_library():
-    """dlopen the engine and bind every symbol of include/said_hip.h (no compute)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(_LIB_PATH):
-        raise EngineError(
-            f"{_LIB_PATH} not found: build it with `python -m said_amd.build` (hipcc, gfx950). "
-            "said_amd has no CPU fallback.")
-    lib = ctypes.CDLL(_LIB_PATH)
-    for name, (res, args) in EXPORTS.items():
-        if name in LATE_EXPORTS and not hasattr(lib, name):
-            continue
+def _bind(lib, table):
+    for name, (res, args) in table.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    got = lib.said_abi_version()
-    if got != ABI_VERSION:
-        raise EngineError(f"{_LIB_PATH} has ABI version {got}, this binding expects {ABI_VERSION}: rebuild it with "
-                          "`python -m said_amd.build --force`")
-    _lib = lib
-    return lib
+
+
+def load_library(group: Optional[str] = None):
+    """dlopen the engine and bind EXPORTS but the VAE decoder (no compute); with `group`, also that group of LAZY_EXPORTS."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(_LIB_PATH):
+            raise EngineError(
+                f"{_LIB_PATH} not found: build it with `python -m said_amd.build` (hipcc, gfx950). "
+                "said_amd has no CPU fallback.")
+        lib = ctypes.CDLL(_LIB_PATH)
+        _bind(lib, {n: sig for n, sig in EXPORTS.items() if n not in LAZY_EXPORTS["vae_decoder"][1]})
+        got = lib.said_abi_version()
+        if got != ABI_VERSION:
+            raise EngineError(f"{_LIB_PATH} has ABI version {got}, this binding expects {ABI_VERSION}: rebuild it with "
+                              "`python -m said_amd.build --force`")
+        _lib = lib
+    if group is not None and group not in _bound:
+        feature, table = LAZY_EXPORTS[group]
+        for name in table:
+            if not hasattr(_lib, name):
+                raise EngineError(f"{_LIB_PATH} predates {feature} ({name} is not exported): rebuild it with `python -m said_amd.build --force`")
+        _bind(_lib, table)
+        _bound.add(group)
+    return _lib
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -142,29 +203,64 @@ def _stream() -> c_void_p:
     return c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-class Engine:
-    """One engine context on one GPU (one process per GPU)."""
+class _Context:
+    """One C context of the library on one GPU, created by <prefix>_create, released by <prefix>_destroy; <prefix>_last_error gives
+    the message of a failed call (NULL: of a failed create).  A subclass names its prefix, its LAZY_EXPORTS group and how it refuses a
+    device that is not a GPU."""
+    prefix = ""
+    group: Optional[str] = None
+    cpu_error = EngineError
+    cpu_message = "said_amd runs on MI355X only (device={}); there is no CPU fallback"
 
-    def __init__(self, device: torch.device, max_batch_eff: int, max_frames: int, in_channels: int = 32, ctx_dim: int = 768, _clone_of=None):
-        self.lib = load_library()
+    def __init__(self, device: torch.device):
+        self.lib = load_library(self.group)
         device = torch.device(device)
         if device.type != "cuda":
-            raise EngineError(f"said_amd runs on MI355X only (device={device}); there is no CPU fallback")
+            raise self.cpu_error(self.cpu_message.format(device))
         self.device = device
         self.index = device.index if device.index is not None else torch.cuda.current_device()
+
+    def _create(self, *args) -> None:
+        h = c_void_p()
+        if getattr(self.lib, self.prefix + "_create")(ctypes.byref(h), self.index, *args) != 0:
+            raise EngineError(f"{self.prefix}_create: " + self._last_error(None))
+        self.h = h
+
+    def _last_error(self, h) -> str:
+        return (getattr(self.lib, self.prefix + "_last_error")(h) or b"?").decode()
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.lib, self.prefix + "_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _call(self, name: str, *args, what: Optional[str] = None) -> None:
+        """name(h, *args); EngineError("<what or name>: <last error>") when it fails."""
+        if getattr(self.lib, name)(self.h, *args) != 0:
+            raise EngineError(f"{what or name}: " + self._last_error(self.h))
+
+
+class Engine(_Context):
+    """One engine context on one GPU (one process per GPU)."""
+    prefix = "said"
+
+    def __init__(self, device: torch.device, max_batch_eff: int, max_frames: int, in_channels: int = 32, ctx_dim: int = 768, _clone_of=None):
+        super().__init__(device)
         self.max_batch_eff, self.max_frames = int(max_batch_eff), int(max_frames)
         self.in_channels, self.ctx_dim = in_channels, ctx_dim
-        h = c_void_p()
         self._parent = _clone_of   # a clone shares its parent's packed weights: keep the parent alive, destroy the clone first
         if _clone_of is not None:
-            rc = self.lib.said_clone(_clone_of.h, ctypes.byref(h), self.max_batch_eff, self.max_frames)
-            if rc != 0:
-                raise EngineError("said_clone: " + (self.lib.said_last_error(_clone_of.h) or b"?").decode())
+            h = c_void_p()
+            _clone_of._call("said_clone", ctypes.byref(h), self.max_batch_eff, self.max_frames)
+            self.h = h
         else:
-            rc = self.lib.said_create(ctypes.byref(h), self.index, self.max_batch_eff, self.max_frames, in_channels, ctx_dim)
-            if rc != 0:
-                raise EngineError("said_create: " + (self.lib.said_last_error(None) or b"?").decode())
-        self.h = h
+            self._create(self.max_batch_eff, self.max_frames, in_channels, ctx_dim)
         self.has_audio = _clone_of.has_audio if _clone_of is not None else False
         self._clones = []
         self._keep = []  # host buffers referenced by in-flight async copies
@@ -182,27 +278,15 @@ class Engine:
         for c in getattr(self, "_clones", []):
             c.close()      # clones first: they point into this context's weights
         self._clones = []
-        if getattr(self, "h", None):
-            self.lib.said_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc: int, what: str):
-        if rc != 0:
-            raise EngineError(f"{what}: " + (self.lib.said_last_error(self.h) or b"?").decode())
+        super().close()
 
     def reserve(self, max_batch_eff: int, max_frames: int) -> None:
         """Grow the workspace (never shrinks); the packed weights stay on the device (said_reserve)."""
         with torch.cuda.device(self.index):
             rc = self.lib.said_reserve(self.h, int(max_batch_eff), int(max_frames))
-        msg = (self.lib.said_last_error(self.h) or b"?").decode() if rc != 0 else ""
+        msg = self._last_error(self.h) if rc != 0 else ""
         b, t = c_int(0), c_int(0)
-        self._chk(self.lib.said_capacity(self.h, ctypes.byref(b), ctypes.byref(t)), "said_capacity")
+        self._call("said_capacity", ctypes.byref(b), ctypes.byref(t))
         self.max_batch_eff, self.max_frames = b.value, t.value   # (0, 0) after a failed growth: the context refuses every size
         if rc != 0:
             raise EngineError("said_reserve: " + msg)
@@ -214,12 +298,12 @@ class Engine:
             half = 96
             freqs = torch.exp(-np.log(10000) * torch.arange(start=0, end=half, dtype=torch.float32) / half)
             fr = np.ascontiguousarray(freqs.numpy())
-            self._chk(self.lib.said_set_timestep_freqs(self.h, fr.ctypes.data_as(c_void_p), half), "said_set_timestep_freqs")
+            self._call("said_set_timestep_freqs", fr.ctypes.data_as(c_void_p), half)
             for k, v in state_dict.items():
                 a = np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy())
                 shape = (c_int64 * a.ndim)(*a.shape)
-                self._chk(self.lib.said_set_weight(self.h, k.encode(), a.ctypes.data_as(c_void_p), shape, a.ndim), f"said_set_weight({k})")
-            self._chk(self.lib.said_finalize_weights(self.h, _stream()), "said_finalize_weights")
+                self._call("said_set_weight", k.encode(), a.ctypes.data_as(c_void_p), shape, a.ndim, what=f"said_set_weight({k})")
+            self._call("said_finalize_weights", _stream())
         self.has_audio = any(k.startswith("audio_encoder.") for k in state_dict)
 
     # ---- compute ----
@@ -238,7 +322,7 @@ class Engine:
                     L = (L - k) // s + 1
                 out = torch.empty(B, max(L, 1), out_dim, device=waveform.device, dtype=torch.float32)
             got = c_int(0)
-            self._chk(self.lib.said_audio_encode(self.h, _ptr(waveform), B, Ta, nf, int(apply_proj), _ptr(out), ctypes.byref(got), _stream()), "said_audio_encode")
+            self._call("said_audio_encode", _ptr(waveform), B, Ta, nf, int(apply_proj), _ptr(out), ctypes.byref(got), _stream())
             assert got.value == out.shape[1], (got.value, out.shape)
         return out
 
@@ -253,8 +337,8 @@ class Engine:
             raise EngineError(f"timesteps must have {Be} entries, got {ts.shape[0]}")
         out = torch.empty_like(sample)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_unet_forward(self.h, _ptr(sample), ts.ctypes.data_as(POINTER(c_int64)), _ptr(context), Be, T,
-                                                 context.shape[1], _ptr(out), _stream()), "said_unet_forward")
+            self._call("said_unet_forward", _ptr(sample), ts.ctypes.data_as(POINTER(c_int64)), _ptr(context), Be, T,
+                       context.shape[1], _ptr(out), _stream())
         return out
 
     def loop_job(self, *, latents: torch.Tensor, context: torch.Tensor, timesteps: np.ndarray, coef: np.ndarray,
@@ -309,12 +393,12 @@ class Engine:
     def prepare_loop(self, job):
         """Builds the job's step graph if this context does not hold it yet (said_loop_prepare); launches nothing of the loop."""
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_loop_prepare(self.h, ctypes.byref(job[0]), _stream()), "said_loop_prepare")
+            self._call("said_loop_prepare", ctypes.byref(job[0]), _stream())
 
     def run_loop(self, job):
         """Enqueues the job's loop on the current stream; returns (result, final_latents, intermediates or None)."""
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_denoise_loop(self.h, ctypes.byref(job[0]), _stream()), "said_denoise_loop")
+            self._call("said_denoise_loop", ctypes.byref(job[0]), _stream())
         self._keep = job[1]  # alive until the next call (async copies / kernels may still reference them)
         return job[2]
 
@@ -331,9 +415,9 @@ class Engine:
         cf = np.ascontiguousarray(np.asarray(coef_row, dtype=np.float32).reshape(NCOEF))
         opt = [None if t is None else _check_dev(t, "tensor") for t in (eps_uncond, step_noise, init_latents, edit_noise, mask)]
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_ddim_step(self.h, _ptr(eps), _ptr(opt[0]), float(guidance_scale), _ptr(sample),
-                                              cf.ctypes.data_as(POINTER(c_float)), PRED[prediction_type], _ptr(opt[1]), _ptr(opt[2]),
-                                              _ptr(opt[3]), _ptr(opt[4]), _ptr(out), sample.numel(), _stream()), "said_ddim_step")
+            self._call("said_ddim_step", _ptr(eps), _ptr(opt[0]), float(guidance_scale), _ptr(sample),
+                       cf.ctypes.data_as(POINTER(c_float)), PRED[prediction_type], _ptr(opt[1]), _ptr(opt[2]),
+                       _ptr(opt[3]), _ptr(opt[4]), _ptr(out), sample.numel(), _stream())
             torch.cuda.current_stream().synchronize()  # cf is a temporary
         return out
 
@@ -352,9 +436,9 @@ class Engine:
         if x0_hist is not None and (_check_dev(x0_hist, "x0_hist") is not x0_hist):
             raise EngineError("x0_hist must be contiguous: it is updated in place")
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_solver_step(self.h, _ptr(model_output), _ptr(opt[0]), float(guidance_scale), _ptr(sample),
-                                                cf.ctypes.data_as(POINTER(c_float)), PRED[prediction_type], _ptr(x0_hist), _ptr(opt[1]),
-                                                _ptr(opt[2]), _ptr(opt[3]), _ptr(opt[4]), _ptr(out), sample.numel(), _stream()), "said_solver_step")
+            self._call("said_solver_step", _ptr(model_output), _ptr(opt[0]), float(guidance_scale), _ptr(sample),
+                       cf.ctypes.data_as(POINTER(c_float)), PRED[prediction_type], _ptr(x0_hist), _ptr(opt[1]),
+                       _ptr(opt[2]), _ptr(opt[3]), _ptr(opt[4]), _ptr(out), sample.numel(), _stream())
             torch.cuda.current_stream().synchronize()  # cf is a temporary
         return out
 
@@ -369,7 +453,7 @@ class Engine:
             y = _check_dev(y, "y")
         out = torch.empty_like(x)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_axpby(self.h, av, _ptr(x), cv, _ptr(y), _ptr(out), B, x.numel() // B, _stream()), "said_axpby")
+            self._call("said_axpby", av, _ptr(x), cv, _ptr(y), _ptr(out), B, x.numel() // B, _stream())
         return out
 
     def profile_unet(self, batch_eff: int, frames: int, reps: int = 50, cfg_clips: int = 0):
@@ -380,8 +464,8 @@ class Engine:
         n = c_int(0)
         vp = lambda a: a.ctypes.data_as(c_void_p)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_profile_unet(self.h, batch_eff, frames, cfg_clips, reps, M, vp(us), vp(by), vp(fl), vp(kind), vp(epi), vp(nb),
-                                                 vp(ks), ctypes.byref(n), _stream()), "said_profile_unet")
+            self._call("said_profile_unet", batch_eff, frames, cfg_clips, reps, M, vp(us), vp(by), vp(fl), vp(kind), vp(epi), vp(nb),
+                       vp(ks), ctypes.byref(n), _stream())
         k = n.value
         return [dict(us=float(us[i]), bytes=float(by[i]), flops=float(fl[i]), kind=int(kind[i]), epi=int(epi[i]), NB=int(nb[i]), KS=int(ks[i]))
                 for i in range(k)]
@@ -391,28 +475,27 @@ class Engine:
         n = int(np.prod(shape))
         out = torch.empty((nsteps,) + tuple(shape), device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_philox_normal(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), int(nsteps), n, _ptr(out), _stream()),
-                      "said_philox_normal")
+            self._call("said_philox_normal", int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), int(nsteps), n, _ptr(out), _stream())
         return out
 
     # ---- debugging aids (tests only) ----
     def debug_option(self, name: str, value: int) -> None:
-        self._chk(self.lib.said_debug_option(self.h, name.encode(), int(value)), "said_debug_option")
+        self._call("said_debug_option", name.encode(), int(value))
 
     def debug_get(self, name: str) -> int:
         return int(self.lib.said_debug_get(self.h, name.encode()))
 
     def debug_stop_after(self, n: int):
-        self._chk(self.lib.said_debug_stop_after(self.h, int(n)), "said_debug_stop_after")
+        self._call("said_debug_stop_after", int(n))
 
     def debug_clocks(self, enable: bool, read: bool = False):
         out = np.zeros((64, 8, 16), dtype=np.int64) if read else None
-        self._chk(self.lib.said_debug_clocks(self.h, int(enable), out.ctypes.data_as(c_void_p) if read else None), "said_debug_clocks")
+        self._call("said_debug_clocks", int(enable), out.ctypes.data_as(c_void_p) if read else None)
         return out
 
     def debug_read(self, name: str, shape) -> np.ndarray:
         out = np.empty(shape, dtype=np.float32)
-        self._chk(self.lib.said_debug_read(self.h, name.encode(), out.ctypes.data_as(c_void_p), out.size), "said_debug_read")
+        self._call("said_debug_read", name.encode(), out.ctypes.data_as(c_void_p), out.size)
         return out
 
     def ws_buffers(self):
@@ -420,18 +503,18 @@ class Engine:
         out = []
         for i in range(int(self.lib.said_debug_ws_count(self.h))):
             p, nb, nm = c_void_p(), ctypes.c_longlong(0), c_char_p()
-            self._chk(self.lib.said_debug_ws_info(self.h, i, ctypes.byref(p), ctypes.byref(nb), ctypes.byref(nm)), "said_debug_ws_info")
+            self._call("said_debug_ws_info", i, ctypes.byref(p), ctypes.byref(nb), ctypes.byref(nm))
             out.append((i, (nm.value or b"?").decode(), int(nb.value)))
         return out
 
     def ws_fill(self, byte_value: int) -> None:
-        self._chk(self.lib.said_debug_ws_fill(self.h, int(byte_value) & 0xFF), "said_debug_ws_fill")
+        self._call("said_debug_ws_fill", int(byte_value) & 0xFF)
 
     def ws_snapshot(self, idx: int, nbytes: int) -> torch.Tensor:
         """Device copy (uint8) of workspace buffer `idx`, enqueued on the current stream."""
         out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_debug_ws_copy(self.h, idx, _ptr(out), nbytes, _stream()), "said_debug_ws_copy")
+            self._call("said_debug_ws_copy", idx, _ptr(out), nbytes, _stream())
         return out
 
     def loop_progress(self) -> int:
@@ -443,7 +526,7 @@ class Engine:
 
     def loop_progress_reset(self) -> None:
         """Forget the previous loop's step count before a polling thread is started."""
-        self._chk(self.lib.said_loop_progress_reset(self.h), "said_loop_progress_reset")
+        self._call("said_loop_progress_reset")
 
     def graph_num_nodes(self) -> int:
         return int(self.lib.said_graph_num_nodes(self.h))
@@ -456,7 +539,7 @@ class Engine:
             mode = PRECISIONS[mode]
         else:
             mode = 1 if mode else 0
-        self._chk(self.lib.said_set_precision(self.h, int(mode)), "said_set_precision")
+        self._call("said_set_precision", int(mode))
 
     def get_precision(self) -> str:
         """The mode asked for."""
@@ -474,44 +557,18 @@ class Engine:
         held an inf / NaN (-1: none) and whether the final latents / the model output hold one.  Synchronises the current stream."""
         a, b = c_int(-1), c_int(0)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_numeric_status(self.h, _stream(), ctypes.byref(a), ctypes.byref(b)), "said_numeric_status")
+            self._call("said_numeric_status", _stream(), ctypes.byref(a), ctypes.byref(b))
         return a.value, bool(b.value)
 
 
-class NoCpuPathError(EngineError, NotImplementedError):
-    """A model method called on a CPU-resident model: said_amd computes on the MI355X only."""
-
-
-class VaeEngine:
+class VaeEngine(_Context):
     """BCVAE context on one GPU (include/said_hip.h, "VAE"): the encoder always, the decoder when its weights were loaded."""
+    prefix = "said_vae"
 
     def __init__(self, device: torch.device, in_channels: int = 32, seq_len: int = 120, z_dim: int = 64):
-        self.lib = load_library()
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise EngineError(f"said_amd runs on MI355X only (device={device}); there is no CPU fallback")
-        self.device = device
-        self.index = device.index if device.index is not None else torch.cuda.current_device()
+        super().__init__(device)
         self.seq_len, self.in_channels, self.z_dim = seq_len, in_channels, z_dim
-        h = c_void_p()
-        if self.lib.said_vae_create(ctypes.byref(h), self.index, in_channels, seq_len, z_dim) != 0:
-            raise EngineError("said_vae_create: " + (self.lib.said_vae_last_error(None) or b"?").decode())
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.said_vae_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc: int, what: str):
-        if rc != 0:
-            raise EngineError(f"{what}: " + (self.lib.said_vae_last_error(self.h) or b"?").decode())
+        self._create(in_channels, seq_len, z_dim)
 
     def load_weights(self, state_dict: Dict[str, torch.Tensor]):
         for k, v in state_dict.items():
@@ -519,8 +576,8 @@ class VaeEngine:
                 continue   # a counter, not a weight
             a = np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy())
             shape = (c_int64 * max(a.ndim, 1))(*(a.shape if a.ndim else (1,)))
-            self._chk(self.lib.said_vae_set_weight(self.h, k.encode(), a.ctypes.data_as(c_void_p), shape, max(a.ndim, 1)), f"said_vae_set_weight({k})")
-        self._chk(self.lib.said_vae_finalize_weights(self.h), "said_vae_finalize_weights")
+            self._call("said_vae_set_weight", k.encode(), a.ctypes.data_as(c_void_p), shape, max(a.ndim, 1), what=f"said_vae_set_weight({k})")
+        self._call("said_vae_finalize_weights")
 
     def encode(self, coeffs: torch.Tensor, n_windows: int, window_stride: int, want_logvar: bool = True):
         """`coeffs`: contiguous fp32 device tensor holding the windows at `window_stride` floats apart."""
@@ -533,23 +590,17 @@ class VaeEngine:
         mean = torch.empty(n_windows, self.z_dim, device=coeffs.device, dtype=torch.float32)
         logvar = torch.empty_like(mean) if want_logvar else None
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_vae_encode(self.h, _ptr(coeffs), int(window_stride), int(n_windows), _ptr(mean), _ptr(logvar), _stream()),
-                      "said_vae_encode")
+            self._call("said_vae_encode", _ptr(coeffs), int(window_stride), int(n_windows), _ptr(mean), _ptr(logvar), _stream())
         return mean, logvar
-
-    def _decode_entry(self, name: str):
-        if not hasattr(self.lib, name):
-            raise EngineError(f"{_LIB_PATH} predates the VAE decoder ({name} is not exported): rebuild it with `python -m said_amd.build --force`")
-        return getattr(self.lib, name)
 
     @property
     def has_decoder(self) -> bool:
-        return bool(self._decode_entry("said_vae_has_decoder")(self.h))
+        return bool(load_library("vae_decoder").said_vae_has_decoder(self.h))
 
     def decode(self, mean: torch.Tensor, log_var: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(n, z_dim) latents -> (n, seq_len, in_channels) coefficients.  With `eps`, the latent is mean + exp(0.5 log_var) eps,
         computed in the decoder launch's prologue."""
-        fn = self._decode_entry("said_vae_decode")
+        load_library("vae_decoder")
         z = self.z_dim
         if eps is not None and log_var is None:
             raise ValueError("eps needs log_var")
@@ -568,7 +619,7 @@ class VaeEngine:
             return out
         lv = args["log_var"] if eps is not None else None
         with torch.cuda.device(self.index):
-            self._chk(fn(self.h, _ptr(args["mean"]), _ptr(lv), _ptr(args["eps"]), n, _ptr(out), _stream()), "said_vae_decode")
+            self._call("said_vae_decode", _ptr(args["mean"]), _ptr(lv), _ptr(args["eps"]), n, _ptr(out), _stream())
         return out
 
 
@@ -580,77 +631,24 @@ def unet_algorithmic_flops(batch_eff: int, frames: int) -> float:
     return float(load_library().said_unet_algorithmic_flops(batch_eff, frames))
 
 
-# ---- evaluation metrics (include/said_metrics.h): a table of their own, bound on first use, outside EXPORTS and the ABI version of said_hip.h
-_c_double_p, _c_ll_p = POINTER(c_double), POINTER(ctypes.c_longlong)
-METRICS_EXPORTS = {
-    "said_metrics_create": (c_int, [POINTER(c_void_p), c_int, ctypes.c_longlong]),
-    "said_metrics_destroy": (c_int, [c_void_p]),
-    "said_metrics_last_error": (c_char_p, [c_void_p]),
-    "said_metrics_max_points": (ctypes.c_longlong, [c_void_p]),
-    "said_metrics_weighted_sums": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, _c_double_p, _c_double_p, c_void_p]),
-    "said_metrics_weighted_scatter": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, _c_double_p, _c_double_p, c_void_p]),
-    "said_metrics_gmm_estep": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-                                       c_void_p, c_void_p, c_void_p]),
-    "said_metrics_kmeans_assign": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, _c_double_p, c_int, _c_ll_p, _c_double_p, c_void_p]),
-    "said_metrics_kmeans_read": (c_int, [c_void_p, ctypes.c_longlong, POINTER(c_int), _c_double_p, c_void_p]),
-    "said_metrics_kmeans_set_labels": (c_int, [c_void_p, ctypes.c_longlong, c_int, POINTER(c_int), c_void_p]),
-    "said_metrics_kmeanspp_first": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_longlong, _c_double_p, c_void_p]),
-    "said_metrics_kmeanspp_step": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, _c_double_p, c_int, _c_ll_p, _c_double_p, c_void_p]),
-}
+# ---- evaluation metrics (include/said_metrics.h)
 METRICS_DIM, METRICS_MAX_K = 64, 8
 W_UNIT, W_LABELS, W_RESP = 0, 1, 2   # SAID_METRICS_W_*
-_metrics_bound = False
-
-
-def load_metrics_library():
-    """The engine library with the said_metrics.h entry points bound."""
-    global _metrics_bound
-    lib = load_library()
-    if not _metrics_bound:
-        for name, (res, args) in METRICS_EXPORTS.items():
-            if not hasattr(lib, name):
-                raise EngineError(f"{_LIB_PATH} predates the metrics passes ({name} is not exported): rebuild it with `python -m said_amd.build --force`")
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _metrics_bound = True
-    return lib
 
 
 def _dp(a: np.ndarray):
     return a.ctypes.data_as(_c_double_p)
 
 
-class MetricsEngine:
+class MetricsEngine(_Context):
     """said_metrics context on one GPU (include/said_metrics.h): workspace for up to `max_points` (n, 64) fp32 latents."""
+    prefix, group = "said_metrics", "metrics"
+    cpu_error, cpu_message = NoCpuPathError, "said_amd computes the metrics on MI355X only (device={}); there is no CPU path"
 
     def __init__(self, device: torch.device, max_points: int):
-        self.lib = load_metrics_library()
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise NoCpuPathError(f"said_amd computes the metrics on MI355X only (device={device}); there is no CPU path")
-        self.device = device
-        self.index = device.index if device.index is not None else torch.cuda.current_device()
-        h = c_void_p()
-        if self.lib.said_metrics_create(ctypes.byref(h), self.index, int(max_points)) != 0:
-            raise EngineError("said_metrics_create: " + (self.lib.said_metrics_last_error(None) or b"?").decode())
-        self.h = h
+        super().__init__(device)
+        self._create(int(max_points))
         self.max_points = int(max_points)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.said_metrics_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc: int, what: str):
-        if rc != 0:
-            raise EngineError(f"{what}: " + (self.lib.said_metrics_last_error(self.h) or b"?").decode())
 
     def _x(self, x: torch.Tensor) -> torch.Tensor:
         if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != METRICS_DIM or not x.is_contiguous():
@@ -666,7 +664,7 @@ class MetricsEngine:
         x = self._x(x)
         nk, sx = np.zeros(k), np.zeros((k, METRICS_DIM))
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_metrics_weighted_sums(self.h, _ptr(x), x.shape[0], k, wsrc, _dp(nk), _dp(sx), _stream()), "said_metrics_weighted_sums")
+            self._call("said_metrics_weighted_sums", _ptr(x), x.shape[0], k, wsrc, _dp(nk), _dp(sx), _stream())
         return nk, sx
 
     def weighted_scatter(self, x: torch.Tensor, k: int, wsrc: int, means: np.ndarray) -> np.ndarray:
@@ -675,8 +673,7 @@ class MetricsEngine:
         mu = np.ascontiguousarray(means, dtype=np.float64).reshape(k, METRICS_DIM)
         out = np.zeros((k, METRICS_DIM, METRICS_DIM))
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_metrics_weighted_scatter(self.h, _ptr(x), x.shape[0], k, wsrc, _dp(mu), _dp(out), _stream()),
-                      "said_metrics_weighted_scatter")
+            self._call("said_metrics_weighted_scatter", _ptr(x), x.shape[0], k, wsrc, _dp(mu), _dp(out), _stream())
         return out
 
     def gmm_estep(self, x: torch.Tensor, prec_chol: np.ndarray, mean_prec: np.ndarray, log_det: np.ndarray, log_weights: np.ndarray,
@@ -691,8 +688,7 @@ class MetricsEngine:
             lr = torch.empty(x.shape[0], k, dtype=torch.float64, device=x.device)
             lpn = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_metrics_gmm_estep(self.h, _ptr(x), x.shape[0], k, *[_dp(a) for a in args], _dp(lb), _ptr(lr), _ptr(lpn), _stream()),
-                      "said_metrics_gmm_estep")
+            self._call("said_metrics_gmm_estep", _ptr(x), x.shape[0], k, *[_dp(a) for a in args], _dp(lb), _ptr(lr), _ptr(lpn), _stream())
         return (float(lb[0]), lr, lpn) if want_resp else float(lb[0])
 
     def kmeans_assign(self, x: torch.Tensor, centres: np.ndarray, compare: bool):
@@ -701,28 +697,27 @@ class MetricsEngine:
         c = np.ascontiguousarray(centres, dtype=np.float64)
         changed, inertia = ctypes.c_longlong(0), np.zeros(1)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_metrics_kmeans_assign(self.h, _ptr(x), x.shape[0], c.shape[0], _dp(c), int(bool(compare)), ctypes.byref(changed),
-                                                          _dp(inertia), _stream()), "said_metrics_kmeans_assign")
+            self._call("said_metrics_kmeans_assign", _ptr(x), x.shape[0], c.shape[0], _dp(c), int(bool(compare)), ctypes.byref(changed),
+                       _dp(inertia), _stream())
         return int(changed.value), float(inertia[0])
 
     def kmeans_read(self, n: int):
         """(labels int32 (n,), squared distance to the assigned centre float64 (n,)) of the last assignment."""
         lab, dist = np.zeros(n, dtype=np.int32), np.zeros(n)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_metrics_kmeans_read(self.h, n, lab.ctypes.data_as(POINTER(c_int)), _dp(dist), _stream()), "said_metrics_kmeans_read")
+            self._call("said_metrics_kmeans_read", n, lab.ctypes.data_as(POINTER(c_int)), _dp(dist), _stream())
         return lab, dist
 
     def kmeans_set_labels(self, labels: np.ndarray, k: int):
         lab = np.ascontiguousarray(labels, dtype=np.int32)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_metrics_kmeans_set_labels(self.h, lab.shape[0], k, lab.ctypes.data_as(POINTER(c_int)), _stream()),
-                      "said_metrics_kmeans_set_labels")
+            self._call("said_metrics_kmeans_set_labels", lab.shape[0], k, lab.ctypes.data_as(POINTER(c_int)), _stream())
 
     def kmeanspp_first(self, x: torch.Tensor, centre_id: int) -> float:
         x = self._x(x)
         pot = np.zeros(1)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_metrics_kmeanspp_first(self.h, _ptr(x), x.shape[0], int(centre_id), _dp(pot), _stream()), "said_metrics_kmeanspp_first")
+            self._call("said_metrics_kmeanspp_first", _ptr(x), x.shape[0], int(centre_id), _dp(pot), _stream())
         return float(pot[0])
 
     def kmeanspp_step(self, x: torch.Tensor, rand_vals: np.ndarray):
@@ -731,73 +726,26 @@ class MetricsEngine:
         r = np.ascontiguousarray(rand_vals, dtype=np.float64)
         cid, pot = ctypes.c_longlong(0), np.zeros(1)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_metrics_kmeanspp_step(self.h, _ptr(x), x.shape[0], _dp(r), r.shape[0], ctypes.byref(cid), _dp(pot), _stream()),
-                      "said_metrics_kmeanspp_step")
+            self._call("said_metrics_kmeanspp_step", _ptr(x), x.shape[0], _dp(r), r.shape[0], ctypes.byref(cid), _dp(pot), _stream())
         return int(cid.value), float(pot[0])
 
 
-# ---- blendshape-coefficient fit (include/said_optimize.h): a table of its own, bound on first use, outside EXPORTS and the ABI version of said_hip.h
-OPTIMIZE_EXPORTS = {
-    "said_optimize_create": (c_int, [POINTER(c_void_p), c_int]),
-    "said_optimize_destroy": (c_int, [c_void_p]),
-    "said_optimize_last_error": (c_char_p, [c_void_p]),
-    "said_optimize_set_bases": (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong, _c_double_p, _c_double_p, _c_double_p, c_void_p]),
-    "said_optimize_rhs": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
-    "said_optimize_solve": (c_int, [c_void_p, c_int, _c_ll_p, POINTER(c_int), c_void_p, c_double, c_int, c_int, c_double, c_void_p, c_void_p,
-                                    POINTER(c_int), POINTER(c_int), _c_double_p, c_void_p]),
-}
+# ---- blendshape-coefficient fit (include/said_optimize.h)
 OPTIMIZE_MAX_K = 64
 OPT_CONVERGED, OPT_MAX_ITER, OPT_NOT_FINITE = 0, 1, 2   # SAID_OPTIMIZE_*
-_optimize_bound = False
 
 
-def load_optimize_library():
-    """The engine library with the said_optimize.h entry points bound."""
-    global _optimize_bound
-    lib = load_library()
-    if not _optimize_bound:
-        for name, (res, args) in OPTIMIZE_EXPORTS.items():
-            if not hasattr(lib, name):
-                raise EngineError(f"{_LIB_PATH} predates the blendshape fit ({name} is not exported): rebuild it with `python -m said_amd.build --force`")
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _optimize_bound = True
-    return lib
-
-
-class OptimizeEngine:
+class OptimizeEngine(_Context):
     """said_optimize context on one GPU (include/said_optimize.h): the bases of a batch, the rhs kernel and the batched QP solver."""
+    prefix, group = "said_optimize", "optimize"
+    cpu_error, cpu_message = NoCpuPathError, "said_amd fits blendshape coefficients on MI355X only (device={}); there is no CPU path"
 
     def __init__(self, device: torch.device):
-        self.lib = load_optimize_library()
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise NoCpuPathError(f"said_amd fits blendshape coefficients on MI355X only (device={device}); there is no CPU path")
-        self.device = device
-        self.index = device.index if device.index is not None else torch.cuda.current_device()
-        h = c_void_p()
-        if self.lib.said_optimize_create(ctypes.byref(h), self.index) != 0:
-            raise EngineError("said_optimize_create: " + (self.lib.said_optimize_last_error(None) or b"?").decode())
-        self.h = h
+        super().__init__(device)
+        self._create()
         self.k = 0
         self.n3v = 0
         self.nbasis = 0
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.said_optimize_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc: int, what: str):
-        if rc != 0:
-            raise EngineError(f"{what}: " + (self.lib.said_optimize_last_error(self.h) or b"?").decode())
 
     def set_bases(self, neutrals: np.ndarray, bdeltas: np.ndarray, ps: np.ndarray):
         """neutrals (nb, 3V), bdeltas (nb, 3V, K) = B - n, ps (nb, K, K) = B_delta' B_delta, float64."""
@@ -806,7 +754,7 @@ class OptimizeEngine:
         p = np.ascontiguousarray(ps, dtype=np.float64)
         nb, n3v, k = b.shape
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_optimize_set_bases(self.h, nb, k, n3v, _dp(n), _dp(b), _dp(p), _stream()), "said_optimize_set_bases")
+            self._call("said_optimize_set_bases", nb, k, n3v, _dp(n), _dp(b), _dp(p), _stream())
         self.nbasis, self.n3v, self.k = nb, n3v, k
 
     def rhs(self, basis: int, verts: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -816,7 +764,7 @@ class OptimizeEngine:
         if out is None:
             out = torch.empty(verts.shape[0], self.k, dtype=torch.float64, device=verts.device)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_optimize_rhs(self.h, int(basis), _ptr(verts), verts.shape[0], _ptr(out), _stream()), "said_optimize_rhs")
+            self._call("said_optimize_rhs", int(basis), _ptr(verts), verts.shape[0], _ptr(out), _stream())
         return out
 
     def solve(self, q: torch.Tensor, offsets: np.ndarray, basis: np.ndarray, delta: float, coupled: bool, max_iter: int, tol: float,
@@ -835,34 +783,13 @@ class OptimizeEngine:
         res = np.zeros((nseq, 3))
         ip = POINTER(c_int)
         with torch.cuda.device(self.index):
-            self._chk(self.lib.said_optimize_solve(self.h, nseq, offs.ctypes.data_as(_c_ll_p), bas.ctypes.data_as(ip), _ptr(q), float(delta),
-                                                   int(bool(coupled)), int(max_iter), float(tol), _ptr(w), _ptr(z), st.ctypes.data_as(ip),
-                                                   it.ctypes.data_as(ip), _dp(res), _stream()), "said_optimize_solve")
+            self._call("said_optimize_solve", nseq, offs.ctypes.data_as(_c_ll_p), bas.ctypes.data_as(ip), _ptr(q), float(delta),
+                       int(bool(coupled)), int(max_iter), float(tol), _ptr(w), _ptr(z), st.ctypes.data_as(ip),
+                       it.ctypes.data_as(ip), _dp(res), _stream())
         return w, z, st, it, res
 
 
-# ---- BCVAE trainer (include/said_train.h): a table of its own, bound on first use, outside EXPORTS and the ABI version of said_hip.h
-_c_float_p = POINTER(c_float)
-TRAIN_EXPORTS = {
-    "said_train_create": (c_int, [POINTER(c_void_p), c_int, c_int]),
-    "said_train_destroy": (c_int, [c_void_p]),
-    "said_train_last_error": (c_char_p, [c_void_p]),
-    "said_train_tensor_name": (c_char_p, [c_int]),
-    "said_train_tensor_numel": (ctypes.c_longlong, [c_int]),
-    "said_train_tensor_is_counter": (c_int, [c_int]),
-    "said_train_set_tensor": (c_int, [c_void_p, c_int, c_char_p, c_void_p, ctypes.c_longlong]),
-    "said_train_get_tensor": (c_int, [c_void_p, c_int, c_char_p, c_void_p, ctypes.c_longlong]),
-    "said_train_reset_optimizer": (c_int, [c_void_p]),
-    "said_train_set_data": (c_int, [c_void_p, c_int, _c_float_p, ctypes.c_longlong, _c_ll_p, POINTER(c_int), c_int, POINTER(c_int)]),
-    "said_train_gather": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), _c_float_p]),
-    "said_train_step": (c_int, [c_void_p, c_int, POINTER(c_int), _c_float_p, _c_float_p, _c_float_p, c_int]),
-    "said_train_apply_update": (c_int, [c_void_p, _c_float_p]),
-    "said_train_eval_loss": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), _c_float_p, _c_float_p, _c_float_p, c_int]),
-    "said_train_read_losses": (c_int, [c_void_p, c_int, _c_double_p, POINTER(c_int), c_int]),
-    "said_train_last_losses": (c_int, [c_void_p, _c_float_p]),
-    "said_train_bn_stats": (c_int, [c_void_p, c_int, _c_float_p]),
-    "said_train_graph_count": (c_int, [c_void_p]),
-}
+# ---- BCVAE trainer (include/said_train.h)
 # SAID_TRAIN_* of include/said_train.h
 TRAIN_NSCAL, TRAIN_NACC, TRAIN_ITEM = 16, 8, 4
 (TRAIN_S_LR, TRAIN_S_WD_FACTOR, TRAIN_S_STEP_SIZE, TRAIN_S_BC2_SQRT, TRAIN_S_EMA_OMD, TRAIN_S_BETA, TRAIN_S_WVEL, TRAIN_S_OMB1, TRAIN_S_B2,
@@ -870,22 +797,6 @@ TRAIN_NSCAL, TRAIN_NACC, TRAIN_ITEM = 16, 8, 4
 TRAIN_STATE, TRAIN_EMA, TRAIN_GRAD, TRAIN_EXP_AVG, TRAIN_EXP_AVG_SQ = range(5)
 TRAIN_OK, TRAIN_NOT_FINITE = 0, 1
 TRAIN_SET_TRAIN, TRAIN_SET_VAL = 0, 1
-_train_bound = False
-
-
-def load_train_library():
-    """The engine library with the said_train.h entry points bound."""
-    global _train_bound
-    lib = load_library()
-    if not _train_bound:
-        for name, (res, args) in TRAIN_EXPORTS.items():
-            if not hasattr(lib, name):
-                raise EngineError(f"{_LIB_PATH} predates the BCVAE trainer ({name} is not exported): rebuild it with `python -m said_amd.build --force`")
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _train_bound = True
-    return lib
 
 
 def _f32(a) -> np.ndarray:
@@ -896,62 +807,40 @@ def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
-class TrainEngine:
+class TrainEngine(_Context):
     """said_train context on one GPU (include/said_train.h): the BCVAE's parameters, buffers, gradients, Adam moments and EMA shadow, the
     window sets, and the captured training step.  Host arrays in and out (numpy); the context keeps its own stream."""
+    prefix, group = "said_train", "train"
+    cpu_error, cpu_message = NoCpuPathError, "said_amd trains the BCVAE on MI355X only (device={}); there is no CPU path"
 
     def __init__(self, device: torch.device, max_batch: int):
-        self.lib = load_train_library()
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise NoCpuPathError(f"said_amd trains the BCVAE on MI355X only (device={device}); there is no CPU path")
-        self.device = device
-        self.index = device.index if device.index is not None else torch.cuda.current_device()
-        h = c_void_p()
-        if self.lib.said_train_create(ctypes.byref(h), self.index, int(max_batch)) != 0:
-            raise EngineError("said_train_create: " + (self.lib.said_train_last_error(None) or b"?").decode())
-        self.h = h
+        super().__init__(device)
+        self._create(int(max_batch))
         self.max_batch = int(max_batch)
         self.tensors = [(self.lib.said_train_tensor_name(i).decode(), int(self.lib.said_train_tensor_numel(i)),
                          bool(self.lib.said_train_tensor_is_counter(i))) for i in range(70)]
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.said_train_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc: int, what: str):
-        if rc != 0:
-            raise EngineError(f"{what}: " + (self.lib.said_train_last_error(self.h) or b"?").decode())
-
     def set_tensor(self, which: int, name: str, value) -> None:
         a = np.ascontiguousarray(value, dtype=np.int64 if name.endswith("num_batches_tracked") else np.float32).reshape(-1)
-        self._chk(self.lib.said_train_set_tensor(self.h, which, name.encode(), a.ctypes.data_as(c_void_p), a.size), "said_train_set_tensor")
+        self._call("said_train_set_tensor", which, name.encode(), a.ctypes.data_as(c_void_p), a.size)
 
     def get_tensor(self, which: int, name: str, numel: int) -> np.ndarray:
         a = np.empty(numel, dtype=np.int64 if name.endswith("num_batches_tracked") else np.float32)
-        self._chk(self.lib.said_train_get_tensor(self.h, which, name.encode(), a.ctypes.data_as(c_void_p), numel), "said_train_get_tensor")
+        self._call("said_train_get_tensor", which, name.encode(), a.ctypes.data_as(c_void_p), numel)
         return a
 
     def reset_optimizer(self) -> None:
-        self._chk(self.lib.said_train_reset_optimizer(self.h), "said_train_reset_optimizer")
+        self._call("said_train_reset_optimizer")
 
     def set_data(self, which_set: int, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, mirror: np.ndarray) -> None:
         fr, off, ln, mi = _f32(frames), np.ascontiguousarray(offsets, dtype=np.int64), _i32(lengths), _i32(mirror)
-        self._chk(self.lib.said_train_set_data(self.h, which_set, fr.ctypes.data_as(_c_float_p), fr.shape[0], off.ctypes.data_as(_c_ll_p),
-                                               ln.ctypes.data_as(POINTER(c_int)), ln.size, mi.ctypes.data_as(POINTER(c_int))), "said_train_set_data")
+        self._call("said_train_set_data", which_set, fr.ctypes.data_as(_c_float_p), fr.shape[0], off.ctypes.data_as(_c_ll_p),
+                   ln.ctypes.data_as(POINTER(c_int)), ln.size, mi.ctypes.data_as(POINTER(c_int)))
 
     def gather(self, which_set: int, items: np.ndarray) -> np.ndarray:
         it = _i32(items)
         x = np.empty((it.shape[0], 120, 32), dtype=np.float32)
-        self._chk(self.lib.said_train_gather(self.h, which_set, it.shape[0], it.ctypes.data_as(POINTER(c_int)), x.ctypes.data_as(_c_float_p)),
-                  "said_train_gather")
+        self._call("said_train_gather", which_set, it.shape[0], it.ctypes.data_as(POINTER(c_int)), x.ctypes.data_as(_c_float_p))
         return x
 
     @staticmethod
@@ -960,34 +849,32 @@ class TrainEngine:
 
     def step(self, items: np.ndarray, eps: np.ndarray, scalars: np.ndarray, std: Optional[np.ndarray], use_graph: bool = True) -> None:
         it, ep, sc, sd = _i32(items), _f32(eps), _f32(scalars), self._opt_f32(std)
-        self._chk(self.lib.said_train_step(self.h, it.shape[0], it.ctypes.data_as(POINTER(c_int)), ep.ctypes.data_as(_c_float_p),
-                                           sc.ctypes.data_as(_c_float_p), None if sd is None else sd.ctypes.data_as(_c_float_p), int(bool(use_graph))),
-                  "said_train_step")
+        self._call("said_train_step", it.shape[0], it.ctypes.data_as(POINTER(c_int)), ep.ctypes.data_as(_c_float_p),
+                   sc.ctypes.data_as(_c_float_p), None if sd is None else sd.ctypes.data_as(_c_float_p), int(bool(use_graph)))
 
     def apply_update(self, scalars: np.ndarray) -> None:
         sc = _f32(scalars)
-        self._chk(self.lib.said_train_apply_update(self.h, sc.ctypes.data_as(_c_float_p)), "said_train_apply_update")
+        self._call("said_train_apply_update", sc.ctypes.data_as(_c_float_p))
 
     def eval_loss(self, which_set: int, items: np.ndarray, eps: np.ndarray, scalars: np.ndarray, std: Optional[np.ndarray], ema: bool) -> None:
         it, ep, sc, sd = _i32(items), _f32(eps), _f32(scalars), self._opt_f32(std)
-        self._chk(self.lib.said_train_eval_loss(self.h, which_set, it.shape[0], it.ctypes.data_as(POINTER(c_int)), ep.ctypes.data_as(_c_float_p),
-                                                sc.ctypes.data_as(_c_float_p), None if sd is None else sd.ctypes.data_as(_c_float_p), int(bool(ema))),
-                  "said_train_eval_loss")
+        self._call("said_train_eval_loss", which_set, it.shape[0], it.ctypes.data_as(POINTER(c_int)), ep.ctypes.data_as(_c_float_p),
+                   sc.ctypes.data_as(_c_float_p), None if sd is None else sd.ctypes.data_as(_c_float_p), int(bool(ema)))
 
     def read_losses(self, val: bool, reset: bool = True):
         acc = np.zeros(TRAIN_NACC, dtype=np.float64)
         st = c_int(0)
-        self._chk(self.lib.said_train_read_losses(self.h, int(bool(val)), _dp(acc), ctypes.byref(st), int(bool(reset))), "said_train_read_losses")
+        self._call("said_train_read_losses", int(bool(val)), _dp(acc), ctypes.byref(st), int(bool(reset)))
         return acc, int(st.value)
 
     def last_losses(self) -> np.ndarray:
         out = np.zeros(4, dtype=np.float32)
-        self._chk(self.lib.said_train_last_losses(self.h, out.ctypes.data_as(_c_float_p)), "said_train_last_losses")
+        self._call("said_train_last_losses", out.ctypes.data_as(_c_float_p))
         return out
 
     def bn_stats(self, bn: int, channels: int) -> np.ndarray:
         out = np.zeros(2 * channels, dtype=np.float32)
-        self._chk(self.lib.said_train_bn_stats(self.h, bn, out.ctypes.data_as(_c_float_p)), "said_train_bn_stats")
+        self._call("said_train_bn_stats", bn, out.ctypes.data_as(_c_float_p))
         return out.reshape(2, channels)
 
     def graph_count(self) -> int:

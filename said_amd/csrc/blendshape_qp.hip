@@ -531,13 +531,8 @@ extern "C" {
 int said_optimize_create(said_optimize** out, int device) {
     if (!out) return fail(nullptr, "said_optimize_create: out is null");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, "said_optimize_create: no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(nullptr, "said_optimize_create: device %d out of range (%d visible)", device, ndev);
     DeviceRestore restore_device;
-    hipDeviceProp_t prop;
-    if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(nullptr, "said_optimize_create: cannot query device %d", device);
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(nullptr, "said_optimize_create: device is %s; this library is built for gfx950 only", prop.gcnArchName);
+    if (open_device("said_optimize_create", device)) return -1;
     said_optimize* o = new said_optimize();
     o->c.device = device;
     *out = o;
@@ -547,8 +542,7 @@ int said_optimize_create(said_optimize** out, int device) {
 int said_optimize_destroy(said_optimize* o) {
     if (!o) return 0;
     DeviceRestore restore_device;
-    (void)hipSetDevice(o->c.device);
-    for (void* p : o->c.allocs) (void)hipFree(p);
+    free_allocs(&o->c);
     delete o;
     return 0;
 }

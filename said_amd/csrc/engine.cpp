@@ -20,6 +20,24 @@ int fail(HostCtx* c, const char* fmt, ...) {
     return -1;
 }
 
+int open_device(const char* entry, int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, "%s: no HIP device visible (this library has no CPU path)", entry);
+    if (device < 0 || device >= ndev) return fail(nullptr, "%s: device %d out of range (%d visible)", entry, device, ndev);
+    hipDeviceProp_t prop;
+    if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(nullptr, "%s: cannot query device %d", entry, device);
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(nullptr, "%s: device is %s; this library is built for gfx950 only", entry, prop.gcnArchName);
+    return 0;
+}
+
+void free_allocs(HostCtx* c) {
+    (void)hipSetDevice(c->device);
+    for (void* p : c->allocs) (void)hipFree(p);
+    for (void* p : c->ws_allocs) (void)hipFree(p);
+    c->allocs.clear();
+    c->ws_allocs.clear();
+}
+
 int check_ready(said_ctx* ctx) {
     if (!ctx) return -1;
     if (!ctx->finalized) return fail(ctx, "weights not finalized: call said_finalize_weights first");
@@ -119,27 +137,14 @@ int said_abi_version(void) { return 9; }   // 9: said_set_precision modes (SAID_
 const char* said_last_error(const said_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
 int said_create(said_ctx** out, int device, int max_batch_eff, int max_frames, int in_channels, int ctx_dim) {
-    said_ctx* ctx = nullptr;
     if (!out) return fail(nullptr, "said_create: out is null");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, "said_create: no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(nullptr, "said_create: device %d out of range (%d visible)", device, ndev);
+    DeviceRestore restore_device;
+    if (open_device("said_create", device)) return -1;
     if (max_batch_eff < 1 || max_frames < 1) return fail(nullptr, "said_create: bad sizes");
     if (in_channels != 32) return fail(nullptr, "said_create: in_channels must be 32 (got %d)", in_channels);
     if (ctx_dim < 16 || ctx_dim % 16) return fail(nullptr, "said_create: ctx_dim must be a positive multiple of 16 (got %d)", ctx_dim);
-    DeviceRestore restore_device;
-    {
-        hipError_t e = hipSetDevice(device);
-        if (e != hipSuccess) return fail(nullptr, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
-        hipDeviceProp_t prop;
-        e = hipGetDeviceProperties(&prop, device);
-        if (e != hipSuccess) return fail(nullptr, "hipGetDeviceProperties: %s", hipGetErrorString(e));
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return fail(nullptr, "said_create: device is %s; this library is built for gfx950 only", prop.gcnArchName);
-    }
-    ctx = new said_ctx();
+    said_ctx* ctx = new said_ctx();
     ctx->device = device; ctx->cin = in_channels; ctx->ctx_dim = ctx_dim;
     configure_gemm_kernels();
     configure_ugemm_kernels();
@@ -170,8 +175,7 @@ int said_destroy(said_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     drop_graphs(ctx);
     release_cap_streams(ctx);   // (own_stream belongs to the pool)
-    for (void* p : ctx->allocs) (void)hipFree(p);
-    for (void* p : ctx->ws_allocs) (void)hipFree(p);
+    free_allocs(ctx);
     delete ctx;
     return 0;
 }

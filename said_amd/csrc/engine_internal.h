@@ -29,7 +29,7 @@ constexpr int FFI = 768;      // GEGLU inner dim (4 * 192)
 constexpr int NRES = 5, NST = 4;
 constexpr int W2V_H = 768, W2V_HEADS = 12, W2V_HD = 64, W2V_FFN = 3072, W2V_CONV = 512;
 
-extern std::string g_create_err;   // the error of a failed said_create / said_vae_create (engine.cpp)
+extern std::string g_create_err;   // the error of a failed said_*_create (engine.cpp)
 
 struct HostTensor {
     std::vector<float> data;
@@ -236,6 +236,11 @@ namespace said {
 namespace host __attribute__((visibility("hidden"))) {
 
 int fail(HostCtx* c, const char* fmt, ...);
+// Every said_*_create: `device` exists and is a gfx950, and is made current (the caller holds a DeviceRestore); failures are create errors
+// ("<entry>: ...", said_*_last_error(NULL)).
+int open_device(const char* entry, int device);
+// Every said_*_destroy: frees the context's device allocations with its device made current (the caller holds a DeviceRestore).
+void free_allocs(HostCtx* c);
 
 // fp32 mode multiplies on split-fp16 operands (split_f16.h) unless the caller asked for strict fp32 (said_set_precision) or the weights do not fit the
 // representation (scan_split_range): `opt` is one of the per-kernel-family development switches (said_debug_option), all on by default.

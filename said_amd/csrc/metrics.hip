@@ -341,14 +341,9 @@ extern "C" {
 int said_metrics_create(said_metrics** out, int device, long long max_points) {
     if (!out) return fail(nullptr, "said_metrics_create: out is null");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, "said_metrics_create: no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(nullptr, "said_metrics_create: device %d out of range (%d visible)", device, ndev);
-    if (max_points < 1 || max_points > (1LL << 30)) return fail(nullptr, "said_metrics_create: max_points %lld outside [1, 2^30]", max_points);
     DeviceRestore restore_device;
-    hipDeviceProp_t prop;
-    if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(nullptr, "said_metrics_create: cannot query device %d", device);
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(nullptr, "said_metrics_create: device is %s; this library is built for gfx950 only", prop.gcnArchName);
+    if (open_device("said_metrics_create", device)) return -1;
+    if (max_points < 1 || max_points > (1LL << 30)) return fail(nullptr, "said_metrics_create: max_points %lld outside [1, 2^30]", max_points);
     said_metrics* m = new said_metrics();
     HostCtx* ctx = &m->c;
     ctx->device = device;
@@ -363,8 +358,7 @@ int said_metrics_create(said_metrics** out, int device, long long max_points) {
         dalloc(ctx, &m->red, (size_t)KMAX * D * D, false) || dalloc(ctx, &m->prm, prm_n, false) || dalloc(ctx, &m->cpart, (size_t)m->pblk, false) ||
         dalloc(ctx, &m->cand, (size_t)TMAX, false)) {
         g_create_err = ctx->err;
-        for (void* p : ctx->allocs) (void)hipFree(p);
-        delete m;
+        said_metrics_destroy(m);
         return -1;
     }
     *out = m;
@@ -374,8 +368,7 @@ int said_metrics_create(said_metrics** out, int device, long long max_points) {
 int said_metrics_destroy(said_metrics* m) {
     if (!m) return 0;
     DeviceRestore restore_device;
-    (void)hipSetDevice(m->c.device);
-    for (void* p : m->c.allocs) (void)hipFree(p);
+    free_allocs(&m->c);
     delete m;
     return 0;
 }

@@ -137,15 +137,10 @@ extern "C" {
 int said_vae_create(said_vae** out, int device, int in_channels, int seq_len, int z_dim) {
     if (!out) return fail(nullptr, "said_vae_create: out is null");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, "said_vae_create: no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(nullptr, "said_vae_create: device %d out of range (%d visible)", device, ndev);
+    DeviceRestore restore_device;
+    if (open_device("said_vae_create", device)) return -1;
     if (in_channels != 32 || seq_len != 120 || z_dim != 64)
         return fail(nullptr, "said_vae_create: only BCVAE(channels=32, seq_len=120, z_dim=64) is supported (the FC stack is sized for it, vae.py:52)");
-    DeviceRestore restore_device;
-    hipDeviceProp_t prop;
-    if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(nullptr, "said_vae_create: cannot query device %d", device);
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(nullptr, "said_vae_create: device is %s; this library is built for gfx950 only", prop.gcnArchName);
     said_vae* v = new said_vae();
     v->c.device = device;
     v->seq_len = seq_len; v->cin = in_channels; v->zdim = z_dim;
@@ -159,8 +154,7 @@ int said_vae_create(said_vae** out, int device, int in_channels, int seq_len, in
 int said_vae_destroy(said_vae* v) {
     if (!v) return 0;
     DeviceRestore restore_device;
-    (void)hipSetDevice(v->c.device);
-    for (void* p : v->c.allocs) (void)hipFree(p);
+    free_allocs(&v->c);
     delete v;
     return 0;
 }

@@ -280,14 +280,9 @@ int said_train_tensor_is_counter(int i) { return (i >= 0 && i < 70) ? (kTensors[
 int said_train_create(said_train** out, int device, int max_batch) {
     if (!out) return fail(nullptr, "said_train_create: out is null");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, "said_train_create: no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(nullptr, "said_train_create: device %d out of range (%d visible)", device, ndev);
-    if (max_batch < 1 || max_batch > 4096) return fail(nullptr, "said_train_create: max_batch %d outside [1, 4096]", max_batch);
     DeviceRestore restore_device;
-    hipDeviceProp_t prop;
-    if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(nullptr, "said_train_create: cannot query device %d", device);
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(nullptr, "said_train_create: device is %s; this library is built for gfx950 only", prop.gcnArchName);
+    if (open_device("said_train_create", device)) return -1;
+    if (max_batch < 1 || max_batch > 4096) return fail(nullptr, "said_train_create: max_batch %d outside [1, 4096]", max_batch);
     said_train* t = new said_train();
     HostCtx* ctx = &t->c;
     ctx->device = device;
@@ -348,7 +343,7 @@ int said_train_destroy(said_train* t) {
     for (int k = 0; k < RING; ++k)
         if (t->ring_ev[k]) (void)hipEventDestroy(t->ring_ev[k]);
     if (t->ring) (void)hipHostFree(t->ring);
-    for (void* p : t->c.allocs) (void)hipFree(p);
+    free_allocs(&t->c);
     if (t->s) (void)hipStreamDestroy(t->s);
     delete t;
     return 0;

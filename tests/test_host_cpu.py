@@ -29,14 +29,51 @@ def test_library_exports_every_declared_symbol():
     assert lib.said_abi_version() == _engine.ABI_VERSION == 9
 
 
+def _declarations(path):
+    """{said_* entry point: parameter count} of the declarations in a header."""
+    code = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, path)).read(), flags=re.S)
+    return {name: 0 if params.strip() in ("", "void") else params.count(",") + 1
+            for name, params in re.findall(r"\b(said_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code)}
+
+
+def test_every_header_matches_its_binding_table():
+    """Every header's declarations are its ctypes table (one argtypes entry per parameter) and are exported by the built library."""
+    from said_amd import _engine
+    lib = _engine.load_library()
+    lazy = {group: table for group, (_, table) in _engine.LAZY_EXPORTS.items()}
+    decoder = lazy.pop("vae_decoder")
+    assert decoder.items() <= _engine.EXPORTS.items(), "the decoder group is part of said_hip.h's table"
+    tables = {("include/said_hip.h", "said_amd/csrc/said_hip_debug.h"): _engine.EXPORTS,
+              ("include/said_metrics.h",): lazy.pop("metrics"), ("include/said_optimize.h",): lazy.pop("optimize"),
+              ("include/said_train.h",): lazy.pop("train")}
+    assert not lazy, f"binding groups without a header here: {sorted(lazy)}"
+    declared, bound = {}, {}
+    for headers, table in tables.items():
+        decl = {name: n for h in headers for name, n in _declarations(h).items()}
+        assert decl, f"no declarations parsed in {headers}"
+        assert set(decl) == set(table), (headers, set(decl) ^ set(table))
+        declared.update(decl)
+        bound.update(table)
+    assert set(declared) == set(bound) and len(declared) == 83
+    for name, nparams in declared.items():
+        assert hasattr(lib, name), f"{name} is declared but not exported"
+        assert len(bound[name][1]) == nparams, f"{name}: {nparams} parameters declared, {len(bound[name][1])} argtypes bound"
+
+
 def test_no_gpu_means_loud_failure_not_fallback():
     from said_amd import _engine
     if torch.cuda.is_available():
         pytest.skip("GPU present")
-    with pytest.raises(_engine.EngineError):
-        _engine.Engine(torch.device("cuda:0"), 2, 64)
-    with pytest.raises(_engine.EngineError):
-        _engine.Engine(torch.device("cpu"), 2, 64)
+    E, N = _engine.EngineError, _engine.NoCpuPathError
+    for make, cpu_error in ((lambda d: _engine.Engine(d, 2, 64), E), (lambda d: _engine.VaeEngine(d), E),
+                            (lambda d: _engine.MetricsEngine(d, 16), N), (lambda d: _engine.OptimizeEngine(d), N),
+                            (lambda d: _engine.TrainEngine(d, 4), N)):
+        with pytest.raises(E) as e:
+            make(torch.device("cuda:0"))   # said_*_create: no HIP device visible
+        assert type(e.value) is E, e.value
+        with pytest.raises(cpu_error) as e:
+            make(torch.device("cpu"))
+        assert type(e.value) is cpu_error, e.value
 
 
 def test_product_never_imports_oracle():
