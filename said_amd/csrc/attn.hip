@@ -50,7 +50,7 @@ struct AttnView {
     float scale;
     int b0;
     int o_mode;   // 0: o channel-major fp32 [b][h * D + d][pitch]; 1 / 2: TOKEN-major fp32 / bf16 [b * o_bstride + i][h * D + d] (o_bstride =
-                  // sample pitch in tokens) — the layout of the round-3 token-major activation path (tgemm.hip: xgemm_kernel)
+                  // sample pitch in tokens) — the layout of the round-3 token-major activation path (xgemm.hip: xgemm_kernel)
 };
 // BF: both products run on v_mfma_f32_32x32x16_bf16 (said_set_precision; round 2: CDNA4's 16-deep opcode, half the MFMA count of
 // the 32x32x8 form).  The operand registers are the same ones: MFMA m of S^T contracts d = lh * D/2 + 8m + (0..7), i.e. the

@@ -332,7 +332,7 @@ __global__ __launch_bounds__(512, 2) void rgemm_kernel(const TGemmArgs a) {
                 const int t = t0 + fr;
                 const bool tv = t < a.M;
                 const int tc = min(t, a.M - 1);
-                band_head<true>(a, acc[0][0], b, t, tv, a.band_lo[tc], a.band_hi[tc], j, l);
+                band_head(a, acc[0][0], b, t, tv, a.band_lo[tc], a.band_hi[tc], j, l);
             } else {
                 // ---- this wave's 32 x 32 tile: MFMA layout (lane == column) -> scratch -> rows (lane == 8 consecutive columns of a row)
 #pragma unroll

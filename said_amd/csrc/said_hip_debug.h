@@ -20,7 +20,7 @@ extern "C" {
  *   "tm_acts"                bf16 mode, large batches: token-major bf16 activations between the UNet kernels, GroupNorm / LayerNorm applied inside the consuming
  *                            GEMMs (-1 / 1, default); 0: channel-major fp32 activations with preparation kernels (round 2).  (The fp32 twin of the schedule, measured
  *                            slower in round 3, was removed in round 6.)
- *   "tgemm_direct"           0: the bf16 audio encoder's projections on tgemm_kernel<128> (rounds 2-5); -1 / 1 (default): on tgemm256d_kernel — 256 x 256 x 64 tile, operand tiles
+ *   "tgemm_direct"           0: the bf16 audio encoder's projections on tgemm_kernel<128, 128> (rounds 2-5); -1 / 1 (default): on tgemm256d_kernel — 256 x 256 x 64 tile, operand tiles
  *                            loaded global -> LDS directly, XOR-swizzled chunks, one barrier per k-tile (round 6; bit-identical)
  *   "out_tm"                 0: bf16 large batches end the step with round 3's channel-major out conv + scheduler kernel (default -1: out_sched_tm_kernel)
  *   "gemm_presplit"          fp32 mode, large batches: 0 = fgemm_kernel splits fp32 operands in its k loop (round 5); -1 / 1 (default): the ResBlock convolutions' and q / k / v's

@@ -1,5 +1,5 @@
-// tgemm.h — launch interface of the token-major GEMMs (bf16: tgemm_kernel / tgemm256_kernel, fp32: fgemm_kernel) and their
-// companion kernels (tgemm.hip).
+// tgemm.h — launch interface of the token-major GEMMs (tgemm.hip: the bf16 tiles; fgemm.hip: fgemm_kernel; xgemm.hip; rgemm.hip) and their
+// companion kernels (tm_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,7 +60,7 @@ struct TGemmArgs {
     // (seg_rows % 32 == 0, >= M); row R is sample R / seg_rows, token R % seg_rows; tokens >= M are padding.  0: per-sample
     // operands addressed through a_bs (audio encoder).
     int seg_rows;
-    int sb;                // tgemm_kernel<128> only: 1 = single-LDS-buffer variant (four workgroups per CU)
+    int sb;                // tgemm_kernel<128, 128> only: 1 = single-LDS-buffer variant (four workgroups per CU)
     int direct;            // 1: per-sample operands with N % 256 == 0 run tgemm256d_kernel (256 x 256 tile, operand tiles loaded straight into LDS; round 6)
     int grp;               // tgemm_kernel only: > 1 = grouped launch, the batch axis is (sample, group) [batch = samples x grp]; group g reads A at
     long long a_gs, w_gs;  //   a + sample a_bs + g a_gs and W at w + g w_gs (elements) and owns the output columns [g col_gs, g col_gs + n_store)
@@ -113,6 +113,9 @@ bool tgemm_supports(const TGemmArgs& a);
 // false: shape not served by any instantiation (nothing launched) — the caller reports it through the C ABI
 bool launch_tgemm(const TGemmArgs& a, int batch, hipStream_t s);   // N % 128 == 0: 128-wide tiles, else N % 64 == 0: 64-wide
 void configure_tgemm_kernel();
+// fgemm.hip: the fp32 / bf16 batch-as-rows branch of launch_tgemm and configure_tgemm_kernel (internal: callers use those two)
+bool launch_fgemm(const TGemmArgs& a, hipStream_t s);
+void configure_fgemm_kernels();
 // GEMMs on token-major activations with the operand transform inside (TGemmArgs fields of round 3)
 bool xgemm_supports(const TGemmArgs& a);
 bool launch_xgemm(const TGemmArgs& a, int batch, hipStream_t s);

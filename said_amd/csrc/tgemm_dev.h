@@ -1,4 +1,4 @@
-// tgemm_dev.h — device code shared by the token-major GEMM kernels (tgemm.hip: tgemm / fgemm / xgemm; rgemm.hip: the persistent register-stationary GEMMs of round 4): the epilogues of one 32-row MFMA tile and the banded cross-attention of one head.
+// tgemm_dev.h — device code shared by the token-major GEMM kernels (tgemm.hip: the bf16 tiles; fgemm.hip; xgemm.hip; rgemm.hip: the persistent register-stationary GEMMs of round 4): the XCD-aware tile order, the K-split tile's LDS size, the epilogues of one 32-row MFMA tile and the banded cross-attention of one head.
 #pragma once
 #include "gemm_common.h"
 #include "tgemm.h"
@@ -9,6 +9,26 @@ namespace said {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4t __attribute__((ext_vector_type(4)));
+
+// XCD-aware tile order: blockIdx.x -> (n tile, global M-tile index over the batch).  The hardware places consecutive workgroup ids on consecutive XCDs (id % 8), each
+// with its own L2.  The NT = N / BN workgroups that share an A tile are given consecutive slots of ONE XCD (n tile fastest), so the A tile is
+// fetched from HBM / Infinity Cache once and hits that XCD's L2 for the other column tiles; the weights are small and
+// stay resident in every L2.  (The natural (m, n) grid re-fetched every A tile N / BN times from beyond L2.)
+// The grid pads the M-tile count to a multiple of 8: the caller returns for the tiles past the end.
+__device__ __forceinline__ void xcd_tile(int NT, int& nt, int& mg) {
+    const unsigned L = blockIdx.x, xcd = L & 7u, slot = L >> 3;
+    nt = (int)(slot % (unsigned)NT);
+    mg = (int)(slot / (unsigned)NT) * 8 + (int)xcd;
+}
+
+// fgemm_kernel's tile (fgemm.hip; xgemm_kernel keeps its workgroup, k-tile geometry and K-half exchange): NJ column tiles of 32
+constexpr int FBK = 32;   // k per tile of the fp32 kernel (host-side checks)
+template <int NJ>
+__host__ __device__ constexpr int fgemm_lds_bytes() {
+    const int tiles = (64 + 32 * NJ) * 144, exch = 2 * NJ * 16 * 64 * 4,
+              scratch = NJ == 4 ? 4 * 32 * (32 * 2 + 4) * 4 : 2 * 32 * (32 * NJ + 4) * 4;
+    return tiles > scratch ? (tiles > exch ? tiles : exch) : (scratch > exch ? scratch : exch);
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 // Epilogues shared by the two tile shapes, one 32-row tile of a wave at a time.
@@ -204,7 +224,6 @@ static __device__ __forceinline__ f32x4t xbload4(rsrc_t r, int voff) {
 }
 
 // banded cross-attention on the transposed q tile of one head: acc[r] = q[d = (r & 3) + 8 (r >> 2) + 4 lh][token lt]
-template <bool BF>
 __device__ __forceinline__ void band_head(const TGemmArgs& a, const f32x16& q, int b, int t, bool tv, int lo, int hi, int head, int l) {
     const int lh = l >> 5;
     const int kvp = a.band_kv_pitch;
@@ -264,14 +283,9 @@ __device__ __forceinline__ void band_head(const TGemmArgs& a, const f32x16& q, i
 #pragma unroll
     for (int qd = 0; qd < 4; ++qd) {
         const long long off = row * a.ldy + head * 32 + 8 * qd + 4 * lh;
-        if constexpr (BF) {
-            typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-            const bf16x4 ov = {(__bf16)o[4 * qd], (__bf16)o[4 * qd + 1], (__bf16)o[4 * qd + 2], (__bf16)o[4 * qd + 3]};
-            *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(a.y_tm) + off) = ov;
-        } else {
-            const f32x4t ov = {o[4 * qd], o[4 * qd + 1], o[4 * qd + 2], o[4 * qd + 3]};
-            *reinterpret_cast<f32x4t*>(reinterpret_cast<float*>(a.y_tm) + off) = ov;
-        }
+        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+        const bf16x4 ov = {(__bf16)o[4 * qd], (__bf16)o[4 * qd + 1], (__bf16)o[4 * qd + 2], (__bf16)o[4 * qd + 3]};
+        *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(a.y_tm) + off) = ov;
     }
 }
 

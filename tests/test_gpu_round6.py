@@ -491,7 +491,7 @@ def test_sliced_tail_reads_the_groupnorm_coefficients_the_qkv_gemm_finalised(dev
 @pytest.mark.parametrize("B,Ta", [(32, 160000), (9, 16000 * 3), (40, 16000)])
 def test_direct_to_lds_gemm_tile_is_bit_identical_to_the_staged_tiles(dev, B, Ta):
     """bf16 mode's audio encoder runs its q/k/v, out_proj and feed-forward projections (where a pass has >= 4096 rows) on tgemm256d_kernel: 256 x 256 x 64 tiles whose
-    operand tiles go global -> LDS directly (XOR-swizzled 16-byte chunks, one barrier per k-tile).  Same operands, same k order per accumulator as tgemm_kernel<128>
+    operand tiles go global -> LDS directly (XOR-swizzled 16-byte chunks, one barrier per k-tile).  Same operands, same k order per accumulator as tgemm_kernel<128, 128>
     (said_debug_option "tgemm_direct" = 0): the embedding is bit-identical — rows past the last tile boundary (499 / 149 / 49 frames per clip), a 40-clip batch in two
     passes; and it stays at the oracle's bf16 distance (tests/test_gpu_parity.py::test_bf16_audio_encoder_vs_fp32_oracle runs on it: it is the default)."""
     m = _make(_base_sd(), dev)   # (two encoder layers: eight projection GEMMs per pass)
