@@ -1,4 +1,4 @@
-"""ctypes binding of libsaid_hip.so (C ABI: include/said_hip.h, said_metrics.h, said_optimize.h, said_train.h).
+"""ctypes binding of libsaid_hip.so (C ABI: include/said_hip.h, said_metrics.h, said_optimize.h, said_train.h, said_render.h).
 
 There is deliberately no fallback: if the library is missing, cannot be loaded,
 or no gfx950 device is visible, every entry point raises.
@@ -148,7 +148,22 @@ LAZY_EXPORTS = {
         "said_train_graph_count": (c_int, [c_void_p]),
     }),
 }
-_bound = set()   # the LAZY_EXPORTS groups bound so far
+# include/said_render.h: a group like those of LAZY_EXPORTS, kept in a table of its own (tests/test_render_cpu.py checks it against its header)
+RENDER_EXPORTS = {
+    "said_render_create": (c_int, [POINTER(c_void_p), c_int]),
+    "said_render_destroy": (c_int, [c_void_p]),
+    "said_render_last_error": (c_char_p, [c_void_p]),
+    "said_render_set_mesh": (c_int, [c_void_p, c_int, c_int, c_int, _c_double_p, POINTER(c_int), _c_double_p, c_void_p]),
+    "said_render_set_scene": (c_int, [c_void_p, c_void_p]),
+    "said_render_set_colormap": (c_int, [c_void_p, _c_float_p, c_void_p]),
+    "said_render_render": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_float, _c_double_p, _c_double_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "said_render_read_vertices": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
+    "said_render_read_normals": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
+    "said_render_read_colors": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
+}
+_GROUPS = {**LAZY_EXPORTS, "render": ("the renderer", RENDER_EXPORTS)}
+_bound = set()   # the groups bound so far
 
 
 def library_path() -> str:
@@ -163,7 +178,7 @@ def _bind(lib, table):
 
 
 def load_library(group: Optional[str] = None):
-    """dlopen the engine and bind EXPORTS but the VAE decoder (no compute); with `group`, also that group of LAZY_EXPORTS."""
+    """dlopen the engine and bind EXPORTS but the VAE decoder (no compute); with `group`, also that group of LAZY_EXPORTS (or "render")."""
     global _lib
     if _lib is None:
         if not os.path.exists(_LIB_PATH):
@@ -178,7 +193,7 @@ def load_library(group: Optional[str] = None):
                               "`python -m said_amd.build --force`")
         _lib = lib
     if group is not None and group not in _bound:
-        feature, table = LAZY_EXPORTS[group]
+        feature, table = _GROUPS[group]
         for name in table:
             if not hasattr(_lib, name):
                 raise EngineError(f"{_LIB_PATH} predates {feature} ({name} is not exported): rebuild it with `python -m said_amd.build --force`")
@@ -879,3 +894,107 @@ class TrainEngine(_Context):
 
     def graph_count(self) -> int:
         return int(self.lib.said_train_graph_count(self.h))
+
+
+# ---- renderer (include/said_render.h)
+RENDER_MAX_K, RENDER_MAX_LIGHTS, RENDER_LUT = 64, 4, 256   # SAID_RENDER_*
+
+
+class RenderScene(ctypes.Structure):
+    """said_render_scene."""
+    _fields_ = [
+        ("width", c_int), ("height", c_int),
+        ("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float), ("znear", c_float), ("zfar", c_float),
+        ("cam_pos", c_float * 3), ("n_lights", c_int),
+        ("light_pos", (c_float * 3) * RENDER_MAX_LIGHTS), ("light_intensity", c_float * RENDER_MAX_LIGHTS),
+        ("ambient", c_float), ("base_color", c_float * 3),
+        ("metallic", c_float), ("roughness", c_float), ("vc_metallic", c_float), ("vc_roughness", c_float),
+    ]
+
+
+class RenderEngine(_Context):
+    """said_render context on one GPU (include/said_render.h): a mesh with its blendshape basis, a scene, and the four kernels of a chunk."""
+    prefix, group = "said_render", "render"
+    cpu_error, cpu_message = NoCpuPathError, "said_amd renders on MI355X only (device={}); there is no CPU path"
+
+    def __init__(self, device: torch.device):
+        super().__init__(device)
+        self._create()
+        self.nv = self.nf = self.k = 0
+        self.width = self.height = 0
+
+    def set_mesh(self, neutral: np.ndarray, faces: np.ndarray, blendshapes_matrix: np.ndarray) -> None:
+        """neutral (V, 3), faces (F, 3) vertex indices, blendshapes_matrix (3V, K) = [b_1 | ... | b_K] (not deltas)."""
+        n = np.ascontiguousarray(neutral, dtype=np.float64).reshape(-1, 3)
+        fa = np.asarray(faces)
+        if fa.ndim != 2 or fa.shape[1] != 3 or fa.dtype.kind not in "iu":
+            raise EngineError(f"faces must be an (F, 3) integer array, got {fa.shape} {fa.dtype}")
+        if fa.size and (fa.min() < -2**31 or fa.max() >= 2**31):
+            raise EngineError("faces hold indices outside int32")
+        fa = np.ascontiguousarray(fa, dtype=np.int32)
+        b = np.ascontiguousarray(blendshapes_matrix, dtype=np.float64)
+        if b.ndim != 2 or b.shape[0] != n.size:
+            raise EngineError(f"blendshapes_matrix must be (3V, K) = ({n.size}, K), got {b.shape}")
+        self.nv = self.nf = self.k = 0
+        with torch.cuda.device(self.index):
+            self._call("said_render_set_mesh", n.shape[0], fa.shape[0], b.shape[1], _dp(n), fa.ctypes.data_as(POINTER(c_int)), _dp(b), _stream())
+        self.nv, self.nf, self.k = n.shape[0], fa.shape[0], b.shape[1]
+
+    def set_scene(self, scene: RenderScene) -> None:
+        self._call("said_render_set_scene", ctypes.byref(scene))
+        self.width, self.height = int(scene.width), int(scene.height)
+
+    def set_colormap(self, lut: np.ndarray) -> None:
+        """lut (256, 3) RGB in [0, 1]."""
+        a = _f32(lut)
+        if a.shape != (RENDER_LUT, 3):
+            raise EngineError(f"the colour table must be ({RENDER_LUT}, 3), got {a.shape}")
+        with torch.cuda.device(self.index):
+            self._call("said_render_set_colormap", a.ctypes.data_as(_c_float_p), _stream())
+
+    def render(self, coeffs: torch.Tensor, t0: int, n_frames: int, out: torch.Tensor, target: Optional[torch.Tensor] = None, max_diff: float = 0.001,
+               rot=None, t_center=None, face_ids: Optional[torch.Tensor] = None) -> None:
+        """Frames [t0, t0 + n_frames) of coeffs (T, K) into out, a contiguous (>= n_frames, H, W, 3) uint8 device tensor, B G R; enqueued on the
+        current stream.  face_ids: a contiguous (>= n_frames, H, W) int32 device tensor that receives the face drawn at each pixel (-1: none)."""
+        if self.nf == 0:
+            raise EngineError("said_render_render: no mesh set (set_mesh)")
+        coeffs = _check_dev(coeffs, "blendshape_coeffs")
+        if coeffs.dim() != 2 or coeffs.shape[1] != self.k:
+            raise EngineError(f"blendshape_coeffs must be (T, {self.k}), got {tuple(coeffs.shape)}")
+        if t0 < 0 or n_frames < 1 or t0 + n_frames > coeffs.shape[0]:
+            raise EngineError(f"frames [{t0}, {t0 + n_frames}) lie outside the {coeffs.shape[0]} frames of blendshape_coeffs")
+        if target is not None:
+            target = _check_dev(target, "target_blendshape_coeffs")
+            if target.shape != coeffs.shape:
+                raise EngineError(f"target_blendshape_coeffs must have the shape of blendshape_coeffs {tuple(coeffs.shape)}, got {tuple(target.shape)}")
+        need = n_frames * self.height * self.width
+        for t, name, dt, per in ((out, "out", torch.uint8, 3), (face_ids, "face_ids", torch.int32, 1)):
+            if t is None:
+                continue
+            if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() < need * per or t.device.index != self.index:
+                raise EngineError(f"{name} must be a contiguous {dt} tensor on cuda:{self.index} with room for {n_frames} frames of {self.height} x {self.width}")
+        if coeffs.device.index != self.index:
+            raise EngineError(f"blendshape_coeffs live on cuda:{coeffs.device.index}, this renderer on cuda:{self.index}")
+        r = None if rot is None else np.ascontiguousarray(rot, dtype=np.float64).reshape(3)
+        c = None if t_center is None else np.ascontiguousarray(t_center, dtype=np.float64).reshape(3)
+        with torch.cuda.device(self.index):
+            self._call("said_render_render", _ptr(coeffs), _ptr(target), int(t0), int(n_frames), float(max_diff), None if r is None else _dp(r),
+                       None if c is None else _dp(c), _ptr(out), _ptr(face_ids), _stream())
+        self._keep = (coeffs, target)   # alive until the next call: the kernels may still be reading them
+
+    def _read(self, name: str, n_frames: int) -> np.ndarray:
+        out = np.empty((n_frames, self.nv, 3), dtype=np.float32)
+        with torch.cuda.device(self.index):
+            self._call(name, int(n_frames), out.ctypes.data_as(_c_float_p), _stream())
+        return out
+
+    def read_vertices(self, n_frames: int) -> np.ndarray:
+        """(n_frames, V, 3) vertices of the last render's chunk, before the rotation."""
+        return self._read("said_render_read_vertices", n_frames)
+
+    def read_normals(self, n_frames: int) -> np.ndarray:
+        return self._read("said_render_read_normals", n_frames)
+
+    def read_colors(self, n_frames: int) -> np.ndarray:
+        """(n_frames, V, 3) difference colours (R, G, B) of the last render's chunk."""
+        return self._read("said_render_read_colors", n_frames)

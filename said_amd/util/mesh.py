@@ -1,7 +1,10 @@
-"""Mesh vertex readers without trimesh (reference: said/util/mesh.py:load_mesh, trimesh.load(process=False, maintain_order=True)).
+"""Mesh readers and writers without trimesh (reference: said/util/mesh.py:load_mesh, trimesh.load(process=False, maintain_order=True)).
 
-Only the vertex positions are read, as (V, 3) float64 in file order: that is all the blendshape-coefficient fit
-(script/optimize_blendshape_coeffs.py) uses.  OBJ: every ``v x y z [...]`` line, extra components (w, vertex colours) ignored,
+``load_vertices`` reads only the vertex positions, as (V, 3) float64 in file order: that is all the blendshape-coefficient fit
+(script/optimize_blendshape_coeffs.py) uses.  ``load_mesh`` also reads the faces, for the renderer: OBJ ``f`` records in the ``v``,
+``v/vt``, ``v//vn`` and ``v/vt/vn`` forms, negative (relative) indices included, and PLY ``face`` lists (``vertex_indices`` or
+``vertex_index``), ascii and binary little-endian; polygons are split into a fan around their first vertex.  ``save_mesh`` writes OBJ
+or PLY that both readers take back.  OBJ: every ``v x y z [...]`` line, extra components (w, vertex colours) ignored,
 every other record skipped.  PLY: ``ascii`` and ``binary_little_endian`` with float / double x, y, z; other vertex properties
 and every other element (faces included, list properties too) are skipped.  Anything else raises ``MeshFormatError``."""
 from __future__ import annotations
@@ -133,3 +136,127 @@ def _ply_binary(path, body, elements):
             return np.stack([rec[c].astype(np.float64) for c in "xyz"], axis=1)
         off += count * dt.itemsize
     raise MeshFormatError(f"{path}: no vertex element")
+
+
+class Mesh:
+    """What the renderer needs of a trimesh.Trimesh: ``vertices`` (V, 3) float64 and ``faces`` (F, 3) int64, in file order."""
+
+    def __init__(self, vertices, faces):
+        self.vertices = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+        self.faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+
+
+def _fan(poly, out) -> None:
+    for i in range(1, len(poly) - 1):
+        out.append((poly[0], poly[i], poly[i + 1]))
+
+
+def load_mesh(path: str) -> Mesh:
+    """Vertices and triangles of an OBJ or PLY file; a face that names a vertex the file does not hold raises MeshFormatError."""
+    vertices = load_vertices(path)
+    ext = os.path.splitext(path)[1].lower()
+    faces = _obj_faces(path) if ext == ".obj" else _ply_faces(path)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= len(vertices)):
+        raise MeshFormatError(f"{path}: a face names vertex {int(f.max() if f.max() >= len(vertices) else f.min())}, the file holds {len(vertices)}")
+    return Mesh(vertices, f)
+
+
+def _obj_faces(path: str):
+    faces, nv = [], 0
+    with open(path, "r") as f:
+        for ln, line in enumerate(f, 1):
+            if line.startswith("v ") or line.startswith("v\t"):
+                nv += 1
+            elif line.startswith("f ") or line.startswith("f\t"):
+                poly = []
+                for tok in line.split()[1:]:
+                    try:
+                        i = int(tok.split("/")[0])
+                    except ValueError:
+                        raise MeshFormatError(f"{path}:{ln}: face element {tok!r} does not start with a vertex index") from None
+                    if i == 0:
+                        raise MeshFormatError(f"{path}:{ln}: OBJ indices start at 1")
+                    poly.append(i - 1 if i > 0 else nv + i)   # negative: relative to the vertices read so far
+                if len(poly) < 3:
+                    raise MeshFormatError(f"{path}:{ln}: face with fewer than 3 vertices")
+                _fan(poly, faces)
+    return faces
+
+
+def _ply_faces(path: str):
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    body = data[data.find(b"\n", end) + 1:]
+    fmt, elements = None, []
+    for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
+        p = line.split()
+        if not p:
+            continue
+        if p[0] == "format":
+            fmt = p[1]
+        elif p[0] == "element":
+            elements.append([p[1], int(p[2]), []])
+        elif p[0] == "property":
+            elements[-1][2].append((p[4], (_PLY_TYPES[p[2]], _PLY_TYPES[p[3]])) if p[1] == "list" else (p[2], _PLY_TYPES[p[1]]))
+    faces = []
+    if fmt == "ascii":
+        lines = body.decode("ascii", "replace").splitlines()
+        pos = 0
+        for name, count, props in elements:
+            if name == "face":
+                for i in range(count):
+                    vals = lines[pos + i].split()
+                    at = 0
+                    for pname, t in props:
+                        if isinstance(t, tuple):
+                            n = int(vals[at])
+                            if pname in ("vertex_indices", "vertex_index"):
+                                _fan([int(v) for v in vals[at + 1:at + 1 + n]], faces)
+                            at += 1 + n
+                        else:
+                            at += 1
+            pos += count
+        return faces
+    off = 0
+    for name, count, props in elements:
+        if not any(isinstance(t, tuple) for _, t in props):
+            off += count * sum(np.dtype(t).itemsize for _, t in props)
+            continue
+        for _ in range(count):
+            for pname, t in props:
+                if isinstance(t, tuple):
+                    cdt, idt = np.dtype("<" + t[0]), np.dtype("<" + t[1])
+                    if off + cdt.itemsize > len(body):
+                        raise MeshFormatError(f"{path}: {name} element ends early")
+                    n = int(np.frombuffer(body, dtype=cdt, count=1, offset=off)[0])
+                    off += cdt.itemsize
+                    if off + n * idt.itemsize > len(body):
+                        raise MeshFormatError(f"{path}: {name} element ends early")
+                    if name == "face" and pname in ("vertex_indices", "vertex_index"):
+                        _fan([int(v) for v in np.frombuffer(body, dtype=idt, count=n, offset=off)], faces)
+                    off += n * idt.itemsize
+                else:
+                    off += np.dtype(t).itemsize
+    return faces
+
+
+def save_mesh(mesh, path: str) -> None:
+    """Write ``mesh.vertices`` and ``mesh.faces`` as OBJ (17 significant digits: float64 round-trips) or binary little-endian PLY (double x, y, z)."""
+    v = np.asarray(mesh.vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(mesh.faces, dtype=np.int64).reshape(-1, 3)
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".obj":
+        with open(path, "w") as out:
+            out.writelines(f"v {x!r} {y!r} {z!r}\n" for x, y, z in v.tolist())
+            out.writelines(f"f {a + 1} {b + 1} {c + 1}\n" for a, b, c in f.tolist())
+    elif ext == ".ply":
+        head = (f"ply\nformat binary_little_endian 1.0\nelement vertex {len(v)}\nproperty double x\nproperty double y\nproperty double z\n"
+                f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
+        rec = np.empty(len(f), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+        rec["n"], rec["i"] = 3, f
+        with open(path, "wb") as out:
+            out.write(head.encode("ascii") + v.astype("<f8").tobytes() + rec.tobytes())
+    else:
+        raise MeshFormatError(f"{path}: unsupported mesh format {ext!r} (OBJ and PLY only)")

@@ -80,3 +80,67 @@ def prepared_audio(net: SAID_UNet1D, path: str, fps: int, divisor: int) -> Tuple
     """(1, Ta) normalised waveform on the model's device, padded for the UNet, and the number of frames to keep."""
     fitted = fit_audio_unet(load_audio(path, net.sampling_rate), net.sampling_rate, fps, divisor)
     return net.process_audio(fitted.waveform).to(next(net.parameters()).device), fitted.window_size
+
+
+# ---- rendering (script/render.py, script/test_render.py)
+def load_blendshape_basis(neutral_path: str, blendshapes_dir: str, names):
+    """(neutral mesh, (3V, K) matrix [b_1 | ... | b_K]) from <neutral_path> and <blendshapes_dir>/<name>.obj, as the reference's drivers build them."""
+    import numpy as np
+    from said_amd.util.mesh import load_mesh, load_vertices
+    neutral = load_mesh(neutral_path)
+    cols = []
+    for name in names:
+        v = load_vertices(os.path.join(blendshapes_dir, f"{name}.obj"))
+        if v.shape != neutral.vertices.shape:
+            raise ValueError(f"blendshape {name} has {len(v)} vertices, the neutral mesh {len(neutral.vertices)}")
+        cols.append(v.reshape(-1, 1))
+    return neutral, np.concatenate(cols, axis=1)
+
+
+def write_video(frames_iter, output_path: str, fps: int, audio_path: str, width: int = 800, height: int = 800, on_frame=None) -> str:
+    """Stream B-G-R frame chunks and the sound of audio_path into a video; returns the path written.  A path ending in .avi gets the built-in
+    Motion-JPEG writer (said_amd/util/video.py).  Any other extension needs moviepy (and its ffmpeg): when it does not import, the .avi is
+    written beside the requested path and stderr says so, rather than failing after the frames were rendered."""
+    import numpy as np
+    from said_amd.util.video import AviWriter
+    want_avi = output_path.lower().endswith(".avi")
+    mpy = None
+    if not want_avi:
+        try:
+            from moviepy import editor as mpy   # noqa: F401
+        except Exception:
+            mpy = None
+            fallback = os.path.splitext(output_path)[0] + ".avi"
+            print(f"moviepy is not importable: writing Motion-JPEG AVI to {fallback} instead of {output_path}", file=sys.stderr)
+            output_path, want_avi = fallback, True
+    os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
+    index = 0
+    if want_avi:
+        audio = rate = None
+        if audio_path:
+            from scipy.io import wavfile
+            rate, audio = wavfile.read(audio_path)
+            if audio.dtype != np.int16:
+                from said_amd.util.video import pcm16
+                audio = pcm16(audio.astype(np.float64) / (np.iinfo(audio.dtype).max if audio.dtype.kind in "iu" else 1.0))
+        with AviWriter(output_path, fps, width, height, audio=audio, audio_rate=rate) as out:
+            for chunk in frames_iter:
+                for frame in chunk:
+                    out.write(frame)
+                    if on_frame is not None:
+                        on_frame(index, frame)
+                    index += 1
+        return output_path
+    frames = []
+    for chunk in frames_iter:   # moviepy's ImageSequenceClip wants the whole list, R-G-B
+        for frame in chunk:
+            frames.append(frame[..., ::-1].copy())
+            if on_frame is not None:
+                on_frame(index, frame)
+            index += 1
+    audio_clip = mpy.AudioFileClip(audio_path)
+    clip = mpy.ImageSequenceClip(frames, fps=fps).set_audio(audio_clip)
+    clip.write_videofile(output_path, fps=fps, logger=None)
+    audio_clip.close()
+    clip.close()
+    return output_path
