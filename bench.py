@@ -1,6 +1,7 @@
 """bench.py — throughput of the SAiD denoising hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W            (N >= 1: spawns N ranks itself when not under torchrun)
+    python bench.py --gpus 1 --steps K --warmup W --full     (the same run, then everything else the benchmark measures: see --full below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus 2 --dry_run_gloo                  (CPU: launch / shard / gather plumbing only, stand-in path)
     python bench.py --rccl_at_one                             (1 GPU: the RCCL collectives of the sharded run on a one-rank group)
@@ -17,10 +18,13 @@ RCCL all-gather assembles the (N*B, 600, 32) result, inside the timed region.
 above 64 MB a fixed seeded sample of the clips).  The inputs, the eta > 0 noise seed included, are the same in every pass and every
 run with the same arguments, so two builds can be compared output for output.
 
-Prints ONE JSON line (rank 0).  Extra objects:
-  roofline      dominant UNet kernel: algorithmic bytes per launch / HIP-event-timed launch duration
+Prints ONE JSON line (rank 0).  A plain run does what its headline figure needs and nothing else: set-up, warm-up, the timed steps,
+--dump-outputs, the line.  --full measures, after the timed steps and the dump, what takes runs of its own, and attaches it to the line:
+  roofline      dominant UNet kernel: algorithmic bytes per launch / HIP-event-timed launch duration (--no_roofline leaves it out)
+  secondary     the other configurations of BASELINE.json, the strict-fp32 and the eta = 1 form of the headline, each with its own
+                roofline (single-GPU headline run only; --no_secondary leaves them out)
   cpu_baseline  the CPU oracle (a port of the reference path, oracle/) timed on this host's cores on a
-                bounded sample and extrapolated to the same workload
+                bounded sample and extrapolated to the same workload (--no_cpu_baseline leaves it out)
 """
 import argparse
 import json
@@ -71,11 +75,15 @@ def parse():
                         "GEMMs (41 launches per step): -1 (default) = on in bf16 mode, off in fp32 mode; 0 / 1 force it (said_debug_option tm_acts)")
     p.add_argument("--dump-outputs", default=None, metavar="DIR",
                    help="after the timed steps, write the result of the last one as DIR/result.npy (float32; at most 64 MB: a seeded sample of the clips above that)")
-    p.add_argument("--no_cpu_baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps (and --dump-outputs), also measure what takes runs of its own and attach it to the line: the roofline "
+                        "block, the secondary configurations and the CPU baseline (each with a --no_... switch); off by default: a plain run "
+                        "sets up, warms up, times the steps and prints the line")
+    p.add_argument("--no_cpu_baseline", action="store_true", help="with --full: leave the CPU baseline out")
     p.add_argument("--no_secondary", action="store_true",
-                   help="skip the secondary configurations (BASELINE configs[2], [3] per GPU, [4], and the headline with eta = 1) that the "
-                        "default single-GPU headline run measures after the headline and attaches as `secondary`")
-    p.add_argument("--no_roofline", action="store_true")
+                   help="with --full: skip the secondary configurations (BASELINE configs[2], [3] per GPU, [4], and the headline with eta = 1) that "
+                        "the single-GPU headline run measures after the headline and attaches as `secondary`")
+    p.add_argument("--no_roofline", action="store_true", help="with --full: leave the roofline block (and with it the secondary configurations) out")
     p.add_argument("--cpu_steps", type=int, default=40, help="UNet evaluations in the CPU-baseline sample")
     p.add_argument("--rccl_at_one", action="store_true",
                    help="N=1 only: create a ONE-rank 'nccl' (= RCCL) process group and run the sharded run's collectives on it")
@@ -450,7 +458,7 @@ def loop_step_ms(model, proc, lat0, edit_kw, T, num_steps, gs, eta):
     return ev0.elapsed_time(ev1) / n
 
 
-# Secondary configurations measured by the default single-GPU headline run (after the headline; N = 1 only).  Each is
+# Secondary configurations measured by the single-GPU headline run with --full (after the headline; N = 1 only).  Each is
 # `python bench.py <flags>` in its own right; here they run for `passes` timed passes after one short warm-up pass.
 SECONDARY = {
     "cfg2_bf16": dict(batch=32, seconds=10.0, num_steps=50, dtype="bf16", eta=0.0, edit=False, passes=2,
@@ -640,7 +648,7 @@ def run(args):
             line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if args.ab_lib or args.debug_option:
             line["development_build"] = {"ab_lib": args.ab_lib, "debug_option": args.debug_option}   # not the shipped defaults: an A/B run
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             step_ms = loop_step_ms(model, proc, lat0, edit_kw, T, args.num_steps, args.guidance_scale, args.eta)
             headline = (B == 1 and args.seconds == 10.0 and args.num_steps == 1000 and args.dtype == "f32" and not args.edit and args.eta == 0.0)
             key = ("cfg1" if headline else
@@ -663,7 +671,7 @@ def run(args):
                         line[name + "_roofline_bound"] = rf.get("bound")
                         line[name + "_hbm_frac_step"] = (rf.get("unet_step") or {}).get("hbm_frac")
                         line[name + "_mfma_frac_executed_step"] = (rf.get("unet_step") or {}).get("mfma_frac_executed")
-        if not args.no_cpu_baseline and world == 1:   # reported at N=1 only: other ranks would sit in the final barrier
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported at N=1 only: other ranks would sit in the final barrier
             line["cpu_baseline"] = cpu_baseline(args, T, Ta)
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -19,7 +19,7 @@ import bench  # noqa: E402
 import re
 
 # Fallback families (config -> bench.py's name of the dominant kernel family) when no bench line is given; normally the names come
-# from the `roofline.kernel` fields of a bench line measured on the same sources (3rd argument, default
+# from the `roofline.kernel` fields of a `bench.py --full` line measured on the same sources (3rd argument, default
 # gpurun_out/final/bench_default.log): the dominant kernel changes when the schedule does.
 FAMILY = {"cfg1": "ugemm_kernel<NB1,KS8,store>", "cfg2_bf16": "xgemm_kernel<96,bf16,store>",
           "cfg3_per_gpu_f32": "fgemm_kernel<96,store>", "cfg4_edit": "ugemm_kernel<NB2,KS8,store>"}

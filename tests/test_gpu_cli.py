@@ -97,26 +97,53 @@ def test_feature_dim_variant_vs_oracle():
     assert float((out - ref.result).abs().max()) <= 1e-3
 
 
-def test_bench_one_rank_rccl_group():
-    """`bench.py --rccl_at_one`: the sharded run's collectives (all-gather, barriers, max-reduce) on a ONE-rank "nccl" (= RCCL)
-    process group — the only form in which that code path runs on a single-GPU box; one JSON line, finite result, the
-    gathered tensor's checksum equal to the plain single-GPU run's."""
+def _bench_line(extra):
+    """One tiny `bench.py` run in a process of its own: its ONE JSON line."""
     import json
     import subprocess
     import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--num_steps", "5", "--seconds", "1"] + extra,
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
 
-    def run(extra):
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--num_steps", "5", "--seconds", "1",
-                              "--no_cpu_baseline", "--no_roofline"] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
-        assert out.returncode == 0, out.stderr[-2000:]
-        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
-        assert len(lines) == 1
-        return json.loads(lines[0])
 
-    a = run(["--rccl_at_one"])
-    b = run([])
+BENCH_FULL_ONLY = ("roofline", "secondary", "cpu_baseline")   # what bench.py measures in runs of their own: behind --full
+_plain = []
+
+
+def _plain_bench_line():
+    """The plain single-GPU run, started once and shared by the tests below."""
+    if not _plain:
+        _plain.append(_bench_line([]))
+    return _plain[0]
+
+
+def test_bench_one_rank_rccl_group():
+    """`bench.py --rccl_at_one`: the sharded run's collectives (all-gather, barriers, max-reduce) on a ONE-rank "nccl" (= RCCL)
+    process group — the only form in which that code path runs on a single-GPU machine; one JSON line, finite result, the
+    gathered tensor's checksum equal to the plain single-GPU run's.  Both are plain runs: the line carries the headline's keys and
+    nothing that takes a run of its own."""
+    a = _bench_line(["--rccl_at_one"])
+    b = _plain_bench_line()
     assert "one-rank RCCL group" in a["config"]["parallelism"] and b["config"]["parallelism"] == "single GPU"
     assert a["n_gpus"] == 1 and a["config"]["gathered_checksum"] == b["config"]["gathered_checksum"]
+    for line in (a, b):
+        assert not [k for k in line if k.startswith(BENCH_FULL_ONLY)], sorted(line)
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+
+
+def test_bench_full_adds_roofline_and_cpu_baseline():
+    """`bench.py --full`: the plain run's timed steps and result, then the roofline block and the CPU baseline on the line (the secondary
+    configurations belong to the headline shape alone)."""
+    plain = _plain_bench_line()
+    full = _bench_line(["--full", "--cpu_steps", "2"])
+    assert full["roofline"]["kernel"] and full["roofline"]["audio_encode"]["ms_per_clip"] > 0 and full["cpu_baseline"]["value"] > 0
+    assert "secondary" not in full
+    assert full["config"]["gathered_checksum"] == plain["config"]["gathered_checksum"]
+    assert {k for k in full if not k.startswith(BENCH_FULL_ONLY)} == set(plain)
 
 
 def test_gather_uneven_pad_and_trim_on_the_one_rank_rccl_group(tmp_path):

@@ -165,6 +165,16 @@ def test_bench_dump_outputs_samples_clips_above_the_limit(tmp_path):
     assert not (tmp_path / ".gitignore").exists()
 
 
+def test_bench_full_is_an_option_and_off_by_default(monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` is the plain run; what takes runs of its own waits for `--full`."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", sys.argv + ["--full"])
+    a = bench.parse()
+    assert a.full is True and (a.gpus, a.steps, a.warmup) == (1, 3, 1) and not (a.no_roofline or a.no_secondary or a.no_cpu_baseline)
+
+
 # ---------------------------------------------------------------- round 4: the product entry point, uneven shards
 def _item_tensor(i, T):
     g = torch.Generator().manual_seed(1000 + i)      # seeded by the GLOBAL item id, as script/test_inference.py --gpus N seeds a repeat
