@@ -162,7 +162,29 @@ RENDER_EXPORTS = {
     "said_render_read_normals": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
     "said_render_read_colors": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
 }
-_GROUPS = {**LAZY_EXPORTS, "render": ("the renderer", RENDER_EXPORTS)}
+# include/said_unet_train.h: a group like those of LAZY_EXPORTS, kept in a table of its own (tests/test_unet_train_cpu.py checks it against its header)
+_c_ull = ctypes.c_ulonglong
+UNET_TRAIN_EXPORTS = {
+    "said_unet_train_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int]),
+    "said_unet_train_destroy": (c_int, [c_void_p]),
+    "said_unet_train_last_error": (c_char_p, [c_void_p]),
+    "said_unet_train_tensor_name": (c_char_p, [c_int]),
+    "said_unet_train_tensor_numel": (ctypes.c_longlong, [c_int]),
+    "said_unet_train_set_tensor": (c_int, [c_void_p, c_int, c_char_p, _c_float_p, ctypes.c_longlong]),
+    "said_unet_train_get_tensor": (c_int, [c_void_p, c_int, c_char_p, _c_float_p, ctypes.c_longlong]),
+    "said_unet_train_reset_optimizer": (c_int, [c_void_p]),
+    "said_unet_train_copy": (c_int, [c_void_p, c_int, c_int]),
+    "said_unet_train_set_alphas": (c_int, [c_void_p, _c_float_p, c_int]),
+    "said_unet_train_step": (c_int, [c_void_p, c_int, c_int, _c_float_p, _c_float_p, _c_ll_p, POINTER(c_int), c_void_p, c_int, _c_ull, _c_float_p,
+                                     _c_float_p, _c_float_p, c_int]),
+    "said_unet_train_eval_loss": (c_int, [c_void_p, c_int, c_int, _c_float_p, _c_float_p, _c_ll_p, POINTER(c_int), c_void_p, c_int, _c_float_p,
+                                          _c_float_p, _c_float_p, c_int, c_int]),
+    "said_unet_train_forward_only": (c_int, [c_void_p, c_int, c_int, _c_float_p, _c_ll_p, POINTER(c_int), c_void_p, c_int, c_int, _c_float_p]),
+    "said_unet_train_apply_update": (c_int, [c_void_p, _c_float_p]),
+    "said_unet_train_read_losses": (c_int, [c_void_p, c_int, _c_double_p, POINTER(c_int), c_int]),
+    "said_unet_train_last_losses": (c_int, [c_void_p, _c_float_p]),
+}
+_GROUPS = {**LAZY_EXPORTS, "render": ("the renderer", RENDER_EXPORTS), "unet_train": ("the UNet trainer", UNET_TRAIN_EXPORTS)}
 _bound = set()   # the groups bound so far
 
 
@@ -894,6 +916,106 @@ class TrainEngine(_Context):
 
     def graph_count(self) -> int:
         return int(self.lib.said_train_graph_count(self.h))
+
+
+# ---- UNet denoiser trainer (include/said_unet_train.h)
+UT_NSCAL, UT_NACC, UT_NUM_TENSORS = 16, 8, 161   # SAID_UT_*
+(UT_S_LR, UT_S_WD_FACTOR, UT_S_STEP_SIZE, UT_S_BC2_SQRT, UT_S_EMA_OMD, UT_S_WVEL, UT_S_WVERTEX, UT_S_OMB1, UT_S_B2, UT_S_OMB2, UT_S_EPS,
+ UT_S_USE_EMA, UT_S_PRED_TYPE, UT_S_DROPOUT) = range(14)
+UT_STATE, UT_EMA, UT_GRAD, UT_EXP_AVG, UT_EXP_AVG_SQ, UT_STASH = range(6)
+
+
+class UNetTrainEngine(_Context):
+    """said_unet_train context on one GPU (include/said_unet_train.h): the denoiser's parameters, gradients, Adam moments and EMA shadow, and
+    the training step.  Host arrays in and out (numpy); the audio embedding may be a device tensor.  The context keeps its own stream."""
+    prefix, group = "said_unet_train", "unet_train"
+    cpu_error, cpu_message = NoCpuPathError, "said_amd trains the denoiser on MI355X only (device={}); there is no CPU path"
+
+    def __init__(self, device: torch.device, max_batch: int, max_frames: int):
+        super().__init__(device)
+        self._create(int(max_batch), int(max_frames))
+        self.max_batch, self.max_frames = int(max_batch), int(max_frames)
+        self.tensors = [(self.lib.said_unet_train_tensor_name(i).decode(), int(self.lib.said_unet_train_tensor_numel(i)))
+                        for i in range(UT_NUM_TENSORS)]
+
+    def set_tensor(self, which: int, name: str, value) -> None:
+        a = _f32(value).reshape(-1)
+        self._call("said_unet_train_set_tensor", which, name.encode(), a.ctypes.data_as(_c_float_p), a.size)
+
+    def get_tensor(self, which: int, name: str, numel: int) -> np.ndarray:
+        a = np.empty(numel, dtype=np.float32)
+        self._call("said_unet_train_get_tensor", which, name.encode(), a.ctypes.data_as(_c_float_p), numel)
+        return a
+
+    def reset_optimizer(self) -> None:
+        self._call("said_unet_train_reset_optimizer")
+
+    def copy(self, dst: int, src: int) -> None:
+        self._call("said_unet_train_copy", dst, src)
+
+    def set_alphas(self, alphas_cumprod) -> None:
+        a = _f32(alphas_cumprod).reshape(-1)
+        self._call("said_unet_train_set_alphas", a.ctypes.data_as(_c_float_p), a.size)
+
+    def _batch(self, x, timesteps, cond, audio):
+        """(B, T, pointers) of a batch; keeps the converted arrays alive in the returned tuple."""
+        x = _f32(x)
+        B, T = x.shape[0], x.shape[1]
+        ts = np.ascontiguousarray(timesteps, dtype=np.int64).reshape(-1)
+        cd = _i32(np.asarray(cond).astype(np.int32)).reshape(-1)
+        if isinstance(audio, torch.Tensor) and audio.is_cuda:
+            au = _check_dev(audio, "audio_embedding")
+            torch.cuda.current_stream(au.device).synchronize()   # the context copies it on its own stream
+            ap, on_dev = c_void_p(au.data_ptr()), 1
+        else:
+            au = _f32(audio.cpu().numpy() if isinstance(audio, torch.Tensor) else audio)
+            ap, on_dev = au.ctypes.data_as(c_void_p), 0
+        if x.shape != (B, T, 32) or ts.size != B or cd.size != B or tuple(au.shape) != (B, T, 768):
+            raise EngineError(f"batch shapes: x {x.shape}, timesteps {ts.shape}, cond {cd.shape}, audio embedding {tuple(au.shape)}")
+        return B, T, x, ts, cd, au, ap, on_dev
+
+    @staticmethod
+    def _opt(a):
+        return (None, None) if a is None else (lambda v: (v, v.ctypes.data_as(_c_float_p)))(_f32(a))
+
+    def step(self, coeffs, noise, timesteps, cond, audio, dropout_seed: int, scalars, std=None, deltas=None) -> None:
+        B, T, x, ts, cd, au, ap, on_dev = self._batch(coeffs, timesteps, cond, audio)
+        nz, sc = _f32(noise), _f32(scalars)
+        (sd, sdp), (dl, dlp) = self._opt(std), self._opt(deltas)
+        V = 0 if dl is None else dl.shape[-1] // 3
+        self._call("said_unet_train_step", B, T, x.ctypes.data_as(_c_float_p), nz.ctypes.data_as(_c_float_p), ts.ctypes.data_as(_c_ll_p),
+                   cd.ctypes.data_as(POINTER(c_int)), ap, on_dev, _c_ull(int(dropout_seed) & (2 ** 64 - 1)), sc.ctypes.data_as(_c_float_p), sdp, dlp, V)
+
+    def eval_loss(self, coeffs, noise, timesteps, cond, audio, scalars, std=None, deltas=None, ema: bool = False) -> None:
+        B, T, x, ts, cd, au, ap, on_dev = self._batch(coeffs, timesteps, cond, audio)
+        nz, sc = _f32(noise), _f32(scalars)
+        (sd, sdp), (dl, dlp) = self._opt(std), self._opt(deltas)
+        V = 0 if dl is None else dl.shape[-1] // 3
+        self._call("said_unet_train_eval_loss", B, T, x.ctypes.data_as(_c_float_p), nz.ctypes.data_as(_c_float_p), ts.ctypes.data_as(_c_ll_p),
+                   cd.ctypes.data_as(POINTER(c_int)), ap, on_dev, sc.ctypes.data_as(_c_float_p), sdp, dlp, V, int(bool(ema)))
+
+    def forward_only(self, sample, timesteps, cond, audio, ema: bool = False) -> np.ndarray:
+        B, T, x, ts, cd, au, ap, on_dev = self._batch(sample, timesteps, cond, audio)
+        out = np.empty((B, T, 32), dtype=np.float32)
+        self._call("said_unet_train_forward_only", B, T, x.ctypes.data_as(_c_float_p), ts.ctypes.data_as(_c_ll_p), cd.ctypes.data_as(POINTER(c_int)),
+                   ap, on_dev, int(bool(ema)), out.ctypes.data_as(_c_float_p))
+        return out
+
+    def apply_update(self, scalars) -> None:
+        sc = _f32(scalars)
+        self._call("said_unet_train_apply_update", sc.ctypes.data_as(_c_float_p))
+
+    def read_losses(self, val: bool, reset: bool = True):
+        acc = np.zeros(UT_NACC, dtype=np.float64)
+        st = c_int(0)
+        self._call("said_unet_train_read_losses", int(bool(val)), _dp(acc), ctypes.byref(st), int(bool(reset)))
+        return acc, int(st.value)
+
+    def last_losses(self) -> np.ndarray:
+        """predict, velocity, vertex, total, clip factor, gradient norm."""
+        out = np.zeros(6, dtype=np.float32)
+        self._call("said_unet_train_last_losses", out.ctypes.data_as(_c_float_p))
+        return out
 
 
 # ---- renderer (include/said_render.h)

@@ -1,0 +1,749 @@
+// unet_trainer.cpp — the UNet denoiser trainer context (include/said_unet_train.h): the table of trainable tensors, the device copies of the
+// parameters and of the optimizer, the activation arena, and the step: add_noise, forward, objective, backward, clip, AdamW, EMA, launched in that
+// order on the context's stream (unet_train.hip).  T is a run-time value, so nothing is captured into a graph.
+#include "../../include/said_unet_train.h"
+
+#include "engine_internal.h"
+#include "unet_train.h"
+
+using namespace said::ut;
+
+namespace {
+
+struct TDesc { std::string name; long long numel; };
+constexpr int CH = 192, TEd = 768, CTX = 768, FF = 768, NH = 6;
+
+// null_cond_emb, then UNet1DConditionModel.state_dict() under "denoiser.", in the reference's registration order
+std::vector<TDesc> make_table() {
+    std::vector<TDesc> v;
+    auto add = [&](const std::string& n, long long k) { v.push_back({n, k}); };
+    add("null_cond_emb", CTX);
+    const std::string m = "denoiser.model.";
+    add(m + "time_embed.0.weight", TEd * CH); add(m + "time_embed.0.bias", TEd);
+    add(m + "time_embed.2.weight", TEd * TEd); add(m + "time_embed.2.bias", TEd);
+    add(m + "input_blocks.0.0.weight", CH * XC * 3); add(m + "input_blocks.0.0.bias", CH);
+    auto res = [&](const std::string& p, int cin) {
+        add(p + ".in_layers.0.weight", cin); add(p + ".in_layers.0.bias", cin);
+        add(p + ".in_layers.2.weight", (long long)CH * cin * 3); add(p + ".in_layers.2.bias", CH);
+        add(p + ".emb_layers.1.weight", CH * TEd); add(p + ".emb_layers.1.bias", CH);
+        add(p + ".out_layers.0.weight", CH); add(p + ".out_layers.0.bias", CH);
+        add(p + ".out_layers.3.weight", CH * CH * 3); add(p + ".out_layers.3.bias", CH);
+        if (cin != CH) { add(p + ".skip_connection.weight", (long long)CH * cin); add(p + ".skip_connection.bias", CH); }
+    };
+    auto st = [&](const std::string& p) {
+        add(p + ".norm.weight", CH); add(p + ".norm.bias", CH);
+        const std::string b = p + ".transformer_blocks.0";
+        auto attn = [&](int a) {
+            const std::string q = b + ".attn" + std::to_string(a);
+            const int kd = a == 1 ? CH : CTX;
+            add(q + ".to_q.weight", CH * CH); add(q + ".to_k.weight", CH * kd); add(q + ".to_v.weight", CH * kd);
+            add(q + ".to_out.0.weight", CH * CH); add(q + ".to_out.0.bias", CH);
+        };
+        // BasicTransformerBlock registers attn1, ff, attn2, norm1..3 (ldm/attention.py:144-157)
+        attn(1);
+        add(b + ".ff.net.0.proj.weight", 2 * FF * CH); add(b + ".ff.net.0.proj.bias", 2 * FF);
+        add(b + ".ff.net.2.weight", CH * FF); add(b + ".ff.net.2.bias", CH);
+        attn(2);
+        for (int n = 1; n <= 3; ++n) { add(b + ".norm" + std::to_string(n) + ".weight", CH); add(b + ".norm" + std::to_string(n) + ".bias", CH); }
+        add(p + ".proj_out.weight", CH * CH); add(p + ".proj_out.bias", CH);
+    };
+    res(m + "input_blocks.1.0", CH); st(m + "input_blocks.1.1");
+    res(m + "middle_block.0", CH); st(m + "middle_block.1"); res(m + "middle_block.2", CH);
+    res(m + "output_blocks.0.0", 2 * CH); st(m + "output_blocks.0.1");
+    res(m + "output_blocks.1.0", 2 * CH); st(m + "output_blocks.1.1");
+    add(m + "out.0.weight", CH); add(m + "out.0.bias", CH);
+    add(m + "out.2.weight", XC * CH * 3); add(m + "out.2.bias", XC);
+    return v;
+}
+const std::vector<TDesc>& table() {
+    static const std::vector<TDesc> t = make_table();
+    return t;
+}
+const char* kRes[5] = {"denoiser.model.input_blocks.1.0", "denoiser.model.middle_block.0", "denoiser.model.middle_block.2",
+                       "denoiser.model.output_blocks.0.0", "denoiser.model.output_blocks.1.0"};
+const int kResCin[5] = {CH, CH, CH, 2 * CH, 2 * CH};
+const char* kST[4] = {"denoiser.model.input_blocks.1.1", "denoiser.model.middle_block.1", "denoiser.model.output_blocks.0.1",
+                      "denoiser.model.output_blocks.1.1"};
+constexpr int SEG = 8192, MAXKS = 16, VBLK = 256;
+
+// what a ResBlock / SpatialTransformer keeps from the forward
+struct ResAct { const float* x; int ldx; float *xh1, *rs1, *a1, *ee, *c1, *xh2, *rs2, *a2, *out; };
+struct STAct {
+    const float* x;
+    float *xhg, *rsg, *hn, *xh1, *rs1, *y1, *q, *k, *v, *P1, *o1, *x1, *xh2, *rs2, *y2, *q2, *k2, *v2, *P2, *o2, *x2, *xh3, *rs3, *y3, *u, *gg, *x3, *out;
+};
+struct Acts {
+    float *ctx, *noisy, *answer, *temb, *e1, *e1s, *emb, *embs, *h0, *cat0, *cat1, *xho, *rso, *ho, *pred;
+    ResAct r[5];
+    STAct s[4];
+    // backward scratch
+    float *d, *dcat, *dH0, *dH1, *g1, *g2, *g3, *g4, *g5, *big1, *big2, *PB, *dctx, *dee, *dembs, *demb, *de1s, *de1, *R, *dpred, *GV;
+};
+
+}  // namespace
+
+struct said_unet_train {
+    HostCtx c;
+    int maxB = 0, maxT = 0;
+    hipStream_t s = nullptr;
+    long long nparam = 0;
+    std::map<std::string, long long> off;
+    float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr, *E = nullptr, *S = nullptr;   // S: the stash of EMAModel.store
+    long long* seg = nullptr;
+    int nseg = 0;
+    double* part = nullptr;
+    float* clip = nullptr;
+    double* acc = nullptr;    // [2][NACC]
+    float* last = nullptr;    // 4
+    float* rec = nullptr;     // NSCAL + 32
+    float *coeffs = nullptr, *noise = nullptr, *tsf = nullptr, *sasb = nullptr, *audio = nullptr;
+    int *cond = nullptr, *band = nullptr;
+    float* arena = nullptr;
+    size_t arena_n = 0;
+    float* gpart = nullptr;   // K-split partial tiles
+    double* vpart = nullptr;  // vertex partial sums
+    float *D = nullptr, *Ev = nullptr;   // vertex loss: deltas (B, 32, 3V) and E (B T, 3V), grown on demand
+    size_t D_n = 0, Ev_n = 0;
+    std::vector<float> alphas;
+    Acts a;
+};
+
+namespace {
+
+size_t layout(Acts& a, float* base, int B, int T) {
+    size_t pos = 0;
+    const size_t M = (size_t)B * T;
+    auto take = [&](size_t n) { float* p = base ? base + pos : nullptr; pos += (n + 63) / 64 * 64; return p; };
+    a.ctx = take(M * CTX); a.noisy = take(M * XC); a.answer = take(M * XC); a.temb = take((size_t)B * CH); a.e1 = take((size_t)B * TEd);
+    a.e1s = take((size_t)B * TEd); a.emb = take((size_t)B * TEd); a.embs = take((size_t)B * TEd); a.h0 = take(M * CH);
+    a.cat0 = take(M * 2 * CH); a.cat1 = take(M * 2 * CH); a.xho = take(M * CH); a.rso = take((size_t)B * 32); a.ho = take(M * CH); a.pred = take(M * XC);
+    for (int i = 0; i < 5; ++i) {
+        ResAct& r = a.r[i];
+        const size_t ci = kResCin[i];
+        r.xh1 = take(M * ci); r.rs1 = take((size_t)B * 32); r.a1 = take(M * ci); r.ee = take((size_t)B * CH); r.c1 = take(M * CH);
+        r.xh2 = take(M * CH); r.rs2 = take((size_t)B * 32); r.a2 = take(M * CH); r.out = take(M * CH);
+    }
+    for (int i = 0; i < 4; ++i) {
+        STAct& s = a.s[i];
+        float** f[] = {&s.xhg, &s.hn, &s.xh1, &s.y1, &s.q, &s.k, &s.v, &s.o1, &s.x1, &s.xh2, &s.y2, &s.q2, &s.k2, &s.v2, &s.o2, &s.x2, &s.xh3, &s.y3, &s.x3, &s.out};
+        for (float** p : f) *p = take(M * CH);
+        s.rsg = take((size_t)B * 32); s.rs1 = take(M); s.rs2 = take(M); s.rs3 = take(M);
+        s.P1 = take((size_t)B * NH * T * T); s.P2 = take((size_t)B * NH * T * T);
+        s.u = take(M * 2 * FF); s.gg = take(M * FF);
+    }
+    a.d = take(M * CH); a.dcat = take(M * 2 * CH); a.dH0 = take(M * CH); a.dH1 = take(M * CH);
+    a.g1 = take(M * 2 * CH); a.g2 = take(M * 2 * CH); a.g3 = take(M * 2 * CH); a.g4 = take(M * CH); a.g5 = take(M * CH);
+    a.big1 = take(M * FF); a.big2 = take(M * 2 * FF); a.PB = take((size_t)B * NH * T * T); a.dctx = take(M * CTX);
+    a.dee = take((size_t)B * CH); a.dembs = take((size_t)B * TEd); a.demb = take((size_t)B * TEd); a.de1s = take((size_t)B * TEd); a.de1 = take((size_t)B * TEd);
+    a.R = take(M * XC); a.dpred = take(M * XC); a.GV = take(M * XC);
+    return pos;
+}
+
+UOp plain(const float* p, int sr, int sc, long long zb = 0, long long zh = 0) { return UOp{p, zb, zh, 0, 1, 0, sr, sc, 0, 1, 1, 0, 0, 0}; }
+
+struct Gm {
+    said_unet_train* t;
+    UGemm base(UOp A, UOp B, float* C, int ldc, int M, int N, int K) const {
+        UGemm g{};
+        g.A = A; g.B = B; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.Z = 1; g.ZH = 1; g.alpha = 1.f; g.rbT = 1; g.KS = 1; g.kchunk = rup(std::max(K, 1), 16);
+        g.part = t->gpart;
+        return g;
+    }
+    void ksplit(UGemm& g) const {   // the weight gradients: few tiles, long K
+        const int ks = std::min(MAXKS, std::max(1, g.K / 128));
+        g.KS = ks;
+        g.kchunk = rup((g.K + ks - 1) / ks, 16);
+    }
+    // y (M, N) = x (M, K; ldx) W^T (W: N x K) + bias (+ rowb) (+ res)
+    void lin(const float* x, int ldx, const float* W, const float* bias, float* y, int ldy, int M, int N, int K, const float* res = nullptr, int ldr = 0,
+             int accumulate = 0) const {
+        UGemm g = base(plain(x, ldx, 1), plain(W, K, 1), y, ldy, M, N, K);
+        g.bias = bias; g.res = res; g.ldr = ldr; g.accumulate = accumulate;
+        gemm(t->s, g);
+    }
+    // dx (M, K; lddx) (+)= dy (M, N) W
+    void lin_dgrad(const float* dy, const float* W, float* dx, int lddx, int M, int N, int K, int accumulate) const {
+        UGemm g = base(plain(dy, N, 1), plain(W, 1, K), dx, lddx, M, K, N);
+        g.accumulate = accumulate;
+        gemm(t->s, g);
+    }
+    // dW (N, K) = dy^T (rows x N) x (rows x K; ldx); dbias = column sums of dy
+    void lin_wgrad(const float* dy, const float* x, int ldx, float* dW, float* dbias, int rows, int N, int K) const {
+        UGemm g = base(plain(dy, 1, N), plain(x, 1, ldx), dW, K, N, K, rows);
+        ksplit(g);
+        gemm(t->s, g);
+        if (dbias) colsum(t->s, dy, N, nullptr, 0, rows, 1, N, dbias, 0);
+    }
+    // Conv1d(k = 3, padding 1) over (B, T): y (M, Co) = sum_j x[t + j - 1] W[:, :, j]^T
+    void conv(const float* x, int ldx, int Ci, const float* W, const float* bias, float* y, int Co, int B, int T, const float* rowb = nullptr,
+              const float* res = nullptr, int ldr = 0, int accumulate = 0) const {
+        UOp A{x, 0, 0, 0, T, ldx, 0, 1, 0, Ci, 3, 0, -1, 1};
+        UOp Bw{W, 0, 0, 0, 1, 0, Ci * 3, 3, 1, Ci, 3, 0, 0, 0};
+        UGemm g = base(A, Bw, y, Co, B * T, Co, 3 * Ci);
+        g.bias = bias; g.rowb = rowb; g.rbT = T; g.res = res; g.ldr = ldr; g.accumulate = accumulate;
+        gemm(t->s, g);
+    }
+    void conv_dgrad(const float* dy, int Co, const float* W, float* dx, int Ci, int B, int T) const {
+        UOp A{dy, 0, 0, 0, T, Co, 0, 1, 0, Co, 3, 0, 1, -1};
+        UOp Bw{W, 0, 0, 0, 1, 0, 3, Ci * 3, 1, Co, 3, 0, 0, 0};
+        gemm(t->s, base(A, Bw, dx, Ci, B * T, Ci, 3 * Co));
+    }
+    void conv_wgrad(const float* dy, int Co, const float* x, int ldx, int Ci, float* dW, float* dbias, int B, int T) const {
+        UOp Bx{x, 0, 0, 1, T, ldx, 0, 1, 0, Ci, 3, 1, -1, 1};
+        UGemm g = base(plain(dy, 1, Co), Bx, dW, Ci * 3, Co, Ci * 3, B * T);
+        ksplit(g);
+        gemm(t->s, g);
+        colsum(t->s, dy, Co, nullptr, 0, B * T, 1, Co, dbias, 0);
+    }
+    // per (sample, head): C (Mz x Nz) = A B^T with the operands' (row, k) strides; activations (B T, 192) hold head h in columns 32 h ..
+    void heads(UOp A, UOp B, float* C, long long czb, long long czh, int ldc, int Bn, int M, int N, int K) const {
+        UGemm g = base(A, B, C, ldc, M, N, K);
+        g.Z = Bn * NH; g.ZH = NH; g.czb = czb; g.czh = czh;
+        gemm(t->s, g);
+    }
+};
+
+UOp act_rows(const float* p, int T) { return plain(p, CH, 1, (long long)T * CH, 32); }     // (t, d) of head h
+UOp act_cols(const float* p, int T) { return plain(p, 1, CH, (long long)T * CH, 32); }     // (d, t)
+UOp prob_rows(const float* p, int T) { return plain(p, T, 1, (long long)NH * T * T, (long long)T * T); }   // (i, j)
+UOp prob_cols(const float* p, int T) { return plain(p, 1, T, (long long)NH * T * T, (long long)T * T); }   // (j, i)
+
+float* par(said_unet_train* t, const float* base, const std::string& name) { return const_cast<float*>(base) + t->off.at(name); }
+
+// the forward; base = P or E; p: dropout probability (0: none); `noisy` already holds the model input
+void enqueue_forward(said_unet_train* t, int B, int T, const float* base, float p, unsigned long long seed) {
+    hipStream_t s = t->s;
+    Acts& a = t->a;
+    const Gm gm{t};
+    const int M = B * T;
+    auto w = [&](const std::string& n) { return par(t, base, n); };
+    const std::string m = "denoiser.model.";
+    select_ctx(s, B, T, CTX, t->audio, w("null_cond_emb"), t->cond, a.ctx);
+    timestep_embedding(s, B, CH, t->tsf, a.temb);
+    gm.lin(a.temb, CH, w(m + "time_embed.0.weight"), w(m + "time_embed.0.bias"), a.e1, TEd, B, TEd, CH);
+    silu_fwd(s, (long long)B * TEd, a.e1, a.e1s);
+    gm.lin(a.e1s, TEd, w(m + "time_embed.2.weight"), w(m + "time_embed.2.bias"), a.emb, TEd, B, TEd, TEd);
+    silu_fwd(s, (long long)B * TEd, a.emb, a.embs);
+    gm.conv(a.noisy, XC, XC, w(m + "input_blocks.0.0.weight"), w(m + "input_blocks.0.0.bias"), a.h0, CH, B, T);
+
+    auto res = [&](int i, const float* x, int ldx, float* out_override, int ldo) {
+        ResAct& r = a.r[i];
+        const std::string q = kRes[i];
+        const int ci = kResCin[i];
+        r.x = x; r.ldx = ldx;
+        float* out = out_override ? out_override : r.out;
+        const int lo = out_override ? ldo : CH;
+        gn_fwd(s, B, T, ci, x, ldx, w(q + ".in_layers.0.weight"), w(q + ".in_layers.0.bias"), 1e-5f, 1, 0.f, 0, 0, r.xh1, r.rs1, r.a1);
+        gm.lin(a.embs, TEd, w(q + ".emb_layers.1.weight"), w(q + ".emb_layers.1.bias"), r.ee, CH, B, CH, TEd);
+        gm.conv(r.a1, ci, ci, w(q + ".in_layers.2.weight"), w(q + ".in_layers.2.bias"), r.c1, CH, B, T, r.ee);
+        gn_fwd(s, B, T, CH, r.c1, CH, w(q + ".out_layers.0.weight"), w(q + ".out_layers.0.bias"), 1e-5f, 1, p, seed, i, r.xh2, r.rs2, r.a2);
+        if (ci != CH) {
+            gm.lin(x, ldx, w(q + ".skip_connection.weight"), w(q + ".skip_connection.bias"), r.out, CH, M, CH, ci);
+            gm.conv(r.a2, CH, CH, w(q + ".out_layers.3.weight"), w(q + ".out_layers.3.bias"), r.out, CH, B, T, nullptr, nullptr, 0, 1);
+        } else {
+            // the convolution's GEMM epilogue writes element (m, n) at m ldc + n: a strided destination is a copy afterwards
+            gm.conv(r.a2, CH, CH, w(q + ".out_layers.3.weight"), w(q + ".out_layers.3.bias"), r.out, CH, B, T, nullptr, x, ldx, 0);
+        }
+        if (out_override) copy2d(s, M, CH, r.out, CH, out, lo, 0);
+        return r.out;
+    };
+    auto st = [&](int i, const float* x, float* out_override, int ldo) {
+        STAct& z = a.s[i];
+        const std::string q = kST[i], b = q + ".transformer_blocks.0";
+        z.x = x;
+        const float scale = 0.17677669529663687f;   // 32^-0.5
+        gn_fwd(s, B, T, CH, x, CH, w(q + ".norm.weight"), w(q + ".norm.bias"), 1e-6f, 0, 0.f, 0, 0, z.xhg, z.rsg, z.hn);
+        ln_fwd(s, M, z.hn, w(b + ".norm1.weight"), w(b + ".norm1.bias"), z.xh1, z.rs1, z.y1);
+        gm.lin(z.y1, CH, w(b + ".attn1.to_q.weight"), nullptr, z.q, CH, M, CH, CH);
+        gm.lin(z.y1, CH, w(b + ".attn1.to_k.weight"), nullptr, z.k, CH, M, CH, CH);
+        gm.lin(z.y1, CH, w(b + ".attn1.to_v.weight"), nullptr, z.v, CH, M, CH, CH);
+        gm.heads(act_rows(z.q, T), act_rows(z.k, T), z.P1, (long long)NH * T * T, (long long)T * T, T, B, T, T, 32);
+        softmax_fwd(s, (long long)B * NH * T, T, T, scale, nullptr, nullptr, z.P1);
+        gm.heads(prob_rows(z.P1, T), act_cols(z.v, T), z.o1, (long long)T * CH, 32, CH, B, T, 32, T);
+        gm.lin(z.o1, CH, w(b + ".attn1.to_out.0.weight"), w(b + ".attn1.to_out.0.bias"), z.x1, CH, M, CH, CH, z.hn, CH);
+        ln_fwd(s, M, z.x1, w(b + ".norm2.weight"), w(b + ".norm2.bias"), z.xh2, z.rs2, z.y2);
+        gm.lin(z.y2, CH, w(b + ".attn2.to_q.weight"), nullptr, z.q2, CH, M, CH, CH);
+        gm.lin(a.ctx, CTX, w(b + ".attn2.to_k.weight"), nullptr, z.k2, CH, M, CH, CTX);
+        gm.lin(a.ctx, CTX, w(b + ".attn2.to_v.weight"), nullptr, z.v2, CH, M, CH, CTX);
+        gm.heads(act_rows(z.q2, T), act_rows(z.k2, T), z.P2, (long long)NH * T * T, (long long)T * T, T, B, T, T, 32);
+        softmax_fwd(s, (long long)B * NH * T, T, T, scale, t->band, t->band + t->maxT, z.P2);
+        gm.heads(prob_rows(z.P2, T), act_cols(z.v2, T), z.o2, (long long)T * CH, 32, CH, B, T, 32, T);
+        gm.lin(z.o2, CH, w(b + ".attn2.to_out.0.weight"), w(b + ".attn2.to_out.0.bias"), z.x2, CH, M, CH, CH, z.x1, CH);
+        ln_fwd(s, M, z.x2, w(b + ".norm3.weight"), w(b + ".norm3.bias"), z.xh3, z.rs3, z.y3);
+        gm.lin(z.y3, CH, w(b + ".ff.net.0.proj.weight"), w(b + ".ff.net.0.proj.bias"), z.u, 2 * FF, M, 2 * FF, CH);
+        geglu_fwd(s, M, FF, z.u, z.gg);
+        gm.lin(z.gg, FF, w(b + ".ff.net.2.weight"), w(b + ".ff.net.2.bias"), z.x3, CH, M, CH, FF, z.x2, CH);
+        gm.lin(z.x3, CH, w(q + ".proj_out.weight"), w(q + ".proj_out.bias"), z.out, CH, M, CH, CH, x, CH);
+        if (out_override) copy2d(s, M, CH, z.out, CH, out_override, ldo, 0);
+        return z.out;
+    };
+    // torch.cat([h, skip], dim = channels): cat0 = [r3 | s1], cat1 = [s3 | h0]
+    const float* r1 = res(0, a.h0, CH, nullptr, 0);
+    const float* s1 = st(0, r1, a.cat0 + CH, 2 * CH);
+    const float* r2 = res(1, s1, CH, nullptr, 0);
+    const float* s2 = st(1, r2, nullptr, 0);
+    res(2, s2, CH, a.cat0, 2 * CH);
+    copy2d(s, M, CH, a.h0, CH, a.cat1 + CH, 2 * CH, 0);
+    const float* r4 = res(3, a.cat0, 2 * CH, nullptr, 0);
+    st(2, r4, a.cat1, 2 * CH);
+    const float* r5 = res(4, a.cat1, 2 * CH, nullptr, 0);
+    const float* s4 = st(3, r5, nullptr, 0);
+    gn_fwd(s, B, T, CH, s4, CH, w(m + "out.0.weight"), w(m + "out.0.bias"), 1e-5f, 1, 0.f, 0, 0, a.xho, a.rso, a.ho);
+    gm.conv(a.ho, CH, CH, w(m + "out.2.weight"), w(m + "out.2.bias"), a.pred, XC, B, T);
+}
+
+// losses of a.pred against a.answer; with_grad: a.dpred = d total / d pred.  V > 0: the vertex term on t->D
+void enqueue_loss(said_unet_train* t, int B, int T, int V, bool with_grad, double* acc) {
+    hipStream_t s = t->s;
+    Acts& a = t->a;
+    const Gm gm{t};
+    const int M = B * T, n = M * XC, V3 = 3 * V;
+    loss_residual(s, n, a.pred, a.answer, t->rec, a.R);
+    if (V > 0) {
+        // E[b] (T, 3V) = R[b] (T, 32) D[b] (32, 3V); GV[b] = sign(E[b]) D[b]^T
+        UGemm g = gm.base(plain(a.R, XC, 1, (long long)T * XC, 0), plain(t->D, 1, V3, (long long)XC * V3, 0), t->Ev, V3, T, V3, XC);
+        g.Z = B; g.czb = (long long)T * V3;
+        gemm(s, g);
+        vertex_abs(s, (long long)M * V3, t->Ev, t->vpart, VBLK);
+        if (with_grad) {
+            UGemm h = gm.base(plain(t->Ev, V3, 1, (long long)T * V3, 0), plain(t->D, V3, 1, (long long)XC * V3, 0), a.GV, XC, T, XC, V3);
+            h.Z = B; h.czb = (long long)T * XC;
+            gemm(s, h);
+        }
+    }
+    loss_final(s, B, T, a.R, V > 0 ? (with_grad ? a.GV : a.R) : nullptr, t->vpart, VBLK, (long long)M * V3, t->rec, with_grad ? a.dpred : nullptr, t->last, acc);
+}
+
+// the caller has zeroed a.dembs and a.dctx (accumulated into below)
+void enqueue_backward(said_unet_train* t, int B, int T, float p, unsigned long long seed) {
+    hipStream_t s = t->s;
+    Acts& a = t->a;
+    const Gm gm{t};
+    const int M = B * T;
+    const float* P = t->P;
+    auto w = [&](const std::string& n) { return par(t, P, n); };
+    auto gw = [&](const std::string& n) { return par(t, t->G, n); };
+    const std::string m = "denoiser.model.";
+    const float scale = 0.17677669529663687f;
+    // norm gradients: dgamma = sum du xhat, dbeta = sum du over the rows
+    auto norm_grads = [&](const float* du, const float* xh, int C, const std::string& name) {
+        colsum(s, du, C, xh, C, M, 1, C, gw(name + ".weight"), 0);
+        colsum(s, du, C, nullptr, 0, M, 1, C, gw(name + ".bias"), 0);
+    };
+    // ResBlock: dout (M, 192) -> dx (M, cin).  cin = 192: in place in `d`; cin = 384: into a.dcat
+    auto res_bwd = [&](int i, float* d) {
+        ResAct& r = a.r[i];
+        const std::string q = kRes[i];
+        const int ci = kResCin[i];
+        gm.conv_wgrad(d, CH, r.a2, CH, CH, gw(q + ".out_layers.3.weight"), gw(q + ".out_layers.3.bias"), B, T);
+        gm.conv_dgrad(d, CH, w(q + ".out_layers.3.weight"), a.g1, CH, B, T);
+        gn_bwd(s, B, T, CH, a.g1, r.xh2, r.rs2, w(q + ".out_layers.0.weight"), w(q + ".out_layers.0.bias"), 1, p, seed, i, a.g2, a.g3, CH, 0);
+        norm_grads(a.g2, r.xh2, CH, q + ".out_layers.0");
+        // g3 = d c1: the embedding row's gradient is its sum over the sample's frames
+        colsum(s, a.g3, CH, nullptr, 0, T, B, CH, a.dee, 0);
+        gm.lin_wgrad(a.dee, a.embs, TEd, gw(q + ".emb_layers.1.weight"), gw(q + ".emb_layers.1.bias"), B, CH, TEd);
+        gm.lin_dgrad(a.dee, w(q + ".emb_layers.1.weight"), a.dembs, TEd, B, CH, TEd, 1);
+        gm.conv_wgrad(a.g3, CH, r.a1, ci, ci, gw(q + ".in_layers.2.weight"), gw(q + ".in_layers.2.bias"), B, T);
+        gm.conv_dgrad(a.g3, CH, w(q + ".in_layers.2.weight"), a.g1, ci, B, T);
+        float* dx = d;
+        if (ci != CH) {
+            dx = a.dcat;
+            gm.lin_wgrad(d, r.x, r.ldx, gw(q + ".skip_connection.weight"), gw(q + ".skip_connection.bias"), M, CH, ci);
+            gm.lin_dgrad(d, w(q + ".skip_connection.weight"), dx, ci, M, CH, ci, 0);
+        }
+        gn_bwd(s, B, T, ci, a.g1, r.xh1, r.rs1, w(q + ".in_layers.0.weight"), w(q + ".in_layers.0.bias"), 1, 0.f, 0, 0, a.g2, dx, ci, 1);
+        norm_grads(a.g2, r.xh1, ci, q + ".in_layers.0");
+    };
+    // SpatialTransformer, in place in d (M, 192)
+    auto st_bwd = [&](int i, float* d) {
+        STAct& z = a.s[i];
+        const std::string q = kST[i], b = q + ".transformer_blocks.0";
+        gm.lin_wgrad(d, z.x3, CH, gw(q + ".proj_out.weight"), gw(q + ".proj_out.bias"), M, CH, CH);
+        gm.lin_dgrad(d, w(q + ".proj_out.weight"), a.g1, CH, M, CH, CH, 0);                       // g1 = d x3
+        gm.lin_wgrad(a.g1, z.gg, FF, gw(b + ".ff.net.2.weight"), gw(b + ".ff.net.2.bias"), M, CH, FF);
+        gm.lin_dgrad(a.g1, w(b + ".ff.net.2.weight"), a.big1, FF, M, CH, FF, 0);
+        geglu_bwd(s, M, FF, z.u, a.big1, a.big2);
+        gm.lin_wgrad(a.big2, z.y3, CH, gw(b + ".ff.net.0.proj.weight"), gw(b + ".ff.net.0.proj.bias"), M, 2 * FF, CH);
+        gm.lin_dgrad(a.big2, w(b + ".ff.net.0.proj.weight"), a.g2, CH, M, 2 * FF, CH, 0);         // g2 = d y3
+        norm_grads(a.g2, z.xh3, CH, b + ".norm3");
+        ln_bwd(s, M, a.g2, z.xh3, z.rs3, w(b + ".norm3.weight"), a.g1, 1);                        // g1 = d x2
+        // attn2
+        gm.lin_wgrad(a.g1, z.o2, CH, gw(b + ".attn2.to_out.0.weight"), gw(b + ".attn2.to_out.0.bias"), M, CH, CH);
+        gm.lin_dgrad(a.g1, w(b + ".attn2.to_out.0.weight"), a.g2, CH, M, CH, CH, 0);              // g2 = d o2
+        gm.heads(act_rows(a.g2, T), act_rows(z.v2, T), a.PB, (long long)NH * T * T, (long long)T * T, T, B, T, T, 32);   // dP = do v^T
+        gm.heads(prob_cols(z.P2, T), act_cols(a.g2, T), a.g3, (long long)T * CH, 32, CH, B, T, 32, T);                   // dv = P^T do
+        softmax_bwd(s, (long long)B * NH * T, T, scale, z.P2, a.PB);
+        gm.heads(prob_rows(a.PB, T), act_cols(z.k2, T), a.g4, (long long)T * CH, 32, CH, B, T, 32, T);                   // dq = dS k
+        gm.heads(prob_cols(a.PB, T), act_cols(z.q2, T), a.g5, (long long)T * CH, 32, CH, B, T, 32, T);                   // dk = dS^T q
+        gm.lin_wgrad(a.g4, z.y2, CH, gw(b + ".attn2.to_q.weight"), nullptr, M, CH, CH);
+        gm.lin_wgrad(a.g5, a.ctx, CTX, gw(b + ".attn2.to_k.weight"), nullptr, M, CH, CTX);
+        gm.lin_wgrad(a.g3, a.ctx, CTX, gw(b + ".attn2.to_v.weight"), nullptr, M, CH, CTX);
+        gm.lin_dgrad(a.g5, w(b + ".attn2.to_k.weight"), a.dctx, CTX, M, CH, CTX, 1);
+        gm.lin_dgrad(a.g3, w(b + ".attn2.to_v.weight"), a.dctx, CTX, M, CH, CTX, 1);
+        gm.lin_dgrad(a.g4, w(b + ".attn2.to_q.weight"), a.g2, CH, M, CH, CH, 0);                  // g2 = d y2
+        norm_grads(a.g2, z.xh2, CH, b + ".norm2");
+        ln_bwd(s, M, a.g2, z.xh2, z.rs2, w(b + ".norm2.weight"), a.g1, 1);                        // g1 = d x1
+        // attn1
+        gm.lin_wgrad(a.g1, z.o1, CH, gw(b + ".attn1.to_out.0.weight"), gw(b + ".attn1.to_out.0.bias"), M, CH, CH);
+        gm.lin_dgrad(a.g1, w(b + ".attn1.to_out.0.weight"), a.g2, CH, M, CH, CH, 0);
+        gm.heads(act_rows(a.g2, T), act_rows(z.v, T), a.PB, (long long)NH * T * T, (long long)T * T, T, B, T, T, 32);
+        gm.heads(prob_cols(z.P1, T), act_cols(a.g2, T), a.g3, (long long)T * CH, 32, CH, B, T, 32, T);
+        softmax_bwd(s, (long long)B * NH * T, T, scale, z.P1, a.PB);
+        gm.heads(prob_rows(a.PB, T), act_cols(z.k, T), a.g4, (long long)T * CH, 32, CH, B, T, 32, T);
+        gm.heads(prob_cols(a.PB, T), act_cols(z.q, T), a.g5, (long long)T * CH, 32, CH, B, T, 32, T);
+        gm.lin_wgrad(a.g4, z.y1, CH, gw(b + ".attn1.to_q.weight"), nullptr, M, CH, CH);
+        gm.lin_wgrad(a.g5, z.y1, CH, gw(b + ".attn1.to_k.weight"), nullptr, M, CH, CH);
+        gm.lin_wgrad(a.g3, z.y1, CH, gw(b + ".attn1.to_v.weight"), nullptr, M, CH, CH);
+        gm.lin_dgrad(a.g4, w(b + ".attn1.to_q.weight"), a.g2, CH, M, CH, CH, 0);
+        gm.lin_dgrad(a.g5, w(b + ".attn1.to_k.weight"), a.g2, CH, M, CH, CH, 1);
+        gm.lin_dgrad(a.g3, w(b + ".attn1.to_v.weight"), a.g2, CH, M, CH, CH, 1);                  // g2 = d y1
+        norm_grads(a.g2, z.xh1, CH, b + ".norm1");
+        ln_bwd(s, M, a.g2, z.xh1, z.rs1, w(b + ".norm1.weight"), a.g1, 1);                        // g1 = d hn
+        gn_bwd(s, B, T, CH, a.g1, z.xhg, z.rsg, w(q + ".norm.weight"), w(q + ".norm.bias"), 0, 0.f, 0, 0, a.g2, d, CH, 1);
+        norm_grads(a.g2, z.xhg, CH, q + ".norm");
+    };
+
+    gm.conv_wgrad(a.dpred, XC, a.ho, CH, CH, gw(m + "out.2.weight"), gw(m + "out.2.bias"), B, T);
+    gm.conv_dgrad(a.dpred, XC, w(m + "out.2.weight"), a.g1, CH, B, T);
+    gn_bwd(s, B, T, CH, a.g1, a.xho, a.rso, w(m + "out.0.weight"), w(m + "out.0.bias"), 1, 0.f, 0, 0, a.g2, a.d, CH, 0);
+    norm_grads(a.g2, a.xho, CH, m + "out.0");
+    st_bwd(3, a.d);
+    res_bwd(4, a.d);                                           // dcat = d [s3 | h0]
+    copy2d(s, M, CH, a.dcat, 2 * CH, a.d, CH, 0);
+    copy2d(s, M, CH, a.dcat + CH, 2 * CH, a.dH0, CH, 0);
+    st_bwd(2, a.d);
+    res_bwd(3, a.d);                                           // dcat = d [r3 | s1]
+    copy2d(s, M, CH, a.dcat, 2 * CH, a.d, CH, 0);
+    copy2d(s, M, CH, a.dcat + CH, 2 * CH, a.dH1, CH, 0);
+    res_bwd(2, a.d);
+    st_bwd(1, a.d);
+    res_bwd(1, a.d);
+    copy2d(s, M, CH, a.dH1, CH, a.d, CH, 1);
+    st_bwd(0, a.d);
+    res_bwd(0, a.d);
+    copy2d(s, M, CH, a.dH0, CH, a.d, CH, 1);
+    gm.conv_wgrad(a.d, CH, a.noisy, XC, XC, gw(m + "input_blocks.0.0.weight"), gw(m + "input_blocks.0.0.bias"), B, T);
+    // the time embedding MLP
+    silu_bwd(s, (long long)B * TEd, a.emb, a.dembs, a.demb);
+    gm.lin_wgrad(a.demb, a.e1s, TEd, gw(m + "time_embed.2.weight"), gw(m + "time_embed.2.bias"), B, TEd, TEd);
+    gm.lin_dgrad(a.demb, w(m + "time_embed.2.weight"), a.de1s, TEd, B, TEd, TEd, 0);
+    silu_bwd(s, (long long)B * TEd, a.e1, a.de1s, a.de1);
+    gm.lin_wgrad(a.de1, a.temb, CH, gw(m + "time_embed.0.weight"), gw(m + "time_embed.0.bias"), B, TEd, CH);
+    // null_cond_emb: the context gradient summed over the unconditional samples' positions
+    mask_cond_rows(s, B, T, CTX, t->cond, a.dctx);
+    colsum(s, a.dctx, CTX, nullptr, 0, M, 1, CTX, gw("null_cond_emb"), 0);
+}
+
+void enqueue_update(said_unet_train* t) {
+    grad_norm(t->s, t->nseg, t->seg, t->G, t->part, t->clip);
+    adamw_ema(t->s, t->nparam, t->P, t->G, t->M, t->V, t->E, t->clip, t->rec);
+}
+
+int put_record(said_unet_train* t, const float* scalars, const float* std_) {
+    HostCtx* ctx = &t->c;
+    float h[NSCAL + XC] = {};
+    if (scalars) memcpy(h, scalars, sizeof(float) * SAID_UT_NSCAL);
+    h[S_USE_STD] = std_ ? 1.f : 0.f;
+    if (std_) memcpy(h + NSCAL, std_, sizeof(float) * XC);
+    HIPCHK(hipMemcpyAsync(t->rec, h, sizeof h, hipMemcpyHostToDevice, t->s));
+    HIPCHK(hipStreamSynchronize(t->s));   // h is on the stack
+    return 0;
+}
+
+// shape checks and the upload of a batch's inputs; x0 / noise may be null (forward_only passes the sample as x0)
+int put_inputs(said_unet_train* t, const char* what, int B, int T, const float* x0, const float* noise, const long long* ts, const int* cond,
+               const void* audio, int audio_on_device, bool need_alphas) {
+    HostCtx* ctx = &t->c;
+    if (B < 1 || B > t->maxB) return fail(ctx, "%s: batch %d outside [1, %d] (the context's max_batch)", what, B, t->maxB);
+    if (T < 2 || T > t->maxT) return fail(ctx, "%s: %d frames outside [2, %d] (the context's max_frames)", what, T, t->maxT);
+    if (!x0 || !ts || !cond || !audio) return fail(ctx, "%s: null input", what);
+    const size_t n = (size_t)B * T * XC;
+    std::vector<float> tf(B), ab(2 * (size_t)B, 0.f);
+    for (int b = 0; b < B; ++b) {
+        tf[b] = (float)ts[b];
+        if (need_alphas) {
+            if (t->alphas.empty()) return fail(ctx, "%s: no alphas_cumprod set (said_unet_train_set_alphas)", what);
+            if (ts[b] < 0 || ts[b] >= (long long)t->alphas.size()) return fail(ctx, "%s: timestep %lld outside [0, %zu)", what, ts[b], t->alphas.size());
+            const float ac = t->alphas[ts[b]];
+            ab[2 * b] = sqrtf(ac);          // diffusers add_noise / get_velocity: alphas_cumprod ** 0.5, (1 - alphas_cumprod) ** 0.5 in float32
+            ab[2 * b + 1] = sqrtf(1.f - ac);
+        }
+    }
+    // ldm/attention.py:170-189 with Python's banker's round; the context has one position per frame
+    std::vector<int> band(2 * (size_t)t->maxT, 0);
+    const double ratio = 1.0, kh = ratio / 2 + 1;   // context length / frames: the audio embedding has one position per frame
+    for (int i = 0; i < T; ++i) {
+        const double mid = (i + 0.5) * ratio;
+        band[i] = std::max((int)std::nearbyint(mid - kh), 0);
+        band[t->maxT + i] = std::min((int)std::nearbyint(mid + kh), T);
+    }
+    HIPCHK(hipMemcpyAsync(t->coeffs, x0, n * sizeof(float), hipMemcpyHostToDevice, t->s));
+    if (noise) HIPCHK(hipMemcpyAsync(t->noise, noise, n * sizeof(float), hipMemcpyHostToDevice, t->s));
+    HIPCHK(hipMemcpyAsync(t->tsf, tf.data(), B * sizeof(float), hipMemcpyHostToDevice, t->s));
+    HIPCHK(hipMemcpyAsync(t->sasb, ab.data(), 2 * B * sizeof(float), hipMemcpyHostToDevice, t->s));
+    HIPCHK(hipMemcpyAsync(t->cond, cond, B * sizeof(int), hipMemcpyHostToDevice, t->s));
+    HIPCHK(hipMemcpyAsync(t->band, band.data(), band.size() * sizeof(int), hipMemcpyHostToDevice, t->s));
+    HIPCHK(hipMemcpyAsync(t->audio, audio, (size_t)B * T * CTX * sizeof(float), audio_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, t->s));
+    HIPCHK(hipStreamSynchronize(t->s));   // the host vectors above end with this call
+    return 0;
+}
+
+int put_deltas(said_unet_train* t, const char* what, int B, int T, const float* deltas, int V) {
+    HostCtx* ctx = &t->c;
+    if (!deltas) return 0;
+    if (V < 1 || V > 65536) return fail(ctx, "%s: %d vertices outside [1, 65536]", what, V);
+    const size_t dn = (size_t)B * XC * 3 * V, en = (size_t)B * T * 3 * V;
+    if (dn > t->D_n) { if (drealloc(ctx, &t->D, dn, false)) return -1; t->D_n = dn; }
+    if (en > t->Ev_n) { if (drealloc(ctx, &t->Ev, en, false)) return -1; t->Ev_n = en; }
+    HIPCHK(hipMemcpyAsync(t->D, deltas, dn * sizeof(float), hipMemcpyHostToDevice, t->s));
+    HIPCHK(hipStreamSynchronize(t->s));
+    return 0;
+}
+
+int check_std(said_unet_train* t, const float* std_, const char* what) {
+    if (!std_) return 0;
+    for (int c = 0; c < XC; ++c)
+        if (!(std::isfinite(std_[c]) && std_[c] != 0.f)) return fail(&t->c, "%s: std[%d] = %g is not a finite non-zero value", what, c, (double)std_[c]);
+    return 0;
+}
+
+int tindex(const char* name) {
+    if (!name) return -1;
+    const auto& tb = table();
+    for (size_t i = 0; i < tb.size(); ++i)
+        if (tb[i].name == name) return (int)i;
+    return -1;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* said_unet_train_tensor_name(int i) { return (i >= 0 && i < (int)table().size()) ? table()[i].name.c_str() : nullptr; }
+long long said_unet_train_tensor_numel(int i) { return (i >= 0 && i < (int)table().size()) ? table()[i].numel : -1; }
+
+int said_unet_train_create(said_unet_train** out, int device, int max_batch, int max_frames) {
+    if (!out) return fail(nullptr, "said_unet_train_create: out is null");
+    *out = nullptr;
+    DeviceRestore restore_device;
+    if (open_device("said_unet_train_create", device)) return -1;
+    if (max_batch < 1 || max_batch > 256) return fail(nullptr, "said_unet_train_create: max_batch %d outside [1, 256]", max_batch);
+    if (max_frames < 2 || max_frames > 2048) return fail(nullptr, "said_unet_train_create: max_frames %d outside [2, 2048]", max_frames);
+    said_unet_train* t = new said_unet_train();
+    HostCtx* ctx = &t->c;
+    ctx->device = device;
+    t->maxB = max_batch;
+    t->maxT = max_frames;
+    std::vector<long long> seg;
+    const auto& tb = table();
+    for (size_t i = 0; i < tb.size(); ++i) {
+        t->off[tb[i].name] = t->nparam;
+        for (long long s0 = 0; s0 < tb[i].numel; s0 += SEG) seg.insert(seg.end(), {t->nparam + s0, std::min<long long>(SEG, tb[i].numel - s0), (long long)i});
+        t->nparam += tb[i].numel;
+    }
+    t->nseg = (int)seg.size() / 3;
+    Acts tmp;
+    t->arena_n = layout(tmp, nullptr, max_batch, max_frames);
+    const size_t Mx = (size_t)max_batch * max_frames;
+    int rc = 0;
+    rc = rc || hipStreamCreateWithFlags(&t->s, hipStreamNonBlocking) != hipSuccess;
+    rc = rc || dalloc(ctx, &t->P, t->nparam) || dalloc(ctx, &t->G, t->nparam) || dalloc(ctx, &t->M, t->nparam) || dalloc(ctx, &t->V, t->nparam) ||
+         dalloc(ctx, &t->E, t->nparam) || dalloc(ctx, &t->S, t->nparam) || dalloc(ctx, &t->seg, seg.size()) || dalloc(ctx, &t->part, (size_t)t->nseg) || dalloc(ctx, &t->clip, 2) ||
+         dalloc(ctx, &t->acc, (size_t)2 * NACC) || dalloc(ctx, &t->last, 4) || dalloc(ctx, &t->rec, NSCAL + XC) || dalloc(ctx, &t->coeffs, Mx * XC) ||
+         dalloc(ctx, &t->noise, Mx * XC) || dalloc(ctx, &t->tsf, max_batch) || dalloc(ctx, &t->sasb, (size_t)2 * max_batch) ||
+         dalloc(ctx, &t->audio, Mx * CTX) || dalloc(ctx, &t->cond, max_batch) || dalloc(ctx, &t->band, (size_t)2 * max_frames) ||
+         dalloc(ctx, &t->arena, t->arena_n) || dalloc(ctx, &t->gpart, (size_t)MAXKS * TEd * TEd) || dalloc(ctx, &t->vpart, VBLK);
+    if (!rc) rc = hipMemcpy(t->seg, seg.data(), seg.size() * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess;
+    if (rc) {
+        g_create_err = ctx->err.empty() ? std::string("said_unet_train_create: allocation failed") : ctx->err;
+        said_unet_train_destroy(t);
+        return -1;
+    }
+    *out = t;
+    return 0;
+}
+
+int said_unet_train_destroy(said_unet_train* t) {
+    if (!t) return 0;
+    DeviceRestore restore_device;
+    (void)hipSetDevice(t->c.device);
+    if (t->s) (void)hipStreamSynchronize(t->s);
+    free_allocs(&t->c);
+    if (t->s) (void)hipStreamDestroy(t->s);
+    delete t;
+    return 0;
+}
+
+const char* said_unet_train_last_error(const said_unet_train* t) { return t ? t->c.err.c_str() : g_create_err.c_str(); }
+
+static float* copy_of(said_unet_train* t, int which, int i) {
+    float* base[6] = {t->P, t->E, t->G, t->M, t->V, t->S};
+    return (which >= 0 && which < 6) ? base[which] + t->off.at(table()[i].name) : nullptr;
+}
+
+int said_unet_train_set_tensor(said_unet_train* t, int which, const char* name, const float* host, long long n) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    const int i = tindex(name);
+    if (i < 0) return fail(ctx, "said_unet_train_set_tensor: unknown tensor %s", name ? name : "(null)");
+    if (!host || n != table()[i].numel) return fail(ctx, "said_unet_train_set_tensor: %s has %lld elements, got %lld", name, table()[i].numel, n);
+    float* dst = copy_of(t, which, i);
+    if (!dst) return fail(ctx, "said_unet_train_set_tensor: no copy %d", which);
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(dst, host, n * sizeof(float), hipMemcpyHostToDevice, t->s));
+    HIPCHK(hipStreamSynchronize(t->s));
+    return 0;
+}
+
+int said_unet_train_get_tensor(said_unet_train* t, int which, const char* name, float* host, long long n) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    const int i = tindex(name);
+    if (i < 0) return fail(ctx, "said_unet_train_get_tensor: unknown tensor %s", name ? name : "(null)");
+    if (!host || n != table()[i].numel) return fail(ctx, "said_unet_train_get_tensor: %s has %lld elements, got %lld", name, table()[i].numel, n);
+    float* src = copy_of(t, which, i);
+    if (!src) return fail(ctx, "said_unet_train_get_tensor: no copy %d", which);
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(host, src, n * sizeof(float), hipMemcpyDeviceToHost, t->s));
+    HIPCHK(hipStreamSynchronize(t->s));
+    return 0;
+}
+
+int said_unet_train_reset_optimizer(said_unet_train* t) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)t->nparam * sizeof(float);
+    HIPCHK(hipMemsetAsync(t->G, 0, bytes, t->s));
+    HIPCHK(hipMemsetAsync(t->M, 0, bytes, t->s));
+    HIPCHK(hipMemsetAsync(t->V, 0, bytes, t->s));
+    HIPCHK(hipMemcpyAsync(t->E, t->P, bytes, hipMemcpyDeviceToDevice, t->s));
+    HIPCHK(hipStreamSynchronize(t->s));
+    return 0;
+}
+
+int said_unet_train_copy(said_unet_train* t, int dst, int src) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    float* base[6] = {t->P, t->E, t->G, t->M, t->V, t->S};
+    if (dst < 0 || dst >= 6 || src < 0 || src >= 6 || dst == src) return fail(ctx, "said_unet_train_copy: copies %d <- %d", dst, src);
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(base[dst], base[src], (size_t)t->nparam * sizeof(float), hipMemcpyDeviceToDevice, t->s));
+    return 0;
+}
+
+int said_unet_train_set_alphas(said_unet_train* t, const float* ac, int n) {
+    if (!t) return -1;
+    if (!ac || n < 1) return fail(&t->c, "said_unet_train_set_alphas: empty table");
+    t->alphas.assign(ac, ac + n);
+    return 0;
+}
+
+int said_unet_train_step(said_unet_train* t, int B, int T, const float* coeffs, const float* noise, const long long* ts, const int* cond,
+                         const void* audio, int audio_on_device, unsigned long long seed, const float* scalars, const float* std_,
+                         const float* deltas, int V) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    const char* what = "said_unet_train_step";
+    if (!noise || !scalars) return fail(ctx, "%s: null noise or scalars", what);
+    const float p = scalars[SAID_UT_S_DROPOUT];
+    if (!(p >= 0.f && p < 1.f)) return fail(ctx, "%s: dropout probability %g outside [0, 1)", what, (double)p);
+    if (check_std(t, std_, what)) return -1;
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (put_inputs(t, what, B, T, coeffs, noise, ts, cond, audio, audio_on_device, true) || put_deltas(t, what, B, T, deltas, V) ||
+        put_record(t, scalars, std_))
+        return -1;
+    layout(t->a, t->arena, B, T);
+    add_noise(t->s, B, T, t->coeffs, t->noise, t->sasb, t->rec, t->a.noisy, t->a.answer);
+    enqueue_forward(t, B, T, t->P, p, seed);
+    enqueue_loss(t, B, T, deltas ? V : 0, true, t->acc);
+    HIPCHK(hipMemsetAsync(t->a.dembs, 0, (size_t)B * TEd * sizeof(float), t->s));
+    HIPCHK(hipMemsetAsync(t->a.dctx, 0, (size_t)B * T * CTX * sizeof(float), t->s));
+    enqueue_backward(t, B, T, p, seed);
+    enqueue_update(t);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int said_unet_train_eval_loss(said_unet_train* t, int B, int T, const float* coeffs, const float* noise, const long long* ts, const int* cond,
+                              const void* audio, int audio_on_device, const float* scalars, const float* std_, const float* deltas, int V, int ema) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    const char* what = "said_unet_train_eval_loss";
+    if (!noise || !scalars) return fail(ctx, "%s: null noise or scalars", what);
+    if (check_std(t, std_, what)) return -1;
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (put_inputs(t, what, B, T, coeffs, noise, ts, cond, audio, audio_on_device, true) || put_deltas(t, what, B, T, deltas, V) ||
+        put_record(t, scalars, std_))
+        return -1;
+    layout(t->a, t->arena, B, T);
+    add_noise(t->s, B, T, t->coeffs, t->noise, t->sasb, t->rec, t->a.noisy, t->a.answer);
+    enqueue_forward(t, B, T, ema ? t->E : t->P, 0.f, 0);
+    enqueue_loss(t, B, T, deltas ? V : 0, false, t->acc + NACC);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int said_unet_train_forward_only(said_unet_train* t, int B, int T, const float* sample, const long long* ts, const int* cond, const void* audio,
+                                 int audio_on_device, int ema, float* out) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    const char* what = "said_unet_train_forward_only";
+    if (!out) return fail(ctx, "%s: null output", what);
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (put_inputs(t, what, B, T, sample, nullptr, ts, cond, audio, audio_on_device, false)) return -1;
+    layout(t->a, t->arena, B, T);
+    HIPCHK(hipMemcpyAsync(t->a.noisy, t->coeffs, (size_t)B * T * XC * sizeof(float), hipMemcpyDeviceToDevice, t->s));
+    enqueue_forward(t, B, T, ema ? t->E : t->P, 0.f, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, t->a.pred, (size_t)B * T * XC * sizeof(float), hipMemcpyDeviceToHost, t->s));
+    HIPCHK(hipStreamSynchronize(t->s));
+    return 0;
+}
+
+int said_unet_train_apply_update(said_unet_train* t, const float* scalars) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    if (!scalars) return fail(ctx, "said_unet_train_apply_update: null scalars");
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (put_record(t, scalars, nullptr)) return -1;
+    enqueue_update(t);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int said_unet_train_read_losses(said_unet_train* t, int val, double* acc_host, int* status, int reset) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    if (!acc_host) return fail(ctx, "said_unet_train_read_losses: null output");
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    double* a = t->acc + (val ? NACC : 0);
+    HIPCHK(hipMemcpyAsync(acc_host, a, NACC * sizeof(double), hipMemcpyDeviceToHost, t->s));
+    if (reset) HIPCHK(hipMemsetAsync(a, 0, NACC * sizeof(double), t->s));
+    HIPCHK(hipStreamSynchronize(t->s));
+    if (status) *status = acc_host[A_BAD] > 0 ? SAID_UT_NOT_FINITE : SAID_UT_OK;
+    return 0;
+}
+
+int said_unet_train_last_losses(said_unet_train* t, float* out) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    if (!out) return fail(ctx, "said_unet_train_last_losses: null output");
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(out, t->last, 4 * sizeof(float), hipMemcpyDeviceToHost, t->s));
+    HIPCHK(hipMemcpyAsync(out + 4, t->clip, 2 * sizeof(float), hipMemcpyDeviceToHost, t->s));
+    HIPCHK(hipStreamSynchronize(t->s));
+    return 0;
+}
+
+}  // extern "C"
