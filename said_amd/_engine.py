@@ -86,6 +86,7 @@ EXPORTS = {
     "said_debug_ws_info": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(ctypes.c_longlong), POINTER(c_char_p)]),
     "said_debug_ws_fill": (c_int, [c_void_p, c_int]),
     "said_debug_ws_copy": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p]),
+    "said_debug_audio_copy": (c_int, [c_void_p, c_char_p, c_void_p, ctypes.c_longlong, c_void_p]),
     "said_unet_algorithmic_bytes": (c_double, [c_int, c_int, c_int]),
     "said_unet_algorithmic_flops": (c_double, [c_int, c_int]),
     "said_vae_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int]),
@@ -552,6 +553,13 @@ class Engine(_Context):
         out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.index):
             self._call("said_debug_ws_copy", idx, _ptr(out), nbytes, _stream())
+        return out
+
+    def audio_snapshot(self, name: str, nbytes: int) -> torch.Tensor:
+        """Device copy (uint8) of the first `nbytes` bytes of the audio encoder's buffer `name` (said_debug_audio_copy), enqueued on the current stream."""
+        out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.index):
+            self._call("said_debug_audio_copy", name.encode(), _ptr(out), nbytes, _stream())
         return out
 
     def loop_progress(self) -> int:

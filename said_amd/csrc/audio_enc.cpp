@@ -70,10 +70,19 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
         }
         for (int b0 = 0; b0 < B; b0 += chunk) {
             const int nb = std::min(chunk, B - b0);
+            // said_debug_option "audio_stop_after": a stage is one launch call site below, numbered per pass in the order documented in said_hip_debug.h;
+            // on() is asked once per site, whether or not the site launches
+            int stage = 0;
+            auto on = [&]() { return ctx->audio_stop_after < 0 || stage++ < ctx->audio_stop_after; };
+            auto tgemm = [&](const TGemmArgs& a, int batch) {
+                int v = TG_NONE;
+                if (!launch_tgemm(a, batch, s, &v)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
+                else ++ctx->n_tgemm[v];
+            };
             const int pitch0 = rup(L[0], 32);
             const long long bs0 = (long long)W2V_CONV * pitch0;
             // conv0 + GroupNorm + GELU straight to token-major bf16 (abufA, sized for the fp32 activation, serves as its scratch)
-            if (!launch_conv0_gn_gelu_tm_bf16(wav_dev + (long long)b0 * Ta, ctx->c0_w, ctx->c0_g, ctx->c0_b, ctx->abufA, ctx->bA0, nb, Ta, W2V_CONV,
+            if (on() && !launch_conv0_gn_gelu_tm_bf16(wav_dev + (long long)b0 * Ta, ctx->c0_w, ctx->c0_g, ctx->c0_b, ctx->abufA, ctx->bA0, nb, Ta, W2V_CONV,
                                               ctx->w2v_kernel[0], ctx->w2v_stride[0], L[0], 1e-5f, s)) {
                 launch_conv0(wav_dev + (long long)b0 * Ta, ctx->c0_w, ctx->abufA, nb, Ta, W2V_CONV, ctx->w2v_kernel[0], ctx->w2v_stride[0], L[0], pitch0, bs0, s);
                 launch_rownorm_gelu(ctx->abufA, ctx->c0_g, ctx->c0_b, W2V_CONV, nb, L[0], pitch0, bs0, 1e-5f, s);
@@ -88,11 +97,11 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                 a.w = ctx->bw_conv[i]; a.act = 1;
                 a.yb = dst; a.y_bs = (long long)L[i] * W2V_CONV; a.ldy = W2V_CONV;
                 a.M = L[i]; a.N = W2V_CONV; a.K = ctx->w2v_kernel[i] * W2V_CONV;
-                if (!launch_tgemm(a, nb, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
+                if (on()) tgemm(a, nb);
                 std::swap(src, dst);
             }
             // interpolation to the frame count (wav2vec2.py:41-44) + feature_projection.layer_norm
-            launch_interp_ln_tm(src, (long long)L[6] * W2V_CONV, L[6], ctx->bX, (long long)Fr * W2V_CONV, Fr, nb, W2V_CONV, ctx->fp_lng, ctx->fp_lnb, 1e-5f, s);
+            if (on()) launch_interp_ln_tm(src, (long long)L[6] * W2V_CONV, L[6], ctx->bX, (long long)Fr * W2V_CONV, Fr, nb, W2V_CONV, ctx->fp_lng, ctx->fp_lnb, 1e-5f, s);
             const long long hsT = (long long)Fr * W2V_H;            // token-major batch stride
             const long long hs = (long long)W2V_H * Fp;             // channel-major batch stride (positional conv, attention operands)
             const long long tt = (long long)nb * ((Fr + 31) / 32);
@@ -101,7 +110,7 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                 memset(&a, 0, sizeof a);
                 a.a = ctx->bX; a.a_bs = (long long)Fr * W2V_CONV; a.lda = W2V_CONV; a.w = ctx->bw_fproj; a.bias = ctx->fproj.bias;
                 a.yf = ctx->bH; a.y_bs = hsT; a.ldy = W2V_H; a.M = Fr; a.N = W2V_H; a.K = W2V_CONV;
-                if (!launch_tgemm(a, nb, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
+                if (on()) tgemm(a, nb);
             }
             const int PK = ctx->posconv.taps, PG = 16, PCG = W2V_H / PG;
             if (ctx->bw_pos && PK % 2 == 0) {
@@ -110,7 +119,7 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                 // that output token t is row t's 128 x 48 contiguous elements times W_g (tap-major) — 150 GFLOP per 32 clips that
                 // the grouped fp32 kernel ran at 40 TFLOP/s (7.5 of the encoder's 21 ms).  Epilogue: + bias, GELU, + hidden state.
                 const int R = rup(Fr + PK, 8);
-                launch_tm_to_group_bf16(ctx->bH, hsT, ctx->bXg, nb, Fr, PG, PCG, R, PK / 2, s);
+                if (on()) launch_tm_to_group_bf16(ctx->bH, hsT, ctx->bXg, nb, Fr, PG, PCG, R, PK / 2, s);
                 {   // ONE grouped launch (batch axis = (clip, group)): 16 launches of 160 workgroups left 40 % of the CUs idle (16 x 60 us)
                     TGemmArgs a;
                     memset(&a, 0, sizeof a);
@@ -120,12 +129,12 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                     a.yf = ctx->bT; a.y_bs = hsT; a.ldy = W2V_H; a.n_store = PCG;
                     a.grp = PG; a.col_gs = PCG;
                     a.M = Fr; a.N = 64; a.K = PK * PCG;
-                    if (!launch_tgemm(a, nb * PG, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
+                    if (on()) tgemm(a, nb * PG);
                 }
-                launch_ln_tm(ctx->bT, nullptr, ctx->bH, ctx->bHb, ctx->enc_lng, ctx->enc_lnb, (long long)nb * Fr, W2V_H, 1e-5f, s);
+                if (on()) launch_ln_tm(ctx->bT, nullptr, ctx->bH, ctx->bHb, ctx->enc_lng, ctx->enc_lnb, (long long)nb * Fr, W2V_H, 1e-5f, s);
             } else {
             {   // positional conv embedding (grouped, fp32 channel-major kernel) on the projected features
-                launch_tm_to_cm(ctx->bH, ctx->aH, nb, Fr, W2V_H, Fp, hs, s);
+                if (on()) launch_tm_to_cm(ctx->bH, ctx->aH, nb, Fr, W2V_H, Fp, hs, s);
                 GemmArgs a = mkargs(Fr, W2V_H / 16);
                 a.groups = 16; a.ntiles_per_group = 2;
                 a.nseg = 1;
@@ -133,10 +142,12 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                 a.seg[0].c_group_stride = W2V_H / 16;
                 a.bias = ctx->posconv.bias; a.act = ACT_GELU;
                 a.y = ctx->aPOS; a.y_bstride = hs; a.y_pitch = Fp;
-                launch_gemm(a, EPI_STORE, nb, tt * 32 <= 2048 ? 1 : 2, 8, s);
-                launch_cm_to_tm(ctx->aPOS, ctx->bPosT, nb, Fr, W2V_H, Fp, hs, s);
+                if (on()) {
+                    launch_gemm(a, EPI_STORE, nb, tt * 32 <= 2048 ? 1 : 2, 8, s);
+                    launch_cm_to_tm(ctx->aPOS, ctx->bPosT, nb, Fr, W2V_H, Fp, hs, s);
+                }
             }
-            launch_ln_tm(ctx->bH, ctx->bPosT, ctx->bH, ctx->bHb, ctx->enc_lng, ctx->enc_lnb, (long long)nb * Fr, W2V_H, 1e-5f, s);
+            if (on()) launch_ln_tm(ctx->bH, ctx->bPosT, ctx->bH, ctx->bHb, ctx->enc_lng, ctx->enc_lnb, (long long)nb * Fr, W2V_H, 1e-5f, s);
             }
             for (int l = 0; l < ctx->w2v_layers; ++l) {
                 const W2VLayer& ly = ctx->layers[l];
@@ -148,7 +159,7 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                     a.qk = ctx->aQK; a.vt = ctx->aVT; a.v_bs = hs; a.qk_n = 2 * W2V_H; a.head_dim = W2V_HD; a.rows = Fp; a.heads2 = 2 * W2V_HEADS;
                     a.v_pitch = Fp; a.M = Fr; a.N = 3 * W2V_H; a.K = W2V_H;
                     a.sb = 1; a.direct = ctx->tgemm_direct != 0;
-                    if (!launch_tgemm(a, nb, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
+                    if (on()) tgemm(a, nb);
                 }
                 {
                     AttnArgs a;
@@ -159,8 +170,11 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                     if (aks == -4) {   // the key-split-free variant writes the out_proj operand itself: token-major bf16 [clip][frame][768]
                         a.o = reinterpret_cast<float*>(ctx->bO); a.o_bstride = Fr; a.o_mode = 2;
                     }
-                    launch_attn(a, nb, W2V_HD, aks, s, 1);
-                    if (aks != -4) launch_cm_to_tm_bf16(ctx->aO, 2 * hs, Fp, ctx->bO, hsT, nb, Fr, W2V_H, s);
+                    if (on()) {
+                        launch_attn(a, nb, W2V_HD, aks, s, 1);
+                        ++ctx->n_audio_attn[aks == -4];
+                    }
+                    if (on() && aks != -4) launch_cm_to_tm_bf16(ctx->aO, 2 * hs, Fp, ctx->bO, hsT, nb, Fr, W2V_H, s);
                 }
                 {   // out_proj + residual, then layer_norm
                     TGemmArgs a;
@@ -170,16 +184,16 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                     a.res = ctx->bH; a.res_bs = hsT; a.ldr = W2V_H;
                     a.yf = ctx->bT; a.y_bs = hsT; a.ldy = W2V_H; a.M = nb * Fr; a.N = W2V_H; a.K = W2V_H;
                     a.sb = 1; a.direct = ctx->tgemm_direct != 0;
-                    if (!launch_tgemm(a, 1, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
+                    if (on()) tgemm(a, 1);
                 }
-                launch_ln_tm(ctx->bT, nullptr, ctx->bH, ctx->bHb, ly.ln1g, ly.ln1b, (long long)nb * Fr, W2V_H, 1e-5f, s);
+                if (on()) launch_ln_tm(ctx->bT, nullptr, ctx->bH, ctx->bHb, ly.ln1g, ly.ln1b, (long long)nb * Fr, W2V_H, 1e-5f, s);
                 {   // feed_forward.intermediate_dense + GELU
                     TGemmArgs a;
                     memset(&a, 0, sizeof a);
                     a.a = ctx->bHb; a.a_bs = hsT; a.lda = W2V_H; a.w = bl.ff1; a.bias = ly.ff1.bias; a.act = 1;
                     a.yb = ctx->bF; a.y_bs = (long long)Fr * W2V_FFN; a.ldy = W2V_FFN; a.M = nb * Fr; a.N = W2V_FFN; a.K = W2V_H;
                     a.sb = 1; a.direct = ctx->tgemm_direct != 0;
-                    if (!launch_tgemm(a, 1, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
+                    if (on()) tgemm(a, 1);
                 }
                 {   // feed_forward.output_dense + residual, then final_layer_norm
                     TGemmArgs a;
@@ -188,18 +202,18 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                     a.res = ctx->bH; a.res_bs = hsT; a.ldr = W2V_H;
                     a.yf = ctx->bT; a.y_bs = hsT; a.ldy = W2V_H; a.M = nb * Fr; a.N = W2V_H; a.K = W2V_FFN;
                     a.sb = 1; a.direct = ctx->tgemm_direct != 0;
-                    if (!launch_tgemm(a, 1, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
+                    if (on()) tgemm(a, 1);
                 }
                 const bool last = l + 1 == ctx->w2v_layers && !apply_proj;   // the last LayerNorm writes the (B, frames, 768) result itself
-                launch_ln_tm(ctx->bT, nullptr, last ? out_dev + (long long)b0 * Fr * W2V_H : ctx->bH, ctx->bHb, ly.ln2g, ly.ln2b, (long long)nb * Fr, W2V_H, 1e-5f, s);
+                if (on()) launch_ln_tm(ctx->bT, nullptr, last ? out_dev + (long long)b0 * Fr * W2V_H : ctx->bH, ctx->bHb, ly.ln2g, ly.ln2b, (long long)nb * Fr, W2V_H, 1e-5f, s);
             }
             if (apply_proj) {   // diffusion.py:228-229
                 TGemmArgs a;
                 memset(&a, 0, sizeof a);
                 a.a = ctx->bHb; a.a_bs = hsT; a.lda = W2V_H; a.w = ctx->bw_aproj; a.bias = ctx->aproj.bias;
                 a.yf = out_dev + (long long)b0 * Fr * out_dim; a.y_bs = (long long)Fr * out_dim; a.ldy = out_dim; a.M = Fr; a.N = out_dim; a.K = W2V_H;
-                if (!launch_tgemm(a, nb, s)) ctx->launch_err = "audio encoder: token-major GEMM shape not served";
-            } else if (ctx->w2v_layers == 0) {
+                if (on()) tgemm(a, nb);
+            } else if (ctx->w2v_layers == 0 && on()) {
                 HIPCHK(hipMemcpyAsync(out_dev + (long long)b0 * Fr * W2V_H, ctx->bH, (size_t)nb * Fr * W2V_H * sizeof(float), hipMemcpyDeviceToDevice, s));
             }
         }

@@ -643,6 +643,8 @@ int said_debug_option(said_ctx* ctx, const char* name, long long value) {
     } else if (k == "audio_chunk") {
         if (value < 1) return fail(ctx, "audio_chunk must be >= 1");
         ctx->audio_chunk = (int)value;
+    } else if (k == "audio_stop_after") {
+        ctx->audio_stop_after = value < 0 ? -1 : (int)std::min<long long>(value, 1 << 20);
     } else if (k == "steps_per_graph") {
         if (value < 1) return fail(ctx, "steps_per_graph must be >= 1");
         ctx->spg_limit = (int)value;
@@ -692,6 +694,15 @@ long long said_debug_get(const said_ctx* ctx, const char* name) {
     if (k == "n_audio_clips") return (int)ctx->n_audio_clips;
     if (k == "unet_tgemm_min_tokens") return ctx->bf16_mode ? ctx->unet_tgemm_min_tokens : ctx->unet_fgemm_min_tokens;
     if (k == "audio_chunk") return ctx->audio_chunk;
+    if (k == "audio_stop_after") return ctx->audio_stop_after;
+    if (k == "n_tgemm_128") return ctx->n_tgemm[TG_128];
+    if (k == "n_tgemm_128sb") return ctx->n_tgemm[TG_128SB];
+    if (k == "n_tgemm_128x64") return ctx->n_tgemm[TG_128X64];
+    if (k == "n_tgemm_256") return ctx->n_tgemm[TG_256];
+    if (k == "n_tgemm_256x192") return ctx->n_tgemm[TG_256X192];
+    if (k == "n_tgemm_256d") return ctx->n_tgemm[TG_256D];
+    if (k == "n_audio_attn_ks8") return ctx->n_audio_attn[0];
+    if (k == "n_audio_attn_tm") return ctx->n_audio_attn[1];
     if (k == "steps_per_graph") return ctx->spg_limit;
     if (k == "tm_acts") return ctx->tm_acts;
     if (k == "gemm_split") return (!ctx->bf16_mode && sp_on(ctx, ctx->gemm_split)) ? 1 : 0;
@@ -785,6 +796,24 @@ int said_debug_ws_copy(said_ctx* ctx, int idx, void* dst_dev, long long bytes, v
     if (!ctx || idx < 0 || idx >= (int)ctx->ws_allocs.size() || !dst_dev) return -1;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipMemcpyAsync(dst_dev, ctx->ws_allocs[idx], (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+// the audio encoder's lazily sized buffers by name (they are not part of the workspace list): bf16 mode's token-major set and the attention operands it shares with fp32 mode
+int said_debug_audio_copy(said_ctx* ctx, const char* name, void* dst_dev, long long bytes, void* stream) {
+    if (!ctx) return -1;
+    if (!name || !dst_dev || bytes < 0) return fail(ctx, "said_debug_audio_copy: bad arguments");
+    const std::pair<const char*, const void*> t[] = {
+        {"bA0", ctx->bA0}, {"bA1", ctx->bA1}, {"bX", ctx->bX}, {"bXg", ctx->bXg}, {"bH", ctx->bH}, {"bHb", ctx->bHb}, {"bT", ctx->bT}, {"bF", ctx->bF},
+        {"bO", ctx->bO}, {"bPosT", ctx->bPosT}, {"aQK", ctx->aQK}, {"aVT", ctx->aVT}, {"aO", ctx->aO}};
+    const void* p = nullptr;
+    bool known = false;
+    for (const auto& e : t) if (!strcmp(e.first, name)) { known = true; p = e.second; }
+    if (!known) return fail(ctx, "said_debug_audio_copy: unknown buffer %s", name);
+    auto it = p ? ctx->alloc_bytes.find(const_cast<void*>(p)) : ctx->alloc_bytes.end();
+    if (it == ctx->alloc_bytes.end()) return fail(ctx, "said_debug_audio_copy: buffer %s is not allocated", name);
+    if ((size_t)bytes > it->second) return fail(ctx, "said_debug_audio_copy: %lld bytes asked of %s, %zu allocated", bytes, name, it->second);
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(dst_dev, p, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 

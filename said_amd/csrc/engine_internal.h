@@ -211,6 +211,9 @@ struct said_ctx : HostCtx {
     int spg_limit = 50;      // denoise steps captured per graph in loops of >= 400 steps, at most 10 below (steps_per_graph; round 6: 10 -> 50: at 0.245 ms per step the 100 graph boundaries of a 1000-step loop were 0.4-0.5 % of it — headline
                              // 2424-2429 -> 2435-2438 frames/s; 100 / 250 / 500 add nothing: profiles/r06l_steps_per_graph.txt)
     int audio_chunk = 32;    // clips per audio-encoder pass
+    int audio_stop_after = -1;   // bf16 encoder: issue only the first n stages of each pass (said_debug_option "audio_stop_after"; < 0: all) — host side only
+    long long n_tgemm[TG_NVARIANTS] = {0};   // the bf16 encoder's launch_tgemm calls per kernel (tgemm.h TGemmVariant; said_debug_get "n_tgemm_*")
+    long long n_audio_attn[2] = {0, 0};      // ... and its attention launches: [0] eight key slices + cm_to_tm_bf16, [1] no key split, token-major bf16 store
 
     // ---- audio workspace (lazily sized) ----
     float *abufA = nullptr, *abufB = nullptr; size_t abuf_elems[2] = {0, 0};

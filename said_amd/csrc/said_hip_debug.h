@@ -16,6 +16,12 @@ extern "C" {
  *   "unet_tgemm_min_tokens"  tokens per launch from which the UNet takes the token-major GEMM path, both precisions
  *                            (< 0: restore the measured defaults 3000 bf16 / 10000 fp32)
  *   "audio_chunk"            clips per audio-encoder pass (default 32)
+ *   "audio_stop_after"       bf16 mode: n >= 0 makes said_audio_encode issue only the first n stages of each pass and return 0 (the output is then undefined; the buffers hold
+ *                            the intermediates: said_debug_audio_copy); < 0 (default): everything.  Host side only.  A stage is one launch site of the bf16 branch, in order:
+ *                              0 conv0 + GroupNorm + GELU, 1-6 the strided convolutions, 7 interpolation + LayerNorm, 8 feature projection, 9 tm_to_group_bf16,
+ *                              10 positional convolution, 11 encoder LayerNorm; layer l from 12 + 8 l: +0 q/k/v, +1 attention, +2 cm_to_tm_bf16 (a stage of its own also where the
+ *                              key-split-free attention stores token-major itself and nothing is launched), +3 out_proj, +4 LayerNorm, +5 ff1, +6 ff2, +7 final LayerNorm;
+ *                              then audio_proj_layer.  (Without the packed positional weights: 9 tm_to_cm, 10 the grouped fp32 convolution + cm_to_tm, 11 LayerNorm.)
  *   "steps_per_graph"        denoise steps captured per hipGraph in loops of >= 400 steps (default 50; until round 6: 10); shorter loops: min(this, 10)
  *   "tm_acts"                bf16 mode, large batches: token-major bf16 activations between the UNet kernels, GroupNorm / LayerNorm applied inside the consuming
  *                            GEMMs (-1 / 1, default); 0: channel-major fp32 activations with preparation kernels (round 2).  (The fp32 twin of the schedule, measured
@@ -45,7 +51,9 @@ extern "C" {
  *                            two workgroups per CU
  *   "xgemm_clk"              1: shader-clock stamps of the token-major schedule's kernels (-DSAID_CLK_STAMPS builds; read with said_debug_clocks)
  * said_debug_get additionally knows "n_set_weight" (said_set_weight calls so far), "n_stchain" / "n_rgemm" / "n_xgemm" (launches issued through those kernels)
- * and "n_out_sched" / "n_out_sched_tm" / "n_sched_step" (the same for the step's last kernel: out_sched_kernel, out_sched_tm_kernel, sched_step_kernel). */
+ * and "n_out_sched" / "n_out_sched_tm" / "n_sched_step" (the same for the step's last kernel: out_sched_kernel, out_sched_tm_kernel, sched_step_kernel);
+ * of the bf16 audio encoder: "n_tgemm_128" / "n_tgemm_128sb" / "n_tgemm_128x64" / "n_tgemm_256" / "n_tgemm_256x192" / "n_tgemm_256d" (its GEMM launches per kernel: tgemm.h
+ * TGemmVariant) and "n_audio_attn_ks8" / "n_audio_attn_tm" (attention launches with eight key slices / without key split and with the token-major bf16 store). */
 int said_debug_option(said_ctx* ctx, const char* name, long long value);
 long long said_debug_get(const said_ctx* ctx, const char* name);
 /* Stop the UNet schedule after `n_launches` kernel launches, counted from the start of each said_unet_forward / said_denoise_loop call (< 0: run
@@ -68,6 +76,11 @@ int said_debug_ws_count(const said_ctx* ctx);
 int said_debug_ws_info(said_ctx* ctx, int idx, void** ptr_out, long long* bytes_out, const char** name_out);
 int said_debug_ws_fill(said_ctx* ctx, int byte_value);
 int said_debug_ws_copy(said_ctx* ctx, int idx, void* dst_dev, long long bytes, void* stream);
+/* The audio encoder's lazily sized buffers are not in that list.  Enqueues a device-to-device copy of the first `bytes` bytes of the named one — bf16 mode's token-major
+ * buffers "bA0" "bA1" (feature-extractor ping-pong, bf16) "bX" (interpolated + normalised features, bf16) "bXg" (per-group positional-conv operand, bf16) "bH" (hidden state, fp32)
+ * "bHb" (its bf16 copy) "bT" (GEMM results before LayerNorm, fp32) "bF" (feed-forward activation, bf16) "bO" (attention output, bf16) "bPosT", and the attention buffers "aQK"
+ * "aVT" "aO" (fp32) — to `dst_dev` on `stream`.  Fails on an unknown name, a buffer no call has allocated yet, or more bytes than it holds. */
+int said_debug_audio_copy(said_ctx* ctx, const char* name, void* dst_dev, long long bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -110,8 +110,22 @@ struct TGemmArgs {
 };
 int tgemm_geglu_src_row(int n, int N);
 bool tgemm_supports(const TGemmArgs& a);
-// false: shape not served by any instantiation (nothing launched) — the caller reports it through the C ABI
-bool launch_tgemm(const TGemmArgs& a, int batch, hipStream_t s);   // N % 128 == 0: 128-wide tiles, else N % 64 == 0: 64-wide
+// The kernel launch_tgemm picks for a launch: its dispatch as a host function of its own, so that tests can ask which tile a shape takes
+// (said_debug_get "n_tgemm_*" counts the audio encoder's launches per variant)
+enum TGemmVariant {
+    TG_NONE = -1,      // shape not served by any instantiation
+    TG_FGEMM = 0,      // fgemm.hip (fp32 operands; bf16 batch-as-rows)
+    TG_128 = 1,        // tgemm_kernel<128, 128>, double buffer
+    TG_128SB = 2,      // tgemm_kernel<128, 128, true>, single buffer
+    TG_128X64 = 3,     // tgemm_kernel<128, 64> (N % 128 != 0; grouped launches)
+    TG_256 = 4,        // tgemm_kernel<256, 256>
+    TG_256X192 = 5,    // tgemm_kernel<256, 192>
+    TG_256D = 6,       // tgemm256d_kernel
+    TG_NVARIANTS = 7
+};
+int tgemm_variant(const TGemmArgs& a, int batch);
+// false: shape not served by any instantiation (nothing launched) — the caller reports it through the C ABI.  variant (optional): receives tgemm_variant(a, batch)
+bool launch_tgemm(const TGemmArgs& a, int batch, hipStream_t s, int* variant = nullptr);   // N % 128 == 0: 128-wide tiles, else N % 64 == 0: 64-wide
 void configure_tgemm_kernel();
 // fgemm.hip: the fp32 / bf16 batch-as-rows branch of launch_tgemm and configure_tgemm_kernel (internal: callers use those two)
 bool launch_fgemm(const TGemmArgs& a, hipStream_t s);

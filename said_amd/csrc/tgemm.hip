@@ -312,24 +312,23 @@ void configure_tgemm_kernel() {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tgemm_kernel<256, 192>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 192) * TLP * 2);
     configure_fgemm_kernels();
 }
-bool launch_tgemm(const TGemmArgs& a, int batch, hipStream_t s) {
-    if (!tgemm_supports(a)) return false;
-    TGemmArgs a2 = a;
-    a2.batch = batch;
+// Which kernel a launch takes (TGemmVariant, tgemm.h): launch_tgemm switches on this and on nothing else.
+int tgemm_variant(const TGemmArgs& a, int batch) {
+    if (!tgemm_supports(a)) return TG_NONE;
     const long long rows_tot = a.seg_rows > 0 ? (long long)batch * a.seg_rows : a.M;
     const int nb = a.seg_rows > 0 ? 1 : batch;
-    if (a.f32) return launch_fgemm(a2, s);
+    if (a.f32) return TG_FGEMM;
     // bf16, batch-as-rows (UNet): the 64-row K-split tile of the fp32 path on bf16 operands.  The kernels' time is their fp32
     // epilogue traffic, and the 256-row tiles give a 192-wide output 152 workgroups on 256 CUs (42.0 -> 35.8 us on the small tile).
     // For q/k/v and GEGLU (456 / 912 big workgroups) the isolated replays of said_profile_unet favour the big tile (29.8 vs 32.7,
     // 69.7 vs 75.0 us) but the real step does not: 122.1 vs 120.3 ms per 32 clips x 50 steps, three alternating runs on one box
     // (scripts/gpu_r2_ak.sh) — one 147 KB-LDS workgroup per CU starts and drains badly between neighbours of other shapes.  So
     // the small tile is the rule.
-    if (a.seg_rows > 0 && a.K % 64 == 0 && (!a.a2 || a.K1 % 64 == 0) && (a.N % 96 == 0 || a.N % 128 == 0)) return launch_fgemm(a2, s);
-    if (a.grp > 1 && (a.seg_rows > 0 || a.a2 || a.n_store < 1 || a.col_gs < a.n_store)) return false;   // grouped launches: tgemm_kernel only
+    if (a.seg_rows > 0 && a.K % 64 == 0 && (!a.a2 || a.K1 % 64 == 0) && (a.N % 96 == 0 || a.N % 128 == 0)) return TG_FGEMM;
+    if (a.grp > 1 && (a.seg_rows > 0 || a.a2 || a.n_store < 1 || a.col_gs < a.n_store)) return TG_NONE;   // grouped launches: tgemm_kernel only
     const bool big = a.grp <= 1 && (a.N % 256 == 0 || a.N % 192 == 0) && rows_tot * nb >= 4096 &&
                      (rows_tot + 2) * (long long)std::max(a.lda, a.lda2) < 0x7fffffffLL;
-    if (a.geglu && !big) return false;   // the GEGLU epilogue needs the 256-wide tile
+    if (a.geglu && !big) return TG_NONE;   // the GEGLU epilogue needs the 256-wide tile
     // Per-sample operands (audio encoder): a 256-row tile holds one workgroup per CU, so its grid runs in rounds of 256 — the
     // encoder's 768-wide GEMMs at 32 clips x 600 frames are 288 workgroups = two rounds, the second 12 % full.  Where the
     // 128 x 128 tile (two per CU, rounds of 512) fills its rounds clearly better (by a margin of 0.15), it is used instead.
@@ -345,32 +344,47 @@ bool launch_tgemm(const TGemmArgs& a, int batch, hipStream_t s) {
     }
     // round 6: per-sample operands with 256-wide outputs (the audio encoder's projections): the direct-to-LDS 256 x 256 tile (a.direct; said_debug_option "tgemm_direct")
     if (a.direct && a.grp <= 1 && a.seg_rows == 0 && !a.geglu && !a.a2 && a.N % 256 == 0 && a.K % TBK == 0 && (long long)a.M * batch >= 4096 &&
-        ((long long)(a.M - 1) * a.lda + a.K) * 2 < 0x7fffffffLL && (long long)a.N * a.K * 2 < 0x7fffffffLL) {
-        const long long mt8 = ((long long)batch * ((a.M + 255) / 256) + 7) / 8 * 8;
-        hipLaunchKernelGGL(tgemm256d_kernel, dim3((unsigned)(mt8 * (a.N / 256))), dim3(512), TG256D_LDS, s, a2);
-        return true;
-    }
+        ((long long)(a.M - 1) * a.lda + a.K) * 2 < 0x7fffffffLL && (long long)a.N * a.K * 2 < 0x7fffffffLL)
+        return TG_256D;
     if (a.sb && a.seg_rows == 0 && !a.geglu && a.N % 128 == 0) use_big = false;   // the single-buffer 128 x 128 variant was asked for
-    if (use_big) {
-        const long long mt8 = ((long long)nb * ((rows_tot + 255) / 256) + 7) / 8 * 8;
-        if (a.N % 256 == 0) {
-            dim3 grid((unsigned)(mt8 * (a.N / 256)));
-            hipLaunchKernelGGL((tgemm_kernel<256, 256>), grid, dim3(512), 2 * (256 + 256) * TLP * 2, s, a2);
-        } else {
-            dim3 grid((unsigned)(mt8 * (a.N / 192)));
-            hipLaunchKernelGGL((tgemm_kernel<256, 192>), grid, dim3(512), 2 * (256 + 192) * TLP * 2, s, a2);
-        }
-        return true;
-    }
-    if (a.seg_rows > 0) return false;   // batch-as-rows addressing needs the 256-row tile
+    if (use_big) return a.N % 256 == 0 ? TG_256 : TG_256X192;
+    if (a.seg_rows > 0) return TG_NONE;   // batch-as-rows addressing needs the 256-row tile
+    if (a.N % 128 == 0) return a.sb ? TG_128SB : TG_128;
+    return TG_128X64;
+}
+bool launch_tgemm(const TGemmArgs& a, int batch, hipStream_t s, int* variant) {
+    const int v = tgemm_variant(a, batch);
+    if (variant) *variant = v;
+    if (v == TG_NONE) return false;
+    TGemmArgs a2 = a;
+    a2.batch = batch;
+    if (v == TG_FGEMM) return launch_fgemm(a2, s);
+    const long long rows_tot = a.seg_rows > 0 ? (long long)batch * a.seg_rows : a.M;
+    const int nb = a.seg_rows > 0 ? 1 : batch;
+    const long long mt8_256d = ((long long)batch * ((a.M + 255) / 256) + 7) / 8 * 8;
+    const long long mt8_big = ((long long)nb * ((rows_tot + 255) / 256) + 7) / 8 * 8;
     const long long mtiles8 = ((long long)batch * ((a.M + TBM - 1) / TBM) + 7) / 8 * 8;   // (sample, M tile) pairs padded to the 8 XCDs
-    if (a.N % 128 == 0) {
-        dim3 grid((unsigned)(mtiles8 * (a.N / 128)));
-        if (a.sb) hipLaunchKernelGGL((tgemm_kernel<128, 128, true>), grid, dim3(256), (TBM + 128) * TLP * 2, s, a2);
-        else hipLaunchKernelGGL((tgemm_kernel<128, 128>), grid, dim3(256), 2 * (TBM + 128) * TLP * 2, s, a2);
-    } else {
-        dim3 grid((unsigned)(mtiles8 * (a.N / 64)));
-        hipLaunchKernelGGL((tgemm_kernel<128, 64>), grid, dim3(256), 2 * (TBM + 64) * TLP * 2, s, a2);
+    switch (v) {
+    case TG_256D:
+        hipLaunchKernelGGL(tgemm256d_kernel, dim3((unsigned)(mt8_256d * (a.N / 256))), dim3(512), TG256D_LDS, s, a2);
+        break;
+    case TG_256:
+        hipLaunchKernelGGL((tgemm_kernel<256, 256>), dim3((unsigned)(mt8_big * (a.N / 256))), dim3(512), 2 * (256 + 256) * TLP * 2, s, a2);
+        break;
+    case TG_256X192:
+        hipLaunchKernelGGL((tgemm_kernel<256, 192>), dim3((unsigned)(mt8_big * (a.N / 192))), dim3(512), 2 * (256 + 192) * TLP * 2, s, a2);
+        break;
+    case TG_128SB:
+        hipLaunchKernelGGL((tgemm_kernel<128, 128, true>), dim3((unsigned)(mtiles8 * (a.N / 128))), dim3(256), (TBM + 128) * TLP * 2, s, a2);
+        break;
+    case TG_128:
+        hipLaunchKernelGGL((tgemm_kernel<128, 128>), dim3((unsigned)(mtiles8 * (a.N / 128))), dim3(256), 2 * (TBM + 128) * TLP * 2, s, a2);
+        break;
+    case TG_128X64:
+        hipLaunchKernelGGL((tgemm_kernel<128, 64>), dim3((unsigned)(mtiles8 * (a.N / 64))), dim3(256), 2 * (TBM + 64) * TLP * 2, s, a2);
+        break;
+    default:
+        return false;
     }
     return true;
 }

@@ -54,7 +54,7 @@ def test_every_header_matches_its_binding_table():
         assert set(decl) == set(table), (headers, set(decl) ^ set(table))
         declared.update(decl)
         bound.update(table)
-    assert set(declared) == set(bound) and len(declared) == 83
+    assert set(declared) == set(bound) and len(declared) == 84
     for name, nparams in declared.items():
         assert hasattr(lib, name), f"{name} is declared but not exported"
         assert len(bound[name][1]) == nparams, f"{name}: {nparams} parameters declared, {len(bound[name][1])} argtypes bound"
