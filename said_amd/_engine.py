@@ -852,10 +852,48 @@ def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
-class TrainEngine(_Context):
+class _TrainContext(_Context):
+    """What the two trainer contexts bind alike (<prefix>_set_tensor, _get_tensor, _reset_optimizer, _apply_update, _read_losses,
+    _last_losses); a subclass names how many values its _last_losses gives and the pointer type its tensor entries are bound with."""
+    n_last, _tensor_ptr = 0, _c_float_p
+
+    @staticmethod
+    def _dtype(name: str):
+        """The element type of tensor `name` on the host."""
+        return np.float32
+
+    def set_tensor(self, which: int, name: str, value) -> None:
+        a = np.ascontiguousarray(value, dtype=self._dtype(name)).reshape(-1)
+        self._call(self.prefix + "_set_tensor", which, name.encode(), a.ctypes.data_as(self._tensor_ptr), a.size)
+
+    def get_tensor(self, which: int, name: str, numel: int) -> np.ndarray:
+        a = np.empty(numel, dtype=self._dtype(name))
+        self._call(self.prefix + "_get_tensor", which, name.encode(), a.ctypes.data_as(self._tensor_ptr), numel)
+        return a
+
+    def reset_optimizer(self) -> None:
+        self._call(self.prefix + "_reset_optimizer")
+
+    def apply_update(self, scalars: np.ndarray) -> None:
+        sc = _f32(scalars)
+        self._call(self.prefix + "_apply_update", sc.ctypes.data_as(_c_float_p))
+
+    def read_losses(self, val: bool, reset: bool = True):
+        acc = np.zeros(TRAIN_NACC, dtype=np.float64)   # SAID_UT_NACC is the same
+        st = c_int(0)
+        self._call(self.prefix + "_read_losses", int(bool(val)), _dp(acc), ctypes.byref(st), int(bool(reset)))
+        return acc, int(st.value)
+
+    def last_losses(self) -> np.ndarray:
+        out = np.zeros(self.n_last, dtype=np.float32)
+        self._call(self.prefix + "_last_losses", out.ctypes.data_as(_c_float_p))
+        return out
+
+
+class TrainEngine(_TrainContext):
     """said_train context on one GPU (include/said_train.h): the BCVAE's parameters, buffers, gradients, Adam moments and EMA shadow, the
     window sets, and the captured training step.  Host arrays in and out (numpy); the context keeps its own stream."""
-    prefix, group = "said_train", "train"
+    prefix, group, n_last = "said_train", "train", 4   # last_losses: reconst, regularize, velocity, total
     cpu_error, cpu_message = NoCpuPathError, "said_amd trains the BCVAE on MI355X only (device={}); there is no CPU path"
 
     def __init__(self, device: torch.device, max_batch: int):
@@ -865,17 +903,11 @@ class TrainEngine(_Context):
         self.tensors = [(self.lib.said_train_tensor_name(i).decode(), int(self.lib.said_train_tensor_numel(i)),
                          bool(self.lib.said_train_tensor_is_counter(i))) for i in range(70)]
 
-    def set_tensor(self, which: int, name: str, value) -> None:
-        a = np.ascontiguousarray(value, dtype=np.int64 if name.endswith("num_batches_tracked") else np.float32).reshape(-1)
-        self._call("said_train_set_tensor", which, name.encode(), a.ctypes.data_as(c_void_p), a.size)
+    _tensor_ptr = c_void_p   # float32, or the int64 of a num_batches_tracked
 
-    def get_tensor(self, which: int, name: str, numel: int) -> np.ndarray:
-        a = np.empty(numel, dtype=np.int64 if name.endswith("num_batches_tracked") else np.float32)
-        self._call("said_train_get_tensor", which, name.encode(), a.ctypes.data_as(c_void_p), numel)
-        return a
-
-    def reset_optimizer(self) -> None:
-        self._call("said_train_reset_optimizer")
+    @staticmethod
+    def _dtype(name: str):
+        return np.int64 if name.endswith("num_batches_tracked") else np.float32
 
     def set_data(self, which_set: int, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, mirror: np.ndarray) -> None:
         fr, off, ln, mi = _f32(frames), np.ascontiguousarray(offsets, dtype=np.int64), _i32(lengths), _i32(mirror)
@@ -897,25 +929,10 @@ class TrainEngine(_Context):
         self._call("said_train_step", it.shape[0], it.ctypes.data_as(POINTER(c_int)), ep.ctypes.data_as(_c_float_p),
                    sc.ctypes.data_as(_c_float_p), None if sd is None else sd.ctypes.data_as(_c_float_p), int(bool(use_graph)))
 
-    def apply_update(self, scalars: np.ndarray) -> None:
-        sc = _f32(scalars)
-        self._call("said_train_apply_update", sc.ctypes.data_as(_c_float_p))
-
     def eval_loss(self, which_set: int, items: np.ndarray, eps: np.ndarray, scalars: np.ndarray, std: Optional[np.ndarray], ema: bool) -> None:
         it, ep, sc, sd = _i32(items), _f32(eps), _f32(scalars), self._opt_f32(std)
         self._call("said_train_eval_loss", which_set, it.shape[0], it.ctypes.data_as(POINTER(c_int)), ep.ctypes.data_as(_c_float_p),
                    sc.ctypes.data_as(_c_float_p), None if sd is None else sd.ctypes.data_as(_c_float_p), int(bool(ema)))
-
-    def read_losses(self, val: bool, reset: bool = True):
-        acc = np.zeros(TRAIN_NACC, dtype=np.float64)
-        st = c_int(0)
-        self._call("said_train_read_losses", int(bool(val)), _dp(acc), ctypes.byref(st), int(bool(reset)))
-        return acc, int(st.value)
-
-    def last_losses(self) -> np.ndarray:
-        out = np.zeros(4, dtype=np.float32)
-        self._call("said_train_last_losses", out.ctypes.data_as(_c_float_p))
-        return out
 
     def bn_stats(self, bn: int, channels: int) -> np.ndarray:
         out = np.zeros(2 * channels, dtype=np.float32)
@@ -933,10 +950,10 @@ UT_NSCAL, UT_NACC, UT_NUM_TENSORS = 16, 8, 161   # SAID_UT_*
 UT_STATE, UT_EMA, UT_GRAD, UT_EXP_AVG, UT_EXP_AVG_SQ, UT_STASH = range(6)
 
 
-class UNetTrainEngine(_Context):
+class UNetTrainEngine(_TrainContext):
     """said_unet_train context on one GPU (include/said_unet_train.h): the denoiser's parameters, gradients, Adam moments and EMA shadow, and
     the training step.  Host arrays in and out (numpy); the audio embedding may be a device tensor.  The context keeps its own stream."""
-    prefix, group = "said_unet_train", "unet_train"
+    prefix, group, n_last = "said_unet_train", "unet_train", 6   # last_losses: predict, velocity, vertex, total, clip factor, gradient norm
     cpu_error, cpu_message = NoCpuPathError, "said_amd trains the denoiser on MI355X only (device={}); there is no CPU path"
 
     def __init__(self, device: torch.device, max_batch: int, max_frames: int):
@@ -945,18 +962,6 @@ class UNetTrainEngine(_Context):
         self.max_batch, self.max_frames = int(max_batch), int(max_frames)
         self.tensors = [(self.lib.said_unet_train_tensor_name(i).decode(), int(self.lib.said_unet_train_tensor_numel(i)))
                         for i in range(UT_NUM_TENSORS)]
-
-    def set_tensor(self, which: int, name: str, value) -> None:
-        a = _f32(value).reshape(-1)
-        self._call("said_unet_train_set_tensor", which, name.encode(), a.ctypes.data_as(_c_float_p), a.size)
-
-    def get_tensor(self, which: int, name: str, numel: int) -> np.ndarray:
-        a = np.empty(numel, dtype=np.float32)
-        self._call("said_unet_train_get_tensor", which, name.encode(), a.ctypes.data_as(_c_float_p), numel)
-        return a
-
-    def reset_optimizer(self) -> None:
-        self._call("said_unet_train_reset_optimizer")
 
     def copy(self, dst: int, src: int) -> None:
         self._call("said_unet_train_copy", dst, src)
@@ -1009,21 +1014,6 @@ class UNetTrainEngine(_Context):
                    ap, on_dev, int(bool(ema)), out.ctypes.data_as(_c_float_p))
         return out
 
-    def apply_update(self, scalars) -> None:
-        sc = _f32(scalars)
-        self._call("said_unet_train_apply_update", sc.ctypes.data_as(_c_float_p))
-
-    def read_losses(self, val: bool, reset: bool = True):
-        acc = np.zeros(UT_NACC, dtype=np.float64)
-        st = c_int(0)
-        self._call("said_unet_train_read_losses", int(bool(val)), _dp(acc), ctypes.byref(st), int(bool(reset)))
-        return acc, int(st.value)
-
-    def last_losses(self) -> np.ndarray:
-        """predict, velocity, vertex, total, clip factor, gradient norm."""
-        out = np.zeros(6, dtype=np.float32)
-        self._call("said_unet_train_last_losses", out.ctypes.data_as(_c_float_p))
-        return out
 
 
 # ---- renderer (include/said_render.h)

@@ -84,8 +84,6 @@ void vertex_abs(hipStream_t s, long long n, float* E, double* part, int nblk);
 // losses and d total / d pred; GV (nullable) = sign(E) D^T; part / nblk / nvert the vertex partial sums and element count
 void loss_final(hipStream_t s, int B, int T, const float* R, const float* GV, const double* part, int nblk, long long nvert, const float* rec,
                 float* dpred, float* last, double* acc);
-void grad_norm(hipStream_t s, int nseg, const long long* seg, const float* G, double* part, float* clip);
-void adamw_ema(hipStream_t s, long long n, float* P, const float* G, float* M, float* V, float* E, const float* clip, const float* rec);
 
 }  // namespace ut
 }  // namespace said

@@ -1,6 +1,6 @@
 // unet_train.hip — the kernels of the UNet denoiser's training step (said/model/unet_1d_condition.py, script/train.py): a training-mode forward
-// that keeps what the backward needs, the backward of every layer, the objective of random_noise_loss and its gradient, the global gradient-norm
-// clip, AdamW and the EMA shadow.  fp32 throughout; activations are token-major (B T, C).
+// that keeps what the backward needs, the backward of every layer, the objective of random_noise_loss and its gradient.  fp32 throughout;
+// activations are token-major (B T, C).  The update that follows (clip, AdamW, EMA) is train_opt.hip.
 //
 // Matrix products (linear layers, the k = 3 / k = 1 convolutions as shifted-operand GEMMs, the attention products) all run on ONE kernel,
 // gemm_kernel, on v_mfma_f32_32x32x2_f32.  Reduction orders: a GEMM element is summed over k in ascending 16-wide tiles, each tile in ascending
@@ -11,34 +11,16 @@
 #include <math.h>
 
 #include "sched_math.h"
+#include "train_dev.h"
 
 namespace said {
 namespace ut {
 namespace {
 
-constexpr int NT = 256;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
-}
-template <typename F>
-__device__ __forceinline__ F block_sum(F v, F* sh) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    sh[t] = v;
-    __syncthreads();
-    for (int w = NT / 2; w >= 1; w >>= 1) {
-        if (t < w) sh[t] = sh[t] + sh[t + w];
-        __syncthreads();
-    }
-    return sh[0];
 }
 
 // ---------------------------------------------------------------------------------------------------------------- GEMM
@@ -456,57 +438,6 @@ __global__ void __launch_bounds__(NT) loss_final_kernel(int B, int T, const floa
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------- clip, AdamW, EMA
-// the formulas of vae_train.hip (torch.nn.utils.clip_grad_norm_, torch.optim.AdamW single-tensor form, diffusers EMAModel.step), restated
-__global__ void __launch_bounds__(NT) grad_sq_kernel(const long long* __restrict__ seg, const float* __restrict__ G, double* __restrict__ part) {
-    __shared__ double sh[NT];
-    const long long st = seg[3 * blockIdx.x], n = seg[3 * blockIdx.x + 1];
-    double q = 0.0;
-    for (long long i = threadIdx.x; i < n; i += NT) {
-        const double g = G[st + i];
-        q += g * g;
-    }
-    q = block_sum(q, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = q;
-}
-__global__ void __launch_bounds__(64) clip_kernel(int nseg, const long long* __restrict__ seg, const double* __restrict__ part, float* __restrict__ clip) {
-    if (threadIdx.x != 0) return;
-    double tot = 0.0, cur = 0.0;
-    for (int s = 0; s < nseg; ++s) {
-        cur += part[s];
-        if (s + 1 == nseg || seg[3 * (s + 1) + 2] != seg[3 * s + 2]) {
-            const float nt = (float)sqrt(cur);
-            tot += (double)nt * (double)nt;
-            cur = 0.0;
-        }
-    }
-    const float total = (float)sqrt(tot);
-    const float f = 1.f / (total + 1e-6f);
-    clip[0] = f < 1.f ? f : 1.f;
-    clip[1] = total;
-}
-__global__ void __launch_bounds__(NT) adamw_ema_kernel(long long n, float* __restrict__ P, const float* __restrict__ G, float* __restrict__ M,
-                                                       float* __restrict__ V, float* __restrict__ E, const float* __restrict__ clip,
-                                                       const float* __restrict__ rec) {
-    const float cf = clip[0], wdf = rec[S_WD_FACTOR], ss = rec[S_STEP_SIZE], bc2 = rec[S_BC2_SQRT], omb1 = rec[S_OMB1], b2 = rec[S_B2],
-                omb2 = rec[S_OMB2], eps = rec[S_EPS], omd = rec[S_EMA_OMD];
-    const bool ema = rec[S_USE_EMA] != 0.f;
-    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n; i += (long long)gridDim.x * NT) {
-        const float g = G[i] * cf;
-        float p = P[i] * wdf;
-        const float m = M[i] + omb1 * (g - M[i]);
-        const float v = V[i] * b2 + (omb2 * g) * g;
-        const float den = sqrtf(v) / bc2 + eps;
-        p = p + (-ss) * (m / den);
-        P[i] = p;
-        M[i] = m;
-        V[i] = v;
-        if (ema) E[i] = E[i] - omd * (E[i] - p);
-    }
-}
-
-inline int nblk(long long n, int per = NT) { return (int)((n + per - 1) / per); }
-
 }  // namespace
 
 void gemm(hipStream_t s, const UGemm& g) {
@@ -567,13 +498,6 @@ void vertex_abs(hipStream_t s, long long n, float* E, double* part, int nb) { ve
 void loss_final(hipStream_t s, int B, int T, const float* R, const float* GV, const double* part, int nb, long long nvert, const float* rec,
                 float* dpred, float* last, double* acc) {
     loss_final_kernel<<<1, NT, 0, s>>>(B, T, R, GV, part, nb, nvert, rec, dpred, last, acc);
-}
-void grad_norm(hipStream_t s, int nseg, const long long* seg, const float* G, double* part, float* clip) {
-    grad_sq_kernel<<<nseg, NT, 0, s>>>(seg, G, part);
-    clip_kernel<<<1, 64, 0, s>>>(nseg, seg, part, clip);
-}
-void adamw_ema(hipStream_t s, long long n, float* P, const float* G, float* M, float* V, float* E, const float* clip, const float* rec) {
-    adamw_ema_kernel<<<std::min(nblk(n), 1024), NT, 0, s>>>(n, P, G, M, V, E, clip, rec);
 }
 
 }  // namespace ut

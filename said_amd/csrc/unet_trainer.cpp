@@ -4,9 +4,13 @@
 #include "../../include/said_unet_train.h"
 
 #include "engine_internal.h"
+#include "train_store.h"
 #include "unet_train.h"
 
 using namespace said::ut;
+
+static_assert(OPT_SLOTS_MATCH(SAID_UT_S_), "said_unet_train.h and train_opt.h disagree on the optimizer's slots of the step record");
+static_assert(NACC == TS_NACC && A_BAD == TS_A_BAD && SAID_UT_NOT_FINITE == 1, "train_store.h reads the accumulators of unet_train.h");
 
 namespace {
 
@@ -64,7 +68,7 @@ const char* kRes[5] = {"denoiser.model.input_blocks.1.0", "denoiser.model.middle
 const int kResCin[5] = {CH, CH, CH, 2 * CH, 2 * CH};
 const char* kST[4] = {"denoiser.model.input_blocks.1.1", "denoiser.model.middle_block.1", "denoiser.model.output_blocks.0.1",
                       "denoiser.model.output_blocks.1.1"};
-constexpr int SEG = 8192, MAXKS = 16, VBLK = 256;
+constexpr int MAXKS = 16, VBLK = 256;
 
 // what a ResBlock / SpatialTransformer keeps from the forward
 struct ResAct { const float* x; int ldx; float *xh1, *rs1, *a1, *ee, *c1, *xh2, *rs2, *a2, *out; };
@@ -86,15 +90,8 @@ struct said_unet_train {
     HostCtx c;
     int maxB = 0, maxT = 0;
     hipStream_t s = nullptr;
-    long long nparam = 0;
+    TrainStore st;            // the parameters (with the stash of EMAModel.store) and the optimizer's state
     std::map<std::string, long long> off;
-    float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr, *E = nullptr, *S = nullptr;   // S: the stash of EMAModel.store
-    long long* seg = nullptr;
-    int nseg = 0;
-    double* part = nullptr;
-    float* clip = nullptr;
-    double* acc = nullptr;    // [2][NACC]
-    float* last = nullptr;    // 4
     float* rec = nullptr;     // NSCAL + 32
     float *coeffs = nullptr, *noise = nullptr, *tsf = nullptr, *sasb = nullptr, *audio = nullptr;
     int *cond = nullptr, *band = nullptr;
@@ -311,7 +308,7 @@ void enqueue_loss(said_unet_train* t, int B, int T, int V, bool with_grad, doubl
             gemm(s, h);
         }
     }
-    loss_final(s, B, T, a.R, V > 0 ? (with_grad ? a.GV : a.R) : nullptr, t->vpart, VBLK, (long long)M * V3, t->rec, with_grad ? a.dpred : nullptr, t->last, acc);
+    loss_final(s, B, T, a.R, V > 0 ? (with_grad ? a.GV : a.R) : nullptr, t->vpart, VBLK, (long long)M * V3, t->rec, with_grad ? a.dpred : nullptr, t->st.last, acc);
 }
 
 // the caller has zeroed a.dembs and a.dctx (accumulated into below)
@@ -320,9 +317,9 @@ void enqueue_backward(said_unet_train* t, int B, int T, float p, unsigned long l
     Acts& a = t->a;
     const Gm gm{t};
     const int M = B * T;
-    const float* P = t->P;
+    const float* P = t->st.P;
     auto w = [&](const std::string& n) { return par(t, P, n); };
-    auto gw = [&](const std::string& n) { return par(t, t->G, n); };
+    auto gw = [&](const std::string& n) { return par(t, t->st.G, n); };
     const std::string m = "denoiser.model.";
     const float scale = 0.17677669529663687f;
     // norm gradients: dgamma = sum du xhat, dbeta = sum du over the rows
@@ -434,11 +431,6 @@ void enqueue_backward(said_unet_train* t, int B, int T, float p, unsigned long l
     colsum(s, a.dctx, CTX, nullptr, 0, M, 1, CTX, gw("null_cond_emb"), 0);
 }
 
-void enqueue_update(said_unet_train* t) {
-    grad_norm(t->s, t->nseg, t->seg, t->G, t->part, t->clip);
-    adamw_ema(t->s, t->nparam, t->P, t->G, t->M, t->V, t->E, t->clip, t->rec);
-}
-
 int put_record(said_unet_train* t, const float* scalars, const float* std_) {
     HostCtx* ctx = &t->c;
     float h[NSCAL + XC] = {};
@@ -534,26 +526,20 @@ int said_unet_train_create(said_unet_train** out, int device, int max_batch, int
     ctx->device = device;
     t->maxB = max_batch;
     t->maxT = max_frames;
-    std::vector<long long> seg;
     const auto& tb = table();
-    for (size_t i = 0; i < tb.size(); ++i) {
-        t->off[tb[i].name] = t->nparam;
-        for (long long s0 = 0; s0 < tb[i].numel; s0 += SEG) seg.insert(seg.end(), {t->nparam + s0, std::min<long long>(SEG, tb[i].numel - s0), (long long)i});
-        t->nparam += tb[i].numel;
-    }
-    t->nseg = (int)seg.size() / 3;
+    std::vector<long long> sizes, off;
+    for (const TDesc& d : tb) sizes.push_back(d.numel);
     Acts tmp;
     t->arena_n = layout(tmp, nullptr, max_batch, max_frames);
     const size_t Mx = (size_t)max_batch * max_frames;
     int rc = 0;
     rc = rc || hipStreamCreateWithFlags(&t->s, hipStreamNonBlocking) != hipSuccess;
-    rc = rc || dalloc(ctx, &t->P, t->nparam) || dalloc(ctx, &t->G, t->nparam) || dalloc(ctx, &t->M, t->nparam) || dalloc(ctx, &t->V, t->nparam) ||
-         dalloc(ctx, &t->E, t->nparam) || dalloc(ctx, &t->S, t->nparam) || dalloc(ctx, &t->seg, seg.size()) || dalloc(ctx, &t->part, (size_t)t->nseg) || dalloc(ctx, &t->clip, 2) ||
-         dalloc(ctx, &t->acc, (size_t)2 * NACC) || dalloc(ctx, &t->last, 4) || dalloc(ctx, &t->rec, NSCAL + XC) || dalloc(ctx, &t->coeffs, Mx * XC) ||
+    rc = rc || dalloc(ctx, &t->rec, NSCAL + XC) || dalloc(ctx, &t->coeffs, Mx * XC) ||
          dalloc(ctx, &t->noise, Mx * XC) || dalloc(ctx, &t->tsf, max_batch) || dalloc(ctx, &t->sasb, (size_t)2 * max_batch) ||
          dalloc(ctx, &t->audio, Mx * CTX) || dalloc(ctx, &t->cond, max_batch) || dalloc(ctx, &t->band, (size_t)2 * max_frames) ||
          dalloc(ctx, &t->arena, t->arena_n) || dalloc(ctx, &t->gpart, (size_t)MAXKS * TEd * TEd) || dalloc(ctx, &t->vpart, VBLK);
-    if (!rc) rc = hipMemcpy(t->seg, seg.data(), seg.size() * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess;
+    rc = rc || store_build(&t->st, ctx, sizes, true, &off);   // last: it ends with a synchronous copy, after every allocation's memset
+    for (size_t i = 0; i < tb.size() && !rc; ++i) t->off[tb[i].name] = off[i];
     if (rc) {
         g_create_err = ctx->err.empty() ? std::string("said_unet_train_create: allocation failed") : ctx->err;
         said_unet_train_destroy(t);
@@ -576,10 +562,7 @@ int said_unet_train_destroy(said_unet_train* t) {
 
 const char* said_unet_train_last_error(const said_unet_train* t) { return t ? t->c.err.c_str() : g_create_err.c_str(); }
 
-static float* copy_of(said_unet_train* t, int which, int i) {
-    float* base[6] = {t->P, t->E, t->G, t->M, t->V, t->S};
-    return (which >= 0 && which < 6) ? base[which] + t->off.at(table()[i].name) : nullptr;
-}
+static float* copy_of(said_unet_train* t, int which, int i) { return store_copy_of(&t->st, which, t->off.at(table()[i].name)); }
 
 int said_unet_train_set_tensor(said_unet_train* t, int which, const char* name, const float* host, long long n) {
     if (!t) return -1;
@@ -591,9 +574,7 @@ int said_unet_train_set_tensor(said_unet_train* t, int which, const char* name, 
     if (!dst) return fail(ctx, "said_unet_train_set_tensor: no copy %d", which);
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMemcpyAsync(dst, host, n * sizeof(float), hipMemcpyHostToDevice, t->s));
-    HIPCHK(hipStreamSynchronize(t->s));
-    return 0;
+    return store_copy(&t->st, t->s, dst, host, n, hipMemcpyHostToDevice, true);
 }
 
 int said_unet_train_get_tensor(said_unet_train* t, int which, const char* name, float* host, long long n) {
@@ -606,9 +587,7 @@ int said_unet_train_get_tensor(said_unet_train* t, int which, const char* name, 
     if (!src) return fail(ctx, "said_unet_train_get_tensor: no copy %d", which);
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMemcpyAsync(host, src, n * sizeof(float), hipMemcpyDeviceToHost, t->s));
-    HIPCHK(hipStreamSynchronize(t->s));
-    return 0;
+    return store_copy(&t->st, t->s, host, src, n, hipMemcpyDeviceToHost, true);
 }
 
 int said_unet_train_reset_optimizer(said_unet_train* t) {
@@ -616,24 +595,17 @@ int said_unet_train_reset_optimizer(said_unet_train* t) {
     HostCtx* ctx = &t->c;
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)t->nparam * sizeof(float);
-    HIPCHK(hipMemsetAsync(t->G, 0, bytes, t->s));
-    HIPCHK(hipMemsetAsync(t->M, 0, bytes, t->s));
-    HIPCHK(hipMemsetAsync(t->V, 0, bytes, t->s));
-    HIPCHK(hipMemcpyAsync(t->E, t->P, bytes, hipMemcpyDeviceToDevice, t->s));
-    HIPCHK(hipStreamSynchronize(t->s));
-    return 0;
+    return store_reset_optimizer(&t->st, t->s);
 }
 
 int said_unet_train_copy(said_unet_train* t, int dst, int src) {
     if (!t) return -1;
     HostCtx* ctx = &t->c;
-    float* base[6] = {t->P, t->E, t->G, t->M, t->V, t->S};
-    if (dst < 0 || dst >= 6 || src < 0 || src >= 6 || dst == src) return fail(ctx, "said_unet_train_copy: copies %d <- %d", dst, src);
+    float *d = store_copy_of(&t->st, dst, 0), *s = store_copy_of(&t->st, src, 0);
+    if (!d || !s || dst == src) return fail(ctx, "said_unet_train_copy: copies %d <- %d", dst, src);
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMemcpyAsync(base[dst], base[src], (size_t)t->nparam * sizeof(float), hipMemcpyDeviceToDevice, t->s));
-    return 0;
+    return store_copy(&t->st, t->s, d, s, t->st.nparam, hipMemcpyDeviceToDevice, false);
 }
 
 int said_unet_train_set_alphas(said_unet_train* t, const float* ac, int n) {
@@ -660,12 +632,12 @@ int said_unet_train_step(said_unet_train* t, int B, int T, const float* coeffs, 
         return -1;
     layout(t->a, t->arena, B, T);
     add_noise(t->s, B, T, t->coeffs, t->noise, t->sasb, t->rec, t->a.noisy, t->a.answer);
-    enqueue_forward(t, B, T, t->P, p, seed);
-    enqueue_loss(t, B, T, deltas ? V : 0, true, t->acc);
+    enqueue_forward(t, B, T, t->st.P, p, seed);
+    enqueue_loss(t, B, T, deltas ? V : 0, true, t->st.acc);
     HIPCHK(hipMemsetAsync(t->a.dembs, 0, (size_t)B * TEd * sizeof(float), t->s));
     HIPCHK(hipMemsetAsync(t->a.dctx, 0, (size_t)B * T * CTX * sizeof(float), t->s));
     enqueue_backward(t, B, T, p, seed);
-    enqueue_update(t);
+    store_enqueue_update(&t->st, t->s, t->rec);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -684,8 +656,8 @@ int said_unet_train_eval_loss(said_unet_train* t, int B, int T, const float* coe
         return -1;
     layout(t->a, t->arena, B, T);
     add_noise(t->s, B, T, t->coeffs, t->noise, t->sasb, t->rec, t->a.noisy, t->a.answer);
-    enqueue_forward(t, B, T, ema ? t->E : t->P, 0.f, 0);
-    enqueue_loss(t, B, T, deltas ? V : 0, false, t->acc + NACC);
+    enqueue_forward(t, B, T, ema ? t->st.E : t->st.P, 0.f, 0);
+    enqueue_loss(t, B, T, deltas ? V : 0, false, t->st.acc + NACC);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -701,7 +673,7 @@ int said_unet_train_forward_only(said_unet_train* t, int B, int T, const float* 
     if (put_inputs(t, what, B, T, sample, nullptr, ts, cond, audio, audio_on_device, false)) return -1;
     layout(t->a, t->arena, B, T);
     HIPCHK(hipMemcpyAsync(t->a.noisy, t->coeffs, (size_t)B * T * XC * sizeof(float), hipMemcpyDeviceToDevice, t->s));
-    enqueue_forward(t, B, T, ema ? t->E : t->P, 0.f, 0);
+    enqueue_forward(t, B, T, ema ? t->st.E : t->st.P, 0.f, 0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, t->a.pred, (size_t)B * T * XC * sizeof(float), hipMemcpyDeviceToHost, t->s));
     HIPCHK(hipStreamSynchronize(t->s));
@@ -715,7 +687,7 @@ int said_unet_train_apply_update(said_unet_train* t, const float* scalars) {
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
     if (put_record(t, scalars, nullptr)) return -1;
-    enqueue_update(t);
+    store_enqueue_update(&t->st, t->s, t->rec);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -726,12 +698,7 @@ int said_unet_train_read_losses(said_unet_train* t, int val, double* acc_host, i
     if (!acc_host) return fail(ctx, "said_unet_train_read_losses: null output");
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
-    double* a = t->acc + (val ? NACC : 0);
-    HIPCHK(hipMemcpyAsync(acc_host, a, NACC * sizeof(double), hipMemcpyDeviceToHost, t->s));
-    if (reset) HIPCHK(hipMemsetAsync(a, 0, NACC * sizeof(double), t->s));
-    HIPCHK(hipStreamSynchronize(t->s));
-    if (status) *status = acc_host[A_BAD] > 0 ? SAID_UT_NOT_FINITE : SAID_UT_OK;
-    return 0;
+    return store_read_losses(&t->st, t->s, val, acc_host, status, reset);
 }
 
 int said_unet_train_last_losses(said_unet_train* t, float* out) {
@@ -740,8 +707,8 @@ int said_unet_train_last_losses(said_unet_train* t, float* out) {
     if (!out) return fail(ctx, "said_unet_train_last_losses: null output");
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMemcpyAsync(out, t->last, 4 * sizeof(float), hipMemcpyDeviceToHost, t->s));
-    HIPCHK(hipMemcpyAsync(out + 4, t->clip, 2 * sizeof(float), hipMemcpyDeviceToHost, t->s));
+    HIPCHK(hipMemcpyAsync(out, t->st.last, 4 * sizeof(float), hipMemcpyDeviceToHost, t->s));
+    HIPCHK(hipMemcpyAsync(out + 4, t->st.clip, 2 * sizeof(float), hipMemcpyDeviceToHost, t->s));
     HIPCHK(hipStreamSynchronize(t->s));
     return 0;
 }

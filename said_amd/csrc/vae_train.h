@@ -44,10 +44,6 @@ void reparam(hipStream_t s, int B, const float* mu, const float* lv, const float
 void loss(hipStream_t s, int B, const float* x, const float* u, const float* mu, const float* lv, const float* rec, float* du, float* last, double* acc);
 // dmu, dlv of beta * kld and of the reparametrisation, from dz
 void kl_reparam_bwd(hipStream_t s, int B, const float* mu, const float* lv, const float* eps, const float* dz, const float* rec, float* dmu, float* dlv);
-// squared 2-norms of the gradient segments (seg: start, length, tensor), then the clip factor min(1, 1 / (norm + 1e-6)) into clip[0] (clip[1] norm)
-void grad_norm(hipStream_t s, int nseg, const long long* seg, int ntensor, const float* G, double* part, float* clip);
-// AdamW (torch.optim.AdamW, single-tensor form) on clip[0] * G, then the EMA shadow
-void adamw_ema(hipStream_t s, long long n, float* P, const float* G, float* M, float* V, float* E, const float* clip, const float* rec);
 
 }  // namespace vt
 }  // namespace said

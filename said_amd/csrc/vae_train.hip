@@ -1,5 +1,5 @@
 // vae_train.hip — the BCVAE training step (said/model/vae.py, script/train_vae.py): training-mode forward with batch statistics, the ELBO
-// loss and its gradient, the backward of every layer, the global gradient-norm clip, AdamW and the EMA shadow.  fp32 throughout.
+// loss and its gradient, the backward of every layer.  fp32 throughout.  The update that follows (clip, AdamW, EMA) is train_opt.hip.
 //
 // Every reduction runs in a fixed order and no kernel uses atomics: a thread's own sum runs in index order, a wave's lanes are combined by a
 // fixed xor butterfly, a workgroup's waves by a fixed LDS tree.  Equal inputs give bit-identical outputs, launched directly or from a graph.
@@ -8,31 +8,11 @@
 
 #include <math.h>
 
+#include "train_dev.h"
+
 namespace said {
 namespace vt {
 namespace {
-
-constexpr int NT = 256;   // threads per workgroup of every kernel here
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum of one value per thread of a 256-thread workgroup, the same order every call; every thread gets the result
-template <typename F>
-__device__ __forceinline__ F block_sum(F v, F* sh) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    sh[t] = v;
-    __syncthreads();
-    for (int w = NT / 2; w >= 1; w >>= 1) {
-        if (t < w) sh[t] = sh[t] + sh[t + w];
-        __syncthreads();
-    }
-    return sh[0];
-}
 
 __global__ void __launch_bounds__(NT) gather_kernel(int B, const float* __restrict__ data, const long long* __restrict__ off,
                                                     const int* __restrict__ len, const int* __restrict__ items, const int* __restrict__ mirror,
@@ -304,59 +284,6 @@ __global__ void __launch_bounds__(NT) kl_reparam_bwd_kernel(int n, int B, const 
     dlv[i] = kb * (e - 1.f) + dz[i] * eps[i] * (0.5f * expf(0.5f * lv[i]));
 }
 
-// seg[3 s + 0..2] = start, length, tensor; segments of one tensor are consecutive
-__global__ void __launch_bounds__(NT) grad_sq_kernel(const long long* __restrict__ seg, const float* __restrict__ G, double* __restrict__ part) {
-    __shared__ double sh[NT];
-    const long long st = seg[3 * blockIdx.x], n = seg[3 * blockIdx.x + 1];
-    double q = 0.0;
-    for (long long i = threadIdx.x; i < n; i += NT) {
-        const double g = G[st + i];
-        q += g * g;
-    }
-    q = block_sum(q, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = q;
-}
-
-// torch.nn.utils.clip_grad_norm_(max_norm=1): total = |(|g_0|, |g_1|, ...)|, factor min(1, 1 / (total + 1e-6)), applied always
-__global__ void __launch_bounds__(64) clip_kernel(int nseg, const long long* __restrict__ seg, const double* __restrict__ part, float* __restrict__ clip) {
-    if (threadIdx.x != 0) return;
-    double tot = 0.0, cur = 0.0;
-    for (int s = 0; s < nseg; ++s) {
-        cur += part[s];
-        if (s + 1 == nseg || seg[3 * (s + 1) + 2] != seg[3 * s + 2]) {
-            const float nt = (float)sqrt(cur);   // per-tensor norm in fp32
-            tot += (double)nt * (double)nt;
-            cur = 0.0;
-        }
-    }
-    const float total = (float)sqrt(tot);
-    const float f = 1.f / (total + 1e-6f);
-    clip[0] = f < 1.f ? f : 1.f;
-    clip[1] = total;
-}
-
-__global__ void __launch_bounds__(NT) adamw_ema_kernel(long long n, float* __restrict__ P, const float* __restrict__ G, float* __restrict__ M,
-                                                       float* __restrict__ V, float* __restrict__ E, const float* __restrict__ clip,
-                                                       const float* __restrict__ rec) {
-    const float cf = clip[0], wdf = rec[S_WD_FACTOR], ss = rec[S_STEP_SIZE], bc2 = rec[S_BC2_SQRT], omb1 = rec[S_OMB1], b2 = rec[S_B2],
-                omb2 = rec[S_OMB2], eps = rec[S_EPS], omd = rec[S_EMA_OMD];
-    const bool ema = rec[S_USE_EMA] != 0.f;
-    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n; i += (long long)gridDim.x * NT) {
-        const float g = G[i] * cf;
-        float p = P[i] * wdf;                         // param.mul_(1 - lr wd)
-        const float m = M[i] + omb1 * (g - M[i]);     // exp_avg.lerp_(grad, 1 - beta1)
-        const float v = V[i] * b2 + (omb2 * g) * g;   // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-        const float den = sqrtf(v) / bc2 + eps;       // exp_avg_sq.sqrt() / bias_correction2_sqrt + eps
-        p = p + (-ss) * (m / den);                    // param.addcdiv_(exp_avg, denom, -lr / bias_correction1)
-        P[i] = p;
-        M[i] = m;
-        V[i] = v;
-        if (ema) E[i] = E[i] - omd * (E[i] - p);      // diffusers EMAModel.step: s -= (1 - decay)(s - p)
-    }
-}
-
-inline int nblk(long long n, int per = NT) { return (int)((n + per - 1) / per); }
-
 }  // namespace
 
 void gather(hipStream_t s, int B, const float* data, const long long* off, const int* len, const int* items, const int* mirror, float* x) {
@@ -397,14 +324,6 @@ void loss(hipStream_t s, int B, const float* x, const float* u, const float* mu,
 }
 void kl_reparam_bwd(hipStream_t s, int B, const float* mu, const float* lv, const float* eps, const float* dz, const float* rec, float* dmu, float* dlv) {
     kl_reparam_bwd_kernel<<<nblk((long long)B * Z), NT, 0, s>>>(B * Z, B, mu, lv, eps, dz, rec, dmu, dlv);
-}
-void grad_norm(hipStream_t s, int nseg, const long long* seg, int ntensor, const float* G, double* part, float* clip) {
-    (void)ntensor;
-    grad_sq_kernel<<<nseg, NT, 0, s>>>(seg, G, part);
-    clip_kernel<<<1, 64, 0, s>>>(nseg, seg, part, clip);
-}
-void adamw_ema(hipStream_t s, long long n, float* P, const float* G, float* M, float* V, float* E, const float* clip, const float* rec) {
-    adamw_ema_kernel<<<std::min(nblk(n), 1024), NT, 0, s>>>(n, P, G, M, V, E, clip, rec);
 }
 
 }  // namespace vt

@@ -5,9 +5,13 @@
 #include "../../include/said_train.h"
 
 #include "engine_internal.h"
+#include "train_store.h"
 #include "vae_train.h"
 
 using namespace said::vt;
+
+static_assert(OPT_SLOTS_MATCH(SAID_TRAIN_S_), "said_train.h and train_opt.h disagree on the optimizer's slots of the step record");
+static_assert(NACC == TS_NACC && A_BAD == TS_A_BAD && SAID_TRAIN_NOT_FINITE == 1, "train_store.h reads the accumulators of vae_train.h");
 
 namespace {
 
@@ -41,7 +45,6 @@ const BNDesc kBN[8] = {{"encoder.conv_layers.1", 32, 118, 0.2f}, {"encoder.conv_
                        {"encoder.fc_layers.1", 256, 1, 0.01f},   {"encoder.fc_layers.4", 128, 1, 0.01f},  {"decoder.fc_layers.1", 240, 1, 0.01f},
                        {"decoder.conv_layers.1", 32, 122, 0.2f}, {"decoder.conv_layers.4", 32, 124, 0.2f}};
 constexpr int NBN = 8;
-constexpr int SEG = 8192;   // gradient-norm segment length
 constexpr int RING = 64;    // pinned step-record slots
 
 struct DataSet {
@@ -61,17 +64,12 @@ struct said_train {
     HostCtx c;
     int maxB = 0;
     hipStream_t s = nullptr;
-    long long nparam = 0, nbuf = 0;
-    long long off[70] = {};   // offset of each tensor in P (parameters) or RS (running stats); counters: index into nbt
-    float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr, *E = nullptr, *RS = nullptr;
+    TrainStore st;            // the parameters and the optimizer's state
+    long long nbuf = 0;
+    std::vector<long long> off;   // offset of each tensor in st.P (parameters) or RS (running stats); counters: index into nbt
+    float* RS = nullptr;
     long long nbt[NBN] = {};
-    long long* seg = nullptr;
-    int nseg = 0;
-    double* part = nullptr;
-    float* clip = nullptr;
     float* stats = nullptr;    // [NBN][2][256]
-    double* acc = nullptr;     // [2][NACC]
-    float* last = nullptr;     // 4
     // step record on the device and its pinned host ring
     float* rec = nullptr;
     size_t rec_n = 0;
@@ -150,8 +148,8 @@ void enqueue_forward(said_train* t, int B, const float* base, int train, int set
 // backward of the whole chain into G (every parameter's gradient is written, none accumulated)
 void enqueue_backward(said_train* t, int B) {
     hipStream_t s = t->s;
-    const float* P = t->P;
-    float* G = t->G;
+    const float* P = t->st.P;
+    float* G = t->st.G;
     float *g0 = t->g0, *g1 = t->g1;
     const std::string E = "encoder.", D = "decoder.";
     auto w = [&](const std::string& n) { return par(t, P, n); };
@@ -162,7 +160,7 @@ void enqueue_backward(said_train* t, int B) {
         (void)b;
     };
     // loss -> du (g0, time-major)
-    loss(s, B, t->X, t->U, t->MU, t->LV, t->rec, g0, t->last, t->acc);
+    loss(s, B, t->X, t->U, t->MU, t->LV, t->rec, g0, t->st.last, t->st.acc);
     // decoder conv_layers.7: D4 -> U
     conv_bwd_weight(s, 0, B, 32, 32, 3, 1, 122, 120, cf(t->D4, 32, 122), tm(g0), gw(D + "conv_layers.7.weight"), gw(D + "conv_layers.7.bias"));
     conv_bwd_data(s, 0, B, 32, 32, 3, 1, 122, 120, tm(g0), w(D + "conv_layers.7.weight"), cfw(g1, 32, 122));
@@ -211,15 +209,10 @@ void enqueue_backward(said_train* t, int B) {
     conv_bwd_weight(s, 0, B, 32, 32, 3, 1, 120, 118, tm(t->X), cf(g1, 32, 118), gw(E + "conv_layers.0.weight"), gw(E + "conv_layers.0.bias"));
 }
 
-void enqueue_update(said_train* t) {
-    grad_norm(t->s, t->nseg, t->seg, 46, t->G, t->part, t->clip);
-    adamw_ema(t->s, t->nparam, t->P, t->G, t->M, t->V, t->E, t->clip, t->rec);
-}
-
 void enqueue_step(said_train* t, int B) {
-    enqueue_forward(t, B, t->P, 1, SAID_TRAIN_SET_TRAIN);
+    enqueue_forward(t, B, t->st.P, 1, SAID_TRAIN_SET_TRAIN);
     enqueue_backward(t, B);
-    enqueue_update(t);
+    store_enqueue_update(&t->st, t->s, t->rec);
 }
 
 // copy the step record (scalars, std, items, eps) through the next pinned ring slot to the device
@@ -264,9 +257,7 @@ int check_std(said_train* t, const float* std_, const char* what) {
 float* copy_of(said_train* t, int which, int i) {
     const TDesc& d = kTensors[i];
     if (d.kind == K_RMEAN || d.kind == K_RVAR) return which == SAID_TRAIN_STATE ? t->RS + t->off[i] : nullptr;
-    if (d.kind != K_PARAM) return nullptr;
-    float* base[5] = {t->P, t->E, t->G, t->M, t->V};
-    return (which >= 0 && which < 5) ? base[which] + t->off[i] : nullptr;
+    return d.kind == K_PARAM ? store_copy_of(&t->st, which, t->off[i]) : nullptr;
 }
 
 }  // namespace
@@ -287,31 +278,23 @@ int said_train_create(said_train** out, int device, int max_batch) {
     HostCtx* ctx = &t->c;
     ctx->device = device;
     t->maxB = max_batch;
-    int nb = 0;
-    std::vector<long long> seg;
-    for (int i = 0; i < 70; ++i) {
+    std::vector<long long> sizes(70);
+    for (int i = 0; i < 70; ++i) sizes[i] = kTensors[i].kind == K_PARAM ? kTensors[i].numel : 0;
+    t->rec_n = NSCAL + C + (size_t)max_batch * ITEM + (size_t)max_batch * Z;
+    const size_t Bm = (size_t)max_batch;
+    auto bnbuf = [&](BNBuf& b, size_t n) { return dalloc(ctx, &b.a, Bm * n) || dalloc(ctx, &b.xhat, Bm * n) || dalloc(ctx, &b.h, Bm * n); };
+    int rc = store_build(&t->st, ctx, sizes, false, &t->off);
+    for (int i = 0, nb = 0; i < 70; ++i) {
         const TDesc& d = kTensors[i];
-        if (d.kind == K_PARAM) {
-            t->off[i] = t->nparam;
-            for (long long s0 = 0; s0 < d.numel; s0 += SEG) seg.insert(seg.end(), {t->nparam + s0, std::min<long long>(SEG, d.numel - s0), (long long)i});
-            t->nparam += d.numel;
-        } else if (d.kind == K_COUNT) {
+        if (d.kind == K_COUNT) {
             t->off[i] = nb++;
-        } else {
+        } else if (d.kind != K_PARAM) {
             t->off[i] = t->nbuf;
             t->nbuf += d.numel;
         }
     }
-    t->nseg = (int)seg.size() / 3;
-    t->rec_n = NSCAL + C + (size_t)max_batch * ITEM + (size_t)max_batch * Z;
-    const size_t Bm = (size_t)max_batch;
-    auto bnbuf = [&](BNBuf& b, size_t n) { return dalloc(ctx, &b.a, Bm * n) || dalloc(ctx, &b.xhat, Bm * n) || dalloc(ctx, &b.h, Bm * n); };
-    int rc = 0;
     rc = rc || hipStreamCreateWithFlags(&t->s, hipStreamNonBlocking) != hipSuccess;
-    rc = rc || dalloc(ctx, &t->P, t->nparam) || dalloc(ctx, &t->G, t->nparam) || dalloc(ctx, &t->M, t->nparam) || dalloc(ctx, &t->V, t->nparam) ||
-         dalloc(ctx, &t->E, t->nparam) || dalloc(ctx, &t->RS, t->nbuf) || dalloc(ctx, &t->seg, seg.size()) || dalloc(ctx, &t->part, (size_t)t->nseg) ||
-         dalloc(ctx, &t->clip, 2) || dalloc(ctx, &t->stats, (size_t)NBN * 512) || dalloc(ctx, &t->acc, (size_t)2 * NACC) || dalloc(ctx, &t->last, 4) ||
-         dalloc(ctx, &t->rec, t->rec_n);
+    rc = rc || dalloc(ctx, &t->RS, t->nbuf) || dalloc(ctx, &t->stats, (size_t)NBN * 512) || dalloc(ctx, &t->rec, t->rec_n);
     rc = rc || dalloc(ctx, &t->X, Bm * T * C) || bnbuf(t->e0, 32 * 118) || bnbuf(t->e1, 64 * 116) || bnbuf(t->e2, 64 * 57) || bnbuf(t->e4, 256) ||
          bnbuf(t->e5, 128) || bnbuf(t->d0, 240) || bnbuf(t->d2, 32 * 122) || bnbuf(t->d3, 32 * 124) || dalloc(ctx, &t->F, Bm * 1760) ||
          dalloc(ctx, &t->A6, Bm * Z) || dalloc(ctx, &t->MU, Bm * Z) || dalloc(ctx, &t->LV, Bm * Z) || dalloc(ctx, &t->Zb, Bm * Z) ||
@@ -320,7 +303,6 @@ int said_train_create(said_train** out, int device, int max_batch) {
     rc = rc || hipHostMalloc((void**)&t->ring, (size_t)RING * t->rec_n * sizeof(float), hipHostMallocDefault) != hipSuccess;
     for (int k = 0; k < RING && !rc; ++k) rc = hipEventCreateWithFlags(&t->ring_ev[k], hipEventDisableTiming) != hipSuccess;
     if (!rc) {
-        rc = hipMemcpy(t->seg, seg.data(), seg.size() * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess;
         std::vector<float> one(t->nbuf, 1.f);   // running_var starts at one, running_mean at zero (nn.BatchNorm1d)
         for (int i = 0; i < 70 && !rc; ++i)
             if (kTensors[i].kind == K_RVAR) rc = hipMemcpy(t->RS + t->off[i], one.data(), kTensors[i].numel * sizeof(float), hipMemcpyHostToDevice) != hipSuccess;
@@ -366,9 +348,7 @@ int said_train_set_tensor(said_train* t, int which, const char* name, const void
     }
     float* dst = copy_of(t, which, i);
     if (!dst) return fail(ctx, "said_train_set_tensor: %s has no copy %d (buffers have only SAID_TRAIN_STATE)", name, which);
-    HIPCHK(hipMemcpyAsync(dst, host, n * sizeof(float), hipMemcpyHostToDevice, t->s));
-    HIPCHK(hipStreamSynchronize(t->s));
-    return 0;
+    return store_copy(&t->st, t->s, dst, static_cast<const float*>(host), n, hipMemcpyHostToDevice, true);
 }
 
 int said_train_get_tensor(said_train* t, int which, const char* name, void* host, long long n) {
@@ -386,9 +366,7 @@ int said_train_get_tensor(said_train* t, int which, const char* name, void* host
     }
     float* src = copy_of(t, which, i);
     if (!src) return fail(ctx, "said_train_get_tensor: %s has no copy %d (buffers have only SAID_TRAIN_STATE)", name, which);
-    HIPCHK(hipMemcpyAsync(host, src, n * sizeof(float), hipMemcpyDeviceToHost, t->s));
-    HIPCHK(hipStreamSynchronize(t->s));
-    return 0;
+    return store_copy(&t->st, t->s, static_cast<float*>(host), src, n, hipMemcpyDeviceToHost, true);
 }
 
 int said_train_reset_optimizer(said_train* t) {
@@ -396,13 +374,7 @@ int said_train_reset_optimizer(said_train* t) {
     HostCtx* ctx = &t->c;
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)t->nparam * sizeof(float);
-    HIPCHK(hipMemsetAsync(t->G, 0, bytes, t->s));
-    HIPCHK(hipMemsetAsync(t->M, 0, bytes, t->s));
-    HIPCHK(hipMemsetAsync(t->V, 0, bytes, t->s));
-    HIPCHK(hipMemcpyAsync(t->E, t->P, bytes, hipMemcpyDeviceToDevice, t->s));
-    HIPCHK(hipStreamSynchronize(t->s));
-    return 0;
+    return store_reset_optimizer(&t->st, t->s);
 }
 
 int said_train_set_data(said_train* t, int set, const float* frames, long long nframes, const long long* off, const int* len, int nseq, const int* mirror) {
@@ -494,7 +466,7 @@ int said_train_apply_update(said_train* t, const float* scalars) {
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
     if (put_record(t, 0, nullptr, nullptr, scalars, nullptr)) return -1;
-    enqueue_update(t);
+    store_enqueue_update(&t->st, t->s, t->rec);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -507,8 +479,8 @@ int said_train_eval_loss(said_train* t, int set, int B, const int* items, const 
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
     if (put_record(t, B, items, eps, scalars, std_)) return -1;
-    enqueue_forward(t, B, ema ? t->E : t->P, 0, set);
-    loss(t->s, B, t->X, t->U, t->MU, t->LV, t->rec, nullptr, t->last, t->acc + NACC);
+    enqueue_forward(t, B, ema ? t->st.E : t->st.P, 0, set);
+    loss(t->s, B, t->X, t->U, t->MU, t->LV, t->rec, nullptr, t->st.last, t->st.acc + NACC);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -519,12 +491,7 @@ int said_train_read_losses(said_train* t, int val, double* acc_host, int* status
     if (!acc_host) return fail(ctx, "said_train_read_losses: null output");
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
-    double* a = t->acc + (val ? NACC : 0);
-    HIPCHK(hipMemcpyAsync(acc_host, a, NACC * sizeof(double), hipMemcpyDeviceToHost, t->s));
-    if (reset) HIPCHK(hipMemsetAsync(a, 0, NACC * sizeof(double), t->s));
-    HIPCHK(hipStreamSynchronize(t->s));
-    if (status) *status = acc_host[A_BAD] > 0 ? SAID_TRAIN_NOT_FINITE : SAID_TRAIN_OK;
-    return 0;
+    return store_read_losses(&t->st, t->s, val, acc_host, status, reset);
 }
 
 int said_train_last_losses(said_train* t, float* out) {
@@ -533,7 +500,7 @@ int said_train_last_losses(said_train* t, float* out) {
     if (!out) return fail(ctx, "said_train_last_losses: null output");
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMemcpyAsync(out, t->last, 4 * sizeof(float), hipMemcpyDeviceToHost, t->s));
+    HIPCHK(hipMemcpyAsync(out, t->st.last, 4 * sizeof(float), hipMemcpyDeviceToHost, t->s));
     HIPCHK(hipStreamSynchronize(t->s));
     return 0;
 }

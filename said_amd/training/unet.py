@@ -24,10 +24,10 @@ from torch.utils.data import DataLoader, Dataset, RandomSampler
 
 from .. import _engine
 from ..scheduler import DDIMScheduler
-from ..util.scheduler import constant_with_warmup_lambda, ema_decay
 from ..util.audio import load_audio
 from ..util.blendshape import DEFAULT_BLENDSHAPE_CLASSES, load_blendshape_coeffs
 from ..util.parser import parse_list
+from .base import TrainerBase, parse_std
 from .vae import DEFAULT_MIRROR_PAIRS, PERSON_IDS_TRAIN, PERSON_IDS_VAL, SENTENCE_IDS
 
 PREDICTION_TYPES = {"epsilon": 0, "sample": 1, "v_prediction": 2}
@@ -139,7 +139,7 @@ def normalize_deltas(blendshape_delta: torch.Tensor) -> torch.Tensor:
     return torch.div(d, norm.view(-1, 1, 1, 1)).reshape(b, k, v * i)
 
 
-class UNetTrainer:
+class UNetTrainer(TrainerBase):
     """The denoiser of SAID_UNet1D trained on one MI355X with the reference's step (script/train.py).
 
     `state_dict` holds at least the trainable keys (null_cond_emb, denoiser.model.*); every other key (the frozen audio_encoder.*) is kept and
@@ -156,28 +156,17 @@ class UNetTrainer:
         self.eng = _engine.UNetTrainEngine(torch.device(device), max_batch, max_frames)
         self.device = self.eng.device
         self.max_batch, self.max_frames = int(max_batch), int(max_frames)
-        self.base_lr, self.weight_decay, self.betas, self.adam_eps = float(learning_rate), float(weight_decay), tuple(betas), float(eps)
-        self.ema, self.ema_decay = bool(ema), float(ema_decay)
-        self.lr_lambda = constant_with_warmup_lambda(num_warmup_steps)
+        self._set_optimizer(learning_rate, num_warmup_steps, weight_decay, betas, eps, ema, ema_decay)
         self.prediction_type, self.dropout = prediction_type, float(dropout)
         self.num_train_timesteps = int(num_train_timesteps)
         self.alphas_cumprod = DDIMScheduler(num_train_timesteps=num_train_timesteps, beta_schedule="squaredcos_cap_v2").alphas_cumprod.float()
         self.eng.set_alphas(self.alphas_cumprod.numpy())
-        self.std = None
-        if std is not None:
-            s = np.asarray(torch.as_tensor(std, dtype=torch.float32).reshape(-1), dtype=np.float32)
-            if s.size != 32:
-                raise ValueError(f"the coefficient std must have 32 values (one per blendshape), got {s.size}")
-            self.std = s
+        self.std = parse_std(std)
         self._shapes = trainable_shapes()
         self._stored = False
         self.load_state_dict(state_dict)
 
     # ---- state
-    @property
-    def names(self) -> List[str]:
-        return [n for n, _ in self.eng.tensors]
-
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor]) -> None:
         """Set the trainable tensors (strict), keep every other key for state_dict(), and restart the optimizer: zero moments, the EMA
         shadow a copy of the parameters, step count 0."""
@@ -192,14 +181,6 @@ class UNetTrainer:
         self._frozen = OrderedDict((k, v.detach().cpu().clone()) for k, v in state_dict.items() if k not in self._shapes)
         self.eng.reset_optimizer()
         self.step_count = 0
-
-    def _get(self, which: int, name: str) -> torch.Tensor:
-        shape = self._shapes[name]
-        return torch.from_numpy(self.eng.get_tensor(which, name, int(np.prod(shape)))).reshape(shape)
-
-    def parameters_of(self, which: int) -> "OrderedDict[str, torch.Tensor]":
-        """One copy of every trainable tensor: _engine.UT_STATE, UT_EMA, UT_GRAD, UT_EXP_AVG or UT_EXP_AVG_SQ."""
-        return OrderedDict((n, self._get(which, n)) for n in self.names)
 
     def state_dict(self, ema: bool = False) -> "OrderedDict[str, torch.Tensor]":
         """SAID_UNet1D's checkpoint layout: the live trainable tensors (the EMA shadow with ema=True) and the frozen keys given at
@@ -226,27 +207,11 @@ class UNetTrainer:
         self._stored = False
 
     # ---- the step
-    def lr_at(self, k: int) -> float:
-        return self.base_lr * self.lr_lambda(k)
-
     def _scalars(self, weight_vel: float, weight_vertex: float, k: int, dropout: float) -> np.ndarray:
         """SAID_UT_S_* for optimizer step k (0-based), in double as torch / diffusers compute them."""
-        b1, b2 = self.betas
-        lr = self.lr_at(k)
-        n = k + 1
-        s = np.zeros(_engine.UT_NSCAL, dtype=np.float64)
-        s[_engine.UT_S_LR] = lr
-        s[_engine.UT_S_WD_FACTOR] = 1 - lr * self.weight_decay
-        s[_engine.UT_S_STEP_SIZE] = lr / (1 - b1 ** n)
-        s[_engine.UT_S_BC2_SQRT] = (1 - b2 ** n) ** 0.5
-        s[_engine.UT_S_EMA_OMD] = 1 - ema_decay(n, self.ema_decay)
+        s = self._optimizer_scalars(k)
         s[_engine.UT_S_WVEL] = weight_vel
         s[_engine.UT_S_WVERTEX] = weight_vertex
-        s[_engine.UT_S_OMB1] = 1 - b1
-        s[_engine.UT_S_B2] = b2
-        s[_engine.UT_S_OMB2] = 1 - b2
-        s[_engine.UT_S_EPS] = self.adam_eps
-        s[_engine.UT_S_USE_EMA] = 1.0 if self.ema else 0.0
         s[_engine.UT_S_PRED_TYPE] = PREDICTION_TYPES[self.prediction_type]
         s[_engine.UT_S_DROPOUT] = dropout
         return s.astype(np.float32)
@@ -292,12 +257,8 @@ class UNetTrainer:
 
     def epoch_output(self, val: bool, lr: Optional[float] = None) -> UNetLossEpochOutput:
         """The averaged losses since the last call (training steps, or eval_loss calls with val=True)."""
-        acc, status = self.eng.read_losses(val, reset=True)
-        if status != 0:
-            raise FloatingPointError(f"{int(acc[5])} {'validation' if val else 'training'} step(s) had a non-finite loss")
+        acc = self._epoch_sums(val)
         n = acc[4]
-        if n <= 0:
-            raise ValueError("no samples in the epoch")
         return UNetLossEpochOutput(total=acc[3] / n, predict=acc[0] / n, velocity=acc[1] / n, vertex=acc[2] / n, lr=lr)
 
     def train_epoch(self, model, train_dataloader: Iterable, weight_vel: float, weight_vertex: float) -> UNetLossEpochOutput:
@@ -317,9 +278,6 @@ class UNetTrainer:
                 self.eval_loss(data.blendshape_coeffs, data.cond, batch_audio_embedding(model, data), weight_vel=weight_vel, weight_vertex=weight_vertex,
                                deltas=None if data.blendshape_delta is None else normalize_deltas(data.blendshape_delta), use_ema=use_ema)
         return self.epoch_output(True)
-
-    def close(self) -> None:
-        self.eng.close()
 
 
 def batch_audio_embedding(model, data) -> torch.Tensor:

@@ -27,7 +27,7 @@ from torch.utils.data import DataLoader, Dataset, RandomSampler
 
 from .. import _engine
 from ..util.blendshape import DEFAULT_BLENDSHAPE_CLASSES, load_blendshape_coeffs
-from ..util.scheduler import constant_with_warmup_lambda, ema_decay
+from .base import TrainerBase, parse_std
 
 PERSON_IDS_TRAIN = [
     "FaceTalk_170725_00137_TA", "FaceTalk_170728_03272_TA", "FaceTalk_170811_03274_TA", "FaceTalk_170904_00128_TA",
@@ -197,7 +197,7 @@ def make_dataloaders(train_dataset: VAEWindowDataset, val_dataset: Optional[VAEW
 
 
 # ---------------------------------------------------------------------------------------------------------------- trainer
-class BCVAETrainer:
+class BCVAETrainer(TrainerBase):
     """BCVAE(channels=32, seq_len=120, z_dim=64) trained on one MI355X with the reference's step (script/train_vae.py).
 
     learning_rate, weight decay 0.01 and betas / eps are torch.optim.AdamW's; the LR follows constant_with_warmup with
@@ -210,25 +210,18 @@ class BCVAETrainer:
         self.eng = _engine.TrainEngine(torch.device(device), max_batch)
         self.device = self.eng.device
         self.max_batch = int(max_batch)
-        self.base_lr, self.weight_decay, self.betas, self.adam_eps = float(learning_rate), float(weight_decay), tuple(betas), float(eps)
-        self.ema, self.ema_decay = bool(ema), float(ema_decay)
         self.num_warmup_steps = 0.1 * num_training_steps
-        self.lr_lambda = constant_with_warmup_lambda(self.num_warmup_steps)
+        self._set_optimizer(learning_rate, self.num_warmup_steps, weight_decay, betas, eps, ema, ema_decay)
         self.use_graph = bool(use_graph)
-        self.std = None
-        if std is not None:
-            s = np.asarray(torch.as_tensor(std, dtype=torch.float32).reshape(-1), dtype=np.float32)
-            if s.size != 32:
-                raise ValueError(f"the coefficient std must have 32 values (one per blendshape), got {s.size}")
-            self.std = s
+        self.std = parse_std(std)
         self._template = bcvae_init_state_dict() if state_dict is None else None
         self.load_state_dict(self._template if state_dict is None else state_dict)
         self._has_train, self._has_val = False, False
 
     # ---- state
     @property
-    def names(self) -> List[str]:
-        return [n for n, _, _ in self.eng.tensors]
+    def param_names(self) -> List[str]:
+        return [n for n, _, c in self.eng.tensors if not (c or n.endswith("running_mean") or n.endswith("running_var"))]
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor]) -> None:
         """Set the model state (all 70 reference keys, strict) and restart the optimizer: zero moments, the EMA shadow a copy of the
@@ -247,11 +240,6 @@ class BCVAETrainer:
         self.eng.reset_optimizer()
         self.step_count = 0
 
-    def _get(self, which: int, name: str) -> torch.Tensor:
-        numel = dict((n, k) for n, k, _ in self.eng.tensors)[name]
-        a = self.eng.get_tensor(which, name, numel)
-        return torch.from_numpy(a).reshape(self._shapes[name])
-
     def state_dict(self, ema: bool = True) -> "OrderedDict[str, torch.Tensor]":
         """The checkpoint layout: the 70 reference keys; parameters from the EMA shadow when ema (and the trainer keeps one), running
         statistics and num_batches_tracked (int64) live."""
@@ -261,11 +249,6 @@ class BCVAETrainer:
             is_param = not (counter or name.endswith("running_mean") or name.endswith("running_var"))
             out[name] = self._get(_engine.TRAIN_EMA if (use_ema and is_param) else _engine.TRAIN_STATE, name)
         return out
-
-    def parameters_of(self, which: int) -> "OrderedDict[str, torch.Tensor]":
-        """One copy of every parameter: _engine.TRAIN_STATE, TRAIN_EMA, TRAIN_GRAD, TRAIN_EXP_AVG or TRAIN_EXP_AVG_SQ."""
-        return OrderedDict((n, self._get(which, n)) for n, _, c in self.eng.tensors
-                           if not (c or n.endswith("running_mean") or n.endswith("running_var")))
 
     # ---- data
     def set_train_data(self, dataset: VAEWindowDataset) -> None:
@@ -277,27 +260,11 @@ class BCVAETrainer:
         self._has_val = True
 
     # ---- the step
-    def lr_at(self, k: int) -> float:
-        return self.base_lr * self.lr_lambda(k)
-
     def _scalars(self, beta: float, weight_vel: float, k: int) -> np.ndarray:
         """SAID_TRAIN_S_* for optimizer step k (0-based), in double as torch / diffusers compute them."""
-        b1, b2 = self.betas
-        lr = self.lr_at(k)
-        n = k + 1
-        s = np.zeros(_engine.TRAIN_NSCAL, dtype=np.float64)
-        s[_engine.TRAIN_S_LR] = lr
-        s[_engine.TRAIN_S_WD_FACTOR] = 1 - lr * self.weight_decay
-        s[_engine.TRAIN_S_STEP_SIZE] = lr / (1 - b1 ** n)
-        s[_engine.TRAIN_S_BC2_SQRT] = (1 - b2 ** n) ** 0.5
-        s[_engine.TRAIN_S_EMA_OMD] = 1 - ema_decay(n, self.ema_decay)
+        s = self._optimizer_scalars(k)
         s[_engine.TRAIN_S_BETA] = beta
         s[_engine.TRAIN_S_WVEL] = weight_vel
-        s[_engine.TRAIN_S_OMB1] = 1 - b1
-        s[_engine.TRAIN_S_B2] = b2
-        s[_engine.TRAIN_S_OMB2] = 1 - b2
-        s[_engine.TRAIN_S_EPS] = self.adam_eps
-        s[_engine.TRAIN_S_USE_EMA] = 1.0 if self.ema else 0.0
         return s.astype(np.float32)
 
     def _items(self, items) -> np.ndarray:
@@ -333,12 +300,8 @@ class BCVAETrainer:
         return LossStepOutput(reconst=torch.tensor(rec), regularize=torch.tensor(reg), velocity=torch.tensor(vel))
 
     def _epoch_output(self, val: bool, lr: Optional[float]) -> LossEpochOutput:
-        acc, status = self.eng.read_losses(val, reset=True)
-        if status != _engine.TRAIN_OK:
-            raise FloatingPointError(f"{int(acc[5])} {'validation' if val else 'training'} step(s) had a non-finite loss")
+        acc = self._epoch_sums(val)
         n = acc[4]
-        if n <= 0:
-            raise ValueError("no samples in the epoch")
         return LossEpochOutput(total=acc[3] / n, reconst=acc[0] / n, regularize=acc[1] / n, velocity=acc[2] / n, lr=lr)
 
     def train_epoch(self, train_dataloader: Iterable, beta: float, weight_vel: float) -> LossEpochOutput:
@@ -360,6 +323,3 @@ class BCVAETrainer:
                 it = self._items(items)
                 self.eng.eval_loss(_engine.TRAIN_SET_VAL, it, self._eps(None, it.shape[0]), sc, self.std, ema)
         return self._epoch_output(True, None)
-
-    def close(self) -> None:
-        self.eng.close()

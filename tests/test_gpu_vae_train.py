@@ -15,6 +15,7 @@ import torch
 from said_amd import _engine
 from said_amd.training import BCVAETrainer, VAEWindowDataset, bcvae_init_state_dict
 from said_amd.training.vae import BN_CANCELLED_BIASES
+from train_opt_check import check_clip_adamw_ema_update
 from vae_train_ref import RefTrainer, encode_eval, forward, split_state, windows_of
 
 pytestmark = pytest.mark.gpu
@@ -101,54 +102,13 @@ def test_batch_and_running_statistics_after_one_step(runs):
         np.testing.assert_allclose(invstd, 1 / torch.sqrt(var + 1e-5), rtol=2e-5)
 
 
-def _ulp_close(a, b, mag, ulps=4):
-    """|a - b| within `ulps` units in the last place of the largest magnitude among a, b and the update's operands (`mag`): a result that
-    cancels (an EMA shadow or a parameter landing near 0) carries the rounding of its operands, not of itself."""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    tol = ulps * np.spacing(np.maximum(np.maximum(np.abs(a), np.abs(b)), np.abs(np.asarray(mag, np.float32)))) + 1e-30
-    assert np.all(np.abs(a.astype(np.float64) - b) <= tol), np.abs(a.astype(np.float64) - b).max()
-
-
 @pytest.mark.parametrize("grad_scale", [1e-4, 10.0])
 def test_clip_adamw_ema_update(grad_scale):
     """One clip + AdamW + EMA update from set gradients against torch's fp32 clip_grad_norm_ and AdamW and the EMA formula; grad_scale 10
     makes the clip active, 1e-4 leaves it off."""
     tr = make_trainer()
-    rng = np.random.default_rng(int(grad_scale * 1000))
-    k = 6   # optimizer step 7: past the warmup, bias corrections still active
-    names = list(tr.parameters_of(_engine.TRAIN_STATE).keys())
-    shapes = {n: t.shape for n, t in tr.parameters_of(_engine.TRAIN_STATE).items()}
-    vals = {}
-    for n in names:
-        p, g, m = (rng.standard_normal(shapes[n]).astype(np.float32) for _ in range(3))
-        v, e = rng.random(shapes[n]).astype(np.float32) * 1e-3, rng.standard_normal(shapes[n]).astype(np.float32)
-        g *= grad_scale / 800.0
-        vals[n] = (p, g, m, v, e)
-        for which, a in zip((_engine.TRAIN_STATE, _engine.TRAIN_GRAD, _engine.TRAIN_EXP_AVG, _engine.TRAIN_EXP_AVG_SQ, _engine.TRAIN_EMA),
-                            (p, g, m, v, e)):
-            tr.eng.set_tensor(which, n, a)
-    tr.eng.apply_update(tr._scalars(1.0, 1.0, k))
-    # torch, fp32
-    params = [torch.tensor(vals[n][0], requires_grad=True) for n in names]
-    for q, n in zip(params, names):
-        q.grad = torch.tensor(vals[n][1])
-    norm = torch.nn.utils.clip_grad_norm_(params, 1.0)
-    assert (norm.item() > 1.0) == (grad_scale > 1)
-    lr = tr.lr_at(k)
-    opt = torch.optim.AdamW(params, lr=lr)
-    for q, n in zip(params, names):
-        opt.state[q] = {"step": torch.tensor(float(k)), "exp_avg": torch.tensor(vals[n][2]), "exp_avg_sq": torch.tensor(vals[n][3])}
-    opt.step()
-    from said_amd.util.scheduler import ema_decay
-    d = ema_decay(k + 1, 0.99)
-    for q, n in zip(params, names):
-        e = torch.tensor(vals[n][4])
-        e.sub_((1 - d) * (e - q.detach()))
-        p0, g0, m0, v0, e0 = vals[n]
-        _ulp_close(tr._get(_engine.TRAIN_STATE, n).numpy(), q.detach().numpy(), p0)
-        _ulp_close(tr._get(_engine.TRAIN_EXP_AVG, n).numpy(), opt.state[q]["exp_avg"].numpy(), np.maximum(np.abs(m0), np.abs(g0)))
-        _ulp_close(tr._get(_engine.TRAIN_EXP_AVG_SQ, n).numpy(), opt.state[q]["exp_avg_sq"].numpy(), np.maximum(v0, g0 * g0))
-        _ulp_close(tr._get(_engine.TRAIN_EMA, n).numpy(), e.numpy(), np.maximum(np.abs(e0), np.abs(p0)), ulps=8)
+    check_clip_adamw_ema_update(tr, (_engine.TRAIN_STATE, _engine.TRAIN_GRAD, _engine.TRAIN_EXP_AVG, _engine.TRAIN_EXP_AVG_SQ, _engine.TRAIN_EMA),
+                                lambda k: tr._scalars(1.0, 1.0, k), grad_scale, 800.0)
 
 
 def test_trajectory_against_float64(runs):
