@@ -24,17 +24,23 @@ namespace {
 // time is that of the busiest CU: ceil(workgroups / 256) workgroups of (F + NB) units each, F = 0.45 the per-workgroup fixed part
 // (GroupNorm finalisation, operand tile; fitted on T = 1800: NB = 1 14.8 us, NB = 2 25.0 us at 342 workgroups each).  Round 2's rule
 // (NB = 2 from 64 tiles) put 342 workgroups on 256 CUs at T = 1800: two rounds of three units where NB = 3 is one round of 3.45.
-LaunchCfg pick_unet(long long t_tiles_total) {
-    if (t_tiles_total * 6 > 1024) return t_tiles_total * 3 >= 192 ? LaunchCfg{2, 8} : LaunchCfg{1, 8};   // (large launches: multi-tile NB = 2 shapes)
+int best_nb(long long token_tiles, int column_tiles) {
     int best = 1;
     double cost = 1e30;
     for (int nb = 1; nb <= 3; ++nb) {
-        const long long wgs = t_tiles_total * (6 / nb);
+        const long long wgs = token_tiles * (column_tiles / nb);
         const double k = (double)((wgs + 255) / 256) * (0.45 + nb);
         if (k < cost - 1e-9) { cost = k; best = nb; }
     }
-    return LaunchCfg{best, 8};
+    return best;
 }
+LaunchCfg pick_unet(long long t_tiles_total) {
+    if (t_tiles_total * 6 > 1024) return t_tiles_total * 3 >= 192 ? LaunchCfg{2, 8} : LaunchCfg{1, 8};   // (large launches: multi-tile NB = 2 shapes)
+    return LaunchCfg{best_nb(t_tiles_total, 6), 8};
+}
+
+constexpr float ATTN_SCALE = 0.17677669529663687f;   // dim_head ** -0.5 = 32 ** -0.5 (attention.py:101)
+constexpr float LOG2E = 1.4426950408889634f;
 
 }  // namespace
 
@@ -74,6 +80,9 @@ inline bool dbg_go(said_ctx* c) {
     if (c->dbg_only >= 0) return k == c->dbg_only;
     return c->dbg_stop < 0 || k < c->dbg_stop;
 }
+
+// -DSAID_TRACE builds: how the launch just issued ended
+inline void trace_done(hipStream_t s) { if (trace_on()) { hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[said]   -> %s\n", hipGetErrorString(e)); fflush(stderr); } }
 
 // (a helper launch that is not a node of the counted schedule: runs whenever the NEXT counted launch would)
 inline bool dbg_go_peek(const said_ctx* c) { return c->dbg_only >= 0 ? c->dbg_count == c->dbg_only : (c->dbg_stop < 0 || c->dbg_count < c->dbg_stop); }
@@ -143,7 +152,7 @@ bool do_gemm(said_ctx* c, const GemmArgs& a, int epi, int batch, int NB, int KS,
         if (on_ugemm) {}
         else if (epi == EPI_QKV && a2.kv_split) c->launch_err = "q/k/v GEMM asked for pre-split k / v but does not run on ugemm_kernel";
         else launch_gemm(a2, epi, batch, NB, KS, s);
-        if (trace_on()) { hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[said]   -> %s\n", hipGetErrorString(e)); fflush(stderr); }
+        trace_done(s);
     }
     return on_ugemm;
 }
@@ -155,7 +164,85 @@ void do_attn(said_ctx* c, const AttnArgs& a, int batch, int head_dim, int KS, hi
     if (dbg_go(c)) {
         if (trace_on()) { fprintf(stderr, "[said] attn #%d D=%d KS=%d T=%d batch=%d\n", c->dbg_count - 1, head_dim, KS, a.T, batch); fflush(stderr); }
         launch_attn(a, batch, head_dim, KS, s, c->bf16_mode ? 1 : (sp_on(c, c->attn_split) ? (presplit ? 3 : 2) : 0));
-        if (trace_on()) { hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[said]   -> %s\n", hipGetErrorString(e)); fflush(stderr); }
+        trace_done(s);
+    }
+}
+// battn_kernel (attn.hip): bf16 q / k / v as the token-major q/k/v projection leaves them (TGemmArgs::qkv_bf16)
+void do_battn(said_ctx* c, const AttnArgs& a, int batch, hipStream_t s) {
+    if (c->log_on) {
+        const double e = (double)batch * a.heads * HD * a.T;
+        c->stage_log.push_back({9, -1, 1, 1, 4.0 * e * 2.0, 4.0 * e * a.T});
+    }
+    if (dbg_go(c)) {
+        if (trace_on()) { fprintf(stderr, "[said] battn #%d T=%d batch=%d\n", c->dbg_count - 1, a.T, batch); fflush(stderr); }
+        launch_battn(a, batch, s);
+        trace_done(s);
+    }
+}
+// the self-attention of one block over q / k (QK) and v (VT) as every q/k/v projection leaves them; o_mode as AttnArgs has it
+AttnArgs mk_attn(const said_ctx* c, const UGeo& g, float* o, long long o_bstride, int o_mode) {
+    AttnArgs a;
+    a.qk = c->QK; a.v = c->VT; a.o = o;
+    a.v_bstride = (long long)MC * g.Tp; a.o_bstride = o_bstride; a.o_mode = o_mode;
+    a.pitch = g.Tp; a.T = g.T; a.heads = HEADS; a.rows = rup(g.T, 32); a.b0 = 0;
+    a.scale = ATTN_SCALE;
+    return a;
+}
+
+inline int tm_seg(const UGeo& g) { return rup(g.T, 64); }   // sample pitch in tokens: a 64-row tile never straddles samples
+// Sample ranges of one SpatialTransformer block.  shared: guidance-shared prefix (first transformer under classifier-free guidance): self-attention and
+// everything before it run once per clip on samples [0, g.Bc).  With g.Bc > 0 the cross-attention (q projection, band softmax, to_out) runs on the
+// conditional half only — the unconditional half attends to one repeated key/value, so its attn2 output is the per-channel constant c2[blk] and
+// attn1's to_out emits its x2 = x1 + c2 directly.
+struct StRange {
+    int n1, n2;      // samples through self-attention / through cross-attention
+    int x_off;       // first sample of the cross-attention range in the activations (X1, O): the conditional half, unless the prefix is
+                     // shared (then X1 exists once per clip, in slots [0, Bc))
+    int kv_off;      // ... in X2 and the K/V: always the conditional half's
+    long long seg;   // sample pitch of the token-major activations (tm_seg)
+    int vt_rows;     // padded T of the q / k rows
+};
+inline StRange st_range(const UGeo& g, bool shared) {
+    return {shared ? g.Bc : g.Be, g.Bc > 0 ? g.Bc : g.Be, (g.Bc > 0 && !shared) ? g.Bc : 0, g.Bc > 0 ? g.Bc : 0, tm_seg(g), rup(g.T, 32)};
+}
+// cross-attention K (v = false) / V rows of block blk in the precomputed KV [sample][NST x (K | V) x 192][Sp], from sample kv_off on
+inline long long kv_bs(const UGeo& g) { return (long long)NST * 2 * MC * g.Sp; }
+inline const float* band_kv(const said_ctx* c, const UGeo& g, int blk, int kv_off, bool v) {
+    return c->KV + (long long)(blk * 2 * MC + (v ? MC : 0)) * g.Sp + (long long)kv_off * kv_bs(g);
+}
+// the timestep-embedding term of ResBlock rb_index (GemmArgs and TGemmArgs spell the fields alike)
+template <class Args> void set_emb(Args& a, const said_ctx* c, const UGeo& g, int rb_index) {
+    a.emb = c->EO + (long long)rb_index * MC * c->maxNp; a.emb_pitch = c->maxNp; a.step_ptr = g.step_ptr; a.emb_b_stride = g.emb_b_stride;
+}
+
+// ---- fp32 / bf16: everything behind a block's self-attention as ONE launch (stchain.hip) ------------------------------------
+// the fields both precisions share; the caller adds the output (y, y_bs) and what its kernel alone reads
+ChainArgs mkchain(const said_ctx* c, const UGeo& g, const STW& sw, int blk, const ActBuf& in, const ActBuf& out, const float* wstream) {
+    ChainArgs ca;
+    memset(&ca, 0, sizeof ca);
+    ca.wstream = wstream; ca.vec = sw.chain_vec;
+    ca.xin_part = in.st; ca.part_bs = g.sts; ca.gn_gamma = sw.gn_g; ca.gn_beta = sw.gn_b;
+    ca.kvt = c->KVT; ca.kvt_bs = (long long)g.S * (NST * 2 * MC); ca.lo = c->band_lo; ca.hi = c->band_hi;
+    ca.stats_out = out.st; ca.stats_bs = g.sts;
+    ca.S = g.S; ca.np = g.np; ca.koff = blk * 2 * MC; ca.wmax = c->band_wmax; ca.scale = ATTN_SCALE;
+    return ca;
+}
+// o / xin: the attention output and the block input, sample strides o_bs / x_bs
+void do_stchain(said_ctx* c, const UGeo& g, const StRange& r, ChainArgs ca, const void* o, const void* xin, long long o_bs, long long x_bs, bool shared, bool bf, hipStream_t s) {
+    if ((bf ? c->xclk_on : c->clk_on) && c->dbg_count < 64) ca.clk = c->clk_dev + (long long)c->dbg_count * 128;   // (bf16: said_debug_option "xgemm_clk": -DSAID_CLK_STAMPS builds)
+    if (c->log_on) {
+        const double eb = bf ? 2.0 : 4.0;   // element size of the weights and the activations (the K / V windows are fp32 in the log of both modes)
+        const int n1 = r.n1, n2 = r.n2;
+        const double w = eb * ((double)3 * MC * MC + 2.0 * FFI * MC + (double)(FFI + MC) * MC);
+        const double io = eb * MC * g.T * ((double)n1 * 2 + g.Be) + 4.0 * 2 * MC * g.T * (double)n2;
+        const double fl = 2.0 * g.T * ((double)n1 * MC * MC + (double)n2 * 2 * MC * MC + (double)g.Be * (2.0 * FFI * MC + (double)(FFI + MC) * MC)) + 4.0 * n2 * MC * g.T * c->band_wmax;
+        c->stage_log.push_back({10, EPI_STORE, 6, 8, w + io, fl});
+    }
+    if (dbg_go(c)) {
+        if (trace_on()) { fprintf(stderr, "[said] stchain #%d T=%d samples=%d shared=%d\n", c->dbg_count - 1, g.T, g.Be, (int)shared); fflush(stderr); }
+        launch_stchain(ca, static_cast<const float*>(o), static_cast<const float*>(xin), g.T, g.Tp, o_bs, x_bs, shared ? g.Bc : 0, g.Bc > 0 ? g.Bc : 0, g.Be, s, bf);
+        ++c->n_stchain;
+        trace_done(s);
     }
 }
 
@@ -172,6 +259,18 @@ bool use_tg(said_ctx* c, const UGeo& g, int nsamples) {
 }
 // weight of the token-major GEMM in the context's precision mode
 inline const void* tw(const said_ctx* c, const void* bf, const void* f32) { return c->bf16_mode ? bf : f32; }
+// conv_in_kernel (conv_in.hip): one result per clip, stored for its in_copies samples; tm: token-major bf16 (H0.t) instead of channel-major fp32 (H0.p)
+void do_conv_in(said_ctx* c, const UGeo& g, int in_copies, bool tm, hipStream_t s) {
+    if (c->log_on)
+        c->stage_log.push_back({11 /* conv_in_kernel */, EPI_STORE, 1, 4, 4.0 * ((double)MC * c->cin * 3 + (double)g.B_lat * c->cin * g.T + (double)g.Be * MC * g.T),
+                                2.0 * g.B_lat * MC * c->cin * 3 * g.T});
+    if (dbg_go(c)) {
+        if (trace_on()) { fprintf(stderr, "[said] conv_in #%d T=%d clips=%d copies=%d tm=%d\n", c->dbg_count - 1, g.T, g.B_lat, in_copies, (int)tm); fflush(stderr); }
+        if (tm) launch_conv_in_tm(c->x_cm, c->conv_in.w4[0], c->conv_in.bias, c->H0.t, tm_seg(g), c->H0.st, g.step_inc, g.B_lat, in_copies, g.T, g.Tp, s);
+        else launch_conv_in(c->x_cm, c->conv_in.w4[0], c->conv_in.bias, c->H0.p, c->H0.st, g.step_inc, g.B_lat, in_copies, g.T, g.Tp, MC, s);
+        trace_done(s);
+    }
+}
 void do_prep(said_ctx* c, const PrepArgs& a, int batch, hipStream_t s) {
     if (c->log_on) c->stage_log.push_back({5, -2, 0, 0, (double)batch * a.C * a.T * (4.0 + (c->bf16_mode ? 2.0 : 4.0)) * (a.dst2 ? 1.5 : 1.0), 0.0});
     PrepArgs a2 = a;
@@ -222,7 +321,6 @@ void tg_cm_out(TGemmArgs& t, const UGeo& g, const ActBuf& out) {
 }
 
 // ---- round 3, large batches: token-major activations between the kernels, operand transforms inside the GEMMs (xgemm_kernel) ----
-inline int tm_seg(const UGeo& g) { return rup(g.T, 64); }   // sample pitch in tokens: a 64-row tile never straddles samples
 // (32-bit element offsets inside the kernels: the widest token-major tensor here is the GEGLU product, sample pitch tm_seg — up to 4/3 of
 // the rup(T + 2, 32) pitch use_tg's guard is written for)
 inline bool use_tm(said_ctx* c, const UGeo& g) {
@@ -273,72 +371,68 @@ TGemmArgs mkx(const UGeo& g, const void* w, int N, int K) {
     t.gn_part_bs = g.sts; t.gn_nparts = g.np; t.stats_bs = g.sts; t.ldy = MC; t.ldr_tm = MC;
     return t;
 }
+// a ResBlock convolution: GroupNorm (eps 1e-5, gamma / beta of src's channels) -> SiLU -> conv3 of `src` as the resident operand, 192 outputs
+TGemmArgs mkx_conv3(const UGeo& g, const void* w, int K, const ActBuf& src, int cpg, const float* gamma, const float* beta) {
+    TGemmArgs t = mkx(g, w, MC, K);
+    t.ra[0] = src.t; t.rmode = 1; t.rtaps = 3;
+    t.gn_part[0] = src.st; t.gn_cpg = cpg; t.gn_eps = 1e-5f; t.gn_gamma = gamma; t.gn_beta = beta;
+    return t;
+}
+// in_layers of a concatenated-input ResBlock over ONE of its sources: input channels [off, off + 192), i.e. that range of every tap's weight columns
+TGemmArgs res_in_range(const UGeo& g, const ResW& rw, const ActBuf& src, int off) {
+    TGemmArgs t = mkx_conv3(g, rw.t_conv1, 3 * MC, src, rw.cin / 32, rw.g1 + off, rw.b1 + off);
+    t.w_ld = 3 * rw.cin; t.w_k0 = off; t.w_seg = rw.cin;
+    return t;
+}
 void run_resblock_tm(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, const ActBuf& in0, const ActBuf* in1, const ActBuf& out, hipStream_t s, bool shared) {
     const int nb = shared ? g.Bc : g.Be;
     // Round 4 (bf16 mode): a concatenated-input ResBlock (K = 1152 / 576 + 384) runs as launches of rgemm_kernel over COLUMN RANGES of the
     // same packed weights — its register-stationary weight fragments hold 576 columns per wave — with a bf16 partial sum in between (one extra
     // rounding of a quantity the next kernel rounds anyway): conv1 = [source 0 -> P] + [source 1 + bias + emb + P], and the 1x1 skip over
     // the raw input becomes the residual of conv2.  The partial / skip tensor lives in tX1 (idle until the block's SpatialTransformer).
-    bool split = false;
     if (in1 && c->bf16_mode && rw.has_skip) {
-        TGemmArgs t = mkx(g, rw.t_conv1, MC, 3 * MC);
-        t.ra[0] = in0.t; t.rmode = 1; t.rtaps = 3; t.gn_part[0] = in0.st; t.gn_cpg = rw.cin / 32; t.gn_eps = 1e-5f; t.gn_gamma = rw.g1; t.gn_beta = rw.b1;
-        t.y_tm = c->tX1; t.w_ld = 3 * rw.cin; t.w_seg = rw.cin;
-        split = rgemm_supports(t, nb);
-    }
-    if (split) {
-        {   // in_layers, source 0: GN -> SiLU -> conv3 over the first 192 input channels -> P
-            TGemmArgs t = mkx(g, rw.t_conv1, MC, 3 * MC);
-            t.ra[0] = in0.t; t.rmode = 1; t.rtaps = 3;
-            t.gn_part[0] = in0.st; t.gn_cpg = rw.cin / 32; t.gn_eps = 1e-5f; t.gn_gamma = rw.g1; t.gn_beta = rw.b1;
-            t.w_ld = 3 * rw.cin; t.w_k0 = 0; t.w_seg = rw.cin;
-            t.y_tm = c->tX1;
-            do_xgemm(c, t, nb, s);
+        // in_layers, source 0: GN -> SiLU -> conv3 over the first 192 input channels -> P
+        TGemmArgs p0 = res_in_range(g, rw, in0, 0);
+        p0.y_tm = c->tX1;
+        if (rgemm_supports(p0, nb)) {
+            do_xgemm(c, p0, nb, s);
+            {   // in_layers, source 1 (the skip connection's channels) + bias + emb term + P
+                TGemmArgs t = res_in_range(g, rw, *in1, MC);
+                t.bias = rw.conv1.bias;
+                set_emb(t, c, g, rb_index);
+                t.res_tm = c->tX1;
+                t.y_tm = c->M.t; t.stats = c->M.st;
+                do_xgemm(c, t, nb, s);
+            }
+            {   // skip_connection: Conv1d 1x1 over the concatenated raw input (openaimodel.py:194) -> tX1
+                TGemmArgs t = mkx(g, rw.t_conv2, MC, 2 * MC);
+                t.sa[0] = in0.t; t.sld[0] = MC; t.sk[0] = MC;
+                t.sa[1] = in1->t; t.sld[1] = MC; t.sk[1] = MC;
+                t.w_ld = 3 * MC + 2 * MC; t.w_k0 = 3 * MC;
+                t.y_tm = c->tX1;
+                do_xgemm(c, t, nb, s);
+            }
+            {   // out_layers: GN -> SiLU -> conv3 + (both biases) + skip(x)
+                TGemmArgs t = mkx_conv3(g, rw.t_conv2, 3 * MC, c->M, 6, rw.g2, rw.b2);
+                t.w_ld = 3 * MC + 2 * MC; t.w_k0 = 0;
+                t.bias = rw.bias2;
+                t.res_tm = c->tX1;
+                t.y_tm = out.t; t.stats = out.st;
+                do_xgemm(c, t, nb, s);
+            }
+            return;
         }
-        {   // in_layers, source 1 (the skip connection's channels) + bias + emb term + P
-            TGemmArgs t = mkx(g, rw.t_conv1, MC, 3 * MC);
-            t.ra[0] = in1->t; t.rmode = 1; t.rtaps = 3;
-            t.gn_part[0] = in1->st; t.gn_cpg = rw.cin / 32; t.gn_eps = 1e-5f; t.gn_gamma = rw.g1 + MC; t.gn_beta = rw.b1 + MC;
-            t.w_ld = 3 * rw.cin; t.w_k0 = MC; t.w_seg = rw.cin;
-            t.bias = rw.conv1.bias;
-            t.emb = c->EO + (long long)rb_index * MC * c->maxNp; t.emb_pitch = c->maxNp; t.step_ptr = g.step_ptr; t.emb_b_stride = g.emb_b_stride;
-            t.res_tm = c->tX1;
-            t.y_tm = c->M.t; t.stats = c->M.st;
-            do_xgemm(c, t, nb, s);
-        }
-        {   // skip_connection: Conv1d 1x1 over the concatenated raw input (openaimodel.py:194) -> tX1
-            TGemmArgs t = mkx(g, rw.t_conv2, MC, 2 * MC);
-            t.sa[0] = in0.t; t.sld[0] = MC; t.sk[0] = MC;
-            t.sa[1] = in1->t; t.sld[1] = MC; t.sk[1] = MC;
-            t.w_ld = 3 * MC + 2 * MC; t.w_k0 = 3 * MC;
-            t.y_tm = c->tX1;
-            do_xgemm(c, t, nb, s);
-        }
-        {   // out_layers: GN -> SiLU -> conv3 + (both biases) + skip(x)
-            TGemmArgs t = mkx(g, rw.t_conv2, MC, 3 * MC);
-            t.ra[0] = c->M.t; t.rmode = 1; t.rtaps = 3;
-            t.gn_part[0] = c->M.st; t.gn_cpg = 6; t.gn_eps = 1e-5f; t.gn_gamma = rw.g2; t.gn_beta = rw.b2;
-            t.w_ld = 3 * MC + 2 * MC; t.w_k0 = 0;
-            t.bias = rw.bias2;
-            t.res_tm = c->tX1;
-            t.y_tm = out.t; t.stats = out.st;
-            do_xgemm(c, t, nb, s);
-        }
-        return;
     }
     {   // in_layers: GN -> SiLU -> conv3 + emb term   (openaimodel.py:205-225)
-        TGemmArgs t = mkx(g, tw(c, rw.t_conv1, rw.tf_conv1), MC, 3 * rw.cin);
-        t.ra[0] = in0.t; t.ra[1] = in1 ? in1->t : nullptr; t.rmode = 1; t.rtaps = 3;
-        t.gn_part[0] = in0.st; t.gn_part[1] = in1 ? in1->st : nullptr; t.gn_cpg = rw.cin / 32; t.gn_eps = 1e-5f; t.gn_gamma = rw.g1; t.gn_beta = rw.b1;
+        TGemmArgs t = mkx_conv3(g, tw(c, rw.t_conv1, rw.tf_conv1), 3 * rw.cin, in0, rw.cin / 32, rw.g1, rw.b1);
+        if (in1) { t.ra[1] = in1->t; t.gn_part[1] = in1->st; }
         t.bias = rw.conv1.bias;
-        t.emb = c->EO + (long long)rb_index * MC * c->maxNp; t.emb_pitch = c->maxNp; t.step_ptr = g.step_ptr; t.emb_b_stride = g.emb_b_stride;
+        set_emb(t, c, g, rb_index);
         t.y_tm = c->M.t; t.stats = c->M.st;
         do_xgemm(c, t, nb, s);
     }
     {   // out_layers: GN -> SiLU -> conv3 ; + skip(x)   (openaimodel.py:226-227)
-        TGemmArgs t = mkx(g, tw(c, rw.t_conv2, rw.tf_conv2), MC, 3 * MC + (rw.has_skip ? 2 * MC : 0));
-        t.ra[0] = c->M.t; t.rmode = 1; t.rtaps = 3;
-        t.gn_part[0] = c->M.st; t.gn_cpg = 6; t.gn_eps = 1e-5f; t.gn_gamma = rw.g2; t.gn_beta = rw.b2;
+        TGemmArgs t = mkx_conv3(g, tw(c, rw.t_conv2, rw.tf_conv2), 3 * MC + (rw.has_skip ? 2 * MC : 0), c->M, 6, rw.g2, rw.b2);
         if (rw.has_skip) {   // 1x1 conv over the concatenated raw input: two streamed K segments behind the resident one
             t.sa[0] = in0.t; t.sld[0] = MC; t.sk[0] = MC;
             t.sa[1] = in1->t; t.sld[1] = MC; t.sk[1] = MC;
@@ -352,139 +446,112 @@ void run_resblock_tm(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, c
         do_xgemm(c, t, nb, s);
     }
 }
+// ---- the SpatialTransformer steps behind the self-attention on token-major activations (do_xgemm), shared by the two bf16 large-batch schedules ----
+// q / k / v of a token-major GEMM in attn.hip's operand layout: q and k token-major into QK [Be][2*heads][rows][32], v channel-major into VT [Be][192][Tp]
+void tg_qkv_out(TGemmArgs& t, const said_ctx* c, const UGeo& g, const StRange& r) {
+    t.qk = c->QK; t.vt = c->VT; t.v_bs = (long long)MC * g.Tp; t.qk_n = 2 * MC; t.head_dim = HD; t.rows = r.vt_rows; t.heads2 = 2 * HEADS; t.v_pitch = g.Tp;
+}
+TGemmArgs tm_out1(said_ctx* c, const UGeo& g, const STW& sw, int blk, const ActBuf& in) {   // x1 = to_out(attn) + GroupNorm(x_in)   (attention.py:127, 168); under guidance also x2 of the unconditional half = x1 + c2
+    TGemmArgs t = mkx(g, tw(c, sw.t_out1, sw.tf_out1), MC, MC);
+    t.sa[0] = c->tO; t.sld[0] = MC; t.sk[0] = MC;
+    t.bias = sw.out1.bias;
+    t.res_tm = in.t; t.res_gn = 1; t.res_part = in.st; t.res_gamma = sw.gn_g; t.res_beta = sw.gn_b; t.res_eps = 1e-6f; t.gn_cpg = 6;
+    t.y_tm = c->tX1;
+    if (g.Bc > 0) { t.y2_tm = c->tX2; t.y2_row_off = 0; t.y2_add = c->c2[blk]; }
+    return t;
+}
+TGemmArgs tm_q2_band(said_ctx* c, const UGeo& g, const STW& sw, int blk, const StRange& r) {   // attn2: q = to_q(norm2(x1)); banded softmax over the precomputed audio K/V   (attention.py:170-191)
+    TGemmArgs t = mkx(g, tw(c, sw.t_q2, sw.tf_q2), MC, MC);
+    t.ra[0] = tm_at(c, c->tX1, r.x_off * r.seg, MC); t.rmode = 2; t.rtaps = 1;
+    t.ln_gamma = sw.l2g; t.ln_beta = sw.l2b;
+    t.band_k = band_kv(c, g, blk, r.kv_off, false);
+    t.band_v = band_kv(c, g, blk, r.kv_off, true);
+    t.band_kv_bs = kv_bs(g); t.band_kv_pitch = g.Sp; t.band_lo = c->band_lo; t.band_hi = c->band_hi; t.band_wmax = c->band_wmax;
+    t.band_scale = ATTN_SCALE;
+    t.y_tm = tm_at(c, c->tO, r.x_off * r.seg, MC);
+    return t;
+}
+TGemmArgs tm_out2(said_ctx* c, const UGeo& g, const STW& sw, const StRange& r) {   // x2 = to_out(attn2) + x1   (conditional half only under guidance: its rows are [Bc, 2 Bc) of X2)
+    TGemmArgs t = mkx(g, tw(c, sw.t_out2, sw.tf_out2), MC, MC);
+    t.sa[0] = tm_at(c, c->tO, r.x_off * r.seg, MC); t.sld[0] = MC; t.sk[0] = MC;
+    t.bias = sw.out2.bias;
+    t.res_tm = tm_at(c, c->tX1, r.x_off * r.seg, MC);
+    t.y_tm = tm_at(c, c->tX2, r.kv_off * r.seg, MC);
+    return t;
+}
+TGemmArgs tm_geglu(said_ctx* c, const UGeo& g, const STW& sw, const StRange& r) {   // GEGLU: proj(norm3(x2)) -> a * gelu(gate)   (attention.py:25-32): the GEMM normalises its operand itself
+    TGemmArgs t = mkx(g, tw(c, sw.t_ff1, sw.tf_ff1), 2 * FFI, MC);
+    t.ra[0] = c->tX2; t.rmode = 2; t.rtaps = 1;
+    t.ln_gamma = sw.l3g; t.ln_beta = sw.l3b;
+    t.bias = sw.t_ff1_bias; t.geglu = 1;
+    t.yb = c->tF; t.y_bs = r.seg * FFI; t.ldy = FFI;
+    return t;
+}
+// proj_out o ff.net.2 over [h ; x2] + x_in   (attention.py:193, 232-234); cm: channel-major fp32 + GroupNorm partials (for a channel-major
+// ResBlock or out_sched_kernel), else token-major
+TGemmArgs tm_proj_out(said_ctx* c, const UGeo& g, const STW& sw, const ActBuf& in, const ActBuf& out, bool cm) {
+    TGemmArgs t = mkx(g, tw(c, sw.t_ffproj, sw.tf_ffproj), MC, FFI + MC);
+    t.sa[0] = c->tF; t.sld[0] = FFI; t.sk[0] = FFI;
+    t.sa[1] = c->tX2; t.sld[1] = MC; t.sk[1] = MC;
+    t.bias = sw.ffproj.bias;
+    t.res_tm = in.t;
+    if (cm) { t.y_cm = out.p; t.cm_bs = g.hs; t.cm_pitch = g.Tp; t.stats = out.st; }
+    else { t.y_tm = out.t; t.stats = out.st; }
+    return t;
+}
+// attn1.to_out, attn2 (q + band), attn2.to_out, GEGLU, folded proj_out.  last: the result goes out channel-major
+void run_tm_tail(said_ctx* c, const UGeo& g, const STW& sw, int blk, const ActBuf& in, const ActBuf& out, const StRange& r, hipStream_t s, bool last) {
+    do_xgemm(c, tm_out1(c, g, sw, blk, in), r.n1, s);
+    do_xgemm(c, tm_q2_band(c, g, sw, blk, r), r.n2, s);
+    do_xgemm(c, tm_out2(c, g, sw, r), r.n2, s);
+    do_xgemm(c, tm_geglu(c, g, sw, r), g.Be, s);
+    if (!last && c->bf16_mode) {   // round 4: as two rgemm launches over column ranges of the folded weight (see run_resblock_tm)
+        TGemmArgs h = mkx(g, sw.t_ffproj, MC, FFI);   // (P F2) h + x_in -> tX1 (x1 is dead by now)
+        h.sa[0] = c->tF; h.sld[0] = FFI; h.sk[0] = FFI; h.w_ld = FFI + MC; h.w_k0 = 0;
+        h.res_tm = in.t; h.y_tm = c->tX1;
+        if (rgemm_supports(h, g.Be)) {
+            do_xgemm(c, h, g.Be, s);
+            TGemmArgs t = mkx(g, sw.t_ffproj, MC, MC);   // + P x2 + (P b2 + bp)
+            t.sa[0] = c->tX2; t.sld[0] = MC; t.sk[0] = MC; t.w_ld = FFI + MC; t.w_k0 = FFI;
+            t.bias = sw.ffproj.bias;
+            t.res_tm = c->tX1; t.y_tm = out.t; t.stats = out.st;
+            do_xgemm(c, t, g.Be, s);
+            return;
+        }
+    }
+    do_xgemm(c, tm_proj_out(c, g, sw, in, out, last), g.Be, s);
+}
+
 // last: this block feeds the `out` convolution, which reads channel-major fp32 + GroupNorm partials (out_sched.hip)
 void run_transformer_tm(said_ctx* c, const UGeo& g, const STW& sw, int blk, const ActBuf& in, const ActBuf& out, hipStream_t s, bool shared, bool last) {
-    const int n1 = shared ? g.Bc : g.Be;
-    const int n2 = g.Bc > 0 ? g.Bc : g.Be;
-    const int x_off = (g.Bc > 0 && !shared) ? g.Bc : 0;
-    const int kv_off = g.Bc > 0 ? g.Bc : 0;
-    const long long seg = tm_seg(g);
-    const int vt_rows = rup(g.T, 32);
+    const StRange r = st_range(g, shared);
+    // softmax(q k^T * scale) v -> token-major   (attention.py:99-126)
+    const AttnArgs at = mk_attn(c, g, static_cast<float*>(c->tO), r.seg, c->bf16_mode ? 2 : 1);
     bool battn = false;
     {   // x = norm(x); q, k, v = to_{q,k,v}(norm1(x)) into attn.hip's operand layout   (attention.py:227, 168, 93-97)
         TGemmArgs t = mkx(g, tw(c, sw.t_qkv, sw.tf_qkv), 3 * MC, MC);
         t.ra[0] = in.t; t.rmode = 3; t.rtaps = 1;
         t.gn_part[0] = in.st; t.gn_cpg = 6; t.gn_eps = 1e-6f; t.gn_gamma = sw.gn_g; t.gn_beta = sw.gn_b;
         t.ln_gamma = sw.l1g; t.ln_beta = sw.l1b;
-        t.qk = c->QK; t.vt = c->VT; t.v_bs = (long long)MC * g.Tp; t.qk_n = 2 * MC; t.head_dim = HD; t.rows = vt_rows; t.heads2 = 2 * HEADS; t.v_pitch = g.Tp;
+        tg_qkv_out(t, c, g, r);
         // round 4 (bf16 mode, T <= 640): the projection writes bf16 q / k / v in battn_kernel's operand layout (attn.hip)
-        AttnArgs pa;
-        pa.qk = c->QK; pa.v = c->VT; pa.o = static_cast<float*>(c->tO); pa.v_bstride = (long long)MC * g.Tp; pa.o_bstride = seg;
-        pa.pitch = g.Tp; pa.T = g.T; pa.heads = HEADS; pa.rows = vt_rows; pa.b0 = 0; pa.scale = 0.17677669529663687f;
-        t.qkv_bf16 = (c->bf16_mode && battn_supports(pa, HD)) ? 1 : 0;
-        if (t.qkv_bf16 && !rgemm_supports(t, n1)) t.qkv_bf16 = 0;
+        t.qkv_bf16 = (c->bf16_mode && battn_supports(at, HD)) ? 1 : 0;
+        if (t.qkv_bf16 && !rgemm_supports(t, r.n1)) t.qkv_bf16 = 0;
         battn = t.qkv_bf16 != 0;
-        t.q_scale = 0.17677669529663687f * 1.4426950408889634f;   // dim_head ** -0.5 (attention.py:101) x log2(e)
-        do_xgemm(c, t, n1, s);
+        t.q_scale = ATTN_SCALE * LOG2E;
+        do_xgemm(c, t, r.n1, s);
     }
-    {   // softmax(q k^T * scale) v -> token-major   (attention.py:99-126)
-        AttnArgs a;
-        a.qk = c->QK; a.v = c->VT; a.o = static_cast<float*>(c->tO);
-        a.v_bstride = (long long)MC * g.Tp; a.o_bstride = seg; a.o_mode = c->bf16_mode ? 2 : 1;
-        a.pitch = g.Tp; a.T = g.T; a.heads = HEADS; a.rows = vt_rows; a.b0 = 0;
-        a.scale = 0.17677669529663687f;
-        if (battn) {
-            if (c->log_on) { const double e = (double)n1 * HEADS * HD * g.T; c->stage_log.push_back({9, -1, 1, 1, 4.0 * e * 2.0, 4.0 * e * g.T}); }
-            if (dbg_go(c)) launch_battn(a, n1, s);
-        } else {
-            do_attn(c, a, n1, HD, -4, s);
-        }
-    }
+    if (battn) do_battn(c, at, r.n1, s);
+    else do_attn(c, at, r.n1, HD, -4, s);
     // round 5: everything behind the attention as ONE launch on bf16 operands (stchain_kernel<true>; the token-major bf16 tensors are its operands as they are)
     if (c->bf16_mode && c->st_chain_bf16 != 0 && !last && sw.chain_wb && sw.chain_vec && c->band_chain_ok && c->kvt_S == g.S && c->kvt_bf16 && g.S == c->band_S && g.T == c->band_T &&
-        (long long)g.Be * seg * MC < 0x7fffffffLL) {
-        ChainArgs ca;
-        memset(&ca, 0, sizeof ca);
-        ca.wstream = static_cast<const float*>(sw.chain_wb); ca.vec = sw.chain_vec;
-        ca.xin_part = in.st; ca.part_bs = g.sts; ca.gn_gamma = sw.gn_g; ca.gn_beta = sw.gn_b;
-        ca.kvt = c->KVT; ca.kvt_bs = (long long)g.S * (NST * 2 * MC); ca.lo = c->band_lo; ca.hi = c->band_hi;
-        ca.y = static_cast<float*>(out.t); ca.y_bs = seg * MC; ca.stats_out = out.st; ca.stats_bs = g.sts;
-        ca.S = g.S; ca.np = g.np; ca.koff = blk * 2 * MC; ca.wmax = c->band_wmax; ca.scale = 0.17677669529663687f;
-        if (c->log_on) {
-            const double w = 2.0 * ((double)3 * MC * MC + 2.0 * FFI * MC + (double)(FFI + MC) * MC);
-            const double io = 2.0 * MC * g.T * ((double)n1 * 2 + g.Be) + 4.0 * 2 * MC * g.T * (double)n2;
-            const double fl = 2.0 * g.T * ((double)n1 * MC * MC + (double)n2 * 2 * MC * MC + (double)g.Be * (2.0 * FFI * MC + (double)(FFI + MC) * MC)) + 4.0 * n2 * MC * g.T * c->band_wmax;
-            c->stage_log.push_back({10, EPI_STORE, 6, 8, w + io, fl});
-        }
-        if (c->xclk_on && c->dbg_count < 64) ca.clk = c->clk_dev + (long long)c->dbg_count * 128;   // (said_debug_option "xgemm_clk": -DSAID_CLK_STAMPS builds)
-        if (dbg_go(c)) {
-            launch_stchain(ca, static_cast<const float*>(c->tO), static_cast<const float*>(in.t), g.T, g.Tp, seg * MC, seg * MC, shared ? g.Bc : 0, g.Bc > 0 ? g.Bc : 0, g.Be, s, true);
-            ++c->n_stchain;
-        }
+        (long long)g.Be * r.seg * MC < 0x7fffffffLL) {
+        ChainArgs ca = mkchain(c, g, sw, blk, in, out, static_cast<const float*>(sw.chain_wb));
+        ca.y = static_cast<float*>(out.t); ca.y_bs = r.seg * MC;
+        do_stchain(c, g, r, ca, c->tO, in.t, r.seg * MC, r.seg * MC, shared, true, s);
         return;
     }
-    {   // x1 = to_out(attn) + GroupNorm(x_in)   (attention.py:127, 168); under guidance also x2 of the unconditional half = x1 + c2
-        TGemmArgs t = mkx(g, tw(c, sw.t_out1, sw.tf_out1), MC, MC);
-        t.sa[0] = c->tO; t.sld[0] = MC; t.sk[0] = MC;
-        t.bias = sw.out1.bias;
-        t.res_tm = in.t; t.res_gn = 1; t.res_part = in.st; t.res_gamma = sw.gn_g; t.res_beta = sw.gn_b; t.res_eps = 1e-6f; t.gn_cpg = 6;
-        t.y_tm = c->tX1;
-        if (g.Bc > 0) { t.y2_tm = c->tX2; t.y2_row_off = 0; t.y2_add = c->c2[blk]; }
-        do_xgemm(c, t, n1, s);
-    }
-    {   // attn2: q = to_q(norm2(x1)); banded softmax over the precomputed audio K/V   (attention.py:170-191)
-        TGemmArgs t = mkx(g, tw(c, sw.t_q2, sw.tf_q2), MC, MC);
-        t.ra[0] = tm_at(c, c->tX1, x_off * seg, MC); t.rmode = 2; t.rtaps = 1;
-        t.ln_gamma = sw.l2g; t.ln_beta = sw.l2b;
-        const long long kvbs = (long long)NST * 2 * MC * g.Sp;
-        t.band_k = c->KV + (long long)(blk * 2 * MC) * g.Sp + (long long)kv_off * kvbs;
-        t.band_v = c->KV + (long long)(blk * 2 * MC + MC) * g.Sp + (long long)kv_off * kvbs;
-        t.band_kv_bs = kvbs; t.band_kv_pitch = g.Sp; t.band_lo = c->band_lo; t.band_hi = c->band_hi; t.band_wmax = c->band_wmax;
-        t.band_scale = 0.17677669529663687f;
-        t.y_tm = tm_at(c, c->tO, x_off * seg, MC);
-        do_xgemm(c, t, n2, s);
-    }
-    {   // x2 = to_out(attn2) + x1   (conditional half only under guidance: its rows are [Bc, 2 Bc) of X2)
-        TGemmArgs t = mkx(g, tw(c, sw.t_out2, sw.tf_out2), MC, MC);
-        t.sa[0] = tm_at(c, c->tO, x_off * seg, MC); t.sld[0] = MC; t.sk[0] = MC;
-        t.bias = sw.out2.bias;
-        t.res_tm = tm_at(c, c->tX1, x_off * seg, MC);
-        t.y_tm = tm_at(c, c->tX2, kv_off * seg, MC);
-        do_xgemm(c, t, n2, s);
-    }
-    {   // GEGLU: proj(norm3(x2)) -> a * gelu(gate)   (attention.py:25-32)
-        TGemmArgs t = mkx(g, tw(c, sw.t_ff1, sw.tf_ff1), 2 * FFI, MC);
-        t.ra[0] = c->tX2; t.rmode = 2; t.rtaps = 1;
-        t.ln_gamma = sw.l3g; t.ln_beta = sw.l3b;
-        t.bias = sw.t_ff1_bias; t.geglu = 1;
-        t.yb = c->tF; t.y_bs = seg * FFI; t.ldy = FFI;
-        do_xgemm(c, t, g.Be, s);
-    }
-    bool split = false;
-    if (!last && c->bf16_mode) {   // round 4: as two rgemm launches over column ranges of the folded weight (see run_resblock_tm)
-        TGemmArgs t = mkx(g, sw.t_ffproj, MC, FFI);
-        t.sa[0] = c->tF; t.sld[0] = FFI; t.sk[0] = FFI; t.w_ld = FFI + MC;
-        t.res_tm = in.t; t.y_tm = c->tX1;
-        split = rgemm_supports(t, g.Be);
-    }
-    if (split) {
-        {   // (P F2) h + x_in -> tX1 (x1 is dead by now)
-            TGemmArgs t = mkx(g, sw.t_ffproj, MC, FFI);
-            t.sa[0] = c->tF; t.sld[0] = FFI; t.sk[0] = FFI; t.w_ld = FFI + MC; t.w_k0 = 0;
-            t.res_tm = in.t;
-            t.y_tm = c->tX1;
-            do_xgemm(c, t, g.Be, s);
-        }
-        {   // + P x2 + (P b2 + bp)
-            TGemmArgs t = mkx(g, sw.t_ffproj, MC, MC);
-            t.sa[0] = c->tX2; t.sld[0] = MC; t.sk[0] = MC; t.w_ld = FFI + MC; t.w_k0 = FFI;
-            t.bias = sw.ffproj.bias;
-            t.res_tm = c->tX1;
-            t.y_tm = out.t; t.stats = out.st;
-            do_xgemm(c, t, g.Be, s);
-        }
-        return;
-    }
-    {   // proj_out o ff.net.2 over [h ; x2] + x_in   (attention.py:193, 232-234)
-        TGemmArgs t = mkx(g, tw(c, sw.t_ffproj, sw.tf_ffproj), MC, FFI + MC);
-        t.sa[0] = c->tF; t.sld[0] = FFI; t.sk[0] = FFI;
-        t.sa[1] = c->tX2; t.sld[1] = MC; t.sk[1] = MC;
-        t.bias = sw.ffproj.bias;
-        t.res_tm = in.t;
-        if (last) { t.y_cm = out.p; t.cm_bs = g.hs; t.cm_pitch = g.Tp; t.stats = out.st; }
-        else { t.y_tm = out.t; t.stats = out.st; }
-        do_xgemm(c, t, g.Be, s);
-    }
+    run_tm_tail(c, g, sw, blk, in, out, r, s, last);
 }
 
 // ---- round 3, bf16 mode at large batch when the token-major activations are off (tm_acts = 0, or beyond their 32-bit offsets): the HYBRID SpatialTransformer.  The ResBlocks and q/k/v keep round 2's kernels
@@ -494,76 +561,19 @@ void run_transformer_tm(said_ctx* c, const UGeo& g, const STW& sw, int blk, cons
 // channel-major fp32 + GroupNorm partials again for the next ResBlock.  The token-major copy of the block's input (the residual of
 // attn1.to_out and of proj_out) is a by-product of the q/k/v operand preparation.  8 launches per block instead of 9.
 void run_transformer_hybrid(said_ctx* c, const UGeo& g, const STW& sw, int blk, const ActBuf& in, const ActBuf& out, hipStream_t s, bool shared) {
-    const int n1 = shared ? g.Bc : g.Be;
-    const int n2 = g.Bc > 0 ? g.Bc : g.Be;
-    const int x_off = (g.Bc > 0 && !shared) ? g.Bc : 0;
-    const int kv_off = g.Bc > 0 ? g.Bc : 0;
-    const long long seg = tm_seg(g);
-    const int vt_rows = rup(g.T, 32);
+    const StRange r = st_range(g, shared);
     {   // q, k, v on round 2's token-major GEMM; the preparation kernel also leaves the raw input token-major (in.t)
         PrepArgs p = mkprep(g, in.p, 1, c->uPL, (long long)tg_rows(g) * MC, MC, 0);
         prep_gn(p, g, in.st, 6, 1e-6f, sw.gn_g, sw.gn_b);
         p.ln_gamma = sw.l1g; p.ln_beta = sw.l1b;
-        p.dst2 = in.t; p.dst2_bs = seg * MC; p.ldd2 = MC; p.coff2 = 0;
+        p.dst2 = in.t; p.dst2_bs = r.seg * MC; p.ldd2 = MC; p.coff2 = 0;
         do_prep(c, p, g.Be, s);   // (all samples: the second half's rows are the residual of proj_out)
         TGemmArgs t = mktg(g, c->uPL, MC, tw(c, sw.t_qkv, sw.tf_qkv), 3 * MC, MC);
-        t.qk = c->QK; t.vt = c->VT; t.v_bs = (long long)MC * g.Tp; t.qk_n = 2 * MC; t.head_dim = HD; t.rows = vt_rows; t.heads2 = 2 * HEADS; t.v_pitch = g.Tp;
-        do_tgemm(c, t, n1, s);
+        tg_qkv_out(t, c, g, r);
+        do_tgemm(c, t, r.n1, s);
     }
-    {   // softmax(q k^T * scale) v -> token-major   (attention.py:99-126)
-        AttnArgs a;
-        a.qk = c->QK; a.v = c->VT; a.o = static_cast<float*>(c->tO);
-        a.v_bstride = (long long)MC * g.Tp; a.o_bstride = seg; a.o_mode = c->bf16_mode ? 2 : 1;
-        a.pitch = g.Tp; a.T = g.T; a.heads = HEADS; a.rows = vt_rows; a.b0 = 0;
-        a.scale = 0.17677669529663687f;
-        do_attn(c, a, n1, HD, -4, s);
-    }
-    {   // x1 = to_out(attn) + GroupNorm(x_in); under guidance also x2 of the unconditional half = x1 + c2
-        TGemmArgs t = mkx(g, tw(c, sw.t_out1, sw.tf_out1), MC, MC);
-        t.sa[0] = c->tO; t.sld[0] = MC; t.sk[0] = MC;
-        t.bias = sw.out1.bias;
-        t.res_tm = in.t; t.res_gn = 1; t.res_part = in.st; t.res_gamma = sw.gn_g; t.res_beta = sw.gn_b; t.res_eps = 1e-6f; t.gn_cpg = 6;
-        t.y_tm = c->tX1;
-        if (g.Bc > 0) { t.y2_tm = c->tX2; t.y2_row_off = 0; t.y2_add = c->c2[blk]; }
-        do_xgemm(c, t, n1, s);
-    }
-    {   // attn2: q = to_q(norm2(x1)); banded softmax over the precomputed audio K/V
-        TGemmArgs t = mkx(g, tw(c, sw.t_q2, sw.tf_q2), MC, MC);
-        t.ra[0] = tm_at(c, c->tX1, x_off * seg, MC); t.rmode = 2; t.rtaps = 1;
-        t.ln_gamma = sw.l2g; t.ln_beta = sw.l2b;
-        const long long kvbs = (long long)NST * 2 * MC * g.Sp;
-        t.band_k = c->KV + (long long)(blk * 2 * MC) * g.Sp + (long long)kv_off * kvbs;
-        t.band_v = c->KV + (long long)(blk * 2 * MC + MC) * g.Sp + (long long)kv_off * kvbs;
-        t.band_kv_bs = kvbs; t.band_kv_pitch = g.Sp; t.band_lo = c->band_lo; t.band_hi = c->band_hi; t.band_wmax = c->band_wmax;
-        t.band_scale = 0.17677669529663687f;
-        t.y_tm = tm_at(c, c->tO, x_off * seg, MC);
-        do_xgemm(c, t, n2, s);
-    }
-    {   // x2 = to_out(attn2) + x1   (conditional half only under guidance: its rows are [Bc, 2 Bc) of X2)
-        TGemmArgs t = mkx(g, tw(c, sw.t_out2, sw.tf_out2), MC, MC);
-        t.sa[0] = tm_at(c, c->tO, x_off * seg, MC); t.sld[0] = MC; t.sk[0] = MC;
-        t.bias = sw.out2.bias;
-        t.res_tm = tm_at(c, c->tX1, x_off * seg, MC);
-        t.y_tm = tm_at(c, c->tX2, kv_off * seg, MC);
-        do_xgemm(c, t, n2, s);
-    }
-    {   // GEGLU: proj(norm3(x2)) -> a * gelu(gate): the GEMM normalises its operand itself
-        TGemmArgs t = mkx(g, tw(c, sw.t_ff1, sw.tf_ff1), 2 * FFI, MC);
-        t.ra[0] = c->tX2; t.rmode = 2; t.rtaps = 1;
-        t.ln_gamma = sw.l3g; t.ln_beta = sw.l3b;
-        t.bias = sw.t_ff1_bias; t.geglu = 1;
-        t.yb = c->tF; t.y_bs = seg * FFI; t.ldy = FFI;
-        do_xgemm(c, t, g.Be, s);
-    }
-    {   // proj_out o ff.net.2 over [h ; x2] + x_in -> channel-major fp32 + GroupNorm partials for the next ResBlock
-        TGemmArgs t = mkx(g, tw(c, sw.t_ffproj, sw.tf_ffproj), MC, FFI + MC);
-        t.sa[0] = c->tF; t.sld[0] = FFI; t.sk[0] = FFI;
-        t.sa[1] = c->tX2; t.sld[1] = MC; t.sk[1] = MC;
-        t.bias = sw.ffproj.bias;
-        t.res_tm = in.t;
-        t.y_cm = out.p; t.cm_bs = g.hs; t.cm_pitch = g.Tp; t.stats = out.st;
-        do_xgemm(c, t, g.Be, s);
-    }
+    do_attn(c, mk_attn(c, g, static_cast<float*>(c->tO), r.seg, c->bf16_mode ? 2 : 1), r.n1, HD, -4, s);   // softmax(q k^T * scale) v -> token-major
+    run_tm_tail(c, g, sw, blk, in, out, r, s, true);
 }
 
 // shared: guidance-shared prefix — only the first g.Bc samples are computed, and the result is ALSO written into the
@@ -578,22 +588,18 @@ void run_resblock(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, cons
         // fp32 mode: the operands reach fgemm_kernel already split (packed h | l pairs: prep_kernel's pack mode + the packed weight copies)
         const int pk = (!c->bf16_mode && sp_on(c, c->gemm_split) && c->gemm_presplit != 0 && rw.tp_conv1 && rw.tp_conv2) ? 1 : 0;
         {   // in_layers: GN -> SiLU -> conv3 + emb term   (openaimodel.py:205-225)
-            PrepArgs p = mkprep(g, in0.p, 0, c->uPA, T2 * rw.cin, rw.cin, 0);
-            p.pack = pk;
-            prep_gn(p, g, in0.st, cpg, 1e-5f, rw.g1, rw.b1);
-            if (rw.has_skip) { p.dst2 = c->uPB; p.dst2_bs = T2 * 2 * MC; p.ldd2 = 2 * MC; p.coff2 = 0; }   // raw copy for the 1x1 skip conv
-            do_prep(c, p, nb, s);
-            if (in1) {
-                PrepArgs q = mkprep(g, in1->p, 0, c->uPA, T2 * rw.cin, rw.cin, MC);
-                q.pack = pk;
-                prep_gn(q, g, in1->st, cpg, 1e-5f, rw.g1 + MC, rw.b1 + MC);
-                if (rw.has_skip) { q.dst2 = c->uPB; q.dst2_bs = T2 * 2 * MC; q.ldd2 = 2 * MC; q.coff2 = MC; }
-                do_prep(c, q, nb, s);
+            for (int off = 0; off < (in1 ? 2 * MC : MC); off += MC) {   // one preparation launch per source: its channels [off, off + 192) of the operand
+                const ActBuf& src = off ? *in1 : in0;
+                PrepArgs p = mkprep(g, src.p, 0, c->uPA, T2 * rw.cin, rw.cin, off);
+                p.pack = pk;
+                prep_gn(p, g, src.st, cpg, 1e-5f, rw.g1 + off, rw.b1 + off);
+                if (rw.has_skip) { p.dst2 = c->uPB; p.dst2_bs = T2 * 2 * MC; p.ldd2 = 2 * MC; p.coff2 = off; }   // raw copy for the 1x1 skip conv
+                do_prep(c, p, nb, s);
             }
             TGemmArgs t = mktg(g, c->uPA, rw.cin, pk ? rw.tp_conv1 : tw(c, rw.t_conv1, rw.tf_conv1), MC, 3 * rw.cin);
             t.f32_packed = pk;
             t.bias = rw.conv1.bias;
-            t.emb = c->EO + (long long)rb_index * MC * c->maxNp; t.emb_pitch = c->maxNp; t.step_ptr = g.step_ptr; t.emb_b_stride = g.emb_b_stride;
+            set_emb(t, c, g, rb_index);
             tg_cm_out(t, g, c->M);
             do_tgemm(c, t, nb, s);
         }
@@ -621,14 +627,13 @@ void run_resblock(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, cons
     {   // in_layers: GN -> SiLU -> conv3 ; + emb_layers(emb)   (openaimodel.py:205-225)
         GemmArgs a = mkargs(g.T, MC);
         a.nseg = in1 ? 2 : 1;
-        a.seg[0] = with_pw(mkseg(in0.p, g.hs, g.Tp, MC, 3, 1, 1, g.T, XF_GN_SILU, rw.conv1.w[0]), rw.conv1, 0);
-        seg_gn(a.seg[0], in0.st, g.sts, cpg, g.np, 1e-5f, rw.g1, rw.b1);
-        if (in1) {
-            a.seg[1] = with_pw(mkseg(in1->p, g.hs, g.Tp, MC, 3, 1, 1, g.T, XF_GN_SILU, rw.conv1.w[1]), rw.conv1, 1);
-            seg_gn(a.seg[1], in1->st, g.sts, cpg, g.np, 1e-5f, rw.g1 + MC, rw.b1 + MC);
+        for (int k = 0; k < a.nseg; ++k) {
+            const ActBuf& src = k ? *in1 : in0;
+            a.seg[k] = with_pw(mkseg(src.p, g.hs, g.Tp, MC, 3, 1, 1, g.T, XF_GN_SILU, rw.conv1.w[k]), rw.conv1, k);
+            seg_gn(a.seg[k], src.st, g.sts, cpg, g.np, 1e-5f, rw.g1 + k * MC, rw.b1 + k * MC);
         }
         a.bias = rw.conv1.bias;
-        a.emb = c->EO + (long long)rb_index * MC * c->maxNp; a.emb_pitch = c->maxNp; a.step_ptr = g.step_ptr; a.emb_b_stride = g.emb_b_stride;
+        set_emb(a, c, g, rb_index);
         a.y = c->M.p; a.y_bstride = g.hs; a.y_pitch = g.Tp;
         a.stats_out = c->M.st; a.stats_bstride = g.sts;
         const LaunchCfg lc = pick_unet(tt);
@@ -656,21 +661,13 @@ void run_resblock(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, cons
     }
 }
 
-// shared: guidance-shared prefix (first transformer under classifier-free guidance): self-attention and everything
-// before it run once per clip on samples [0, g.Bc).  With g.Bc > 0 the cross-attention (q projection, band softmax,
-// to_out) runs on the conditional half only — the unconditional half attends to one repeated key/value, so its
-// attn2 output is the per-channel constant c2[blk] and attn1's to_out emits its x2 = x1 + c2 directly.
+// the channel-major schedule (shared: see StRange)
 void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const ActBuf& in, const ActBuf& out, hipStream_t s,
                      bool shared = false) {
-    const int n1 = shared ? g.Bc : g.Be;          // samples through self-attention
-    const int n2 = g.Bc > 0 ? g.Bc : g.Be;        // samples through cross-attention
-    // first sample of the cross-attention range in the activations (X1, O): the conditional half, unless the prefix is
-    // shared (then X1 exists once per clip, in slots [0, Bc)); its K/V are always the conditional half's
-    const int x_off = (g.Bc > 0 && !shared) ? g.Bc : 0;
-    const int kv_off = g.Bc > 0 ? g.Bc : 0;
+    const StRange r = st_range(g, shared);
+    const int n1 = r.n1, n2 = r.n2, x_off = r.x_off, kv_off = r.kv_off;
     const long long tt1 = (long long)n1 * ((g.T + 31) / 32), tt2 = (long long)n2 * ((g.T + 31) / 32);
     const long long tt = (long long)g.Be * ((g.T + 31) / 32);
-    const int vt_rows = rup(g.T, 32);
     const long long obs = 2LL * MC * g.Tp;   // batch stride of O (shared with QK so attention uses one stride)
     const bool tg = use_tg(c, g, n1);
     if (c->bf16_mode && tg && use_tg(c, g, g.Be)) { run_transformer_hybrid(c, g, sw, blk, in, out, s, shared); return; }
@@ -693,7 +690,7 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         do_prep(c, p, n1, s);
         TGemmArgs t = mktg(g, c->uPL, MC, pk ? sw.tp_qkv : tw(c, sw.t_qkv, sw.tf_qkv), 3 * MC, MC);
         t.f32_packed = pk;
-        t.qk = c->QK; t.vt = c->VT; t.v_bs = (long long)MC * g.Tp; t.qk_n = 2 * MC; t.head_dim = HD; t.rows = vt_rows; t.heads2 = 2 * HEADS; t.v_pitch = g.Tp;
+        tg_qkv_out(t, c, g, r);
         // round 6: this GEMM's epilogue stores k and v pre-split too (as ugemm_kernel's does at small batch), for every attention shape that unpacks them: the
         // key-split ones and the four-query-tile one of large batches (each wave of which used to split all of K and V for itself)
         presplit = !c->bf16_mode && sp_on(c, c->attn_split) && c->attn_presplit != 0 && sp_on(c, c->gemm_split) &&
@@ -710,19 +707,12 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         // q and k tiles (0..11) token-major into QK [Be][2*heads][rows][32]; v tiles channel-major into VT [Be][192][Tp]
         // (y is biased so that output channel n = 384 + c lands on row c)
         a.tm_tiles = 2 * MC / 32;
-        a.vt = c->QK; a.vt_heads = 2 * HEADS; a.vt_dim = HD; a.vt_rows = vt_rows;
+        a.vt = c->QK; a.vt_heads = 2 * HEADS; a.vt_dim = HD; a.vt_rows = r.vt_rows;
         a.y = c->VT - (long long)a.tm_tiles * 32 * g.Tp; a.y_bstride = (long long)MC * g.Tp; a.y_pitch = g.Tp;
         // tiles per workgroup: the largest shape that still gives every CU a workgroup in ONE round (at Be=2, T=600:
         // NB=3 -> 228 workgroups, 27.5 -> 13.8 us per launch against NB=1's 684 workgroups in 2.7 rounds)
-        int qkv_nb = tt1 * 6 >= 192 ? 3 : (tt1 * 9 >= 192 ? 2 : 1);
-        if (tt1 * 18 <= 1024) {   // pick_unet's busiest-CU model over the 18 column tiles (19 tiles: NB 1 -> 2, 342 -> 171 workgroups)
-            double cost = 1e30;
-            for (int nb = 1; nb <= 3; ++nb) {
-                const double k = (double)((tt1 * (18 / nb) + 255) / 256) * (0.45 + nb);
-                if (k < cost - 1e-9) { cost = k; qkv_nb = nb; }
-            }
-        }
-        const LaunchCfg lc{qkv_nb, 8};
+        // pick_unet's busiest-CU model over the 18 column tiles where it applies (19 tiles: NB 1 -> 2, 342 -> 171 workgroups)
+        const LaunchCfg lc{tt1 * 18 <= 1024 ? best_nb(tt1, 18) : (tt1 * 6 >= 192 ? 3 : (tt1 * 9 >= 192 ? 2 : 1)), 8};
         // k and v pre-split for the key-split attention shapes (same rule as below), when this GEMM runs on ugemm_kernel (the only epilogue that packs)
         const bool key_split = tt1 * HEADS < 2048;
         presplit = !c->bf16_mode && sp_on(c, c->attn_split) && c->attn_presplit != 0 && key_split && !c->clk_on &&
@@ -735,11 +725,7 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
     }
     bool out1_done = false;
     {   // softmax(q k^T * scale) v   (attention.py:99-126)
-        AttnArgs a;
-        a.qk = c->QK; a.v = c->VT; a.o = c->O;
-        a.v_bstride = (long long)MC * g.Tp; a.o_bstride = obs;
-        a.pitch = g.Tp; a.T = g.T; a.heads = HEADS; a.rows = vt_rows; a.b0 = 0;
-        a.scale = 0.17677669529663687f;  // 32 ** -0.5
+        AttnArgs a = mk_attn(c, g, c->O, obs, 0);
         // waves per workgroup = ways the key tiles are split: 8 only pays while a wave would otherwise hold a single
         // tile (T <= 256); from there 4 waves with ~5 tiles each merge half as many partial states (B=1: -0.5 % per step)
         // large batches: four query tiles per workgroup sharing each K / V tile through the CU's L1 (-4), see attn.hip
@@ -752,13 +738,8 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         out1_done = a.o_mode == 1;
     }
     if (chain && !out1_done) {
-        ChainArgs ca;
-        memset(&ca, 0, sizeof ca);
-        ca.wstream = sw.chain_w; ca.vec = sw.chain_vec;
-        ca.xin_part = in.st; ca.part_bs = g.sts; ca.gn_gamma = sw.gn_g; ca.gn_beta = sw.gn_b;
-        ca.kvt = c->KVT; ca.kvt_bs = (long long)g.S * (NST * 2 * MC); ca.lo = c->band_lo; ca.hi = c->band_hi;
-        ca.y = out.p; ca.y_bs = g.hs; ca.stats_out = out.st; ca.stats_bs = g.sts;
-        ca.S = g.S; ca.np = g.np; ca.koff = blk * 2 * MC; ca.wmax = c->band_wmax; ca.scale = 0.17677669529663687f;
+        ChainArgs ca = mkchain(c, g, sw, blk, in, out, sw.chain_w);
+        ca.y = out.p; ca.y_bs = g.hs;
         // small launches: three workgroups per token tile, each streaming a third of the GEGLU / folded proj_out weights (38 workgroups on 256 CUs were bound by
         // one CU's L2 port each: 2.36 MB per workgroup) — while the launch still is one round of the chip
         ca.slices = 1;
@@ -770,19 +751,7 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         // the fp32 kernels read the block input's GroupNorm coefficients (round 6): left by the q/k/v GEMM (ugemm_kernel) or its operand preparation (prep_kernel), else made here
         if (!coef_ready && dbg_go_peek(c)) launch_gn_coef(in.st, g.sts, 6, g.np, g.T, 1e-6f, sw.gn_g, sw.gn_b, c->gn_coef, 2 * MC, n1, s);
         ca.gn_coef = c->gn_coef; ca.coef_bs = 2 * MC;
-        if (c->clk_on && c->dbg_count < 64) ca.clk = c->clk_dev + (long long)c->dbg_count * 128;
-        if (c->log_on) {
-            const double w = 4.0 * ((double)3 * MC * MC + 2.0 * FFI * MC + (double)(FFI + MC) * MC);
-            const double io = 4.0 * MC * g.T * ((double)n1 * 2 + g.Be) + 4.0 * 2 * MC * g.T * (double)n2;
-            const double fl = 2.0 * g.T * ((double)n1 * MC * MC + (double)n2 * 2 * MC * MC + (double)g.Be * (2.0 * FFI * MC + (double)(FFI + MC) * MC)) + 4.0 * n2 * MC * g.T * c->band_wmax;
-            c->stage_log.push_back({10, EPI_STORE, 6, 8, w + io, fl});
-        }
-        if (dbg_go(c)) {
-            if (trace_on()) { fprintf(stderr, "[said] stchain #%d T=%d samples=%d shared=%d\n", c->dbg_count - 1, g.T, g.Be, (int)shared); fflush(stderr); }
-            launch_stchain(ca, c->O, in.p, g.T, g.Tp, obs, g.hs, shared ? g.Bc : 0, g.Bc > 0 ? g.Bc : 0, g.Be, s, false);
-            ++c->n_stchain;
-            if (trace_on()) { hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[said]   -> %s\n", hipGetErrorString(e)); fflush(stderr); }
-        }
+        do_stchain(c, g, r, ca, c->O, in.p, obs, g.hs, shared, false, s);
         return;
     }
     if (out1_done) {   // x1 = to_out(attn) + GroupNorm(x_in) on fgemm_kernel; under guidance also x2 of the unconditional half = x1 + c2
@@ -814,11 +783,10 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         a.seg[0] = with_pw(mkseg(c->X1 + (long long)x_off * g.hs, g.hs, g.Tp, MC, 1, 0, 1, g.T, XF_LN, sw.q2.w[0]), sw.q2, 0);
         a.seg[0].ln_gamma = sw.l2g; a.seg[0].ln_beta = sw.l2b; a.seg[0].ln_eps = 1e-5f;
         a.y = c->O + (long long)x_off * obs; a.y_bstride = obs; a.y_pitch = g.Tp;
-        const long long kvbs = (long long)NST * 2 * MC * g.Sp;
-        a.band.k = c->KV + (long long)(blk * 2 * MC) * g.Sp + (long long)kv_off * kvbs;
-        a.band.v = c->KV + (long long)(blk * 2 * MC + MC) * g.Sp + (long long)kv_off * kvbs;
-        a.band.kv_bstride = kvbs; a.band.kv_pitch = g.Sp;
-        a.band.lo = c->band_lo; a.band.hi = c->band_hi; a.band.wmax = c->band_wmax; a.band.scale = 0.17677669529663687f;
+        a.band.k = band_kv(c, g, blk, kv_off, false);
+        a.band.v = band_kv(c, g, blk, kv_off, true);
+        a.band.kv_bstride = kv_bs(g); a.band.kv_pitch = g.Sp;
+        a.band.lo = c->band_lo; a.band.hi = c->band_hi; a.band.wmax = c->band_wmax; a.band.scale = ATTN_SCALE;
         if (c->band_wmax > 8) {   // windows wider than the fused epilogue's eight keys (S >> T through SAID.forward): plain q projection, then the
                                   // generic band kernel in place (misc.hip; never on SAID.inference's path)
             const BandArgs bd = a.band;
@@ -899,13 +867,7 @@ void run_unet(said_ctx* c, const UGeo& g, hipStream_t s) {
         // input_blocks.0: Conv1d(32 -> 192, k3), computed once per clip (conv_in.hip)
         // (large batches in bf16 mode: straight into the token-major bf16 layout the persistent GEMMs read — no channel-major copy, no transposition)
         conv_in_tm = c->bf16_mode && use_tm(c, g) && tm_seg(g) <= 0xffff;
-        if (dbg_go(c)) {
-            if (conv_in_tm) launch_conv_in_tm(c->x_cm, c->conv_in.w4[0], c->conv_in.bias, c->H0.t, tm_seg(g), c->H0.st, g.step_inc, g.B_lat, in_copies, g.T, g.Tp, s);
-            else launch_conv_in(c->x_cm, c->conv_in.w4[0], c->conv_in.bias, c->H0.p, c->H0.st, g.step_inc, g.B_lat, in_copies, g.T, g.Tp, MC, s);
-        }
-        if (c->log_on)
-            c->stage_log.push_back({11 /* conv_in_kernel */, EPI_STORE, 1, 4, 4.0 * ((double)MC * c->cin * 3 + (double)g.B_lat * c->cin * g.T + (double)g.Be * MC * g.T),
-                                    2.0 * g.B_lat * MC * c->cin * 3 * g.T});
+        do_conv_in(c, g, in_copies, conv_in_tm, s);
     } else {   // input_blocks.0: Conv1d(32 -> 192, k3)
         GemmArgs a = mkargs(g.T, MC);
         a.nseg = 1;
@@ -926,31 +888,29 @@ void run_unet(said_ctx* c, const UGeo& g, hipStream_t s) {
         osa_tm.x_tm = c->P.t; osa_tm.wb = c->bw_out; osa_tm.seg = tm_seg(g);
         out_tm = out_sched_tm_supports(osa_tm);
     }
-    if (use_tm(c, g)) {
-        if (!conv_in_tm) {   // conv_in's result (channel-major fp32 + GroupNorm partials) -> token-major, raw
-            PrepArgs p = mkprep(g, c->H0.p, 3, c->H0.t, (long long)tm_seg(g) * MC, MC, 0);
-            do_prep(c, p, g.Be, s);
-        }
-        run_resblock_tm(c, g, c->res[0], 0, c->H0, nullptr, c->P, s, sh);            // input_blocks.1.0
-        run_transformer_tm(c, g, c->st[0], 0, c->P, c->H1, s, sh, false);           // input_blocks.1.1
-        run_resblock_tm(c, g, c->res[1], 1, c->H1, nullptr, c->P, s, false);         // middle_block.0
-        run_transformer_tm(c, g, c->st[1], 1, c->P, c->Q, s, false, false);         // middle_block.1
-        run_resblock_tm(c, g, c->res[2], 2, c->Q, nullptr, c->P, s, false);          // middle_block.2
-        run_resblock_tm(c, g, c->res[3], 3, c->P, &c->H1, c->Q, s, false);           // output_blocks.0.0  cat([h, H1])
-        run_transformer_tm(c, g, c->st[2], 2, c->Q, c->P, s, false, false);         // output_blocks.0.1
-        run_resblock_tm(c, g, c->res[4], 4, c->P, &c->H0, c->Q, s, false);           // output_blocks.1.0  cat([h, H0])
-        run_transformer_tm(c, g, c->st[3], 3, c->Q, c->P, s, false, !out_tm);       // output_blocks.1.1 (-> channel-major for out_sched_kernel unless out_tm)
-    } else {
-    run_resblock(c, g, c->res[0], 0, c->H0, nullptr, c->P, s, sh);   // input_blocks.1.0
-    run_transformer(c, g, c->st[0], 0, c->P, c->H1, s, sh);          // input_blocks.1.1   (hs: H0, H1)
-    run_resblock(c, g, c->res[1], 1, c->H1, nullptr, c->P, s);       // middle_block.0
-    run_transformer(c, g, c->st[1], 1, c->P, c->Q, s);               // middle_block.1
-    run_resblock(c, g, c->res[2], 2, c->Q, nullptr, c->P, s);        // middle_block.2
-    run_resblock(c, g, c->res[3], 3, c->P, &c->H1, c->Q, s);         // output_blocks.0.0  cat([h, H1])
-    run_transformer(c, g, c->st[2], 2, c->Q, c->P, s);               // output_blocks.0.1
-    run_resblock(c, g, c->res[4], 4, c->P, &c->H0, c->Q, s);         // output_blocks.1.0  cat([h, H0])
-    run_transformer(c, g, c->st[3], 3, c->Q, c->P, s);               // output_blocks.1.1
+    const bool tm = use_tm(c, g);
+    if (tm && !conv_in_tm) {   // conv_in's result (channel-major fp32 + GroupNorm partials) -> token-major, raw
+        PrepArgs p = mkprep(g, c->H0.p, 3, c->H0.t, (long long)tm_seg(g) * MC, MC, 0);
+        do_prep(c, p, g.Be, s);
     }
+    auto res = [&](int i, const ActBuf& in0, const ActBuf* in1, const ActBuf& out, bool shared = false) {
+        if (tm) run_resblock_tm(c, g, c->res[i], i, in0, in1, out, s, shared);
+        else run_resblock(c, g, c->res[i], i, in0, in1, out, s, shared);
+    };
+    // last: -> channel-major for out_sched_kernel unless out_tm
+    auto st = [&](int i, const ActBuf& in, const ActBuf& out, bool shared = false, bool last = false) {
+        if (tm) run_transformer_tm(c, g, c->st[i], i, in, out, s, shared, last && !out_tm);
+        else run_transformer(c, g, c->st[i], i, in, out, s, shared);
+    };
+    res(0, c->H0, nullptr, c->P, sh);    // input_blocks.1.0
+    st(0, c->P, c->H1, sh);              // input_blocks.1.1   (hs: H0, H1)
+    res(1, c->H1, nullptr, c->P);        // middle_block.0
+    st(1, c->P, c->Q);                   // middle_block.1
+    res(2, c->Q, nullptr, c->P);         // middle_block.2
+    res(3, c->P, &c->H1, c->Q);          // output_blocks.0.0  cat([h, H1])
+    st(2, c->Q, c->P);                   // output_blocks.0.1
+    res(4, c->P, &c->H0, c->Q);          // output_blocks.1.0  cat([h, H0])
+    st(3, c->Q, c->P, false, true);      // output_blocks.1.1
     if (g.out_sched) {   // out conv + guidance + DDIM update in one kernel (out_sched.hip)
         if (dbg_go(c)) {
             if (out_tm) { launch_out_sched_tm(osa_tm, s); ++c->n_out_sched_tm; }
@@ -973,33 +933,19 @@ void run_time_embed(said_ctx* c, int n, hipStream_t s) {
     const int Np = c->maxNp;
     launch_timestep_embedding(c->ts_dev, c->freqs, c->E0, n, MC, Np, s);
     const long long tt = (n + 31) / 32;
-    {
-        GemmArgs a = mkargs(n, TE);
+    // y [N][Np] = act(W xform(x) + b) over the n columns
+    auto linear = [&](const float* x, int K, int xform, const PW& pw, int N, int act, float* y) {
+        GemmArgs a = mkargs(n, N);
         a.nseg = 1;
-        a.seg[0] = with_pw(mkseg(c->E0, 0, Np, MC, 1, 0, 1, n, XF_NONE, c->te1.w[0]), c->te1, 0);
-        a.bias = c->te1.bias; a.act = ACT_SILU;
-        a.y = c->E1; a.y_pitch = Np;
-        const LaunchCfg lc = pick_cfg(tt, TE / 32);
+        a.seg[0] = with_pw(mkseg(x, 0, Np, K, 1, 0, 1, n, xform, pw.w[0]), pw, 0);
+        a.bias = pw.bias; a.act = act;
+        a.y = y; a.y_pitch = Np;
+        const LaunchCfg lc = pick_cfg(tt, N / 32);
         launch_gemm(a, EPI_STORE, 1, lc.NB, lc.KS, s);
-    }
-    {
-        GemmArgs a = mkargs(n, TE);
-        a.nseg = 1;
-        a.seg[0] = with_pw(mkseg(c->E1, 0, Np, TE, 1, 0, 1, n, XF_NONE, c->te2.w[0]), c->te2, 0);
-        a.bias = c->te2.bias;
-        a.y = c->E2; a.y_pitch = Np;
-        const LaunchCfg lc = pick_cfg(tt, TE / 32);
-        launch_gemm(a, EPI_STORE, 1, lc.NB, lc.KS, s);
-    }
-    {
-        GemmArgs a = mkargs(n, NRES * MC);
-        a.nseg = 1;
-        a.seg[0] = with_pw(mkseg(c->E2, 0, Np, TE, 1, 0, 1, n, XF_SILU, c->emb_all.w[0]), c->emb_all, 0);
-        a.bias = c->emb_all.bias;
-        a.y = c->EO; a.y_pitch = Np;
-        const LaunchCfg lc = pick_cfg(tt, NRES * MC / 32);
-        launch_gemm(a, EPI_STORE, 1, lc.NB, lc.KS, s);
-    }
+    };
+    linear(c->E0, MC, XF_NONE, c->te1, TE, ACT_SILU, c->E1);
+    linear(c->E1, TE, XF_NONE, c->te2, TE, ACT_NONE, c->E2);
+    linear(c->E2, TE, XF_SILU, c->emb_all, NRES * MC, ACT_NONE, c->EO);
 }
 
 // cross-attention K/V of all four transformer blocks from the channel-major context (step-invariant)
