@@ -21,7 +21,7 @@ HEAD_DIM = 32
 # bf16-EMULATING mode (VERDICT r4 #3b; tests/test_gpu_round5.py): with ROUND_OPERANDS = "bf16" every matrix product that bf16 mode (said_set_precision) runs on
 # bf16 operands takes BOTH operands rounded to bf16 (round-to-nearest-even, as the kernels' conversions) and accumulates in float64; everything the kernels keep in
 # fp32 stays fp32 here: statistics, normalisations, activations, softmax, biases, residual sums, conv_in, the time embedding, the cross-attention K / V projection and
-# its banded products.  The folded (proj_out o ff.net.2) product is formed as the engine forms it (in double, then rounded once: weights.cpp make_pw "__ffproj").
+# its banded products.  The folded (proj_out o ff.net.2) product is formed as the engine forms it (in double, then rounded once: weights.cpp fold_ffproj).
 # What it cannot reproduce: the summation order, and roundings that depend on a kernel's tiling (the online softmax rounds UNNORMALISED probabilities per key
 # slice; large batches additionally store activations in bf16 between kernels: ROUND_STORES).  Agreement with the HIP bf16 path is therefore statistical, but at the
 # level of single rounding flips instead of the rounding itself.
@@ -240,7 +240,7 @@ def spatial_transformer(sd: SD, p: str, x: torch.Tensor, context: Optional[torch
     h = h.transpose(1, 2)
     h = transformer_block(sd, p + ".transformer_blocks.0", h, context)
     if ROUND_OPERANDS == "bf16":
-        # proj(F2 y + b2 + x2) + bp = (P F2) y + P x2 + (P b2 + bp): the products P F2 and P b2 + bp in double, each rounded ONCE (weights.cpp: "__ffproj")
+        # proj(F2 y + b2 + x2) + bp = (P F2) y + P x2 + (P b2 + bp): the products P F2 and P b2 + bp in double, each rounded ONCE (weights.cpp: fold_ffproj)
         y, x2 = h
         b0 = p + ".transformer_blocks.0.ff.net.2."
         P = sd[p + ".proj_out.weight"].reshape(MODEL_CH, MODEL_CH).double()

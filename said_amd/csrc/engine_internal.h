@@ -41,7 +41,7 @@ struct PW {  // packed GEMM weight (up to 2 K-segments) + bias
     float* w[2] = {nullptr, nullptr};
     float* w4[2] = {nullptr, nullptr};   // dwordx4 packing for the LDS-staged kernel
     float* w2[2] = {nullptr, nullptr};   // bf16 packing for the LDS-staged kernel's bf16 MFMA mode (same tails as w4)
-    float* ws[2] = {nullptr, nullptr};   // split-fp16 packing (kernels.h Seg::ws; same tails as w4) — UNet weights only (said_ctx::pw_split)
+    float* ws[2] = {nullptr, nullptr};   // split-fp16 packing (kernels.h Seg::ws; same tails as w4) — UNet weights only (weights.cpp pack_pw_split)
     bool ws_flat = false;                // ws in the flat step layout (GEGLU's one-tile-per-wave shape)
     float* bias = nullptr;
     int N = 0, C[2] = {0, 0}, taps = 1, nseg = 1;
@@ -195,7 +195,6 @@ struct said_ctx : HostCtx {
     int chain_coef = -1;      // fp32 small batch: stchain_kernel takes the block input's GroupNorm coefficients from the q/k/v GEMM (-1 / 1: on; 0: finalises them itself — said_debug_option "chain_coef")
     int ugemm_split = -1;     // fp32 mode: the small-batch channel-major GEMMs (ugemm_kernel) on split-fp16 operands too (gemm_lds.hip: SP; weights pre-split on the host:
                               // Seg::ws).  Default (-1) and 1: ON; 0: fp32 MFMAs (said_debug_option "ugemm_split")
-    int pw_split = 0;         // make_pw: also build the split-fp16 packing (1: per-block layout, 2: flat) — set around the UNet weights only
     long long n_rgemm = 0;
     long long n_stchain = 0;  // launches issued through stchain_kernel (said_debug_get)
     long long n_out_sched = 0, n_out_sched_tm = 0, n_sched_step = 0;   // ... through the step's last kernel: out_sched_kernel, out_sched_tm_kernel, sched_step_kernel

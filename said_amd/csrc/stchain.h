@@ -1,11 +1,11 @@
-// stchain.h — launch-level interface of the fused SpatialTransformer tail (stchain.hip); shared with engine.cpp, which packs its operands.
+// stchain.h — launch-level interface of the fused SpatialTransformer tail (stchain.hip); shared with unet_sched.cpp, which launches it, and weights.cpp, which packs its operands.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace said {
 
 constexpr int CHAIN_KW = 56;                    // key rows of the cross-attention window tile kept in LDS per 32-token tile: the tile's windows must fit
-                                                // (engine.cpp: set_band checks max(hi) - lo[t0] <= CHAIN_KW per tile, else the five-launch schedule runs)
+                                                // (unet_sched.cpp: set_band checks max(hi) - lo[t0] <= CHAIN_KW per tile, else the five-launch schedule runs)
 constexpr size_t CHAIN_STREAM_UNITS = 4 * 168 + 2 * 138 + 2 * 102;
 constexpr size_t CHAIN_STREAM_BYTES = CHAIN_STREAM_UNITS * 2048;   // 2 KB units (one k16 step: h + l fragments) of the eight waves' streams: 2,359,296 per transformer block
 // round 6, small launches: three workgroups ("slices") per token tile, each with its own stream: [to_out1 | to_q | to_out2] as above, ONE GEGLU pair per wave
@@ -21,7 +21,7 @@ constexpr int CHAIN_VEC_FLOATS = 5 * 192 + 1536;        // global: b1, bq, bo2, 
 constexpr int CHAIN_VEC_FLOATS_LDS = 4 * 192 + 1536;    // LDS: bo2 | c2 share a slot (conditional | unconditional sample)
 
 struct ChainArgs {
-    const float* wstream;    // this block's weight stream (fp16 h / l planes in each wave's consumption order: engine.cpp pack_chain_stream)
+    const float* wstream;    // this block's weight stream (fp16 h / l planes in each wave's consumption order: weight_pack.h chain_plan)
     const float* xin_part;   // GroupNorm partials of the block input [sample][tile][192][2] (mean, M2)
     const float* gn_coef;    // fp32 kernels (round 6): the block input's finalised GroupNorm (a, b) [sample][192][2] as the q/k/v GEMM or its operand preparation left them (coef_bs
                              // floats between samples) — 1 load per wave instead of 23 and no finalisation in front of the first barrier; the bf16 kernel finalises from xin_part

@@ -8,8 +8,8 @@
 // block's output:
 //   * activations never leave the CU: every GEMM's B operand is a token-major split-fp16 tile in LDS (two planes h, l of [32 tokens][K]: split_f16.h),
 //     written by the previous GEMM's epilogue straight from the accumulator registers (a lane holds 16 channels of ONE token);
-//   * weights are pre-split, pre-ordered by the host into one stream per wave in exactly the order the wave consumes them (engine.cpp:
-//     pack_chain_stream): 1 KB fragments of v_mfma_f32_32x32x16_f16 A operands, fetched with a 12-deep register ring that runs across GEMM
+//   * weights are pre-split, pre-ordered by the host into one stream per wave in exactly the order the wave consumes them (weight_pack.h:
+//     chain_plan): 1 KB fragments of v_mfma_f32_32x32x16_f16 A operands, fetched with a 12-deep register ring that runs across GEMM
 //     boundaries — the launch is bound by that stream (2.36 MB per workgroup through one CU's 64 B/clk L2 port), nothing else is on the critical path;
 //   * waves 0-5 own output columns [32 j, 32 j + 32) of the 192-wide GEMMs (= head j of the cross-attention), all eight share GEGLU's 24 (value, gate)
 //     tile pairs; LayerNorm statistics are merged across the six column owners through 1.5 KB of LDS (Chan's update, fixed order); LayerNorm affines are

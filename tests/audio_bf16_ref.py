@@ -11,7 +11,7 @@ prefix) and returns what the kernel should store:
   * dtype: torch.float64 for the reference, torch.float32 for the "same operands, fp32 arithmetic" evaluation that measures how far a correct fp32
     accumulation may sit from the float64 one.
 
-Weight layouts follow said_amd/csrc/weights.cpp: conv weights tap-major [N][taps * 512], q | k | v concatenated, the positional convolution's
+Weight layouts follow said_amd/csrc/weights.cpp and weight_pack.h: conv weights tap-major [N][taps * 512], q | k | v concatenated, the positional convolution's
 weight_norm folded in fp32 as the host folds it and split into 16 groups of 48 output rows over [tap][48 channels].
 """
 from __future__ import annotations
@@ -98,7 +98,7 @@ def conv_rows(x, k, s):
 
 
 def conv_weight_tap_major(w):
-    """(N, C, k) -> (N, k * C) (weights.cpp upload_bf16)."""
+    """(N, C, k) -> (N, k * C) (weight_pack.h tap_major)."""
     return w.permute(0, 2, 1).reshape(w.shape[0], -1)
 
 

@@ -436,7 +436,7 @@ def test_stchain_bf16_against_the_operand_rounded_evaluation_of_its_own_inputs(m
     first stchain_kernel<bf16> launch, its inputs are read back as stored (attention output and block input in bf16, the context), and the whole tail — to_out + GroupNorm'ed
     residual, LayerNorm, to_q, banded cross-attention over bf16 K / V tiles, to_out, LayerNorm, GEGLU, folded proj_out + x_in — is re-evaluated on the CPU with the
     kernel's operand roundings and ITS weights (LayerNorm affines folded into the next product's weights before rounding, proj_out o ff.net.2 formed in double:
-    weights.cpp pack_chain), float64 accumulation, everything else fp32.  The stored bf16 result must be the rounding of that evaluation almost everywhere."""
+    weights.cpp fold_ffproj, weight_pack.h fold_gamma), float64 accumulation, everything else fp32.  The stored bf16 result must be the rounding of that evaluation almost everywhere."""
     import torch.nn.functional as F
     sd = sd_parts[2]
     B, T = 16, 600
