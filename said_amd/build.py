@@ -80,11 +80,11 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
         objs.append(obj)
         if force or _stale(obj, [sp] + headers):
             # leading scalar kernel parameters arrive in SGPRs (14 is what the hardware has room for): see gemm_lds.hip, attn.hip
-            extra = ["-mllvm", "-amdgpu-kernarg-preload-count=14"] if (src in ("gemm_lds.hip", "attn.hip", "conv_in.hip", "stchain.hip", "out_sched.hip") and not os.environ.get("SAID_NO_PRELOAD")) else []
+            extra = ["-mllvm", "-amdgpu-kernarg-preload-count=14"] if src in ("gemm_lds.hip", "attn.hip", "conv_in.hip", "stchain.hip", "out_sched.hip") else []
             if src == "attn2q.hip":   # MFMA results in the vector registers although a 256-thread workgroup could have 512 registers per wave (attn2q.hip's header)
                 extra += ["-mllvm", "-amdgpu-kernarg-preload-count=14", "-mllvm", "-amdgpu-mfma-vgpr-form"]
-            extra += os.environ.get("SAID_EXTRA_DEFS", "").split()   # development: -D switches for A/B builds (scripts/gpu_ab_build.sh)
-            if src in NO_SLP and not os.environ.get("SAID_KEEP_SLP"):
+            extra += os.environ.get("SAID_EXTRA_DEFS", "").split()   # development: extra compiler flags, e.g. -DSAID_CLK_STAMPS (scripts/build_variant.sh)
+            if src in NO_SLP:
                 extra += ["-fno-slp-vectorize"]
             extra += ["-save-temps=obj"]   # keeps <name>-hip-amdgcn-amd-amdhsa-<arch>.s next to the object: the ISA the checks below read
             # the register allocator's report: a kernel that uses scratch (spills) fails the build — see check_scratch below

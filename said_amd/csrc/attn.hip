@@ -27,18 +27,11 @@
 #include "kernels.h"
 #include "split_f16.h"
 
-#ifndef SAID_ATTN_SP_ORDER
-#define SAID_ATTN_SP_ORDER 0
-#endif
-
 namespace said {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4a __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8a __attribute__((ext_vector_type(8)));
 // eight floats (two loaded quads) -> eight bf16 (round to nearest even): the v_mfma_f32_32x32x16_bf16 operand of one lane
-static __device__ __forceinline__ bf16x8a pk_bf16x8(const f32x4a a, const f32x4a b) {
-    const bf16x8a v = {(__bf16)a[0], (__bf16)a[1], (__bf16)a[2], (__bf16)a[3], (__bf16)b[0], (__bf16)b[1], (__bf16)b[2], (__bf16)b[3]};
+static __device__ __forceinline__ bf16x8 pk_bf16x8(const f32x4 a, const f32x4 b) {
+    const bf16x8 v = {(__bf16)a[0], (__bf16)a[1], (__bf16)a[2], (__bf16)a[3], (__bf16)b[0], (__bf16)b[1], (__bf16)b[2], (__bf16)b[3]};
     return v;
 }
 
@@ -70,9 +63,6 @@ template <int ND, int KS, int PM, int QW = 1>
 __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void attn_kernel(const float* pqk, const float* pv, float* po, int v_bstride, int o_bstride, int ppitch,
                                                        int pT, int pheads, int prows, float pscale, int pb0, int po_mode) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-#ifdef SAID_AB_FLOOR
-    if (pT > 0) return;
-#endif
     const AttnView a = {pqk, pv, po, v_bstride, o_bstride, ppitch, pT, pheads, prows, pscale, pb0, po_mode};
     constexpr int D = 32 * ND, NQ = D / 8;   // NQ dwordx4 per lane and operand row
     constexpr bool BF = PM == 1, SP = PM == 2 || PM == 3, PS = PM == 3;   // PS: K and V arrive split (packed h | l dwords: split_f16.h pack_split_f16)
@@ -90,43 +80,41 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
     const float* kb = a.qk + (((long long)b * 2 * H + H + h) * rows) * D + lh * (D / 2);
     const float* vb = a.v + (long long)b * a.v_bstride + (long long)(h * D + lt) * pitch + 4 * lh;
 
-    f32x4a qf[NQ];
+    f32x4 qf[NQ];
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) qf[q] = *reinterpret_cast<const f32x4a*>(qb + (long long)min(i0 + lt, rows - 1) * D + 4 * q);
+    for (int q = 0; q < NQ; ++q) qf[q] = *reinterpret_cast<const f32x4*>(qb + (long long)min(i0 + lt, rows - 1) * D + 4 * q);
 
-    bf16x8a qh[NQ / 2];   // bf16 mode: the query fragments are converted once, not once per key tile
+    bf16x8 qh[NQ / 2];   // bf16 mode: the query fragments are converted once, not once per key tile
 #pragma unroll
     for (int q = 0; q < NQ / 2; ++q) qh[q] = pk_bf16x8(qf[2 * q], qf[2 * q + 1]);
     SplitH qs[NQ / 2];    // split mode: likewise
 #pragma unroll
     for (int q = 0; q < NQ / 2; ++q) qs[q] = split_f16x8(qf[2 * q], qf[2 * q + 1]);
     float m = -1.0e30f, lsum = 0.f;
-    constexpr bool ROT = SP && SAID_ATTN_SP_ORDER == 3;   // (round 4's three-accumulator rotation: race-hunt builds only)
-    f32x16 o[ND], ox[SP ? ND : 1], oy[ROT ? ND : 1];   // ox (, oy): the split mode's cross terms v.l p.h + v.h p.l (x 2^11)
+    f32x16 o[ND], ox[SP ? ND : 1];   // ox: the split mode's cross terms v.l p.h + v.h p.l (x 2^11)
 #pragma unroll
     for (int nd = 0; nd < ND; ++nd)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             o[nd][r] = 0.f;
             if (SP) ox[SP ? nd : 0][r] = 0.f;
-            if (ROT) oy[ROT ? nd : 0][r] = 0.f;
         }
 
     const int nkt = (T + 31) >> 5;
     // K and V fragments of a key tile are fetched together and one tile ahead of the MFMAs that use them
     // (register double buffer).  Every load is unconditional — tiles past the end re-read the last tile —
     // so that the compiler can count outstanding loads exactly instead of draining them all.
-    auto load_kv = [&](int kt, f32x4a (&kf)[NQ], f32x4a (&vf)[ND][4]) {
+    auto load_kv = [&](int kt, f32x4 (&kf)[NQ], f32x4 (&vf)[ND][4]) {
         const int j0 = min(kt, nkt - 1) * 32;
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) kf[q] = *reinterpret_cast<const f32x4a*>(kb + (long long)(j0 + lt) * D + 4 * q);
+        for (int q = 0; q < NQ; ++q) kf[q] = *reinterpret_cast<const f32x4*>(kb + (long long)(j0 + lt) * D + 4 * q);
 #pragma unroll
         for (int nd = 0; nd < ND; ++nd)
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                vf[nd][q] = *reinterpret_cast<const f32x4a*>(vb + (long long)(nd * 32) * pitch + j0 + 8 * q);
+                vf[nd][q] = *reinterpret_cast<const f32x4*>(vb + (long long)(nd * 32) * pitch + j0 + 8 * q);
     };
-    auto compute = [&](int kt, const f32x4a (&kf)[NQ], const f32x4a (&vf)[ND][4]) {
+    auto compute = [&](int kt, const f32x4 (&kf)[NQ], const f32x4 (&vf)[ND][4]) {
         const int j0 = kt * 32;
         f32x16 s;
 #pragma unroll
@@ -136,36 +124,22 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
 #pragma unroll
             for (int q = 0; q < NQ / 2; ++q) ks[q] = PS ? unpack_f16x8(kf[2 * q], kf[2 * q + 1]) : split_f16x8(kf[2 * q], kf[2 * q + 1]);
             operand_fence();
-            // Two accumulators: main (k.h q.h) and cross (k.l q.h + k.h q.l, scaled by 2^-11 at the end).  Round 4 believed same-accumulator MFMAs had to be
-            // "in rotation over three accumulators" to be bit-stable beside other streams; round 5 found the actual mechanism (a packed-fp32 operand misread in
-            // OTHER kernels' waves while fp16 / bf16 MFMAs run beside them: DESIGN.md 8.4, said_amd/build.py NO_SLP) — the issue order here never mattered.
-            // SAID_ATTN_SP_ORDER (race-hunt builds, scripts/race_localise.py): 2 = idle slots between the MFMAs, the densest aggressor pattern round 4 had
-            // (every concurrent run wrong before the fix), 3 = round 4's three-accumulator rotation.
-            f32x16 sxa, sxb;
+            // Two accumulators: main (k.h q.h) and cross (k.l q.h + k.h q.l, scaled by 2^-11 at the end).  The issue order is free: what corrupted runs beside
+            // other streams was a packed-fp32 operand misread in OTHER kernels' waves while fp16 / bf16 MFMAs run beside them (said_amd/build.py NO_SLP).
+            f32x16 sxa;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { sxa[r] = 0.f; sxb[r] = 0.f; }   // (sxb: the rotation build's third accumulator)
-#if SAID_ATTN_SP_ORDER == 3
-#pragma unroll
-            for (int q = 0; q < NQ / 2; ++q) {
-                sxa = __builtin_amdgcn_mfma_f32_32x32x16_f16(ks[q].l, qs[q].h, sxa, 0, 0, 0);
-                sxb = __builtin_amdgcn_mfma_f32_32x32x16_f16(ks[q].h, qs[q].l, sxb, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(ks[q].h, qs[q].h, s, 0, 0, 0);
-            }
-#else
+            for (int r = 0; r < 16; ++r) sxa[r] = 0.f;
 #pragma unroll
             for (int q = 0; q < NQ / 2; ++q) {
                 sxa = __builtin_amdgcn_mfma_f32_32x32x16_f16(ks[q].l, qs[q].h, sxa, 0, 0, 0);
                 s = __builtin_amdgcn_mfma_f32_32x32x16_f16(ks[q].h, qs[q].h, s, 0, 0, 0);
-                if (SAID_ATTN_SP_ORDER == 2) idle_slots16();
                 sxa = __builtin_amdgcn_mfma_f32_32x32x16_f16(ks[q].h, qs[q].l, sxa, 0, 0, 0);
-                if (SAID_ATTN_SP_ORDER == 2) idle_slots16();
             }
-#endif
 #pragma unroll
-            for (int r = 0; r < 16; ++r) s[r] = fmaf(ROT ? sxa[r] + sxb[r] : sxa[r], 0x1p-11f, s[r]);
+            for (int r = 0; r < 16; ++r) s[r] = fmaf(sxa[r], 0x1p-11f, s[r]);
         }
         if constexpr (BF) {   // (converted operands first, then the fence, then the MFMAs: operand_fence)
-            bf16x8a kh[NQ / 2];
+            bf16x8 kh[NQ / 2];
 #pragma unroll
             for (int q = 0; q < NQ / 2; ++q) kh[q] = pk_bf16x8(kf[2 * q], kf[2 * q + 1]);
             operand_fence();
@@ -245,14 +219,13 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
                 for (int r = 0; r < 16; ++r) {
                     o[nd][r] *= alpha;
                     if (SP) ox[SP ? nd : 0][r] *= alpha;
-                    if (ROT) oy[ROT ? nd : 0][r] *= alpha;
                 }
         }
         }
         // keys past T: p is exactly 0, but the never-written columns of v hold whatever the workspace held (0 x NaN is NaN; in split mode 0 x inf
         // once a finite value leaves fp16's range): zeroed in the one tile that has such keys, so no result depends on memory nobody wrote
         // (scripts/poison_ws.py: every workspace byte 0xFF before the run)
-        f32x4a vz[ND][4];
+        f32x4 vz[ND][4];
 #pragma unroll
         for (int nd = 0; nd < ND; ++nd)
 #pragma unroll
@@ -269,7 +242,7 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
             SplitH psa[2], vsa[2][ND];
 #pragma unroll
             for (int m8 = 0; m8 < 2; ++m8) {
-                const f32x4a p0 = {s[8 * m8], s[8 * m8 + 1], s[8 * m8 + 2], s[8 * m8 + 3]}, p1 = {s[8 * m8 + 4], s[8 * m8 + 5], s[8 * m8 + 6], s[8 * m8 + 7]};
+                const f32x4 p0 = {s[8 * m8], s[8 * m8 + 1], s[8 * m8 + 2], s[8 * m8 + 3]}, p1 = {s[8 * m8 + 4], s[8 * m8 + 5], s[8 * m8 + 6], s[8 * m8 + 7]};
                 psa[m8] = split_f16x8(p0, p1);
 #pragma unroll
                 for (int nd = 0; nd < ND; ++nd) vsa[m8][nd] = PS ? unpack_f16x8(vz[nd][2 * m8], vz[nd][2 * m8 + 1]) : split_f16x8(vz[nd][2 * m8], vz[nd][2 * m8 + 1]);
@@ -279,24 +252,16 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
             for (int m8 = 0; m8 < 2; ++m8)
 #pragma unroll
                 for (int nd = 0; nd < ND; ++nd) {   // (two accumulators, as for the scores)
-#if SAID_ATTN_SP_ORDER == 3
-                    ox[nd] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vsa[m8][nd].l, psa[m8].h, ox[nd], 0, 0, 0);
-                    oy[ROT ? nd : 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vsa[m8][nd].h, psa[m8].l, oy[ROT ? nd : 0], 0, 0, 0);
-                    o[nd] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vsa[m8][nd].h, psa[m8].h, o[nd], 0, 0, 0);
-#else
                     ox[nd] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vsa[m8][nd].l, psa[m8].h, ox[nd], 0, 0, 0);
                     o[nd] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vsa[m8][nd].h, psa[m8].h, o[nd], 0, 0, 0);
-                    if (SAID_ATTN_SP_ORDER == 2) idle_slots16();
                     ox[nd] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vsa[m8][nd].h, psa[m8].l, ox[nd], 0, 0, 0);
-                    if (SAID_ATTN_SP_ORDER == 2) idle_slots16();
-#endif
                 }
         }
         if constexpr (BF) {
-            bf16x8a pb[2], vb8[2][ND];
+            bf16x8 pb[2], vb8[2][ND];
 #pragma unroll
             for (int m8 = 0; m8 < 2; ++m8) {
-                const f32x4a p0 = {s[8 * m8], s[8 * m8 + 1], s[8 * m8 + 2], s[8 * m8 + 3]}, p1 = {s[8 * m8 + 4], s[8 * m8 + 5], s[8 * m8 + 6], s[8 * m8 + 7]};
+                const f32x4 p0 = {s[8 * m8], s[8 * m8 + 1], s[8 * m8 + 2], s[8 * m8 + 3]}, p1 = {s[8 * m8 + 4], s[8 * m8 + 5], s[8 * m8 + 6], s[8 * m8 + 7]};
                 pb[m8] = pk_bf16x8(p0, p1);
 #pragma unroll
                 for (int nd = 0; nd < ND; ++nd) vb8[m8][nd] = pk_bf16x8(vz[nd][2 * m8], vz[nd][2 * m8 + 1]);
@@ -325,16 +290,16 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
         float* kv = smem + QW * (KS * 64 + KS * ND * 16 * 64);  // [2][K 32 x KP | V D x VP] behind the merge scratch
         const float* kg = a.qk + (((long long)b * 2 * H + H + h) * rows) * D;
         const float* vg = a.v + (long long)b * a.v_bstride + (long long)(h * D) * pitch;
-        f32x4a rk[NLD], rv[NLD];
+        f32x4 rk[NLD], rv[NLD];
         auto gload = [&](int kt) {
             const int j0 = min(kt, nkt - 1) * 32;
 #pragma unroll
             for (int i = 0; i < NLD; ++i) {
                 const int idx = tid + 64 * QW * i;
                 const int krow = idx / (D / 4), kq = idx - krow * (D / 4);     // K: 32 rows of D floats
-                rk[i] = *reinterpret_cast<const f32x4a*>(kg + (long long)(j0 + krow) * D + 4 * kq);
+                rk[i] = *reinterpret_cast<const f32x4*>(kg + (long long)(j0 + krow) * D + 4 * kq);
                 const int vrow = idx >> 3, vq = idx & 7;                      // V: D rows of 32 floats
-                rv[i] = *reinterpret_cast<const f32x4a*>(vg + (long long)vrow * pitch + j0 + 4 * vq);
+                rv[i] = *reinterpret_cast<const f32x4*>(vg + (long long)vrow * pitch + j0 + 4 * vq);
             }
         };
         auto lstore = [&](int buf) {
@@ -344,9 +309,9 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
             for (int i = 0; i < NLD; ++i) {
                 const int idx = tid + 64 * QW * i;
                 const int krow = idx / (D / 4), kq = idx - krow * (D / 4);
-                *reinterpret_cast<f32x4a*>(ks + krow * KP + 4 * kq) = rk[i];
+                *reinterpret_cast<f32x4*>(ks + krow * KP + 4 * kq) = rk[i];
                 const int vrow = idx >> 3, vq = idx & 7;
-                *reinterpret_cast<f32x4a*>(vs + vrow * VP + 4 * vq) = rv[i];
+                *reinterpret_cast<f32x4*>(vs + vrow * VP + 4 * vq) = rv[i];
             }
         };
         gload(0);
@@ -356,13 +321,13 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
             gload(kt + 1);
             const float* ks = kv + (kt & 1) * TILE_F;
             const float* vs = ks + 32 * KP;
-            f32x4a kA[NQ], vA[ND][4];
+            f32x4 kA[NQ], vA[ND][4];
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) kA[q] = *reinterpret_cast<const f32x4a*>(ks + lt * KP + lh * (D / 2) + 4 * q);
+            for (int q = 0; q < NQ; ++q) kA[q] = *reinterpret_cast<const f32x4*>(ks + lt * KP + lh * (D / 2) + 4 * q);
 #pragma unroll
             for (int nd = 0; nd < ND; ++nd)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) vA[nd][q] = *reinterpret_cast<const f32x4a*>(vs + (nd * 32 + lt) * VP + 8 * q + 4 * lh);
+                for (int q = 0; q < 4; ++q) vA[nd][q] = *reinterpret_cast<const f32x4*>(vs + (nd * 32 + lt) * VP + 8 * q + 4 * lh);
             __builtin_amdgcn_sched_barrier(0);
             compute(kt, kA, vA);
             __builtin_amdgcn_sched_barrier(0);
@@ -370,7 +335,7 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
             __syncthreads();
         }
     } else if constexpr (ND == 1) {
-        f32x4a kA[NQ], vA[ND][4], kB[NQ], vB[ND][4];
+        f32x4 kA[NQ], vA[ND][4], kB[NQ], vB[ND][4];
         // sched_barrier: without it the machine scheduler sinks the prefetch loads down between the MFMAs that consume
         // them (s_waitcnt vmcnt(0) in front of every fourth MFMA) and the double buffer hides nothing
         load_kv(w, kA, vA);
@@ -386,7 +351,7 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
             __builtin_amdgcn_sched_barrier(0);
         }
     } else {  // head_dim 64: one register buffer (a second one would spill); loads of a tile still go out together
-        f32x4a kA[NQ], vA[ND][4];
+        f32x4 kA[NQ], vA[ND][4];
         for (int kt = w; kt < nkt; kt += KS) {
             load_kv(kt, kA, vA);
             compute(kt, kA, vA);
@@ -397,7 +362,7 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
 #pragma unroll
         for (int nd = 0; nd < ND; ++nd)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) o[nd][r] = fmaf(ROT ? ox[nd][r] + oy[ROT ? nd : 0][r] : ox[nd][r], 0x1p-11f, o[nd][r]);
+            for (int r = 0; r < 16; ++r) o[nd][r] = fmaf(ox[nd][r], 0x1p-11f, o[nd][r]);
     }
 
     // ---- merge the KS partial states ----
@@ -439,12 +404,11 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
                         const float v0 = o[nd][4 * q] * invL, v1 = o[nd][4 * q + 1] * invL, v2 = o[nd][4 * q + 2] * invL, v3 = o[nd][4 * q + 3] * invL;
                         const long long off = row + nd * 32 + 8 * q + 4 * lh;
                         if (a.o_mode == 2) {
-                            typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
                             const bf16x4 ov = {(__bf16)v0, (__bf16)v1, (__bf16)v2, (__bf16)v3};
                             *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(a.o) + off) = ov;
                         } else {
-                            const f32x4a ov = {v0, v1, v2, v3};
-                            *reinterpret_cast<f32x4a*>(a.o + off) = ov;
+                            const f32x4 ov = {v0, v1, v2, v3};
+                            *reinterpret_cast<f32x4*>(a.o + off) = ov;
                         }
                     }
             }
@@ -482,14 +446,13 @@ __global__ __launch_bounds__(64 * KS * QW, (64 * KS * QW <= 256) ? 2 : 1) void a
 // QT = query tiles (= waves) per workgroup.  The key loop is one dependent chain per wave (LDS read -> MFMA -> max -> exp2 -> MFMA): with
 // four waves per workgroup and two workgroups per CU a SIMD holds two such chains and the kernel ran latency-bound (52 us); eight waves
 // put four on every SIMD and halve the K / V copies per query tile.
-typedef unsigned int u32x4b __attribute__((ext_vector_type(4)));
 template <int QT>
 __global__ __launch_bounds__(64 * QT, (QT == 10 ? 5 : (QT == 8 ? 4 : 2))) void battn_kernel(const unsigned short* __restrict__ qk, const unsigned short* __restrict__ vt, unsigned short* __restrict__ outp,
                                                        int v_bstride, int o_bstride, int pitch, int T, int heads, int rows, float scale) {
-    extern __shared__ __attribute__((aligned(16))) u32x4b bsm[];
+    extern __shared__ __attribute__((aligned(16))) u32x4 bsm[];
     const int nkt = (T + 31) >> 5, nkr = nkt * 32;
-    u32x4b* const Ks = bsm;                 // [nkr keys][4 pieces]
-    u32x4b* const Vs = bsm + nkr * 4;       // [32 channels][81 pieces]: rows one piece longer than 80 -> conflict-free 16-byte reads of 16 consecutive rows
+    u32x4* const Ks = bsm;                 // [nkr keys][4 pieces]
+    u32x4* const Vs = bsm + nkr * 4;       // [32 channels][81 pieces]: rows one piece longer than 80 -> conflict-free 16-byte reads of 16 consecutive rows
     const int tid = threadIdx.x, l = tid & 63, lt = l & 31, lh = l >> 5, w = tid >> 6;
     const int h = blockIdx.y, b = blockIdx.z, H = heads;
     constexpr int NTH = 64 * QT;
@@ -502,16 +465,16 @@ __global__ __launch_bounds__(64 * QT, (QT == 10 ? 5 : (QT == 8 ? 4 : 2))) void b
         const float rnpc = __builtin_amdgcn_rcpf((float)npc);   // idx / npc through one float multiply (exact here: idx < 2^12, npc <= 80, the + 0.5 keeps the quotient clear of
                                                                 // rounding at multiples of npc; an integer division is ~25 dependent vector instructions, four of them per lane and pass)
         for (int i = tid; i < nkr * 4; i += NTH * 4) {
-            u32x4b kv[4], vv[4];
+            u32x4 kv[4], vv[4];
             int ki[4], vi[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int idx = min(i + NTH * u, nkr * 4 - 1);
                 const int row = idx >> 2, pc = idx & 3;
-                kv[u] = *reinterpret_cast<const u32x4b*>(kg + (long long)min(row, rows - 1) * 32 + 8 * pc);
+                kv[u] = *reinterpret_cast<const u32x4*>(kg + (long long)min(row, rows - 1) * 32 + 8 * pc);
                 ki[u] = row * 4 + (pc ^ ((row >> 2) & 3));
                 const int d = (int)(((float)idx + 0.5f) * rnpc), p = idx - d * npc;        // (32 npc == 4 nkr: the same index range)
-                vv[u] = *reinterpret_cast<const u32x4b*>(vg + (long long)d * pitch + 8 * p);
+                vv[u] = *reinterpret_cast<const u32x4*>(vg + (long long)d * pitch + 8 * p);
                 vi[u] = d * 81 + p;
             }
 #pragma unroll
@@ -519,8 +482,8 @@ __global__ __launch_bounds__(64 * QT, (QT == 10 ? 5 : (QT == 8 ? 4 : 2))) void b
         }
     }
     const unsigned short* qb = qk + (((long long)b * 2 * H + h) * rows + min(i0 + lt, rows - 1)) * 32 + 8 * lh;
-    const bf16x8a q0 = __builtin_bit_cast(bf16x8a, *reinterpret_cast<const u32x4b*>(qb));
-    const bf16x8a q1 = __builtin_bit_cast(bf16x8a, *reinterpret_cast<const u32x4b*>(qb + 16));
+    const bf16x8 q0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qb));
+    const bf16x8 q1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qb + 16));
     __syncthreads();
     if (i0 >= T) return;                    // (a workgroup's spare wave: it only helped with the copy)
     // The loop below is bound by VALU ISSUE — knock-outs on the box (profiles/r04e_battn_knockouts.txt): copy 13 us, loop 30 us = 420 clocks per
@@ -534,19 +497,19 @@ __global__ __launch_bounds__(64 * QT, (QT == 10 ? 5 : (QT == 8 ? 4 : 2))) void b
     f32x16 o, ls, nref;                     // nref: every register = -(the lane's reference): the score MFMAs accumulate onto it (no 16 moves per tile)
 #pragma unroll
     for (int r = 0; r < 16; ++r) { o[r] = 0.f; ls[r] = 0.f; nref[r] = 0.f; }
-    const bf16x8a ones = {(__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f};
-    const u32x4b* kp = Ks + lt * 4;
+    const bf16x8 ones = {(__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f};
+    const u32x4* kp = Ks + lt * 4;
     const int ksw0 = lh ^ ((lt >> 2) & 3), ksw1 = (2 + lh) ^ ((lt >> 2) & 3);   // (key rows advance by 32: the swizzle term is loop-invariant)
-    const u32x4b* vp = Vs + lt * 81 + lh;
+    const u32x4* vp = Vs + lt * 81 + lh;
     // One key tile.  MASK: the tile holds keys past T (only the last tile of a T % 32 != 0 sequence) — a separate instantiation, because the
     // compiler turns a run-time `if (j0 + 32 > T)` around the 16 selects into 32 compare / select instructions executed for EVERY tile (ISA, round 4).
     auto key_tile = [&](int kt, auto mask_c) __attribute__((always_inline)) {
         constexpr bool MASK = decltype(mask_c)::value;
         const int j0 = kt * 32;
-        const bf16x8a k0 = __builtin_bit_cast(bf16x8a, kp[kt * 128 + ksw0]);
-        const bf16x8a k1 = __builtin_bit_cast(bf16x8a, kp[kt * 128 + ksw1]);
-        const bf16x8a v0 = __builtin_bit_cast(bf16x8a, vp[kt * 4]);
-        const bf16x8a v1 = __builtin_bit_cast(bf16x8a, vp[kt * 4 + 2]);
+        const bf16x8 k0 = __builtin_bit_cast(bf16x8, kp[kt * 128 + ksw0]);
+        const bf16x8 k1 = __builtin_bit_cast(bf16x8, kp[kt * 128 + ksw1]);
+        const bf16x8 v0 = __builtin_bit_cast(bf16x8, vp[kt * 4]);
+        const bf16x8 v1 = __builtin_bit_cast(bf16x8, vp[kt * 4 + 2]);
         f32x16 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0, q0, nref, 0, 0, 0);
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, q1, s, 0, 0, 0);
         if constexpr (MASK) {
@@ -572,8 +535,8 @@ __global__ __launch_bounds__(64 * QT, (QT == 10 ? 5 : (QT == 8 ? 4 : 2))) void b
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]);
-        const f32x4a p0 = {s[0], s[1], s[2], s[3]}, p1 = {s[4], s[5], s[6], s[7]}, p2 = {s[8], s[9], s[10], s[11]}, p3 = {s[12], s[13], s[14], s[15]};
-        const bf16x8a pa = pk_bf16x8(p0, p1), pb = pk_bf16x8(p2, p3);
+        const f32x4 p0 = {s[0], s[1], s[2], s[3]}, p1 = {s[4], s[5], s[6], s[7]}, p2 = {s[8], s[9], s[10], s[11]}, p3 = {s[12], s[13], s[14], s[15]};
+        const bf16x8 pa = pk_bf16x8(p0, p1), pb = pk_bf16x8(p2, p3);
         operand_fence();   // (the converted probabilities are MFMA operands: see operand_fence; never seen failing here, costs nothing measurable)
         o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v0, pa, o, 0, 0, 0);
         ls = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pa, ls, 0, 0, 0);
@@ -586,7 +549,6 @@ __global__ __launch_bounds__(64 * QT, (QT == 10 ? 5 : (QT == 8 ? 4 : 2))) void b
     const float invL = 1.0f / ls[0];        // (every row of the ones-product is the query's sum over all keys)
     const int i = i0 + lt;
     if (i < T) {   // registers 4 q .. 4 q + 3 are channels 8 q + 4 lh + (0 .. 3) of the head: four consecutive bf16 of the query's token-major row
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
         __bf16* orow = reinterpret_cast<__bf16*>(outp) + ((long long)b * o_bstride + i) * (H * 32) + h * 32 + 4 * lh;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {

@@ -8,9 +8,6 @@
 
 namespace said {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4a __attribute__((ext_vector_type(4)));
-
 // ------------------------------------------------------------------------------------------------------------------
 // attn2q_kernel (round 6) — long sequences at small batch (configs[4]: T = 1800): QT = 3 query tiles per wave.
 //
@@ -41,15 +38,15 @@ __global__ __launch_bounds__(64 * KS, 1) void attn2q_kernel(const float* pqk, co
     int i0[QT];
     // the query fragments live in LDS (a private copy per wave: no barrier): 16 registers per tile that the vector-register form of the MFMAs needs for accumulators
     constexpr int SCR = KS * 64 + KS * 16 * 64;
-    f16x8a* const qL = reinterpret_cast<f16x8a*>(smem + QT * SCR) + (w * QT * 4) * 64 + l;   // [wave][tile][q0.h, q0.l, q1.h, q1.l][64 lanes]
+    f16x8* const qL = reinterpret_cast<f16x8*>(smem + QT * SCR) + (w * QT * 4) * 64 + l;   // [wave][tile][q0.h, q0.l, q1.h, q1.l][64 lanes]
     float m[QT], lsum[QT];
     f32x16 o[QT], ox[QT];
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
         i0[t] = (blockIdx.x * QT + t) * 32;
-        f32x4a qf[NQ];
+        f32x4 qf[NQ];
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) qf[q] = *reinterpret_cast<const f32x4a*>(qb + (long long)min(i0[t] + lt, rows - 1) * D + 4 * q);
+        for (int q = 0; q < NQ; ++q) qf[q] = *reinterpret_cast<const f32x4*>(qb + (long long)min(i0[t] + lt, rows - 1) * D + 4 * q);
 #pragma unroll
         for (int q = 0; q < NQ / 2; ++q) {
             const SplitH sq = split_f16x8(qf[2 * q], qf[2 * q + 1]);
@@ -61,13 +58,13 @@ __global__ __launch_bounds__(64 * KS, 1) void attn2q_kernel(const float* pqk, co
         for (int r = 0; r < 16; ++r) { o[t][r] = 0.f; ox[t][r] = 0.f; }
     }
     const int nkt = (T + 31) >> 5;
-    f32x4a kR[NQ], vR[4];
+    f32x4 kR[NQ], vR[4];
     auto load_kv = [&](int kt) {   // (unconditional: tiles past the end re-read the last one)
         const int j0 = min(kt, nkt - 1) * 32;
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) kR[q] = *reinterpret_cast<const f32x4a*>(kb + (long long)(j0 + lt) * D + 4 * q);
+        for (int q = 0; q < NQ; ++q) kR[q] = *reinterpret_cast<const f32x4*>(kb + (long long)(j0 + lt) * D + 4 * q);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) vR[q] = *reinterpret_cast<const f32x4a*>(vb + j0 + 8 * q);
+        for (int q = 0; q < 4; ++q) vR[q] = *reinterpret_cast<const f32x4*>(vb + j0 + 8 * q);
     };
     load_kv(w);
     __builtin_amdgcn_sched_barrier(0);
@@ -95,7 +92,7 @@ __global__ __launch_bounds__(64 * KS, 1) void attn2q_kernel(const float* pqk, co
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; sxa[r] = 0.f; }
 #pragma unroll
             for (int q = 0; q < NQ / 2; ++q) {
-                const f16x8a qh = qL[((t * 2 + q) * 2 + 0) * 64], ql = qL[((t * 2 + q) * 2 + 1) * 64];
+                const f16x8 qh = qL[((t * 2 + q) * 2 + 0) * 64], ql = qL[((t * 2 + q) * 2 + 1) * 64];
                 sxa = __builtin_amdgcn_mfma_f32_32x32x16_f16(ks[q].l, qh, sxa, 0, 0, 0);
                 s = __builtin_amdgcn_mfma_f32_32x32x16_f16(ks[q].h, qh, s, 0, 0, 0);
                 sxa = __builtin_amdgcn_mfma_f32_32x32x16_f16(ks[q].h, ql, sxa, 0, 0, 0);
@@ -136,7 +133,7 @@ __global__ __launch_bounds__(64 * KS, 1) void attn2q_kernel(const float* pqk, co
             SplitH psa[2];
 #pragma unroll
             for (int m8 = 0; m8 < 2; ++m8) {
-                const f32x4a p0 = {s[8 * m8], s[8 * m8 + 1], s[8 * m8 + 2], s[8 * m8 + 3]}, p1 = {s[8 * m8 + 4], s[8 * m8 + 5], s[8 * m8 + 6], s[8 * m8 + 7]};
+                const f32x4 p0 = {s[8 * m8], s[8 * m8 + 1], s[8 * m8 + 2], s[8 * m8 + 3]}, p1 = {s[8 * m8 + 4], s[8 * m8 + 5], s[8 * m8 + 6], s[8 * m8 + 7]};
                 psa[m8] = split_f16x8(p0, p1);
             }
 #pragma unroll

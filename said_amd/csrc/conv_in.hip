@@ -14,11 +14,6 @@
 
 namespace said {
 
-typedef float f32x4c __attribute__((ext_vector_type(4)));
-static __device__ __forceinline__ f32x4c ci_bload4(rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4c, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-
 constexpr int CI_W = 4, CI_XP = 40;
 
 // TM (round 4, large batches in bf16 mode): the result goes out token-major in bf16, y = [sample][seg rows][192] (dims = seg | copies << 16, Cout = 192) —
@@ -39,20 +34,20 @@ __global__ __launch_bounds__(64 * CI_W) void conv_in_kernel(const float* x, cons
     const int sr = l >> 3, sq = l & 7;
     const rsrc_t rx = make_rsrc(x + (long long)b * 32 * pitch, 32u * (unsigned)pitch * 4u);
     const rsrc_t rw = make_rsrc(w4, (unsigned)((Cout + 31) >> 5) * 3u * 4u * 1024u);
-    const f32x4c xv = ci_bload4(rx, (sr * pitch + t0 + 4 * sq) * 4, (w * 8) * pitch * 4);
+    const f32x4 xv = bload4(rx, (sr * pitch + t0 + 4 * sq) * 4, (w * 8) * pitch * 4);
     const int hrow = l >> 1, htin = (l & 1) ? (t0 + 32) : (t0 - 1);
     const bool hok = (hrow < 8) && ((unsigned)htin < (unsigned)T);
     const float halo = bload(rx, hok ? (hrow * pitch + htin) * 4 : (int)0x80000000, (w * 8) * pitch * 4);
-    f32x4c wv[3];
+    f32x4 wv[3];
 #pragma unroll
-    for (int tap = 0; tap < 3; ++tap) wv[tap] = ci_bload4(rw, l * 16, ((tile * 3 + tap) * 4 + w) * 1024);
+    for (int tap = 0; tap < 3; ++tap) wv[tap] = bload4(rw, l * 16, ((tile * 3 + tap) * 4 + w) * 1024);
 
     float* xt = smem + w * (8 * CI_XP);
     {
-        f32x4c o;
+        f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = (t0 + 4 * sq + e < T) ? xv[e] : 0.f;
-        *reinterpret_cast<f32x4c*>(xt + sr * CI_XP + 4 + 4 * sq) = o;
+        *reinterpret_cast<f32x4*>(xt + sr * CI_XP + 4 + 4 * sq) = o;
         if (hrow < 8) xt[hrow * CI_XP + ((l & 1) ? 36 : 3)] = hok ? halo : 0.f;
     }
     f32x16 acc;
@@ -96,7 +91,6 @@ __global__ __launch_bounds__(64 * CI_W) void conv_in_kernel(const float* x, cons
         }
     }
     if constexpr (TM) {   // this thread's four values are channels tile * 32 + 8 w + 4 lh + (0 .. 3) of token t: one 8-byte store per copy
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
         const bf16x4 ov = {(__bf16)tmv[0], (__bf16)tmv[1], (__bf16)tmv[2], (__bf16)tmv[3]};
         if (t < T)
             for (int k = 0; k < copies; ++k)

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256, OCC) void fgemm_kernel(const TGemmArgs a) {
     const int nk = a.K / FBK;
     const int nk1 = (a.a2 ? a.K1 : a.K) / FBK;
 
-    f32x4t ra[ACH], rw[WCH], ra1[PF == 2 ? ACH : 1], rw1[PF == 2 ? WCH : 1];
+    f32x4 ra[ACH], rw[WCH], ra1[PF == 2 ? ACH : 1], rw1[PF == 2 ? WCH : 1];
     int aoff[ACH], a2off[ACH], woff[WCH];   // element offsets: < 2^31 (host-checked)
     int loff[ACH], lwoff[WCH];
 #pragma unroll
@@ -98,24 +98,24 @@ __global__ __launch_bounds__(256, OCC) void fgemm_kernel(const TGemmArgs a) {
         woff[i] = (n0 + row) * a.K + kp * EPC;
         lwoff[i] = BM * FLP + row * FLP + kp * EPC;
     }
-    auto gload_tile = [&](f32x4t* xa, f32x4t* xw, int kt) {
+    auto gload_tile = [&](f32x4* xa, f32x4* xw, int kt) {
         const bool first = kt < nk1;
 #pragma unroll
         for (int i = 0; i < ACH; ++i) {
             const elt_t* p = first ? A + (aoff[i] + kt * FBK) : A2 + (a2off[i] + (kt - nk1) * FBK);
-            xa[i] = *reinterpret_cast<const f32x4t*>(p);
+            xa[i] = *reinterpret_cast<const f32x4*>(p);
         }
 #pragma unroll
-        for (int i = 0; i < WCH; ++i) xw[i] = *reinterpret_cast<const f32x4t*>(W + (woff[i] + kt * FBK));
+        for (int i = 0; i < WCH; ++i) xw[i] = *reinterpret_cast<const f32x4*>(W + (woff[i] + kt * FBK));
     };
     // PK: TWO operand buffers in LDS — the next tile is parked in the other buffer before the one barrier of a k-step (the single-buffer loop pays two barriers per
     // nine MFMAs of a wave); the other variants keep one buffer (their k loop is bound elsewhere, and their occupancy is budgeted on 23-28 KB)
     constexpr int BUFE = PK ? (BM + BN) * FLP : 0;   // elements between the two buffers
-    auto lds_store = [&](const f32x4t* xa, const f32x4t* xw, int buf = 0) {
+    auto lds_store = [&](const f32x4* xa, const f32x4* xw, int buf = 0) {
 #pragma unroll
-        for (int i = 0; i < ACH; ++i) *reinterpret_cast<f32x4t*>(ldse + buf * BUFE + loff[i]) = xa[i];
+        for (int i = 0; i < ACH; ++i) *reinterpret_cast<f32x4*>(ldse + buf * BUFE + loff[i]) = xa[i];
 #pragma unroll
-        for (int i = 0; i < WCH; ++i) *reinterpret_cast<f32x4t*>(ldse + buf * BUFE + lwoff[i]) = xw[i];
+        for (int i = 0; i < WCH; ++i) *reinterpret_cast<f32x4*>(ldse + buf * BUFE + lwoff[i]) = xw[i];
     };
     f32x16 acc[NJ], accx[SP ? NJ : 1];
 #pragma unroll
@@ -136,13 +136,13 @@ __global__ __launch_bounds__(256, OCC) void fgemm_kernel(const TGemmArgs a) {
         if constexpr (SP) {
             const float* const pa2 = paS + buf * BUFE;
             const float* const pw2 = pwS + buf * BUFE;
-            const SplitH sa = PK ? unpack_f16x8(*reinterpret_cast<const f32x4s*>(pa2), *reinterpret_cast<const f32x4s*>(pa2 + 4))
-                                 : split_f16x8(*reinterpret_cast<const f32x4s*>(pa2), *reinterpret_cast<const f32x4s*>(pa2 + 4));
+            const SplitH sa = PK ? unpack_f16x8(*reinterpret_cast<const f32x4*>(pa2), *reinterpret_cast<const f32x4*>(pa2 + 4))
+                                 : split_f16x8(*reinterpret_cast<const f32x4*>(pa2), *reinterpret_cast<const f32x4*>(pa2 + 4));
             SplitH sb[NJ];
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
-                sb[j] = PK ? unpack_f16x8(*reinterpret_cast<const f32x4s*>(pw2 + j * 32 * 36), *reinterpret_cast<const f32x4s*>(pw2 + j * 32 * 36 + 4))
-                           : split_f16x8(*reinterpret_cast<const f32x4s*>(pw2 + j * 32 * 36), *reinterpret_cast<const f32x4s*>(pw2 + j * 32 * 36 + 4));
+                sb[j] = PK ? unpack_f16x8(*reinterpret_cast<const f32x4*>(pw2 + j * 32 * 36), *reinterpret_cast<const f32x4*>(pw2 + j * 32 * 36 + 4))
+                           : split_f16x8(*reinterpret_cast<const f32x4*>(pw2 + j * 32 * 36), *reinterpret_cast<const f32x4*>(pw2 + j * 32 * 36 + 4));
             operand_fence();
             // two MFMAs on the same accumulator are NJ - 1 or more apart (never back to back: attn.hip)
 #pragma unroll
@@ -164,10 +164,10 @@ __global__ __launch_bounds__(256, OCC) void fgemm_kernel(const TGemmArgs a) {
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb[j], acc[j], 0, 0, 0);
             } else {
-                const f32x4t fa = *reinterpret_cast<const f32x4t*>(pa + ks * 8);
-                f32x4t fb[NJ];
+                const f32x4 fa = *reinterpret_cast<const f32x4*>(pa + ks * 8);
+                f32x4 fb[NJ];
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) fb[j] = *reinterpret_cast<const f32x4t*>(pw + j * 32 * FLP + ks * 8);
+                for (int j = 0; j < NJ; ++j) fb[j] = *reinterpret_cast<const f32x4*>(pw + j * 32 * FLP + ks * 8);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll

@@ -3,10 +3,9 @@
 #include <cstddef>
 
 #include "kernels.h"
+#include "vec_types.h"
 
 namespace said {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 // erf by Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7 absolute (about two fp32 ulps at 1): ~12 VALU ops against ~40
@@ -25,20 +24,13 @@ __device__ __forceinline__ float gelu_f(float v) { return 0.5f * v * (1.0f + erf
 // gelu(g) = g * Phi(g),  Phi = g < 0 ? q : 1 - q,  q = (p(t) / 2) t exp(-g^2 / 2),  t = 1 / (1 + (0.3275911 / sqrt 2) |g|)  — 14 vector instructions + 2 transcendentals
 // per element against 20 + 2 for value * gelu_f(gate) (the fused tails are bound by vector-instruction issue: profiles/r06m_sq_lds_l2_counters.txt), and for g < 0 the
 // tail q keeps its own bits instead of passing through 1 - (1 - 2 q).  |error of Phi| <= 0.75e-7 as before.
-#ifndef SAID_GEGLU_FORM
-#define SAID_GEGLU_FORM 1
-#endif
 __device__ __forceinline__ float geglu_f(float val, float gate) {
-#if SAID_GEGLU_FORM == 0
-    return val * gelu_f(gate);
-#else
     const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678118654752440f, fabsf(gate), 1.0f));
     float p = fmaf(0.5f * 1.061405429f, t, 0.5f * -1.453152027f);
     p = fmaf(p, t, 0.5f * 1.421413741f); p = fmaf(p, t, 0.5f * -0.284496736f); p = fmaf(p, t, 0.5f * 0.254829592f);
     const float e = __builtin_amdgcn_exp2f((gate * gate) * (-0.5f * 1.4426950408889634f));
     const float q = (p * t) * e;
     return (val * gate) * (gate < 0.f ? q : 1.0f - q);
-#endif
 }
 
 // value * gelu(gate) for two elements at a time on packed fp32 instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: two floats per lane
@@ -46,7 +38,6 @@ __device__ __forceinline__ float geglu_f(float val, float gate) {
 // + 2 transcendentals each in the scalar form against 24 MFMAs — so the erf (gemm_common.h: Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7)
 // is evaluated pairwise and without the copysign / 1 + erf round trip:  gelu(g) = g * (x < 0 ? q : 1 - q),  q = (p(t) / 2) t exp(-x^2),
 // x = g / sqrt(2), t = 1 / (1 + 0.3275911 |x|)  (for x < 0 the scalar form computes 1 - (1 - 2q): this one keeps q's own bits).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 geglu2(f32x2 val, f32x2 gate) {
     const f32x2 x = gate * 0.70710678118654752440f;
     const f32x2 ax = {__builtin_fabsf(x[0]), __builtin_fabsf(x[1])};
@@ -144,19 +135,6 @@ __device__ __forceinline__ float cload(const float* p, long long i) { return ((c
 __device__ __forceinline__ int cload(const int* p, long long i) { return ((cint_p)(unsigned long long)p)[i]; }
 __device__ __forceinline__ float gload(const float* p, long long i) { return ((gfloat_p)(unsigned long long)p)[i]; }
 __device__ __forceinline__ void gstore(float* p, long long i, float v) { ((float __attribute__((address_space(1)))*)(unsigned long long)p)[i] = v; }
-
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-// 32-bit-offset load: byte address = base + voff (VGPR) + soff (SGPR) [+ folded immediate]; out-of-range
-// offsets (e.g. the t = -1 halo of the first row) return 0 from the hardware bounds check.
-__device__ __forceinline__ float bload(rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ float2 bload2(rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
-}
 
 // ---- cross-lane sums on DPP (1 VALU each) instead of ds_bpermute chains ----
 template <int CTRL>

@@ -8,6 +8,7 @@
 
 #include "kernels.h"
 #include "sched_math.h"
+#include "vec_types.h"
 
 namespace said {
 
@@ -542,7 +543,6 @@ __global__ __launch_bounds__(256) void conv0_apply_tm_kernel(const float* __rest
         bb[j] = coef[((long long)b * C0_C + 8 * l + j) * 2 + 1];
     }
     __syncthreads();
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     for (int f = wv; f < nf; f += 4) {
         float x[C0_K];
 #pragma unroll

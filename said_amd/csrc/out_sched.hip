@@ -17,11 +17,6 @@
 
 namespace said {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-static __device__ __forceinline__ f32x4 bload4(rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-
 constexpr int OS_KS = 8, OS_C = 192, OS_CW = OS_C / OS_KS, OS_XP = 40;
 static_assert(OS_CW == 24, "one 24-channel block per wave");
 
@@ -37,7 +32,6 @@ __global__ __launch_bounds__(64 * OS_KS) void out_sched_kernel(const float* hx, 
     constexpr int NH = CFG ? 2 : 1;
     constexpr int SPR = 34, SPP = 24;                       // SP tile: token rows (32 + 2 halo), halfs per row
     constexpr int TILE_F = SP ? (2 * SPR * SPP) / 2 : OS_CW * OS_XP;   // floats of one half's staging tile
-    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
     const int tid = threadIdx.x, l = tid & 63, lt = l & 31, lh = l >> 5;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int t0 = blockIdx.x * 32, b = blockIdx.y;
@@ -296,8 +290,6 @@ void launch_out_sched(const OutSchedArgs& a, hipStream_t s) {
 // (rgemm's 400-byte rows), the convolution as a TRANSPOSED product D[out channel][token] on v_mfma_f32_32x32x16_bf16 — lane == token, as
 // out_sched_kernel's epilogue wants it — with the 36 k-steps split over the four waves (fixed-order LDS reduction), both samples sharing every
 // weight fragment, then exactly out_sched_kernel's epilogue (sched_math.h: same explicitly rounded op sequence).
-typedef __bf16 os_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int os_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int OT_AP = 200, OT_ROWS = 34, OT_NP = 4;   // tile row pitch (elements), rows, 16-byte pieces per thread and sample (34 x 24 = 816 <= 4 x 256)
 
 template <bool CFG, int SF>
@@ -314,7 +306,7 @@ __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a)
     const unsigned short* xb = reinterpret_cast<const unsigned short*>(a.x_tm);
 
     // ---- requests: source rows (raw), epilogue operands, weight fragments; then the statistics partials
-    os_u32x4 raw[NH][OT_NP];
+    u32x4 raw[NH][OT_NP];
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
         const long long sb = b + h * a.B;
@@ -323,7 +315,7 @@ __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a)
             const int idx = min(tid + 256 * i, OT_ROWS * 24 - 1);
             const int row = idx / 24, pc = idx - row * 24;
             const int tt = min(max(t0 + row - 1, 0), T - 1);
-            raw[h][i] = *reinterpret_cast<const os_u32x4*>(xb + ((sb * a.seg + tt) * 192 + 8 * pc));
+            raw[h][i] = *reinterpret_cast<const u32x4*>(xb + ((sb * a.seg + tt) * 192 + 8 * pc));
         }
     }
     const int step = *a.step_ptr;
@@ -358,11 +350,11 @@ __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a)
         e_bias[j] = a.bias[n < a.Cout ? n : 0];
     }
     // this wave's nine k16 steps of the [32][576] weight matrix (row = output channel, k = tap * 192 + channel); rows past Cout: row 0 again (unused)
-    os_bf16x8 wf[9];
+    bf16x8 wf[9];
     {
         const unsigned short* wb = reinterpret_cast<const unsigned short*>(a.wb) + (long long)(lt < a.Cout ? lt : 0) * 576 + 8 * lh;
 #pragma unroll
-        for (int i = 0; i < 9; ++i) wf[i] = __builtin_bit_cast(os_bf16x8, *reinterpret_cast<const os_u32x4*>(wb + 16 * (9 * w + i)));
+        for (int i = 0; i < 9; ++i) wf[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(wb + 16 * (9 * w + i)));
     }
     // ---- GroupNorm tables: wave w = channels [48 w, 48 w + 48) of each sample
     const GnP gp = {OS_C / 32, a.gn_nparts, T, 1e-5f, a.gn_gamma, a.gn_beta, OS_C};
@@ -392,17 +384,16 @@ __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a)
                 const int row = idx / 24, pc = idx - row * 24;
                 const int tt = t0 + row - 1;
                 const bool valid = tt >= 0 && tt < T;
-                os_u32x4 o;
+                u32x4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float2 g0 = cG[8 * pc + 2 * e], g1 = cG[8 * pc + 2 * e + 1];
                     const float x0 = silu_f(fmaf(__builtin_bit_cast(float, raw[h][i][e] << 16), g0.x, g0.y));
                     const float x1 = silu_f(fmaf(__builtin_bit_cast(float, raw[h][i][e] & 0xffff0000u), g1.x, g1.y));
-                    typedef __bf16 os_bf16x2 __attribute__((ext_vector_type(2)));
-                    const os_bf16x2 p2 = {(__bf16)x0, (__bf16)x1};
+                    const bf16x2 p2 = {(__bf16)x0, (__bf16)x1};
                     o[e] = valid ? __builtin_bit_cast(unsigned, p2) : 0u;
                 }
-                *reinterpret_cast<os_u32x4*>(At + (h * OT_ROWS + row) * OT_AP + 8 * pc) = o;
+                *reinterpret_cast<u32x4*>(At + (h * OT_ROWS + row) * OT_AP + 8 * pc) = o;
             }
         }
     }
@@ -418,7 +409,7 @@ __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a)
         const int sidx = 9 * w + i, tap = sidx / 12, c0 = (sidx - 12 * tap) * 16;
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
-            const os_bf16x8 fa = __builtin_bit_cast(os_bf16x8, *reinterpret_cast<const os_u32x4*>(At + (h * OT_ROWS + lt + tap) * OT_AP + c0 + 8 * lh));
+            const bf16x8 fa = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(At + (h * OT_ROWS + lt + tap) * OT_AP + c0 + 8 * lh));
             acc[h] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], fa, acc[h], 0, 0, 0);
         }
     }

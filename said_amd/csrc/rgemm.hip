@@ -42,15 +42,10 @@
 
 namespace said {
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 // Cache policy of the result stores (buffer_store aux bits: 1 = sc0, 2 = nt, 16 = sc1).  sc1 = agent scope: the 16-byte result stores are
 // written THROUGH the XCD's L2 while the launch runs instead of leaving 15 - 59 MB dirty for the write-back at its end, behind which the next
 // launch's first loads queue: 1.243 -> 1.227 / 1.263 -> 1.237 ms per step on two boxes (plain / sc1; nt: 1.266; profiles/r04g_rgemm_ab.txt).
-#ifndef SAID_RG_ST_AUX
-#define SAID_RG_ST_AUX 16
-#endif
+constexpr int RG_ST_AUX = 16;
 constexpr int RG_AP = 200;                        // A tile row pitch in elements (192 + 8: 400 bytes)
 constexpr int RG_AROWS = 34;                      // 32 tokens + 2 halo
 constexpr int RG_A_ELEMS = RG_AROWS * RG_AP;
@@ -277,8 +272,8 @@ __global__ __launch_bounds__(512, 2) void rgemm_kernel(const TGemmArgs a) {
                             // v (rows = channels, columns = tokens): the stored token order inside a block of 16 is [0-3, 8-11, 4-7, 12-15], so the
                             // eight stored positions 8 ec .. 8 ec + 7 are tokens x0 .. x0 + 3 and x0 + 8 .. x0 + 11
                             const int x0 = ct == 2 ? 16 * (ec >> 1) + 4 * (ec & 1) : 8 * ec, x1 = ct == 2 ? x0 + 8 : x0 + 4;
-                            f32x4t v0 = *reinterpret_cast<const f32x4t*>(ws + row * 36 + x0);
-                            f32x4t v1 = *reinterpret_cast<const f32x4t*>(ws + row * 36 + x1);
+                            f32x4 v0 = *reinterpret_cast<const f32x4*>(ws + row * 36 + x0);
+                            f32x4 v1 = *reinterpret_cast<const f32x4*>(ws + row * 36 + x1);
                             int off;
                             if (ct < 2) {
                                 off = row < nrows ? (((b * a.heads2 + ct * 6 + j) * a.rows + t0 + row) * 32 + 8 * ec) * 2 : (int)0x80000000;
@@ -289,13 +284,13 @@ __global__ __launch_bounds__(512, 2) void rgemm_kernel(const TGemmArgs a) {
                             }
                             if (ct == 0) { v0 *= a.q_scale; v1 *= a.q_scale; }
                             const u32x4 ov = {pack_bf16(v0[0], v0[1]), pack_bf16(v0[2], v0[3]), pack_bf16(v1[0], v1[1]), pack_bf16(v1[2], v1[3])};
-                            __builtin_amdgcn_raw_buffer_store_b128(ov, ct < 2 ? rq : rv, off, 0, SAID_RG_ST_AUX);
+                            __builtin_amdgcn_raw_buffer_store_b128(ov, ct < 2 ? rq : rv, off, 0, RG_ST_AUX);
                         }
                     } else {
 #pragma unroll
                     for (int p4 = 0; p4 < 4; ++p4) {
                         const int row = 8 * p4 + prow;
-                        f32x4t v = *reinterpret_cast<const f32x4t*>(ws + row * 36 + pc4);
+                        f32x4 v = *reinterpret_cast<const f32x4*>(ws + row * 36 + pc4);
                         int off;
                         if (ct < 2) {
                             off = row < nrows ? (((b * a.heads2 + ct * 6 + j) * a.rows + t0 + row) * 32 + pc4) * 4 : (int)0x80000000;
@@ -304,7 +299,7 @@ __global__ __launch_bounds__(512, 2) void rgemm_kernel(const TGemmArgs a) {
                             for (int e = 0; e < 4; ++e) v[e] = pc4 + e < nrows ? v[e] : 0.f;
                             off = (int)(((long long)b * a.v_bs + (long long)(32 * j + row) * a.v_pitch + t0 + pc4) * 4);
                         }
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ct < 2 ? rq : rv, off, 0, SAID_RG_ST_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ct < 2 ? rq : rv, off, 0, RG_ST_AUX);
                     }
                     }
                     __builtin_amdgcn_wave_barrier();
@@ -322,10 +317,10 @@ __global__ __launch_bounds__(512, 2) void rgemm_kernel(const TGemmArgs a) {
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const int row = 16 * q + er;
-                    const f32x4t v0 = *reinterpret_cast<const f32x4t*>(ws + row * 36 + 8 * ec);
-                    const f32x4t v1 = *reinterpret_cast<const f32x4t*>(ws + row * 36 + 8 * ec + 4);
+                    const f32x4 v0 = *reinterpret_cast<const f32x4*>(ws + row * 36 + 8 * ec);
+                    const f32x4 v1 = *reinterpret_cast<const f32x4*>(ws + row * 36 + 8 * ec + 4);
                     const u32x4 ov = {pack_bf16(v0[0], v0[1]), pack_bf16(v0[2], v0[3]), pack_bf16(v1[0], v1[1]), pack_bf16(v1[2], v1[3])};
-                    __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y, row < nrows ? ((R0 + row) * a.ldy + c0 + 8 * ec) * 2 : (int)0x80000000, 0, SAID_RG_ST_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y, row < nrows ? ((R0 + row) * a.ldy + c0 + 8 * ec) * 2 : (int)0x80000000, 0, RG_ST_AUX);
                 }
                 __builtin_amdgcn_wave_barrier();
             } else if constexpr (EK == 4) {
@@ -342,8 +337,8 @@ __global__ __launch_bounds__(512, 2) void rgemm_kernel(const TGemmArgs a) {
                 for (int q = 0; q < 2; ++q) {
                     const int row = 16 * q + er;
                     const bool on = row < nrows;
-                    const f32x4t v0 = *reinterpret_cast<const f32x4t*>(ws + row * 36 + 8 * ec);
-                    const f32x4t v1 = *reinterpret_cast<const f32x4t*>(ws + row * 36 + 8 * ec + 4);
+                    const f32x4 v0 = *reinterpret_cast<const f32x4*>(ws + row * 36 + 8 * ec);
+                    const f32x4 v1 = *reinterpret_cast<const f32x4*>(ws + row * 36 + 8 * ec + 4);
                     float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                     if constexpr (RES != 0) {
 #pragma unroll
@@ -355,18 +350,18 @@ __global__ __launch_bounds__(512, 2) void rgemm_kernel(const TGemmArgs a) {
                     }
                     const u32x4 ov = {pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])};
                     const int off = on ? ((R0 + row) * a.ldy + 32 * j + 8 * ec) * 2 : (int)0x80000000;   // (out of range: the hardware drops the store)
-                    __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y, off, 0, SAID_RG_ST_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y, off, 0, RG_ST_AUX);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { v[2 * e] = bf_lo(ov[e]); v[2 * e + 1] = bf_hi(ov[e]); }   // the stored values
                     if constexpr (DUP) {
                         const u32x4 o2 = {pack_bf16(v[0] + add2[0], v[1] + add2[1]), pack_bf16(v[2] + add2[2], v[3] + add2[3]),
                                           pack_bf16(v[4] + add2[4], v[5] + add2[5]), pack_bf16(v[6] + add2[6], v[7] + add2[7])};
-                        __builtin_amdgcn_raw_buffer_store_b128(o2, rsrc_y2, on ? off + (int)(a.y2_row_off * a.ldy * 2) : (int)0x80000000, 0, SAID_RG_ST_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b128(o2, rsrc_y2, on ? off + (int)(a.y2_row_off * a.ldy * 2) : (int)0x80000000, 0, RG_ST_AUX);
                     }
                     if constexpr (STATS) {   // back into the scratch for the column sums (lane == column again)
-                        const f32x4t w0 = {v[0], v[1], v[2], v[3]}, w1 = {v[4], v[5], v[6], v[7]};
-                        *reinterpret_cast<f32x4t*>(ws + row * 36 + 8 * ec) = w0;
-                        *reinterpret_cast<f32x4t*>(ws + row * 36 + 8 * ec + 4) = w1;
+                        const f32x4 w0 = {v[0], v[1], v[2], v[3]}, w1 = {v[4], v[5], v[6], v[7]};
+                        *reinterpret_cast<f32x4*>(ws + row * 36 + 8 * ec) = w0;
+                        *reinterpret_cast<f32x4*>(ws + row * 36 + 8 * ec + 4) = w1;
                     }
                 }
                 if constexpr (STATS) {

@@ -24,15 +24,9 @@
 #include "gemm_common.h"
 #include "split_f16.h"
 #include "stchain.h"
-#ifndef SAID_GEGLU_BIAS_INIT
-#define SAID_GEGLU_BIAS_INIT 1
-#endif
 
 namespace said {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef const f32x4 __attribute__((address_space(1))) * gf4_p;
 
 // ---- LDS carve (bytes) ----
@@ -111,9 +105,6 @@ __device__ __forceinline__ void sfor(F&& f) {
 template <int NR> struct Ring { f32x4 h[NR], l[NR]; };
 struct WStream { rsrc_t r; int vo; };   // the wave's stream, lane * 16
 // BF (bf16 mode, large batches): ONE plane everywhere — weights and activations rounded to bf16 (RNE), v_mfma_f32_32x32x16_bf16, a unit is 1 KB
-typedef __bf16 bf16x8c __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4c __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2c __attribute__((ext_vector_type(2)));
 template <int MODE, bool BF, int SC, int NR, int Q>
 __device__ __forceinline__ void ring_issue(Ring<NR>& R, const WStream& wp) {
     if constexpr (Q < n_units<MODE, SC>()) {
@@ -150,7 +141,7 @@ __device__ __forceinline__ void gemm_run(Ring<NR>& R, const WStream& wp, const c
             if constexpr (!BF) nl = *reinterpret_cast<const f16x8*>(bh + pl + 32 * (s + 1));
         }
         if constexpr (BF) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8c, R.h[(Q0 + s) % NR]), __builtin_bit_cast(bf16x8c, xh), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, R.h[(Q0 + s) % NR]), __builtin_bit_cast(bf16x8, xh), acc, 0, 0, 0);
         } else {
             const f16x8 wh = __builtin_bit_cast(f16x8, R.h[(Q0 + s) % NR]), wl = __builtin_bit_cast(f16x8, R.l[(Q0 + s) % NR]);
             accx = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, accx, 0, 0, 0);
@@ -177,8 +168,8 @@ __device__ __forceinline__ void geglu_run(Ring<NR>& R, const WStream& wp, const 
         }
         constexpr int qv = Q0 + 2 * s, qg = Q0 + 2 * s + 1;
         if constexpr (BF) {
-            av = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8c, R.h[qv % NR]), __builtin_bit_cast(bf16x8c, xh), av, 0, 0, 0);
-            ag = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8c, R.h[qg % NR]), __builtin_bit_cast(bf16x8c, xh), ag, 0, 0, 0);
+            av = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, R.h[qv % NR]), __builtin_bit_cast(bf16x8, xh), av, 0, 0, 0);
+            ag = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, R.h[qg % NR]), __builtin_bit_cast(bf16x8, xh), ag, 0, 0, 0);
         } else {
             const f16x8 vh = __builtin_bit_cast(f16x8, R.h[qv % NR]), vl = __builtin_bit_cast(f16x8, R.l[qv % NR]);
             const f16x8 gh = __builtin_bit_cast(f16x8, R.h[qg % NR]), gl = __builtin_bit_cast(f16x8, R.l[qg % NR]);
@@ -213,10 +204,10 @@ __device__ __forceinline__ void put_split(char* plane_h, int pl, int row_bytes, 
     for (int m = 0; m < 4; ++m) {
         char* p = plane_h + row_bytes + (col0 + 8 * m) * 2;
         if constexpr (BF) {
-            bf16x4c h;
+            bf16x4 h;
 #pragma unroll
             for (int i = 0; i < 4; ++i) h[i] = (__bf16)v[4 * m + i];
-            *reinterpret_cast<bf16x4c*>(p) = h;
+            *reinterpret_cast<bf16x4*>(p) = h;
         } else {
             f16x4 h, lo;
             split_f16x4(v[4 * m], v[4 * m + 1], v[4 * m + 2], v[4 * m + 3], h, lo);
@@ -342,12 +333,10 @@ __device__ __forceinline__ void chain_body(const ChainHdr& hd, const ChainArgs& 
                 __bf16* kt = reinterpret_cast<__bf16*>(smem + CH_R0);
                 kv_walk(i0, [&](int i, int k, int p8) {
                     const int e = (p8 < 24 ? 0 : CHAIN_KW * CH_KP) + k * CH_KP + 8 * (p8 < 24 ? p8 : p8 - 24);   // (392-byte rows: two 8-byte stores)
-                    typedef unsigned int u32x2k __attribute__((ext_vector_type(2)));
-                    typedef unsigned int u32x4k __attribute__((ext_vector_type(4)));
-                    const u32x4k v = __builtin_bit_cast(u32x4k, kvv[i]);
-                    const u32x2k v0 = {v[0], v[1]}, v1 = {v[2], v[3]};
-                    *reinterpret_cast<u32x2k*>(kt + e) = v0;
-                    *reinterpret_cast<u32x2k*>(kt + e + 4) = v1;
+                    const u32x4 v = __builtin_bit_cast(u32x4, kvv[i]);
+                    const u32x2 v0 = {v[0], v[1]}, v1 = {v[2], v[3]};
+                    *reinterpret_cast<u32x2*>(kt + e) = v0;
+                    *reinterpret_cast<u32x2*>(kt + e + 4) = v1;
                 });
             };
             if (!uncond) {
@@ -391,10 +380,10 @@ __device__ __forceinline__ void chain_body(const ChainHdr& hd, const ChainArgs& 
                 kv_walk(i0, [&](int i, int k, int p4) {
                     const int e = (p4 < 48 ? 0 : CHAIN_KW * CH_KP) + k * CH_KP + 4 * (p4 < 48 ? p4 : p4 - 48);
                     if constexpr (BF) {   // bf16 tiles (RNE)
-                        bf16x4c b;
+                        bf16x4 b;
     #pragma unroll
                         for (int q = 0; q < 4; ++q) b[q] = (__bf16)kvv[i][q];
-                        *reinterpret_cast<bf16x4c*>(reinterpret_cast<__bf16*>(kt) + e) = b;
+                        *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(kt) + e) = b;
                     } else {
                         *reinterpret_cast<f32x4*>(kt + e) = kvv[i];
                     }
@@ -558,7 +547,7 @@ __device__ __forceinline__ void chain_body(const ChainHdr& hd, const ChainArgs& 
             if constexpr (BF) {
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
-                    const bf16x4c xb = *reinterpret_cast<const bf16x4c*>(r2h + wrowA + (col0 + 8 * m) * 2);
+                    const bf16x4 xb = *reinterpret_cast<const bf16x4*>(r2h + wrowA + (col0 + 8 * m) * 2);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) xr[4 * m + i] = (float)xb[i];
                 }
@@ -611,7 +600,7 @@ __device__ __forceinline__ void chain_body(const ChainHdr& hd, const ChainArgs& 
                 const float* kt = reinterpret_cast<const float*>(smem + CH_R0);
                 auto kv4 = [&](int e) -> f32x4 {   // four consecutive elements of the window tiles (element index from the K tile's start; BF: bf16 tiles)
                     if constexpr (BF) {
-                        const bf16x4c b = *reinterpret_cast<const bf16x4c*>(reinterpret_cast<const __bf16*>(kt) + e);
+                        const bf16x4 b = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const __bf16*>(kt) + e);
                         f32x4 o;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) o[q] = (float)b[q];
@@ -699,21 +688,15 @@ __device__ __forceinline__ void chain_body(const ChainHdr& hd, const ChainArgs& 
         auto lpair = [&](int pi) { return w + U::LSTEP * pi + U::L0; };   // local pair (= column tile of the product plane) of this wave's pair pi
         auto epi_piece = [&](int p, int m) {   // channels 32 p + 4 lh + 8 m .. + 3 of the token: bias, gelu, product, split, 8 bytes per plane
             float hv[4];
-#if SAID_GEGLU_BIAS_INIT   // (the pair's accumulators started from the bias: below)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) hv[i] = geglu_f(pv[4 * m + i], pg[4 * m + i]);
-#else
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(bff + 32 * (gp0 + p) + 4 * lh + 8 * m), bg = *reinterpret_cast<const f32x4*>(bff + 768 + 32 * (gp0 + p) + 4 * lh + 8 * m);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) hv[i] = geglu_f(pv[4 * m + i] + bv[i], pg[4 * m + i] + bg[i]);
-#endif
+            for (int i = 0; i < 4; ++i) hv[i] = geglu_f(pv[4 * m + i], pg[4 * m + i]);   // (the pair's accumulators started from the bias: below)
             (void)p;
             char* pp = hh + wrowH + (32 * p + 4 * lh + 8 * m) * 2;
             if constexpr (BF) {
-                bf16x4c h;
+                bf16x4 h;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) h[i] = (__bf16)hv[i];
-                *reinterpret_cast<bf16x4c*>(pp) = h;
+                *reinterpret_cast<bf16x4*>(pp) = h;
             } else {
                 f16x4 h, lo;
                 split_f16x4(hv[0], hv[1], hv[2], hv[3], h, lo);
@@ -725,7 +708,6 @@ __device__ __forceinline__ void chain_body(const ChainHdr& hd, const ChainArgs& 
             constexpr int pi = decltype(pc)::value;
             f32x16 av, avx, ag, agx;
             zero16(avx); zero16(agx);
-#if SAID_GEGLU_BIAS_INIT
             // the value and gate sums start from ff.net.0's bias (a lane's 16 channels of the pair's tiles: four 16-byte LDS reads each) instead of from zero: two additions per
             // element leave the epilogue, which is what the fused tails' waves are short of (vector-instruction issue: profiles/r06m_sq_lds_l2_counters.txt)
 #pragma unroll
@@ -734,9 +716,6 @@ __device__ __forceinline__ void chain_body(const ChainHdr& hd, const ChainArgs& 
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { av[4 * m + i] = bv[i]; ag[4 * m + i] = bg[i]; }
             }
-#else
-            zero16(av); zero16(ag);
-#endif
             geglu_run<MODE, BF, SC, NR, QG + 24 * pi>(R, wp, r1h + browA, CH_APL, av, avx, ag, agx, [&](auto sc) {
                 constexpr int s = decltype(sc)::value;
                 if constexpr (!BF && pi > 0 && s % 3 == 1) epi_piece(lpair(pi - 1), s / 3);
@@ -783,7 +762,7 @@ __device__ __forceinline__ void chain_body(const ChainHdr& hd, const ChainArgs& 
         if constexpr (BF) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                const bf16x4c xb = __builtin_bit_cast(bf16x4c, __builtin_amdgcn_raw_buffer_load_b64(rxin, xvo + 16 * m, 0, 0));
+                const bf16x4 xb = __builtin_bit_cast(bf16x4, __builtin_amdgcn_raw_buffer_load_b64(rxin, xvo + 16 * m, 0, 0));
 #pragma unroll
                 for (int i = 0; i < 4; ++i) xr[4 * m + i] = (float)xb[i];
             }
@@ -854,13 +833,13 @@ __device__ __forceinline__ void chain_body(const ChainHdr& hd, const ChainArgs& 
         if constexpr (BF) {   // token-major bf16 result [sample][row][192]; the statistics are those of the STORED (rounded) values
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                bf16x4c yb;
+                bf16x4 yb;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     yb[i] = (__bf16)(y[4 * m + i] + bp[4 * m + i] + xr[4 * m + i]);
                     y[4 * m + i] = (float)yb[i];
                 }
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2c, yb), ryo, xvo + 16 * m, 0, 0);   // (rows past T: out of range, dropped)
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, yb), ryo, xvo + 16 * m, 0, 0);   // (rows past T: out of range, dropped)
             }
         } else {
 #pragma unroll
@@ -891,9 +870,6 @@ template <bool BF, int NS>
 __global__ __launch_bounds__(512, BF ? 4 : 1) void stchain_kernel(const float* h_w, const float* h_o, const float* h_x, const int* h_lo, int h_T, int h_pitch, int h_obs, int h_xbs, int h_inmod,
                                                          int h_nunc_wmax, const ChainArgs a) {
     extern __shared__ __attribute__((aligned(16))) char csmem[];
-#ifdef SAID_AB_FLOOR
-    if (h_T > 0) return;
-#endif
     const ChainHdr hd = {h_w, h_o, h_x, h_lo, h_T, h_pitch, h_obs, h_xbs, h_inmod, h_nunc_wmax & 0xffffff, (int)((unsigned)h_nunc_wmax >> 24)};
     const int tid = threadIdx.x, l = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);

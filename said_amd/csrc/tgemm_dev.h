@@ -3,12 +3,9 @@
 #include "gemm_common.h"
 #include "tgemm.h"
 #include "split_f16.h"
+#include "vec_types.h"
 
 namespace said {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4t __attribute__((ext_vector_type(4)));
 
 // XCD-aware tile order: blockIdx.x -> (n tile, global M-tile index over the batch).  The hardware places consecutive workgroup ids on consecutive XCDs (id % 8), each
 // with its own L2.  The NT = N / BN workgroups that share an A tile are given consecutive slots of ONE XCD (n tile fastest), so the A tile is
@@ -169,7 +166,6 @@ __device__ __forceinline__ void tg_epilogue(const TGemmArgs& a, f32x16 (&acc)[NJ
     } else if (P_BF && a.yb && !a.yf && !a.qk && !a.res && !n_store) {
         // ---- phase 2a', bf16-only token-major destination (GEGLU product, the audio encoder's conv / FFN activations): lane -> 8
         // consecutive columns = one 16-byte store (8-byte stores run at 0.54-0.70x the 16-byte rate)
-        typedef __bf16 bf16x8s __attribute__((ext_vector_type(8)));
         const int lanes_per_row = cw / 8;                // 16, 12, 8 or 4
         const int rows_pp = 64 / lanes_per_row;          // 4, 5 (60 lanes active), 8 or 16
         const int rr = l / lanes_per_row, cq = l - rr * lanes_per_row;
@@ -177,10 +173,10 @@ __device__ __forceinline__ void tg_epilogue(const TGemmArgs& a, f32x16 (&acc)[NJ
         for (int r0 = r_lo; r0 < r_hi; r0 += rows_pp) {
             const int row = r0 + rr;
             if (!lane_on || row >= r_hi) continue;
-            const f32x4t v0 = *reinterpret_cast<const f32x4t*>(sc + row * CP + 8 * cq);
-            const f32x4t v1 = *reinterpret_cast<const f32x4t*>(sc + row * CP + 8 * cq + 4);
-            const bf16x8s o = {(__bf16)v0[0], (__bf16)v0[1], (__bf16)v0[2], (__bf16)v0[3], (__bf16)v1[0], (__bf16)v1[1], (__bf16)v1[2], (__bf16)v1[3]};
-            *reinterpret_cast<bf16x8s*>(reinterpret_cast<__bf16*>(a.yb) + (long long)b * a.y_bs + (long long)(mt + row) * a.ldy + n_first + 8 * cq) = o;
+            const f32x4 v0 = *reinterpret_cast<const f32x4*>(sc + row * CP + 8 * cq);
+            const f32x4 v1 = *reinterpret_cast<const f32x4*>(sc + row * CP + 8 * cq + 4);
+            const bf16x8 o = {(__bf16)v0[0], (__bf16)v0[1], (__bf16)v0[2], (__bf16)v0[3], (__bf16)v1[0], (__bf16)v1[1], (__bf16)v1[2], (__bf16)v1[3]};
+            *reinterpret_cast<bf16x8*>(reinterpret_cast<__bf16*>(a.yb) + (long long)b * a.y_bs + (long long)(mt + row) * a.ldy + n_first + 8 * cq) = o;
         }
     } else if (P_GEN) {
         // ---- phase 2a: token-major destination: lane -> 4 consecutive columns of a row; rows_pp rows per pass
@@ -194,9 +190,9 @@ __device__ __forceinline__ void tg_epilogue(const TGemmArgs& a, f32x16 (&acc)[NJ
             const int m = mt + row;
             const int n = n_first + 4 * cq;
             if (n_store && n >= n_store) continue;
-            f32x4t v = *reinterpret_cast<const f32x4t*>(sc + row * CP + 4 * cq);
+            f32x4 v = *reinterpret_cast<const f32x4*>(sc + row * CP + 4 * cq);
             if (a.res) {
-                const f32x4t rv = *reinterpret_cast<const f32x4t*>(a.res + (long long)b * a.res_bs + (long long)m * a.ldr + n);
+                const f32x4 rv = *reinterpret_cast<const f32x4*>(a.res + (long long)b * a.res_bs + (long long)m * a.ldr + n);
                 v += rv;
             }
             if (a.qk) {   // q / k heads token-major [b][2 heads][rows][head_dim]; head_dim % 4 == 0
@@ -205,11 +201,10 @@ __device__ __forceinline__ void tg_epilogue(const TGemmArgs& a, f32x16 (&acc)[NJ
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = pack_split_f16(v[e]);
                 }
-                *reinterpret_cast<f32x4t*>(a.qk + (((long long)b * a.heads2 + h) * a.rows + m) * a.head_dim + d) = v;
+                *reinterpret_cast<f32x4*>(a.qk + (((long long)b * a.heads2 + h) * a.rows + m) * a.head_dim + d) = v;
             } else {
-                if (a.yf) *reinterpret_cast<f32x4t*>(a.yf + (long long)b * a.y_bs + (long long)m * a.ldy + n) = v;
+                if (a.yf) *reinterpret_cast<f32x4*>(a.yf + (long long)b * a.y_bs + (long long)m * a.ldy + n) = v;
                 if (a.yb) {
-                    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
                     const bf16x4 o = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
                     *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(a.yb) + (long long)b * a.y_bs + (long long)m * a.ldy + n) = o;
                 }
@@ -217,10 +212,6 @@ __device__ __forceinline__ void tg_epilogue(const TGemmArgs& a, f32x16 (&acc)[NJ
         }
     }
     __builtin_amdgcn_wave_barrier();   // the scratch is reused for the wave's next row tile
-}
-
-static __device__ __forceinline__ f32x4t xbload4(rsrc_t r, int voff) {
-    return __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
 }
 
 // banded cross-attention on the transposed q tile of one head: acc[r] = q[d = (r & 3) + 8 (r >> 2) + 4 lh][token lt]
@@ -235,9 +226,9 @@ __device__ __forceinline__ void band_head(const TGemmArgs& a, const f32x16& q, i
 #pragma unroll
     for (int wi = 0; wi < 8; ++wi) sc[wi] = 0.f;
     for (int hf = 0; hf < nh; ++hf) {
-        f32x4t kq[16];
+        f32x4 kq[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) kq[r] = xbload4(rk, (((r & 3) + 8 * (r >> 2) + 4 * lh) * kvp + lo + 4 * hf) * 4);
+        for (int r = 0; r < 16; ++r) kq[r] = bload4(rk, (((r & 3) + 8 * (r >> 2) + 4 * lh) * kvp + lo + 4 * hf) * 4, 0);
 #pragma unroll
         for (int r = 0; r < 16; ++r)
 #pragma unroll
@@ -265,9 +256,9 @@ __device__ __forceinline__ void band_head(const TGemmArgs& a, const f32x16& q, i
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[r] = 0.f;
     for (int hf = 0; hf < nh; ++hf) {
-        f32x4t vq[16];
+        f32x4 vq[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) vq[r] = xbload4(rv, (((r & 3) + 8 * (r >> 2) + 4 * lh) * kvp + lo + 4 * hf) * 4);
+        for (int r = 0; r < 16; ++r) vq[r] = bload4(rv, (((r & 3) + 8 * (r >> 2) + 4 * lh) * kvp + lo + 4 * hf) * 4, 0);
 #pragma unroll
         for (int r = 0; r < 16; ++r)
 #pragma unroll
@@ -283,7 +274,6 @@ __device__ __forceinline__ void band_head(const TGemmArgs& a, const f32x16& q, i
 #pragma unroll
     for (int qd = 0; qd < 4; ++qd) {
         const long long off = row * a.ldy + head * 32 + 8 * qd + 4 * lh;
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
         const bf16x4 ov = {(__bf16)o[4 * qd], (__bf16)o[4 * qd + 1], (__bf16)o[4 * qd + 2], (__bf16)o[4 * qd + 3]};
         *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(a.y_tm) + off) = ov;
     }

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256, 5) void prep_kernel(const PrepArgs a) {   // f
             const bool tv = t < T;
             if (!(tv || (a.mode == 0 && t == T))) continue;   // the conv operand's right padding row (token T) is written as zeros
             if (ln) { mu = lnst[tt][0]; rs = lnst[tt][1]; }
-            f32x4t o, r;
+            f32x4 o, r;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int c = c0 + k;
@@ -145,13 +145,13 @@ __global__ __launch_bounds__(256, 5) void prep_kernel(const PrepArgs a) {   // f
                 r[k] = raw;
                 if (a.pack) { o[k] = pack_split_f16(o[k]); r[k] = pack_split_f16(r[k]); }   // (0 packs to 0: the padding rows stay all-zero bits)
             }
-            *reinterpret_cast<f32x4t*>(reinterpret_cast<float*>(a.dst) + (long long)b * a.dst_bs + (long long)(t + row_off) * a.ldd + a.coff + c0) = o;
+            *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.dst) + (long long)b * a.dst_bs + (long long)(t + row_off) * a.ldd + a.coff + c0) = o;
             if (a.dst2 && tv)   // raw copy (1x1 skip conv over the ResBlock input; x2 for the folded proj_out)
-                *reinterpret_cast<f32x4t*>(reinterpret_cast<float*>(a.dst2) + (long long)b * a.dst2_bs + (long long)t * a.ldd2 + a.coff2 + c0) = r;
+                *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.dst2) + (long long)b * a.dst2_bs + (long long)t * a.ldd2 + a.coff2 + c0) = r;
         }
         if (a.mode == 0 && t0 == 0 && tid < 48) {   // left padding row
-            const f32x4t zero = {0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<f32x4t*>(reinterpret_cast<float*>(a.dst) + (long long)b * a.dst_bs + a.coff + 4 * tid) = zero;
+            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.dst) + (long long)b * a.dst_bs + a.coff + 4 * tid) = zero;
         }
         return;
     }

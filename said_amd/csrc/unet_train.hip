@@ -12,6 +12,7 @@
 
 #include "sched_math.h"
 #include "train_dev.h"
+#include "vec_types.h"
 
 namespace said {
 namespace ut {
@@ -82,8 +83,7 @@ __global__ void __launch_bounds__(NT) gemm_kernel(const UGemm g) {
         ra[i] = part_r(g.A, min(m0 + am[i], g.M - 1));
         rb[i] = part_r(g.B, min(n0 + bn[i], g.N - 1));
     }
-    typedef float f16v __attribute__((ext_vector_type(16)));
-    f16v acc;
+    f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     const int kbeg = ks * g.kchunk, kend = min(g.K, kbeg + g.kchunk);

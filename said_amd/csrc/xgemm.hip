@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256, OCC) void xgemm_kernel(const TGemmArgs a) {
     };
 
     // ---- k-tile pipeline: weights always, streamed A tiles when SS
-    f32x4t ra_[ACH], rw[WCH];
+    f32x4 ra_[ACH], rw[WCH];
     int woff[WCH], lwoff[WCH], loff[ACH], arow[ACH], akp[ACH];
     auto setup_offsets = [&]() {   // (called AFTER the prologue: these are live through the whole k loop, the prologue's registers are not)
 #pragma unroll
@@ -194,13 +194,13 @@ __global__ __launch_bounds__(256, OCC) void xgemm_kernel(const TGemmArgs a) {
         }
         return kt * FBK;
     };
-    auto lds_store = [&](const f32x4t* xa, const f32x4t* xw) {
+    auto lds_store = [&](const f32x4* xa, const f32x4* xw) {
         if constexpr (SS) {
 #pragma unroll
-            for (int i = 0; i < ACH; ++i) *reinterpret_cast<f32x4t*>(ldse + loff[i]) = xa[i];
+            for (int i = 0; i < ACH; ++i) *reinterpret_cast<f32x4*>(ldse + loff[i]) = xa[i];
         }
 #pragma unroll
-        for (int i = 0; i < WCH; ++i) *reinterpret_cast<f32x4t*>(ldse + lwoff[i]) = xw[i];
+        for (int i = 0; i < WCH; ++i) *reinterpret_cast<f32x4*>(ldse + lwoff[i]) = xw[i];
     };
     f32x16 acc[NJ];
     const int frow = l & 31, fk = EPC * (l >> 5) + 4 * EPC * kh;
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256, OCC) void xgemm_kernel(const TGemmArgs a) {
         const int jn = step / nk, kt = step - jn * nk;
         const int wk = wk_of(kt) + jn * BN * a.K;
 #pragma unroll
-        for (int i = 0; i < WCH; ++i) rw[i] = *reinterpret_cast<const f32x4t*>(W + (woff[i] + wk));
+        for (int i = 0; i < WCH; ++i) rw[i] = *reinterpret_cast<const f32x4*>(W + (woff[i] + wk));
         if constexpr (SS) {
             const int st = min(max(kt - nkr, 0), nst - 1);        // (resident steps re-request the first streamed tile: an L1 hit)
             const elt_t* base; int ld, off;
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256, OCC) void xgemm_kernel(const TGemmArgs a) {
             else if (st < sk0 + sk1) { base = reinterpret_cast<const elt_t*>(a.sa[1]); ld = a.sld[1]; off = (st - sk0) * FBK; }
             else { base = reinterpret_cast<const elt_t*>(a.sa[2]); ld = a.sld[2]; off = (st - sk0 - sk1) * FBK; }
 #pragma unroll
-            for (int i = 0; i < ACH; ++i) ra_[i] = *reinterpret_cast<const f32x4t*>(base + ((long long)arow[i] * ld + off + akp[i]));
+            for (int i = 0; i < ACH; ++i) ra_[i] = *reinterpret_cast<const f32x4*>(base + ((long long)arow[i] * ld + off + akp[i]));
         }
     };
     clk_stamp_p(a.clk, w, l, 0);
@@ -270,11 +270,11 @@ __global__ __launch_bounds__(256, OCC) void xgemm_kernel(const TGemmArgs a) {
         auto wload = [&](int jn, int kt) {
             const int wk = wk_of(kt) + jn * BN * a.K;
 #pragma unroll
-            for (int i = 0; i < WCH; ++i) rw[i] = *reinterpret_cast<const f32x4t*>(W + (wo[i] + wk));
+            for (int i = 0; i < WCH; ++i) rw[i] = *reinterpret_cast<const f32x4*>(W + (wo[i] + wk));
         };
         auto wstore = [&](int buf) {
 #pragma unroll
-            for (int i = 0; i < WCH; ++i) *reinterpret_cast<f32x4t*>(ldse + buf * (BN * FBK) + wl[i]) = rw[i];
+            for (int i = 0; i < WCH; ++i) *reinterpret_cast<f32x4*>(ldse + buf * (BN * FBK) + wl[i]) = rw[i];
         };
         const int fr = l & 31;
         const int sw0 = (((l >> 5) + 4 * kh) ^ (fr & 7)) * EPC, sw1 = (((l >> 5) + 4 * kh + 2) ^ (fr & 7)) * EPC;   // the K half's two operand steps
@@ -402,8 +402,8 @@ __global__ __launch_bounds__(256, OCC) void xgemm_kernel(const TGemmArgs a) {
                 for (int ps = 0; ps < 4; ++ps) {
                     const int row = 16 * kh + 4 * ps + rr;
                     if (!lane_on || row >= nrows) continue;
-                    const f32x4t v0 = *reinterpret_cast<const f32x4t*>(sc + row * CP + 8 * cq);
-                    const f32x4t v1 = *reinterpret_cast<const f32x4t*>(sc + row * CP + 8 * cq + 4);
+                    const f32x4 v0 = *reinterpret_cast<const f32x4*>(sc + row * CP + 8 * cq);
+                    const f32x4 v1 = *reinterpret_cast<const f32x4*>(sc + row * CP + 8 * cq + 4);
                     float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                     if (a.res_tm) {
                         const u32x4 rv = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(a.res_tm) + (R0 + row) * a.ldr_tm + n);
@@ -576,8 +576,8 @@ __global__ __launch_bounds__(256, OCC) void xgemm_kernel(const TGemmArgs a) {
             for (int ps = 0; ps < 4; ++ps) {
                 const int row = 16 * kh + 4 * ps + rr;
                 if (!lane_on || row >= nrows) continue;
-                const f32x4t v0 = *reinterpret_cast<const f32x4t*>(sc + row * CP + 8 * cq);
-                const f32x4t v1 = *reinterpret_cast<const f32x4t*>(sc + row * CP + 8 * cq + 4);
+                const f32x4 v0 = *reinterpret_cast<const f32x4*>(sc + row * CP + 8 * cq);
+                const f32x4 v1 = *reinterpret_cast<const f32x4*>(sc + row * CP + 8 * cq + 4);
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                 if (a.res_tm) {
                     const u32x4 rv = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(a.res_tm) + (R0 + row) * a.ldr_tm + n);

@@ -427,3 +427,27 @@ def test_tgemm256d_lds_swizzle_is_conflict_free_under_the_real_b128_lane_groups(
     # and the chunk permutation of a row is a bijection (every k-chunk of a row is fetched exactly once)
     for row in range(256):
         assert sorted(p ^ swz(row) for p in range(8)) == list(range(8))
+
+
+def test_vector_types_and_bload4_are_defined_once_in_vec_types_h():
+    """The clang vector types of the device sources (any name for f32x2/4/16, f16x4/8, bf16x2/4/8, u32x2/4, s16x4) and the 16-byte buffer load exist only in csrc/vec_types.h."""
+    csrc = os.path.join(ROOT, "said_amd", "csrc")
+    shared = {("float", 2), ("float", 4), ("float", 16), ("_Float16", 4), ("_Float16", 8), ("__bf16", 2), ("__bf16", 4), ("__bf16", 8),
+              ("unsigned int", 2), ("unsigned int", 4), ("unsigned", 2), ("unsigned", 4), ("short", 4)}
+    typedef = re.compile(r"typedef\s+([A-Za-z_][\w ]*?)\s+(\w+)\s+__attribute__\(\(ext_vector_type\((\d+)\)\)\)")
+    bload4 = re.compile(r"\b\w*bload4\s*\([^;{)]*\)\s*\{")   # a definition (a body follows the parameter list), under any prefix
+    names = sorted(f for f in os.listdir(csrc) if f.endswith((".h", ".hip", ".cpp")))
+    assert "vec_types.h" in names and len(names) > 40
+    found = set()
+    for f in names:
+        code = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(csrc, f)).read(), flags=re.S)
+        types = [(elem, name, int(n)) for elem, name, n in typedef.findall(code) if (elem, int(n)) in shared]
+        loads = bload4.findall(code)
+        if f == "vec_types.h":
+            found = {name for _, name, _ in types}
+            assert len(types) == len(found) == 11 and len({(e, n) for e, _, n in types}) == 11, types   # each type once
+            assert len(loads) == 1, loads
+        else:
+            assert not types, f"{f} defines {types}: use the type of vec_types.h"
+            assert not loads, f"{f} defines its own bload4: {loads}"
+    assert found == {"f32x2", "f32x4", "f32x16", "f16x4", "f16x8", "bf16x2", "bf16x4", "bf16x8", "u32x2", "u32x4", "s16x4"}
