@@ -163,6 +163,16 @@ RENDER_EXPORTS = {
     "said_render_read_normals": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
     "said_render_read_colors": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
 }
+# include/said_jpeg.h: a group like the renderer's, in a table of its own (tests/test_jpeg_ref_cpu.py checks it against its header)
+JPEG_EXPORTS = {
+    "said_jpeg_create": (c_int, [POINTER(c_void_p), c_int]),
+    "said_jpeg_destroy": (c_int, [c_void_p]),
+    "said_jpeg_last_error": (c_char_p, [c_void_p]),
+    "said_jpeg_configure": (c_int, [c_void_p, c_int, c_int, c_int]),
+    "said_jpeg_header": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, _c_ll_p]),
+    "said_jpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_longlong, c_void_p, _c_ll_p, c_void_p]),
+    "said_jpeg_read_coefficients": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+}
 # include/said_unet_train.h: a group like those of LAZY_EXPORTS, kept in a table of its own (tests/test_unet_train_cpu.py checks it against its header)
 _c_ull = ctypes.c_ulonglong
 UNET_TRAIN_EXPORTS = {
@@ -185,7 +195,8 @@ UNET_TRAIN_EXPORTS = {
     "said_unet_train_read_losses": (c_int, [c_void_p, c_int, _c_double_p, POINTER(c_int), c_int]),
     "said_unet_train_last_losses": (c_int, [c_void_p, _c_float_p]),
 }
-_GROUPS = {**LAZY_EXPORTS, "render": ("the renderer", RENDER_EXPORTS), "unet_train": ("the UNet trainer", UNET_TRAIN_EXPORTS)}
+_GROUPS = {**LAZY_EXPORTS, "render": ("the renderer", RENDER_EXPORTS), "jpeg": ("the JPEG encoder", JPEG_EXPORTS),
+           "unet_train": ("the UNet trainer", UNET_TRAIN_EXPORTS)}
 _bound = set()   # the groups bound so far
 
 
@@ -1118,3 +1129,60 @@ class RenderEngine(_Context):
     def read_colors(self, n_frames: int) -> np.ndarray:
         """(n_frames, V, 3) difference colours (R, G, B) of the last render's chunk."""
         return self._read("said_render_read_colors", n_frames)
+
+
+# ---- JPEG encoder (include/said_jpeg.h)
+JPEG_OVERFLOW = 1   # SAID_JPEG_OVERFLOW
+
+
+class JpegEngine(_Context):
+    """said_jpeg context on one GPU (include/said_jpeg.h): (n, H, W, 3) uint8 device frames -> one baseline JFIF scan per frame, back to back
+    in one device buffer."""
+    prefix, group = "said_jpeg", "jpeg"
+    cpu_error, cpu_message = NoCpuPathError, "said_amd encodes JPEG on MI355X only (device={}); there is no CPU path (PIL is the host encoder)"
+
+    def __init__(self, device: torch.device, width: int, height: int, quality: int = 90):
+        super().__init__(device)
+        self._create()
+        self.configure(width, height, quality)
+
+    def configure(self, width: int, height: int, quality: int) -> None:
+        self.width = self.height = self.quality = self.blocks = 0   # nothing is configured until every call below has succeeded
+        self.header = b""
+        with torch.cuda.device(self.index):
+            self._call("said_jpeg_configure", int(width), int(height), int(quality))
+        self.width, self.height, self.quality = int(width), int(height), int(quality)
+        self.blocks = ((self.width + 15) // 16) * ((self.height + 15) // 16) * 6
+        buf, size = ctypes.create_string_buffer(1024), ctypes.c_longlong(0)
+        self._call("said_jpeg_header", buf, 1024, ctypes.byref(size))
+        self.header = buf.raw[:size.value]   # SOI .. SOS: the same for every frame
+
+    def encode(self, frames: torch.Tensor, n_frames: int, out: Optional[torch.Tensor], offsets: torch.Tensor, bgr: bool = True,
+               capacity: Optional[int] = None):
+        """The first n_frames of frames, a contiguous (>= n_frames, H, W, 3) uint8 device tensor, into out (uint8, device): each frame's scan and
+        EOI, back to back; offsets, a contiguous int64 device tensor of at least n_frames + 1 elements, receives where each starts and the
+        total.  `capacity` (default: all of out) bounds what may be written.  Returns (fits, bytes required); synchronises the current stream."""
+        need = n_frames * self.height * self.width * 3
+        if n_frames < 1 or not frames.is_cuda or frames.dtype != torch.uint8 or not frames.is_contiguous() or frames.numel() < need or frames.device.index != self.index:
+            raise EngineError(f"frames must be a contiguous uint8 tensor on cuda:{self.index} holding {n_frames} >= 1 frames of {self.height} x {self.width} x 3")
+        if not offsets.is_cuda or offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.numel() < n_frames + 1 or offsets.device.index != self.index:
+            raise EngineError(f"offsets must be a contiguous int64 tensor on cuda:{self.index} with at least {n_frames + 1} elements")
+        if out is not None and (not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.device.index != self.index):
+            raise EngineError(f"out must be a contiguous uint8 tensor on cuda:{self.index}")
+        room = 0 if out is None else out.numel()
+        cap = room if capacity is None else int(capacity)
+        if cap < 0 or cap > room:
+            raise EngineError(f"capacity {cap} lies outside the {room} bytes of out")
+        required = ctypes.c_longlong(0)
+        with torch.cuda.device(self.index):
+            rc = self.lib.said_jpeg_encode(self.h, _ptr(frames), int(n_frames), 1 if bgr else 0, _ptr(out), cap, _ptr(offsets), ctypes.byref(required), _stream())
+        if rc not in (0, JPEG_OVERFLOW):
+            raise EngineError("said_jpeg_encode: " + self._last_error(self.h))
+        return rc == 0, int(required.value)
+
+    def read_coefficients(self, n_frames: int) -> np.ndarray:
+        """(n_frames, blocks, 64) int16: the last encode's quantised coefficients, blocks in scan order, each in zigzag order."""
+        out = np.empty((n_frames, self.blocks, 64), dtype=np.int16)
+        with torch.cuda.device(self.index):
+            self._call("said_jpeg_read_coefficients", int(n_frames), out.ctypes.data_as(c_void_p), _stream())
+        return out

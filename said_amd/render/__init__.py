@@ -11,7 +11,7 @@ from typing import Iterator, List, Optional
 import numpy as np
 import torch
 
-from .._engine import RENDER_LUT, EngineError, RenderEngine, RenderScene
+from .._engine import RENDER_LUT, EngineError, JpegEngine, RenderEngine, RenderScene
 
 WIDTH = HEIGHT = 800
 FOCAL = 4754.97941935 / 2
@@ -82,6 +82,7 @@ class RendererObject:
         self.engine.set_scene(sc)
         self._mesh_key = None
         self._cmap = None
+        self._jpeg = None   # the JpegEncoder iter_encoded_frames keeps here, one per size and quality
 
     def set_mesh(self, vertices, faces, blendshapes_matrix) -> None:
         self._mesh_key = None
@@ -93,6 +94,9 @@ class RendererObject:
             self._cmap = color_map
 
     def close(self) -> None:
+        if self._jpeg is not None:
+            self._jpeg.close()
+            self._jpeg = None
         self.engine.close()
 
 
@@ -103,14 +107,9 @@ def _device_coeffs(a, device, name: str) -> torch.Tensor:
     return t.to(device).contiguous()
 
 
-def iter_rendered_frames(renderer: RendererObject, neutral_mesh, blendshapes_matrix: np.ndarray, blendshape_coeffs, target_blendshape_coeffs=None,
-                         color_map: str = "viridis", max_diff: float = 0.001, chunk: int = DEFAULT_CHUNK, rot=None, t_center=None,
-                         face_ids: bool = False) -> Iterator[np.ndarray]:
-    """Yields (n, 800, 800, 3) uint8 B-G-R arrays, n <= chunk frames at a time, in order (with face_ids: pairs (frames, (n, 800, 800) int32)).
-    The arrays are views of one pinned host buffer that the next chunk overwrites: copy what must outlive the iteration step.
-    `t_center` defaults to the mean of the neutral vertices, as in the reference; `rot` (axis-angle) to no rotation."""
-    if chunk < 1:
-        raise ValueError("chunk must be at least 1")
+def _prepare_sequence(renderer: RendererObject, neutral_mesh, blendshapes_matrix, blendshape_coeffs, target_blendshape_coeffs, color_map: str, t_center):
+    """What both frame iterators do before their first chunk: the mesh upload (skipped when the same mesh is drawn again), the coefficient
+    sequences on the device, the colour map of a difference render, and the rotation centre.  Returns (coeffs, target or None, center)."""
     eng = renderer.engine
     verts = np.asarray(neutral_mesh.vertices, dtype=np.float64)
     faces = np.asarray(neutral_mesh.faces)
@@ -127,6 +126,19 @@ def iter_rendered_frames(renderer: RendererObject, neutral_mesh, blendshapes_mat
             raise ValueError(f"target_blendshape_coeffs {tuple(target.shape)} and blendshape_coeffs {tuple(coeffs.shape)} differ in shape")
         renderer.set_colormap(color_map)
     center = verts.mean(axis=0) if t_center is None else np.asarray(t_center, dtype=np.float64)
+    return coeffs, target, center
+
+
+def iter_rendered_frames(renderer: RendererObject, neutral_mesh, blendshapes_matrix: np.ndarray, blendshape_coeffs, target_blendshape_coeffs=None,
+                         color_map: str = "viridis", max_diff: float = 0.001, chunk: int = DEFAULT_CHUNK, rot=None, t_center=None,
+                         face_ids: bool = False) -> Iterator[np.ndarray]:
+    """Yields (n, 800, 800, 3) uint8 B-G-R arrays, n <= chunk frames at a time, in order (with face_ids: pairs (frames, (n, 800, 800) int32)).
+    The arrays are views of one pinned host buffer that the next chunk overwrites: copy what must outlive the iteration step.
+    `t_center` defaults to the mean of the neutral vertices, as in the reference; `rot` (axis-angle) to no rotation."""
+    if chunk < 1:
+        raise ValueError("chunk must be at least 1")
+    eng = renderer.engine
+    coeffs, target, center = _prepare_sequence(renderer, neutral_mesh, blendshapes_matrix, blendshape_coeffs, target_blendshape_coeffs, color_map, t_center)
     T = coeffs.shape[0]
     n_max = min(chunk, T)
     if n_max == 0:
@@ -156,5 +168,88 @@ def render_blendshape_coefficients(renderer: RendererObject, neutral_mesh, blend
     return out
 
 
-__all__ = ["RendererObject", "render_blendshape_coefficients", "iter_rendered_frames", "rodrigues", "light_positions", "colormap_index",
-           "colormap_table", "EngineError"]
+class JpegEncoder:
+    """Baseline JPEG files of device frames (include/said_jpeg.h): ``encode`` takes an (n, height, width, 3) uint8 tensor
+    on the device (a numpy array is uploaded) and returns one complete JFIF file per frame.  Only the compressed bytes travel to the host."""
+
+    def __init__(self, device, width: int, height: int, quality: int = 90) -> None:
+        self.engine = JpegEngine(torch.device(device), width, height, quality)
+        self.device, self.width, self.height, self.quality = self.engine.device, int(width), int(height), int(quality)
+        self.header = self.engine.header
+        self._out = self._host = self._offsets = None
+
+    def _room(self, n: int, capacity: int) -> None:
+        dev = torch.device("cuda", self.engine.index)
+        if self._out is None or self._out.numel() < capacity:
+            self._out = torch.empty(capacity, dtype=torch.uint8, device=dev)
+            self._host = torch.empty(capacity, dtype=torch.uint8, pin_memory=True)
+        if self._offsets is None or self._offsets.numel() < n + 1:
+            self._offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+
+    def encode(self, frames, bgr: bool = True) -> List[bytes]:
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        if frames.dim() == 3:
+            frames = frames[None]
+        if frames.dim() != 4 or tuple(frames.shape[1:]) != (self.height, self.width, 3) or frames.dtype != torch.uint8:
+            raise ValueError(f"frames must be (n, {self.height}, {self.width}, 3) uint8, got {tuple(frames.shape)} {frames.dtype}")
+        n = frames.shape[0]
+        if n == 0:
+            return []
+        eng = self.engine
+        with torch.cuda.device(eng.index):
+            frames = frames.to(torch.device("cuda", eng.index)).contiguous()
+            # a quarter of the raw size to start with (rendered frames compress about sixty times); one retry at the size the encoder reports
+            self._room(n, max(frames.numel() // 4, 1))
+            fits, total = eng.encode(frames, n, self._out, self._offsets, bgr=bgr)
+            if not fits:
+                self._room(n, total)
+                fits, total = eng.encode(frames, n, self._out, self._offsets, bgr=bgr)
+                if not fits:
+                    raise EngineError(f"said_jpeg_encode: {total} bytes required twice over a buffer of that size")
+            self._host[:total].copy_(self._out[:total], non_blocking=True)   # only the used bytes
+            offsets = self._offsets[:n + 1].cpu().tolist()                    # synchronises the stream: the copy above has landed
+            torch.cuda.current_stream().synchronize()
+        data = self._host[:total].numpy().tobytes()
+        return [self.header + data[offsets[i]:offsets[i + 1]] for i in range(n)]
+
+    def close(self) -> None:
+        self.engine.close()
+
+
+def iter_encoded_frames(renderer: RendererObject, neutral_mesh, blendshapes_matrix: np.ndarray, blendshape_coeffs, target_blendshape_coeffs=None,
+                        color_map: str = "viridis", max_diff: float = 0.001, chunk: int = DEFAULT_CHUNK, rot=None, t_center=None,
+                        face_ids: bool = False, quality: int = 90, raw: bool = False):
+    """``iter_rendered_frames`` with the JPEG encoding done on the device: yields, per chunk, the list of its frames' JPEG files (bytes).  With
+    ``raw`` it yields (files, frames), the frames as ``iter_rendered_frames`` gives them (views of a buffer the next chunk overwrites);
+    without it no pixel leaves the device.  ``face_ids`` is accepted for the signature's sake and must be False."""
+    if face_ids:
+        raise ValueError("iter_encoded_frames yields JPEG files; face ids come from iter_rendered_frames")
+    if chunk < 1:
+        raise ValueError("chunk must be at least 1")
+    eng = renderer.engine
+    coeffs, target, center = _prepare_sequence(renderer, neutral_mesh, blendshapes_matrix, blendshape_coeffs, target_blendshape_coeffs, color_map, t_center)
+    T = coeffs.shape[0]
+    n_max = min(chunk, T)
+    if n_max == 0:
+        return
+    h, w = eng.height, eng.width
+    enc = renderer._jpeg
+    if enc is None or (enc.width, enc.height, enc.quality) != (w, h, int(quality)):
+        if enc is not None:
+            enc.close()
+        enc = renderer._jpeg = JpegEncoder(eng.device, w, h, quality)
+    with torch.cuda.device(eng.index):
+        dev = torch.empty((n_max, h, w, 3), dtype=torch.uint8, device=eng.device)
+        host = torch.empty((n_max, h, w, 3), dtype=torch.uint8, pin_memory=True) if raw else None
+        for t0 in range(0, T, chunk):
+            n = min(chunk, T - t0)
+            eng.render(coeffs, t0, n, dev, target=target, max_diff=max_diff, rot=rot, t_center=center)
+            if raw:
+                host[:n].copy_(dev[:n], non_blocking=True)
+            files = enc.encode(dev[:n], bgr=True)   # synchronises the stream
+            yield (files, host[:n].numpy()) if raw else files
+
+
+__all__ = ["RendererObject", "render_blendshape_coefficients", "iter_rendered_frames", "iter_encoded_frames", "JpegEncoder", "rodrigues",
+           "light_positions", "colormap_index", "colormap_table", "EngineError"]

@@ -24,6 +24,23 @@ def pcm16(waveform) -> np.ndarray:
     return np.round(np.clip(a.astype(np.float64), -1.0, 1.0) * 32767.0).astype(np.int16)
 
 
+def jpeg_size(jpeg: bytes):
+    """(width, height) of a baseline JPEG file, from its SOF0 segment; ValueError when the bytes do not start with SOI or carry no SOF0 before
+    the scan."""
+    if len(jpeg) < 4 or jpeg[:2] != b"\xff\xd8":
+        raise ValueError("not a JPEG file: no SOI marker at the start")
+    pos = 2
+    while pos + 4 <= len(jpeg) and jpeg[pos] == 0xFF:
+        marker, size = jpeg[pos + 1], struct.unpack(">H", jpeg[pos + 2:pos + 4])[0]
+        if marker == 0xC0 and pos + 9 <= len(jpeg):
+            height, width = struct.unpack(">HH", jpeg[pos + 5:pos + 9])
+            return width, height
+        if marker == 0xDA:
+            break
+        pos += 2 + size
+    raise ValueError("not a baseline JPEG file: no SOF0 segment before the scan")
+
+
 class AviWriter:
     """``write(frame)`` takes (height, width, 3) uint8 images, B-G-R unless ``bgr=False``.  ``audio``: int16 samples, (n,) or (n, channels), at
     ``audio_rate`` Hz; whatever lies past the last frame is written at ``close``."""
@@ -98,6 +115,17 @@ class AviWriter:
         buf = io.BytesIO()
         Image.fromarray(np.ascontiguousarray(a[..., ::-1] if self.bgr else a), "RGB").save(buf, format="JPEG", quality=self.quality)
         self._put(0, b"00dc", buf.getvalue())
+        self.frames += 1
+        if self.audio is not None:
+            self._audio_until(int(round(self.frames * self.audio_rate / self.fps)))
+
+    def write_encoded(self, jpeg: bytes) -> None:
+        """A frame that is already a JPEG file (said_amd.render.JpegEncoder): what ``write`` does after its encode step.  The file must start
+        with SOI and its SOF0 must carry the writer's width and height."""
+        size = jpeg_size(jpeg)
+        if size != (self.width, self.height):
+            raise ValueError(f"the JPEG is {size[0]} x {size[1]}, the video {self.width} x {self.height}")
+        self._put(0, b"00dc", bytes(jpeg))
         self.frames += 1
         if self.audio is not None:
             self._audio_until(int(round(self.frames * self.audio_rate / self.fps)))

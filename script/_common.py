@@ -97,10 +97,23 @@ def load_blendshape_basis(neutral_path: str, blendshapes_dir: str, names):
     return neutral, np.concatenate(cols, axis=1)
 
 
-def write_video(frames_iter, output_path: str, fps: int, audio_path: str, width: int = 800, height: int = 800, on_frame=None) -> str:
+def _decoded_chunks(encoded_iter):
+    """Chunks of JPEG files (or (files, frames) pairs) -> chunks of B-G-R frames, for a writer that wants pixels."""
+    import io
+
+    import numpy as np
+    from PIL import Image
+    for chunk in encoded_iter:
+        files, pixels = chunk if isinstance(chunk, tuple) else (chunk, None)
+        yield pixels if pixels is not None else [np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))[..., ::-1] for f in files]
+
+
+def write_video(frames_iter, output_path: str, fps: int, audio_path: str, width: int = 800, height: int = 800, on_frame=None, encoded: bool = False) -> str:
     """Stream B-G-R frame chunks and the sound of audio_path into a video; returns the path written.  A path ending in .avi gets the built-in
     Motion-JPEG writer (said_amd/util/video.py).  Any other extension needs moviepy (and its ffmpeg): when it does not import, the .avi is
-    written beside the requested path and stderr says so, rather than failing after the frames were rendered."""
+    written beside the requested path and stderr says so, rather than failing after the frames were rendered.
+    With `encoded`, frames_iter yields chunks that are already JPEG files (said_amd.render.iter_encoded_frames): lists of bytes, or pairs
+    (files, frames) when on_frame needs the pixels.  They go into the .avi as they are; moviepy, which wants pixels, gets them decoded."""
     import numpy as np
     from said_amd.util.video import AviWriter
     want_avi = output_path.lower().endswith(".avi")
@@ -125,12 +138,20 @@ def write_video(frames_iter, output_path: str, fps: int, audio_path: str, width:
                 audio = pcm16(audio.astype(np.float64) / (np.iinfo(audio.dtype).max if audio.dtype.kind in "iu" else 1.0))
         with AviWriter(output_path, fps, width, height, audio=audio, audio_rate=rate) as out:
             for chunk in frames_iter:
-                for frame in chunk:
-                    out.write(frame)
+                files, pixels = (chunk if isinstance(chunk, tuple) else (chunk, None)) if encoded else (None, chunk)
+                if on_frame is not None and pixels is None:
+                    raise ValueError("on_frame needs the pixels: ask iter_encoded_frames for raw=True")
+                for i in range(len(files if encoded else pixels)):
+                    if encoded:
+                        out.write_encoded(files[i])
+                    else:
+                        out.write(pixels[i])
                     if on_frame is not None:
-                        on_frame(index, frame)
+                        on_frame(index, pixels[i])
                     index += 1
         return output_path
+    if encoded:
+        frames_iter = _decoded_chunks(frames_iter)
     frames = []
     for chunk in frames_iter:   # moviepy's ImageSequenceClip wants the whole list, R-G-B
         for frame in chunk:

@@ -9,7 +9,8 @@ type=bool behaviour: any non-empty string turns them on), with these differences
 - PNG frames (--save_images) are written with PIL, and --output_images_dir is created when missing;
 - the reference passes R-G-B-reversed frames to moviepy (its renderer returns B-G-R for cv2.imwrite); with a grey material that is invisible,
   in difference mode it swaps red and blue in the video.  Here video and PNGs both show the colour map's own colours;
-- new optional flags: --device, --chunk (frames per launch).
+- new optional flags: --device, --chunk (frames per launch), --jpeg {pil,gpu}: who encodes the .avi's frames, PIL on the host (default) or
+  the HIP encoder on the device, after which only the compressed frames are copied to the host.
 """
 import argparse
 import os
@@ -40,6 +41,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--output_images_dir", type=str, default="../out_imgs", help="Saving directory of the output image for each frame")
     p.add_argument("--device", type=str, default="cuda:0", help="MI355X to run on")
     p.add_argument("--chunk", type=int, default=64, help="Frames rendered per launch")
+    p.add_argument("--jpeg", choices=["pil", "gpu"], default="pil", help="JPEG encoder of the video's frames: PIL on the host, or the HIP encoder on the device")
     return p
 
 
@@ -48,7 +50,7 @@ def main(argv=None) -> None:
     from PIL import Image
 
     from _common import load_blendshape_basis, write_video
-    from said_amd.render import RendererObject, iter_rendered_frames
+    from said_amd.render import RendererObject, iter_encoded_frames, iter_rendered_frames
     from said_amd.util.blendshape import DEFAULT_BLENDSHAPE_CLASSES, load_blendshape_coeffs
     from said_amd.util.parser import parse_list
 
@@ -57,7 +59,10 @@ def main(argv=None) -> None:
     coeffs = load_blendshape_coeffs(args.blendshape_coeffs_path).numpy()
     target = load_blendshape_coeffs(args.target_diff_blendshape_coeffs_path).numpy() if args.show_difference else None
     renderer = RendererObject(device=args.device)
-    frames = iter_rendered_frames(renderer, neutral, basis, coeffs, target, max_diff=args.max_diff, chunk=args.chunk)
+    if args.jpeg == "gpu":   # the PNGs of --save_images need the pixels as well
+        frames = iter_encoded_frames(renderer, neutral, basis, coeffs, target, max_diff=args.max_diff, chunk=args.chunk, raw=bool(args.save_images))
+    else:
+        frames = iter_rendered_frames(renderer, neutral, basis, coeffs, target, max_diff=args.max_diff, chunk=args.chunk)
 
     on_frame = None
     if args.save_images:
@@ -66,7 +71,7 @@ def main(argv=None) -> None:
         def on_frame(index, frame):
             Image.fromarray(frame[..., ::-1].copy(), "RGB").save(os.path.join(args.output_images_dir, f"{index}.png"))
 
-    written = write_video(frames, args.output_path, args.fps, args.audio_path, on_frame=on_frame)
+    written = write_video(frames, args.output_path, args.fps, args.audio_path, on_frame=on_frame, encoded=args.jpeg == "gpu")
     print(f"{len(coeffs)} frames -> {written}")
     renderer.close()
 
