@@ -388,15 +388,11 @@ static std::vector<long long> loop_graph_key(const said_ctx* ctx, const said_loo
             (long long)(uintptr_t)(p->save_intermediate ? p->intermediates_dev : nullptr), (long long)(uintptr_t)(p->use_step_noise == 1 ? noise_cm : nullptr), solver};
 }
 
-static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, bool prepare_only) {
-    if (check_ready(ctx)) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->cur_concurrent = p->concurrent != 0;
-    ctx->dbg_count = 0;   // (said_debug_stop_after counts launches from the start of the call: the eager warm-up step then runs the first n launches, the captured steps none)
-    const int B = p->batch, T = p->frames, N = p->num_steps, C = ctx->cin;
-    const bool cfg = p->guidance_scale > 1.0f;
-    const int Be = cfg ? 2 * B : B;
+// ---- the loop's phases, in the order loop_impl runs them ----
+// Argument checks; *solver <- the coefficient table's solver family.
+static int loop_check(said_ctx* ctx, const said_loop_params* p, int* solver) {
+    const int B = p->batch, T = p->frames, N = p->num_steps;
+    const int Be = p->guidance_scale > 1.0f ? 2 * B : B;
     if (B < 1 || Be > ctx->maxBe) return fail(ctx, "effective batch %d exceeds the context's max_batch_eff %d", Be, ctx->maxBe);
     if (T < 1 || T > ctx->maxT) return fail(ctx, "frames %d exceed max_frames %d", T, ctx->maxT);
     if (N < 0 || N > ctx->maxNp) return fail(ctx, "num_steps %d exceeds %d", N, ctx->maxNp);
@@ -408,21 +404,15 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
     if (p->save_intermediate && !p->intermediates_dev) return fail(ctx, "save_intermediate needs intermediates_dev");
     if (N > 0 && !p->coef_host) return fail(ctx, "coef_host must not be null");
     std::string why;
-    const int solver = table_solver(p, &why);
-    if (solver < 0) return fail(ctx, "said_denoise_loop: %s", why.c_str());
-    if (prepare_only) {   // nothing to do when the step graph of this configuration exists
-        if (N == 0) return 0;
-        const bool grow = p->use_step_noise == 1 && (size_t)N * B * C * (size_t)rup(T, 32) > ctx->noise_cm_elems;
-        if (!grow && ctx->gexec && loop_graph_key(ctx, p, ctx->noise_cm, solver) == ctx->gkey) return 0;
-    }
-    if (set_band(ctx, T, T, s)) return -1;
-    UGeo g = make_geo(ctx, Be, cfg ? B : 0, T, T);
-    g.step_ptr = ctx->step_dev;
-    if (cfg) g.Bc = B;
+    *solver = table_solver(p, &why);
+    if (*solver < 0) return fail(ctx, "said_denoise_loop: %s", why.c_str());
+    return 0;
+}
+// The per-clip, step-invariant work: everything the step graph reads from device memory at replay time.
+static int loop_stage(said_ctx* ctx, const said_loop_params* p, const UGeo& g, hipStream_t s) {
+    const int B = p->batch, T = p->frames, N = p->num_steps, C = ctx->cin;
+    const bool cfg = p->guidance_scale > 1.0f;
     const long long xs = (long long)C * g.Tp;
-
-    TRACE("loop: begin");
-    // per-clip, step-invariant work
     if (N > 0) {
         HIPCHK(hipMemcpyAsync(ctx->ts_dev, p->timesteps_host, N * sizeof(long long), hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(ctx->coef_dev, p->coef_host, (size_t)N * 8 * sizeof(float), hipMemcpyHostToDevice, s));
@@ -437,7 +427,7 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
         launch_tm_to_cm(p->context_dev, ctx->CTX, B, T, ctx->ctx_dim, g.Sp, cs, s);
     }
     TRACE("loop: ctx done");
-    if (uncond_const) run_kv(ctx, B, B, T, g.Sp, s); else run_kv(ctx, 0, Be, T, g.Sp, s);
+    if (uncond_const) run_kv(ctx, B, B, T, g.Sp, s); else run_kv(ctx, 0, g.Be, T, g.Sp, s);
     TRACE("loop: kv launched");
     launch_tm_to_cm(p->latents_dev, ctx->x_cm, B, T, C, g.Tp, xs, s);
     if (p->use_mask) {
@@ -459,36 +449,130 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
         launch_tm_to_cm(p->step_noise_dev, ctx->noise_cm, N * B, T, C, g.Tp, xs, s);
     }
     HIPCHK(hipMemsetAsync(ctx->step_dev, 0xFF, sizeof(int), s));  // step = -1
-    HIPCHK(hipMemsetAsync(ctx->status_dev, 0, 2 * sizeof(int), s));   // numeric status of THIS loop (the eager warm-up step below sees step 0's own data)
+    HIPCHK(hipMemsetAsync(ctx->status_dev, 0, 2 * sizeof(int), s));   // numeric status of THIS loop (the eager warm-up step sees step 0's own data)
+    return 0;
+}
+// The argument blocks of the step's last kernel: the update's operands once, then what each route adds.  `fused`: the out conv runs inside that kernel.
+struct LoopArgs {
+    SchedArgs sa{};
+    OutSchedArgs osa{};
+    bool fused = false;
+};
+static void loop_args(const said_ctx* ctx, const said_loop_params* p, const UGeo& g, int solver, LoopArgs* la) {
+    const bool cfg = p->guidance_scale > 1.0f;
+    StepUpdateArgs u{};
+    u.coef = ctx->coef_dev; u.step_ptr = ctx->step_dev;
+    u.x = ctx->x_cm; u.x_bstride = (long long)ctx->cin * g.Tp; u.pitch = g.Tp;
+    u.B = p->batch; u.T = p->frames; u.C = ctx->cin; u.cfg = cfg ? 1 : 0; u.prediction_type = p->prediction_type;
+    u.guidance_scale = p->guidance_scale; u.guidance_rescale = (cfg && p->guidance_rescale > 0.f) ? p->guidance_rescale : 0.f; u.latent_scale = p->latent_scale;
+    u.step_noise = p->use_step_noise == 1 ? ctx->noise_cm : nullptr;
+    u.noise_seed = p->use_step_noise == 2 ? ctx->seed_dev : nullptr;
+    u.noise_elem0 = (unsigned)((long long)p->noise_batch_offset * p->frames * ctx->cin);
+    u.init = p->use_mask ? ctx->init_cm : nullptr; u.edit_noise = p->use_mask ? ctx->enoise_cm : nullptr; u.mask = p->use_mask ? ctx->mask_cm : nullptr;
+    u.inter = p->save_intermediate ? p->intermediates_dev : nullptr;
+    u.status = ctx->status_dev;
+    u.x0h = solver ? ctx->x0h_cm : nullptr; u.solver = solver;
 
-    // per-step graph
-    SchedArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.eps = ctx->eps_cm; sa.eps_bstride = xs; sa.pitch = g.Tp; sa.B = B; sa.T = T; sa.C = C; sa.cfg = cfg ? 1 : 0;
-    sa.guidance_scale = p->guidance_scale; sa.guidance_rescale = (cfg && p->guidance_rescale > 0.f) ? p->guidance_rescale : 0.f;
-    sa.rescale_part = ctx->rescale_part; sa.rescale_nblk = 16; sa.prediction_type = p->prediction_type;
-    sa.coef = ctx->coef_dev; sa.step_ptr = ctx->step_dev; sa.x = ctx->x_cm; sa.x_bstride = xs;
-    sa.step_noise = p->use_step_noise == 1 ? ctx->noise_cm : nullptr;
-    sa.noise_seed = p->use_step_noise == 2 ? ctx->seed_dev : nullptr;
-    sa.noise_elem0 = (unsigned)((long long)p->noise_batch_offset * T * C);
-    sa.init = p->use_mask ? ctx->init_cm : nullptr; sa.edit_noise = p->use_mask ? ctx->enoise_cm : nullptr;
-    sa.mask = p->use_mask ? ctx->mask_cm : nullptr;
-    sa.inter = p->save_intermediate ? p->intermediates_dev : nullptr; sa.latent_scale = p->latent_scale;
-    sa.status = ctx->status_dev;
+    static_cast<StepUpdateArgs&>(la->sa) = u;
+    la->sa.eps = ctx->eps_cm; la->sa.eps_bstride = u.x_bstride; la->sa.rescale_part = ctx->rescale_part; la->sa.rescale_nblk = 16;
 
-    OutSchedArgs osa;
-    memset(&osa, 0, sizeof osa);
-    osa.x = ctx->P.p; osa.gn_part = ctx->P.st; osa.gn_gamma = ctx->out_g; osa.gn_beta = ctx->out_b;
-    osa.w4 = ctx->conv_out.w4[0]; osa.ws = sp_on(ctx, ctx->out_split) ? ctx->conv_out.ws[0] : nullptr; osa.bias = ctx->conv_out.bias; osa.coef = ctx->coef_dev; osa.step_ptr = ctx->step_dev;
-    osa.lat = ctx->x_cm; osa.step_noise = sa.step_noise; osa.noise_seed = sa.noise_seed; osa.noise_elem0 = sa.noise_elem0; osa.init = sa.init; osa.edit_noise = sa.edit_noise; osa.mask = sa.mask;
-    osa.inter = sa.inter; osa.x_bstride = g.hs; osa.gn_part_bstride = g.sts; osa.lat_bstride = xs;
-    osa.pitch = g.Tp; osa.T = T; osa.B = B; osa.Cin = MC; osa.Cout = C; osa.gn_nparts = g.np; osa.cfg = cfg ? 1 : 0;
-    osa.prediction_type = p->prediction_type; osa.guidance_scale = p->guidance_scale; osa.guidance_rescale = sa.guidance_rescale;
-    osa.latent_scale = p->latent_scale;
-    osa.status = ctx->status_dev;
-    osa.x0h = solver ? ctx->x0h_cm : nullptr; osa.solver = solver;
-    const bool fused = ctx->conv_out.w4[0] && out_sched_supports(osa);
-    if (fused) g.out_sched = &osa;
+    static_cast<StepUpdateArgs&>(la->osa) = u;
+    OutSchedArgs& o = la->osa;
+    o.h = ctx->P.p; o.h_bstride = g.hs; o.gn_part = ctx->P.st; o.gn_part_bstride = g.sts; o.gn_nparts = g.np; o.gn_gamma = ctx->out_g; o.gn_beta = ctx->out_b;
+    o.w4 = ctx->conv_out.w4[0]; o.ws = sp_on(ctx, ctx->out_split) ? ctx->conv_out.ws[0] : nullptr; o.bias = ctx->conv_out.bias; o.Cin = MC;
+    la->fused = ctx->conv_out.w4[0] && out_sched_supports(o);
+}
+// Until keep is set, leaving the scope drops the step graphs: a half-built or faulted graph is never cached.  The capture stream is released either way
+// (a live stream pins a hardware queue: DESIGN.md 5.1).
+struct GraphBuildGuard {
+    said_ctx* ctx;
+    bool keep = false;
+    ~GraphBuildGuard() {
+        if (!keep) drop_graphs(ctx);
+        release_cap_streams(ctx);
+    }
+};
+// One denoise step: the UNet (its last kernel holds the update when fused), else the unfused scheduler launches behind it.
+static void run_step(said_ctx* ctx, const UGeo& g, const LoopArgs& la, hipStream_t s) {
+    run_unet(ctx, g, s);
+    if (!la.fused) {
+        if (la.sa.guidance_rescale > 0.f) launch_rescale_partials(la.sa, ctx->rescale_part, s);
+        launch_sched_step(la.sa, s);
+        ++ctx->n_sched_step;
+    }
+}
+// Warm-up, then capture of the spg-step graph and of the graph of the rem remaining steps.
+static int build_step_graphs(said_ctx* ctx, const said_loop_params* p, const UGeo& g, const LoopArgs& la, hipStream_t s, int spg, int rem, const std::vector<long long>& key) {
+    drop_graphs(ctx);
+    GraphBuildGuard guard{ctx};
+    // Eager warm-up of the exact step sequence first: the first launch of a kernel inside a
+    // stream capture hangs on ROCm 7.2 (lazy per-kernel initialisation is not capturable).
+    // The step is run on step index 0 and its effect on the latents is undone afterwards.
+    TRACE("loop: warmup begin");
+    run_step(ctx, g, la, s);
+    TRACE("loop: warmup unet launched");
+    launch_tm_to_cm(p->latents_dev, ctx->x_cm, p->batch, p->frames, ctx->cin, g.Tp, (long long)ctx->cin * g.Tp, s);
+    HIPCHK(hipMemsetAsync(ctx->step_dev, 0xFF, sizeof(int), s));
+    HIPCHK(hipStreamSynchronize(s));
+    TRACE("loop: warmup synced");
+    // A launch helper that refused a shape launched NOTHING (launch_fault / launch_err): a graph captured from the same schedule would be
+    // missing that kernel and — cached under this key — replay silently wrong on every later call.  So the faults of the warm-up and of
+    // each capture are consumed HERE, on the thread that drove them, in the prepare-only path too, and nothing is cached.
+    auto loop_fault = [&]() -> bool { return launch_fault_peek() != nullptr || !ctx->launch_err.empty(); };
+    if (loop_fault()) LAUNCHCHK();
+    // capture on a private stream: the caller's stream may be the legacy default stream,
+    // which cannot be captured; the instantiated graph is then replayed on the caller's stream
+    if (ensure_cap_streams(ctx)) return -1;
+    hipStream_t cs = ctx->cap_stream;
+    auto capture_steps = [&](int nsteps, hipGraph_t* gr, hipGraphExec_t* ge) -> int {
+        HIPCHK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+        for (int rep = 0; rep < nsteps; ++rep) run_step(ctx, g, la, cs);
+        TRACE("loop: capture recorded");
+        hipError_t e = hipStreamEndCapture(cs, gr);
+        if (e != hipSuccess) return fail(ctx, "hipStreamEndCapture: %s", hipGetErrorString(e));
+        HIPCHK(hipGraphInstantiate(ge, *gr, nullptr, nullptr, 0));
+        return 0;
+    };
+    if (capture_steps(spg, &ctx->graph, &ctx->gexec)) return -1;
+    if (loop_fault()) LAUNCHCHK();
+    if (rem > 0 && capture_steps(rem, &ctx->graph_rem, &ctx->gexec_rem)) return -1;
+    if (loop_fault()) LAUNCHCHK();
+    size_t nn = 0;
+    (void)hipGraphGetNodes(ctx->graph, nullptr, &nn);
+    ctx->gnodes = (int)nn / spg;
+    ctx->gspg = spg;
+    ctx->gkey = key;
+    guard.keep = true;
+    TRACE("loop: graph instantiated");
+    return 0;
+}
+
+static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, bool prepare_only) {
+    if (check_ready(ctx)) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->cur_concurrent = p->concurrent != 0;
+    ctx->dbg_count = 0;   // (said_debug_stop_after counts launches from the start of the call: the eager warm-up step then runs the first n launches, the captured steps none)
+    int solver = 0;
+    if (loop_check(ctx, p, &solver)) return -1;
+    const int B = p->batch, T = p->frames, N = p->num_steps, C = ctx->cin;
+    const bool cfg = p->guidance_scale > 1.0f;
+    if (prepare_only) {   // nothing to do when the step graph of this configuration exists
+        if (N == 0) return 0;
+        const bool grow = p->use_step_noise == 1 && (size_t)N * B * C * (size_t)rup(T, 32) > ctx->noise_cm_elems;
+        if (!grow && ctx->gexec && loop_graph_key(ctx, p, ctx->noise_cm, solver) == ctx->gkey) return 0;
+    }
+    if (set_band(ctx, T, T, s)) return -1;
+    UGeo g = make_geo(ctx, cfg ? 2 * B : B, cfg ? B : 0, T, T);
+    g.step_ptr = ctx->step_dev;
+    g.step_inc = ctx->step_dev;   // the first kernel of the step (conv_in) advances the step counter itself
+    if (cfg) g.Bc = B;
+
+    TRACE("loop: begin");
+    if (loop_stage(ctx, p, g, s)) return -1;
+    LoopArgs la;
+    loop_args(ctx, p, g, solver, &la);
+    if (la.fused) g.out_sched = &la.osa;
 
     if (N > 0) {
         // steps per graph: consecutive denoise steps captured back to back in ONE graph (the device-side step counter
@@ -496,68 +580,14 @@ static int loop_impl(said_ctx* ctx, const said_loop_params* p, void* stream, boo
         // the N % spg remaining steps finishes it (prime N, e.g. 997 = 99 x 10 + 7)
         const int spg = steps_per_graph(ctx, N);   // measured: ~6 us per graph launch boundary; 10 steps per graph recovered 1.2 % at B=1 (round 1), 50 another 0.4-0.5 % of a long loop (round 6)
         const int rem = N % spg;
-        const std::vector<long long> key = loop_graph_key(ctx, p, sa.step_noise, solver);
-        if (!ctx->gexec || key != ctx->gkey) {
-            drop_graphs(ctx);
-            // Eager warm-up of the exact step sequence first: the first launch of a kernel inside a
-            // stream capture hangs on ROCm 7.2 (lazy per-kernel initialisation is not capturable).
-            // The step is run on step index 0 and its effect on the latents is undone afterwards.
-            TRACE("loop: warmup begin");
-            g.step_inc = ctx->step_dev;   // the first kernel of the step (conv_in) advances the step counter itself
-            run_unet(ctx, g, s);
-            TRACE("loop: warmup unet launched");
-            if (!fused) {
-                if (sa.guidance_rescale > 0.f) launch_rescale_partials(sa, ctx->rescale_part, s);
-                launch_sched_step(sa, solver, osa.x0h, s);
-                ++ctx->n_sched_step;
-            }
-            launch_tm_to_cm(p->latents_dev, ctx->x_cm, B, T, C, g.Tp, xs, s);
-            HIPCHK(hipMemsetAsync(ctx->step_dev, 0xFF, sizeof(int), s));
-            HIPCHK(hipStreamSynchronize(s));
-            TRACE("loop: warmup synced");
-            // A launch helper that refused a shape launched NOTHING (launch_fault / launch_err): a graph captured from the same schedule would be
-            // missing that kernel and — cached under this key — replay silently wrong on every later call.  So the faults of the warm-up and of
-            // each capture are consumed HERE, on the thread that drove them, in the prepare-only path too, and nothing is cached.
-            auto loop_fault = [&]() -> bool { return launch_fault_peek() != nullptr || !ctx->launch_err.empty(); };
-            if (loop_fault()) { drop_graphs(ctx); LAUNCHCHK(); }
-            // capture on a private stream: the caller's stream may be the legacy default stream,
-            // which cannot be captured; the instantiated graph is then replayed on the caller's stream
-            if (ensure_cap_streams(ctx)) return -1;
-            hipStream_t cs = ctx->cap_stream;
-            auto capture_steps = [&](int nsteps, hipGraph_t* gr, hipGraphExec_t* ge) -> int {
-                HIPCHK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-                for (int rep = 0; rep < nsteps; ++rep) {
-                    run_unet(ctx, g, cs);
-                    if (!fused) {
-                        if (sa.guidance_rescale > 0.f) launch_rescale_partials(sa, ctx->rescale_part, cs);
-                        launch_sched_step(sa, solver, osa.x0h, cs);
-                        ++ctx->n_sched_step;
-                    }
-                }
-                TRACE("loop: capture recorded");
-                hipError_t e = hipStreamEndCapture(cs, gr);
-                if (e != hipSuccess) return fail(ctx, "hipStreamEndCapture: %s", hipGetErrorString(e));
-                HIPCHK(hipGraphInstantiate(ge, *gr, nullptr, nullptr, 0));
-                return 0;
-            };
-            if (capture_steps(spg, &ctx->graph, &ctx->gexec)) { drop_graphs(ctx); release_cap_streams(ctx); return -1; }
-            if (loop_fault()) { drop_graphs(ctx); release_cap_streams(ctx); LAUNCHCHK(); }
-            if (rem > 0 && capture_steps(rem, &ctx->graph_rem, &ctx->gexec_rem)) { drop_graphs(ctx); release_cap_streams(ctx); return -1; }
-            if (loop_fault()) { drop_graphs(ctx); release_cap_streams(ctx); LAUNCHCHK(); }
-            size_t nn = 0;
-            (void)hipGraphGetNodes(ctx->graph, nullptr, &nn);
-            ctx->gnodes = (int)nn / spg;
-            ctx->gspg = spg;
-            ctx->gkey = key;
-            release_cap_streams(ctx);
-            TRACE("loop: graph instantiated");
-        }
+        const std::vector<long long> key = loop_graph_key(ctx, p, la.sa.step_noise, solver);
+        if ((!ctx->gexec || key != ctx->gkey) && build_step_graphs(ctx, p, g, la, s, spg, rem, key)) return -1;
         if (prepare_only) return 0;
         for (int k = 0; k < N / ctx->gspg; ++k) HIPCHK(hipGraphLaunch(ctx->gexec, s));
         if (rem > 0) HIPCHK(hipGraphLaunch(ctx->gexec_rem, s));
     }
     TRACE("loop: graphs launched");
-    launch_finish(ctx->x_cm, xs, g.Tp, B, T, C, p->latent_scale, p->latents_dev, p->result_dev, s, ctx->dbg_stop < 0 ? ctx->status_dev : nullptr);
+    launch_finish(ctx->x_cm, (long long)C * g.Tp, g.Tp, B, T, C, p->latent_scale, p->latents_dev, p->result_dev, s, ctx->dbg_stop < 0 ? ctx->status_dev : nullptr);
     LAUNCHCHK();
     HIPCHK(hipGetLastError());
     return 0;
@@ -567,28 +597,34 @@ int said_denoise_loop(said_ctx* ctx, const said_loop_params* p, void* stream) { 
 
 int said_loop_prepare(said_ctx* ctx, const said_loop_params* p, void* stream) { return loop_impl(ctx, p, stream, true); }
 
+// said_ddim_step / said_solver_step after their own argument checks: the coefficient row's upload and the launch
+static int step_flat(said_ctx* ctx, int solver, const float* model_out_dev, const float* uncond_dev, float guidance_scale, const float* sample_dev, const float* coef_host,
+                     int prediction_type, float* x0_hist_dev, const float* step_noise_dev, const float* init_latents_dev, const float* edit_noise_dev, const float* mask_dev,
+                     float* prev_sample_dev, int64_t n, hipStream_t s) {
+    HIPCHK(hipMemcpyAsync(ctx->coef1_dev, coef_host, 8 * sizeof(float), hipMemcpyHostToDevice, s));
+    if (n > 0)
+        launch_step_flat(solver, model_out_dev, uncond_dev, guidance_scale, sample_dev, ctx->coef1_dev, prediction_type, x0_hist_dev, step_noise_dev, init_latents_dev,
+                         edit_noise_dev, mask_dev, prev_sample_dev, n, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int said_ddim_step(said_ctx* ctx, const float* eps_dev, const float* eps_uncond_dev, float guidance_scale,
                    const float* sample_dev, const float* coef_host, int prediction_type, const float* step_noise_dev,
                    const float* init_latents_dev, const float* edit_noise_dev, const float* mask_dev, float* prev_sample_dev,
                    int64_t n, void* stream) {
     if (!ctx) return -1;
-    hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
     if (prediction_type < 0 || prediction_type > 2) return fail(ctx, "bad prediction_type %d", prediction_type);
     if (mask_dev && !(init_latents_dev && edit_noise_dev)) return fail(ctx, "mask needs init_latents_dev and edit_noise_dev");
-    HIPCHK(hipMemcpyAsync(ctx->coef1_dev, coef_host, 8 * sizeof(float), hipMemcpyHostToDevice, s));
-    if (n > 0)
-        launch_ddim_flat(eps_dev, eps_uncond_dev, guidance_scale, sample_dev, ctx->coef1_dev, prediction_type, step_noise_dev,
-                         init_latents_dev, edit_noise_dev, mask_dev, prev_sample_dev, n, s);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return step_flat(ctx, 0, eps_dev, eps_uncond_dev, guidance_scale, sample_dev, coef_host, prediction_type, nullptr, step_noise_dev, init_latents_dev, edit_noise_dev, mask_dev,
+                     prev_sample_dev, n, (hipStream_t)stream);
 }
 
 int said_solver_step(said_ctx* ctx, const float* model_out_dev, const float* uncond_dev, float guidance_scale, const float* sample_dev,
                      const float* coef_host, int prediction_type, float* x0_hist_dev, const float* step_noise_dev, const float* init_latents_dev,
                      const float* edit_noise_dev, const float* mask_dev, float* prev_sample_dev, int64_t n, void* stream) {
     if (!ctx) return -1;
-    hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
     if (prediction_type < 0 || prediction_type > 2) return fail(ctx, "bad prediction_type %d", prediction_type);
     if (!coef_host) return fail(ctx, "said_solver_step: coef_host must not be null");
@@ -599,12 +635,8 @@ int said_solver_step(said_ctx* ctx, const float* model_out_dev, const float* unc
         return fail(ctx, "said_solver_step: solver code %g in column 7 is not DDPM (1) or DPM-Solver++ (2, 3); DDIM rows go to said_ddim_step", (double)v);
     if (code >= 2 && step_noise_dev) return fail(ctx, "said_solver_step: DPM-Solver++ rows draw no step noise");
     if (code >= 2 && !x0_hist_dev) return fail(ctx, "said_solver_step: DPM-Solver++ rows need x0_hist_dev");
-    HIPCHK(hipMemcpyAsync(ctx->coef1_dev, coef_host, 8 * sizeof(float), hipMemcpyHostToDevice, s));
-    if (n > 0)
-        launch_solver_flat(model_out_dev, uncond_dev, guidance_scale, sample_dev, ctx->coef1_dev, prediction_type, x0_hist_dev, step_noise_dev,
-                           init_latents_dev, edit_noise_dev, mask_dev, prev_sample_dev, n, s);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return step_flat(ctx, 1, model_out_dev, uncond_dev, guidance_scale, sample_dev, coef_host, prediction_type, x0_hist_dev, step_noise_dev, init_latents_dev, edit_noise_dev,
+                     mask_dev, prev_sample_dev, n, (hipStream_t)stream);
 }
 
 int said_axpby(said_ctx* ctx, const float* a_host, const float* x_dev, const float* c_host, const float* y_dev, float* out_dev,

@@ -188,70 +188,54 @@ void launch_attn2q(const AttnArgs& a, int batch, hipStream_t s);
 void configure_attn2q_kernel();
 void launch_battn(const AttnArgs& a, int batch, hipStream_t s);
 
-struct SchedArgs {
-    const float* eps;          // channel-major [Be][C][pitch] model output
-    long long eps_bstride;
-    int pitch;
-    int B, T, C;
-    int cfg;                   // 1: eps = e_c + s*(e_c - e_u), uncond half first (diffusion.py:430-434)
-    float guidance_scale;
-    float guidance_rescale;    // > 0: rescale_noise_cfg using rescale_stats
-    const float* rescale_part; // [B][2][nblk][3] partial (n, mean, M2) of e_c and eps_cfg
-    int rescale_nblk;
-    int prediction_type;
-    const float* coef;         // device [nsteps][8]
+// The operands of the update that ends a denoise step (sched_math.h: step_update), common to the unfused route (SchedArgs) and the fused one (OutSchedArgs).
+// (The field order is part of out_sched_kernel's tuning: it decides how the compiler groups the scalar loads of the argument block, and with that the kernel's
+// schedule — profiles/r07b_step_update_ab.txt has a measured example.  Re-measure the headline after reordering.)
+struct StepUpdateArgs {
+    const float* coef;         // device [nsteps][8] scheduler coefficients
     const int* step_ptr;       // device step counter
     float* x;                  // latents, channel-major [B][C][pitch], updated in place
-    long long x_bstride;
     const float* step_noise;   // channel-major [nsteps][B][C][pitch] or null
-    const float* init;         // channel-major or null
+    const float* init;         // channel-major or null (editing)
     const float* edit_noise;
     const float* mask;
     float* inter;              // token-major (nsteps, B, T, C) or null: pre-step latents / latent_scale
+    long long x_bstride;
+    int pitch, T, B, C;
+    int cfg;                   // 1: model output = e_c + s*(e_c - e_u), samples [0, B) unconditional, [B, 2B) conditional (diffusion.py:397-400, 430-434)
+    int prediction_type;
+    float guidance_scale;
+    float guidance_rescale;    // > 0: rescale_noise_cfg (needs whole-output statistics: the unfused route only)
     float latent_scale;
     const unsigned* noise_seed;   // device [2] Philox key: the eta noise is generated in the kernel (sched_math.h), or null
     unsigned noise_elem0;         // element index of this call's first clip in the whole batch (clip groups on concurrent streams draw the noise of ONE batch)
-    int* status;                  // device [2] sticky numeric status (said_numeric_status): [0] <- 1 + the first step whose model output was not finite, or null
+    int* status;               // device [2] sticky numeric status (said_numeric_status): [0] <- 1 + the first step whose model output was not finite, or null
+    float* x0h;                // DPM-Solver++'s previous-step x0, channel-major like x (read by order-2 rows, written by every DPM row); null for a DDIM table
+    int solver;                // 0 = the table's rows are DDIM (sched_math.h ddim_prev), 1 = DDPM / DPM-Solver++ rows (solver_prev, x0h); a table never mixes the two
 };
-// sched_step_kernel<1>'s arguments: DPM-Solver++'s previous-step x0, channel-major like x (read by order-2 rows, written by every DPM row).
-// (A separate type, so that the DDIM kernel's argument block — and its code — stays as it was.)
-struct SolverSchedArgs : SchedArgs {
-    float* x0h;
+struct SchedArgs : StepUpdateArgs {
+    const float* eps;          // channel-major [Be][C][pitch] model output
+    long long eps_bstride;
+    const float* rescale_part; // [B][2][nblk][3] partial (n, mean, M2) of e_c and eps_cfg
+    int rescale_nblk;
 };
-// solver: 0 = the table's rows are DDIM (sched_math.h ddim_prev), 1 = DDPM / DPM-Solver++ rows (solver_prev, x0h); a table never mixes the two
-void launch_sched_step(const SchedArgs& a, int solver, float* x0h, hipStream_t s);
+void launch_sched_step(const SchedArgs& a, hipStream_t s);
 
-// out conv (GN -> SiLU -> Conv1d(192 -> Cout, k3)) + guidance + DDIM update in one kernel (out_sched.hip)
-struct OutSchedArgs {
-    const float* x;            // last hidden state, channel-major [Be][192][pitch]
+// out conv (GN -> SiLU -> Conv1d(192 -> C, k3)) + guidance + the step's update in one kernel (out_sched.hip)
+struct OutSchedArgs : StepUpdateArgs {
+    const float* h;            // last hidden state, channel-major [Be][192][pitch]
     const float* gn_part;      // its GroupNorm partials [Be][192][gn_nparts][2]
     const float* gn_gamma;     // out.0
     const float* gn_beta;
     const float* w4;           // out.2 weights, dwordx4 packing [1][3][24][64][4] (+ out.0's gamma[192], beta[192] behind)
     const float* ws;           // the same in the split-fp16 packing (Seg::ws layout, one tile; same tail), or null: fp32 matrix instructions
     const float* bias;
-    const float* coef;         // device [nsteps][8] scheduler coefficients
-    const int* step_ptr;       // device step counter
-    float* lat;                // latents, channel-major [B][Cout][pitch], updated in place
-    const float* step_noise;   // channel-major [nsteps][B][Cout][pitch] or null
-    const float* init;         // channel-major or null (editing)
-    const float* edit_noise;
-    const float* mask;
-    float* inter;              // token-major (nsteps, B, T, Cout) or null: pre-step latents / latent_scale
-    long long x_bstride, gn_part_bstride, lat_bstride;
-    int pitch, T, B, Cin, Cout, gn_nparts;
-    int cfg;                   // 1: samples [0, B) unconditional, [B, 2B) conditional
-    int prediction_type;
-    float guidance_scale, guidance_rescale, latent_scale;
-    const unsigned* noise_seed;   // device [2] Philox key: eta noise generated in the kernel (sched_math.h), or null
-    unsigned noise_elem0;         // see SchedArgs
+    long long h_bstride, gn_part_bstride;
+    int Cin, gn_nparts;
     // out_sched_tm_kernel (bf16 large-batch schedule): the last hidden state token-major bf16 [Be][seg][192], out.2 weights bf16 [32][3 taps][192]
     const void* x_tm;
     const void* wb;
     int seg;
-    int* status;               // see SchedArgs
-    float* x0h;                // see SolverSchedArgs (channel-major like lat)
-    int solver;                // see launch_sched_step
 };
 bool out_sched_supports(const OutSchedArgs& a);
 bool out_sched_tm_supports(const OutSchedArgs& a);
@@ -260,13 +244,10 @@ void launch_out_sched(const OutSchedArgs& a, hipStream_t s);
 void configure_out_sched_kernel();
 // pre-pass for guidance_rescale > 0: per-block Welford partials of e_c and eps_cfg
 void launch_rescale_partials(const SchedArgs& a, float* part_out, hipStream_t s);
-// standalone elementwise scheduler step on token-major buffers (said_ddim_step)
-void launch_ddim_flat(const float* eps, const float* eps_u, float gs, const float* x, const float* coef_dev, int pred,
-                      const float* noise, const float* init, const float* edit_noise, const float* mask, float* out,
-                      long long n, hipStream_t s);
-// standalone DDPM / DPM-Solver++ step on token-major buffers (said_solver_step); x0h: in / out x0 history (DPM rows), may be null for DDPM
-void launch_solver_flat(const float* mo, const float* mo_u, float gs, const float* x, const float* coef_dev, int pred, float* x0h,
-                        const float* noise, const float* init, const float* edit_noise, const float* mask, float* out, long long n, hipStream_t s);
+// standalone elementwise scheduler step on token-major buffers (said_ddim_step, said_solver_step): one coefficient row over n values.
+// solver as in StepUpdateArgs; x0h: in / out x0 history of DPM-Solver++ rows (unused by DDIM and DDPM rows, may be null for them)
+void launch_step_flat(int solver, const float* mo, const float* mo_u, float gs, const float* x, const float* coef_dev, int pred, float* x0h,
+                      const float* noise, const float* init, const float* edit_noise, const float* mask, float* out, long long n, hipStream_t s);
 // out[b][i] = a[b]*x[b][i] + c[b]*y[b][i] (explicitly rounded mul, mul, add); coefficients live in device memory
 void launch_axpby(const float* a_dev, const float* x, const float* c_dev, const float* y, float* out, int B, long long n,
                   hipStream_t s);

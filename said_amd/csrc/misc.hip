@@ -4,7 +4,6 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <type_traits>
 
 #include "kernels.h"
 #include "sched_math.h"
@@ -210,9 +209,9 @@ void launch_rescale_partials(const SchedArgs& a, float* part_out, hipStream_t s)
     hipLaunchKernelGGL(rescale_partials_kernel, grid, dim3(256), 0, s, a, part_out);
 }
 
-// SF: the solver family of the table (launch_sched_step): 0 = DDIM, 1 = DDPM / DPM-Solver++ (x0 history in a.x0h)
+// SF: the solver family of the table (a.solver): 0 = DDIM, 1 = DDPM / DPM-Solver++ (x0 history in a.x0h)
 template <int SF>
-__global__ void sched_step_kernel(const std::conditional_t<SF == 0, SchedArgs, SolverSchedArgs> a) {
+__global__ void sched_step_kernel(const SchedArgs a) {
     const int c = blockIdx.y, b = blockIdx.z;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int step = *a.step_ptr;
@@ -256,40 +255,20 @@ __global__ void sched_step_kernel(const std::conditional_t<SF == 0, SchedArgs, S
     }
     float* xp = a.x + (long long)b * a.x_bstride + off;
     const float x = *xp;
-    note_nonfinite(e, a.status, step);
-    if (a.inter) a.inter[(((long long)step * a.B + b) * a.T + t) * a.C + c] = x / a.latent_scale;
-    float prev;
-    if constexpr (SF == 0) {
-        prev = ddim_prev(e, x, cf, a.prediction_type);
-    } else {
-        const int code = solver_code(cf);
-        float* hp = a.x0h + (long long)b * a.x_bstride + off;
-        float x0n = 0.f;
-        prev = solver_prev(e, x, cf, a.prediction_type, code == SOLVER_DPM2 ? *hp : 0.f, x0n);
-        if (code >= SOLVER_DPM1) *hp = x0n;
-    }
-    if (a.step_noise) {
-        const float nz = a.step_noise[((long long)step * a.B + b) * a.x_bstride + off];
-        prev = __fadd_rn(prev, __fmul_rn(cf[4], nz));
-    } else if (a.noise_seed) {
-        prev = __fadd_rn(prev, __fmul_rn(cf[4], philox_normal(a.noise_seed[0], a.noise_seed[1], (unsigned)step, a.noise_elem0 + (unsigned)((b * a.T + t) * a.C + c))));
-    }
-    if (a.mask) {
-        const long long o2 = (long long)b * a.x_bstride + off;
-        prev = mask_blend(prev, a.init[o2], a.edit_noise[o2], a.mask[o2], cf);
-    }
-    *xp = prev;
+    const long long o2 = (long long)b * a.x_bstride + off;
+    const int code = SF != 0 ? solver_code(cf) : SOLVER_DDIM;
+    const StepNoise nz = {a.step_noise != nullptr, a.step_noise ? a.step_noise[((long long)step * a.B + b) * a.x_bstride + off] : 0.f, a.noise_seed,
+                          a.noise_elem0, (unsigned)((b * a.T + t) * a.C + c)};
+    const StepResult r = step_update<SF>(e, x, cf, a.prediction_type, code == SOLVER_DPM2 ? a.x0h[o2] : 0.f, step, nz, a.mask != nullptr, a.mask ? a.init[o2] : 0.f,
+                                         a.mask ? a.edit_noise[o2] : 0.f, a.mask ? a.mask[o2] : 0.f, a.status, a.inter != nullptr,
+                                         a.inter + (((long long)step * a.B + b) * a.T + t) * a.C + c, a.latent_scale);
+    if (code >= SOLVER_DPM1) a.x0h[o2] = r.x0;
+    *xp = r.prev;
 }
-void launch_sched_step(const SchedArgs& a, int solver, float* x0h, hipStream_t s) {
+void launch_sched_step(const SchedArgs& a, hipStream_t s) {
     dim3 grid((a.T + 63) / 64, a.C, a.B);
-    if (solver == 0) {
-        hipLaunchKernelGGL(sched_step_kernel<0>, grid, dim3(64), 0, s, a);
-    } else {
-        SolverSchedArgs sa;
-        static_cast<SchedArgs&>(sa) = a;
-        sa.x0h = x0h;
-        hipLaunchKernelGGL(sched_step_kernel<1>, grid, dim3(64), 0, s, sa);
-    }
+    if (a.solver == 0) hipLaunchKernelGGL(sched_step_kernel<0>, grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(sched_step_kernel<1>, grid, dim3(64), 0, s, a);
 }
 
 __global__ void philox_normal_kernel(const unsigned* __restrict__ seed, int step0, long long n_per_step, long long n, float* __restrict__ out) {
@@ -302,49 +281,28 @@ void launch_philox_normal(const unsigned* seed_dev, int step0, int nsteps, long 
     if (n > 0) hipLaunchKernelGGL(philox_normal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, seed_dev, step0, n_per_step, n, out);
 }
 
-__global__ void ddim_flat_kernel(const float* __restrict__ eps, const float* __restrict__ eps_u, float gs,
-                                 const float* __restrict__ x, const float* __restrict__ cf, int pred,
+// said_ddim_step (SF = 0) / said_solver_step (SF = 1): one coefficient row over n values, the update as in the loop
+template <int SF>
+__global__ void step_flat_kernel(const float* __restrict__ mo, const float* __restrict__ mo_u, float gs,
+                                 const float* __restrict__ x, const float* __restrict__ cf, int pred, float* __restrict__ x0h,
                                  const float* __restrict__ noise, const float* __restrict__ init,
                                  const float* __restrict__ enoise, const float* __restrict__ mask, float* __restrict__ out,
                                  long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float e = eps[i];
-    if (eps_u) e = cfg_combine(e, eps_u[i], gs);
-    float prev = ddim_prev(e, x[i], cf, pred);
-    if (noise) prev = __fadd_rn(prev, __fmul_rn(cf[4], noise[i]));
-    if (mask) prev = mask_blend(prev, init[i], enoise[i], mask[i], cf);
-    out[i] = prev;
-}
-void launch_ddim_flat(const float* eps, const float* eps_u, float gs, const float* x, const float* coef_dev, int pred,
-                      const float* noise, const float* init, const float* edit_noise, const float* mask, float* out,
-                      long long n, hipStream_t s) {
-    hipLaunchKernelGGL(ddim_flat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, eps, eps_u, gs, x, coef_dev, pred,
-                       noise, init, edit_noise, mask, out, n);
-}
-
-// said_solver_step: one DDPM / DPM-Solver++ row over n values, solver_prev as in the loop
-__global__ void solver_flat_kernel(const float* __restrict__ mo, const float* __restrict__ mo_u, float gs,
-                                   const float* __restrict__ x, const float* __restrict__ cf, int pred, float* __restrict__ x0h,
-                                   const float* __restrict__ noise, const float* __restrict__ init,
-                                   const float* __restrict__ enoise, const float* __restrict__ mask, float* __restrict__ out,
-                                   long long n) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int code = solver_code(cf);
+    const int code = SF != 0 ? solver_code(cf) : SOLVER_DDIM;
     float e = mo[i];
     if (mo_u) e = cfg_combine(e, mo_u[i], gs);
-    float x0n = 0.f;
-    float prev = solver_prev(e, x[i], cf, pred, code == SOLVER_DPM2 ? x0h[i] : 0.f, x0n);
-    if (code >= SOLVER_DPM1) x0h[i] = x0n;
-    if (noise) prev = __fadd_rn(prev, __fmul_rn(cf[4], noise[i]));
-    if (mask) prev = mask_blend(prev, init[i], enoise[i], mask[i], cf);
-    out[i] = prev;
+    const StepNoise nz = {noise != nullptr, noise ? noise[i] : 0.f, nullptr, 0u, 0u};
+    const StepResult r = step_update<SF>(e, x[i], cf, pred, code == SOLVER_DPM2 ? x0h[i] : 0.f, 0, nz, mask != nullptr, mask ? init[i] : 0.f, mask ? enoise[i] : 0.f,
+                                         mask ? mask[i] : 0.f, nullptr);
+    if (code >= SOLVER_DPM1) x0h[i] = r.x0;
+    out[i] = r.prev;
 }
-void launch_solver_flat(const float* mo, const float* mo_u, float gs, const float* x, const float* coef_dev, int pred, float* x0h,
-                        const float* noise, const float* init, const float* edit_noise, const float* mask, float* out, long long n, hipStream_t s) {
-    hipLaunchKernelGGL(solver_flat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, mo, mo_u, gs, x, coef_dev, pred, x0h,
-                       noise, init, edit_noise, mask, out, n);
+void launch_step_flat(int solver, const float* mo, const float* mo_u, float gs, const float* x, const float* coef_dev, int pred, float* x0h,
+                      const float* noise, const float* init, const float* edit_noise, const float* mask, float* out, long long n, hipStream_t s) {
+    const auto k = solver == 0 ? step_flat_kernel<0> : step_flat_kernel<1>;
+    hipLaunchKernelGGL(k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, mo, mo_u, gs, x, coef_dev, pred, x0h, noise, init, edit_noise, mask, out, n);
 }
 
 __global__ void axpby_kernel(const float* __restrict__ a, const float* __restrict__ x, const float* __restrict__ c,

@@ -8,10 +8,14 @@
 // Structure = gemm_lds.hip's 3-tap GroupNorm variant: 8 waves split the 192 input channels, each stages its
 // 24-channel x 32-token slice (per half) through a wave-private LDS tile after applying GroupNorm+SiLU once, the
 // main loop is ds_read + v_mfma_f32_32x32x2_f32, the split-K partials are summed through LDS in a fixed order.
-// The scheduler arithmetic is sched_math.h's explicitly rounded op sequence, so given the same model output the
-// update is bit-identical to the stand-alone scheduler kernel (and to oracle/scheduler.py).
+// The scheduler arithmetic is sched_math.h's step_update — the explicitly rounded op sequence every scheduler kernel calls — so
+// given the same model output the update is bit-identical to the stand-alone scheduler kernel (and to oracle/scheduler.py).
+// out_sched_kernel and out_sched_tm_kernel (below) keep their own staging, GroupNorm and matrix loops and share OutEpilogue:
+// the request of the update's operands and, after the split-K reduction, its application and stores.
 // guidance_rescale > 0 needs per-sample standard deviations of the whole model output (rescale_noise_cfg): that case
 // keeps the unfused path (conv -> partial statistics -> sched_step_kernel).
+#include <type_traits>
+
 #include "gemm_common.h"
 #include "sched_math.h"
 
@@ -19,6 +23,77 @@ namespace said {
 
 constexpr int OS_KS = 8, OS_C = 192, OS_CW = OS_C / OS_KS, OS_XP = 40;
 static_assert(OS_CW == 24, "one 24-channel block per wave");
+
+// The scheduler epilogue of both kernels.  After the matrix instructions, lane == token t0 + (l & 31) and the NW waves' split-K partials of the 32 output
+// channels lie in `red` [NW][NH][16][64]; wave w finishes ROWS = 16 / NW of the 16 accumulator rows (r = w + j * NW: channel (r & 3) + 8 * (r >> 2) + 4 * (l >> 5)).
+// request(): the buffer resources and the loads of a row's latent, noise, init, edit noise, mask, x0 history and bias — a kernel calls it where it wants these
+// requests issued (their place among the kernel's other loads is part of its tuning).  apply(): the fixed-order split-K sum + bias, guidance, sched_math.h's
+// step_update and the stores.  The object holds only what request() loaded (the step index and the token are the kernel's: kept in the object they changed the
+// schedule of the whole kernel, profiles/r07b_step_update_ab.txt).  Out-of-range elements (token >= T, channel >= C) load through offset 0x80000000 (the buffer's bounds check returns 0) and store nothing.
+template <bool CFG, int SF, int ROWS, int NW>
+struct OutEpilogue {
+    static constexpr int NH = CFG ? 2 : 1;
+    float cfv[8];
+    float e_x[ROWS], e_nz[ROWS], e_in[ROWS], e_en[ROWS], e_mk[ROWS], e_bias[ROWS], e_h[ROWS];
+    int e_n[ROWS];
+
+    __device__ __forceinline__ void request(const OutSchedArgs& a, int step, int T, int b, int t0, int w, int lt, int lh) {
+        const float* cf = a.coef + step * 8;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) cfv[i] = cf[i];
+        const int t = t0 + lt;
+        const bool tok = t < T;
+        const unsigned bytes = (unsigned)a.C * (unsigned)a.pitch * 4u;
+        const rsrc_t rlat = make_rsrc(a.x + (long long)b * a.x_bstride, bytes);
+        const rsrc_t rnz = make_rsrc(a.step_noise ? a.step_noise + ((long long)step * a.B + b) * a.x_bstride : nullptr, a.step_noise ? bytes : 0u);
+        const rsrc_t rin = make_rsrc(a.mask ? a.init + (long long)b * a.x_bstride : nullptr, a.mask ? bytes : 0u);
+        const rsrc_t ren = make_rsrc(a.mask ? a.edit_noise + (long long)b * a.x_bstride : nullptr, a.mask ? bytes : 0u);
+        const rsrc_t rmk = make_rsrc(a.mask ? a.mask + (long long)b * a.x_bstride : nullptr, a.mask ? bytes : 0u);
+        const bool want_h = SF != 0 && solver_code(cfv) == SOLVER_DPM2;   // (order 2 reads the previous step's x0)
+        const rsrc_t rh = make_rsrc(SF != 0 ? a.x0h + (long long)b * a.x_bstride : nullptr, SF != 0 ? bytes : 0u);
+#pragma unroll
+        for (int j = 0; j < ROWS; ++j) {
+            const int r = w + j * NW;
+            const int n = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            e_n[j] = n;
+            const int vo = (tok && n < a.C) ? (n * a.pitch + t) * 4 : (int)0x80000000;
+            e_x[j] = bload(rlat, vo, 0);
+            e_nz[j] = bload(rnz, vo, 0);
+            e_in[j] = bload(rin, vo, 0);
+            e_en[j] = bload(ren, vo, 0);
+            e_mk[j] = bload(rmk, vo, 0);
+            if constexpr (SF != 0) e_h[j] = bload(rh, want_h ? vo : (int)0x80000000, 0);
+            e_bias[j] = a.bias[n < a.C ? n : 0];
+        }
+    }
+
+    __device__ __forceinline__ void apply(const OutSchedArgs& a, const float* red, int step, int T, int b, int t0, int w, int l) const {
+        const int t = t0 + (l & 31);
+        const bool tok = t < T;
+        float* latp = a.x + (long long)b * a.x_bstride;
+#pragma unroll
+        for (int j = 0; j < ROWS; ++j) {
+            const int r = w + j * NW;
+            float eh[NH];
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                float s = 0.f;
+#pragma unroll
+                for (int w2 = 0; w2 < NW; ++w2) s += red[((w2 * NH + h) * 16 + r) * 64 + l];
+                eh[h] = s + e_bias[j];
+            }
+            const float e = CFG ? cfg_combine(eh[NH - 1], eh[0], a.guidance_scale) : eh[0];
+            const int n = e_n[j];
+            if (!(tok && n < a.C)) continue;
+            const float x = e_x[j];
+            const StepNoise nz = {a.step_noise != nullptr, e_nz[j], a.noise_seed, a.noise_elem0, (unsigned)((b * T + t) * a.C + n)};
+            const StepResult u = step_update<SF>(e, x, cfv, a.prediction_type, SF != 0 ? e_h[j] : 0.f, step, nz, a.mask != nullptr, e_in[j], e_en[j], e_mk[j], a.status,
+                                                 a.inter != nullptr, a.inter + (((long long)step * a.B + b) * T + t) * a.C + n, a.latent_scale);
+            if (SF != 0 && solver_code(cfv) >= SOLVER_DPM1) a.x0h[(long long)b * a.x_bstride + (long long)n * a.pitch + t] = u.x0;
+            latp[(long long)n * a.pitch + t] = u.prev;
+        }
+    }
+};
 
 // SP (round 5, the default): the convolution on split-fp16 operands (split_f16.h; gemm_lds.hip SP): the wave-private tile is token-major, two fp16 planes [34 rows][24 channels],
 // the weights out.2 in engine.cpp's pack_rows_split layout (a.ws: [8 blocks][5 k16 steps][2 planes][64 lanes][8 halfs], GroupNorm affine behind) — 30 v_mfma_f32_32x32x16_f16
@@ -75,38 +150,9 @@ __global__ __launch_bounds__(64 * OS_KS) void out_sched_kernel(const float* hx, 
 #pragma unroll
         for (int i1 = 0; i1 < WD1; ++i1)
             wv[i0][i1] = SP ? bload4(rw, l * 16, ((w * 5 + i0) * 2 + i1) * 1024) : bload4(rw, l * 16, (i0 * (OS_C / 8) + 3 * w + i1) * 1024);
-    // epilogue operands of this wave's two output rows (channels n0, n1 of token t0 + lt)
+    OutEpilogue<CFG, SF, 16 / OS_KS, OS_KS> epi;   // (this wave's two output rows)
     const int step = *hstep;
-    const float* cf = a.coef + step * 8;
-    float cfv[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) cfv[i] = cf[i];
-    const int t = t0 + lt;
-    const bool tok = t < T;
-    const rsrc_t rlat = make_rsrc(a.lat + (long long)b * a.lat_bstride, (unsigned)a.Cout * (unsigned)a.pitch * 4u);
-    const rsrc_t rnz = make_rsrc(a.step_noise ? a.step_noise + ((long long)step * a.B + b) * a.lat_bstride : nullptr,
-                                 a.step_noise ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
-    const rsrc_t rin = make_rsrc(a.mask ? a.init + (long long)b * a.lat_bstride : nullptr, a.mask ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
-    const rsrc_t ren = make_rsrc(a.mask ? a.edit_noise + (long long)b * a.lat_bstride : nullptr, a.mask ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
-    const rsrc_t rmk = make_rsrc(a.mask ? a.mask + (long long)b * a.lat_bstride : nullptr, a.mask ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
-    float e_x[2], e_nz[2], e_in[2], e_en[2], e_mk[2], e_bias[2], e_h[2];
-    int e_n[2];
-    const bool want_h = SF != 0 && solver_code(cfv) == SOLVER_DPM2;   // (order 2 reads the previous step's x0)
-    const rsrc_t rh = make_rsrc(SF != 0 ? a.x0h + (long long)b * a.lat_bstride : nullptr, SF != 0 ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int r = w + j * OS_KS;
-        const int n = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        e_n[j] = n;
-        const int vo = (tok && n < a.Cout) ? (n * a.pitch + t) * 4 : (int)0x80000000;
-        e_x[j] = bload(rlat, vo, 0);
-        e_nz[j] = bload(rnz, vo, 0);
-        e_in[j] = bload(rin, vo, 0);
-        e_en[j] = bload(ren, vo, 0);
-        e_mk[j] = bload(rmk, vo, 0);
-        if constexpr (SF != 0) e_h[j] = bload(rh, want_h ? vo : (int)0x80000000, 0);
-        e_bias[j] = a.bias[n < a.Cout ? n : 0];
-    }
+    epi.request(a, step, T, b, t0, w, lt, lh);
 
     // ---- GroupNorm coefficients of the wave's own 24 channels, per half ----
 #pragma unroll
@@ -210,74 +256,16 @@ __global__ __launch_bounds__(64 * OS_KS) void out_sched_kernel(const float* hx, 
         for (int r = 0; r < 16; ++r) red[((w * NH + h) * 16 + r) * 64 + l] = acc[h][r];
     __syncthreads();
 
-    // ---- epilogue: bias, guidance, DDIM update, noise, mask blend; latents updated in place ----
-    float* latp = a.lat + (long long)b * a.lat_bstride;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int r = w + j * OS_KS;
-        float eh[NH];
-#pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            float s = 0.f;
-#pragma unroll
-            for (int w2 = 0; w2 < OS_KS; ++w2) s += red[((w2 * NH + h) * 16 + r) * 64 + l];
-            eh[h] = s + e_bias[j];
-        }
-        const float e = CFG ? cfg_combine(eh[NH - 1], eh[0], a.guidance_scale) : eh[0];
-        const int n = e_n[j];
-        if (!(tok && n < a.Cout)) continue;
-        const float x = e_x[j];
-        note_nonfinite(e, a.status, step);
-        if (a.inter) a.inter[(((long long)step * a.B + b) * T + t) * a.Cout + n] = x / a.latent_scale;
-        float prev;
-        if constexpr (SF == 0) {
-            prev = ddim_prev(e, x, cfv, a.prediction_type);
-        } else {
-            float x0n = 0.f;
-            prev = solver_prev(e, x, cfv, a.prediction_type, e_h[j], x0n);
-            if (solver_code(cfv) >= SOLVER_DPM1) a.x0h[(long long)b * a.lat_bstride + (long long)n * a.pitch + t] = x0n;
-        }
-        if (a.step_noise) prev = __fadd_rn(prev, __fmul_rn(cfv[4], e_nz[j]));
-        else if (a.noise_seed) prev = __fadd_rn(prev, __fmul_rn(cfv[4], philox_normal(a.noise_seed[0], a.noise_seed[1], (unsigned)step, a.noise_elem0 + (unsigned)((b * T + t) * a.Cout + n))));
-        if (a.mask) prev = mask_blend(prev, e_in[j], e_en[j], e_mk[j], cfv);
-        latp[(long long)n * a.pitch + t] = prev;
-    }
+    epi.apply(a, red, step, T, b, t0, w, l);
 }
-
-template <bool CFG, int SF> __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a);   // (below)
 static int out_sched_smem(bool cfg) {   // (the split-fp16 tile is the smaller one: 2 x 34 x 24 halfs against 24 x 40 floats)
     const int nh = cfg ? 2 : 1;
     const int stage = OS_KS * nh * OS_CW * OS_XP, red = OS_KS * nh * 16 * 64;
     return (nh * 2 * OS_C + OS_KS * GN_SCRATCH + (stage > red ? stage : red)) * (int)sizeof(float);
 }
-void configure_out_sched_kernel() {
-#define OS_ATTR(K, BYTES) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, BYTES)
-    OS_ATTR((out_sched_kernel<true, false, 0>), 160 * 1024); OS_ATTR((out_sched_kernel<false, false, 0>), 160 * 1024);
-    OS_ATTR((out_sched_kernel<true, true, 0>), 160 * 1024); OS_ATTR((out_sched_kernel<false, true, 0>), 160 * 1024);
-    OS_ATTR((out_sched_kernel<true, false, 1>), 160 * 1024); OS_ATTR((out_sched_kernel<false, false, 1>), 160 * 1024);
-    OS_ATTR((out_sched_kernel<true, true, 1>), 160 * 1024); OS_ATTR((out_sched_kernel<false, true, 1>), 160 * 1024);
-    OS_ATTR((out_sched_tm_kernel<true, 0>), 64 * 1024); OS_ATTR((out_sched_tm_kernel<false, 0>), 64 * 1024);
-    OS_ATTR((out_sched_tm_kernel<true, 1>), 64 * 1024); OS_ATTR((out_sched_tm_kernel<false, 1>), 64 * 1024);
-#undef OS_ATTR
-}
 bool out_sched_supports(const OutSchedArgs& a) {
-    return a.Cin == OS_C && a.Cout <= 32 && a.guidance_rescale <= 0.f && a.gn_nparts < 0x7fff && a.T <= 0xffff && a.pitch <= 0xffff && a.B <= 0xffff &&
-           a.x_bstride <= 0x7fffffffLL && a.gn_part_bstride <= 0x7fffffffLL;
-}
-void launch_out_sched(const OutSchedArgs& a, hipStream_t s) {
-    dim3 grid((a.T + 31) / 32, a.B);
-    const int tp = a.T | (a.pitch << 16), bn = a.B | (a.gn_nparts << 16);
-    const bool sp = a.ws != nullptr;   // split-fp16 products (engine.cpp: fp32 mode's default; said_debug_option "out_split")
-#define OS_LAUNCH(CFG, SP, SF) hipLaunchKernelGGL((out_sched_kernel<CFG, SP, SF>), grid, dim3(64 * OS_KS), out_sched_smem(CFG), s, a.x, a.gn_part, (SP) ? a.ws : a.w4, a.step_ptr, tp, (int)a.x_bstride, \
-                                              (int)a.gn_part_bstride, bn, a)
-    if (a.solver == 0) {
-        if (a.cfg) { if (sp) OS_LAUNCH(true, true, 0); else OS_LAUNCH(true, false, 0); }
-        else { if (sp) OS_LAUNCH(false, true, 0); else OS_LAUNCH(false, false, 0); }
-    } else {
-        if (a.cfg) { if (sp) OS_LAUNCH(true, true, 1); else OS_LAUNCH(true, false, 1); }
-        else { if (sp) OS_LAUNCH(false, true, 1); else OS_LAUNCH(false, false, 1); }
-    }
-#undef OS_LAUNCH
+    return a.Cin == OS_C && a.C <= 32 && a.guidance_rescale <= 0.f && a.gn_nparts < 0x7fff && a.T <= 0xffff && a.pitch <= 0xffff && a.B <= 0xffff &&
+           a.h_bstride <= 0x7fffffffLL && a.gn_part_bstride <= 0x7fffffffLL;
 }
 
 
@@ -289,7 +277,7 @@ void launch_out_sched(const OutSchedArgs& a, hipStream_t s) {
 // 48-channel slice w, all partial tiles in flight: gn20_*), GroupNorm + SiLU once per element into a bf16 LDS tile [sample][34 rows][192]
 // (rgemm's 400-byte rows), the convolution as a TRANSPOSED product D[out channel][token] on v_mfma_f32_32x32x16_bf16 — lane == token, as
 // out_sched_kernel's epilogue wants it — with the 36 k-steps split over the four waves (fixed-order LDS reduction), both samples sharing every
-// weight fragment, then exactly out_sched_kernel's epilogue (sched_math.h: same explicitly rounded op sequence).
+// weight fragment, then out_sched_kernel's epilogue (OutEpilogue above, four rows per wave).
 constexpr int OT_AP = 200, OT_ROWS = 34, OT_NP = 4;   // tile row pitch (elements), rows, 16-byte pieces per thread and sample (34 x 24 = 816 <= 4 x 256)
 
 template <bool CFG, int SF>
@@ -318,41 +306,13 @@ __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a)
             raw[h][i] = *reinterpret_cast<const u32x4*>(xb + ((sb * a.seg + tt) * 192 + 8 * pc));
         }
     }
+    OutEpilogue<CFG, SF, 4, 4> epi;   // (this wave's four output rows)
     const int step = *a.step_ptr;
-    const float* cf = a.coef + step * 8;
-    float cfv[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) cfv[i] = cf[i];
-    const int t = t0 + lt;
-    const bool tok = t < T;
-    const rsrc_t rlat = make_rsrc(a.lat + (long long)b * a.lat_bstride, (unsigned)a.Cout * (unsigned)a.pitch * 4u);
-    const rsrc_t rnz = make_rsrc(a.step_noise ? a.step_noise + ((long long)step * a.B + b) * a.lat_bstride : nullptr,
-                                 a.step_noise ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
-    const rsrc_t rin = make_rsrc(a.mask ? a.init + (long long)b * a.lat_bstride : nullptr, a.mask ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
-    const rsrc_t ren = make_rsrc(a.mask ? a.edit_noise + (long long)b * a.lat_bstride : nullptr, a.mask ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
-    const rsrc_t rmk = make_rsrc(a.mask ? a.mask + (long long)b * a.lat_bstride : nullptr, a.mask ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
-    float e_x[4], e_nz[4], e_in[4], e_en[4], e_mk[4], e_bias[4], e_h[4];
-    int e_n[4];
-    const bool want_h = SF != 0 && solver_code(cfv) == SOLVER_DPM2;   // (order 2 reads the previous step's x0)
-    const rsrc_t rh = make_rsrc(SF != 0 ? a.x0h + (long long)b * a.lat_bstride : nullptr, SF != 0 ? (unsigned)a.Cout * (unsigned)a.pitch * 4u : 0u);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int r = w + 4 * j;
-        const int n = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        e_n[j] = n;
-        const int vo = (tok && n < a.Cout) ? (n * a.pitch + t) * 4 : (int)0x80000000;
-        e_x[j] = bload(rlat, vo, 0);
-        e_nz[j] = bload(rnz, vo, 0);
-        e_in[j] = bload(rin, vo, 0);
-        e_en[j] = bload(ren, vo, 0);
-        e_mk[j] = bload(rmk, vo, 0);
-        if constexpr (SF != 0) e_h[j] = bload(rh, want_h ? vo : (int)0x80000000, 0);
-        e_bias[j] = a.bias[n < a.Cout ? n : 0];
-    }
-    // this wave's nine k16 steps of the [32][576] weight matrix (row = output channel, k = tap * 192 + channel); rows past Cout: row 0 again (unused)
+    epi.request(a, step, T, b, t0, w, lt, lh);
+    // this wave's nine k16 steps of the [32][576] weight matrix (row = output channel, k = tap * 192 + channel); rows past C: row 0 again (unused)
     bf16x8 wf[9];
     {
-        const unsigned short* wb = reinterpret_cast<const unsigned short*>(a.wb) + (long long)(lt < a.Cout ? lt : 0) * 576 + 8 * lh;
+        const unsigned short* wb = reinterpret_cast<const unsigned short*>(a.wb) + (long long)(lt < a.C ? lt : 0) * 576 + 8 * lh;
 #pragma unroll
         for (int i = 0; i < 9; ++i) wf[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(wb + 16 * (9 * w + i)));
     }
@@ -419,38 +379,7 @@ __global__ __launch_bounds__(256) void out_sched_tm_kernel(const OutSchedArgs a)
 #pragma unroll
         for (int r = 0; r < 16; ++r) red[((w * NH + h) * 16 + r) * 64 + l] = acc[h][r];
     __syncthreads();
-    // ---- epilogue: bias, guidance, DDIM update, noise, mask blend; latents updated in place (out_sched_kernel's)
-    float* latp = a.lat + (long long)b * a.lat_bstride;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int r = w + 4 * j;
-        float eh[NH];
-#pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            float s = 0.f;
-#pragma unroll
-            for (int w2 = 0; w2 < 4; ++w2) s += red[((w2 * NH + h) * 16 + r) * 64 + l];
-            eh[h] = s + e_bias[j];
-        }
-        const float e = CFG ? cfg_combine(eh[NH - 1], eh[0], a.guidance_scale) : eh[0];
-        const int n = e_n[j];
-        if (!(tok && n < a.Cout)) continue;
-        const float x = e_x[j];
-        note_nonfinite(e, a.status, step);
-        if (a.inter) a.inter[(((long long)step * a.B + b) * T + t) * a.Cout + n] = x / a.latent_scale;
-        float prev;
-        if constexpr (SF == 0) {
-            prev = ddim_prev(e, x, cfv, a.prediction_type);
-        } else {
-            float x0n = 0.f;
-            prev = solver_prev(e, x, cfv, a.prediction_type, e_h[j], x0n);
-            if (solver_code(cfv) >= SOLVER_DPM1) a.x0h[(long long)b * a.lat_bstride + (long long)n * a.pitch + t] = x0n;
-        }
-        if (a.step_noise) prev = __fadd_rn(prev, __fmul_rn(cfv[4], e_nz[j]));
-        else if (a.noise_seed) prev = __fadd_rn(prev, __fmul_rn(cfv[4], philox_normal(a.noise_seed[0], a.noise_seed[1], (unsigned)step, a.noise_elem0 + (unsigned)((b * T + t) * a.Cout + n))));
-        if (a.mask) prev = mask_blend(prev, e_in[j], e_en[j], e_mk[j], cfv);
-        latp[(long long)n * a.pitch + t] = prev;
-    }
+    epi.apply(a, red, step, T, b, t0, w, l);
 }
 static int out_sched_tm_smem(bool cfg) {
     const int nh = cfg ? 2 : 1;
@@ -460,15 +389,35 @@ static int out_sched_tm_smem(bool cfg) {
 bool out_sched_tm_supports(const OutSchedArgs& a) {
     return out_sched_supports(a) && a.x_tm && a.wb && a.seg > 0 && (long long)(a.cfg ? 2 : 1) * a.B * a.seg * 192 < 0x7fffffffLL;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Run-time flags -> kernel instantiation, in ONE place: the launches and the shared-memory attribute both go through these, so every instantiation that can
+// be launched is also configured.  f receives the kernel's address and the instantiation's CFG.
+// ------------------------------------------------------------------------------------------------------------------
+template <class F> static void pick_bool(bool v, F&& f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static void with_out_sched_kernel(bool cfg, bool sp, bool sf, F&& f) {
+    pick_bool(cfg, [&](auto c) { pick_bool(sp, [&](auto p) { pick_bool(sf, [&](auto v) {
+        f(&out_sched_kernel<decltype(c)::value, decltype(p)::value, decltype(v)::value ? 1 : 0>); }); }); });
+}
+template <class F> static void with_out_sched_tm_kernel(bool cfg, bool sf, F&& f) {
+    pick_bool(cfg, [&](auto c) { pick_bool(sf, [&](auto v) { f(&out_sched_tm_kernel<decltype(c)::value, decltype(v)::value ? 1 : 0>); }); });
+}
+void configure_out_sched_kernel() {
+    const auto lds = [](int bytes) { return [bytes](auto* k) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }; };
+    for (int i = 0; i < 8; ++i) with_out_sched_kernel(i & 1, i & 2, i & 4, lds(160 * 1024));
+    for (int i = 0; i < 4; ++i) with_out_sched_tm_kernel(i & 1, i & 2, lds(64 * 1024));
+}
+void launch_out_sched(const OutSchedArgs& a, hipStream_t s) {
+    dim3 grid((a.T + 31) / 32, a.B);
+    const int tp = a.T | (a.pitch << 16), bn = a.B | (a.gn_nparts << 16);
+    const bool sp = a.ws != nullptr;   // split-fp16 products (engine.cpp: fp32 mode's default; said_debug_option "out_split")
+    with_out_sched_kernel(a.cfg, sp, a.solver, [&](auto* k) {
+        hipLaunchKernelGGL(k, grid, dim3(64 * OS_KS), out_sched_smem(a.cfg), s, a.h, a.gn_part, sp ? a.ws : a.w4, a.step_ptr, tp, (int)a.h_bstride, (int)a.gn_part_bstride, bn, a);
+    });
+}
 void launch_out_sched_tm(const OutSchedArgs& a, hipStream_t s) {
     dim3 grid((a.T + 31) / 32, a.B);
-    if (a.solver == 0) {
-        if (a.cfg) hipLaunchKernelGGL((out_sched_tm_kernel<true, 0>), grid, dim3(256), out_sched_tm_smem(true), s, a);
-        else hipLaunchKernelGGL((out_sched_tm_kernel<false, 0>), grid, dim3(256), out_sched_tm_smem(false), s, a);
-    } else {
-        if (a.cfg) hipLaunchKernelGGL((out_sched_tm_kernel<true, 1>), grid, dim3(256), out_sched_tm_smem(true), s, a);
-        else hipLaunchKernelGGL((out_sched_tm_kernel<false, 1>), grid, dim3(256), out_sched_tm_smem(false), s, a);
-    }
+    with_out_sched_tm_kernel(a.cfg, a.solver, [&](auto* k) { hipLaunchKernelGGL(k, grid, dim3(256), out_sched_tm_smem(a.cfg), s, a); });
 }
 
 }  // namespace said

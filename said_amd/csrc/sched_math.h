@@ -1,5 +1,7 @@
-// sched_math.h — the DDIM, DDPM and DPM-Solver++ updates as device functions shared by the stand-alone scheduler kernels (misc.hip) and the
-// fused output-conv + scheduler kernel (out_sched.hip).
+// sched_math.h — the per-element update that ends a denoise step.  step_update<SF> (at the end of this file) is the ONE statement of the sequence
+// non-finite note -> optional dump of the pre-step latent -> DDIM / DDPM / DPM-Solver++ update -> eta noise -> editing-mask blend; every kernel that updates latents calls it: the stand-alone
+// scheduler kernels (misc.hip: sched_step_kernel, step_flat_kernel) and the fused output-conv + scheduler kernels (out_sched.hip: OutEpilogue).
+// The callers keep their loads, stores and addressing; the primitives (ddim_prev, solver_prev, mask_blend, philox_normal) are called from nowhere else.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -97,6 +99,33 @@ __device__ __forceinline__ float philox_normal(unsigned seed_lo, unsigned seed_h
     const float u1 = ((float)(r[0] >> 8) + 1.0f) * 5.9604644775390625e-8f;    // (0, 1], 24 bits
     const float u2 = (float)(r[1] >> 8) * 5.9604644775390625e-8f;             // [0, 1)
     return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
+}
+
+// ------------------------------------------------------------------------------------------
+// One element's update.  The caller has loaded the operands; it stores `prev` over x and, for DPM-Solver++ rows (solver_code >= SOLVER_DPM1), `x0`
+// into the history that the next step's `x0_prev` is read from (only second-order rows read it).
+// ------------------------------------------------------------------------------------------
+struct StepNoise {         // the eta noise of one element: cf[4] * ...
+    bool from_tensor;      // ... `value`, loaded from the step-noise tensor
+    float value;
+    const unsigned* seed;  // ... else, if not null, philox_normal(seed, step, elem0 + elem) drawn here
+    unsigned elem0, elem;  // element index in (B, T, C) order: of the call's first clip within the whole batch, of this element within the call
+};
+struct StepResult { float prev, x0; };
+// SF (solver family of the table): 0 = DDIM rows (ddim_prev), 1 = DDPM / DPM-Solver++ rows (solver_prev).  e: the model output after guidance.
+// dump_to (addressed by the caller, or null): the pre-step latent / latent_scale is stored there.
+template <int SF>
+__device__ __forceinline__ StepResult step_update(float e, float x, const float* cf, int pred, float x0_prev, int step, const StepNoise& nz, bool masked, float init,
+                                                  float enoise, float mask, int* status, bool dump = false, float* dump_to = nullptr, float latent_scale = 1.f) {
+    note_nonfinite(e, status, step);
+    if (dump) *dump_to = x / latent_scale;
+    StepResult r = {0.f, 0.f};
+    if constexpr (SF == 0) r.prev = ddim_prev(e, x, cf, pred);
+    else r.prev = solver_prev(e, x, cf, pred, x0_prev, r.x0);
+    if (nz.from_tensor) r.prev = __fadd_rn(r.prev, __fmul_rn(cf[4], nz.value));
+    else if (nz.seed) r.prev = __fadd_rn(r.prev, __fmul_rn(cf[4], philox_normal(nz.seed[0], nz.seed[1], (unsigned)step, nz.elem0 + nz.elem)));
+    if (masked) r.prev = mask_blend(r.prev, init, enoise, mask, cf);
+    return r;
 }
 
 }  // namespace said
