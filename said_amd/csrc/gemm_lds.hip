@@ -16,7 +16,9 @@
 // are finalised per wave for its own channel slice from the producer's Welford partials (gemm_common.h).
 // Work split, reduction and epilogues are those of gemm.hip: NB output tiles x 32 tokens per workgroup,
 // KS waves splitting K by input channel, fixed-order LDS reduction, fused epilogues.
-// Here: the kernel, the LDS sizing, the shape tables and the launch dispatch; ugemm_dev.h: tile constants, header, variants; ugemm_body.h, kconv_body.h: the two bodies.
+// Here: the kernel, the LDS sizing, and the table of instantiations with its one lookup (configure_ugemm_kernels walks it, launch_ugemm calls the row's launch).
+// ugemm_plan.h (host only): the shape lists, the launch variants, ugemm_supports and plan_gemm, which picks a launch's row; ugemm_dev.h: tile constants, header;
+// ugemm_body.h, kconv_body.h: the two bodies.
 #include <cstdio>
 #include <cstdlib>
 
@@ -77,7 +79,7 @@ static int ugemm_smem_floats(const GemmArgs& a, int KS, bool mt = false) {
 }
 
 constexpr int kMaxLds = 160 * 1024;
-template <int NB, int KS, int EPI, int VAR, bool BF, bool MT, bool SP = false>
+template <int NB, int KS, int EPI, int VAR, bool BF, bool MT, bool SP>
 static void ulaunch_one(const GemmArgs& a, int batch, hipStream_t s, int tt) {
     int smem = ugemm_smem_floats<NB, EPI>(a, KS, MT) * (int)sizeof(float);
     constexpr bool KCONV = is_kconv_shape(SP, MT, NB, KS, EPI, VAR);
@@ -101,187 +103,26 @@ static void ulaunch_one(const GemmArgs& a, int batch, hipStream_t s, int tt) {
                        a.T | (a.N << 16), s0.x_pitch | (gate_vft << 16), (int)s0.x_bstride, bmod_b0, (int)grid.x,
                        gn0 ? s0.gn_part : nullptr, (int)s0.gn_part_bstride, s0.gn_cpg | (s0.gn_nparts << 16), a);
 }
-template <int NB, int KS, int EPI, int VAR, bool BF, bool MT, bool SP = false>
+template <int NB, int KS, int EPI, int VAR, bool BF, bool MT, bool SP>
 static void uconfigure_one() {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ugemm_kernel<NB, KS, EPI, VAR, BF, MT, SP>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
 }
 
-// (epilogue, NB, KS, variant): small-batch tile shapes; large batches use the generic kernel's NB = 3..6 shapes
-#define SAID_UGEMM_CONFIGS(X)                                                                                    \
-    X(EPI_STORE, 1, 8, 0) X(EPI_STORE, 1, 8, UV_DEEP) X(EPI_STORE, 1, 8, UV_T3 | UV_GN0)                         \
-    X(EPI_STORE, 1, 8, UV_MULTI) X(EPI_STORE, 2, 8, UV_MULTI)                                                    \
-    X(EPI_STORE, 1, 8, UV_RGN | UV_DUP) X(EPI_STORE, 1, 8, UV_T3 | UV_GN0 | UV_DUP) X(EPI_STORE, 2, 8, UV_T3 | UV_GN0 | UV_DUP) \
-    X(EPI_STORE, 1, 8, UV_T3 | UV_GN0 | UV_MULTI)                                                                \
-    X(EPI_STORE, 1, 8, UV_T3 | UV_GN0 | UV_GN1 | UV_MULTI) X(EPI_STORE, 1, 8, UV_RGN)                            \
-    X(EPI_STORE, 2, 8, 0) X(EPI_STORE, 2, 8, UV_DEEP) X(EPI_STORE, 2, 8, UV_T3 | UV_GN0)                         \
-    X(EPI_STORE, 2, 8, UV_T3 | UV_GN0 | UV_MULTI)                                                                \
-    X(EPI_STORE, 2, 8, UV_T3 | UV_GN0 | UV_GN1 | UV_MULTI)                                                       \
-    X(EPI_STORE, 3, 8, 0) X(EPI_STORE, 3, 8, UV_DEEP) X(EPI_STORE, 3, 8, UV_T3 | UV_GN0) X(EPI_STORE, 3, 8, UV_MULTI) \
-    X(EPI_STORE, 3, 8, UV_T3 | UV_GN0 | UV_DUP)                                                                  \
-    X(EPI_QKV, 1, 8, UV_GN0) X(EPI_QKV, 2, 8, UV_GN0) X(EPI_QKV, 3, 8, UV_GN0)                                   \
-    X(EPI_GEGLU, 1, 8, 0) X(EPI_GEGLU, 2, 8, 0) X(EPI_GEGLU, 4, 8, 0)                                            \
-    X(EPI_BAND, 1, 8, 0)
+// The instantiations: ugemm_plan.h's three shape lists, expanded once, each row with its launch and configure functions
+#define SAID_UGEMM_ROW_FNS(NB, KS, EPI, VAR, BF, MT, SP) &ulaunch_one<NB, KS, EPI, VAR, BF, MT, SP>, &uconfigure_one<NB, KS, EPI, VAR, BF, MT, SP>
+static const URow kRows[] = {SAID_UGEMM_ROWS};
 
-// split-fp16 product shapes (SP; fp32 mode, single-tile workgroups): the small-batch step's launches.  Not built: the shapes that spill with the second
-// accumulator set (NB = 2 with two or three K segments of 3-tap blocks, NB = 3 DEEP / MULTI: 148-180 bytes of scratch per lane) and GEGLU other than the one-tile-per-wave
-// NB = 4 shape (its weights use the flat step layout) — those launches stay on the fp32 MFMAs.
-#define SAID_UGEMM_SP_CONFIGS(X)                                                                                 \
-    X(EPI_STORE, 1, 8, 0) X(EPI_STORE, 1, 8, UV_DEEP) X(EPI_STORE, 1, 8, UV_T3 | UV_GN0)                         \
-    X(EPI_STORE, 1, 8, UV_MULTI) X(EPI_STORE, 2, 8, UV_MULTI)                                                    \
-    X(EPI_STORE, 1, 8, UV_RGN | UV_DUP) X(EPI_STORE, 1, 8, UV_T3 | UV_GN0 | UV_DUP) X(EPI_STORE, 2, 8, UV_T3 | UV_GN0 | UV_DUP) \
-    X(EPI_STORE, 1, 8, UV_T3 | UV_GN0 | UV_MULTI)                                                                \
-    X(EPI_STORE, 1, 8, UV_T3 | UV_GN0 | UV_GN1 | UV_MULTI) X(EPI_STORE, 1, 8, UV_RGN)                            \
-    X(EPI_STORE, 2, 8, 0) X(EPI_STORE, 2, 8, UV_DEEP) X(EPI_STORE, 2, 8, UV_T3 | UV_GN0)                         \
-    X(EPI_STORE, 3, 8, 0) X(EPI_STORE, 3, 8, UV_T3 | UV_GN0)                                                     \
-    X(EPI_STORE, 3, 8, UV_T3 | UV_GN0 | UV_DUP)                                                                  \
-    X(EPI_QKV, 1, 8, UV_GN0) X(EPI_QKV, 2, 8, UV_GN0) X(EPI_QKV, 3, 8, UV_GN0)                                   \
-    X(EPI_GEGLU, 4, 8, 0)                                                                                        \
-    X(EPI_BAND, 1, 8, 0)
-
-// multi-tile shapes (large batches; single-block launches).  (Round 2's single-n-tile store shapes at two workgroups per CU — an
-// experiment that measured slower, two of whose instantiations spilled 6 VGPRs — are gone.)  fp32 GEGLU uses NB = 2: with 8 accumulator tiles the
-// weight fragments only fit by rolling them through the registers, which a multi-tile workgroup cannot do.
-#define SAID_UGEMM_MT_CONFIGS(X)                                                                   \
-    X(EPI_STORE, 2, 8, 0, 0) X(EPI_STORE, 2, 8, UV_T3 | UV_GN0, 0) X(EPI_STORE, 1, 8, UV_RGN, 0)   \
-    X(EPI_STORE, 2, 8, 0, 1) X(EPI_STORE, 2, 8, UV_T3 | UV_GN0, 1) X(EPI_STORE, 1, 8, UV_RGN, 1)   \
-    X(EPI_STORE, 2, 8, UV_T3 | UV_GN0 | UV_DUP, 0) X(EPI_STORE, 1, 8, UV_RGN | UV_DUP, 0)          \
-    X(EPI_STORE, 2, 8, UV_T3 | UV_GN0 | UV_DUP, 1) X(EPI_STORE, 1, 8, UV_RGN | UV_DUP, 1)          \
-    X(EPI_QKV, 3, 8, UV_GN0, 0) X(EPI_QKV, 3, 8, UV_GN0, 1)                                        \
-    X(EPI_GEGLU, 2, 8, 0, 0) X(EPI_GEGLU, 2, 8, 0, 1)                                              \
-    X(EPI_BAND, 1, 8, 0, 0) X(EPI_BAND, 1, 8, 0, 1)
-
-void configure_ugemm_kernels() {
-#define X(E, nb, ks, var) uconfigure_one<nb, ks, E, var, false, false>(); uconfigure_one<nb, ks, E, var, true, false>();
-    SAID_UGEMM_CONFIGS(X)
-#undef X
-#define X(E, nb, ks, var) uconfigure_one<nb, ks, E, var, false, false, true>();
-    SAID_UGEMM_SP_CONFIGS(X)
-#undef X
-#define X(E, nb, ks, var, bf) uconfigure_one<nb, ks, E, var, bf != 0, true>();
-    SAID_UGEMM_MT_CONFIGS(X)
-#undef X
+const URow* ugemm_row(int epi, int NB, int KS, int var, UMode mode, bool mt) {
+    for (const URow& r : kRows)
+        if (r.epi == epi && r.NB == NB && r.KS == KS && r.var == var && r.mode == mode && r.mt == mt) return &r;
+    return nullptr;
 }
 
-static inline bool is_gn(int xf) { return xf == XF_GN_SILU || xf == XF_GN_LN; }
-static int uvar_of(const GemmArgs& a, int epi) {
-    int v = 0;
-    if (a.seg[0].taps == 3) v |= UV_T3;
-    if (is_gn(a.seg[0].xform)) v |= UV_GN0;
-    if (a.nseg > 1 && is_gn(a.seg[1].xform)) v |= UV_GN1;
-    if (epi == EPI_STORE && a.res_kind == RES_GN) v |= UV_RGN;
-    if (epi == EPI_STORE && a.y2) v |= UV_DUP;
-    if (a.nseg > 1) v |= UV_MULTI;
-    else if (a.seg[0].C > 24 * 8) v |= UV_DEEP;   // KS = 8 everywhere: more than one 24-channel block per wave
-    return v;
-}
+void configure_ugemm_kernels() { for (const URow& r : kRows) r.configure(); }
 
-// The LDS-staged kernel covers stride-1, k in {1,3}, ungrouped GEMMs whose per-wave channel slice is a
-// multiple of 24 (or 8 / 16); everything else stays on the generic kernel.
-bool ugemm_supports(const GemmArgs& a, int epi, int NB, int KS, int pm, int tt) {
-    const bool bf16 = pm == 1, sp = pm == 2;
-    bool cfg = false;
-    const int var = uvar_of(a, epi);
-    if (tt > 1) {   // multi-tile: own shape list, one K block per wave, at most 15 tiles per workgroup
-        bool mt = false;
-#define X(E, nb, ks, v, bf) mt = mt || (epi == E && NB == nb && KS == ks && var == (v) && bf16 == (bf != 0));
-        SAID_UGEMM_MT_CONFIGS(X)
-#undef X
-        const int cw = a.seg[0].C / KS;
-        if (!mt || tt > 15 || a.nseg != 1 || cw != 24) return false;
-    }
-#define X(E, nb, ks, v) cfg = cfg || (epi == E && NB == nb && KS == ks && var == (v));
-    SAID_UGEMM_CONFIGS(X)
-#undef X
-    if (!cfg || a.groups != 1 || a.ntiles_per_group % NB) return false;
-    if (sp) {   // split-fp16 products: single-tile workgroups, every segment packed for them, the flat layout exactly where the kernel expects it
-        bool spc = false;
-#define X(E, nb, ks, v) spc = spc || (epi == E && NB == nb && KS == ks && var == (v));
-        SAID_UGEMM_SP_CONFIGS(X)
-#undef X
-        if (tt > 1 || !spc) return false;
-        const bool flat_shape = epi == EPI_GEGLU && NB == 4 && KS == 8 && !(var & (UV_MULTI | UV_DEEP));
-        for (int s = 0; s < a.nseg; ++s) if (!a.seg[s].ws || (a.seg[s].ws_flat != 0) != flat_shape) return false;
-        if (is_kconv_shape(sp, tt > 1, NB, KS, epi, var) && !a.kconv_off) {
-            // kconv_body's shapes: every segment 8 x 24 channels; [3-tap GN + SiLU] x 2, or 3-tap GN + SiLU followed by one or two plain 1-tap segments
-            const bool gn1 = (var & UV_GN1) != 0;
-            if (a.res_kind != RES_NONE || a.y2 || (gn1 ? a.nseg != 2 : (a.nseg < 2 || a.nseg > 3))) return false;
-            for (int s = 0; s < a.nseg; ++s) {
-                const Seg& sg = a.seg[s];
-                const bool gn3 = (s == 0) || gn1;
-                if (sg.C != 24 * 8 || sg.taps != (gn3 ? 3 : 1) || sg.xform != (gn3 ? XF_GN_SILU : XF_NONE) || sg.Tin != a.T) return false;
-                if (sg.x_bstride > 0x7fffffffLL || sg.gn_part_bstride > 0x7fffffffLL) return false;
-            }
-            if (a.emb && (long long)a.N * a.emb_pitch * 4 > 0x7fffffffLL) return false;
-        }
-    }
-    {   // what the compile-time variant assumes about the arguments
-        const int xf0 = a.seg[0].xform;
-        if (epi == EPI_QKV && (xf0 != XF_GN_LN || a.vt_dim <= 0 || (a.vt_dim & (a.vt_dim - 1)))) return false;
-        if ((epi == EPI_GEGLU || epi == EPI_BAND) && xf0 != XF_LN) return false;
-        if (epi == EPI_STORE && !(xf0 == XF_NONE || xf0 == XF_SILU || xf0 == XF_GN_SILU)) return false;
-        if (a.nseg > 2 && is_gn(a.seg[2].xform)) return false;
-        if ((xf0 == XF_LN || xf0 == XF_GN_LN) && !(a.seg[0].w4_ln_tail && a.seg[0].ln_eps == 1e-5f)) return false;
-        const int nacc = (epi == EPI_GEGLU) ? 2 * NB : NB;
-        if (nacc >= 8 && !(a.nseg == 1 && a.seg[0].C == 24 * KS)) return false;   // rolling weight rounds: one block only
-        if (epi != EPI_STORE && a.res_kind != RES_NONE) return false;
-        if (!(var & UV_T3))
-            for (int s = 0; s < a.nseg; ++s) if (a.seg[s].taps != 1) return false;
-        if (var & UV_RGN) {   // one residual GroupNorm group per wave
-            const int c_span = NB * 32;
-            if (a.res_gn_cpg <= 0 || (c_span + a.res_gn_cpg - 1) / a.res_gn_cpg + 1 > KS) return false;
-        }
-    }
-    if (a.seg[0].x_bstride > 0x7fffffffLL || a.b0 > 0x3fff || a.seg[0].C > 0xffff) return false;
-    for (int s = 0; s < a.nseg; ++s) if (a.seg[s].b_mod != 0) return false;   // sample aliasing (b % b_mod) stays on the generic kernel
-    if (a.seg[0].Tin != a.T || a.ntiles_per_group != (a.N + 31) / 32) return false;
-    if (a.T > 0xffff || a.N > 0xffff || a.seg[0].x_pitch > 0xffff || a.geglu_gate_tiles > 0xffff || (epi == EPI_QKV && a.tm_tiles > 0xffff)) return false;   // packed header fields
-    {   // header-only GroupNorm path of segment 0: parameters behind the weights, eps one of two known values
-        const Seg& s0 = a.seg[0];
-        if (s0.xform == XF_GN_SILU || s0.xform == XF_GN_LN) {
-            if (!s0.w4_gn_tail || !(s0.gn_eps == 1e-5f || s0.gn_eps == 1e-6f)) return false;
-            if (s0.gn_part_bstride > 0x7fffffffLL || s0.gn_cpg > 0xffff || s0.gn_nparts > 0x7fff) return false;
-        }
-    }
-    for (int s = 0; s < a.nseg; ++s) {
-        const Seg& sg = a.seg[s];
-        if (bf16 && !sg.w2) return false;
-        if (!sg.w4 || sg.stride != 1 || !(sg.taps == 1 || sg.taps == 3) || sg.pad != (sg.taps - 1) / 2) return false;
-        if (sg.taps == 3 && epi != EPI_STORE) return false;
-        if (sg.C % KS) return false;
-        const int cw = sg.C / KS;
-        if (cw % 24 != 0) return false;   // blocks of three 8-channel rounds; narrower slices stay on the generic kernel
-        if ((sg.xform == XF_GN_SILU || sg.xform == XF_GN_LN) && (cw % sg.gn_cpg || cw > 64)) return false;
-        if ((sg.xform == XF_LN || sg.xform == XF_GN_LN) && (sg.taps != 1 || cw > 24 || s != 0)) return false;
-    }
-    return true;
-}
-
-void launch_ugemm(const GemmArgs& a, int epi, int batch, int NB, int KS, hipStream_t s, int pm, int tt) {
-    const int var = uvar_of(a, epi);
-    const bool bf16 = pm == 1, sp = pm == 2;
-    if (tt > 1) {
-#define X(E, nb, ks, v, bf) \
-        if (epi == E && NB == nb && KS == ks && var == (v) && bf16 == (bf != 0)) { ulaunch_one<nb, ks, E, v, bf != 0, true>(a, batch, s, tt); return; }
-        SAID_UGEMM_MT_CONFIGS(X)
-#undef X
-    }
-    if (sp) {
-#define X(E, nb, ks, v) \
-        if (epi == E && NB == nb && KS == ks && var == (v)) { ulaunch_one<nb, ks, E, v, false, false, true>(a, batch, s, 1); return; }
-        SAID_UGEMM_SP_CONFIGS(X)
-#undef X
-        launch_fault("unsupported split-fp16 ugemm config epi=%d NB=%d KS=%d", epi, NB, KS);
-        return;
-    }
-#define X(E, nb, ks, v) \
-    if (epi == E && NB == nb && KS == ks && var == (v)) {                   \
-        if (bf16) ulaunch_one<nb, ks, E, v, true, false>(a, batch, s, 1);   \
-        else ulaunch_one<nb, ks, E, v, false, false>(a, batch, s, 1);       \
-        return;                                                             \
-    }
-    SAID_UGEMM_CONFIGS(X)
-#undef X
-    launch_fault("unsupported ugemm config epi=%d NB=%d KS=%d", epi, NB, KS);
+void launch_ugemm(const GemmArgs& a, int epi, int batch, int NB, int KS, hipStream_t s, UMode mode, int tt) {
+    if (const URow* r = ugemm_row(epi, NB, KS, uvar_of(a, epi), mode, tt > 1)) r->launch(a, batch, s, tt);
+    else launch_fault("unsupported ugemm config epi=%d NB=%d KS=%d mode=%d tt=%d", epi, NB, KS, (int)mode, tt);
 }
 
 }  // namespace said

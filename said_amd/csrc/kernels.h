@@ -159,12 +159,32 @@ struct AttnArgs {
 // tile shape selection: NB 32-row tiles per workgroup, KS waves splitting K
 void launch_gemm(const GemmArgs& a, int epi, int batch, int NB, int KS, hipStream_t s);
 void launch_attn(const AttnArgs& a, int batch, int head_dim, int KS, hipStream_t s, int mode = 0);   // mode: 0 fp32 MFMA, 1 bf16 operands, 2 split-fp16 operands
-// LDS-staged UNet GEMM (gemm_lds.hip): same arguments; only for shapes ugemm_supports() accepts
-// pm (product mode): 0 = v_mfma_f32_32x32x2_f32 on fp32 operands; 1 = bf16 (v_mfma_f32_32x32x8_bf16_1k; needs Seg::w2), everything else stays fp32;
-// 2 = split-fp16 operands (round 5: x = h + 2^-11 l, three v_mfma_f32_32x32x16_f16 per eight fp32 MFMAs, fp32 accumulation; needs Seg::ws; tt == 1 only)
+// LDS-staged UNet GEMM (gemm_lds.hip): same arguments; only for launches ugemm_supports(a, epi, NB, KS, mode, tt) accepts (ugemm_plan.h, with the table of
+// instantiations both look a launch up in; which of the two kernels, which NB, mode and tt a UNet launch gets is decided in one place: ugemm_plan.h plan_gemm)
+// mode (what the matrix instructions multiply; accumulation and everything else stay fp32):
+enum UMode : int {
+    U_F32 = 0,    // v_mfma_f32_32x32x2_f32 on fp32 operands
+    U_BF16 = 1,   // v_mfma_f32_32x32x8_bf16_1k on bf16 operands; needs Seg::w2
+    U_SP = 2,     // split-fp16 operands (round 5: x = h + 2^-11 l, three v_mfma_f32_32x32x16_f16 per eight fp32 MFMAs); needs Seg::ws; tt == 1 only
+};
+// VAR (compile-time launch variant): which conditional load groups exist.  Every vector-memory request of the request
+// phase is then UNCONDITIONAL code (lanes/groups that do not apply use an out-of-range offset and get 0 back), so the
+// compiler can count outstanding loads exactly.  With loads inside run-time branches it falls back to
+// s_waitcnt vmcnt(0) and e.g. the GroupNorm coefficients wait for the epilogue operands requested after them: one
+// extra memory round trip on the critical path (measured 21.7k -> see profiles/ for the phase clocks).
+enum UVar : int { UV_T3 = 1 /* segment 0 is a 3-tap conv */, UV_GN0 = 2 /* GroupNorm'ed segment 0 */,
+                  UV_GN1 = 4 /* GroupNorm'ed segment 1 (concatenated skip) */, UV_RGN = 8 /* GroupNorm'ed residual */,
+                  UV_MULTI = 16 /* more than one K segment: the argument blocks of segments 1, 2 are fetched */,
+                  UV_DEEP = 32 /* single segment whose per-wave K slice spans several 24-channel blocks (FF out) */,
+                  UV_DUP = 64 /* the result is stored twice: y and y2 (+ a per-channel constant), kernels.h GemmCommon::y2 */ };
+
+// the instantiations whose launches run kconv_body (kconv_body.h): split-fp16, single-tile, NB = 1 store kernels over a 3-tap GroupNorm'ed
+// segment 0 and one or two more segments — the kernel, its LDS sizing (ulaunch_one) and the shape check (ugemm_supports) all ask here
+__host__ __device__ constexpr bool is_kconv_shape(bool SP, bool MT, int NB, int KS, int EPI, int VAR) {
+    return SP && !MT && NB == 1 && KS == 8 && EPI == EPI_STORE && (VAR == (UV_T3 | UV_GN0 | UV_MULTI) || VAR == (UV_T3 | UV_GN0 | UV_GN1 | UV_MULTI));
+}
 // tt > 1: multi-tile workgroups (each walks over tt consecutive 32-token tiles keeping its weights in registers)
-bool ugemm_supports(const GemmArgs& a, int epi, int NB, int KS, int pm = 0, int tt = 1);
-void launch_ugemm(const GemmArgs& a, int epi, int batch, int NB, int KS, hipStream_t s, int pm = 0, int tt = 1);
+void launch_ugemm(const GemmArgs& a, int epi, int batch, int NB, int KS, hipStream_t s, UMode mode, int tt = 1);
 void configure_ugemm_kernels();
 
 // token-major (B,T,C) <-> channel-major [B][C][pitch]

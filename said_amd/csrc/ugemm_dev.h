@@ -1,7 +1,8 @@
 // ugemm_dev.h — what the bodies of the LDS-staged UNet GEMM (ugemm_body.h, kconv_body.h) and its host side (gemm_lds.hip) share: the tile constants, the
-// preloaded header, a wave's block descriptor, the compile-time launch variants and which instantiations are kconv_body's.
+// preloaded header and a wave's block descriptor.  (The compile-time launch variants and which instantiations are kconv_body's: kernels.h; the shape lists: ugemm_plan.h.)
 #pragma once
 #include "gemm_common.h"
+#include "ugemm_plan.h"
 
 namespace said {
 
@@ -49,22 +50,5 @@ struct UBlock {   // one (segment, channel block) of this wave
     const float2* cGN;   // LDS coefficient tables, indexed by segment channel
     const float2* cLN;
 };
-
-// VAR (compile-time launch variant): which conditional load groups exist.  Every vector-memory request of the request
-// phase is then UNCONDITIONAL code (lanes/groups that do not apply use an out-of-range offset and get 0 back), so the
-// compiler can count outstanding loads exactly.  With loads inside run-time branches it falls back to
-// s_waitcnt vmcnt(0) and e.g. the GroupNorm coefficients wait for the epilogue operands requested after them: one
-// extra memory round trip on the critical path (measured 21.7k -> see profiles/ for the phase clocks).
-enum UVar : int { UV_T3 = 1 /* segment 0 is a 3-tap conv */, UV_GN0 = 2 /* GroupNorm'ed segment 0 */,
-                  UV_GN1 = 4 /* GroupNorm'ed segment 1 (concatenated skip) */, UV_RGN = 8 /* GroupNorm'ed residual */,
-                  UV_MULTI = 16 /* more than one K segment: the argument blocks of segments 1, 2 are fetched */,
-                  UV_DEEP = 32 /* single segment whose per-wave K slice spans several 24-channel blocks (FF out) */,
-                  UV_DUP = 64 /* the result is stored twice: y and y2 (+ a per-channel constant), kernels.h GemmCommon::y2 */ };
-
-// the instantiations whose launches run kconv_body (kconv_body.h): split-fp16, single-tile, NB = 1 store kernels over a 3-tap GroupNorm'ed
-// segment 0 and one or two more segments — the kernel, its LDS sizing (ulaunch_one) and the shape check (ugemm_supports) all ask here
-__host__ __device__ constexpr bool is_kconv_shape(bool SP, bool MT, int NB, int KS, int EPI, int VAR) {
-    return SP && !MT && NB == 1 && KS == 8 && EPI == EPI_STORE && (VAR == (UV_T3 | UV_GN0 | UV_MULTI) || VAR == (UV_T3 | UV_GN0 | UV_GN1 | UV_MULTI));
-}
 
 }  // namespace said

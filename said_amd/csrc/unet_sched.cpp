@@ -1,6 +1,8 @@
-// unet_sched.cpp — the UNet1D launch schedules: launch-shape choices, the per-block ResBlock / SpatialTransformer
-// launch sequences of every precision mode and batch size, time embedding, cross-attention K/V and the alignment band.
+// unet_sched.cpp — the UNet1D launch schedules: the per-block ResBlock / SpatialTransformer launch sequences of every precision mode and
+// batch size, time embedding, cross-attention K/V and the alignment band.  Every launch of run_unet goes through counted(); a channel-major
+// GEMM (do_gemm) runs on whatever ugemm_plan.h's plan_gemm decides — the column-tile rules and the rule order are written there, once.
 #include "engine_internal.h"
+#include "ugemm_plan.h"
 
 namespace said {
 namespace host {
@@ -17,27 +19,6 @@ LaunchCfg pick_cfg(long long t_tiles_total, int ntiles, bool allow6) {
 }
 
 namespace {
-
-// UNet GEMMs with 6 output tiles (192 channels): the LDS-staged kernel at every batch size — two tiles per workgroup
-// as soon as that still fills the chip (measured at Be=32: 47 TFLOP/s against 34 for the generic NB=6 shape)
-// Column tiles per workgroup (NB) of the UNet's 192-wide channel-major GEMMs.  A launch is t_tiles x 6 / NB workgroups on 256 CUs; its
-// time is that of the busiest CU: ceil(workgroups / 256) workgroups of (F + NB) units each, F = 0.45 the per-workgroup fixed part
-// (GroupNorm finalisation, operand tile; fitted on T = 1800: NB = 1 14.8 us, NB = 2 25.0 us at 342 workgroups each).  Round 2's rule
-// (NB = 2 from 64 tiles) put 342 workgroups on 256 CUs at T = 1800: two rounds of three units where NB = 3 is one round of 3.45.
-int best_nb(long long token_tiles, int column_tiles) {
-    int best = 1;
-    double cost = 1e30;
-    for (int nb = 1; nb <= 3; ++nb) {
-        const long long wgs = token_tiles * (column_tiles / nb);
-        const double k = (double)((wgs + 255) / 256) * (0.45 + nb);
-        if (k < cost - 1e-9) { cost = k; best = nb; }
-    }
-    return best;
-}
-LaunchCfg pick_unet(long long t_tiles_total) {
-    if (t_tiles_total * 6 > 1024) return t_tiles_total * 3 >= 192 ? LaunchCfg{2, 8} : LaunchCfg{1, 8};   // (large launches: multi-tile NB = 2 shapes)
-    return LaunchCfg{best_nb(t_tiles_total, 6), 8};
-}
 
 constexpr float ATTN_SCALE = 0.17677669529663687f;   // dim_head ** -0.5 = 32 ** -0.5 (attention.py:101)
 constexpr float LOG2E = 1.4426950408889634f;
@@ -75,57 +56,32 @@ GemmArgs mkargs(int T, int N) {
 
 namespace {
 
-inline bool dbg_go(said_ctx* c) {
+// One counted launch of the schedule.  Every launch of run_unet takes exactly one number from dbg_count, in launch order: said_profile_unet replays number
+// dbg_only alone, said_debug_stop_after issues the numbers below dbg_stop.  `log` adds the launch's stage_log entry (called only while logging), `launch` issues it
+// (called only when its number is wanted); -DSAID_TRACE builds report the launch (fmt, args) before it and how it ended after it.  Returns whether it ran.
+template <class Log, class Launch, class... A>
+bool counted(said_ctx* c, hipStream_t s, Log&& log, Launch&& launch, const char* fmt, A... args) {
+    if (c->log_on) log();
     const int k = c->dbg_count++;
-    if (c->dbg_only >= 0) return k == c->dbg_only;
-    return c->dbg_stop < 0 || k < c->dbg_stop;
+    if (c->dbg_only >= 0 ? k != c->dbg_only : (c->dbg_stop >= 0 && k >= c->dbg_stop)) return false;
+    if (trace_on()) { fprintf(stderr, "[said] #%d ", k); fprintf(stderr, fmt, args...); fputc('\n', stderr); fflush(stderr); }
+    launch();
+    if (trace_on()) { hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[said]   -> %s\n", hipGetErrorString(e)); fflush(stderr); }
+    return true;
 }
-
-// -DSAID_TRACE builds: how the launch just issued ended
-inline void trace_done(hipStream_t s) { if (trace_on()) { hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[said]   -> %s\n", hipGetErrorString(e)); fflush(stderr); } }
-
 // (a helper launch that is not a node of the counted schedule: runs whenever the NEXT counted launch would)
 inline bool dbg_go_peek(const said_ctx* c) { return c->dbg_only >= 0 ? c->dbg_count == c->dbg_only : (c->dbg_stop < 0 || c->dbg_count < c->dbg_stop); }
 
-// algorithmic HBM bytes / flops of one launch: weights + operands in + residual + result out
-// Multi-tile workgroups (gemm_lds.hip, MT): once a launch would have several thousand workgroups, each workgroup walks
-// over `tt` consecutive token tiles instead, keeping its weights in registers; tt is chosen so that ~4 workgroups per
-// CU remain.  Returns 1 when the launch is not eligible.
-constexpr long long KCONV_MAX_TILES = 4096;   // do_gemm: launches of at most this many (sample, token tile) pairs may run the K-long convolutions as NB = 1 kconv_body workgroups
-constexpr long long MT_WGS_PER_TILE = 1024;   // workgroups per extra token tile of a large launch
-constexpr long long MT_MID_WGS = 228;         // ... of a mid-size one
-static int pick_tt(const GemmArgs& a, int epi, int batch, int NB, int KS, bool bf) {
-    if (a.step_inc) return 1;
-    if (epi == EPI_GEGLU || epi == EPI_BAND) return 1;   // measured slower multi-tile (B=32: GEGLU NB=2 x tt vs NB=4, band)
-    const long long ntt = (a.T + 31) / 32;
-    const long long wgs = ntt * (a.ntiles_per_group / NB) * batch;
-    long long want = wgs / MT_WGS_PER_TILE;
-    // mid-size launches (one to four rounds of one workgroup per CU, e.g. q/k/v at T = 1800: 684 workgroups): as many token tiles per
-    // workgroup as there would be rounds, so that ONE round of <= 256 workgroups remains (configs[4]: 16.87k -> 17.34k frames/s)
-    if (want <= 1) want = wgs / MT_MID_WGS;
-    int tt = (int)std::min<long long>(std::min<long long>(8, want), ntt);
-    if (tt <= 1 || !ugemm_supports(a, epi, NB, KS, bf, tt)) return 1;
-    return tt;
-}
+inline PlanSwitches plan_switches(const said_ctx* c) { return {c->bf16_mode, sp_on(c, c->ugemm_split), c->kconv, c->clk_on, c->cur_concurrent}; }
 
+// One channel-major UNet GEMM: planned (ugemm_plan.h plan_gemm — the schedule's NB / KS are a request), logged, launched by the plan.
 // returns true when the launch went to ugemm_kernel (gemm_lds.hip) — the only kernel that honours GemmCommon::gn_coef_out / kv_split
 bool do_gemm(said_ctx* c, const GemmArgs& a, int epi, int batch, int NB, int KS, hipStream_t s) {
-    bool on_ugemm = false;
+    const GemmPlan p = plan_gemm(plan_switches(c), a, epi, batch, NB, KS);
     GemmArgs a2 = a;
     a2.kconv_off = (c->kconv == 0) ? 1 : 0;
-    const bool bf = c->bf16_mode;
-    if (NB == 3 && epi == EPI_STORE && !ugemm_supports(a2, epi, 3, KS, bf)) NB = 2;   // (the two-segment fp32 shapes spill at NB = 3: not built)
-    // K-long up-path convolutions (two / three K segments): the split-fp16 shapes exist for one column tile per workgroup only (kconv_body; with two the second accumulator
-    // set spills).  Where that takes at most 1.5 x the rounds of the chosen shape on the fp32 matrix instructions it wins (a round of NB = 1 split ~11 us, of NB = 2 fp32 ~21 us:
-    // configs[4] 24.3k -> 25.5k frames/s, 3 clips +6 %; 76 tiles — 2 rounds against 1 — loses 2 %: profiles/r06g_kconv_ab.txt)
-    if (!bf && epi == EPI_STORE && NB > 1 && a2.nseg >= 2 && c->kconv != 0 && sp_on(c, c->ugemm_split) && !a2.step_inc && !c->clk_on && (!c->cur_concurrent || c->kconv == 2)) {   // (concurrent clip groups share the CUs: fewer workgroups win there — 5 clips -1.9 %; "kconv" = 2: there too)
-        const long long tiles = (long long)batch * ((a2.T + 31) / 32), r1 = (tiles * 6 + 255) / 256, rn = (tiles * (6 / NB) + 255) / 256;
-        if (tiles <= KCONV_MAX_TILES && 2 * r1 <= 3 * rn && !ugemm_supports(a2, epi, NB, KS, 2) && ugemm_supports(a2, epi, 1, 8, 2)) { NB = 1; KS = 8; }
-    }
-    const int tt = pick_tt(a2, epi, batch, NB, KS, bf);
-    // fp32 mode, single-tile workgroups: split-fp16 products wherever the shape is built for them (gemm_lds.hip SP) and the weights carry the packing
-    const bool sp = !bf && tt <= 1 && sp_on(c, c->ugemm_split) && !a2.step_inc && ugemm_supports(a2, epi, NB, KS, 2);
-    if (c->log_on) {
+    if (c->clk_on && c->dbg_count < 64) a2.clk = c->clk_dev + (long long)c->dbg_count * 128;
+    auto log = [&] {   // algorithmic HBM bytes / flops of the launch: weights + operands in + residual + result out
         double w = 0, in = 0, fl = 0;
         const double nout = (double)a.groups * a.N * (epi == EPI_GEGLU ? 2 : 1);
         for (int i = 0; i < a.nseg; ++i) {
@@ -137,47 +93,25 @@ bool do_gemm(said_ctx* c, const GemmArgs& a, int epi, int batch, int NB, int KS,
         double out = (double)batch * a.groups * a.N * a.T * 4.0;
         if (a.res_kind != RES_NONE) in += out;
         if (epi == EPI_BAND) in += 2.0 * batch * a.N * a.T * 4.0;  // this block's K and V rows
-        c->stage_log.push_back({((tt > 1 || ugemm_supports(a, epi, NB, KS, bf) || ugemm_supports(a, epi, NB, KS))) ? 2 : 0, epi, NB, KS, w + in + out, fl});
-    }
-    if (c->clk_on && c->dbg_count < 64) a2.clk = c->clk_dev + (long long)c->dbg_count * 128;
-    if (dbg_go(c)) {
-        if (trace_on()) { fprintf(stderr, "[said] gemm #%d epi=%d NB=%d KS=%d T=%d N=%d batch=%d tt=%d\n", c->dbg_count - 1, epi, NB, KS, a.T, a.N, batch, tt); fflush(stderr); }
-        const bool ug = !a2.step_inc;
-        on_ugemm = true;
-        if (tt > 1) launch_ugemm(a2, epi, batch, NB, KS, s, bf, tt);
-        else if (sp) launch_ugemm(a2, epi, batch, NB, KS, s, 2);
-        else if (ug && bf && ugemm_supports(a2, epi, NB, KS, true)) launch_ugemm(a2, epi, batch, NB, KS, s, true);
-        else if (ug && ugemm_supports(a2, epi, NB, KS)) launch_ugemm(a2, epi, batch, NB, KS, s);
-        else on_ugemm = false;
-        if (on_ugemm) {}
+        c->stage_log.push_back({p.on_ugemm() ? 2 : 0, epi, p.NB, p.KS, w + in + out, fl});
+    };
+    auto launch = [&] {
+        if (p.on_ugemm()) launch_ugemm(a2, epi, batch, p.NB, p.KS, s, p.mode(), p.tt);
         else if (epi == EPI_QKV && a2.kv_split) c->launch_err = "q/k/v GEMM asked for pre-split k / v but does not run on ugemm_kernel";
-        else launch_gemm(a2, epi, batch, NB, KS, s);
-        trace_done(s);
-    }
-    return on_ugemm;
+        else launch_gemm(a2, epi, batch, p.NB, p.KS, s);
+    };
+    return counted(c, s, log, launch, "gemm epi=%d NB=%d KS=%d T=%d N=%d batch=%d tt=%d kernel=%d", epi, p.NB, p.KS, a.T, a.N, batch, p.tt, (int)p.kernel) && p.on_ugemm();
 }
 void do_attn(said_ctx* c, const AttnArgs& a, int batch, int head_dim, int KS, hipStream_t s, bool presplit = false) {
-    if (c->log_on) {
-        const double e = (double)batch * a.heads * head_dim * a.T;
-        c->stage_log.push_back({1, -1, head_dim / 32, KS, 4.0 * e * 4.0, 4.0 * e * a.T});
-    }
-    if (dbg_go(c)) {
-        if (trace_on()) { fprintf(stderr, "[said] attn #%d D=%d KS=%d T=%d batch=%d\n", c->dbg_count - 1, head_dim, KS, a.T, batch); fflush(stderr); }
-        launch_attn(a, batch, head_dim, KS, s, c->bf16_mode ? 1 : (sp_on(c, c->attn_split) ? (presplit ? 3 : 2) : 0));
-        trace_done(s);
-    }
+    const double e = (double)batch * a.heads * head_dim * a.T;
+    counted(c, s, [&] { c->stage_log.push_back({1, -1, head_dim / 32, KS, 4.0 * e * 4.0, 4.0 * e * a.T}); },
+            [&] { launch_attn(a, batch, head_dim, KS, s, c->bf16_mode ? 1 : (sp_on(c, c->attn_split) ? (presplit ? 3 : 2) : 0)); },
+            "attn D=%d KS=%d T=%d batch=%d", head_dim, KS, a.T, batch);
 }
 // battn_kernel (attn.hip): bf16 q / k / v as the token-major q/k/v projection leaves them (TGemmArgs::qkv_bf16)
 void do_battn(said_ctx* c, const AttnArgs& a, int batch, hipStream_t s) {
-    if (c->log_on) {
-        const double e = (double)batch * a.heads * HD * a.T;
-        c->stage_log.push_back({9, -1, 1, 1, 4.0 * e * 2.0, 4.0 * e * a.T});
-    }
-    if (dbg_go(c)) {
-        if (trace_on()) { fprintf(stderr, "[said] battn #%d T=%d batch=%d\n", c->dbg_count - 1, a.T, batch); fflush(stderr); }
-        launch_battn(a, batch, s);
-        trace_done(s);
-    }
+    const double e = (double)batch * a.heads * HD * a.T;
+    counted(c, s, [&] { c->stage_log.push_back({9, -1, 1, 1, 4.0 * e * 2.0, 4.0 * e * a.T}); }, [&] { launch_battn(a, batch, s); }, "battn T=%d batch=%d", a.T, batch);
 }
 // the self-attention of one block over q / k (QK) and v (VT) as every q/k/v projection leaves them; o_mode as AttnArgs has it
 AttnArgs mk_attn(const said_ctx* c, const UGeo& g, float* o, long long o_bstride, int o_mode) {
@@ -230,20 +164,18 @@ ChainArgs mkchain(const said_ctx* c, const UGeo& g, const STW& sw, int blk, cons
 // o / xin: the attention output and the block input, sample strides o_bs / x_bs
 void do_stchain(said_ctx* c, const UGeo& g, const StRange& r, ChainArgs ca, const void* o, const void* xin, long long o_bs, long long x_bs, bool shared, bool bf, hipStream_t s) {
     if ((bf ? c->xclk_on : c->clk_on) && c->dbg_count < 64) ca.clk = c->clk_dev + (long long)c->dbg_count * 128;   // (bf16: said_debug_option "xgemm_clk": -DSAID_CLK_STAMPS builds)
-    if (c->log_on) {
+    auto log = [&] {
         const double eb = bf ? 2.0 : 4.0;   // element size of the weights and the activations (the K / V windows are fp32 in the log of both modes)
         const int n1 = r.n1, n2 = r.n2;
         const double w = eb * ((double)3 * MC * MC + 2.0 * FFI * MC + (double)(FFI + MC) * MC);
         const double io = eb * MC * g.T * ((double)n1 * 2 + g.Be) + 4.0 * 2 * MC * g.T * (double)n2;
         const double fl = 2.0 * g.T * ((double)n1 * MC * MC + (double)n2 * 2 * MC * MC + (double)g.Be * (2.0 * FFI * MC + (double)(FFI + MC) * MC)) + 4.0 * n2 * MC * g.T * c->band_wmax;
         c->stage_log.push_back({10, EPI_STORE, 6, 8, w + io, fl});
-    }
-    if (dbg_go(c)) {
-        if (trace_on()) { fprintf(stderr, "[said] stchain #%d T=%d samples=%d shared=%d\n", c->dbg_count - 1, g.T, g.Be, (int)shared); fflush(stderr); }
+    };
+    counted(c, s, log, [&] {
         launch_stchain(ca, static_cast<const float*>(o), static_cast<const float*>(xin), g.T, g.Tp, o_bs, x_bs, shared ? g.Bc : 0, g.Bc > 0 ? g.Bc : 0, g.Be, s, bf);
         ++c->n_stchain;
-        trace_done(s);
-    }
+    }, "stchain T=%d samples=%d shared=%d", g.T, g.Be, (int)shared);
 }
 
 // ---- bf16 mode, large batches: UNet GEMMs on the token-major bf16 kernel (tgemm.hip) ------------------------------------
@@ -261,40 +193,39 @@ bool use_tg(said_ctx* c, const UGeo& g, int nsamples) {
 inline const void* tw(const said_ctx* c, const void* bf, const void* f32) { return c->bf16_mode ? bf : f32; }
 // conv_in_kernel (conv_in.hip): one result per clip, stored for its in_copies samples; tm: token-major bf16 (H0.t) instead of channel-major fp32 (H0.p)
 void do_conv_in(said_ctx* c, const UGeo& g, int in_copies, bool tm, hipStream_t s) {
-    if (c->log_on)
+    counted(c, s, [&] {
         c->stage_log.push_back({11 /* conv_in_kernel */, EPI_STORE, 1, 4, 4.0 * ((double)MC * c->cin * 3 + (double)g.B_lat * c->cin * g.T + (double)g.Be * MC * g.T),
                                 2.0 * g.B_lat * MC * c->cin * 3 * g.T});
-    if (dbg_go(c)) {
-        if (trace_on()) { fprintf(stderr, "[said] conv_in #%d T=%d clips=%d copies=%d tm=%d\n", c->dbg_count - 1, g.T, g.B_lat, in_copies, (int)tm); fflush(stderr); }
+    }, [&] {
         if (tm) launch_conv_in_tm(c->x_cm, c->conv_in.w4[0], c->conv_in.bias, c->H0.t, tm_seg(g), c->H0.st, g.step_inc, g.B_lat, in_copies, g.T, g.Tp, s);
         else launch_conv_in(c->x_cm, c->conv_in.w4[0], c->conv_in.bias, c->H0.p, c->H0.st, g.step_inc, g.B_lat, in_copies, g.T, g.Tp, MC, s);
-        trace_done(s);
-    }
+    }, "conv_in T=%d clips=%d copies=%d tm=%d", g.T, g.B_lat, in_copies, (int)tm);
 }
 void do_prep(said_ctx* c, const PrepArgs& a, int batch, hipStream_t s) {
-    if (c->log_on) c->stage_log.push_back({5, -2, 0, 0, (double)batch * a.C * a.T * (4.0 + (c->bf16_mode ? 2.0 : 4.0)) * (a.dst2 ? 1.5 : 1.0), 0.0});
     PrepArgs a2 = a;
     a2.f32 = c->bf16_mode ? 0 : 1;
     if (!a2.f32) a2.pack = 0;
-    if (dbg_go(c) && !launch_prep(a2, batch, s)) c->launch_err = "operand preparation kernel: unsupported shape";
+    counted(c, s, [&] { c->stage_log.push_back({5, -2, 0, 0, (double)batch * a.C * a.T * (4.0 + (c->bf16_mode ? 2.0 : 4.0)) * (a.dst2 ? 1.5 : 1.0), 0.0}); },
+            [&] { if (!launch_prep(a2, batch, s)) c->launch_err = "operand preparation kernel: unsupported shape"; }, "prep mode=%d C=%d T=%d batch=%d", a.mode, a.C, a.T, batch);
 }
 void do_tgemm(said_ctx* c, const TGemmArgs& a, int batch, hipStream_t s) {
-    if (c->log_on) {
-        const double eb = c->bf16_mode ? 2.0 : 4.0;   // operand element size; KS = 32 marks the fp32 kernel (fgemm_kernel) in the log
-        const double out_b = a.geglu ? a.N / 2 * eb : (a.y_cm ? 4.0 * a.N * (a.res_cm ? 2 : 1) : 4.0 * a.N);
-        const int tile_n = c->bf16_mode ? (a.N % 128 == 0 ? 128 : 64) : ((a.N % 128 == 0 && (a.geglu || a.N % 96)) ? 128 : 96);
-        c->stage_log.push_back({4, a.geglu ? EPI_GEGLU : (a.qk ? EPI_QKV : EPI_STORE), tile_n, c->bf16_mode ? 4 : 32,
-                                eb * a.N * a.K + (double)batch * a.M * (eb * a.K + out_b), 2.0 * batch * (double)a.M * a.N * a.K});
-    }
     TGemmArgs a2 = a;
     a2.f32 = c->bf16_mode ? 0 : 1;
     if (a2.f32 && a2.yb) { a2.yf = reinterpret_cast<float*>(a2.yb); a2.yb = nullptr; }   // token-major intermediate (GEGLU product) in fp32
     a2.f32_split = (a2.f32 && sp_on(c, c->gemm_split)) ? 1 : 0;
     if (!a2.f32_split) a2.f32_packed = 0;
-    if (dbg_go(c) && !launch_tgemm(a2, batch, s)) {
+    auto log = [&] {
+        const double eb = c->bf16_mode ? 2.0 : 4.0;   // operand element size; KS = 32 marks the fp32 kernel (fgemm_kernel) in the log
+        const double out_b = a.geglu ? a.N / 2 * eb : (a.y_cm ? 4.0 * a.N * (a.res_cm ? 2 : 1) : 4.0 * a.N);
+        const int tile_n = c->bf16_mode ? (a.N % 128 == 0 ? 128 : 64) : ((a.N % 128 == 0 && (a.geglu || a.N % 96)) ? 128 : 96);
+        c->stage_log.push_back({4, a.geglu ? EPI_GEGLU : (a.qk ? EPI_QKV : EPI_STORE), tile_n, c->bf16_mode ? 4 : 32,
+                                eb * a.N * a.K + (double)batch * a.M * (eb * a.K + out_b), 2.0 * batch * (double)a.M * a.N * a.K});
+    };
+    counted(c, s, log, [&] {
+        if (launch_tgemm(a2, batch, s)) return;
         char b[160]; snprintf(b, sizeof b, "token-major GEMM: shape M=%d N=%d K=%d (batch %d) is not served by any kernel", a.M, a.N, a.K, batch);
         c->launch_err = b;
-    }
+    }, "tgemm M=%d N=%d K=%d batch=%d", a.M, a.N, a.K, batch);
 }
 // per-sample row pitch of the token-major operands: a multiple of 32 that holds the T tokens plus the two Conv1d padding rows, so
 // that all samples form ONE row axis for the 256-row GEMM tiles (tgemm.h: seg_rows) and 32-row MFMA tiles never straddle samples
@@ -335,7 +266,13 @@ void do_xgemm(said_ctx* c, const TGemmArgs& a, int batch, hipStream_t s) {
     if (a2.f32 && a2.yb) { a2.yf = reinterpret_cast<float*>(a2.yb); a2.yb = nullptr; }
     // kernel family: 7 = rgemm_kernel (round 4: register-stationary weights, helper waves), 6 = round 3's xgemm_kernel
     const int fam = (!a2.f32 && rgemm_supports(a2, batch)) ? 7 : 6;
-    if (c->log_on) {
+    // a launch over a COLUMN RANGE of the packed weights (the split concatenated-input ResBlocks / folded proj_out probe only their first launch) is
+    // something only rgemm_kernel understands: falling through to xgemm_kernel would silently multiply the wrong columns (ADVICE r4)
+    if (fam == 6 && (a2.w_k0 != 0 || (a2.w_ld != 0 && a2.w_ld != a2.K) || a2.w_seg != 0)) {
+        c->launch_err = "token-major GEMM over a weight column range is not served by rgemm_kernel for this shape";
+        return;
+    }
+    auto log = [&] {
         const double eb = c->bf16_mode ? 2.0 : 4.0;
         const double out_n = a.geglu ? a.N / 2 : a.N;
         const double out_b = a.y_cm ? 4.0 * out_n : (a.qk ? 4.0 * out_n : eb * out_n * (a.y2_tm ? 2 : 1));
@@ -344,25 +281,17 @@ void do_xgemm(said_ctx* c, const TGemmArgs& a, int batch, hipStream_t s) {
         const double band_b = a.band_k ? 2.0 * 4.0 * a.N : 0.0;
         c->stage_log.push_back({fam, a.geglu ? EPI_GEGLU : (a.qk ? EPI_QKV : (a.band_k ? EPI_BAND : EPI_STORE)), a.N % 128 == 0 && (a.geglu || a.N % 96) ? 128 : 96, c->bf16_mode ? 4 : 32,
                                 eb * a.N * a.K + (double)batch * a.M * (eb * in_k + out_b + res_b + band_b), 2.0 * batch * (double)a.M * a.N * a.K});
-    }
-    if (fam == 7) {
-        if (dbg_go(c)) {
+    };
+    if (fam == 6) ++c->n_xgemm;   // (every xgemm launch of the schedule, issued or not; n_rgemm: the issued ones)
+    counted(c, s, log, [&] {
+        if (fam == 7) {
             if (!launch_rgemm(a2, batch, s)) c->launch_err = "rgemm_kernel refused a launch its own rgemm_supports() had accepted";
             ++c->n_rgemm;
+        } else if (!launch_xgemm(a2, batch, s)) {
+            char b[160]; snprintf(b, sizeof b, "token-major activation GEMM: shape M=%d N=%d K=%d (batch %d) is not served by any kernel", a.M, a.N, a.K, batch);
+            c->launch_err = b;
         }
-        return;
-    }
-    // a launch over a COLUMN RANGE of the packed weights (the split concatenated-input ResBlocks / folded proj_out probe only their first launch) is
-    // something only rgemm_kernel understands: falling through to xgemm_kernel would silently multiply the wrong columns (ADVICE r4)
-    if (a2.w_k0 != 0 || (a2.w_ld != 0 && a2.w_ld != a2.K) || a2.w_seg != 0) {
-        c->launch_err = "token-major GEMM over a weight column range is not served by rgemm_kernel for this shape";
-        return;
-    }
-    ++c->n_xgemm;
-    if (dbg_go(c) && !launch_xgemm(a2, batch, s)) {
-        char b[160]; snprintf(b, sizeof b, "token-major activation GEMM: shape M=%d N=%d K=%d (batch %d) is not served by any kernel", a.M, a.N, a.K, batch);
-        c->launch_err = b;
-    }
+    }, "xgemm family=%d M=%d N=%d K=%d batch=%d", fam, a.M, a.N, a.K, batch);
 }
 TGemmArgs mkx(const UGeo& g, const void* w, int N, int K) {
     TGemmArgs t;
@@ -636,8 +565,7 @@ void run_resblock(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, cons
         set_emb(a, c, g, rb_index);
         a.y = c->M.p; a.y_bstride = g.hs; a.y_pitch = g.Tp;
         a.stats_out = c->M.st; a.stats_bstride = g.sts;
-        const LaunchCfg lc = pick_unet(tt);
-        do_gemm(c, a, EPI_STORE, nb, lc.NB, lc.KS, s);
+        do_gemm(c, a, EPI_STORE, nb, pick_unet_nb(tt), 8, s);
     }
     {   // out_layers: GN -> SiLU -> conv3 ; + skip(x)   (openaimodel.py:226-227)
         GemmArgs a = mkargs(g.T, MC);
@@ -656,8 +584,7 @@ void run_resblock(said_ctx* c, const UGeo& g, const ResW& rw, int rb_index, cons
         a.y = out.p; a.y_bstride = g.hs; a.y_pitch = g.Tp;
         a.stats_out = out.st; a.stats_bstride = g.sts;
         if (shared) { a.y2 = out.p + (long long)g.Bc * g.hs; a.y2_bstride = g.hs; a.y2_add = nullptr; }
-        const LaunchCfg lc = pick_unet(tt);
-        do_gemm(c, a, EPI_STORE, nb, lc.NB, lc.KS, s);
+        do_gemm(c, a, EPI_STORE, nb, pick_unet_nb(tt), 8, s);
     }
 }
 
@@ -709,19 +636,16 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         a.tm_tiles = 2 * MC / 32;
         a.vt = c->QK; a.vt_heads = 2 * HEADS; a.vt_dim = HD; a.vt_rows = r.vt_rows;
         a.y = c->VT - (long long)a.tm_tiles * 32 * g.Tp; a.y_bstride = (long long)MC * g.Tp; a.y_pitch = g.Tp;
-        // tiles per workgroup: the largest shape that still gives every CU a workgroup in ONE round (at Be=2, T=600:
-        // NB=3 -> 228 workgroups, 27.5 -> 13.8 us per launch against NB=1's 684 workgroups in 2.7 rounds)
-        // pick_unet's busiest-CU model over the 18 column tiles where it applies (19 tiles: NB 1 -> 2, 342 -> 171 workgroups)
-        const LaunchCfg lc{tt1 * 18 <= 1024 ? best_nb(tt1, 18) : (tt1 * 6 >= 192 ? 3 : (tt1 * 9 >= 192 ? 2 : 1)), 8};
-        // k and v pre-split for the key-split attention shapes (same rule as below), when this GEMM runs on ugemm_kernel (the only epilogue that packs)
+        const int nb = qkv_nb(tt1);   // tiles per workgroup (ugemm_plan.h)
+        // k and v pre-split for the key-split attention shapes (same rule as below), when this GEMM runs on ugemm_kernel (the only epilogue that packs): ask the plan
         const bool key_split = tt1 * HEADS < 2048;
         presplit = !c->bf16_mode && sp_on(c, c->attn_split) && c->attn_presplit != 0 && key_split && !c->clk_on &&
-                   (ugemm_supports(a, EPI_QKV, lc.NB, lc.KS, 2) || ugemm_supports(a, EPI_QKV, lc.NB, lc.KS));
+                   plan_gemm(plan_switches(c), a, EPI_QKV, n1, nb, 8).on_ugemm();
         a.kv_split = presplit ? 1 : 0;
         // round 6: this GEMM finalises the block input's GroupNorm coefficients anyway (its operand is LayerNorm(GroupNorm(x))): the first workgroup of every sample
         // leaves them for stchain_kernel, whose GroupNorm'ed residual then needs 2 loads per wave instead of 23 and no finalisation in front of its first barrier
         if (chain && c->chain_coef != 0 && c->gn_coef) { a.gn_coef_out = c->gn_coef; a.gn_coef_bs = 2 * MC; }
-        coef_ready = do_gemm(c, a, EPI_QKV, n1, lc.NB, lc.KS, s) && a.gn_coef_out != nullptr;
+        coef_ready = do_gemm(c, a, EPI_QKV, n1, nb, 8, s) && a.gn_coef_out != nullptr;
     }
     bool out1_done = false;
     {   // softmax(q k^T * scale) v   (attention.py:99-126)
@@ -792,8 +716,8 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
             const BandArgs bd = a.band;
             memset(&a.band, 0, sizeof a.band);
             do_gemm(c, a, EPI_STORE, n2, 1, 8, s);
-            if (c->log_on) c->stage_log.push_back({5, -2, 0, 0, 0.0, 0.0});
-            if (dbg_go(c)) launch_band_wide(a.y, obs, g.Tp, bd.k, bd.v, bd.kv_bstride, bd.kv_pitch, bd.lo, bd.hi, g.T, HEADS, n2, bd.scale, s);
+            counted(c, s, [&] { c->stage_log.push_back({5, -2, 0, 0, 0.0, 0.0}); },
+                    [&] { launch_band_wide(a.y, obs, g.Tp, bd.k, bd.v, bd.kv_bstride, bd.kv_pitch, bd.lo, bd.hi, g.T, HEADS, n2, bd.scale, s); }, "band_wide T=%d batch=%d", g.T, n2);
         } else
         do_gemm(c, a, EPI_BAND, n2, 1, 8, s);
     }
@@ -804,8 +728,7 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         a.bias = sw.out2.bias;
         a.res_kind = RES_PLAIN; a.res = c->X1 + (long long)x_off * g.hs; a.res_bstride = g.hs; a.res_pitch = g.Tp;
         a.y = c->X2 + (long long)kv_off * g.hs; a.y_bstride = g.hs; a.y_pitch = g.Tp;
-        const LaunchCfg lc = pick_unet(tt2);
-        do_gemm(c, a, EPI_STORE, n2, lc.NB, lc.KS, s);
+        do_gemm(c, a, EPI_STORE, n2, pick_unet_nb(tt2), 8, s);
     }
     if (use_tg(c, g, g.Be)) {
         {   // GEGLU: operand norm3(x2) (and raw x2 for the folded proj_out), value/gate pairs multiplied in the epilogue
@@ -836,8 +759,7 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         a.seg[0].ln_gamma = sw.l3g; a.seg[0].ln_beta = sw.l3b; a.seg[0].ln_eps = 1e-5f;
         a.bias = sw.ff1.bias; a.geglu_gate_tiles = FFI / 32;
         a.y = c->F; a.y_bstride = (long long)FFI * g.Tp; a.y_pitch = g.Tp;
-        const int geglu_nb = tt * 6 >= 192 ? 4 : (tt * 12 >= 192 ? 2 : 1);   // one round of workgroups, as for qkv
-        do_gemm(c, a, EPI_GEGLU, g.Be, geglu_nb, 8, s);
+        do_gemm(c, a, EPI_GEGLU, g.Be, geglu_nb(tt), 8, s);
     }
     {
         // x3 = net.2(h) + x2 and out = proj_out(x3) + x_in as ONE GEMM over the K segments [h ; x2] with the host-folded
@@ -850,8 +772,7 @@ void run_transformer(said_ctx* c, const UGeo& g, const STW& sw, int blk, const A
         a.res_kind = RES_PLAIN; a.res = in.p; a.res_bstride = g.hs; a.res_pitch = g.Tp;
         a.y = out.p; a.y_bstride = g.hs; a.y_pitch = g.Tp;
         a.stats_out = out.st; a.stats_bstride = g.sts;
-        const LaunchCfg lc = pick_unet(tt);
-        do_gemm(c, a, EPI_STORE, g.Be, lc.NB, lc.KS, s);
+        do_gemm(c, a, EPI_STORE, g.Be, pick_unet_nb(tt), 8, s);
     }
 }
 
@@ -876,8 +797,7 @@ void run_unet(said_ctx* c, const UGeo& g, hipStream_t s) {
         a.step_inc = g.step_inc;   // the loop's device step counter is advanced by the first kernel of the step
         a.bias = c->conv_in.bias;
         a.y = c->H0.p; a.y_bstride = g.hs; a.y_pitch = g.Tp; a.stats_out = c->H0.st; a.stats_bstride = g.sts;
-        const LaunchCfg lc = pick_unet(tt);
-        do_gemm(c, a, EPI_STORE, g.Be, lc.NB, lc.KS, s);
+        do_gemm(c, a, EPI_STORE, g.Be, pick_unet_nb(tt), 8, s);
     }
     const bool sh = g.Bc > 0;   // guidance-shared prefix: the two halves first differ at input_blocks.1.1's cross-attention
     // round 4: the loop's last kernel reads the token-major bf16 hidden state itself (out_sched.hip: out_sched_tm_kernel)
@@ -912,10 +832,10 @@ void run_unet(said_ctx* c, const UGeo& g, hipStream_t s) {
     res(4, c->P, &c->H0, c->Q);          // output_blocks.1.0  cat([h, H0])
     st(3, c->Q, c->P, false, true);      // output_blocks.1.1
     if (g.out_sched) {   // out conv + guidance + DDIM update in one kernel (out_sched.hip)
-        if (dbg_go(c)) {
+        counted(c, s, [] {} /* (the loop is never logged) */, [&] {
             if (out_tm) { launch_out_sched_tm(osa_tm, s); ++c->n_out_sched_tm; }
             else { launch_out_sched(*g.out_sched, s); ++c->n_out_sched; }
-        }
+        }, "out_sched tm=%d", (int)out_tm);
     } else {   // out: GN -> SiLU -> Conv1d(192 -> 32, k3)
         GemmArgs a = mkargs(g.T, c->cin);
         a.nseg = 1;

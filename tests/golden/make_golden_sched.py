@@ -25,6 +25,7 @@ from said_amd.util import synth  # noqa: E402
 
 FIXTURE = os.path.join(HERE, "unet_sched.json")
 TM = {"unet_tgemm_min_tokens": 0}   # every launch on the token-major GEMMs
+CM = {"unet_tgemm_min_tokens": 1000000}   # ... on the channel-major ones
 
 # name, precision, Be, T, cfg_clips, options
 CASES = [
@@ -46,6 +47,10 @@ CASES = [
     ("bf16_hybrid", "bf16", 4, 96, 0, {**TM, "tm_acts": 0}),
     ("bf16_hybrid_guided", "bf16", 4, 96, 2, {**TM, "tm_acts": 0}),
     ("bf16_hybrid_long", "bf16", 2, 672, 0, {**TM, "tm_acts": 0}),
+    # 114 token tiles on the channel-major schedule: plan_gemm's NB 3 -> 2 fallback and kconv NB = 1 switch (the concatenated-input ResBlocks), multi-tile q/k/v
+    ("fp32_long_two_samples", "fp32", 2, 1800, 0, {}),
+    # ... and bf16 mode's multi-tile q/k/v and attn1.to_out; 3600 tokens are past the token-major threshold, so that is moved out of the way
+    ("bf16_long_two_samples", "bf16", 2, 1800, 0, CM),
 ]
 # S = 10 T: band_wmax > 8, the channel-major schedule's plain q projection + generic band kernel.  said_profile_unet runs S = T, so this
 # branch has no stage list; it is covered by the bit-for-bit comparison alone.
@@ -164,7 +169,7 @@ def main(out_path=FIXTURE, dump_dir=None):
     torch.set_grad_enabled(False)
     dev = torch.device("cuda:0")
     model = make_model(dev)
-    model._get_engine(16, 704)   # the largest case: one workspace for all of them
+    model._get_engine(16, 1800)   # the most samples and the most frames of any case: one workspace for all of them
     doc = {"comment": "recorded by tests/golden/make_golden_sched.py: launch order of said_profile_unet and graph nodes per guided step",
            "stage_fields": list(FIELDS), "cases": []}
     for case in CASES:

@@ -1,0 +1,121 @@
+"""The host-side decisions of the UNet GEMM (said_amd/csrc/ugemm_plan.h) without a GPU: tests/ugemm_plan_main.cpp — the header behind a command line, compiled
+once per session with the host compiler of the ROCm installation — against tests/golden/ugemm_plan.txt.
+
+The fixture was recorded from the logic the header replaced (ugemm_supports and its three shape lists in gemm_lds.hip, pick_unet / best_nb / pick_tt and the body
+of do_gemm in unet_sched.cpp, behind the same command line), so it holds what each launch of the channel-major schedule ran on before there was a plan: per case,
+frame count, and setting of the five switches, the (kernel, NB, KS, tiles per workgroup) of every batch size of a scan, printed where it changes.  A change that
+is meant to keep the schedule keeps the file; one that is meant to alter a rule records it again from the new program and says so."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+from test_weight_pack_cpu import _host_compiler  # noqa: E402
+
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "said_amd", "csrc")
+FIXTURE = os.path.join(HERE, "golden", "ugemm_plan.txt")
+
+
+@pytest.fixture(scope="session")
+def planner(tmp_path_factory):
+    """run(*args) -> stdout of the compiled tests/ugemm_plan_main.cpp."""
+    cxx, inc = _host_compiler()
+    exe = str(tmp_path_factory.mktemp("ugemm_plan") / "ugemm_plan_main")
+    cmd = [cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-x", "c++", f"-I{inc}", "-D__HIP_PLATFORM_AMD__", "-I" + CSRC, os.path.join(HERE, "ugemm_plan_main.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, " ".join(cmd) + "\n" + r.stderr[-4000:]
+
+    def run(*args):
+        r = subprocess.run([exe, *args], capture_output=True, text=True)
+        assert r.returncode == 0, (args, r.stdout[-2000:], r.stderr[-2000:])
+        return r.stdout
+    return run
+
+
+def test_split_and_multi_tile_rows_are_base_rows(planner):
+    """ugemm_supports used to ask for a base-list entry beside every split-fp16 / multi-tile one; the table lookup no longer does, because every such row has one."""
+    m = re.fullmatch(r"rows base=(\d+) split=(\d+) multi_tile=(\d+) bad=0\n", planner("rows"))
+    assert m, planner("rows")
+    assert [int(g) for g in m.groups()] == [56, 22, 16]   # 28 base shapes x (fp32, bf16), 22 split-fp16 shapes, 8 multi-tile shapes x (fp32, bf16)
+
+
+def test_plans_are_the_recorded_ones(planner):
+    with open(FIXTURE) as f:
+        want = f.read().splitlines()
+    got = planner().splitlines()
+    assert len(want) == 148
+    for g, w in zip(got, want):
+        assert g == w
+    assert len(got) == len(want)
+
+
+def test_fixture_covers_the_rules():
+    """Every kernel, the NB 3 -> 2 fallback, the kconv NB = 1 window, every tiles-per-workgroup count up to the cap, and the unserved launches appear in the file."""
+    with open(FIXTURE) as f:
+        lines = f.read().splitlines()
+    plans = {p.split("=")[1] for ln in lines for p in ln.split(" : ")[1].split()}
+    assert {p.split("/")[0] for p in plans} == {"cgemm", "f32", "bf16", "sp"}
+    assert {int(p.split("/")[3]) for p in plans} == set(range(1, 9))
+    by = {}
+    for ln in lines:
+        head, scan = ln.split(" : ")
+        name, T, codes = head.split()
+        for c in codes.split(","):
+            by[name, T, c] = scan
+    assert len(by) == 19 * 3 * 48   # cases x frame counts x switch settings: every combination is on exactly one line
+    # pick_unet_nb asks for NB = 3 from 86 tiles; the two-segment fp32 shape is not built (NB -> 2), and with split products and kconv on the launch becomes NB = 1
+    assert by["in_layers_cat", "T=32", "f0100"] == "b1=f32/1/8/1 b43=f32/2/8/1"
+    assert by["in_layers_cat", "T=32", "f1100"] == "b1=sp/1/8/1 b43=f32/2/8/1 b86=sp/1/8/1 b129=f32/2/8/1"
+    assert by["in_layers_cat", "T=32", "f1110"] == by["in_layers_cat", "T=32", "f1101"] == by["in_layers_cat", "T=32", "f1000"] == "b1=sp/1/8/1 b43=f32/2/8/1"   # concurrent, clk, kconv = 0
+    assert by["in_layers_cat", "T=32", "f1210"] == by["in_layers_cat", "T=32", "f1100"]   # kconv = 2: under concurrent clip groups too
+    assert by["to_out2_no_w2", "T=32", "b0000"].startswith("b1=f32/1/8/1")   # bf16 mode without Seg::w2: the fp32 ugemm
+    assert by["conv_in_step", "T=32", "f1100"] == by["conv_in", "T=32", "f1100"] == "b1=cgemm/1/8/1 b43=cgemm/2/8/1"
+
+
+def test_presplit_term_is_the_plan_s(planner):
+    """run_transformer stores k and v pre-split when the q/k/v GEMM runs on ugemm_kernel.  It used to work that out with two ugemm_supports calls of its own (the
+    /p field, recorded from them); it now asks the plan.  In fp32 mode — the only mode that pre-splits — the two agree for every switch setting and batch size."""
+    n = 0
+    for ln in planner().splitlines():
+        head, scan = ln.split(" : ")
+        if not head.startswith("qkv") or "f" not in head.split()[2]:   # (a line lists the switch settings that share its result)
+            continue
+        for p in scan.split():
+            kernel, *_, pre = p.split("=")[1].split("/")
+            assert (kernel != "cgemm") == (pre == "p1"), ln
+            n += 1
+    assert n > 50
+
+
+def _calls(src, name):
+    """The argument lists of every call of `name` in a source text."""
+    out = []
+    for m in re.finditer(r"\b" + name + r"\(", src):
+        depth, i = 1, m.end()
+        while depth:
+            depth += {"(": 1, ")": -1}.get(src[i], 0)
+            i += 1
+        out.append([a.strip() for a in src[m.end():i - 1].split(",")])
+    return out
+
+
+def test_mode_arguments_are_umode_values():
+    """The product mode is the enum UMode everywhere: no call passes a bool, a literal, or the schedule's `bf` flag."""
+    n = 0
+    for fn in ("gemm_lds.hip", "unet_sched.cpp", "ugemm_plan.h"):
+        with open(os.path.join(CSRC, fn)) as f:
+            src = f.read()
+        for name, pos in (("ugemm_supports", 4), ("launch_ugemm", 6)):
+            for args in _calls(src, name):
+                if args[0].startswith("const GemmArgs&"):   # the declaration / definition
+                    continue
+                assert len(args) > pos, (fn, name, args)   # the mode has no default
+                mode = args[pos]
+                assert mode in ("U_F32", "U_BF16", "U_SP", "m", "mode", "p.mode()"), (fn, name, args)
+                n += 1
+    assert n >= 8
