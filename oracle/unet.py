@@ -96,7 +96,7 @@ def attn_bf16_online(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, KS: int)
     return out * (1.0 / L)[..., None]
 
 
-# Optional stage trace for kernel bring-up (tests/debug_stages.py): when set to a list, every
+# Optional stage trace for kernel bring-up (scripts/probe_bf16_emu.py): when set to a list, every
 # tensor that one HIP kernel launch materialises is appended as (name, tensor), in launch order.
 TRACE = None
 

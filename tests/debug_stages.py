@@ -1,17 +1,19 @@
-"""Kernel bring-up aid (run on the GPU box): stops the UNet schedule after every launch and
-compares the buffer that launch produced against the oracle's trace of the same stage.
+"""Kernel bring-up aid (run on the GPU box): the fp32 denoise step launch by launch, with its default options, each launch against the float64 evaluation of its
+own stored inputs — a command line over tests/test_gpu_unet_f32_kernels.py's harness and tests/unet_f32_ref.py.
 
-    python tests/debug_stages.py [B] [T] [S] [plain|trained] [fp32|fp32_strict]
+    python tests/debug_stages.py [B] [T] [plain|trained]
+
+Prints one line per comparison (e, the fp32 CPU evaluation's own e32, the bound 4 max(e32, 1e-6)) and stops at the first launch beyond its bound.
 """
 import os
 import sys
 
-import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from oracle import unet as ou  # noqa: E402
-from said_amd import _engine  # noqa: E402
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.dirname(HERE), HERE]
+import test_gpu_unet_f32_kernels as K  # noqa: E402
+from oracle import pipeline as op  # noqa: E402
 from said_amd.util import synth  # noqa: E402
 
 torch.set_grad_enabled(False)
@@ -19,105 +21,12 @@ torch.set_grad_enabled(False)
 
 def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 2
-    T = int(sys.argv[2]) if len(sys.argv) > 2 else 48
-    S = int(sys.argv[3]) if len(sys.argv) > 3 else T
+    T = int(sys.argv[2]) if len(sys.argv) > 2 else 70
+    fill = sys.argv[3] if len(sys.argv) > 3 else "plain"
     dev = torch.device("cuda:0")
-    fill = sys.argv[4] if len(sys.argv) > 4 else "plain"
-    mode = sys.argv[5] if len(sys.argv) > 5 else "fp32"
-    if fill == "trained":   # heavy tails, outlier channels, norm gains up to 10 (synth.trained_like_state_dict)
-        full = synth.trained_like_state_dict(num_w2v_layers=2)
-        sd = {k: v for k, v in full.items() if k.startswith("denoiser.") or k == "null_cond_emb"}
-        sd_u = {k[len("denoiser."):]: v for k, v in sd.items() if k.startswith("denoiser.")}
-    else:
-        sd_u = synth.fill_state_dict(synth.unet_param_shapes())
-        sd = {"denoiser." + k: v for k, v in sd_u.items()}
-        sd["null_cond_emb"] = synth.fill_tensor("null_cond_emb", (1, 1, 768))
-    eng = _engine.Engine(dev, max(B, 2), max(T, S, 64))
-    eng.load_weights(sd)
-    eng.set_precision(mode)
-    eng.debug_option("st_chain", 0)        # the stage list below is the five-launch tail's (rounds 1-4); round 5's fused tail has no intermediate buffers to read
-    eng.debug_option("attn_presplit", 0)   # QK / VT as plain fp32 (round 5 stores k and v as packed split-fp16 pairs otherwise)
-    x = synth.synth_latents(21, (B, T, 32))
-    c = synth.synth_latents(121, (B, S, 768))
-    ts = torch.tensor([999, 17, 500, 3][:B])
-    ou.TRACE = []
-    if fill == "trained":   # this fill is badly conditioned in fp32: the yardstick is the oracle's op sequence in float64
-        from unittest import mock
-        with mock.patch.object(torch.Tensor, "float", torch.Tensor.double):
-            ref = ou.unet1d_forward({k: v.double() for k, v in sd_u.items()}, x.double(), ts, c.double())
-        ou.TRACE = [(n, t.float()) for n, t in ou.TRACE]
-        ref = ref.float()
-    else:
-        ref = ou.unet1d_forward(sd_u, x, ts, c)
-    trace = ou.TRACE
-    ou.TRACE = None
-    Tp = (T + 31) // 32 * 32
-
-    def cm(name, C, bstride_rows=None):  # read channel-major buffer -> (B, C, T)
-        rows = bstride_rows or C
-        a = eng.debug_read(name, (B, rows, Tp))
-        return a[:, :C, :T]
-
-    def tm(t):  # oracle (B,T,C) -> (B,C,T)
-        return t.transpose(1, 2).numpy()
-
-    # launch index -> (trace name suffix, reader)
-    stages = []
-    k = 0
-    def add(tname, reader):
-        nonlocal k
-        k += 1
-        stages.append((k, tname, reader))
-    add("conv_in", lambda: cm("H0", 192))
-    def rb(p, outbuf):
-        add(p + ":mid", lambda: cm("M", 192))
-        add(p + ":out", lambda: cm(outbuf, 192))
-    def st(p, outbuf):
-        b = p + ".transformer_blocks.0"
-        add(b + ".attn1:qkv", lambda: None)
-        add(b + ".attn1:attn", lambda: cm("O", 192, 384))
-        add(b + ":x1", lambda: cm("X1", 192))
-        add(b + ".attn2:attn", lambda: cm("O", 192, 384))
-        add(b + ":x2", lambda: cm("X2", 192))
-        add(b + ".ff:geglu", lambda: cm("F", 768))
-        # (x3 = ff(norm3(x2)) + x2 is not materialised: proj_out o ff.net.2 is ONE folded GEMM over [h ; x2] since round 2)
-        add(p + ":out", lambda: cm(outbuf, 192))
-    rb("model.input_blocks.1.0", "P"); st("model.input_blocks.1.1", "H1")
-    rb("model.middle_block.0", "P"); st("model.middle_block.1", "Q")
-    rb("model.middle_block.2", "P")
-    rb("model.output_blocks.0.0", "Q"); st("model.output_blocks.0.1", "P")
-    rb("model.output_blocks.1.0", "Q"); st("model.output_blocks.1.1", "P")
-
-    tdict = {}
-    for n, t in trace:
-        tdict.setdefault(n, []).append(t)
-    xd, cd = x.to(dev), c.to(dev)
-    worst = 0.0
-    for (k, tname, reader) in stages:
-        eng.debug_stop_after(k)
-        eng.unet_forward(xd, ts, cd)
-        if tname.endswith(":qkv"):
-            base = tname[:-4]
-            # q and k are token-major [B][2*heads][rows][32] (q heads, then k heads), v channel-major [B][192][Tp]
-            qkt = eng.debug_read("QK", (B, 12, Tp, 32))[:, :, :T, :]
-            vc = eng.debug_read("VT", (B, 192, Tp))[:, :, :T]
-            q, kk, v = (tdict[base + s][0] for s in (":q", ":k", ":v"))
-            heads = lambda t: t.reshape(B, T, 6, 32).permute(0, 2, 1, 3).numpy()
-            e1 = np.abs(qkt[:, :6] - heads(q)).max(); e2 = np.abs(qkt[:, 6:] - heads(kk)).max()
-            e3 = np.abs(vc - tm(v)).max()
-            err, scale = max(e1, e2, e3), float(np.abs(tm(q)).max())
-        else:
-            got = reader()
-            t = tdict[tname][0]
-            want = tm(t) if tname.endswith((":attn", ":x1", ":x2", ":x3", ":geglu")) else t.numpy()
-            err, scale = float(np.abs(got - want).max()), float(np.abs(want).max())
-        worst = max(worst, err / max(scale, 1e-9))
-        flag = "" if err <= 2e-4 * max(scale, 1.0) else "   <<<<<< MISMATCH"
-        print(f"launch {k:2d} {tname:58s} max|err|={err:.3e} (max|ref|={scale:.3e}){flag}", flush=True)
-    eng.debug_stop_after(-1)
-    out = eng.unet_forward(xd, ts, cd).cpu()
-    err = float((out - ref).abs().max())
-    print(f"final eps: max|err|={err:.3e}  max|ref|={float(ref.abs().max()):.3e}   worst stage rel err {worst:.3e}")
+    full = synth.trained_like_state_dict(num_w2v_layers=1) if fill == "trained" else synth.said_state_dict(num_w2v_layers=1)
+    _, sd_u, _ = op.split_state_dict(full)
+    K._forward_case(K._model(dev, full), sd_u, dev, f"{B} x {T} {fill}", B, T, 21, None)
 
 
 if __name__ == "__main__":

@@ -92,6 +92,43 @@ def test_presplit_term_is_the_plan_s(planner):
     assert n > 50
 
 
+def _plan(planner, batch, T):
+    """{case: "kernel/NB/KS/tt body"} at one batch and frame count, fp32 mode's default switches."""
+    return dict(ln.split(" ", 1) for ln in planner("plan", str(batch), str(T)).splitlines())
+
+
+def test_shapes_of_the_fp32_kernel_test_reach_what_they_are_named_for(planner):
+    """tests/test_gpu_unet_f32_kernels.py asserts (kind, epi, NB, KS) per launch from the engine's stage log; what the log does not carry — split-fp16 or fp32 matrix
+    instructions, kconv_body or the block loop, token tiles per workgroup, the fused tail's slices — is held here, from the same header the engine plans with."""
+    import test_gpu_unet_f32_kernels as K
+    SP1, SP2, SP3 = "sp/1/8/1 block", "sp/2/8/1 block", "sp/3/8/1 block"
+    want = {   # conv_in, in_layers, out_layers, in_layers_cat, out_layers_skip, qkv, out_conv
+        "S": ("cgemm/1/8/1 block", SP1, SP1, "sp/1/8/1 kconv", "sp/1/8/1 kconv", SP1, SP1),
+        "M1": ("cgemm/1/8/1 block", SP1, SP1, "sp/1/8/1 kconv", "sp/1/8/1 kconv", SP3, SP1),
+        "M2": ("cgemm/2/8/1 block", SP2, SP2, "f32/2/8/1 block", "f32/2/8/1 block", SP2, SP1),            # the concatenated convolutions stay off split-fp16
+        "L": ("cgemm/2/8/1 block", SP3, SP3, "sp/1/8/1 kconv", "sp/1/8/1 kconv", "f32/3/8/2 block", SP1),   # the kconv NB = 1 switch; q/k/v two token tiles per workgroup
+    }
+    names = ("conv_in", "in_layers", "out_layers", "in_layers_cat", "out_layers_skip", "qkv", "out_conv")
+    for tag, (B, T, nb_in, nb, nb_cat, nb_qkv, _) in K.SHAPES.items():
+        p = _plan(planner, B, T)
+        assert tuple(p[n] for n in names) == want[tag], (tag, p)
+        # ... and the NB the GPU test expects in the stage log is the plan's
+        assert [int(p[n].split("/")[1]) for n in ("conv_in", "in_layers", "in_layers_cat", "qkv")] == [nb_in, nb, nb_cat, nb_qkv], tag
+    # G: the shared first block runs on the clip alone (batch 1, the second convolution with the duplicate store), everything behind it on both halves as S
+    p1 = _plan(planner, 1, 70)
+    assert (p1["in_layers"], p1["out_layers_dup"], p1["qkv"]) == (SP1, SP1, SP1)
+    # F: what stays on the channel-major kernels at 3 x 70
+    p3 = _plan(planner, 3, 70)
+    assert (p3["conv_in"], p3["out_conv"]) == ("cgemm/1/8/1 block", SP1)
+    # slices of the fused tail by (sample, token tile) pairs (unet_sched.cpp run_transformer)
+    with open(os.path.join(CSRC, "stchain.h")) as f:
+        src = f.read()
+    c3, c2 = (int(re.search(r"constexpr int %s = (\d+);" % n, src).group(1)) for n in ("CHAIN3_MAX_TILES", "CHAIN2_MAX_TILES"))
+    slices = lambda B, T: 3 if B * ((T + 31) // 32) <= c3 else (2 if B * ((T + 31) // 32) <= c2 else 1)
+    assert {t: slices(*K.SHAPES[t][:2]) for t in K.SHAPES} == {"S": 3, "M1": 3, "M2": 3, "L": 2}
+    assert slices(2, 70) == 3 and slices(3, 70) == 3   # G (both halves), F
+
+
 def _calls(src, name):
     """The argument lists of every call of `name` in a source text."""
     out = []
