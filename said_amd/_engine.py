@@ -1,4 +1,5 @@
-"""ctypes binding of libsaid_hip.so (C ABI: include/said_hip.h, said_metrics.h, said_optimize.h, said_train.h, said_render.h).
+"""ctypes binding of libsaid_hip.so (C ABI: include/said_hip.h, said_metrics.h, said_optimize.h, said_train.h, said_render.h, said_jpeg.h,
+said_unet_train.h, said_beat.h).
 
 There is deliberately no fallback: if the library is missing, cannot be loaded,
 or no gfx950 device is visible, every entry point raises.
@@ -195,8 +196,26 @@ UNET_TRAIN_EXPORTS = {
     "said_unet_train_read_losses": (c_int, [c_void_p, c_int, _c_double_p, POINTER(c_int), c_int]),
     "said_unet_train_last_losses": (c_int, [c_void_p, _c_float_p]),
 }
+# include/said_beat.h: a group like the renderer's, in a table of its own (tests/test_beat_cpu.py checks it against its header)
+_c_int_p = POINTER(c_int)
+BEAT_EXPORTS = {
+    "said_beat_create": (c_int, [POINTER(c_void_p), c_int]),
+    "said_beat_destroy": (c_int, [c_void_p]),
+    "said_beat_last_error": (c_char_p, [c_void_p]),
+    "said_beat_set_sampling_rate": (c_int, [c_void_p, c_int, _c_int_p]),
+    "said_beat_clips": (c_int, [c_void_p, c_void_p, c_int, _c_ll_p, c_void_p]),
+    "said_beat_coeffs": (c_int, [c_void_p, c_void_p, c_int, _c_ll_p, c_int, c_double, c_void_p]),
+    "said_beat_score": (c_int, [c_void_p, _c_int_p, c_double, c_double, _c_double_p, c_void_p]),
+    "said_beat_set_deltas": (c_int, [c_void_p, c_int, c_int, c_int, _c_double_p, c_void_p]),
+    "said_beat_vertex_error": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, _c_ll_p, _c_ll_p, _c_int_p, _c_int_p, _c_double_p, c_void_p]),
+    "said_beat_read_mel": (c_int, [c_void_p, _c_double_p, c_void_p]),
+    "said_beat_read_envelope": (c_int, [c_void_p, _c_double_p, c_void_p]),
+    "said_beat_read_onsets": (c_int, [c_void_p, _c_int_p, _c_int_p, c_void_p]),
+    "said_beat_read_rates": (c_int, [c_void_p, _c_double_p, c_void_p]),
+    "said_beat_read_minima": (c_int, [c_void_p, _c_int_p, _c_int_p, c_void_p]),
+}
 _GROUPS = {**LAZY_EXPORTS, "render": ("the renderer", RENDER_EXPORTS), "jpeg": ("the JPEG encoder", JPEG_EXPORTS),
-           "unet_train": ("the UNet trainer", UNET_TRAIN_EXPORTS)}
+           "unet_train": ("the UNet trainer", UNET_TRAIN_EXPORTS), "beat": ("the beat-consistency passes", BEAT_EXPORTS)}
 _bound = set()   # the groups bound so far
 
 
@@ -1186,3 +1205,137 @@ class JpegEngine(_Context):
         with torch.cuda.device(self.index):
             self._call("said_jpeg_read_coefficients", int(n_frames), out.ctypes.data_as(c_void_p), _stream())
         return out
+
+
+# ---- beat consistency and vertex error (include/said_beat.h)
+BEAT_N_FFT, BEAT_HOP, BEAT_N_MELS = 2048, 512, 128   # SAID_BEAT_*
+
+
+def _i64(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def host_f32(a) -> np.ndarray:
+    """A contiguous float32 host array of an array, a list or a tensor (on any device)."""
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+class BeatEngine(_Context):
+    """said_beat context on one GPU (include/said_beat.h): onsets of audio clips, change-rate minima of coefficient
+    sequences, the beat-consistency score of each sequence, and the vertex error of (real, generated) pairs; all in float64."""
+    prefix, group = "said_beat", "beat"
+    cpu_error, cpu_message = NoCpuPathError, "said_amd computes beat consistency and vertex error on MI355X only (device={}); there is no CPU path"
+
+    def __init__(self, device: torch.device, sampling_rate: Optional[int] = None):
+        super().__init__(device)
+        self._create()
+        self.sampling_rate, self.peak_pick = 0, None
+        self.frame_start = self.seq_off = self.delta_shape = None
+        if sampling_rate is not None:
+            self.set_sampling_rate(sampling_rate)
+
+    def _f32_dev(self, t: torch.Tensor, name: str) -> torch.Tensor:
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.device.index != self.index:
+            raise EngineError(f"{name} must be a contiguous float32 tensor on cuda:{self.index}, got {t.dtype} on {t.device}")
+        return t
+
+    def set_sampling_rate(self, sampling_rate: int):
+        """Forms the mel bank of the rate; returns librosa's peak-pick windows in frames (pre_max, post_max, pre_avg, post_avg, wait)."""
+        pick = (c_int * 5)()
+        self.sampling_rate, self.frame_start = 0, None
+        with torch.cuda.device(self.index):
+            self._call("said_beat_set_sampling_rate", int(sampling_rate), pick)
+        self.sampling_rate, self.peak_pick = int(sampling_rate), tuple(pick)
+        return self.peak_pick
+
+    def clips(self, wave: torch.Tensor, offsets) -> np.ndarray:
+        """Analyse the clips wave[offsets[i]:offsets[i + 1]] (one float32 device vector); returns the first frame number of each clip, (n + 1)."""
+        wave, offs = self._f32_dev(wave, "the waveforms"), _i64(offsets)
+        if wave.dim() != 1 or offs.ndim != 1 or offs.shape[0] < 2 or offs[-1] != wave.shape[0]:
+            raise EngineError(f"offsets must have n + 1 >= 2 entries ending at the {wave.numel()} samples of the waveforms")
+        self.frame_start = None
+        with torch.cuda.device(self.index):
+            self._call("said_beat_clips", _ptr(wave), offs.shape[0] - 1, offs.ctypes.data_as(_c_ll_p), _stream())
+        self.frame_start = np.concatenate([[0], np.cumsum(1 + np.diff(offs) // BEAT_HOP)]).astype(np.int64)
+        return self.frame_start
+
+    def coeffs(self, coeffs: torch.Tensor, offsets, threshold: float) -> None:
+        """Change rates and their minima of the sequences coeffs[offsets[i]:offsets[i + 1]], a (frames, channels) float32 device tensor."""
+        coeffs, offs = self._f32_dev(coeffs, "the coefficients"), _i64(offsets)
+        if coeffs.dim() != 2 or offs.ndim != 1 or offs.shape[0] < 2 or offs[-1] != coeffs.shape[0]:
+            raise EngineError(f"offsets must have n + 1 >= 2 entries ending at the {coeffs.shape[0]} frames of the coefficients")
+        self.seq_off = None
+        with torch.cuda.device(self.index):
+            self._call("said_beat_coeffs", _ptr(coeffs), offs.shape[0] - 1, offs.ctypes.data_as(_c_ll_p), coeffs.shape[1], float(threshold), _stream())
+        self.seq_off = offs
+
+    def score(self, clip_index, fps: float, sigma: float) -> np.ndarray:
+        """(n_seq,) float64: the score of each sequence of the last coeffs() against clip clip_index[s] of the last clips()."""
+        if self.seq_off is None or self.frame_start is None:
+            raise EngineError("score() needs clips() and coeffs() first")
+        idx = _i32(clip_index)
+        if idx.shape != (self.seq_off.shape[0] - 1,):
+            raise EngineError(f"clip_index must name one clip for each of the {self.seq_off.shape[0] - 1} sequences")
+        out = np.empty(idx.shape[0])
+        with torch.cuda.device(self.index):
+            self._call("said_beat_score", idx.ctypes.data_as(_c_int_p), float(fps), float(sigma), _dp(out), _stream())
+        return out
+
+    def set_deltas(self, deltas: np.ndarray) -> None:
+        """deltas (persons, channels, 3V) float64."""
+        d = np.ascontiguousarray(deltas, dtype=np.float64)
+        if d.ndim != 3:
+            raise EngineError(f"deltas must be (persons, channels, 3V), got {d.shape}")
+        self.delta_shape = None
+        with torch.cuda.device(self.index):
+            self._call("said_beat_set_deltas", d.shape[0], d.shape[1], d.shape[2], _dp(d), _stream())
+        self.delta_shape = d.shape
+
+    def vertex_error(self, coeffs: torch.Tensor, real_off, eval_off, length, person) -> np.ndarray:
+        """(n_pairs,) float64: max over t < length[p] of |(coeffs[real_off[p] + t] - coeffs[eval_off[p] + t]) @ deltas[person[p]]|."""
+        if self.delta_shape is None:
+            raise EngineError("vertex_error() needs set_deltas() first")
+        coeffs = self._f32_dev(coeffs, "the coefficients")
+        ro, eo, ln, pe = _i64(real_off), _i64(eval_off), _i32(length), _i32(person)
+        if coeffs.dim() != 2 or coeffs.shape[1] != self.delta_shape[1] or not (ro.shape == eo.shape == ln.shape == pe.shape) or ro.ndim != 1:
+            raise EngineError(f"coefficients must be (frames, {self.delta_shape[1]}) and the four pair tables of one length")
+        out = np.empty(ro.shape[0])
+        with torch.cuda.device(self.index):
+            self._call("said_beat_vertex_error", _ptr(coeffs), coeffs.shape[0], ro.shape[0], ro.ctypes.data_as(_c_ll_p), eo.ctypes.data_as(_c_ll_p),
+                       ln.ctypes.data_as(_c_int_p), pe.ctypes.data_as(_c_int_p), _dp(out), _stream())
+        return out
+
+    def _lists(self, name: str, start: np.ndarray):
+        counts, flat = np.zeros(start.shape[0] - 1, dtype=np.int32), np.zeros(int(start[-1]), dtype=np.int32)
+        with torch.cuda.device(self.index):
+            self._call(name, counts.ctypes.data_as(_c_int_p), flat.ctypes.data_as(_c_int_p), _stream())
+        return [flat[int(s):int(s) + int(n)].copy() for s, n in zip(start[:-1], counts)]
+
+    def _array(self, name: str, shape) -> np.ndarray:
+        out = np.empty(shape)
+        with torch.cuda.device(self.index):
+            self._call(name, _dp(out), _stream())
+        return out
+
+    def read_mel(self) -> np.ndarray:
+        """(frames, 128) mel power of all clips' frames."""
+        return self._array("said_beat_read_mel", (int(self.frame_start[-1]), BEAT_N_MELS))
+
+    def read_envelope(self) -> np.ndarray:
+        """(frames,) onset envelope of all clips' frames."""
+        return self._array("said_beat_read_envelope", (int(self.frame_start[-1]),))
+
+    def read_onsets(self):
+        """Per clip its onset frame indices, ascending."""
+        return self._lists("said_beat_read_onsets", self.frame_start)
+
+    def read_rates(self):
+        """Per sequence its (frames - 1,) change rates."""
+        flat = self._array("said_beat_read_rates", (int(self.seq_off[-1]),))
+        return [flat[int(a):int(b) - 1].copy() for a, b in zip(self.seq_off[:-1], self.seq_off[1:])]
+
+    def read_minima(self):
+        """Per sequence the indices of its change rate's minima, ascending."""
+        return self._lists("said_beat_read_minima", self.seq_off)

@@ -112,3 +112,12 @@ def fit_audio_unet(waveform: torch.FloatTensor, sampling_rate: int, fps: int, di
     missing = -n % quantum
     padded = torch.nn.functional.pad(waveform, (0, missing)) if missing else waveform
     return FittedWaveform(waveform=padded, window_size=int(n / sampling_rate * fps))
+
+
+def compute_audio_beat_time(waveform, sampling_rate: int, device=None) -> np.ndarray:
+    """Audio beat times in seconds of a mono waveform (T_a,): a restatement of ``librosa.onset.onset_detect(y=waveform, sr=sampling_rate,
+    units="time")`` with its defaults, computed on the MI355X in float64 (the reference's audio.py:78-96)."""
+    from ..metric.beat_consistency import analyse_clips, engine_for
+    eng = engine_for(device, sampling_rate)
+    analyse_clips(eng, [waveform])
+    return eng.read_onsets()[0].astype(np.float64) * 512 / float(sampling_rate)

@@ -1,0 +1,198 @@
+"""CPU checks of the beat-consistency restatement (tests/beat_ref.py): closed forms of the spectrum and the mel
+scale, librosa's peak-pick windows, the plateau rule against scipy's find_peaks, the score's conventions, the binding table against
+include/said_beat.h, the flags of script/evaluate_extra.py, and that the seeded fixtures of the GPU tests decide nothing within rounding."""
+import importlib.util
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+from scipy.signal import find_peaks
+
+import beat_ref as br
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _load(name, path):
+    spec = importlib.util.spec_from_file_location(name, path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("k", [64, 300, 1000])
+def test_sinusoid_at_a_bin_centre(k):
+    """A sin(2 pi k n / N) under the periodic Hann window: power (A N / 4)^2 at bin k, (A N / 8)^2 at k - 1 and k + 1, nothing two bins away."""
+    A, N = 0.7, br.N_FFT
+    y = A * np.sin(2 * np.pi * k * np.arange(8 * N) / N)
+    p = br.power_spectrum(y)[8]   # a frame that lies inside the signal
+    assert abs(p[k] - (A * N / 4) ** 2) <= 1e-9 * (A * N / 4) ** 2
+    for side in (k - 1, k + 1):
+        assert abs(p[side] - (A * N / 8) ** 2) <= 1e-9 * (A * N / 8) ** 2
+    assert p[k + 2] <= 1e-18 * p[k] and p[k - 2] <= 1e-18 * p[k]
+
+
+def test_frame_count_and_zero_padding():
+    assert [br.n_frames(n) for n in (1, 511, 512, 800, 2048, 2049)] == [1, 1, 2, 2, 5, 5]
+    y = np.ones(2048)
+    p = br.power_spectrum(y)
+    assert p.shape == (5, 1025)
+    # frame 0 covers 1024 zeros and the clip's first 1024 samples; its DC term is the window's second half summed: its peak of 1 at
+    # sample 1024 and half of the remaining 1023
+    assert abs(p[0, 0] - (br.N_FFT / 4 + 0.5) ** 2) <= 1e-9 * (br.N_FFT / 4) ** 2
+    assert abs(p[2, 0] - (br.N_FFT / 2) ** 2) <= 1e-9 * (br.N_FFT / 2) ** 2
+
+
+def test_slaney_scale_and_triangles():
+    assert br.hz_to_mel(1000.0) == 15.0 and abs(float(br.mel_to_hz(15.0)) - 1000.0) <= 1e-12
+    assert abs(br.hz_to_mel(6400.0) - 42.0) <= 1e-12 and abs(br.hz_to_mel(500.0) - 7.5) <= 1e-12
+    for sr in (16000, 44100):
+        bank, m = br.mel_bank(sr), br.mel_points(sr)
+        assert bank.shape == (128, 1025) and (bank >= 0).all() and m[0] == 0.0 and abs(m[-1] - sr / 2) <= 1e-9
+        spacing = (sr / 2) / 1024
+        # a unit-area triangle sampled every `spacing`: the rectangle rule is off by at most (spacing / base)^2 and change of a kink or two
+        for i in range(128):
+            base = m[i + 2] - m[i]
+            assert abs(bank[i].sum() * spacing - 1.0) <= 2.0 * (spacing / base) ** 2 + 1e-12, (sr, i)
+        assert (np.count_nonzero(bank, axis=0) <= 2).all()
+
+
+def test_peak_pick_parameters():
+    assert br.peak_params(16000) == (0, 1, 3, 4, 0)
+    assert br.peak_params(44100) == (2, 1, 8, 9, 2)
+
+
+def test_peak_pick_on_a_hand_made_envelope():
+    """At 16 kHz a frame is an onset when it exceeds its local mean (3 before, itself) by 0.07 of the range; at 44.1 kHz the max window and
+    `wait` apply too."""
+    env = np.array([0, 0, 0, 1.0, 0.9, 0.1, 0.1, 0.1, 0.1, 0.5, 0.1, 0.1, 0.1, 0.1, 0.1, 0.1, 0.1, 0.1])
+    on16, _ = br.peak_pick(env, 16000)
+    assert on16.tolist() == [3, 4, 9]
+    on44, _ = br.peak_pick(env, 44100)
+    assert on44.tolist() == [3, 9]           # 4 is not the maximum of [2, 4]
+    on, dec = br.peak_pick(np.zeros(9), 16000)
+    assert on.shape == (0,) and dec == []
+
+
+def test_plateau_rule_is_find_peaks():
+    rng = np.random.default_rng(3)
+    for trial in range(9):
+        r = np.round(rng.uniform(0, 2, size=rng.integers(3, 80)), 1 if trial % 2 else 6)   # one decimal: many exact plateaus
+        for thr in (0.0, 0.1, 0.5):
+            idx, props = find_peaks(-r, threshold=0)
+            want = idx[np.logical_or(props["left_thresholds"] > thr, props["right_thresholds"] > thr)]
+            assert br.minima_loop(r, thr).tolist() == want.tolist() == br.minima(r, thr)[0].tolist(), (trial, thr)
+    assert br.minima_loop(np.array([1.0]), 0.1).tolist() == [] and br.minima_loop(np.array([2.0, 1.0]), 0.1).tolist() == []
+    assert br.minima_loop(np.array([2.0, 1.0, 1.0, 1.0, 3.0]), 0.1).tolist() == []      # the middle of three: both sides level
+    assert br.minima_loop(np.array([2.0, 1.0, 1.0, 3.0]), 0.1).tolist() == [1]
+
+
+def test_score_conventions():
+    s = br.sequence_scores([np.array([0.5]), np.zeros(0), np.array([0.5, 1.0])], [np.zeros(0), np.array([0.2]), np.array([0.5, 2.0])], 0.1)
+    assert s[0] == 0.0 and math.isnan(s[1])
+    assert abs(s[2] - (1.0 + math.exp(-0.25 / 0.02)) / 2) <= 1e-15
+    with pytest.raises(ValueError):
+        br.change_rates([np.zeros((1, 32))])
+    rates = br.change_rates(br.constant_channel_sequences()[0])
+    assert all(np.isnan(r).all() for r in rates)
+
+
+def test_vertex_error_closed_form():
+    delta = np.zeros((2, 3, 3))
+    delta[0, 0, 0], delta[1, 2, 1] = 3.0, 4.0
+    real, gen = np.array([[1.0, 1.0], [0.0, 0.0], [9.0, 9.0]]), np.array([[0.0, 0.0], [0.5, 0.0]])
+    assert br.vertex_error(real, gen, delta) == 5.0   # frame 0: (3, 4); frame 1: 1.5; frame 2 lies past the shorter sequence
+
+
+def test_export_table_matches_the_header():
+    """include/said_beat.h's declarations are BEAT_EXPORTS, one argtypes entry per parameter, and the built library exports them."""
+    from said_amd import _engine
+    code = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, "include", "said_beat.h")).read(), flags=re.S)
+    decl = {name: 0 if params.strip() in ("", "void") else params.count(",") + 1
+            for name, params in re.findall(r"\b(said_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code)}
+    assert set(decl) == set(_engine.BEAT_EXPORTS) and len(decl) == 14
+    assert _engine._GROUPS["beat"][1] is _engine.BEAT_EXPORTS
+    assert not set(_engine.BEAT_EXPORTS) & {n for _, table in _engine.LAZY_EXPORTS.values() for n in table}
+    lib = _engine.load_library()
+    for name, n in decl.items():
+        assert hasattr(lib, name), f"{name} is declared but not exported"
+        assert len(_engine.BEAT_EXPORTS[name][1]) == n, f"{name}: {n} parameters declared, {len(_engine.BEAT_EXPORTS[name][1])} argtypes bound"
+    assert (_engine.BEAT_N_FFT, _engine.BEAT_HOP, _engine.BEAT_N_MELS) == (2048, 512, 128)
+    assert re.search(r"SAID_BEAT_N_FFT\s*=\s*2048\b", code) and re.search(r"SAID_BEAT_HOP\s*=\s*512\b", code) and re.search(r"SAID_BEAT_N_MELS\s*=\s*128\b", code)
+    assert _engine.ABI_VERSION == 9
+
+
+def test_driver_flags():
+    """script/evaluate_extra.py takes every flag of script/test_evaluate.py (the reference's flags among them, equal defaults) and its own."""
+    ex = _load("said_evaluate_extra_flags", os.path.join(ROOT, "script", "evaluate_extra.py"))
+    ap = ex.build_parser()
+    plain = ap.parse_args(["--vae_weights_path", "synthetic"])
+    assert plain.beat_consistency is False and plain.vertex_error is False
+    assert (plain.sampling_rate, plain.fps, plain.bc_threshold) == (16000, 60, 0.1)
+    assert vars(ex.ev.build_parser().parse_args(["--vae_weights_path", "synthetic"])).items() <= vars(plain).items()
+    args = ap.parse_args(["--vae_weights_path", "x.pth", "--beat_consistency", "--vertex_error", "--audio_dir", "a", "--coeffs_dir", "b",
+                          "--coeffs_real_dir", "c", "--blendshape_residuals_path", "d.pickle", "--sampling_rate", "44100", "--fps", "30",
+                          "--bc_threshold", "0.2", "--wind_num_clusters", "3", "--wind_num_repeats", "4", "--window_step_size", "2",
+                          "--device", "cuda:0", "--seed", "1"])
+    assert args.beat_consistency and args.vertex_error and (args.sampling_rate, args.fps, args.bc_threshold) == (44100, 30, 0.2)
+    assert args.blendshape_residuals_path == "d.pickle"
+    with pytest.raises(SystemExit):
+        ap.parse_args(["--vae_weights_path", "synthetic", "--beat"])          # no abbreviations: the flags are filtered by their full names
+    assert ap.parse_args(["--vae_weights_path", "synthetic", "--vertex_error", "--only_extra"]).only_extra
+    with pytest.raises(SystemExit, match="does not exist"):   # refused before anything is computed
+        ex.main(["--vae_weights_path", "synthetic", "--vertex_error", "--blendshape_residuals_path", os.path.join(ROOT, "no", "such.pickle")])
+    with pytest.raises(SystemExit, match="does not exist"):
+        ex.evaluate_vertex_error([], [], os.path.join(ROOT, "no", "such.pickle"), "cuda:0")
+
+
+def test_no_cpu_path():
+    import torch
+    from said_amd import _engine, metric
+    from said_amd.util.audio import compute_audio_beat_time
+    assert {"beat_consistency", "vertex_error"} <= set(metric.__all__)
+    with pytest.raises(_engine.NoCpuPathError):
+        _engine.BeatEngine(torch.device("cpu"))
+    seqs, _ = br.constant_channel_sequences()
+    with pytest.raises(_engine.NoCpuPathError):
+        metric.beat_consistency.beat_consistency_score([np.zeros(800, dtype=np.float32)] * 2, seqs, 16000, 60, 0.1, device="cpu")
+    with pytest.raises(_engine.NoCpuPathError):
+        metric.vertex_error.vertex_error(seqs[0], seqs[1], np.zeros((32, 5, 3)), device="cpu")
+    with pytest.raises(_engine.NoCpuPathError):
+        compute_audio_beat_time(np.zeros(800, dtype=np.float32), 16000, device="cpu")
+    with pytest.raises(ValueError, match="fewer than 2 frames"):
+        metric.beat_consistency.beat_consistency_score([np.zeros(800, dtype=np.float32)], [np.zeros((1, 32), dtype=np.float32)], 16000, 60, 0.1, device="cpu")
+    if not torch.cuda.is_available():   # the default device, where there is none
+        with pytest.raises(_engine.NoCpuPathError):
+            metric.beat_consistency.beat_consistency_score([np.zeros(800, dtype=np.float32)] * 2, seqs, 16000, 60, 0.1)
+        with pytest.raises(_engine.NoCpuPathError):
+            compute_audio_beat_time(np.zeros(800, dtype=np.float32), 16000)
+
+
+def test_fixtures_decide_nothing_within_rounding():
+    """A condition on the GPU tests' inputs, not on the code under test: in the restatement no decision of the seeded fixtures has a margin
+    below 1e-6 (no two neighbouring rates differ by less than 1e-9 without being equal), so the device must reproduce every index; and every
+    group has an onset and a kinematic beat."""
+    groups = [(16000, br.clips_16k()), (44100, [br.clip_44k()])]
+    for sr, clips in groups:
+        beats = [br.audio_beats(y, sr) for y in clips]
+        assert min(br.onset_margin(b["decisions"]) for b in beats) >= 1e-6, sr
+        assert sum(len(b["onsets"]) for b in beats) >= 1, sr
+        assert all(b["env"].shape == (br.n_frames(len(y)),) for b, y in zip(beats, clips))
+    silent = br.audio_beats(br.clips_16k()[-1], 16000)
+    assert silent["onsets"].shape == (0,) and not silent["env"].any()
+    seqs, clip_index = br.sequences()
+    assert [c.shape for c in seqs] == [(T, 32) for T in br.SEQ_FRAMES] and len(clip_index) == len(seqs)
+    assert all(c.dtype == np.float32 and c.min() >= 0.0 and c.max() <= 1.0 for c in seqs)
+    rates = br.change_rates(seqs)
+    zeros = [int(np.count_nonzero(r == 0.0)) for r in rates]
+    assert zeros[5] == 5 and zeros[6] == 5          # rows copied over 3 and 4 frames: plateaus of 2 and 3 equal rates
+    for thr in (0.1, 0.5):
+        found = 0
+        for r in rates:
+            idx, margins = br.minima(r, thr)
+            sides, steps = margins[:len(margins) - np.count_nonzero(np.diff(r))], margins[len(margins) - np.count_nonzero(np.diff(r)):]
+            assert all(m >= 1e-6 for m in sides) and all(m >= 1e-9 for m in steps), thr
+            found += len(idx)
+        assert found >= 1, thr
