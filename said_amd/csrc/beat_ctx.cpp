@@ -113,25 +113,16 @@ int frames_of(double seconds, int sr) {
 extern "C" {
 
 int said_beat_create(said_beat** out, int device) {
-    if (!out) return fail(nullptr, "said_beat_create: out is null");
-    *out = nullptr;
     DeviceRestore restore_device;
-    if (open_device("said_beat_create", device)) return -1;
-    said_beat* b = new said_beat();
-    b->c.device = device;
+    said_beat* b = new_ctx("said_beat_create", out, device);
+    if (!b) return -1;
     *out = b;
     return 0;
 }
 
-int said_beat_destroy(said_beat* b) {
-    if (!b) return 0;
-    DeviceRestore restore_device;
-    free_allocs(&b->c);
-    delete b;
-    return 0;
-}
+int said_beat_destroy(said_beat* b) { return delete_ctx(b); }
 
-const char* said_beat_last_error(const said_beat* b) { return b ? b->c.err.c_str() : g_create_err.c_str(); }
+const char* said_beat_last_error(const said_beat* b) { return ctx_error(b); }
 
 int said_beat_set_sampling_rate(said_beat* b, int sampling_rate, int* pick_host) {
     if (!b) return -1;

@@ -529,25 +529,16 @@ struct said_optimize {
 extern "C" {
 
 int said_optimize_create(said_optimize** out, int device) {
-    if (!out) return fail(nullptr, "said_optimize_create: out is null");
-    *out = nullptr;
     DeviceRestore restore_device;
-    if (open_device("said_optimize_create", device)) return -1;
-    said_optimize* o = new said_optimize();
-    o->c.device = device;
+    said_optimize* o = new_ctx("said_optimize_create", out, device);
+    if (!o) return -1;
     *out = o;
     return 0;
 }
 
-int said_optimize_destroy(said_optimize* o) {
-    if (!o) return 0;
-    DeviceRestore restore_device;
-    free_allocs(&o->c);
-    delete o;
-    return 0;
-}
+int said_optimize_destroy(said_optimize* o) { return delete_ctx(o); }
 
-const char* said_optimize_last_error(const said_optimize* o) { return o ? o->c.err.c_str() : g_create_err.c_str(); }
+const char* said_optimize_last_error(const said_optimize* o) { return ctx_error(o); }
 
 int said_optimize_set_bases(said_optimize* o, int nbasis, int k, long long n3v, const double* neutral_host, const double* bdelta_host,
                             const double* p_host, void* stream) {

@@ -61,6 +61,18 @@ static void release_cap_streams(said_ctx* ctx) {
     ctx->cap_stream = nullptr;
 }
 
+// The fixed-size device cells of a context (Cells), for said_create and said_clone.
+int alloc_cells(said_ctx* ctx) {
+    int rc = 0;
+    rc |= dalloc(ctx, &ctx->coef1_dev, 8);
+    rc |= dalloc(ctx, &ctx->step_dev, 4);
+    rc |= dalloc(ctx, &ctx->status_dev, 4);
+    rc |= dalloc(ctx, &ctx->chain_ticket, CHAIN2_MAX_TILES * 6);
+    rc |= dalloc(ctx, &ctx->seed_dev, 4);
+    rc |= dalloc(ctx, &ctx->clk_dev, 64 * 128);
+    return rc;
+}
+
 // The workspace of a context: every buffer whose size depends on (max_batch_eff, max_frames).  Allocated by said_create and
 // replaced as a whole by said_reserve; weights, packed tables and the lazily grown audio / noise buffers are not touched.
 int alloc_workspace(said_ctx* ctx, int max_batch_eff, int max_frames) {
@@ -155,13 +167,7 @@ int said_create(said_ctx** out, int device, int max_batch_eff, int max_frames, i
     configure_xgemm_kernels();
     configure_rgemm_kernels();
 
-    int rc = 0;
-    rc |= dalloc(ctx, &ctx->coef1_dev, 8);
-    rc |= dalloc(ctx, &ctx->step_dev, 4);
-    rc |= dalloc(ctx, &ctx->status_dev, 4);
-    rc |= dalloc(ctx, &ctx->chain_ticket, CHAIN2_MAX_TILES * 6);
-    rc |= dalloc(ctx, &ctx->seed_dev, 4);
-    rc |= dalloc(ctx, &ctx->clk_dev, 64 * 128);
+    int rc = alloc_cells(ctx);
     rc |= dalloc(ctx, &ctx->freqs, MC / 2);
     rc |= alloc_workspace(ctx, max_batch_eff, max_frames);
     if (rc) { g_create_err = ctx->err; said_destroy(ctx); return -1; }
@@ -276,33 +282,16 @@ int said_clone(said_ctx* parent, said_ctx** out, int max_batch_eff, int max_fram
         said_ctx* ctx = parent;
         HIPCHK(hipSetDevice(parent->device));
     }
-    // a copy of the parent: every packed weight / table pointer is SHARED (read-only on the device); everything a run writes is its own
-    said_ctx* c = new said_ctx(*parent);
-    c->err.clear(); c->launch_err.clear(); c->host_w.clear();
-    c->allocs.clear(); c->ws_allocs.clear(); c->alloc_list = &c->allocs;
+    // a new context with the parent's model and switches: every packed weight / table pointer is SHARED (read-only on the device); everything a run writes is its own
+    said_ctx* c = new said_ctx();
+    static_cast<ModelWeights&>(*c) = *parent;
+    static_cast<Switches&>(*c) = *parent;
+    c->device = parent->device;
     c->is_clone = true;
-    c->graph = c->graph_rem = nullptr; c->gexec = c->gexec_rem = nullptr; c->gkey.clear(); c->gnodes = 0;
-    c->cap_stream = nullptr; c->own_stream = nullptr;
-    c->stage_log.clear(); c->log_on = false; c->dbg_stop = -1; c->dbg_only = -1; c->dbg_count = 0; c->clk_on = false; c->xclk_on = false;
-    // lazily grown buffers start empty
-    c->abufA = c->abufB = nullptr; c->abuf_elems[0] = c->abuf_elems[1] = 0;
-    c->aH = c->aT = c->aO = c->aQK = c->aVT = c->aF = c->aPOS = c->aX = nullptr; c->a_tok_elems = 0;
-    c->bA0 = c->bA1 = c->bX = c->bHb = c->bF = c->bO = nullptr; c->bH = c->bT = c->bPosT = nullptr; c->b_conv_elems[0] = c->b_conv_elems[1] = 0; c->b_tok = 0;
-    c->bXg = nullptr; c->bXg_elems = 0;
-    c->noise_cm = nullptr; c->noise_cm_elems = 0;
-    c->kvt_S = -1;   // (the clone's own workspace holds no key-major copy yet)
-    said_ctx* ctx = c;
     auto bail = [&](const char* what) { parent->err = std::string("said_clone: ") + what + (c->err.empty() ? "" : ": " + c->err); said_destroy(c); return -1; };
     c->own_stream = pool_stream(parent->device, parent->n_clones++ % POOL_STREAMS);
     if (!c->own_stream) return bail("hipStreamCreateWithFlags failed");
-    c->n_clones = 0;
-    int rc = 0;
-    rc |= dalloc(ctx, &c->coef1_dev, 8);
-    rc |= dalloc(ctx, &c->step_dev, 4);
-    rc |= dalloc(ctx, &c->status_dev, 4);
-    rc |= dalloc(ctx, &c->chain_ticket, CHAIN2_MAX_TILES * 6);
-    rc |= dalloc(ctx, &c->seed_dev, 4);
-    rc |= dalloc(ctx, &c->clk_dev, 64 * 128);
+    int rc = alloc_cells(c);
     rc |= alloc_workspace(c, max_batch_eff, max_frames);
     if (rc) return bail("workspace allocation failed");
     *out = c;
@@ -666,6 +655,15 @@ int said_debug_clocks(said_ctx* ctx, int enable, long long* out_host /* [64][8][
     return 0;
 }
 
+// The said_debug_option names whose value is a tri-state: < 0 the default (-1), 0 off, anything else on (1).
+struct TriState { const char* name; int Switches::*field; };
+static const TriState kTriStates[] = {
+    {"tm_acts", &Switches::tm_acts},           {"gemm_presplit", &Switches::gemm_presplit}, {"gemm_split", &Switches::gemm_split},
+    {"attn_split", &Switches::attn_split},     {"attn_presplit", &Switches::attn_presplit}, {"out_split", &Switches::out_split},
+    {"ugemm_split", &Switches::ugemm_split},   {"chain_coef", &Switches::chain_coef},       {"tgemm_direct", &Switches::tgemm_direct},
+    {"st_chain", &Switches::st_chain},         {"attn_2q", &Switches::attn_2q},             {"st_chain_bf16", &Switches::st_chain_bf16},
+};
+
 int said_debug_option(said_ctx* ctx, const char* name, long long value) {
     if (!ctx || !name) return -1;
     const std::string k = name;
@@ -684,36 +682,15 @@ int said_debug_option(said_ctx* ctx, const char* name, long long value) {
         ctx->out_tm = (int)value;
     } else if (k == "xgemm_clk") {   // shader-clock stamps of the token-major-activation GEMMs (-DSAID_CLK_STAMPS builds); read with said_debug_clocks
         ctx->xclk_on = value != 0;
-    } else if (k == "tm_acts") {
-        ctx->tm_acts = value < 0 ? -1 : (value != 0);
-    } else if (k == "gemm_presplit") {
-        ctx->gemm_presplit = value < 0 ? -1 : (value != 0);
-    } else if (k == "gemm_split") {
-        ctx->gemm_split = value < 0 ? -1 : (value != 0);
-    } else if (k == "attn_split") {
-        ctx->attn_split = value < 0 ? -1 : (value != 0);
-    } else if (k == "attn_presplit") {
-        ctx->attn_presplit = value < 0 ? -1 : (value != 0);
-    } else if (k == "out_split") {
-        ctx->out_split = value < 0 ? -1 : (value != 0);
-    } else if (k == "ugemm_split") {
-        ctx->ugemm_split = value < 0 ? -1 : (value != 0);
-    } else if (k == "chain_coef") {
-        ctx->chain_coef = value < 0 ? -1 : (value != 0);
-    } else if (k == "tgemm_direct") {
-        ctx->tgemm_direct = value < 0 ? -1 : (value != 0);
     } else if (k == "kconv") {
         ctx->kconv = value < 0 ? -1 : (value == 2 ? 2 : (value != 0));
-    } else if (k == "st_chain") {
-        ctx->st_chain = value < 0 ? -1 : (value != 0);
-    } else if (k == "attn_2q") {
-        ctx->attn_2q = value < 0 ? -1 : (value != 0);
     } else if (k == "st_chain_slices") {
         ctx->st_chain_slices = value < 0 ? -1 : ((value == 3 || value == 2) ? (int)value : 1);   // 2: two slices wherever a sliced launch is possible (<= 128 tiles)
-    } else if (k == "st_chain_bf16") {
-        ctx->st_chain_bf16 = value < 0 ? -1 : (value != 0);
     } else {
-        return fail(ctx, "said_debug_option: unknown option %s", name);
+        int Switches::*tri = nullptr;
+        for (const TriState& t : kTriStates) if (k == t.name) tri = t.field;
+        if (!tri) return fail(ctx, "said_debug_option: unknown option %s", name);
+        ctx->*tri = value < 0 ? -1 : (value != 0);
     }
     ctx->gkey.clear();   // the captured step graph may hold the other schedule
     return 0;

@@ -118,25 +118,16 @@ std::vector<unsigned char> make_header(int width, int height, const unsigned cha
 extern "C" {
 
 int said_jpeg_create(said_jpeg** out, int device) {
-    if (!out) return fail(nullptr, "said_jpeg_create: out is null");
-    *out = nullptr;
     DeviceRestore restore_device;
-    if (open_device("said_jpeg_create", device)) return -1;
-    said_jpeg* j = new said_jpeg();
-    j->c.device = device;
+    said_jpeg* j = new_ctx("said_jpeg_create", out, device);
+    if (!j) return -1;
     *out = j;
     return 0;
 }
 
-int said_jpeg_destroy(said_jpeg* j) {
-    if (!j) return 0;
-    DeviceRestore restore_device;
-    free_allocs(&j->c);
-    delete j;
-    return 0;
-}
+int said_jpeg_destroy(said_jpeg* j) { return delete_ctx(j); }
 
-const char* said_jpeg_last_error(const said_jpeg* j) { return j ? j->c.err.c_str() : g_create_err.c_str(); }
+const char* said_jpeg_last_error(const said_jpeg* j) { return ctx_error(j); }
 
 int said_jpeg_configure(said_jpeg* j, int width, int height, int quality) {
     if (!j) return -1;

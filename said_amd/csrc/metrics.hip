@@ -339,14 +339,11 @@ int reduce_to_host(said_metrics* m, const double* part, int nblk, int M, double*
 extern "C" {
 
 int said_metrics_create(said_metrics** out, int device, long long max_points) {
-    if (!out) return fail(nullptr, "said_metrics_create: out is null");
-    *out = nullptr;
     DeviceRestore restore_device;
-    if (open_device("said_metrics_create", device)) return -1;
-    if (max_points < 1 || max_points > (1LL << 30)) return fail(nullptr, "said_metrics_create: max_points %lld outside [1, 2^30]", max_points);
-    said_metrics* m = new said_metrics();
+    said_metrics* m = new_ctx("said_metrics_create", out, device);
+    if (!m) return -1;
+    if (max_points < 1 || max_points > (1LL << 30)) { delete m; return fail(nullptr, "said_metrics_create: max_points %lld outside [1, 2^30]", max_points); }
     HostCtx* ctx = &m->c;
-    ctx->device = device;
     m->maxN = max_points;
     m->pblk = (int)((max_points + PT - 1) / PT);
     const size_t N = (size_t)max_points;
@@ -365,15 +362,9 @@ int said_metrics_create(said_metrics** out, int device, long long max_points) {
     return 0;
 }
 
-int said_metrics_destroy(said_metrics* m) {
-    if (!m) return 0;
-    DeviceRestore restore_device;
-    free_allocs(&m->c);
-    delete m;
-    return 0;
-}
+int said_metrics_destroy(said_metrics* m) { return delete_ctx(m); }
 
-const char* said_metrics_last_error(const said_metrics* m) { return m ? m->c.err.c_str() : g_create_err.c_str(); }
+const char* said_metrics_last_error(const said_metrics* m) { return ctx_error(m); }
 
 long long said_metrics_max_points(const said_metrics* m) { return m ? m->maxN : 0; }
 

@@ -59,25 +59,16 @@ int read_stage(said_render* r, const char* entry, const float* src, int n_frames
 extern "C" {
 
 int said_render_create(said_render** out, int device) {
-    if (!out) return fail(nullptr, "said_render_create: out is null");
-    *out = nullptr;
     DeviceRestore restore_device;
-    if (open_device("said_render_create", device)) return -1;
-    said_render* r = new said_render();
-    r->c.device = device;
+    said_render* r = new_ctx("said_render_create", out, device);
+    if (!r) return -1;
     *out = r;
     return 0;
 }
 
-int said_render_destroy(said_render* r) {
-    if (!r) return 0;
-    DeviceRestore restore_device;
-    free_allocs(&r->c);
-    delete r;
-    return 0;
-}
+int said_render_destroy(said_render* r) { return delete_ctx(r); }
 
-const char* said_render_last_error(const said_render* r) { return r ? r->c.err.c_str() : g_create_err.c_str(); }
+const char* said_render_last_error(const said_render* r) { return ctx_error(r); }
 
 int said_render_set_mesh(said_render* r, int nv, int nf, int k, const double* neutral_host, const int* faces_host, const double* blendshapes_host,
                          void* stream) {

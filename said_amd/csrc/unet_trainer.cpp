@@ -515,15 +515,12 @@ const char* said_unet_train_tensor_name(int i) { return (i >= 0 && i < (int)tabl
 long long said_unet_train_tensor_numel(int i) { return (i >= 0 && i < (int)table().size()) ? table()[i].numel : -1; }
 
 int said_unet_train_create(said_unet_train** out, int device, int max_batch, int max_frames) {
-    if (!out) return fail(nullptr, "said_unet_train_create: out is null");
-    *out = nullptr;
     DeviceRestore restore_device;
-    if (open_device("said_unet_train_create", device)) return -1;
-    if (max_batch < 1 || max_batch > 256) return fail(nullptr, "said_unet_train_create: max_batch %d outside [1, 256]", max_batch);
-    if (max_frames < 2 || max_frames > 2048) return fail(nullptr, "said_unet_train_create: max_frames %d outside [2, 2048]", max_frames);
-    said_unet_train* t = new said_unet_train();
+    said_unet_train* t = new_ctx("said_unet_train_create", out, device);
+    if (!t) return -1;
+    if (max_batch < 1 || max_batch > 256) { delete t; return fail(nullptr, "said_unet_train_create: max_batch %d outside [1, 256]", max_batch); }
+    if (max_frames < 2 || max_frames > 2048) { delete t; return fail(nullptr, "said_unet_train_create: max_frames %d outside [2, 2048]", max_frames); }
     HostCtx* ctx = &t->c;
-    ctx->device = device;
     t->maxB = max_batch;
     t->maxT = max_frames;
     const auto& tb = table();
@@ -553,14 +550,11 @@ int said_unet_train_destroy(said_unet_train* t) {
     if (!t) return 0;
     DeviceRestore restore_device;
     (void)hipSetDevice(t->c.device);
-    if (t->s) (void)hipStreamSynchronize(t->s);
-    free_allocs(&t->c);
-    if (t->s) (void)hipStreamDestroy(t->s);
-    delete t;
-    return 0;
+    if (t->s) { (void)hipStreamSynchronize(t->s); (void)hipStreamDestroy(t->s); }
+    return delete_ctx(t);
 }
 
-const char* said_unet_train_last_error(const said_unet_train* t) { return t ? t->c.err.c_str() : g_create_err.c_str(); }
+const char* said_unet_train_last_error(const said_unet_train* t) { return ctx_error(t); }
 
 static float* copy_of(said_unet_train* t, int which, int i) { return store_copy_of(&t->st, which, t->off.at(table()[i].name)); }
 

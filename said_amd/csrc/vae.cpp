@@ -135,14 +135,13 @@ int load_vae_decoder(said_vae* v) {
 extern "C" {
 
 int said_vae_create(said_vae** out, int device, int in_channels, int seq_len, int z_dim) {
-    if (!out) return fail(nullptr, "said_vae_create: out is null");
-    *out = nullptr;
     DeviceRestore restore_device;
-    if (open_device("said_vae_create", device)) return -1;
-    if (in_channels != 32 || seq_len != 120 || z_dim != 64)
+    said_vae* v = new_ctx("said_vae_create", out, device);
+    if (!v) return -1;
+    if (in_channels != 32 || seq_len != 120 || z_dim != 64) {
+        delete v;   // (nothing allocated yet)
         return fail(nullptr, "said_vae_create: only BCVAE(channels=32, seq_len=120, z_dim=64) is supported (the FC stack is sized for it, vae.py:52)");
-    said_vae* v = new said_vae();
-    v->c.device = device;
+    }
     v->seq_len = seq_len; v->cin = in_channels; v->zdim = z_dim;
     v->L[0] = seq_len;
     for (int i = 0; i < 4; ++i) v->L[i + 1] = (v->L[i] - v->conv_k[i]) / v->conv_s[i] + 1;   // 118, 116, 57, 55
@@ -151,15 +150,9 @@ int said_vae_create(said_vae** out, int device, int in_channels, int seq_len, in
     return 0;
 }
 
-int said_vae_destroy(said_vae* v) {
-    if (!v) return 0;
-    DeviceRestore restore_device;
-    free_allocs(&v->c);
-    delete v;
-    return 0;
-}
+int said_vae_destroy(said_vae* v) { return delete_ctx(v); }
 
-const char* said_vae_last_error(const said_vae* v) { return v ? v->c.err.c_str() : g_create_err.c_str(); }
+const char* said_vae_last_error(const said_vae* v) { return ctx_error(v); }
 
 int said_vae_set_weight(said_vae* v, const char* name, const float* data_host, const int64_t* shape, int ndim) {
     if (!v) return -1;

@@ -269,14 +269,11 @@ long long said_train_tensor_numel(int i) { return (i >= 0 && i < 70) ? kTensors[
 int said_train_tensor_is_counter(int i) { return (i >= 0 && i < 70) ? (kTensors[i].kind == K_COUNT) : -1; }
 
 int said_train_create(said_train** out, int device, int max_batch) {
-    if (!out) return fail(nullptr, "said_train_create: out is null");
-    *out = nullptr;
     DeviceRestore restore_device;
-    if (open_device("said_train_create", device)) return -1;
-    if (max_batch < 1 || max_batch > 4096) return fail(nullptr, "said_train_create: max_batch %d outside [1, 4096]", max_batch);
-    said_train* t = new said_train();
+    said_train* t = new_ctx("said_train_create", out, device);
+    if (!t) return -1;
+    if (max_batch < 1 || max_batch > 4096) { delete t; return fail(nullptr, "said_train_create: max_batch %d outside [1, 4096]", max_batch); }
     HostCtx* ctx = &t->c;
-    ctx->device = device;
     t->maxB = max_batch;
     std::vector<long long> sizes(70);
     for (int i = 0; i < 70; ++i) sizes[i] = kTensors[i].kind == K_PARAM ? kTensors[i].numel : 0;
@@ -325,13 +322,11 @@ int said_train_destroy(said_train* t) {
     for (int k = 0; k < RING; ++k)
         if (t->ring_ev[k]) (void)hipEventDestroy(t->ring_ev[k]);
     if (t->ring) (void)hipHostFree(t->ring);
-    free_allocs(&t->c);
-    if (t->s) (void)hipStreamDestroy(t->s);
-    delete t;
-    return 0;
+    if (t->s) (void)hipStreamDestroy(t->s);   // (synchronised above)
+    return delete_ctx(t);
 }
 
-const char* said_train_last_error(const said_train* t) { return t ? t->c.err.c_str() : g_create_err.c_str(); }
+const char* said_train_last_error(const said_train* t) { return ctx_error(t); }
 
 int said_train_set_tensor(said_train* t, int which, const char* name, const void* host, long long n) {
     if (!t) return -1;
