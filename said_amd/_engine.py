@@ -1,5 +1,5 @@
 """ctypes binding of libsaid_hip.so (C ABI: include/said_hip.h, said_metrics.h, said_optimize.h, said_train.h, said_render.h, said_jpeg.h,
-said_unet_train.h, said_beat.h).
+said_unet_train.h, said_beat.h, said_render_ms.h).
 
 There is deliberately no fallback: if the library is missing, cannot be loaded,
 or no gfx950 device is visible, every entry point raises.
@@ -164,6 +164,11 @@ RENDER_EXPORTS = {
     "said_render_read_normals": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
     "said_render_read_colors": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
 }
+# include/said_render_ms.h: the renderer's multisampled entry, a group of its own (tests/test_render_ms_cpu.py checks it against its header)
+RENDER_MS_EXPORTS = {
+    "said_render_render_ms": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_float, _c_double_p, _c_double_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
+}
 # include/said_jpeg.h: a group like the renderer's, in a table of its own (tests/test_jpeg_ref_cpu.py checks it against its header)
 JPEG_EXPORTS = {
     "said_jpeg_create": (c_int, [POINTER(c_void_p), c_int]),
@@ -214,7 +219,8 @@ BEAT_EXPORTS = {
     "said_beat_read_rates": (c_int, [c_void_p, _c_double_p, c_void_p]),
     "said_beat_read_minima": (c_int, [c_void_p, _c_int_p, _c_int_p, c_void_p]),
 }
-_GROUPS = {**LAZY_EXPORTS, "render": ("the renderer", RENDER_EXPORTS), "jpeg": ("the JPEG encoder", JPEG_EXPORTS),
+_GROUPS = {**LAZY_EXPORTS, "render": ("the renderer", RENDER_EXPORTS), "render_ms": ("multisampled rendering", RENDER_MS_EXPORTS),
+           "jpeg": ("the JPEG encoder", JPEG_EXPORTS),
            "unet_train": ("the UNet trainer", UNET_TRAIN_EXPORTS), "beat": ("the beat-consistency passes", BEAT_EXPORTS)}
 _bound = set()   # the groups bound so far
 
@@ -1103,11 +1109,13 @@ class RenderEngine(_Context):
             self._call("said_render_set_colormap", a.ctypes.data_as(_c_float_p), _stream())
 
     def render(self, coeffs: torch.Tensor, t0: int, n_frames: int, out: torch.Tensor, target: Optional[torch.Tensor] = None, max_diff: float = 0.001,
-               rot=None, t_center=None, face_ids: Optional[torch.Tensor] = None) -> None:
+               rot=None, t_center=None, face_ids: Optional[torch.Tensor] = None, samples: int = 1, sample_ids: Optional[torch.Tensor] = None) -> None:
         """Frames [t0, t0 + n_frames) of coeffs (T, K) into out, a contiguous (>= n_frames, H, W, 3) uint8 device tensor, B G R; enqueued on the
-        current stream.  face_ids: a contiguous (>= n_frames, H, W) int32 device tensor that receives the face drawn at each pixel (-1: none)."""
+        current stream.  face_ids: a contiguous (>= n_frames, H, W) int32 device tensor that receives the face drawn at each pixel (-1: none).
+        samples: 1, or 4 for the multisampled render of include/said_render_ms.h, which takes no face_ids and fills sample_ids instead, a
+        contiguous (>= n_frames, H, W, 4) int32 device tensor: the face of each of a pixel's four samples."""
         if self.nf == 0:
-            raise EngineError("said_render_render: no mesh set (set_mesh)")
+            raise EngineError(("said_render_render" if samples == 1 and sample_ids is None else "said_render_render_ms") + ": no mesh set (set_mesh)")
         coeffs = _check_dev(coeffs, "blendshape_coeffs")
         if coeffs.dim() != 2 or coeffs.shape[1] != self.k:
             raise EngineError(f"blendshape_coeffs must be (T, {self.k}), got {tuple(coeffs.shape)}")
@@ -1118,7 +1126,7 @@ class RenderEngine(_Context):
             if target.shape != coeffs.shape:
                 raise EngineError(f"target_blendshape_coeffs must have the shape of blendshape_coeffs {tuple(coeffs.shape)}, got {tuple(target.shape)}")
         need = n_frames * self.height * self.width
-        for t, name, dt, per in ((out, "out", torch.uint8, 3), (face_ids, "face_ids", torch.int32, 1)):
+        for t, name, dt, per in ((out, "out", torch.uint8, 3), (face_ids, "face_ids", torch.int32, 1), (sample_ids, "sample_ids", torch.int32, 4)):
             if t is None:
                 continue
             if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() < need * per or t.device.index != self.index:
@@ -1128,8 +1136,13 @@ class RenderEngine(_Context):
         r = None if rot is None else np.ascontiguousarray(rot, dtype=np.float64).reshape(3)
         c = None if t_center is None else np.ascontiguousarray(t_center, dtype=np.float64).reshape(3)
         with torch.cuda.device(self.index):
-            self._call("said_render_render", _ptr(coeffs), _ptr(target), int(t0), int(n_frames), float(max_diff), None if r is None else _dp(r),
-                       None if c is None else _dp(c), _ptr(out), _ptr(face_ids), _stream())
+            if samples == 1 and sample_ids is None:
+                self._call("said_render_render", _ptr(coeffs), _ptr(target), int(t0), int(n_frames), float(max_diff), None if r is None else _dp(r),
+                           None if c is None else _dp(c), _ptr(out), _ptr(face_ids), _stream())
+            else:   # what goes with which sample count is said_render_render_ms's to refuse
+                load_library("render_ms")
+                self._call("said_render_render_ms", int(samples), _ptr(coeffs), _ptr(target), int(t0), int(n_frames), float(max_diff),
+                           None if r is None else _dp(r), None if c is None else _dp(c), _ptr(out), _ptr(face_ids), _ptr(sample_ids), _stream())
         self._keep = (coeffs, target)   # alive until the next call: the kernels may still be reading them
 
     def _read(self, name: str, n_frames: int) -> np.ndarray:

@@ -72,7 +72,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     # every header any source may include: a change to one of them rebuilds all objects
     headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
-    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("said_hip.h", "said_metrics.h", "said_optimize.h", "said_train.h", "said_unet_train.h", "said_render.h", "said_jpeg.h", "said_beat.h")]
+    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("said_hip.h", "said_metrics.h", "said_optimize.h", "said_train.h", "said_unet_train.h", "said_render.h", "said_render_ms.h", "said_jpeg.h", "said_beat.h")]
     objs, jobs = [], []
     for src in SOURCES:
         sp = os.path.join(CSRC, src)

@@ -6,6 +6,7 @@
 //   vertex_normals_kernel   angle-weighted smooth normals, gathered through the incidence list in ascending face order  one thread per vertex
 //   tri_setup_kernel        rotation about t_center, pinhole projection, winding made positive, pixel box            one thread per triangle
 //   raster_shade_kernel     one workgroup per 32 x 32 tile: box cull + ballot compaction into LDS, depth test in registers, shading in place
+//   raster_shade_ms_kernel  in its place at 4 samples per pixel (section 15.2): coverage and depth per sample, one shade per face, box resolve
 // fp32 throughout, no atomics; every product-sum that section 15 writes as a chain is an explicit fmaf chain (the library is built with
 // -ffp-contract=off, so nothing else is fused).
 #include "render_kernels.h"
@@ -357,6 +358,149 @@ __global__ __launch_bounds__(256) void raster_shade_kernel(Mesh m, Frames f, Cam
     }
 }
 
+// The 4-sample variant: coverage and depth per sample at the rotated-grid offsets below, the winners of a thread's
+// 4 pixels x 4 samples in registers (every index a compile-time constant: all loops over them are unrolled), then one shade per distinct
+// face of a pixel at the pixel centre, to_u8 per sample and the box resolve (c0 + c1 + c2 + c3 + 2) >> 2.  The tile scan is that of
+// raster_shade_kernel; the compacting thread also leaves the triangle's pixel box in the two spare words of its LDS record, so a thread
+// whose four pixels lie outside the box skips the sixteen sample tests (the box holds every sample of every pixel the triangle can touch).
+__device__ __forceinline__ constexpr float ms_ox(int s) { return s == 0 ? -0.125f : s == 1 ? 0.375f : s == 2 ? -0.375f : 0.125f; }
+__device__ __forceinline__ constexpr float ms_oy(int s) { return s == 0 ? -0.375f : s == 1 ? -0.125f : s == 2 ? 0.125f : 0.375f; }
+
+__global__ __launch_bounds__(256) void raster_shade_ms_kernel(Mesh m, Frames f, Cam cam, Shading sh, int vertex_colors, int tiles_x,
+                                                              unsigned char* __restrict__ out, int* __restrict__ sample_ids) {
+    __shared__ float4 lrec[256 * 3];
+    __shared__ int wave_cnt[4];
+    const int fr = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tx0 = (blockIdx.x % tiles_x) * TILE, ty0 = (blockIdx.x / tiles_x) * TILE;
+    const int row = ty0 + (tid >> 3), col0 = tx0 + (tid & 7) * 4;   // four pixels of one row
+    const float py = ((float)row + 0.5f) - cam.hh;
+    float px[4], best_d[4][4];
+    int best[4][4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        px[p] = ((float)(col0 + p) + 0.5f) - cam.hw;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            best_d[p][s] = INFINITY;
+            best[p][s] = -1;
+        }
+    }
+    const float* rec_fr = f.tri_rec + (size_t)fr * m.nf * TRI_REC;
+    const int* box_fr = f.tri_box + (size_t)fr * m.nf * 2;
+    for (int base = 0; base < m.nf; base += 256) {
+        const int t = base + tid;
+        bool hit = false;
+        int bx = 1, by = 1;
+        if (t < m.nf) {
+            bx = box_fr[t * 2];
+            by = box_fr[t * 2 + 1];
+            const int xmin = bx & 0xffff, xmax = bx >> 16, ymin = by & 0xffff, ymax = by >> 16;
+            hit = xmin <= xmax && xmin <= tx0 + TILE - 1 && xmax >= tx0 && ymin <= ty0 + TILE - 1 && ymax >= ty0;
+        }
+        const unsigned long long mask = __ballot(hit);
+        if (lane == 0) wave_cnt[wv] = __popcll(mask);
+        __syncthreads();
+        int off = 0, total = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = wave_cnt[i];
+            off += i < wv ? c : 0;
+            total += c;
+        }
+        if (hit) {   // ascending triangle index: waves in order, lanes in order within a wave
+            const int pos = off + __popcll(mask & ((1ull << lane) - 1ull));
+            const float4* src = reinterpret_cast<const float4*>(rec_fr + (size_t)t * TRI_REC);
+            float4 c = src[2];
+            c.z = __int_as_float(bx);
+            c.w = __int_as_float(by);
+            lrec[pos * 3 + 0] = src[0];
+            lrec[pos * 3 + 1] = src[1];
+            lrec[pos * 3 + 2] = c;
+        }
+        __syncthreads();
+        for (int j = 0; j < total; ++j) {
+            const float4 rc = lrec[j * 3 + 2];
+            const int bxj = __float_as_int(rc.z), byj = __float_as_int(rc.w);
+            if (row < (byj & 0xffff) || row > (byj >> 16) || col0 + 3 < (bxj & 0xffff) || col0 > (bxj >> 16)) continue;
+            const float4 ra = lrec[j * 3], rb = lrec[j * 3 + 1];
+            const Edges ed(ra, rb);
+            const int id = __float_as_int(rc.y);
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    float E0, E1, E2;
+                    if (ed.eval(px[p] + ms_ox(s), py + ms_oy(s), E0, E1, E2)) {
+                        const float d = ((E0 + E1) + E2) / fmaf(E2, rc.x, fmaf(E1, rb.w, E0 * rb.z));
+                        if (d >= cam.znear && d <= cam.zfar && d < best_d[p][s]) {   // strict: a tie stays with the lower face index
+                            best_d[p][s] = d;
+                            best[p][s] = id;
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();   // the list and the counts are rewritten by the next chunk
+    }
+    if (row >= cam.H) return;
+    // One shade per distinct face of a pixel.  The loop is not unrolled, so shade_fragment has one call site; `it` picks its sample through
+    // selects and hands the colour to every sample of the same pixel that shows the same face.
+    unsigned packed[4][4];   // B | G << 8 | R << 16 of each sample, 0 where nothing covers it
+    unsigned done = 0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) packed[p][s] = 0u;
+#pragma unroll 1
+    for (int it = 0; it < 16; ++it) {
+        int id = -1;
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) id = it == p * 4 + s ? best[p][s] : id;
+        const int pi = it >> 2;
+        if (id < 0 || ((done >> it) & 1u) || col0 + pi >= cam.W) continue;   // a pixel beyond the image's last column is never stored
+        const float pxc = ((float)(col0 + pi) + 0.5f) - cam.hw;
+        const size_t r = (size_t)fr * m.nf + id;
+        const V3 c = shade_fragment(f.tri_rec + r * TRI_REC, f.tri_attr + r * TRI_ATTR, pxc, py, cam, sh, vertex_colors);
+        const unsigned v = to_u8(c.z) | (to_u8(c.y) << 8) | (to_u8(c.x) << 16);
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                if (p == pi && best[p][s] == id) {
+                    packed[p][s] = v;
+                    done |= 1u << (p * 4 + s);
+                }
+    }
+    unsigned bytes[12];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            unsigned sum = 2u;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) sum += (packed[p][s] >> (8 * q)) & 0xffu;
+            bytes[p * 3 + q] = sum >> 2;
+        }
+    const size_t pix = ((size_t)fr * cam.H + row) * cam.W + col0;
+    if ((cam.W & 3) == 0 && col0 + 3 < cam.W) {   // 12 bytes at a multiple of 12 from a row start that is a multiple of 4
+        unsigned* o = reinterpret_cast<unsigned*>(out + pix * 3);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) o[q] = bytes[q * 4] | (bytes[q * 4 + 1] << 8) | (bytes[q * 4 + 2] << 16) | (bytes[q * 4 + 3] << 24);
+    } else {
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            if (col0 + p < cam.W)
+                for (int q = 0; q < 3; ++q) out[(pix + p) * 3 + q] = (unsigned char)bytes[p * 3 + q];
+    }
+    if (sample_ids) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            if (col0 + p < cam.W) reinterpret_cast<int4*>(sample_ids)[pix + p] = make_int4(best[p][0], best[p][1], best[p][2], best[p][3]);
+    }
+}
+
 Cam make_cam(const said_render_scene& sc) {
     Cam c;
     c.fx = sc.fx; c.fy = sc.fy;
@@ -366,6 +510,20 @@ Cam make_cam(const said_render_scene& sc) {
     for (int i = 0; i < 3; ++i) c.cam[i] = sc.cam_pos[i];
     c.W = sc.width; c.H = sc.height;
     return c;
+}
+
+Shading make_shading(const said_render_scene& sc, bool vertex_colors) {
+    Shading sh;
+    sh.n_lights = sc.n_lights;
+    for (int l = 0; l < SAID_RENDER_MAX_LIGHTS; ++l) {
+        for (int i = 0; i < 3; ++i) sh.light[l][i] = sc.light_pos[l][i];
+        sh.intensity[l] = sc.light_intensity[l];
+    }
+    sh.ambient = sc.ambient;
+    for (int i = 0; i < 3; ++i) sh.base[i] = sc.base_color[i];
+    sh.metallic = vertex_colors ? sc.vc_metallic : sc.metallic;
+    sh.roughness = vertex_colors ? sc.vc_roughness : sc.roughness;
+    return sh;
 }
 
 }  // namespace
@@ -388,18 +546,14 @@ void launch_tri_setup(const Mesh& m, const Frames& f, const said_render_scene& s
 
 void launch_raster_shade(const Mesh& m, const Frames& f, const said_render_scene& sc, bool vertex_colors, unsigned char* out, int* face_ids,
                          hipStream_t s) {
-    Shading sh;
-    sh.n_lights = sc.n_lights;
-    for (int l = 0; l < SAID_RENDER_MAX_LIGHTS; ++l) {
-        for (int i = 0; i < 3; ++i) sh.light[l][i] = sc.light_pos[l][i];
-        sh.intensity[l] = sc.light_intensity[l];
-    }
-    sh.ambient = sc.ambient;
-    for (int i = 0; i < 3; ++i) sh.base[i] = sc.base_color[i];
-    sh.metallic = vertex_colors ? sc.vc_metallic : sc.metallic;
-    sh.roughness = vertex_colors ? sc.vc_roughness : sc.roughness;
     const int tiles_x = (sc.width + TILE - 1) / TILE, tiles_y = (sc.height + TILE - 1) / TILE;
-    raster_shade_kernel<<<dim3(tiles_x * tiles_y, f.n), 256, 0, s>>>(m, f, make_cam(sc), sh, vertex_colors ? 1 : 0, tiles_x, out, face_ids);
+    raster_shade_kernel<<<dim3(tiles_x * tiles_y, f.n), 256, 0, s>>>(m, f, make_cam(sc), make_shading(sc, vertex_colors), vertex_colors ? 1 : 0, tiles_x, out, face_ids);
+}
+
+void launch_raster_shade_ms(const Mesh& m, const Frames& f, const said_render_scene& sc, bool vertex_colors, unsigned char* out, int* sample_ids,
+                            hipStream_t s) {
+    const int tiles_x = (sc.width + TILE - 1) / TILE, tiles_y = (sc.height + TILE - 1) / TILE;
+    raster_shade_ms_kernel<<<dim3(tiles_x * tiles_y, f.n), 256, 0, s>>>(m, f, make_cam(sc), make_shading(sc, vertex_colors), vertex_colors ? 1 : 0, tiles_x, out, sample_ids);
 }
 
 }  // namespace render

@@ -43,6 +43,9 @@ void launch_vertex_normals(const Mesh& m, const Frames& f, hipStream_t s);
 void launch_tri_setup(const Mesh& m, const Frames& f, const said_render_scene& sc, const Xform& x, bool vertex_colors, hipStream_t s);
 void launch_raster_shade(const Mesh& m, const Frames& f, const said_render_scene& sc, bool vertex_colors, unsigned char* out, int* face_ids,
                          hipStream_t s);
+// 4 samples per pixel; sample_ids (n, height, width, 4), 16-byte aligned, nullable
+void launch_raster_shade_ms(const Mesh& m, const Frames& f, const said_render_scene& sc, bool vertex_colors, unsigned char* out, int* sample_ids,
+                            hipStream_t s);
 
 }  // namespace render
 }  // namespace said

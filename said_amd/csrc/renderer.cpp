@@ -1,8 +1,10 @@
 // renderer.cpp — host side of the renderer (C ABI: include/said_render.h; kernels: render.hip): the context, the mesh
-// upload with its incidence list, the scene, and the five launches of a chunk.  (Not render.cpp: a .cpp and a .hip of one stem would share the
-// names of their -save-temps files, which the build's ISA scan reads — section 14.)
+// upload with its incidence list, the scene, and the five launches of a chunk, the last of them at one sample per pixel or, through
+// include/said_render_ms.h, at four (section 15.2).  (Not render.cpp: a .cpp and a .hip of one stem would share the names of their
+// -save-temps files, which the build's ISA scan reads — section 14.)
 #include "engine_internal.h"
 #include "render_kernels.h"
+#include "../../include/said_render_ms.h"
 
 using namespace said::render;
 
@@ -51,6 +53,54 @@ int read_stage(said_render* r, const char* entry, const float* src, int n_frames
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipMemcpyAsync(out_host, src, sizeof(float) * 3 * r->nv * n_frames, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+// Both render entries: `samples` is 1 (said_render_render's path, whatever entry asked for it) or 4 (section 15.2).
+int render_chunk(said_render* r, const char* entry, int samples, const float* coeffs_dev, const float* target_dev, long long t0, int n_frames, float max_diff,
+                 const double* rot_host, const double* t_center_host, unsigned char* out_u8_dev, int* face_ids_dev, int* sample_ids_dev, void* stream) {
+    HostCtx* ctx = &r->c;
+    if (r->nf == 0) return fail(ctx, "%s: no mesh set (said_render_set_mesh)", entry);
+    if (!r->has_scene) return fail(ctx, "%s: no scene set (said_render_set_scene)", entry);
+    if (!coeffs_dev || !out_u8_dev) return fail(ctx, "%s: null coefficients or output", entry);
+    if (t0 < 0 || n_frames < 1 || n_frames > MAX_CHUNK) return fail(ctx, "%s: t0 %lld, n_frames %d (t0 >= 0, 1 .. %d frames per call)", entry, t0, n_frames, MAX_CHUNK);
+    if (target_dev && !r->has_lut) return fail(ctx, "%s: a target sequence needs a colour map (said_render_set_colormap)", entry);
+    if (target_dev && !(max_diff > 0.f && std::isfinite(max_diff))) return fail(ctx, "%s: max_diff must be positive and finite", entry);
+    Xform xf;
+    rodrigues(rot_host, xf.R);
+    for (int i = 0; i < 3; ++i) {
+        const double c = t_center_host ? t_center_host[i] : 0.0;
+        if (!std::isfinite(c) || !std::isfinite((double)xf.R[i * 3])) return fail(ctx, "%s: non-finite rotation or centre", entry);
+        xf.c[i] = (float)c;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (n_frames > r->cap) {
+        HIPCHK(hipStreamSynchronize(s));
+        r->cap = r->last_n = 0;
+        const size_t n = (size_t)n_frames, nv3 = n * r->nv * 3, nf = n * r->nf;
+        if (drealloc(ctx, &r->verts, nv3, false) || drealloc(ctx, &r->face_na, nf * 6, false) || drealloc(ctx, &r->normals, nv3, false) || drealloc(ctx, &r->colors, nv3, false) ||
+            drealloc(ctx, &r->tri_rec, nf * TRI_REC, false) || drealloc(ctx, &r->tri_box, nf * 2, false) || drealloc(ctx, &r->tri_attr, nf * TRI_ATTR, false))
+            return -1;
+        r->cap = n_frames;
+    }
+    const Mesh m = mesh_of(r);
+    const Frames f = frames_of(r, n_frames);
+    const bool vc = target_dev != nullptr;
+    launch_blend_vertices(m, f, coeffs_dev + t0 * r->k, vc ? target_dev + t0 * r->k : nullptr, max_diff, r->lut, s);
+    HIPCHK(hipGetLastError());
+    launch_face_normals(m, f, coeffs_dev + t0 * r->k, s);
+    HIPCHK(hipGetLastError());
+    launch_vertex_normals(m, f, s);
+    HIPCHK(hipGetLastError());
+    launch_tri_setup(m, f, r->scene, xf, vc, s);
+    HIPCHK(hipGetLastError());
+    if (samples == 4)
+        launch_raster_shade_ms(m, f, r->scene, vc, out_u8_dev, sample_ids_dev, s);
+    else
+        launch_raster_shade(m, f, r->scene, vc, out_u8_dev, face_ids_dev, s);
+    HIPCHK(hipGetLastError());
+    r->last_n = n_frames;
     return 0;
 }
 
@@ -169,46 +219,20 @@ int said_render_set_colormap(said_render* r, const float* lut_host, void* stream
 int said_render_render(said_render* r, const float* coeffs_dev, const float* target_dev, long long t0, int n_frames, float max_diff,
                        const double* rot_host, const double* t_center_host, unsigned char* out_u8_dev, int* face_ids_dev, void* stream) {
     if (!r) return -1;
+    return render_chunk(r, "said_render_render", 1, coeffs_dev, target_dev, t0, n_frames, max_diff, rot_host, t_center_host, out_u8_dev, face_ids_dev, nullptr, stream);
+}
+
+int said_render_render_ms(said_render* r, int samples, const float* coeffs_dev, const float* target_dev, long long t0, int n_frames, float max_diff,
+                          const double* rot_host, const double* t_center_host, unsigned char* out_u8_dev, int* face_ids_dev, int* sample_ids_dev,
+                          void* stream) {
+    if (!r) return -1;
     HostCtx* ctx = &r->c;
-    if (r->nf == 0) return fail(ctx, "said_render_render: no mesh set (said_render_set_mesh)");
-    if (!r->has_scene) return fail(ctx, "said_render_render: no scene set (said_render_set_scene)");
-    if (!coeffs_dev || !out_u8_dev) return fail(ctx, "said_render_render: null coefficients or output");
-    if (t0 < 0 || n_frames < 1 || n_frames > MAX_CHUNK) return fail(ctx, "said_render_render: t0 %lld, n_frames %d (t0 >= 0, 1 .. %d frames per call)", t0, n_frames, MAX_CHUNK);
-    if (target_dev && !r->has_lut) return fail(ctx, "said_render_render: a target sequence needs a colour map (said_render_set_colormap)");
-    if (target_dev && !(max_diff > 0.f && std::isfinite(max_diff))) return fail(ctx, "said_render_render: max_diff must be positive and finite");
-    Xform xf;
-    rodrigues(rot_host, xf.R);
-    for (int i = 0; i < 3; ++i) {
-        const double c = t_center_host ? t_center_host[i] : 0.0;
-        if (!std::isfinite(c) || !std::isfinite((double)xf.R[i * 3])) return fail(ctx, "said_render_render: non-finite rotation or centre");
-        xf.c[i] = (float)c;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(ctx->device));
-    if (n_frames > r->cap) {
-        HIPCHK(hipStreamSynchronize(s));
-        r->cap = r->last_n = 0;
-        const size_t n = (size_t)n_frames, nv3 = n * r->nv * 3, nf = n * r->nf;
-        if (drealloc(ctx, &r->verts, nv3, false) || drealloc(ctx, &r->face_na, nf * 6, false) || drealloc(ctx, &r->normals, nv3, false) || drealloc(ctx, &r->colors, nv3, false) ||
-            drealloc(ctx, &r->tri_rec, nf * TRI_REC, false) || drealloc(ctx, &r->tri_box, nf * 2, false) || drealloc(ctx, &r->tri_attr, nf * TRI_ATTR, false))
-            return -1;
-        r->cap = n_frames;
-    }
-    const Mesh m = mesh_of(r);
-    const Frames f = frames_of(r, n_frames);
-    const bool vc = target_dev != nullptr;
-    launch_blend_vertices(m, f, coeffs_dev + t0 * r->k, vc ? target_dev + t0 * r->k : nullptr, max_diff, r->lut, s);
-    HIPCHK(hipGetLastError());
-    launch_face_normals(m, f, coeffs_dev + t0 * r->k, s);
-    HIPCHK(hipGetLastError());
-    launch_vertex_normals(m, f, s);
-    HIPCHK(hipGetLastError());
-    launch_tri_setup(m, f, r->scene, xf, vc, s);
-    HIPCHK(hipGetLastError());
-    launch_raster_shade(m, f, r->scene, vc, out_u8_dev, face_ids_dev, s);
-    HIPCHK(hipGetLastError());
-    r->last_n = n_frames;
-    return 0;
+    const char* entry = "said_render_render_ms";
+    if (samples != 1 && samples != 4) return fail(ctx, "%s: %d samples per pixel (1 or 4)", entry, samples);
+    if (samples == 1 && sample_ids_dev) return fail(ctx, "%s: sample_ids_dev must be NULL at 1 sample (face_ids_dev receives the faces)", entry);
+    if (samples == 4 && face_ids_dev) return fail(ctx, "%s: face_ids_dev must be NULL at 4 samples (sample_ids_dev receives the faces)", entry);
+    if (((uintptr_t)sample_ids_dev & 15) != 0) return fail(ctx, "%s: sample_ids_dev must be 16-byte aligned", entry);
+    return render_chunk(r, entry, samples, coeffs_dev, target_dev, t0, n_frames, max_diff, rot_host, t_center_host, out_u8_dev, face_ids_dev, sample_ids_dev, stream);
 }
 
 int said_render_read_vertices(said_render* r, int n_frames, float* out_host, void* stream) {

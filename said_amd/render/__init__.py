@@ -3,7 +3,8 @@
 ``RendererObject`` holds the reference's scene (its camera, four point lights, ambient term and material) and a ``RenderEngine``;
 ``render_blendshape_coefficients`` returns the list of (800, 800, 3) uint8 B-G-R images the reference returns, and
 ``iter_rendered_frames`` yields the same images chunk by chunk, so a long clip never holds all its frames on the device.
-There is no CPU path."""
+``RendererObject(samples=4)`` draws with four samples per pixel and a box resolve, as pyrender's offscreen target
+does; the default is one sample.  There is no CPU path."""
 from __future__ import annotations
 
 from typing import Iterator, List, Optional
@@ -59,8 +60,11 @@ class RendererObject:
     """The reference's scene.  The camera stands at (0, 0, 1) whatever z_offset is: the reference computes a camera pose from z_offset and then
     adds the camera with a literal pose, so z_offset moves the four lights only.  That quirk is kept."""
 
-    def __init__(self, z_offset: float = 0.0, device="cuda:0") -> None:
+    def __init__(self, z_offset: float = 0.0, device="cuda:0", samples: int = 1) -> None:
+        if samples not in (1, 4):
+            raise ValueError(f"samples must be 1 or 4, got {samples}")
         self.z_offset = float(z_offset)
+        self.samples = int(samples)   # per pixel, used by the frame iterators below
         self.frustum = {"near": ZNEAR, "far": ZFAR, "height": HEIGHT, "width": WIDTH}
         self.engine = RenderEngine(torch.device(device))
         self.device = self.engine.device
@@ -132,7 +136,8 @@ def _prepare_sequence(renderer: RendererObject, neutral_mesh, blendshapes_matrix
 def iter_rendered_frames(renderer: RendererObject, neutral_mesh, blendshapes_matrix: np.ndarray, blendshape_coeffs, target_blendshape_coeffs=None,
                          color_map: str = "viridis", max_diff: float = 0.001, chunk: int = DEFAULT_CHUNK, rot=None, t_center=None,
                          face_ids: bool = False) -> Iterator[np.ndarray]:
-    """Yields (n, 800, 800, 3) uint8 B-G-R arrays, n <= chunk frames at a time, in order (with face_ids: pairs (frames, (n, 800, 800) int32)).
+    """Yields (n, 800, 800, 3) uint8 B-G-R arrays, n <= chunk frames at a time, in order (with face_ids: pairs (frames, (n, 800, 800) int32);
+    a renderer of 4 samples gives the face of every sample instead, (n, 800, 800, 4) int32).
     The arrays are views of one pinned host buffer that the next chunk overwrites: copy what must outlive the iteration step.
     `t_center` defaults to the mean of the neutral vertices, as in the reference; `rot` (axis-angle) to no rotation."""
     if chunk < 1:
@@ -147,10 +152,12 @@ def iter_rendered_frames(renderer: RendererObject, neutral_mesh, blendshapes_mat
     with torch.cuda.device(eng.index):
         dev = torch.empty((n_max, h, w, 3), dtype=torch.uint8, device=eng.device)
         host = torch.empty((n_max, h, w, 3), dtype=torch.uint8, pin_memory=True)
-        ids_dev = torch.empty((n_max, h, w), dtype=torch.int32, device=eng.device) if face_ids else None
+        ms = renderer.samples != 1
+        ids_dev = torch.empty((n_max, h, w, 4) if ms else (n_max, h, w), dtype=torch.int32, device=eng.device) if face_ids else None
         for t0 in range(0, T, chunk):
             n = min(chunk, T - t0)
-            eng.render(coeffs, t0, n, dev, target=target, max_diff=max_diff, rot=rot, t_center=center, face_ids=ids_dev)
+            eng.render(coeffs, t0, n, dev, target=target, max_diff=max_diff, rot=rot, t_center=center, face_ids=None if ms else ids_dev,
+                       samples=renderer.samples, sample_ids=ids_dev if ms else None)
             host[:n].copy_(dev[:n], non_blocking=True)
             ids = ids_dev[:n].cpu() if face_ids else None
             torch.cuda.current_stream().synchronize()
@@ -244,7 +251,7 @@ def iter_encoded_frames(renderer: RendererObject, neutral_mesh, blendshapes_matr
         host = torch.empty((n_max, h, w, 3), dtype=torch.uint8, pin_memory=True) if raw else None
         for t0 in range(0, T, chunk):
             n = min(chunk, T - t0)
-            eng.render(coeffs, t0, n, dev, target=target, max_diff=max_diff, rot=rot, t_center=center)
+            eng.render(coeffs, t0, n, dev, target=target, max_diff=max_diff, rot=rot, t_center=center, samples=renderer.samples)
             if raw:
                 host[:n].copy_(dev[:n], non_blocking=True)
             files = enc.encode(dev[:n], bgr=True)   # synchronises the stream

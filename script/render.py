@@ -3,13 +3,14 @@
 Command-line compatible with the reference's script/render.py:23-96 (same twelve flags, types and defaults; `bool` flags keep argparse's
 type=bool behaviour: any non-empty string turns them on), with these differences:
 - --blendshape_list_path defaults to the 32 built-in names of said_amd/util/blendshape.py (the reference's default file lists the same names);
-- the frames come from said_amd.render (HIP rasteriser, one sample per pixel) instead of pyrender / OpenGL: DESIGN.md section 15;
+- the frames come from said_amd.render (HIP rasteriser) instead of pyrender / OpenGL: DESIGN.md section 15.  One sample per pixel by default;
+  --samples 4 draws with four samples per pixel and a box resolve, as pyrender's multisampled offscreen target does (section 15.2);
 - an --output_path ending in .avi is written by the built-in Motion-JPEG writer with the clip's sound as 16-bit PCM; any other extension goes
   through moviepy when it imports, and otherwise the .avi is written beside the requested path with a note on stderr;
 - PNG frames (--save_images) are written with PIL, and --output_images_dir is created when missing;
 - the reference passes R-G-B-reversed frames to moviepy (its renderer returns B-G-R for cv2.imwrite); with a grey material that is invisible,
   in difference mode it swaps red and blue in the video.  Here video and PNGs both show the colour map's own colours;
-- new optional flags: --device, --chunk (frames per launch), --jpeg {pil,gpu}: who encodes the .avi's frames, PIL on the host (default) or
+- new optional flags: --device, --chunk (frames per launch), --samples {1,4}, --jpeg {pil,gpu}: who encodes the .avi's frames, PIL on the host (default) or
   the HIP encoder on the device, after which only the compressed frames are copied to the host.
 """
 import argparse
@@ -41,6 +42,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--output_images_dir", type=str, default="../out_imgs", help="Saving directory of the output image for each frame")
     p.add_argument("--device", type=str, default="cuda:0", help="MI355X to run on")
     p.add_argument("--chunk", type=int, default=64, help="Frames rendered per launch")
+    p.add_argument("--samples", type=int, choices=[1, 4], default=1, help="Samples per pixel: 1, or 4 with a box resolve (smooth silhouettes)")
     p.add_argument("--jpeg", choices=["pil", "gpu"], default="pil", help="JPEG encoder of the video's frames: PIL on the host, or the HIP encoder on the device")
     return p
 
@@ -58,7 +60,7 @@ def main(argv=None) -> None:
     neutral, basis = load_blendshape_basis(args.neutral_path, args.blendshapes_dir, names)
     coeffs = load_blendshape_coeffs(args.blendshape_coeffs_path).numpy()
     target = load_blendshape_coeffs(args.target_diff_blendshape_coeffs_path).numpy() if args.show_difference else None
-    renderer = RendererObject(device=args.device)
+    renderer = RendererObject(device=args.device, samples=args.samples)
     if args.jpeg == "gpu":   # the PNGs of --save_images need the pixels as well
         frames = iter_encoded_frames(renderer, neutral, basis, coeffs, target, max_diff=args.max_diff, chunk=args.chunk, raw=bool(args.save_images))
     else:

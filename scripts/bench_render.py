@@ -7,7 +7,7 @@ Two figures per mesh, each the median of `--repeats` renders of `--frames` frame
 Prints one JSON line.  The coefficient sequence is a seeded smooth random walk in [0, 1]; vertices and bases come from golden G13, faces from
 golden G15.
 
-Usage:  python scripts/bench_render.py [--frames 600] [--repeats 5] [--chunk 64] [--difference]
+Usage:  python scripts/bench_render.py [--frames 600] [--repeats 5] [--chunk 64] [--difference] [--samples {1,4}]
 """
 import argparse
 import json
@@ -67,16 +67,17 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--chunk", type=int, default=64)
     ap.add_argument("--difference", action="store_true", help="render the difference heat map against a second sequence")
+    ap.add_argument("--samples", type=int, choices=[1, 4], default=1, help="samples per pixel (DESIGN.md section 15.2)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_render.py needs the MI355X"
     w = sequence(args.frames)
     wt = sequence(args.frames, seed=1) if args.difference else None
-    result = {"frames": args.frames, "chunk": args.chunk, "difference": bool(args.difference), "meshes": {}}
+    result = {"frames": args.frames, "chunk": args.chunk, "difference": bool(args.difference), "samples": args.samples, "meshes": {}}
     base = arkit()
     for name, (neutral, shapes, faces) in (("arkit", base), ("arkit_split4", split_in_four(*base))):
         mesh, basis = Mesh(neutral, faces), shapes.reshape(32, -1).T.copy()
-        r = RendererObject(device=args.device)
+        r = RendererObject(device=args.device, samples=args.samples)
         eng = r.engine
         r.set_mesh(neutral, faces, basis)
         if wt is not None:
@@ -88,7 +89,7 @@ def main():
 
         def device_pass():
             for t0 in range(0, args.frames, args.chunk):
-                eng.render(cw, t0, min(args.chunk, args.frames - t0), out, target=ct, t_center=center)
+                eng.render(cw, t0, min(args.chunk, args.frames - t0), out, target=ct, t_center=center, samples=args.samples)
 
         def host_pass():
             n = 0
