@@ -65,7 +65,8 @@ int said_set_timestep_freqs(said_ctx* ctx, const float* freqs_host, int n);
 /* ---- audio path (once per clip) ----------------------------------------- */
 /* Replaces SAID.get_audio_embedding (diffusion.py:209-230) → ModifiedWav2Vec2Model.forward (said/model/wav2vec2.py:13-82): conv feature extractor, linear
  * interpolation to `num_frames` (<=0: none), projection, positional conv, transformer encoder; with apply_proj != 0 also the audio_proj_layer Linear(768,
- * feature_dim) of diffusion.py:228-229. waveform_dev (B, Ta) → out_dev (B, F, D), D = 768 or feature_dim.  *out_frames receives F. */
+ * feature_dim) of diffusion.py:228-229. waveform_dev (B, Ta) → out_dev (B, F, D), D = 768 or feature_dim.  *out_frames receives F.
+ * The same forward in Wav2Vec2's train mode (SpecAugment, dropouts, LayerDrop) is declared in said_audio_train.h. */
 int said_audio_encode(said_ctx* ctx, const float* waveform_dev, int batch, int num_samples, int num_frames,
                       int apply_proj, float* out_dev, int* out_frames, void* stream);
 

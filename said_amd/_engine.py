@@ -219,8 +219,21 @@ BEAT_EXPORTS = {
     "said_beat_read_rates": (c_int, [c_void_p, _c_double_p, c_void_p]),
     "said_beat_read_minima": (c_int, [c_void_p, _c_int_p, _c_int_p, c_void_p]),
 }
+
+
+class AudioTrainParams(ctypes.Structure):
+    """Mirror of said_audio_train_params (include/said_audio_train.h)."""
+    _fields_ = [("p_feat_proj", c_float), ("p_hidden", c_float), ("p_attention", c_float), ("p_activation", c_float),
+                ("seed", ctypes.c_uint64), ("time_mask_dev", c_void_p), ("skip_layers", ctypes.c_uint32)]
+
+
+# include/said_audio_train.h: the audio encoder's train mode, an entry point of the said_ctx context added without an ABI version bump; a group
+# like the renderer's, in a table of its own (tests/test_audio_train_cpu.py checks it against its header)
+AUDIO_TRAIN_EXPORTS = {
+    "said_audio_encode_train": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(AudioTrainParams), c_void_p, POINTER(c_int), c_void_p]),
+}
 _GROUPS = {**LAZY_EXPORTS, "render": ("the renderer", RENDER_EXPORTS), "render_ms": ("multisampled rendering", RENDER_MS_EXPORTS),
-           "jpeg": ("the JPEG encoder", JPEG_EXPORTS),
+           "jpeg": ("the JPEG encoder", JPEG_EXPORTS), "audio_train": ("the audio encoder's train mode", AUDIO_TRAIN_EXPORTS),
            "unet_train": ("the UNet trainer", UNET_TRAIN_EXPORTS), "beat": ("the beat-consistency passes", BEAT_EXPORTS)}
 _bound = set()   # the groups bound so far
 
@@ -381,7 +394,7 @@ class Engine(_Context):
         self.has_audio = any(k.startswith("audio_encoder.") for k in state_dict)
 
     # ---- compute ----
-    def audio_encode(self, waveform: torch.Tensor, num_frames: Optional[int], apply_proj: bool = False) -> torch.Tensor:
+    def audio_encode(self, waveform: torch.Tensor, num_frames: Optional[int], apply_proj: bool = False, _train=None) -> torch.Tensor:
         waveform = _check_dev(waveform, "waveform")
         B, Ta = waveform.shape
         out_dim = self.ctx_dim if apply_proj else 768
@@ -396,8 +409,39 @@ class Engine(_Context):
                     L = (L - k) // s + 1
                 out = torch.empty(B, max(L, 1), out_dim, device=waveform.device, dtype=torch.float32)
             got = c_int(0)
-            self._call("said_audio_encode", _ptr(waveform), B, Ta, nf, int(apply_proj), _ptr(out), ctypes.byref(got), _stream())
+            if _train is None:
+                self._call("said_audio_encode", _ptr(waveform), B, Ta, nf, int(apply_proj), _ptr(out), ctypes.byref(got), _stream())
+            else:
+                self._call("said_audio_encode_train", _ptr(waveform), B, Ta, nf, int(apply_proj), ctypes.byref(_train), _ptr(out), ctypes.byref(got), _stream())
             assert got.value == out.shape[1], (got.value, out.shape)
+        return out
+
+    def audio_encode_train(self, waveform: torch.Tensor, num_frames: Optional[int], draws, cfg, apply_proj: bool = False) -> torch.Tensor:
+        """audio_encode in Wav2Vec2's train mode (include/said_audio_train.h): `draws` is an AudioTrainDraws (time mask, skipped layers,
+        dropout seed), `cfg` an AudioTrainConfig (the dropout probabilities) — said_amd.model.wav2vec2."""
+        load_library("audio_train")
+        cfg.check()
+        B, frames = waveform.shape[0], int(num_frames or 0)
+        if frames <= 0:   # no interpolation: the feature extractor's own frame count
+            frames = waveform.shape[1]
+            for k, s in zip((10, 3, 3, 3, 3, 2, 2), (5, 2, 2, 2, 2, 2, 2)):
+                frames = (frames - k) // s + 1
+        mask = None
+        if draws.mask is not None:
+            m = np.ascontiguousarray(np.asarray(draws.mask) != 0, dtype=np.uint8)
+            if m.shape != (B, frames):
+                raise EngineError(f"time mask of shape {m.shape} does not match {B} clips of {frames} frames")
+            mask = torch.from_numpy(m).to(waveform.device)
+        skip = 0
+        for l, sk in enumerate(draws.skip):
+            skip |= int(bool(sk)) << l
+        if skip >> 32:
+            raise EngineError("skip list longer than 32 layers")
+        p = AudioTrainParams(cfg.feat_proj_dropout, cfg.hidden_dropout, cfg.attention_dropout, cfg.activation_dropout,
+                             int(draws.seed) & 0xFFFFFFFFFFFFFFFF, _ptr(mask), skip)
+        out = self.audio_encode(waveform, num_frames, apply_proj, _train=p)
+        if mask is not None:
+            mask.record_stream(torch.cuda.current_stream(waveform.device))
         return out
 
     def unet_forward(self, sample: torch.Tensor, timesteps: torch.Tensor, context: torch.Tensor) -> torch.Tensor:

@@ -1,11 +1,16 @@
 // audio_enc.cpp — said_audio_encode: the Wav2Vec2 audio encoder (feature extractor, positional conv, transformer layers,
-// optional projection) on the gfx950 kernels.
+// optional projection) on the gfx950 kernels; said_audio_encode_train: its fp32 channel-major route in Wav2Vec2's train mode
+// (include/said_audio_train.h; kernels: audio_train.hip).
+#include "../../include/said_audio_train.h"
+#include "audio_train.h"
 #include "engine_internal.h"
 
-extern "C" {
+namespace {
 
-int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_frames, int apply_proj, float* out_dev,
-                      int* out_frames, void* stream) {
+// Both entry points.  tp == nullptr: said_audio_encode, launch for launch what it always issued.  tp != nullptr (validated by
+// said_audio_encode_train; fp32 route only): SpecAugment span replacement, the four dropouts and LayerDrop of the train-mode forward.
+int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_frames, int apply_proj, const said_audio_train_params* tp,
+                 float* out_dev, int* out_frames, void* stream) {
     if (check_ready(ctx)) return -1;
     if (!ctx->has_audio) return fail(ctx, "audio_encoder.* weights were not loaded");
     hipStream_t s = (hipStream_t)stream;
@@ -23,6 +28,9 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
     const int Fr = num_frames > 0 ? num_frames : L[6];
     if (out_frames) *out_frames = Fr;
     const int Fp = rup(Fr, 32);
+    // the dropout masks count logical elements in 32 bits; the largest site is the FFN activation (B, frames, 3072)
+    if (tp && (unsigned long long)B * Fr * W2V_FFN >= (1ull << 32))
+        return fail(ctx, "said_audio_encode_train: %d clips of %d frames need a dropout index of 2^32 or more", B, Fr);
     if (apply_proj && !ctx->has_audio_proj) return fail(ctx, "apply_proj requested but audio_proj_layer.* was not loaded");
     const int out_dim = apply_proj ? ctx->ctx_dim : W2V_H;
     // workspace: ping-pong conv buffers + token-domain buffers, for `chunk` clips at a time
@@ -46,7 +54,7 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
     }
     // bf16 mode (said_set_precision): token-major bf16 encoder on v_mfma_f32_32x32x16_bf16 (tgemm.hip).  conv0 + its
     // per-channel GroupNorm, the grouped positional convolution and the attention kernel are shared with the fp32 path.
-    const bool bfa = ctx->bf16_mode && (!apply_proj || ctx->ctx_dim % 128 == 0) && (int)ctx->blayers.size() == ctx->w2v_layers;
+    const bool bfa = !tp && ctx->bf16_mode && (!apply_proj || ctx->ctx_dim % 128 == 0) && (int)ctx->blayers.size() == ctx->w2v_layers;
     if (bfa) {
         const size_t e0 = (size_t)chunk * L[0] * W2V_CONV, e1 = (size_t)chunk * L[1] * W2V_CONV, tk = (size_t)chunk * Fr;
         const size_t xg = (size_t)chunk * 16 * (size_t)rup(Fr + ctx->posconv.taps, 8) * (W2V_H / 16) + 4096;   // per-group positional-conv operand
@@ -261,6 +269,14 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
             const LaunchCfg lc = pick_cfg(tt, W2V_H / 32);
             launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
         }
+        // train mode: every mask is indexed from the call's first clip (b0 + the launch's clip), so the result does not depend on `chunk`
+        const unsigned long long seed = tp ? tp->seed : 0;
+        // kind: the site's bit in said_debug_option "audio_train_sites" (all set unless a test isolates a site)
+        auto site = [&](int id, float p, int kind) { return drop_site(seed, id, (ctx->audio_train_sites & kind) ? p : 0.f); };
+        const DropSite none = drop_site(0, 0, 0.f);
+        if (tp)   // dropout on the projection, then the SpecAugment spans
+            launch_drop_cm(ctx->aH, nb, W2V_H, Fr, Fp, hs, b0, site(AT_SITE_FEAT_PROJ, tp->p_feat_proj, 1),
+                           tp->time_mask_dev ? tp->time_mask_dev + (long long)b0 * Fr : nullptr, ctx->mask_embed, s);
         {   // positional conv embedding: grouped Conv1d(k=128, pad=64, groups=16) + GELU; last frame dropped
             GemmArgs a = mkargs(Fr, W2V_H / 16);
             a.groups = 16; a.ntiles_per_group = 2;
@@ -271,9 +287,11 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
             a.y = ctx->aPOS; a.y_bstride = hs; a.y_pitch = Fp;
             launch_gemm(a, EPI_STORE, nb, tt * 32 <= 2048 ? 1 : 2, 8, s);
         }
-        launch_layernorm_cm(ctx->aH, ctx->aPOS, ctx->aH, ctx->enc_lng, ctx->enc_lnb, nb, W2V_H, Fr, Fp, hs, 1e-5f, s);
+        if (tp) launch_ln_drop_cm(ctx->aH, ctx->aPOS, ctx->aH, ctx->enc_lng, ctx->enc_lnb, nb, W2V_H, Fr, Fp, hs, 1e-5f, b0, none, site(AT_SITE_FRONT, tp->p_hidden, 2), s);
+        else launch_layernorm_cm(ctx->aH, ctx->aPOS, ctx->aH, ctx->enc_lng, ctx->enc_lnb, nb, W2V_H, Fr, Fp, hs, 1e-5f, s);
         const int vt_rows = Fp;
         for (int l = 0; l < ctx->w2v_layers; ++l) {
+            if (tp && (tp->skip_layers >> l & 1u)) continue;   // LayerDrop: the layer is the identity for the whole batch
             const W2VLayer& ly = ctx->layers[l];
             {
                 GemmArgs a = mkargs(Fr, 3 * W2V_H);
@@ -291,19 +309,25 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                 a.qk = ctx->aQK; a.v = ctx->aVT; a.o = ctx->aO;
                 a.v_bstride = hs; a.o_bstride = 2 * hs; a.b0 = 0;
                 a.pitch = Fp; a.T = Fr; a.heads = W2V_HEADS; a.rows = vt_rows; a.scale = 0.125f;
-                launch_attn(a, nb, W2V_HD, tt * W2V_HEADS <= 2048 ? 8 : (tt * W2V_HEADS <= 8192 ? 4 : 1), s, sp_on(ctx, ctx->attn_split) ? 2 : 0);
+                const int mode = sp_on(ctx, ctx->attn_split) ? 2 : 0;
+                const DropSite pd = site(at_site_layer(l, 0), tp ? tp->p_attention : 0.f, 4);
+                if (pd.p > 0.f)   // (training batches are small: the key split stays on, eight waves or four)
+                    launch_attn_drop(a, nb, tt * W2V_HEADS <= 2048 ? 8 : 4, s, mode, b0, pd);
+                else
+                    launch_attn(a, nb, W2V_HD, tt * W2V_HEADS <= 2048 ? 8 : (tt * W2V_HEADS <= 8192 ? 4 : 1), s, mode);
             }
             {
                 GemmArgs a = mkargs(Fr, W2V_H);
                 a.nseg = 1;
                 a.seg[0] = mkseg(ctx->aO, 2 * hs, Fp, W2V_H, 1, 0, 1, Fr, XF_NONE, ly.out.w[0]);
                 a.bias = ly.out.bias;
-                a.res_kind = RES_PLAIN; a.res = ctx->aH; a.res_bstride = hs; a.res_pitch = Fp;
+                if (!tp) { a.res_kind = RES_PLAIN; a.res = ctx->aH; a.res_bstride = hs; a.res_pitch = Fp; }   // train mode: the LayerNorm kernel adds the residual, behind the dropout
                 a.y = ctx->aT; a.y_bstride = hs; a.y_pitch = Fp;
                 const LaunchCfg lc = pick_cfg(tt, W2V_H / 32);
                 launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
             }
-            launch_layernorm_cm(ctx->aT, nullptr, ctx->aH, ly.ln1g, ly.ln1b, nb, W2V_H, Fr, Fp, hs, 1e-5f, s);
+            if (tp) launch_ln_drop_cm(ctx->aT, ctx->aH, ctx->aH, ly.ln1g, ly.ln1b, nb, W2V_H, Fr, Fp, hs, 1e-5f, b0, site(at_site_layer(l, 1), tp->p_hidden, 8), none, s);
+            else launch_layernorm_cm(ctx->aT, nullptr, ctx->aH, ly.ln1g, ly.ln1b, nb, W2V_H, Fr, Fp, hs, 1e-5f, s);
             {
                 GemmArgs a = mkargs(Fr, W2V_FFN);
                 a.nseg = 1;
@@ -313,17 +337,19 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
                 const LaunchCfg lc = pick_cfg(tt, W2V_FFN / 32);
                 launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
             }
+            if (tp) launch_drop_cm(ctx->aF, nb, W2V_FFN, Fr, Fp, (long long)W2V_FFN * Fp, b0, site(at_site_layer(l, 2), tp->p_activation, 16), nullptr, nullptr, s);
             {
                 GemmArgs a = mkargs(Fr, W2V_H);
                 a.nseg = 1;
                 a.seg[0] = mkseg(ctx->aF, (long long)W2V_FFN * Fp, Fp, W2V_FFN, 1, 0, 1, Fr, XF_NONE, ly.ff2.w[0]);
                 a.bias = ly.ff2.bias;
-                a.res_kind = RES_PLAIN; a.res = ctx->aH; a.res_bstride = hs; a.res_pitch = Fp;
+                if (!tp) { a.res_kind = RES_PLAIN; a.res = ctx->aH; a.res_bstride = hs; a.res_pitch = Fp; }   // train mode: the LayerNorm kernel adds the residual, behind the dropout
                 a.y = ctx->aT; a.y_bstride = hs; a.y_pitch = Fp;
                 const LaunchCfg lc = pick_cfg(tt, W2V_H / 32);
                 launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
             }
-            launch_layernorm_cm(ctx->aT, nullptr, ctx->aH, ly.ln2g, ly.ln2b, nb, W2V_H, Fr, Fp, hs, 1e-5f, s);
+            if (tp) launch_ln_drop_cm(ctx->aT, ctx->aH, ctx->aH, ly.ln2g, ly.ln2b, nb, W2V_H, Fr, Fp, hs, 1e-5f, b0, site(at_site_layer(l, 3), tp->p_hidden, 32), none, s);
+            else launch_layernorm_cm(ctx->aT, nullptr, ctx->aH, ly.ln2g, ly.ln2b, nb, W2V_H, Fr, Fp, hs, 1e-5f, s);
         }
         const float* fin = ctx->aH; long long fin_bs = hs;
         if (apply_proj) {  // diffusion.py:228-229
@@ -340,6 +366,29 @@ int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int nu
     LAUNCHCHK();
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int said_audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_frames, int apply_proj, float* out_dev,
+                      int* out_frames, void* stream) {
+    return audio_encode(ctx, wav_dev, B, Ta, num_frames, apply_proj, nullptr, out_dev, out_frames, stream);
+}
+
+int said_audio_encode_train(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_frames, int apply_proj,
+                            const said_audio_train_params* tp, float* out_dev, int* out_frames, void* stream) {
+    if (check_ready(ctx)) return -1;
+    if (!tp) return fail(ctx, "said_audio_encode_train: params is null");
+    if (ctx->bf16_mode)
+        return fail(ctx, "said_audio_encode_train: the context is in bf16 mode; the train-mode encoder runs on the fp32 route only (said_set_precision)");
+    for (const float p : {tp->p_feat_proj, tp->p_hidden, tp->p_attention, tp->p_activation})
+        if (!(p >= 0.f && p < 1.f)) return fail(ctx, "said_audio_encode_train: dropout probability %g is outside [0, 1)", (double)p);
+    if (tp->time_mask_dev && !ctx->mask_embed)
+        return fail(ctx, "said_audio_encode_train: a time mask needs audio_encoder.masked_spec_embed, which was not loaded");
+    if (ctx->w2v_layers > 32) return fail(ctx, "said_audio_encode_train: skip_layers holds 32 layers, the encoder has %d", ctx->w2v_layers);
+    return audio_encode(ctx, wav_dev, B, Ta, num_frames, apply_proj, tp, out_dev, out_frames, stream);
 }
 
 }  // extern "C"

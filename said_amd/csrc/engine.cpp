@@ -3,6 +3,7 @@
 #include <cstdarg>
 #include <mutex>
 
+#include "audio_train.h"
 #include "engine_internal.h"
 
 namespace said {
@@ -162,6 +163,7 @@ int said_create(said_ctx** out, int device, int max_batch_eff, int max_frames, i
     configure_ugemm_kernels();
     configure_stchain_kernel();
     configure_attn_kernels();
+    configure_audio_train_kernels();
     configure_out_sched_kernel();
     configure_tgemm_kernel();
     configure_xgemm_kernels();
@@ -673,6 +675,8 @@ int said_debug_option(said_ctx* ctx, const char* name, long long value) {
     } else if (k == "audio_chunk") {
         if (value < 1) return fail(ctx, "audio_chunk must be >= 1");
         ctx->audio_chunk = (int)value;
+    } else if (k == "audio_train_sites") {
+        ctx->audio_train_sites = value < 0 ? -1 : (int)(value & 63);
     } else if (k == "audio_stop_after") {
         ctx->audio_stop_after = value < 0 ? -1 : (int)std::min<long long>(value, 1 << 20);
     } else if (k == "steps_per_graph") {
@@ -704,6 +708,7 @@ long long said_debug_get(const said_ctx* ctx, const char* name) {
     if (k == "unet_tgemm_min_tokens") return ctx->bf16_mode ? ctx->unet_tgemm_min_tokens : ctx->unet_fgemm_min_tokens;
     if (k == "audio_chunk") return ctx->audio_chunk;
     if (k == "audio_stop_after") return ctx->audio_stop_after;
+    if (k == "audio_train_sites") return ctx->audio_train_sites;
     if (k == "n_tgemm_128") return ctx->n_tgemm[TG_128];
     if (k == "n_tgemm_128sb") return ctx->n_tgemm[TG_128SB];
     if (k == "n_tgemm_128x64") return ctx->n_tgemm[TG_128X64];

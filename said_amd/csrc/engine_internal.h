@@ -113,6 +113,7 @@ struct ModelWeights {
     float *c0_w = nullptr, *c0_g = nullptr, *c0_b = nullptr;
     PW aconv[7];
     float *fp_lng = nullptr, *fp_lnb = nullptr, *enc_lng = nullptr, *enc_lnb = nullptr;
+    float* mask_embed = nullptr;   // audio_encoder.masked_spec_embed [768], or null: optional, read by said_audio_encode_train's time mask only
     PW fproj, posconv, aproj;
     std::vector<W2VLayer> layers;
 
@@ -169,6 +170,8 @@ struct Switches {
     int spg_limit = 50;      // denoise steps captured per graph in loops of >= 400 steps, at most 10 below (steps_per_graph; round 6: 10 -> 50: at 0.245 ms per step the 100 graph boundaries of a 1000-step loop were 0.4-0.5 % of it — headline
                              // 2424-2429 -> 2435-2438 frames/s; 100 / 250 / 500 add nothing: profiles/r06l_steps_per_graph.txt)
     int audio_chunk = 32;    // clips per audio-encoder pass
+    int audio_train_sites = -1;  // said_audio_encode_train: which kinds of dropout site draw a mask — bits 1 feature projection, 2 encoder front, 4 probabilities, 8 attention output,
+                                 // 16 activation, 32 FFN output; -1: all (said_debug_option "audio_train_sites": tests isolate the three sites that share p_hidden)
     int audio_stop_after = -1;   // bf16 encoder: issue only the first n stages of each pass (said_debug_option "audio_stop_after"; < 0: all) — host side only
 };
 

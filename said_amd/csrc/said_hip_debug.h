@@ -16,6 +16,8 @@ extern "C" {
  *   "unet_tgemm_min_tokens"  tokens per launch from which the UNet takes the token-major GEMM path, both precisions
  *                            (< 0: restore the measured defaults 3000 bf16 / 10000 fp32)
  *   "audio_chunk"            clips per audio-encoder pass (default 32)
+ *   "audio_train_sites"      said_audio_encode_train: bit mask of the kinds of dropout site that draw a mask (1 feature projection, 2 encoder front, 4 attention probabilities,
+ *                            8 attention output, 16 activation, 32 FFN output); the others run with p = 0.  < 0 (default): all.  The three sites of p_hidden can be told apart this way.
  *   "audio_stop_after"       bf16 mode: n >= 0 makes said_audio_encode issue only the first n stages of each pass and return 0 (the output is then undefined; the buffers hold
  *                            the intermediates: said_debug_audio_copy); < 0 (default): everything.  Host side only.  A stage is one launch site of the bf16 branch, in order:
  *                              0 conv0 + GroupNorm + GELU, 1-6 the strided convolutions, 7 interpolation + LayerNorm, 8 feature projection, 9 tm_to_group_bf16,

@@ -384,7 +384,8 @@ int finalize_audio(said_ctx* ctx) {
         if (upvec(ctx, &ctx->fp_lnb, A + "feature_projection.layer_norm.bias", W2V_CONV)) return -1;
         if (make_pw(ctx, &ctx->fproj, A + "feature_projection.projection.weight", A + "feature_projection.projection.bias", W2V_H, W2V_CONV, 0)) return -1;
         if (upload_bf16(ctx, &ctx->bw_fproj, ctx->host_w[A + "feature_projection.projection.weight"].data.data(), W2V_H, W2V_CONV, 1)) return -1;
-        if (!getw(ctx, A + "masked_spec_embed", {W2V_H})) return -1;
+        const bool has_mse = ctx->host_w.count(A + "masked_spec_embed") != 0;   // optional: only a train-mode time mask reads it
+        if (has_mse && upvec(ctx, &ctx->mask_embed, A + "masked_spec_embed", W2V_H)) return -1;
         {   // positional conv: weight_norm(dim=2) folded on the host, then grouped packing (16 groups of 48)
             auto ig = ctx->host_w.find(A + "encoder.pos_conv_embed.conv.weight_g");
             if (ig == ctx->host_w.end() || ig->second.shape.size() != 3) return fail(ctx, "missing key in state dict: %sencoder.pos_conv_embed.conv.weight_g", A.c_str());
@@ -454,7 +455,7 @@ int finalize_audio(said_ctx* ctx) {
             if (upvec(ctx, &ly.ln1g, p + ".layer_norm.weight", W2V_H) || upvec(ctx, &ly.ln1b, p + ".layer_norm.bias", W2V_H)) return -1;
             if (upvec(ctx, &ly.ln2g, p + ".final_layer_norm.weight", W2V_H) || upvec(ctx, &ly.ln2b, p + ".final_layer_norm.bias", W2V_H)) return -1;
         }
-        const size_t expect = 1 + 7 + 2 + 4 + 3 + 2 + (size_t)L * 16;
+        const size_t expect = (has_mse ? 1 : 0) + 7 + 2 + 4 + 3 + 2 + (size_t)L * 16;
         if (n_audio != expect) return fail(ctx, "unexpected key(s) in state dict: %zu audio_encoder.* tensors, expected %zu", n_audio, expect);
         ctx->has_audio = true;
     }

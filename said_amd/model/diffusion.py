@@ -251,10 +251,16 @@ class SAID(ABC, nn.Module):
         """(audio_seq_len,) or list thereof → (B, T_a) processed mono waveform (CPU, as in the reference)."""
         return self.audio_processor(waveform, sampling_rate=self.sampling_rate, return_tensors="pt")["input_values"]
 
-    def get_audio_embedding(self, waveform: torch.FloatTensor, num_frames: Optional[int]) -> torch.FloatTensor:
-        """(B, T_a) → (B, num_frames, hidden or feature_dim)."""
+    def get_audio_embedding(self, waveform: torch.FloatTensor, num_frames: Optional[int], train_draws=None, train_cfg=None) -> torch.FloatTensor:
+        """(B, T_a) → (B, num_frames, hidden or feature_dim).  With `train_draws` (an AudioTrainDraws of said_amd.model.wav2vec2) the
+        encoder runs as the reference's does under train(): SpecAugment spans, dropouts and LayerDrop with the probabilities of
+        `train_cfg` (default AudioTrainConfig()).  nn.Module.training has no effect on either call."""
         e = self._get_engine(1, num_frames or 1)
-        return e.audio_encode(waveform, num_frames, apply_proj=self.feature_dim > 0)
+        if train_draws is None:
+            return e.audio_encode(waveform, num_frames, apply_proj=self.feature_dim > 0)
+        from .wav2vec2 import AudioTrainConfig
+        return e.audio_encode_train(waveform, num_frames, train_draws, train_cfg if train_cfg is not None else AudioTrainConfig(),
+                                    apply_proj=self.feature_dim > 0)
 
     def _encode_distinct(self, waveform: torch.FloatTensor, num_frames: int) -> torch.FloatTensor:
         """get_audio_embedding with byte-identical rows encoded once.  Candidates are found from two cheap per-row checksums (two passes over

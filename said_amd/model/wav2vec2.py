@@ -13,6 +13,7 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -36,6 +37,75 @@ class AudioConfig:
     feat_extract_norm: str = "group"
     conv_bias: bool = False
     do_stable_layer_norm: bool = False
+
+
+@dataclass
+class AudioTrainConfig:
+    """What ``Wav2Vec2Model.train()`` switches on, with the values of ``facebook/wav2vec2-base-960h``'s ``config.json`` as defaults.  That
+    file is not part of this repository: the nine values below are its published ones (SpecAugment time masking, the four dropouts,
+    LayerDrop; ``mask_feature_prob`` is 0 there, and a non-zero value is refused: feature-axis masking is not built)."""
+    mask_time_prob: float = 0.05
+    mask_time_length: int = 10
+    mask_time_min_masks: int = 2
+    mask_feature_prob: float = 0.0
+    feat_proj_dropout: float = 0.1
+    hidden_dropout: float = 0.1
+    attention_dropout: float = 0.1
+    activation_dropout: float = 0.1
+    layerdrop: float = 0.1
+
+    def check(self) -> None:
+        if self.mask_feature_prob > 0:
+            raise NotImplementedError(f"mask_feature_prob = {self.mask_feature_prob}: feature-axis masking is not supported by the HIP audio encoder")
+        for name in ("feat_proj_dropout", "hidden_dropout", "attention_dropout", "activation_dropout"):
+            p = getattr(self, name)
+            if not 0.0 <= p < 1.0:
+                raise ValueError(f"{name} = {p} is outside [0, 1)")
+
+
+@dataclass
+class AudioTrainDraws:
+    """The host's random draws of one train-mode encode: the SpecAugment time mask (B, frames) bool (None: no masking), the LayerDrop
+    decisions (one bool per layer, True = skipped) and the 64-bit key of the device's dropout masks."""
+    mask: Optional[np.ndarray]
+    skip: Tuple[bool, ...]
+    seed: int
+
+
+def compute_mask_indices(shape: Tuple[int, int], mask_prob: float, mask_length: int, min_masks: int = 0) -> np.ndarray:
+    """(batch, length) bool SpecAugment span mask: transformers' published ``_compute_mask_indices`` without an attention mask, drawing
+    from ``np.random`` in the same order (one ``rand(1)`` for the rounding epsilon, then one ``choice(..., replace=False)`` per row), so
+    that after the same ``np.random.seed`` it returns the same mask."""
+    batch, length = shape
+    if mask_length < 1:
+        raise ValueError("`mask_length` has to be bigger than 0.")
+    if mask_length > length:
+        raise ValueError(f"`mask_length` has to be smaller than `sequence_length`, but got `mask_length`: {mask_length} and `sequence_length`: {length}`")
+    epsilon = np.random.rand(1).item()
+    spans = max(int(mask_prob * length / mask_length + epsilon), min_masks)
+    if spans * mask_length > length:
+        spans = length // mask_length
+    if length - (mask_length - 1) < spans:
+        spans = max(length - (mask_length - 1), 0)
+    mask = np.zeros((batch, length), dtype=bool)
+    if spans == 0:
+        return mask
+    starts = np.stack([np.random.choice(np.arange(length - (mask_length - 1)), spans, replace=False) for _ in range(batch)])
+    idx = np.minimum(starts[:, :, None] + np.arange(mask_length)[None, None, :], length - 1).reshape(batch, -1)
+    np.put_along_axis(mask, idx, True, -1)
+    return mask
+
+
+def draw_audio_train(cfg: AudioTrainConfig, batch: int, frames: int, num_layers: int, layerdrop_draw=None) -> AudioTrainDraws:
+    """The draws of one train-mode forward, in the reference's order: the span mask (``np.random``), one LayerDrop draw per layer — a
+    layer is skipped iff ``draw < cfg.layerdrop``; ``layerdrop_draw`` defaults to ``np.random.uniform(0, 1)``, what transformers 4.30.2
+    is published to call (later versions call ``torch.rand([])``: pass ``lambda: float(torch.rand([]))``) — and the dropout seed, one
+    ``torch.randint(0, 2**62, (1,))`` on torch's CPU generator."""
+    cfg.check()
+    mask = compute_mask_indices((batch, frames), cfg.mask_time_prob, cfg.mask_time_length, cfg.mask_time_min_masks) if cfg.mask_time_prob > 0 else None
+    draw = layerdrop_draw if layerdrop_draw is not None else (lambda: np.random.uniform(0, 1))
+    skip = tuple(bool(draw() < cfg.layerdrop) for _ in range(num_layers))
+    return AudioTrainDraws(mask=mask, skip=skip, seed=int(torch.randint(0, 2 ** 62, (1,)).item()))
 
 
 @dataclass

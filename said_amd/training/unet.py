@@ -4,7 +4,8 @@
 (include/said_unet_train.h) and runs a whole optimizer step there: add_noise, training-mode forward with ResBlock dropout, the objective of
 ``random_noise_loss``, backward, ``clip_grad_norm_(1.0)``, ``torch.optim.AdamW`` and diffusers' ``EMAModel.step``.  The host draws what the
 reference draws on the host (noise and timesteps on torch's CPU generator, plus one 64-bit dropout seed per step) and writes the per-step
-scalars.  The audio encoder is frozen and runs as it does in inference: its embedding of the batch is an input of the step.
+scalars.  The audio encoder is frozen; its embedding of the batch is an input of the step.  It runs as in inference, or, with
+``train_epoch(..., audio_train=AudioTrainConfig())``, in Wav2Vec2's train mode as the reference's does.
 """
 from __future__ import annotations
 
@@ -23,6 +24,7 @@ from torch import nn
 from torch.utils.data import DataLoader, Dataset, RandomSampler
 
 from .. import _engine
+from ..model.wav2vec2 import AudioTrainConfig, draw_audio_train
 from ..scheduler import DDIMScheduler
 from ..util.audio import load_audio
 from ..util.blendshape import DEFAULT_BLENDSHAPE_CLASSES, load_blendshape_coeffs
@@ -261,11 +263,13 @@ class UNetTrainer(TrainerBase):
         n = acc[4]
         return UNetLossEpochOutput(total=acc[3] / n, predict=acc[0] / n, velocity=acc[1] / n, vertex=acc[2] / n, lr=lr)
 
-    def train_epoch(self, model, train_dataloader: Iterable, weight_vel: float, weight_vertex: float) -> UNetLossEpochOutput:
+    def train_epoch(self, model, train_dataloader: Iterable, weight_vel: float, weight_vertex: float,
+                    audio_train: Optional[AudioTrainConfig] = None) -> UNetLossEpochOutput:
         """train_epoch of script/train.py: one step per batch, the audio embedded by `model` (a SAID_UNet1D: its frozen HIP encoder), the
-        losses read once at the end; lr is the LR after the last step."""
+        losses read once at the end; lr is the LR after the last step.  audio_train: the encoder in Wav2Vec2's train mode (the reference
+        calls said_model.train() before its epoch); None: as in inference."""
         for data in train_dataloader:
-            self.enqueue_step(data.blendshape_coeffs, data.cond, batch_audio_embedding(model, data), weight_vel=weight_vel,
+            self.enqueue_step(data.blendshape_coeffs, data.cond, batch_audio_embedding(model, data, audio_train), weight_vel=weight_vel,
                               weight_vertex=weight_vertex, deltas=None if data.blendshape_delta is None else normalize_deltas(data.blendshape_delta))
         return self.epoch_output(False, self.lr_at(self.step_count))
 
@@ -280,10 +284,16 @@ class UNetTrainer(TrainerBase):
         return self.epoch_output(True)
 
 
-def batch_audio_embedding(model, data) -> torch.Tensor:
-    """(B, T, 768) embedding of a batch's waveforms by the model's frozen audio encoder, as random_noise_loss obtains it."""
+def batch_audio_embedding(model, data, audio_train: Optional[AudioTrainConfig] = None) -> torch.Tensor:
+    """(B, T, 768) embedding of a batch's waveforms by the model's frozen audio encoder, as random_noise_loss obtains it.  With
+    `audio_train` the encoder runs in Wav2Vec2's train mode, as the reference's does during its training epoch: the span mask, the
+    LayerDrop decisions and the dropout seed are drawn here (draw_audio_train), before the step draws its own."""
     wave = model.process_audio(data.waveform).to(next(model.parameters()).device)
-    return model.get_audio_embedding(wave, data.blendshape_coeffs.shape[1]).float()
+    frames = data.blendshape_coeffs.shape[1]
+    if audio_train is None:
+        return model.get_audio_embedding(wave, frames).float()
+    draws = draw_audio_train(audio_train, wave.shape[0], frames, model.audio_config.num_hidden_layers)
+    return model.get_audio_embedding(wave, frames, train_draws=draws, train_cfg=audio_train).float()
 
 
 # ---------------------------------------------------------------------------------------------------------------- data sets

@@ -3,7 +3,10 @@
 Command-line compatible with the reference (same flags, names and defaults; `--ema` keeps argparse's type=bool behaviour).  Differences:
 - The frozen Wav2Vec2 encoder comes from --audio_encoder_weights: a state dict holding `audio_encoder.*` (a SAID_UNet1D checkpoint will
   do), or 'synthetic' for the seeded test weights.  The reference downloads facebook/wav2vec2-base-960h; nothing is downloaded here.
-  The encoder runs as in inference (the reference leaves it in train() mode: DESIGN.md 16.6).
+- --audio_encoder_mode {eval,train}: how that frozen encoder runs during the training epoch.  'eval' (the default: the behaviour and, for a
+  given --seed, the logs of every earlier version) runs it as in inference.  'train' reproduces the reference, which calls
+  said_model.train() before its epoch and so feeds the denoiser conditioning that went through Wav2Vec2's SpecAugment time masking,
+  dropouts and LayerDrop (wav2vec2-base-960h's published config values).  Validation runs in eval mode either way.
 - --unet_feature_dim > 0 is accepted and refused: the extra audio_proj_layer is not trainable here.
 - New flags: --seed, --device.  Logs go to stdout and to <output_dir>/log.csv (the reference's TensorBoard keys as columns).
 - <output_dir>/<epoch>.pth is SAID_UNet1D's state dict, written between EMA copy_to and restore as in the reference.
@@ -22,6 +25,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from said_amd.model.diffusion import SAID_UNet1D  # noqa: E402
+from said_amd.model.wav2vec2 import AudioTrainConfig  # noqa: E402
 from said_amd.training import TrainWindowDataset, UNetTrainer, ValWindowDataset, make_unet_dataloaders, unet_init_state_dict  # noqa: E402
 from said_amd.util.blendshape import load_blendshape_coeffs  # noqa: E402
 
@@ -55,6 +59,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--save_period", type=int, default=200, help="Period of saving model")
     ap.add_argument("--audio_encoder_weights", type=str, default="../BlendVOCA/SAiD.pth",
                     help="state dict holding audio_encoder.* (the frozen Wav2Vec2), or 'synthetic' for the seeded test weights")
+    ap.add_argument("--audio_encoder_mode", type=str, default="eval", choices=["eval", "train"],
+                    help="the frozen audio encoder during training: 'eval' as in inference, 'train' as the reference leaves it (SpecAugment, dropout, LayerDrop)")
     ap.add_argument("--seed", type=int, default=None, help="seed of Python's random, numpy and torch (unseeded by default)")
     ap.add_argument("--device", type=str, default="cuda:0", help="MI355X to train on (there is no CPU path)")
     return ap
@@ -96,12 +102,13 @@ def main(argv=None):
                           num_warmup_steps=len(train_dataloader) * args.num_warmup_epochs, ema=args.ema, ema_decay=args.ema_decay, std=coeffs_std,
                           prediction_type=args.prediction_type)
 
+    audio_train = AudioTrainConfig() if args.audio_encoder_mode == "train" else None
     with open(os.path.join(args.output_dir, "log.csv"), "a", newline="") as f:
         log = csv.DictWriter(f, fieldnames=COLUMNS)
         if f.tell() == 0:
             log.writeheader()
         for epoch in range(1, args.epochs + 1):
-            tl = trainer.train_epoch(model, train_dataloader, args.weight_vel, args.weight_vertex)
+            tl = trainer.train_epoch(model, train_dataloader, args.weight_vel, args.weight_vertex, audio_train=audio_train)
             logs = {"epoch": epoch, "Train/Total Loss": tl.total, "Train/Predict Loss": tl.predict, "Train/Velocity Loss": tl.velocity,
                     "Train/Vertex Loss": tl.vertex, "Train/Learning Rate": tl.lr}
             if epoch % args.val_period == 0 and len(val_dataset) > 0:

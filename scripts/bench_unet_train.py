@@ -1,7 +1,12 @@
 """Median time of one denoiser training step on one MI355X (said_amd.training.UNetTrainer) beside torch-eager on the same GPU running the
 restatement of the same step (tests/unet_train_ref.py: forward, objective, autograd backward, clip_grad_norm_, torch.optim.AdamW; no EMA).
 
-    python scripts/bench_unet_train.py [--batch 8] [--frames 120 240] [--steps 20] [--warmup 5]
+    python scripts/bench_unet_train.py [--batch 8] [--frames 120 240] [--steps 20] [--warmup 5] [--audio_encoder_mode eval|train]
+
+With --audio_encoder_mode the line also carries what the frozen audio encoder (twelve layers, clips of frames / 60 seconds) adds to a step of
+script/train.py: `encode_eval_ms` and, in mode `train`, `encode_train_ms` (Wav2Vec2's train mode: SpecAugment spans, dropouts, LayerDrop off so
+that all twelve layers run) — device-event medians, the two modes alternating in one loop — and `step_with_encode_ms`, the host time of encode
+(in the chosen mode, draws included) plus step.
 """
 import argparse
 import json
@@ -28,11 +33,21 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--audio_encoder_mode", choices=["eval", "train"], default=None, help="also time the twelve-layer audio encoder, in eval mode and (train) in train mode")
     a = ap.parse_args()
     dev = torch.device(a.device)
     sd = said_state_dict(num_w2v_layers=1)
     B = a.batch
     tr = UNetTrainer(sd, dev, max_batch=B, max_frames=max(a.frames), learning_rate=1e-5, num_warmup_steps=10)
+    enc = None
+    if a.audio_encoder_mode:
+        from said_amd.model.diffusion import SAID_UNet1D
+        from said_amd.model.wav2vec2 import AudioTrainConfig, draw_audio_train
+        from said_amd.util.synth import synth_waveform
+        enc = SAID_UNet1D()
+        enc.load_state_dict(said_state_dict(), strict=True)
+        enc.to(dev)
+        cfg = AudioTrainConfig(layerdrop=0.0)   # every layer runs: the time does not depend on the draw
     for T in a.frames:
         g = torch.Generator().manual_seed(T)
         coeffs, noise, audio = torch.rand(B, T, 32, generator=g), torch.randn(B, T, 32, generator=g), torch.randn(B, T, 768, generator=g)
@@ -64,8 +79,35 @@ def main():
             torch.cuda.synchronize(dev)
             times.append(time.perf_counter() - t0)
         eager_ms = 1e3 * statistics.median(times[a.warmup:])
-        print(json.dumps({"batch": B, "frames": T, "hip_step_ms": round(hip_ms, 3), "torch_eager_step_ms": round(eager_ms, 3),
-                          "speedup": round(eager_ms / hip_ms, 3)}), flush=True)
+        line = {"batch": B, "frames": T, "hip_step_ms": round(hip_ms, 3), "torch_eager_step_ms": round(eager_ms, 3), "speedup": round(eager_ms / hip_ms, 3)}
+        if enc is not None:
+            wave = enc.process_audio([synth_waveform(i, 16000 * T // 60).numpy() for i in range(B)]).to(dev)
+            train = a.audio_encoder_mode == "train"
+
+            def encode(in_train_mode):
+                draws = draw_audio_train(cfg, B, T, 12) if in_train_mode else None
+                return enc.get_audio_embedding(wave, T, train_draws=draws, train_cfg=cfg)
+
+            ev = {False: [], True: []}
+            for k in range(a.warmup + a.steps):
+                for m in ((False, True) if train else (False,)):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    encode(m)
+                    e1.record()
+                    torch.cuda.synchronize(dev)
+                    ev[m].append(e0.elapsed_time(e1))
+            line["encode_eval_ms"] = round(statistics.median(ev[False][a.warmup:]), 3)
+            if train:
+                line["encode_train_ms"] = round(statistics.median(ev[True][a.warmup:]), 3)
+            times = []
+            for k in range(a.warmup + a.steps):
+                t0 = time.perf_counter()
+                tr.step(coeffs, cond, encode(train), noise=noise, timesteps=ts, dropout_seed=k)
+                times.append(time.perf_counter() - t0)
+            line["audio_encoder_mode"] = a.audio_encoder_mode
+            line["step_with_encode_ms"] = round(1e3 * statistics.median(times[a.warmup:]), 3)
+        print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":
