@@ -183,10 +183,18 @@ JPEG_EXPORTS = {
 _c_ull = ctypes.c_ulonglong
 UNET_TRAIN_EXPORTS = {
     "said_unet_train_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int]),
+    "said_unet_train_create_dim": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int]),
     "said_unet_train_destroy": (c_int, [c_void_p]),
     "said_unet_train_last_error": (c_char_p, [c_void_p]),
     "said_unet_train_tensor_name": (c_char_p, [c_int]),
     "said_unet_train_tensor_numel": (ctypes.c_longlong, [c_int]),
+    "said_unet_train_table_size": (c_int, [c_int]),
+    "said_unet_train_table_name": (c_char_p, [c_int, c_int]),
+    "said_unet_train_table_numel": (ctypes.c_longlong, [c_int, c_int]),
+    "said_unet_train_num_tensors": (c_int, [c_void_p]),
+    "said_unet_train_context_tensor_name": (c_char_p, [c_void_p, c_int]),
+    "said_unet_train_context_tensor_numel": (ctypes.c_longlong, [c_void_p, c_int]),
+    "said_unet_train_feature_dim": (c_int, [c_void_p]),
     "said_unet_train_set_tensor": (c_int, [c_void_p, c_int, c_char_p, _c_float_p, ctypes.c_longlong]),
     "said_unet_train_get_tensor": (c_int, [c_void_p, c_int, c_char_p, _c_float_p, ctypes.c_longlong]),
     "said_unet_train_reset_optimizer": (c_int, [c_void_p]),
@@ -1036,12 +1044,19 @@ class UNetTrainEngine(_TrainContext):
     prefix, group, n_last = "said_unet_train", "unet_train", 6   # last_losses: predict, velocity, vertex, total, clip factor, gradient norm
     cpu_error, cpu_message = NoCpuPathError, "said_amd trains the denoiser on MI355X only (device={}); there is no CPU path"
 
-    def __init__(self, device: torch.device, max_batch: int, max_frames: int):
+    def __init__(self, device: torch.device, max_batch: int, max_frames: int, feature_dim: Optional[int] = -1):
         super().__init__(device)
-        self._create(int(max_batch), int(max_frames))
+        if feature_dim is None:   # the entry point without a feature_dim: the default context, as feature_dim=-1 is
+            self._create(int(max_batch), int(max_frames))
+        else:
+            h = c_void_p()
+            if self.lib.said_unet_train_create_dim(ctypes.byref(h), self.index, int(max_batch), int(max_frames), int(feature_dim)) != 0:
+                raise EngineError("said_unet_train_create_dim: " + self._last_error(None))
+            self.h = h
         self.max_batch, self.max_frames = int(max_batch), int(max_frames)
-        self.tensors = [(self.lib.said_unet_train_tensor_name(i).decode(), int(self.lib.said_unet_train_tensor_numel(i)))
-                        for i in range(UT_NUM_TENSORS)]
+        self.feature_dim = int(self.lib.said_unet_train_feature_dim(self.h))   # -1: no audio_proj_layer
+        self.tensors = [(self.lib.said_unet_train_context_tensor_name(self.h, i).decode(), int(self.lib.said_unet_train_context_tensor_numel(self.h, i)))
+                        for i in range(self.lib.said_unet_train_num_tensors(self.h))]
 
     def copy(self, dst: int, src: int) -> None:
         self._call("said_unet_train_copy", dst, src)

@@ -73,6 +73,8 @@ void copy2d(hipStream_t s, int M, int N, const float* src, int lds, float* dst, 
 void select_ctx(hipStream_t s, int B, int T, int Cc, const float* audio, const float* null_emb, const int* cond, float* ctx);
 // zero the rows of the samples whose cond is set
 void mask_cond_rows(hipStream_t s, int B, int T, int Cc, const int* cond, float* d);
+// dc = d with the rows of the samples whose cond is not set zeroed; those rows stay in d, whose other rows become zero
+void split_cond_rows(hipStream_t s, int B, int T, int Cc, const int* cond, float* d, float* dc);
 // e[b][:] = [cos(t_b f_i), sin(t_b f_i)], f_i = exp(-ln(10000) i / (dim / 2)), fp32 as the reference computes it
 void timestep_embedding(hipStream_t s, int B, int dim, const float* tsteps, float* e);
 // noisy = sa x0 + sb noise; answer = noise | x0 | sa noise - sb x0 by prediction type (rec[S_PRED_TYPE]); sasb (B, 2)

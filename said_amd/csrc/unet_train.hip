@@ -349,6 +349,15 @@ __global__ void __launch_bounds__(NT) mask_cond_rows_kernel(long long n, int T, 
     if (i >= n) return;
     if (cond[(int)(i / ((long long)T * Cc))]) d[i] = 0.f;
 }
+__global__ void __launch_bounds__(NT) split_cond_rows_kernel(long long n, int T, int Cc, const int* __restrict__ cond, float* __restrict__ d,
+                                                             float* __restrict__ dc) {
+    const long long i = (long long)blockIdx.x * NT + threadIdx.x;
+    if (i >= n) return;
+    const bool c = cond[(int)(i / ((long long)T * Cc))] != 0;
+    const float v = d[i];
+    dc[i] = c ? v : 0.f;
+    d[i] = c ? 0.f : v;
+}
 __global__ void __launch_bounds__(NT) timestep_embedding_kernel(int B, int dim, const float* __restrict__ ts, float* __restrict__ e) {
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i >= B * dim) return;
@@ -484,6 +493,10 @@ void select_ctx(hipStream_t s, int B, int T, int Cc, const float* audio, const f
 void mask_cond_rows(hipStream_t s, int B, int T, int Cc, const int* cond, float* d) {
     const long long n = (long long)B * T * Cc;
     mask_cond_rows_kernel<<<nblk(n), NT, 0, s>>>(n, T, Cc, cond, d);
+}
+void split_cond_rows(hipStream_t s, int B, int T, int Cc, const int* cond, float* d, float* dc) {
+    const long long n = (long long)B * T * Cc;
+    split_cond_rows_kernel<<<nblk(n), NT, 0, s>>>(n, T, Cc, cond, d, dc);
 }
 void timestep_embedding(hipStream_t s, int B, int dim, const float* tsteps, float* e) {
     timestep_embedding_kernel<<<nblk((long long)B * dim), NT, 0, s>>>(B, dim, tsteps, e);

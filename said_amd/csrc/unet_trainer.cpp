@@ -1,11 +1,15 @@
 // unet_trainer.cpp — the UNet denoiser trainer context (include/said_unet_train.h): the table of trainable tensors, the device copies of the
 // parameters and of the optimizer, the activation arena, and the step: add_noise, forward, objective, backward, clip, AdamW, EMA, launched in that
-// order on the context's stream (unet_train.hip).  T is a run-time value, so nothing is captured into a graph.
+// order on the context's stream (unet_train.hip).  T is a run-time value, so nothing is captured into a graph.  A context made with
+// feature_dim = F > 0 also holds and trains audio_proj_layer (768 -> F) and runs the context at width F; F <= 0 leaves every launch as it is.
 #include "../../include/said_unet_train.h"
 
 #include "engine_internal.h"
 #include "train_store.h"
 #include "unet_train.h"
+
+#include <map>
+#include <mutex>
 
 using namespace said::ut;
 
@@ -15,13 +19,17 @@ static_assert(NACC == TS_NACC && A_BAD == TS_A_BAD && SAID_UT_NOT_FINITE == 1, "
 namespace {
 
 struct TDesc { std::string name; long long numel; };
-constexpr int CH = 192, TEd = 768, CTX = 768, FF = 768, NH = 6;
+constexpr int CH = 192, TEd = 768, FF = 768, NH = 6;
+constexpr int AUD = SAID_UT_CTX_DIM;   // width of the frozen encoder's output, and of the context without an audio_proj_layer
 
-// null_cond_emb, then UNet1DConditionModel.state_dict() under "denoiser.", in the reference's registration order
-std::vector<TDesc> make_table() {
+// null_cond_emb, (F > 0: audio_proj_layer,) then UNet1DConditionModel.state_dict() under "denoiser.", in the reference's registration order.
+// F <= 0: the context is the encoder's output itself (SAID_UNet1D(feature_dim = -1))
+std::vector<TDesc> make_table(int F) {
     std::vector<TDesc> v;
     auto add = [&](const std::string& n, long long k) { v.push_back({n, k}); };
+    const int CTX = F > 0 ? F : AUD;
     add("null_cond_emb", CTX);
+    if (F > 0) { add("audio_proj_layer.weight", (long long)F * AUD); add("audio_proj_layer.bias", F); }
     const std::string m = "denoiser.model.";
     add(m + "time_embed.0.weight", TEd * CH); add(m + "time_embed.0.bias", TEd);
     add(m + "time_embed.2.weight", TEd * TEd); add(m + "time_embed.2.bias", TEd);
@@ -59,9 +67,15 @@ std::vector<TDesc> make_table() {
     add(m + "out.2.weight", XC * CH * 3); add(m + "out.2.bias", XC);
     return v;
 }
-const std::vector<TDesc>& table() {
-    static const std::vector<TDesc> t = make_table();
-    return t;
+// the table of feature_dim F (<= 0: the default one), built once; a std::map's nodes stay where they are
+const std::vector<TDesc>& table(int F = 0) {
+    static std::mutex mu;
+    static std::map<int, std::vector<TDesc>> tabs;
+    const int key = F > 0 ? F : 0;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = tabs.find(key);
+    if (it == tabs.end()) it = tabs.emplace(key, make_table(key)).first;
+    return it->second;
 }
 const char* kRes[5] = {"denoiser.model.input_blocks.1.0", "denoiser.model.middle_block.0", "denoiser.model.middle_block.2",
                        "denoiser.model.output_blocks.0.0", "denoiser.model.output_blocks.1.0"};
@@ -82,6 +96,8 @@ struct Acts {
     STAct s[4];
     // backward scratch
     float *d, *dcat, *dH0, *dH1, *g1, *g2, *g3, *g4, *g5, *big1, *big2, *PB, *dctx, *dee, *dembs, *demb, *de1s, *de1, *R, *dpred, *GV;
+    // feature_dim > 0: the projected audio (B T, F) and the conditional samples' rows of dctx
+    float *proj, *dcond;
 };
 
 }  // namespace
@@ -89,6 +105,8 @@ struct Acts {
 struct said_unet_train {
     HostCtx c;
     int maxB = 0, maxT = 0;
+    int F = 0, CTX = AUD;     // feature_dim (0: no audio_proj_layer) and the context width, F or 768
+    const std::vector<TDesc>* tb = nullptr;
     hipStream_t s = nullptr;
     TrainStore st;            // the parameters (with the stash of EMAModel.store) and the optimizer's state
     std::map<std::string, long long> off;
@@ -107,9 +125,9 @@ struct said_unet_train {
 
 namespace {
 
-size_t layout(Acts& a, float* base, int B, int T) {
+size_t layout(Acts& a, float* base, int B, int T, int F) {
     size_t pos = 0;
-    const size_t M = (size_t)B * T;
+    const size_t M = (size_t)B * T, CTX = F > 0 ? F : AUD;
     auto take = [&](size_t n) { float* p = base ? base + pos : nullptr; pos += (n + 63) / 64 * 64; return p; };
     a.ctx = take(M * CTX); a.noisy = take(M * XC); a.answer = take(M * XC); a.temb = take((size_t)B * CH); a.e1 = take((size_t)B * TEd);
     a.e1s = take((size_t)B * TEd); a.emb = take((size_t)B * TEd); a.embs = take((size_t)B * TEd); a.h0 = take(M * CH);
@@ -133,6 +151,8 @@ size_t layout(Acts& a, float* base, int B, int T) {
     a.big1 = take(M * FF); a.big2 = take(M * 2 * FF); a.PB = take((size_t)B * NH * T * T); a.dctx = take(M * CTX);
     a.dee = take((size_t)B * CH); a.dembs = take((size_t)B * TEd); a.demb = take((size_t)B * TEd); a.de1s = take((size_t)B * TEd); a.de1 = take((size_t)B * TEd);
     a.R = take(M * XC); a.dpred = take(M * XC); a.GV = take(M * XC);
+    a.proj = a.dcond = nullptr;
+    if (F > 0) { a.proj = take(M * F); a.dcond = take(M * F); }
     return pos;
 }
 
@@ -215,7 +235,14 @@ void enqueue_forward(said_unet_train* t, int B, int T, const float* base, float 
     const int M = B * T;
     auto w = [&](const std::string& n) { return par(t, base, n); };
     const std::string m = "denoiser.model.";
-    select_ctx(s, B, T, CTX, t->audio, w("null_cond_emb"), t->cond, a.ctx);
+    const int CTX = t->CTX;
+    if (t->F > 0) {
+        // get_audio_embedding projects, then the trainer selects (script/train.py:86-94)
+        gm.lin(t->audio, AUD, w("audio_proj_layer.weight"), w("audio_proj_layer.bias"), a.proj, CTX, M, CTX, AUD);
+        select_ctx(s, B, T, CTX, a.proj, w("null_cond_emb"), t->cond, a.ctx);
+    } else {
+        select_ctx(s, B, T, CTX, t->audio, w("null_cond_emb"), t->cond, a.ctx);
+    }
     timestep_embedding(s, B, CH, t->tsf, a.temb);
     gm.lin(a.temb, CH, w(m + "time_embed.0.weight"), w(m + "time_embed.0.bias"), a.e1, TEd, B, TEd, CH);
     silu_fwd(s, (long long)B * TEd, a.e1, a.e1s);
@@ -322,6 +349,7 @@ void enqueue_backward(said_unet_train* t, int B, int T, float p, unsigned long l
     auto gw = [&](const std::string& n) { return par(t, t->st.G, n); };
     const std::string m = "denoiser.model.";
     const float scale = 0.17677669529663687f;
+    const int CTX = t->CTX;
     // norm gradients: dgamma = sum du xhat, dbeta = sum du over the rows
     auto norm_grads = [&](const float* du, const float* xh, int C, const std::string& name) {
         colsum(s, du, C, xh, C, M, 1, C, gw(name + ".weight"), 0);
@@ -427,8 +455,15 @@ void enqueue_backward(said_unet_train* t, int B, int T, float p, unsigned long l
     silu_bwd(s, (long long)B * TEd, a.e1, a.de1s, a.de1);
     gm.lin_wgrad(a.de1, a.temb, CH, gw(m + "time_embed.0.weight"), gw(m + "time_embed.0.bias"), B, TEd, CH);
     // null_cond_emb: the context gradient summed over the unconditional samples' positions
-    mask_cond_rows(s, B, T, CTX, t->cond, a.dctx);
-    colsum(s, a.dctx, CTX, nullptr, 0, M, 1, CTX, gw("null_cond_emb"), 0);
+    if (t->F > 0) {
+        // the conditional samples' rows go to the projection (nothing flows into the frozen encoder's output)
+        split_cond_rows(s, B, T, CTX, t->cond, a.dctx, a.dcond);
+        colsum(s, a.dctx, CTX, nullptr, 0, M, 1, CTX, gw("null_cond_emb"), 0);
+        gm.lin_wgrad(a.dcond, t->audio, AUD, gw("audio_proj_layer.weight"), gw("audio_proj_layer.bias"), M, CTX, AUD);
+    } else {
+        mask_cond_rows(s, B, T, CTX, t->cond, a.dctx);
+        colsum(s, a.dctx, CTX, nullptr, 0, M, 1, CTX, gw("null_cond_emb"), 0);
+    }
 }
 
 int put_record(said_unet_train* t, const float* scalars, const float* std_) {
@@ -475,7 +510,7 @@ int put_inputs(said_unet_train* t, const char* what, int B, int T, const float* 
     HIPCHK(hipMemcpyAsync(t->sasb, ab.data(), 2 * B * sizeof(float), hipMemcpyHostToDevice, t->s));
     HIPCHK(hipMemcpyAsync(t->cond, cond, B * sizeof(int), hipMemcpyHostToDevice, t->s));
     HIPCHK(hipMemcpyAsync(t->band, band.data(), band.size() * sizeof(int), hipMemcpyHostToDevice, t->s));
-    HIPCHK(hipMemcpyAsync(t->audio, audio, (size_t)B * T * CTX * sizeof(float), audio_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, t->s));
+    HIPCHK(hipMemcpyAsync(t->audio, audio, (size_t)B * T * AUD * sizeof(float), audio_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, t->s));
     HIPCHK(hipStreamSynchronize(t->s));   // the host vectors above end with this call
     return 0;
 }
@@ -499,9 +534,9 @@ int check_std(said_unet_train* t, const float* std_, const char* what) {
     return 0;
 }
 
-int tindex(const char* name) {
+int tindex(const said_unet_train* t, const char* name) {
     if (!name) return -1;
-    const auto& tb = table();
+    const auto& tb = *t->tb;
     for (size_t i = 0; i < tb.size(); ++i)
         if (tb[i].name == name) return (int)i;
     return -1;
@@ -511,11 +546,37 @@ int tindex(const char* name) {
 
 extern "C" {
 
-const char* said_unet_train_tensor_name(int i) { return (i >= 0 && i < (int)table().size()) ? table()[i].name.c_str() : nullptr; }
-long long said_unet_train_tensor_numel(int i) { return (i >= 0 && i < (int)table().size()) ? table()[i].numel : -1; }
+const char* said_unet_train_tensor_name(int i) { return said_unet_train_table_name(0, i); }
+long long said_unet_train_tensor_numel(int i) { return said_unet_train_table_numel(0, i); }
+
+int said_unet_train_table_size(int feature_dim) { return feature_dim > SAID_UT_MAX_FEATURE_DIM ? -1 : (int)table(feature_dim).size(); }
+const char* said_unet_train_table_name(int feature_dim, int i) {
+    if (feature_dim > SAID_UT_MAX_FEATURE_DIM) return nullptr;
+    const auto& tb = table(feature_dim);
+    return (i >= 0 && i < (int)tb.size()) ? tb[i].name.c_str() : nullptr;
+}
+long long said_unet_train_table_numel(int feature_dim, int i) {
+    if (feature_dim > SAID_UT_MAX_FEATURE_DIM) return -1;
+    const auto& tb = table(feature_dim);
+    return (i >= 0 && i < (int)tb.size()) ? tb[i].numel : -1;
+}
+int said_unet_train_num_tensors(const said_unet_train* t) { return t ? (int)t->tb->size() : -1; }
+int said_unet_train_feature_dim(const said_unet_train* t) { return (t && t->F > 0) ? t->F : -1; }
+const char* said_unet_train_context_tensor_name(const said_unet_train* t, int i) {
+    return (t && i >= 0 && i < (int)t->tb->size()) ? (*t->tb)[i].name.c_str() : nullptr;
+}
+long long said_unet_train_context_tensor_numel(const said_unet_train* t, int i) {
+    return (t && i >= 0 && i < (int)t->tb->size()) ? (*t->tb)[i].numel : -1;
+}
 
 int said_unet_train_create(said_unet_train** out, int device, int max_batch, int max_frames) {
+    return said_unet_train_create_dim(out, device, max_batch, max_frames, -1);
+}
+
+int said_unet_train_create_dim(said_unet_train** out, int device, int max_batch, int max_frames, int feature_dim) {
     DeviceRestore restore_device;
+    if (feature_dim > SAID_UT_MAX_FEATURE_DIM)
+        return fail(nullptr, "said_unet_train_create_dim: feature_dim %d above %d (SAID_UT_MAX_FEATURE_DIM)", feature_dim, SAID_UT_MAX_FEATURE_DIM);
     said_unet_train* t = new_ctx("said_unet_train_create", out, device);
     if (!t) return -1;
     if (max_batch < 1 || max_batch > 256) { delete t; return fail(nullptr, "said_unet_train_create: max_batch %d outside [1, 256]", max_batch); }
@@ -523,18 +584,21 @@ int said_unet_train_create(said_unet_train** out, int device, int max_batch, int
     HostCtx* ctx = &t->c;
     t->maxB = max_batch;
     t->maxT = max_frames;
-    const auto& tb = table();
+    t->F = feature_dim > 0 ? feature_dim : 0;
+    t->CTX = t->F > 0 ? t->F : AUD;
+    t->tb = &table(t->F);
+    const auto& tb = *t->tb;
     std::vector<long long> sizes, off;
     for (const TDesc& d : tb) sizes.push_back(d.numel);
     Acts tmp;
-    t->arena_n = layout(tmp, nullptr, max_batch, max_frames);
+    t->arena_n = layout(tmp, nullptr, max_batch, max_frames, t->F);
     const size_t Mx = (size_t)max_batch * max_frames;
     int rc = 0;
     rc = rc || hipStreamCreateWithFlags(&t->s, hipStreamNonBlocking) != hipSuccess;
     rc = rc || dalloc(ctx, &t->rec, NSCAL + XC) || dalloc(ctx, &t->coeffs, Mx * XC) ||
          dalloc(ctx, &t->noise, Mx * XC) || dalloc(ctx, &t->tsf, max_batch) || dalloc(ctx, &t->sasb, (size_t)2 * max_batch) ||
-         dalloc(ctx, &t->audio, Mx * CTX) || dalloc(ctx, &t->cond, max_batch) || dalloc(ctx, &t->band, (size_t)2 * max_frames) ||
-         dalloc(ctx, &t->arena, t->arena_n) || dalloc(ctx, &t->gpart, (size_t)MAXKS * TEd * TEd) || dalloc(ctx, &t->vpart, VBLK);
+         dalloc(ctx, &t->audio, Mx * AUD) || dalloc(ctx, &t->cond, max_batch) || dalloc(ctx, &t->band, (size_t)2 * max_frames) ||
+         dalloc(ctx, &t->arena, t->arena_n) || dalloc(ctx, &t->gpart, (size_t)MAXKS * std::max(TEd, t->F) * TEd) || dalloc(ctx, &t->vpart, VBLK);
     rc = rc || store_build(&t->st, ctx, sizes, true, &off);   // last: it ends with a synchronous copy, after every allocation's memset
     for (size_t i = 0; i < tb.size() && !rc; ++i) t->off[tb[i].name] = off[i];
     if (rc) {
@@ -556,14 +620,14 @@ int said_unet_train_destroy(said_unet_train* t) {
 
 const char* said_unet_train_last_error(const said_unet_train* t) { return ctx_error(t); }
 
-static float* copy_of(said_unet_train* t, int which, int i) { return store_copy_of(&t->st, which, t->off.at(table()[i].name)); }
+static float* copy_of(said_unet_train* t, int which, int i) { return store_copy_of(&t->st, which, t->off.at((*t->tb)[i].name)); }
 
 int said_unet_train_set_tensor(said_unet_train* t, int which, const char* name, const float* host, long long n) {
     if (!t) return -1;
     HostCtx* ctx = &t->c;
-    const int i = tindex(name);
+    const int i = tindex(t, name);
     if (i < 0) return fail(ctx, "said_unet_train_set_tensor: unknown tensor %s", name ? name : "(null)");
-    if (!host || n != table()[i].numel) return fail(ctx, "said_unet_train_set_tensor: %s has %lld elements, got %lld", name, table()[i].numel, n);
+    if (!host || n != (*t->tb)[i].numel) return fail(ctx, "said_unet_train_set_tensor: %s has %lld elements, got %lld", name, (*t->tb)[i].numel, n);
     float* dst = copy_of(t, which, i);
     if (!dst) return fail(ctx, "said_unet_train_set_tensor: no copy %d", which);
     DeviceRestore restore_device;
@@ -574,9 +638,9 @@ int said_unet_train_set_tensor(said_unet_train* t, int which, const char* name, 
 int said_unet_train_get_tensor(said_unet_train* t, int which, const char* name, float* host, long long n) {
     if (!t) return -1;
     HostCtx* ctx = &t->c;
-    const int i = tindex(name);
+    const int i = tindex(t, name);
     if (i < 0) return fail(ctx, "said_unet_train_get_tensor: unknown tensor %s", name ? name : "(null)");
-    if (!host || n != table()[i].numel) return fail(ctx, "said_unet_train_get_tensor: %s has %lld elements, got %lld", name, table()[i].numel, n);
+    if (!host || n != (*t->tb)[i].numel) return fail(ctx, "said_unet_train_get_tensor: %s has %lld elements, got %lld", name, (*t->tb)[i].numel, n);
     float* src = copy_of(t, which, i);
     if (!src) return fail(ctx, "said_unet_train_get_tensor: no copy %d", which);
     DeviceRestore restore_device;
@@ -624,12 +688,12 @@ int said_unet_train_step(said_unet_train* t, int B, int T, const float* coeffs, 
     if (put_inputs(t, what, B, T, coeffs, noise, ts, cond, audio, audio_on_device, true) || put_deltas(t, what, B, T, deltas, V) ||
         put_record(t, scalars, std_))
         return -1;
-    layout(t->a, t->arena, B, T);
+    layout(t->a, t->arena, B, T, t->F);
     add_noise(t->s, B, T, t->coeffs, t->noise, t->sasb, t->rec, t->a.noisy, t->a.answer);
     enqueue_forward(t, B, T, t->st.P, p, seed);
     enqueue_loss(t, B, T, deltas ? V : 0, true, t->st.acc);
     HIPCHK(hipMemsetAsync(t->a.dembs, 0, (size_t)B * TEd * sizeof(float), t->s));
-    HIPCHK(hipMemsetAsync(t->a.dctx, 0, (size_t)B * T * CTX * sizeof(float), t->s));
+    HIPCHK(hipMemsetAsync(t->a.dctx, 0, (size_t)B * T * t->CTX * sizeof(float), t->s));
     enqueue_backward(t, B, T, p, seed);
     store_enqueue_update(&t->st, t->s, t->rec);
     HIPCHK(hipGetLastError());
@@ -648,7 +712,7 @@ int said_unet_train_eval_loss(said_unet_train* t, int B, int T, const float* coe
     if (put_inputs(t, what, B, T, coeffs, noise, ts, cond, audio, audio_on_device, true) || put_deltas(t, what, B, T, deltas, V) ||
         put_record(t, scalars, std_))
         return -1;
-    layout(t->a, t->arena, B, T);
+    layout(t->a, t->arena, B, T, t->F);
     add_noise(t->s, B, T, t->coeffs, t->noise, t->sasb, t->rec, t->a.noisy, t->a.answer);
     enqueue_forward(t, B, T, ema ? t->st.E : t->st.P, 0.f, 0);
     enqueue_loss(t, B, T, deltas ? V : 0, false, t->st.acc + NACC);
@@ -665,7 +729,7 @@ int said_unet_train_forward_only(said_unet_train* t, int B, int T, const float* 
     DeviceRestore restore_device;
     HIPCHK(hipSetDevice(ctx->device));
     if (put_inputs(t, what, B, T, sample, nullptr, ts, cond, audio, audio_on_device, false)) return -1;
-    layout(t->a, t->arena, B, T);
+    layout(t->a, t->arena, B, T, t->F);
     HIPCHK(hipMemcpyAsync(t->a.noisy, t->coeffs, (size_t)B * T * XC * sizeof(float), hipMemcpyDeviceToDevice, t->s));
     enqueue_forward(t, B, T, ema ? t->st.E : t->st.P, 0.f, 0);
     HIPCHK(hipGetLastError());

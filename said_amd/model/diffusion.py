@@ -251,16 +251,20 @@ class SAID(ABC, nn.Module):
         """(audio_seq_len,) or list thereof → (B, T_a) processed mono waveform (CPU, as in the reference)."""
         return self.audio_processor(waveform, sampling_rate=self.sampling_rate, return_tensors="pt")["input_values"]
 
-    def get_audio_embedding(self, waveform: torch.FloatTensor, num_frames: Optional[int], train_draws=None, train_cfg=None) -> torch.FloatTensor:
+    def get_audio_embedding(self, waveform: torch.FloatTensor, num_frames: Optional[int], train_draws=None, train_cfg=None,
+                            before_proj: bool = False) -> torch.FloatTensor:
         """(B, T_a) → (B, num_frames, hidden or feature_dim).  With `train_draws` (an AudioTrainDraws of said_amd.model.wav2vec2) the
         encoder runs as the reference's does under train(): SpecAugment spans, dropouts and LayerDrop with the probabilities of
-        `train_cfg` (default AudioTrainConfig()).  nn.Module.training has no effect on either call."""
+        `train_cfg` (default AudioTrainConfig()).  nn.Module.training has no effect on either call.  `before_proj` (not part of the
+        reference surface): with feature_dim > 0, the encoder's (B, num_frames, hidden) features before audio_proj_layer, which is what
+        the denoiser trainer takes (it trains the projection itself); no effect without an audio_proj_layer."""
         e = self._get_engine(1, num_frames or 1)
+        apply_proj = self.feature_dim > 0 and not before_proj
         if train_draws is None:
-            return e.audio_encode(waveform, num_frames, apply_proj=self.feature_dim > 0)
+            return e.audio_encode(waveform, num_frames, apply_proj=apply_proj)
         from .wav2vec2 import AudioTrainConfig
         return e.audio_encode_train(waveform, num_frames, train_draws, train_cfg if train_cfg is not None else AudioTrainConfig(),
-                                    apply_proj=self.feature_dim > 0)
+                                    apply_proj=apply_proj)
 
     def _encode_distinct(self, waveform: torch.FloatTensor, num_frames: int) -> torch.FloatTensor:
         """get_audio_embedding with byte-identical rows encoded once.  Candidates are found from two cheap per-row checksums (two passes over

@@ -1,6 +1,7 @@
 """Denoiser training on the MI355X (script/train.py of the reference).
 
-``UNetTrainer`` holds UNet1DConditionModel's parameters and ``null_cond_emb``, their AdamW moments and the EMA shadow in one device context
+``UNetTrainer`` holds UNet1DConditionModel's parameters and ``null_cond_emb`` (with ``feature_dim > 0`` also ``audio_proj_layer``, the
+trainable nn.Linear(768, feature_dim) behind the frozen encoder), their AdamW moments and the EMA shadow in one device context
 (include/said_unet_train.h) and runs a whole optimizer step there: add_noise, training-mode forward with ResBlock dropout, the objective of
 ``random_noise_loss``, backward, ``clip_grad_norm_(1.0)``, ``torch.optim.AdamW`` and diffusers' ``EMAModel.step``.  The host draws what the
 reference draws on the host (noise and timesteps on torch's CPU generator, plus one 64-bit dropout seed per step) and writes the per-step
@@ -55,11 +56,15 @@ class UNetLossEpochOutput:
     lr: Optional[float] = None
 
 
-def trainable_shapes() -> "OrderedDict[str, Tuple[int, ...]]":
-    """Names and shapes of the trainable tensors of SAID_UNet1D in state_dict() order: null_cond_emb, then denoiser.model.* as the
-    reference registers them (BasicTransformerBlock: attn1, ff, attn2, norm1..3)."""
-    C, E, X = 192, 768, 768
+def trainable_shapes(feature_dim: int = -1) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Names and shapes of the trainable tensors of SAID_UNet1D(feature_dim=feature_dim) in state_dict() order: null_cond_emb, with
+    feature_dim > 0 audio_proj_layer.weight / .bias, then denoiser.model.* as the reference registers them (BasicTransformerBlock: attn1,
+    ff, attn2, norm1..3).  The context width (null_cond_emb, attn2.to_k / to_v) is feature_dim when > 0, else 768."""
+    C, E = 192, 768
+    X = feature_dim if feature_dim > 0 else 768
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict([("null_cond_emb", (1, 1, X))])
+    if feature_dim > 0:
+        s["audio_proj_layer.weight"], s["audio_proj_layer.bias"] = (X, 768), (X,)
     m = "denoiser.model."
 
     def wb(p, *shape):
@@ -102,20 +107,24 @@ def trainable_shapes() -> "OrderedDict[str, Tuple[int, ...]]":
     return s
 
 
-def unet_init_state_dict() -> "OrderedDict[str, torch.Tensor]":
+def unet_init_state_dict(feature_dim: int = -1) -> "OrderedDict[str, torch.Tensor]":
     """The trainable tensors of a freshly constructed reference denoiser: null_cond_emb = randn(1, 1, 768) (SAID.__init__ draws it before
-    the denoiser is built), then the layers of UNet1DConditionModel(32, 32, 768) built in the reference's construction order with torch's
+    the denoiser is built; with feature_dim = F > 0 it constructs nn.Linear(768, F) first and then draws randn(1, 1, F), and the denoiser
+    has cross_attention_dim = F), then the layers of UNet1DConditionModel(32, 32, 768) built in the reference's construction order with torch's
     default initialisation, so that after torch.manual_seed(s) the draws are the reference's for the same generator state.  The
     zero_module convolutions (ResBlock out conv, SpatialTransformer proj_out, final out conv) are drawn and then zeroed, as there.
     GroupNorm / LayerNorm gains are 1, biases 0.  (The reference's SAID also constructs the Wav2Vec2 encoder before null_cond_emb, which
     consumes generator state; it is frozen and loaded from a checkpoint, so it is not rebuilt here.)"""
-    shapes = trainable_shapes()
+    shapes = trainable_shapes(feature_dim)
     out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
-    out["null_cond_emb"] = torch.randn(1, 1, 768)
+    if feature_dim > 0:
+        proj = nn.Linear(768, feature_dim)
+        out["audio_proj_layer.weight"], out["audio_proj_layer.bias"] = proj.weight.detach().clone(), proj.bias.detach().clone()
+    out["null_cond_emb"] = torch.randn(shapes["null_cond_emb"])
     zeroed = (".out_layers.3.", ".proj_out.", "model.out.2.")
     done = set()
     for k, shp in shapes.items():
-        if k == "null_cond_emb" or k in done:
+        if k in out or k in done:
             continue
         base, leaf = k.rsplit(".", 1)
         if len(shp) == 1 and (base + ".weight") in shapes and len(shapes[base + ".weight"]) == 1:   # a norm
@@ -147,15 +156,20 @@ class UNetTrainer(TrainerBase):
     `state_dict` holds at least the trainable keys (null_cond_emb, denoiser.model.*); every other key (the frozen audio_encoder.*) is kept and
     passed through by state_dict(), so a saved file loads into SAID_UNet1D.  num_warmup_steps is the reference's
     len(train_dataloader) * num_warmup_epochs.  `std` (32,) reweights the losses.
+
+    feature_dim = F > 0 trains SAID_UNet1D(feature_dim=F): audio_proj_layer.* of `state_dict` is the trainable projection's initial value,
+    the context is F wide, and the audio embedding given to step / eval_loss / forward_only stays the encoder's (B, T, 768) output, before
+    the projection (batch_audio_embedding asks the model for that).
     """
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", max_batch: int = 8, max_frames: int = 512, learning_rate: float = 1e-5,
                  num_warmup_steps: float = 0, ema: bool = True, ema_decay: float = 0.9999, std=None, prediction_type: str = "epsilon",
                  dropout: float = 0.1, weight_decay: float = 0.01, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 num_train_timesteps: int = 1000):
+                 num_train_timesteps: int = 1000, feature_dim: int = -1):
         if prediction_type not in PREDICTION_TYPES:
             raise ValueError(f"prediction_type must be one of {sorted(PREDICTION_TYPES)}, got {prediction_type!r}")
-        self.eng = _engine.UNetTrainEngine(torch.device(device), max_batch, max_frames)
+        self.eng = _engine.UNetTrainEngine(torch.device(device), max_batch, max_frames, feature_dim)
+        self.feature_dim = self.eng.feature_dim
         self.device = self.eng.device
         self.max_batch, self.max_frames = int(max_batch), int(max_frames)
         self._set_optimizer(learning_rate, num_warmup_steps, weight_decay, betas, eps, ema, ema_decay)
@@ -164,7 +178,7 @@ class UNetTrainer(TrainerBase):
         self.alphas_cumprod = DDIMScheduler(num_train_timesteps=num_train_timesteps, beta_schedule="squaredcos_cap_v2").alphas_cumprod.float()
         self.eng.set_alphas(self.alphas_cumprod.numpy())
         self.std = parse_std(std)
-        self._shapes = trainable_shapes()
+        self._shapes = trainable_shapes(self.feature_dim)
         self._stored = False
         self.load_state_dict(state_dict)
 
@@ -178,7 +192,7 @@ class UNetTrainer(TrainerBase):
         for name, numel in self.eng.tensors:
             v = state_dict[name].detach().cpu().float()
             if tuple(v.shape) != self._shapes[name]:
-                raise ValueError(f"{name}: shape {tuple(v.shape)}, expected {self._shapes[name]}")
+                raise ValueError(f"{name}: shape {tuple(v.shape)}, expected {self._shapes[name]} (feature_dim={self.feature_dim})")
             self.eng.set_tensor(_engine.UT_STATE, name, v.numpy())
         self._frozen = OrderedDict((k, v.detach().cpu().clone()) for k, v in state_dict.items() if k not in self._shapes)
         self.eng.reset_optimizer()
@@ -189,7 +203,7 @@ class UNetTrainer(TrainerBase):
         construction.  The CLI saves between ema_copy_to() and ema_restore(), as the reference does."""
         out = OrderedDict()
         tr = self.parameters_of(_engine.UT_EMA if (ema and self.ema) else _engine.UT_STATE)
-        out["null_cond_emb"] = tr["null_cond_emb"]
+        out["null_cond_emb"] = tr["null_cond_emb"]   # SAID registers audio_encoder, (audio_proj_layer,) null_cond_emb's parameter first, denoiser
         out.update(self._frozen)
         out.update((k, v) for k, v in tr.items() if k != "null_cond_emb")
         return out
@@ -269,7 +283,7 @@ class UNetTrainer(TrainerBase):
         losses read once at the end; lr is the LR after the last step.  audio_train: the encoder in Wav2Vec2's train mode (the reference
         calls said_model.train() before its epoch); None: as in inference."""
         for data in train_dataloader:
-            self.enqueue_step(data.blendshape_coeffs, data.cond, batch_audio_embedding(model, data, audio_train), weight_vel=weight_vel,
+            self.enqueue_step(data.blendshape_coeffs, data.cond, batch_audio_embedding(model, data, audio_train, self.feature_dim > 0), weight_vel=weight_vel,
                               weight_vertex=weight_vertex, deltas=None if data.blendshape_delta is None else normalize_deltas(data.blendshape_delta))
         return self.epoch_output(False, self.lr_at(self.step_count))
 
@@ -279,21 +293,23 @@ class UNetTrainer(TrainerBase):
         reference does) or, with use_ema, directly on the EMA copy."""
         for _ in range(num_repeat):
             for data in val_dataloader:
-                self.eval_loss(data.blendshape_coeffs, data.cond, batch_audio_embedding(model, data), weight_vel=weight_vel, weight_vertex=weight_vertex,
+                self.eval_loss(data.blendshape_coeffs, data.cond, batch_audio_embedding(model, data, before_proj=self.feature_dim > 0), weight_vel=weight_vel, weight_vertex=weight_vertex,
                                deltas=None if data.blendshape_delta is None else normalize_deltas(data.blendshape_delta), use_ema=use_ema)
         return self.epoch_output(True)
 
 
-def batch_audio_embedding(model, data, audio_train: Optional[AudioTrainConfig] = None) -> torch.Tensor:
-    """(B, T, 768) embedding of a batch's waveforms by the model's frozen audio encoder, as random_noise_loss obtains it.  With
+def batch_audio_embedding(model, data, audio_train: Optional[AudioTrainConfig] = None, before_proj: bool = False) -> torch.Tensor:
+    """(B, T, 768) embedding of a batch's waveforms by the model's frozen audio encoder, as random_noise_loss obtains it.  `before_proj`
+    (the trainers with feature_dim > 0 set it): a model with an audio_proj_layer returns the features before it, still (B, T, 768); the
+    model's own projection is never read.  With
     `audio_train` the encoder runs in Wav2Vec2's train mode, as the reference's does during its training epoch: the span mask, the
     LayerDrop decisions and the dropout seed are drawn here (draw_audio_train), before the step draws its own."""
     wave = model.process_audio(data.waveform).to(next(model.parameters()).device)
     frames = data.blendshape_coeffs.shape[1]
     if audio_train is None:
-        return model.get_audio_embedding(wave, frames).float()
+        return model.get_audio_embedding(wave, frames, before_proj=before_proj).float()
     draws = draw_audio_train(audio_train, wave.shape[0], frames, model.audio_config.num_hidden_layers)
-    return model.get_audio_embedding(wave, frames, train_draws=draws, train_cfg=audio_train).float()
+    return model.get_audio_embedding(wave, frames, train_draws=draws, train_cfg=audio_train, before_proj=before_proj).float()
 
 
 # ---------------------------------------------------------------------------------------------------------------- data sets

@@ -7,7 +7,9 @@ Command-line compatible with the reference (same flags, names and defaults; `--e
   given --seed, the logs of every earlier version) runs it as in inference.  'train' reproduces the reference, which calls
   said_model.train() before its epoch and so feeds the denoiser conditioning that went through Wav2Vec2's SpecAugment time masking,
   dropouts and LayerDrop (wav2vec2-base-960h's published config values).  Validation runs in eval mode either way.
-- --unet_feature_dim > 0 is accepted and refused: the extra audio_proj_layer is not trainable here.
+- --unet_feature_dim F > 0 trains the extra audio_proj_layer = nn.Linear(768, F) inside the HIP step, with the rest: the
+  model built here serves only as the frozen encoder, its own audio_proj_layer is never read.  F must be a multiple of 16, at most 1024:
+  the inference engine, which runs that encoder and later the checkpoint, takes such context widths only.
 - New flags: --seed, --device.  Logs go to stdout and to <output_dir>/log.csv (the reference's TensorBoard keys as columns).
 - <output_dir>/<epoch>.pth is SAID_UNet1D's state dict, written between EMA copy_to and restore as in the reference.
 """
@@ -68,8 +70,8 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if args.unet_feature_dim > 0:
-        raise SystemExit("--unet_feature_dim > 0 (the extra audio_proj_layer) is not supported by the HIP training step")
+    if args.unet_feature_dim > 0 and (args.unet_feature_dim % 16 or args.unet_feature_dim > 1024):
+        raise SystemExit(f"--unet_feature_dim {args.unet_feature_dim}: must be a multiple of 16 up to 1024 (the context widths SAID_UNet1D's engine and the trainer take)")
     if args.seed is not None:
         random.seed(args.seed)
         np.random.seed(args.seed)
@@ -85,7 +87,7 @@ def main(argv=None):
     state = {k: v for k, v in given.items() if k.startswith("audio_encoder.")}
     if not state:
         raise SystemExit(f"{args.audio_encoder_weights} holds no audio_encoder.* tensors")
-    state.update(unet_init_state_dict())
+    state.update(unet_init_state_dict(args.unet_feature_dim))
     model = SAID_UNet1D(feature_dim=args.unet_feature_dim, prediction_type=args.prediction_type)
     model.load_state_dict(state, strict=True)
     model.to(args.device)
@@ -100,7 +102,7 @@ def main(argv=None):
     max_frames = max([c.shape[0] for _, c, _ in train_dataset.data + val_dataset.data])
     trainer = UNetTrainer(state, args.device, max_batch=args.batch_size, max_frames=max_frames, learning_rate=args.learning_rate,
                           num_warmup_steps=len(train_dataloader) * args.num_warmup_epochs, ema=args.ema, ema_decay=args.ema_decay, std=coeffs_std,
-                          prediction_type=args.prediction_type)
+                          prediction_type=args.prediction_type, feature_dim=args.unet_feature_dim)
 
     audio_train = AudioTrainConfig() if args.audio_encoder_mode == "train" else None
     with open(os.path.join(args.output_dir, "log.csv"), "a", newline="") as f:
