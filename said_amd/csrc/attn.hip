@@ -557,14 +557,19 @@ __global__ __launch_bounds__(64 * QT, (QT == 10 ? 5 : (QT == 8 ? 4 : 2))) void b
         }
     }
 }
+// battn_kernel's LDS image of a T-token sequence in bytes: K — the key rows actually used, four 16-byte pieces each — and V^T — 32 rows of 81 pieces.  ONE
+// function for the request of a launch and for the maximum the kernel is configured with (its value at the longest supported sequence): until this function
+// the declared maximum was a constant, 81,920, which is the image of T <= 608 — 512 bytes short of what battn_supports admits (T in (608, 640]: 82,432).
+constexpr int BATTN_MAX_T = 640;
+constexpr int battn_lds_bytes(int T) { return ((((T + 31) / 32) * 32) * 4 + 32 * 81) * 16; }
+static_assert(battn_lds_bytes(BATTN_MAX_T) == 82432 && battn_lds_bytes(608) == 80384, "battn_kernel's LDS image");   // (T > 608: more than half of a CU's 160 KB — one workgroup per CU)
 bool battn_supports(const AttnArgs& a, int head_dim) {
-    return head_dim == 32 && a.T >= 1 && a.T <= 640 && a.pitch >= ((a.T + 31) & ~31) && a.rows >= ((a.T + 31) & ~31) && a.v_bstride <= 0x7fffffffLL && a.o_bstride <= 0x7fffffffLL;
+    return head_dim == 32 && a.T >= 1 && a.T <= BATTN_MAX_T && a.pitch >= ((a.T + 31) & ~31) && a.rows >= ((a.T + 31) & ~31) && a.v_bstride <= 0x7fffffffLL && a.o_bstride <= 0x7fffffffLL;
 }
 // q / k: bf16 [b][2 heads][rows][32] at a.qk, v: bf16 [b][heads * 32][pitch] at a.v (tokens permuted per 16: TGemmArgs::qkv_bf16), o: bf16 token-major
 void launch_battn(const AttnArgs& a, int batch, hipStream_t s) {
-    // K: the key rows actually used; V^T: 81 pieces per row.  T = 600: 80,384 bytes — two workgroups per CU with room to spare (2 x 81,920 is the
-    // whole LDS of a CU to the byte, and measured like ONE workgroup per CU)
-    const int lds_bytes = ((((a.T + 31) / 32) * 32) * 4 + 32 * 81) * 16;
+    // T = 600: 80,384 bytes — two workgroups per CU with room to spare (2 x 81,920 is the whole LDS of a CU to the byte, and measured like ONE workgroup per CU)
+    const int lds_bytes = battn_lds_bytes(a.T);
     dim3 grid((((a.T + 31) / 32) + 7) / 8, a.heads, batch);
     hipLaunchKernelGGL(battn_kernel<8>, grid, dim3(512), lds_bytes, s, reinterpret_cast<const unsigned short*>(a.qk), reinterpret_cast<const unsigned short*>(a.v),
                        reinterpret_cast<unsigned short*>(a.o), (int)a.v_bstride, (int)a.o_bstride, a.pitch, a.T, a.heads, a.rows, a.scale);
@@ -590,7 +595,7 @@ static void configure_attn_modes() {
     configure_attn_one<2, 8, PM>(); configure_attn_one<2, 4, PM>(); configure_attn_one<2, 1, PM>(); configure_attn_one<2, 1, PM, 4>();
 }
 void configure_attn_kernels() {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&battn_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&battn_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, battn_lds_bytes(BATTN_MAX_T));
     configure_attn_modes<0>(); configure_attn_modes<1>(); configure_attn_modes<2>();
     configure_attn_one<1, 8, 3>(); configure_attn_one<1, 4, 3>(); configure_attn_one<1, 1, 3, 4>();
     configure_attn2q_kernel();
