@@ -1,5 +1,5 @@
 """ctypes binding of libsaid_hip.so (C ABI: include/said_hip.h, said_metrics.h, said_optimize.h, said_train.h, said_render.h, said_jpeg.h,
-said_unet_train.h, said_beat.h, said_render_ms.h).
+said_unet_train.h, said_beat.h, said_render_ms.h, said_transfer.h).
 
 There is deliberately no fallback: if the library is missing, cannot be loaded,
 or no gfx950 device is visible, every entry point raises.
@@ -235,6 +235,27 @@ class AudioTrainParams(ctypes.Structure):
                 ("seed", ctypes.c_uint64), ("time_mask_dev", c_void_p), ("skip_layers", ctypes.c_uint32)]
 
 
+# include/said_transfer.h: a group like the renderer's, in a table of its own (tests/test_deform_transfer_cpu.py checks it against its header)
+TRANSFER_EXPORTS = {
+    "said_transfer_create": (c_int, [POINTER(c_void_p), c_int]),
+    "said_transfer_destroy": (c_int, [c_void_p]),
+    "said_transfer_last_error": (c_char_p, [c_void_p]),
+    "said_transfer_set_source": (c_int, [c_void_p, c_int, c_int, c_int, _c_double_p, POINTER(c_int), _c_double_p, c_void_p]),
+    "said_transfer_set_target": (c_int, [c_void_p, c_int, c_int, _c_double_p, POINTER(c_int), c_void_p]),
+    "said_transfer_solve": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), _c_double_p, POINTER(c_int), POINTER(c_int),
+                                    _c_double_p, _c_double_p, _c_double_p, c_double, c_int, c_int, _c_double_p, POINTER(c_int), POINTER(c_int),
+                                    _c_double_p, c_void_p]),
+    "said_transfer_register": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int), _c_double_p, c_double, c_double, c_int, _c_double_p, c_double, c_int,
+                                       _c_double_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), _c_double_p, c_void_p]),
+    "said_transfer_correspond": (c_int, [c_void_p, _c_double_p, c_double, POINTER(c_int), POINTER(c_int), _c_double_p, _c_double_p, c_void_p]),
+    "said_transfer_transfer": (c_int, [c_void_p, c_void_p, c_double, c_int, _c_double_p, POINTER(c_int), POINTER(c_int), _c_double_p, c_void_p]),
+    "said_transfer_mesh": (c_int, [c_void_p, c_int, c_int, _c_double_p, POINTER(c_int), _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                   c_void_p]),
+    "said_transfer_gradients": (c_int, [c_void_p, c_int, c_int, _c_double_p, POINTER(c_int), c_int, _c_double_p, _c_double_p, c_void_p]),
+    "said_transfer_closest": (c_int, [c_void_p, c_int, _c_double_p, _c_double_p, c_int, _c_double_p, _c_double_p, POINTER(c_int), _c_double_p, c_void_p]),
+}
+
+
 # include/said_audio_train.h: the audio encoder's train mode, an entry point of the said_ctx context added without an ABI version bump; a group
 # like the renderer's, in a table of its own (tests/test_audio_train_cpu.py checks it against its header)
 AUDIO_TRAIN_EXPORTS = {
@@ -242,7 +263,8 @@ AUDIO_TRAIN_EXPORTS = {
 }
 _GROUPS = {**LAZY_EXPORTS, "render": ("the renderer", RENDER_EXPORTS), "render_ms": ("multisampled rendering", RENDER_MS_EXPORTS),
            "jpeg": ("the JPEG encoder", JPEG_EXPORTS), "audio_train": ("the audio encoder's train mode", AUDIO_TRAIN_EXPORTS),
-           "unet_train": ("the UNet trainer", UNET_TRAIN_EXPORTS), "beat": ("the beat-consistency passes", BEAT_EXPORTS)}
+           "unet_train": ("the UNet trainer", UNET_TRAIN_EXPORTS), "beat": ("the beat-consistency passes", BEAT_EXPORTS),
+           "transfer": ("deformation transfer", TRANSFER_EXPORTS)}
 _bound = set()   # the groups bound so far
 
 
@@ -1411,3 +1433,139 @@ class BeatEngine(_Context):
     def read_minima(self):
         """Per sequence the indices of its change rate's minima, ascending."""
         return self._lists("said_beat_read_minima", self.seq_off)
+
+
+# ---- deformation transfer (include/said_transfer.h)
+TRANSFER_CONVERGED, TRANSFER_MAX_ITER, TRANSFER_NOT_FINITE = 0, 1, 2   # SAID_TRANSFER_*
+TRANSFER_ROW_SMOOTH, TRANSFER_ROW_IDENTITY, TRANSFER_ROW_CLOSEST, TRANSFER_ROW_UNIT = range(4)
+TRANSFER_RHS_PAIR, TRANSFER_RHS_IDENTITY, TRANSFER_RHS_ANCHOR = range(3)
+_TRANSFER_ARRAYS = ("rowptr", "col", "c0", "c1", "rowclass", "rowaux", "rhsclass", "at_rowptr", "at_col", "at_src")
+
+
+class TransferSystem(ctypes.Structure):
+    """said_transfer_system: the host-built index structure of a system."""
+    _fields_ = [("m", c_int), ("n", c_int), ("nnz", c_int)] + [(name, POINTER(c_int)) for name in _TRANSFER_ARRAYS]
+
+
+def _ip(a: Optional[np.ndarray]):
+    return None if a is None else a.ctypes.data_as(POINTER(c_int))
+
+
+def _odp(a: Optional[np.ndarray]):
+    return None if a is None else _dp(a)
+
+
+def _f64(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+class TransferEngine(_Context):
+    """said_transfer context on one GPU (include/said_transfer.h): the mesh passes, the three stages and the solver
+    alone; float64 host arrays in and out."""
+    prefix, group = "said_transfer", "transfer"
+    cpu_error, cpu_message = NoCpuPathError, "said_amd transfers blendshapes on MI355X only (device={}); there is no CPU path"
+
+    def __init__(self, device: torch.device):
+        super().__init__(device)
+        self._create()
+        self.source = self.target = None   # (V, F, K) and (V, F)
+
+    def _go(self, name: str, *args) -> None:
+        with torch.cuda.device(self.index):
+            self._call(name, *args, _stream())
+
+    @staticmethod
+    def _system(structure: dict):
+        """(TransferSystem, the arrays it points into) of a structure from said_amd.optimize.deformation_transfer."""
+        keep = {name: (None if structure.get(name) is None else _i32(structure[name])) for name in _TRANSFER_ARRAYS}
+        sys_ = TransferSystem(int(structure["m"]), int(structure["n"]), int(keep["col"].shape[0]), *[_ip(keep[name]) for name in _TRANSFER_ARRAYS])
+        return sys_, keep
+
+    def set_source(self, neutral, faces, shapes=None) -> None:
+        v, f = _f64(neutral), _i32(faces)
+        sh = None if shapes is None or len(shapes) == 0 else _f64(shapes)
+        if sh is not None and sh.shape[1:] != v.shape:
+            raise EngineError(f"shapes must be (K, {v.shape[0]}, 3), got {sh.shape}")
+        k = 0 if sh is None else sh.shape[0]
+        self._go("said_transfer_set_source", v.shape[0], f.shape[0], k, _dp(v), _ip(f), _odp(sh))
+        self.source = (v.shape[0], f.shape[0], k)
+
+    def set_target(self, neutral, faces) -> None:
+        v, f = _f64(neutral), _i32(faces)
+        self._go("said_transfer_set_target", v.shape[0], f.shape[0], _dp(v), _ip(f))
+        self.target = (v.shape[0], f.shape[0])
+
+    def solve(self, a_rowptr, a_col, a_val, at_rowptr, at_col, at_val, b, x0=None, tol: float = 1e-10, max_iter: int = 20000, check_every: int = 50):
+        """(x (n, R), status (R), iters (R), relative residual (R)) of min |A x - b| by the device solver; A (m, n) and A' in CSR."""
+        b = _f64(b)
+        m, r = b.shape
+        n = len(at_rowptr) - 1
+        arp, ac, av, trp, tc, tv = _i32(a_rowptr), _i32(a_col), _f64(a_val), _i32(at_rowptr), _i32(at_col), _f64(at_val)
+        if arp.shape[0] != m + 1 or ac.shape != av.shape or tc.shape != tv.shape or ac.shape != tc.shape:
+            raise EngineError("the CSR arrays of A and A' do not fit the right-hand side")
+        x0 = None if x0 is None else _f64(x0)
+        if x0 is not None and x0.shape != (n, r):
+            raise EngineError(f"x0 must be ({n}, {r}), got {x0.shape}")
+        x = np.empty((n, r))
+        st, it, res = np.zeros(r, dtype=np.int32), np.zeros(r, dtype=np.int32), np.zeros(r)
+        self._go("said_transfer_solve", m, n, ac.shape[0], r, _ip(arp), _ip(ac), _dp(av), _ip(trp), _ip(tc), _dp(tv), _dp(b), _odp(x0), float(tol),
+                 int(max_iter), int(check_every), _dp(x), _ip(st), _ip(it), _dp(res))
+        return x, st, it, res
+
+    def register(self, structure: dict, marker_src, marker_pos, w_s: float, w_i: float, schedule, tol: float, max_iter: int):
+        """(x (solves, V_s + F_s, 3), closest (solves, V_s), status, iters, resid (solves, 3))."""
+        sys_, keep = self._system(structure)
+        ms, mp, wc = _i32(marker_src), _f64(marker_pos), _f64(schedule)
+        ns, nv = wc.shape[0], self.source[0]
+        x = np.empty((ns, sys_.n, 3))
+        closest = np.empty((ns, nv), dtype=np.int32)
+        st, it, res = np.zeros((ns, 3), dtype=np.int32), np.zeros((ns, 3), dtype=np.int32), np.zeros((ns, 3))
+        self._go("said_transfer_register", ctypes.byref(sys_), ms.shape[0], _ip(ms), _dp(mp), float(w_s), float(w_i), ns, _dp(wc), float(tol), int(max_iter),
+                 _dp(x), _ip(closest), _ip(st), _ip(it), _dp(res))
+        del keep
+        return x, closest, st, it, res
+
+    def correspond(self, threshold: float, registered=None):
+        """(t2s (F_t), s2t (F_s), their squared centroid distances): -1 where a triangle has no partner within the threshold."""
+        reg = None if registered is None else _f64(registered)
+        if reg is not None and reg.shape != (self.source[0], 3):
+            raise EngineError(f"the registered source must be ({self.source[0]}, 3), got {reg.shape}")
+        t2s, s2t = np.empty(self.target[1], dtype=np.int32), np.empty(self.source[1], dtype=np.int32)
+        dt, ds = np.empty(self.target[1]), np.empty(self.source[1])
+        self._go("said_transfer_correspond", _odp(reg), float(threshold), _ip(t2s), _ip(s2t), _dp(dt), _dp(ds))
+        return t2s, s2t, dt, ds
+
+    def transfer(self, structure: dict, tol: float, max_iter: int):
+        """(residuals (K, V_t, 3), status, iters, resid (3 K))."""
+        sys_, keep = self._system(structure)
+        k, nv = self.source[2], self.target[0]
+        out = np.empty((k, nv, 3))
+        st, it, res = np.zeros(3 * k, dtype=np.int32), np.zeros(3 * k, dtype=np.int32), np.zeros(3 * k)
+        self._go("said_transfer_transfer", ctypes.byref(sys_), float(tol), int(max_iter), _dp(out), _ip(st), _ip(it), _dp(res))
+        del keep
+        return out, st, it, res
+
+    def mesh(self, verts, faces):
+        """{"w": (F, 3, 3) V^-T, "gc": (F, 3, 4), "fn": (F, 3), "centroid": (F, 3), "vn": (V, 3)} of a mesh."""
+        v, f = _f64(verts), _i32(faces)
+        nv, nf = v.shape[0], f.shape[0]
+        out = {"w": np.empty((nf, 3, 3)), "gc": np.empty((nf, 3, 4)), "fn": np.empty((nf, 3)), "centroid": np.empty((nf, 3)), "vn": np.empty((nv, 3))}
+        self._go("said_transfer_mesh", nv, nf, _dp(v), _ip(f), *[_dp(out[name]) for name in ("w", "gc", "fn", "centroid", "vn")])
+        return out
+
+    def gradients(self, ref, faces, deformed) -> np.ndarray:
+        """(K, F, 3, 3) deformation gradients of deformed (K, V, 3) against ref."""
+        v, f, d = _f64(ref), _i32(faces), _f64(deformed)
+        if d.ndim != 3 or d.shape[1:] != v.shape:
+            raise EngineError(f"deformed must be (K, {v.shape[0]}, 3), got {d.shape}")
+        q = np.empty((d.shape[0], f.shape[0], 3, 3))
+        self._go("said_transfer_gradients", v.shape[0], f.shape[0], _dp(v), _ip(f), d.shape[0], _dp(d), _dp(q))
+        return q
+
+    def closest(self, qpos, qnrm, tpos, tnrm):
+        """(index per query, squared distance): the nearest target whose normal has a positive dot product with the query's (both None: the nearest)."""
+        qp, tp = _f64(qpos), _f64(tpos)
+        qn, tn = (None, None) if qnrm is None else (_f64(qnrm), _f64(tnrm))
+        idx, d2 = np.empty(qp.shape[0], dtype=np.int32), np.empty(qp.shape[0])
+        self._go("said_transfer_closest", qp.shape[0], _dp(qp), _odp(qn), tp.shape[0], _dp(tp), _odp(tn), _ip(idx), _dp(d2))
+        return idx, d2

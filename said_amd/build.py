@@ -20,7 +20,7 @@ LIB = os.path.join(LIBDIR, "libsaid_hip.so")
 # give a fat binary from which the runtime picks the one matching the device).
 ARCHS = os.environ.get("SAID_OFFLOAD_ARCH", "gfx950").split(",")
 SOURCES = ["gemm.hip", "gemm_lds.hip", "attn.hip", "attn2q.hip", "audio_train.hip", "misc.hip", "out_sched.hip", "conv_in.hip", "tgemm.hip", "fgemm.hip", "xgemm.hip", "tm_kernels.hip", "rgemm.hip", "stchain.hip",
-           "vae_dec.hip", "metrics.hip", "blendshape_qp.hip", "vae_train.hip", "unet_train.hip", "train_opt.hip", "render.hip", "jpeg.hip", "beat.hip", "engine.cpp", "weights.cpp", "unet_sched.cpp", "audio_enc.cpp", "vae.cpp", "vae_trainer.cpp", "unet_trainer.cpp", "renderer.cpp", "jpeg_enc.cpp", "beat_ctx.cpp"]
+           "vae_dec.hip", "metrics.hip", "blendshape_qp.hip", "vae_train.hip", "unet_train.hip", "train_opt.hip", "render.hip", "jpeg.hip", "beat.hip", "deform_transfer.hip", "engine.cpp", "weights.cpp", "unet_sched.cpp", "audio_enc.cpp", "vae.cpp", "vae_trainer.cpp", "unet_trainer.cpp", "renderer.cpp", "jpeg_enc.cpp", "beat_ctx.cpp", "deform_transfer_ctx.cpp"]
 FLAGS = [*[f"--offload-arch={a}" for a in ARCHS], "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result"]
 # Round 5 (profiles/r05a_pk_fma_hazard.txt): on gfx950 a packed-fp32 VALU instruction (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) whose LOW half
 # reads the HIGH register of an operand pair (an op_sel bit set) can read that operand as 0 in lanes 48-63 while ANOTHER wave of the SIMD issues fp16 / bf16
@@ -72,7 +72,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     # every header any source may include: a change to one of them rebuilds all objects
     headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
-    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("said_hip.h", "said_audio_train.h", "said_metrics.h", "said_optimize.h", "said_train.h", "said_unet_train.h", "said_render.h", "said_render_ms.h", "said_jpeg.h", "said_beat.h")]
+    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("said_hip.h", "said_audio_train.h", "said_metrics.h", "said_optimize.h", "said_train.h", "said_unet_train.h", "said_render.h", "said_render_ms.h", "said_jpeg.h", "said_beat.h", "said_transfer.h")]
     objs, jobs = [], []
     for src in SOURCES:
         sp = os.path.join(CSRC, src)

@@ -35,3 +35,20 @@ def save_blendshape_coeffs_image(coeffs: np.ndarray, output_path: str) -> None:
     from PIL import Image
 
     Image.fromarray((255 * coeffs.transpose()).round()).convert("L").save(output_path)
+
+
+def load_blendshape_deltas(blendshape_deltas_path: str):
+    """{person id: {blendshape name: (V, 3) array}} from the residuals pickle (reference: said/util/blendshape.py:load_blendshape_deltas)."""
+    import pickle
+
+    with open(blendshape_deltas_path, "rb") as f:
+        return pickle.load(f)
+
+
+def save_blendshape_deltas(deltas, blendshape_deltas_path: str) -> None:
+    """The pickle load_blendshape_deltas reads: plain dictionaries of float64 arrays."""
+    import pickle
+
+    plain = {str(pid): {str(name): np.asarray(d, dtype=np.float64) for name, d in shapes.items()} for pid, shapes in deltas.items()}
+    with open(blendshape_deltas_path, "wb") as f:
+        pickle.dump(plain, f)

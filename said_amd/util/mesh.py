@@ -260,3 +260,18 @@ def save_mesh(mesh, path: str) -> None:
             out.write(head.encode("ascii") + v.astype("<f8").tobytes() + rec.tobytes())
     else:
         raise MeshFormatError(f"{path}: unsupported mesh format {ext!r} (OBJ and PLY only)")
+
+
+def get_submesh(vertices, faces, indices) -> Mesh:
+    """The part of a mesh on the vertices ``indices`` (reference: said/util/mesh.py:get_submesh): vertex i of the result is vertex
+    ``indices[i]``; a face is kept, in its place in the order, when all three of its vertices are among them (the first occurrence of an
+    index that is listed twice), and is renumbered."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= len(v)):
+        raise MeshFormatError(f"a sub-mesh index lies outside the mesh's {len(v)} vertices")
+    new = np.full(len(v), -1, dtype=np.int64)
+    new[idx[::-1]] = np.arange(len(idx))[::-1]   # the first occurrence wins
+    sub = new[f] if f.size else f
+    return Mesh(v[idx], sub[(sub >= 0).all(axis=1)] if f.size else f)
