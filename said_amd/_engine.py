@@ -1,5 +1,13 @@
-"""ctypes binding of libsaid_hip.so (C ABI: include/said_hip.h, said_metrics.h, said_optimize.h, said_train.h, said_render.h, said_jpeg.h,
-said_unet_train.h, said_beat.h, said_render_ms.h, said_transfer.h).
+"""ctypes binding of libsaid_hip.so.
+
+`ABI` below is the one description of the library's C surface: group -> Group(headers, feature, table).  The "core" group (include/said_hip.h
+and csrc/said_hip_debug.h) is bound when the library is loaded and guarded by said_abi_version; every other group is bound on first use
+(load_library(group)) and lies outside the ABI version, so a library built before a group still loads and only what uses the group raises
+"rebuild".  tests/test_host_cpu.py checks every group against its headers: names, parameter counts, kinds and sizes.
+
+To add a context: declare its entry points in a header of their own, add one Group to `ABI`, and write one subclass of _Context that names
+its prefix and group.  Host arrays go through _f32 / _f64 / _i32 / _i64 and the pointer helpers _fp / _dp / _ip / _lp / _vp, device tensors
+through _dev and _ptr, and calls through _Context._go (entries that end in a stream) or _Context._call (the others).
 
 There is deliberately no fallback: if the library is missing, cannot be loaded,
 or no gfx950 device is visible, every entry point raises.
@@ -9,7 +17,7 @@ from __future__ import annotations
 import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_void_p
-from typing import Dict, Optional, Sequence
+from typing import Dict, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -33,200 +41,46 @@ class NoCpuPathError(EngineError, NotImplementedError):
     """A model method called on a CPU-resident model: said_amd computes on the MI355X only."""
 
 
+_c_ll, _c_ull = ctypes.c_longlong, ctypes.c_ulonglong
+_c_float_p, _c_double_p, _c_int_p, _c_ll_p, _c_void_pp = POINTER(c_float), POINTER(c_double), POINTER(c_int), POINTER(_c_ll), POINTER(c_void_p)
+
+# ---- the constants and structs of the headers
+METRICS_DIM, METRICS_MAX_K = 64, 8     # include/said_metrics.h
+W_UNIT, W_LABELS, W_RESP = 0, 1, 2   # SAID_METRICS_W_*
+OPTIMIZE_MAX_K = 64                    # include/said_optimize.h
+OPT_CONVERGED, OPT_MAX_ITER, OPT_NOT_FINITE = 0, 1, 2   # SAID_OPTIMIZE_*
+# SAID_TRAIN_* of include/said_train.h
+TRAIN_NSCAL, TRAIN_NACC, TRAIN_ITEM = 16, 8, 4
+(TRAIN_S_LR, TRAIN_S_WD_FACTOR, TRAIN_S_STEP_SIZE, TRAIN_S_BC2_SQRT, TRAIN_S_EMA_OMD, TRAIN_S_BETA, TRAIN_S_WVEL, TRAIN_S_OMB1, TRAIN_S_B2,
+ TRAIN_S_OMB2, TRAIN_S_EPS, TRAIN_S_USE_EMA) = range(12)
+TRAIN_STATE, TRAIN_EMA, TRAIN_GRAD, TRAIN_EXP_AVG, TRAIN_EXP_AVG_SQ = range(5)
+TRAIN_OK, TRAIN_NOT_FINITE = 0, 1
+TRAIN_SET_TRAIN, TRAIN_SET_VAL = 0, 1
+UT_NSCAL, UT_NACC, UT_NUM_TENSORS = 16, 8, 161   # SAID_UT_* of include/said_unet_train.h
+(UT_S_LR, UT_S_WD_FACTOR, UT_S_STEP_SIZE, UT_S_BC2_SQRT, UT_S_EMA_OMD, UT_S_WVEL, UT_S_WVERTEX, UT_S_OMB1, UT_S_B2, UT_S_OMB2, UT_S_EPS,
+ UT_S_USE_EMA, UT_S_PRED_TYPE, UT_S_DROPOUT) = range(14)
+UT_STATE, UT_EMA, UT_GRAD, UT_EXP_AVG, UT_EXP_AVG_SQ, UT_STASH = range(6)
+RENDER_MAX_K, RENDER_MAX_LIGHTS, RENDER_LUT = 64, 4, 256   # SAID_RENDER_* of include/said_render.h
+JPEG_OVERFLOW = 1   # SAID_JPEG_OVERFLOW
+BEAT_N_FFT, BEAT_HOP, BEAT_N_MELS = 2048, 512, 128   # SAID_BEAT_* of include/said_beat.h
+TRANSFER_CONVERGED, TRANSFER_MAX_ITER, TRANSFER_NOT_FINITE = 0, 1, 2   # SAID_TRANSFER_* of include/said_transfer.h
+TRANSFER_ROW_SMOOTH, TRANSFER_ROW_IDENTITY, TRANSFER_ROW_CLOSEST, TRANSFER_ROW_UNIT = range(4)
+TRANSFER_RHS_PAIR, TRANSFER_RHS_IDENTITY, TRANSFER_RHS_ANCHOR = range(3)
+_TRANSFER_ARRAYS = ("rowptr", "col", "c0", "c1", "rowclass", "rowaux", "rhsclass", "at_rowptr", "at_col", "at_src")
+
+
 class LoopParams(ctypes.Structure):
+    """said_loop_params."""
     _fields_ = [
         ("batch", c_int), ("frames", c_int), ("num_steps", c_int), ("prediction_type", c_int),
         ("guidance_scale", c_float), ("guidance_rescale", c_float), ("latent_scale", c_float),
         ("use_step_noise", c_int), ("use_mask", c_int), ("save_intermediate", c_int),
-        ("timesteps_host", POINTER(c_int64)), ("coef_host", POINTER(c_float)),
+        ("timesteps_host", _c_ll_p), ("coef_host", _c_float_p),
         ("context_dev", c_void_p), ("latents_dev", c_void_p), ("step_noise_dev", c_void_p),
         ("init_latents_dev", c_void_p), ("edit_noise_dev", c_void_p), ("mask_dev", c_void_p),
         ("intermediates_dev", c_void_p), ("result_dev", c_void_p), ("noise_seed", ctypes.c_uint64),
         ("noise_batch_offset", c_int), ("concurrent", c_int),
     ]
-
-
-EXPORTS = {
-    "said_abi_version": (c_int, []),
-    "said_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int]),
-    "said_destroy": (c_int, [c_void_p]),
-    "said_reserve": (c_int, [c_void_p, c_int, c_int]),
-    "said_capacity": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
-    "said_clone": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int]),
-    "said_stream": (c_void_p, [c_void_p]),
-    "said_loop_prepare": (c_int, [c_void_p, POINTER(LoopParams), c_void_p]),
-    "said_last_error": (c_char_p, [c_void_p]),
-    "said_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
-    "said_finalize_weights": (c_int, [c_void_p, c_void_p]),
-    "said_set_timestep_freqs": (c_int, [c_void_p, c_void_p, c_int]),
-    "said_audio_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, POINTER(c_int), c_void_p]),
-    "said_unet_forward": (c_int, [c_void_p, c_void_p, POINTER(c_int64), c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "said_denoise_loop": (c_int, [c_void_p, POINTER(LoopParams), c_void_p]),
-    "said_ddim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, POINTER(c_float), c_int, c_void_p,
-                               c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "said_solver_step": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, POINTER(c_float), c_int, c_void_p, c_void_p,
-                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "said_axpby": (c_int, [c_void_p, POINTER(c_float), c_void_p, POINTER(c_float), c_void_p, c_void_p, c_int, c_int64, c_void_p]),
-    "said_graph_num_nodes": (c_int, [c_void_p]),
-    "said_loop_progress": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
-    "said_loop_progress_reset": (c_int, [c_void_p]),
-    "said_set_precision": (c_int, [c_void_p, c_int]),
-    "said_get_precision": (c_int, [c_void_p]),
-    "said_effective_precision": (c_int, [c_void_p]),
-    "said_precision_note": (c_char_p, [c_void_p]),
-    "said_numeric_status": (c_int, [c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
-    "said_profile_unet": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, POINTER(c_int), c_void_p]),
-    "said_philox_normal": (c_int, [c_void_p, ctypes.c_uint64, c_int, c_int, c_int64, c_void_p, c_void_p]),
-    "said_debug_option": (c_int, [c_void_p, c_char_p, ctypes.c_longlong]),
-    "said_debug_get": (ctypes.c_longlong, [c_void_p, c_char_p]),
-    "said_debug_stop_after": (c_int, [c_void_p, c_int]),
-    "said_debug_clocks": (c_int, [c_void_p, c_int, c_void_p]),
-    "said_debug_read": (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),
-    "said_debug_ws_count": (c_int, [c_void_p]),
-    "said_debug_ws_info": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(ctypes.c_longlong), POINTER(c_char_p)]),
-    "said_debug_ws_fill": (c_int, [c_void_p, c_int]),
-    "said_debug_ws_copy": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p]),
-    "said_debug_audio_copy": (c_int, [c_void_p, c_char_p, c_void_p, ctypes.c_longlong, c_void_p]),
-    "said_unet_algorithmic_bytes": (c_double, [c_int, c_int, c_int]),
-    "said_unet_algorithmic_flops": (c_double, [c_int, c_int]),
-    "said_vae_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int]),
-    "said_vae_destroy": (c_int, [c_void_p]),
-    "said_vae_last_error": (c_char_p, [c_void_p]),
-    "said_vae_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
-    "said_vae_finalize_weights": (c_int, [c_void_p]),
-    "said_vae_encode": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p]),
-    "said_vae_has_decoder": (c_int, [c_void_p]),
-    "said_vae_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-}
-_c_float_p, _c_double_p, _c_ll_p = POINTER(c_float), POINTER(c_double), POINTER(ctypes.c_longlong)
-# Groups bound on first use (load_library(group)), outside the ABI version of said_hip.h: a library built before a group still loads, and only
-# what uses the group raises "rebuild".  group: (what a library without it predates, its table).
-LAZY_EXPORTS = {
-    # said_hip.h entries added without an ABI version bump: part of EXPORTS, but not bound at load
-    "vae_decoder": ("the VAE decoder", {n: EXPORTS[n] for n in ("said_vae_has_decoder", "said_vae_decode")}),
-    "metrics": ("the metrics passes", {   # include/said_metrics.h
-        "said_metrics_create": (c_int, [POINTER(c_void_p), c_int, ctypes.c_longlong]),
-        "said_metrics_destroy": (c_int, [c_void_p]),
-        "said_metrics_last_error": (c_char_p, [c_void_p]),
-        "said_metrics_max_points": (ctypes.c_longlong, [c_void_p]),
-        "said_metrics_weighted_sums": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, _c_double_p, _c_double_p, c_void_p]),
-        "said_metrics_weighted_scatter": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, _c_double_p, _c_double_p, c_void_p]),
-        "said_metrics_gmm_estep": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-                                           _c_double_p, c_void_p, c_void_p, c_void_p]),
-        "said_metrics_kmeans_assign": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, _c_double_p, c_int, _c_ll_p, _c_double_p, c_void_p]),
-        "said_metrics_kmeans_read": (c_int, [c_void_p, ctypes.c_longlong, POINTER(c_int), _c_double_p, c_void_p]),
-        "said_metrics_kmeans_set_labels": (c_int, [c_void_p, ctypes.c_longlong, c_int, POINTER(c_int), c_void_p]),
-        "said_metrics_kmeanspp_first": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_longlong, _c_double_p, c_void_p]),
-        "said_metrics_kmeanspp_step": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, _c_double_p, c_int, _c_ll_p, _c_double_p, c_void_p]),
-    }),
-    "optimize": ("the blendshape fit", {   # include/said_optimize.h
-        "said_optimize_create": (c_int, [POINTER(c_void_p), c_int]),
-        "said_optimize_destroy": (c_int, [c_void_p]),
-        "said_optimize_last_error": (c_char_p, [c_void_p]),
-        "said_optimize_set_bases": (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong, _c_double_p, _c_double_p, _c_double_p, c_void_p]),
-        "said_optimize_rhs": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
-        "said_optimize_solve": (c_int, [c_void_p, c_int, _c_ll_p, POINTER(c_int), c_void_p, c_double, c_int, c_int, c_double, c_void_p, c_void_p,
-                                        POINTER(c_int), POINTER(c_int), _c_double_p, c_void_p]),
-    }),
-    "train": ("the BCVAE trainer", {   # include/said_train.h
-        "said_train_create": (c_int, [POINTER(c_void_p), c_int, c_int]),
-        "said_train_destroy": (c_int, [c_void_p]),
-        "said_train_last_error": (c_char_p, [c_void_p]),
-        "said_train_tensor_name": (c_char_p, [c_int]),
-        "said_train_tensor_numel": (ctypes.c_longlong, [c_int]),
-        "said_train_tensor_is_counter": (c_int, [c_int]),
-        "said_train_set_tensor": (c_int, [c_void_p, c_int, c_char_p, c_void_p, ctypes.c_longlong]),
-        "said_train_get_tensor": (c_int, [c_void_p, c_int, c_char_p, c_void_p, ctypes.c_longlong]),
-        "said_train_reset_optimizer": (c_int, [c_void_p]),
-        "said_train_set_data": (c_int, [c_void_p, c_int, _c_float_p, ctypes.c_longlong, _c_ll_p, POINTER(c_int), c_int, POINTER(c_int)]),
-        "said_train_gather": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), _c_float_p]),
-        "said_train_step": (c_int, [c_void_p, c_int, POINTER(c_int), _c_float_p, _c_float_p, _c_float_p, c_int]),
-        "said_train_apply_update": (c_int, [c_void_p, _c_float_p]),
-        "said_train_eval_loss": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), _c_float_p, _c_float_p, _c_float_p, c_int]),
-        "said_train_read_losses": (c_int, [c_void_p, c_int, _c_double_p, POINTER(c_int), c_int]),
-        "said_train_last_losses": (c_int, [c_void_p, _c_float_p]),
-        "said_train_bn_stats": (c_int, [c_void_p, c_int, _c_float_p]),
-        "said_train_graph_count": (c_int, [c_void_p]),
-    }),
-}
-# include/said_render.h: a group like those of LAZY_EXPORTS, kept in a table of its own (tests/test_render_cpu.py checks it against its header)
-RENDER_EXPORTS = {
-    "said_render_create": (c_int, [POINTER(c_void_p), c_int]),
-    "said_render_destroy": (c_int, [c_void_p]),
-    "said_render_last_error": (c_char_p, [c_void_p]),
-    "said_render_set_mesh": (c_int, [c_void_p, c_int, c_int, c_int, _c_double_p, POINTER(c_int), _c_double_p, c_void_p]),
-    "said_render_set_scene": (c_int, [c_void_p, c_void_p]),
-    "said_render_set_colormap": (c_int, [c_void_p, _c_float_p, c_void_p]),
-    "said_render_render": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_float, _c_double_p, _c_double_p, c_void_p, c_void_p,
-                                   c_void_p]),
-    "said_render_read_vertices": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
-    "said_render_read_normals": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
-    "said_render_read_colors": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
-}
-# include/said_render_ms.h: the renderer's multisampled entry, a group of its own (tests/test_render_ms_cpu.py checks it against its header)
-RENDER_MS_EXPORTS = {
-    "said_render_render_ms": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_float, _c_double_p, _c_double_p, c_void_p, c_void_p,
-                                      c_void_p, c_void_p]),
-}
-# include/said_jpeg.h: a group like the renderer's, in a table of its own (tests/test_jpeg_ref_cpu.py checks it against its header)
-JPEG_EXPORTS = {
-    "said_jpeg_create": (c_int, [POINTER(c_void_p), c_int]),
-    "said_jpeg_destroy": (c_int, [c_void_p]),
-    "said_jpeg_last_error": (c_char_p, [c_void_p]),
-    "said_jpeg_configure": (c_int, [c_void_p, c_int, c_int, c_int]),
-    "said_jpeg_header": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, _c_ll_p]),
-    "said_jpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_longlong, c_void_p, _c_ll_p, c_void_p]),
-    "said_jpeg_read_coefficients": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
-}
-# include/said_unet_train.h: a group like those of LAZY_EXPORTS, kept in a table of its own (tests/test_unet_train_cpu.py checks it against its header)
-_c_ull = ctypes.c_ulonglong
-UNET_TRAIN_EXPORTS = {
-    "said_unet_train_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int]),
-    "said_unet_train_create_dim": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int]),
-    "said_unet_train_destroy": (c_int, [c_void_p]),
-    "said_unet_train_last_error": (c_char_p, [c_void_p]),
-    "said_unet_train_tensor_name": (c_char_p, [c_int]),
-    "said_unet_train_tensor_numel": (ctypes.c_longlong, [c_int]),
-    "said_unet_train_table_size": (c_int, [c_int]),
-    "said_unet_train_table_name": (c_char_p, [c_int, c_int]),
-    "said_unet_train_table_numel": (ctypes.c_longlong, [c_int, c_int]),
-    "said_unet_train_num_tensors": (c_int, [c_void_p]),
-    "said_unet_train_context_tensor_name": (c_char_p, [c_void_p, c_int]),
-    "said_unet_train_context_tensor_numel": (ctypes.c_longlong, [c_void_p, c_int]),
-    "said_unet_train_feature_dim": (c_int, [c_void_p]),
-    "said_unet_train_set_tensor": (c_int, [c_void_p, c_int, c_char_p, _c_float_p, ctypes.c_longlong]),
-    "said_unet_train_get_tensor": (c_int, [c_void_p, c_int, c_char_p, _c_float_p, ctypes.c_longlong]),
-    "said_unet_train_reset_optimizer": (c_int, [c_void_p]),
-    "said_unet_train_copy": (c_int, [c_void_p, c_int, c_int]),
-    "said_unet_train_set_alphas": (c_int, [c_void_p, _c_float_p, c_int]),
-    "said_unet_train_step": (c_int, [c_void_p, c_int, c_int, _c_float_p, _c_float_p, _c_ll_p, POINTER(c_int), c_void_p, c_int, _c_ull, _c_float_p,
-                                     _c_float_p, _c_float_p, c_int]),
-    "said_unet_train_eval_loss": (c_int, [c_void_p, c_int, c_int, _c_float_p, _c_float_p, _c_ll_p, POINTER(c_int), c_void_p, c_int, _c_float_p,
-                                          _c_float_p, _c_float_p, c_int, c_int]),
-    "said_unet_train_forward_only": (c_int, [c_void_p, c_int, c_int, _c_float_p, _c_ll_p, POINTER(c_int), c_void_p, c_int, c_int, _c_float_p]),
-    "said_unet_train_apply_update": (c_int, [c_void_p, _c_float_p]),
-    "said_unet_train_read_losses": (c_int, [c_void_p, c_int, _c_double_p, POINTER(c_int), c_int]),
-    "said_unet_train_last_losses": (c_int, [c_void_p, _c_float_p]),
-}
-# include/said_beat.h: a group like the renderer's, in a table of its own (tests/test_beat_cpu.py checks it against its header)
-_c_int_p = POINTER(c_int)
-BEAT_EXPORTS = {
-    "said_beat_create": (c_int, [POINTER(c_void_p), c_int]),
-    "said_beat_destroy": (c_int, [c_void_p]),
-    "said_beat_last_error": (c_char_p, [c_void_p]),
-    "said_beat_set_sampling_rate": (c_int, [c_void_p, c_int, _c_int_p]),
-    "said_beat_clips": (c_int, [c_void_p, c_void_p, c_int, _c_ll_p, c_void_p]),
-    "said_beat_coeffs": (c_int, [c_void_p, c_void_p, c_int, _c_ll_p, c_int, c_double, c_void_p]),
-    "said_beat_score": (c_int, [c_void_p, _c_int_p, c_double, c_double, _c_double_p, c_void_p]),
-    "said_beat_set_deltas": (c_int, [c_void_p, c_int, c_int, c_int, _c_double_p, c_void_p]),
-    "said_beat_vertex_error": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, _c_ll_p, _c_ll_p, _c_int_p, _c_int_p, _c_double_p, c_void_p]),
-    "said_beat_read_mel": (c_int, [c_void_p, _c_double_p, c_void_p]),
-    "said_beat_read_envelope": (c_int, [c_void_p, _c_double_p, c_void_p]),
-    "said_beat_read_onsets": (c_int, [c_void_p, _c_int_p, _c_int_p, c_void_p]),
-    "said_beat_read_rates": (c_int, [c_void_p, _c_double_p, c_void_p]),
-    "said_beat_read_minima": (c_int, [c_void_p, _c_int_p, _c_int_p, c_void_p]),
-}
 
 
 class AudioTrainParams(ctypes.Structure):
@@ -235,36 +89,225 @@ class AudioTrainParams(ctypes.Structure):
                 ("seed", ctypes.c_uint64), ("time_mask_dev", c_void_p), ("skip_layers", ctypes.c_uint32)]
 
 
-# include/said_transfer.h: a group like the renderer's, in a table of its own (tests/test_deform_transfer_cpu.py checks it against its header)
-TRANSFER_EXPORTS = {
-    "said_transfer_create": (c_int, [POINTER(c_void_p), c_int]),
-    "said_transfer_destroy": (c_int, [c_void_p]),
-    "said_transfer_last_error": (c_char_p, [c_void_p]),
-    "said_transfer_set_source": (c_int, [c_void_p, c_int, c_int, c_int, _c_double_p, POINTER(c_int), _c_double_p, c_void_p]),
-    "said_transfer_set_target": (c_int, [c_void_p, c_int, c_int, _c_double_p, POINTER(c_int), c_void_p]),
-    "said_transfer_solve": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), _c_double_p, POINTER(c_int), POINTER(c_int),
-                                    _c_double_p, _c_double_p, _c_double_p, c_double, c_int, c_int, _c_double_p, POINTER(c_int), POINTER(c_int),
-                                    _c_double_p, c_void_p]),
-    "said_transfer_register": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int), _c_double_p, c_double, c_double, c_int, _c_double_p, c_double, c_int,
-                                       _c_double_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), _c_double_p, c_void_p]),
-    "said_transfer_correspond": (c_int, [c_void_p, _c_double_p, c_double, POINTER(c_int), POINTER(c_int), _c_double_p, _c_double_p, c_void_p]),
-    "said_transfer_transfer": (c_int, [c_void_p, c_void_p, c_double, c_int, _c_double_p, POINTER(c_int), POINTER(c_int), _c_double_p, c_void_p]),
-    "said_transfer_mesh": (c_int, [c_void_p, c_int, c_int, _c_double_p, POINTER(c_int), _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-                                   c_void_p]),
-    "said_transfer_gradients": (c_int, [c_void_p, c_int, c_int, _c_double_p, POINTER(c_int), c_int, _c_double_p, _c_double_p, c_void_p]),
-    "said_transfer_closest": (c_int, [c_void_p, c_int, _c_double_p, _c_double_p, c_int, _c_double_p, _c_double_p, POINTER(c_int), _c_double_p, c_void_p]),
-}
+class RenderScene(ctypes.Structure):
+    """said_render_scene."""
+    _fields_ = [
+        ("width", c_int), ("height", c_int),
+        ("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float), ("znear", c_float), ("zfar", c_float),
+        ("cam_pos", c_float * 3), ("n_lights", c_int),
+        ("light_pos", (c_float * 3) * RENDER_MAX_LIGHTS), ("light_intensity", c_float * RENDER_MAX_LIGHTS),
+        ("ambient", c_float), ("base_color", c_float * 3),
+        ("metallic", c_float), ("roughness", c_float), ("vc_metallic", c_float), ("vc_roughness", c_float),
+    ]
 
 
-# include/said_audio_train.h: the audio encoder's train mode, an entry point of the said_ctx context added without an ABI version bump; a group
-# like the renderer's, in a table of its own (tests/test_audio_train_cpu.py checks it against its header)
-AUDIO_TRAIN_EXPORTS = {
-    "said_audio_encode_train": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(AudioTrainParams), c_void_p, POINTER(c_int), c_void_p]),
+class TransferSystem(ctypes.Structure):
+    """said_transfer_system: the host-built index structure of a system."""
+    _fields_ = [("m", c_int), ("n", c_int), ("nnz", c_int)] + [(name, _c_int_p) for name in _TRANSFER_ARRAYS]
+
+
+class Group(NamedTuple):
+    """The entry points that are bound together."""
+    headers: tuple   # the headers that declare them, relative to the repository root
+    feature: str     # what a library without them predates, for the "rebuild" error
+    table: dict      # {name: (restype, argtypes)}
+    late: dict = {}  # {group: (feature, names)}: entries of `table` that these headers declare but that are bound as a group of their own
+
+
+ABI = {
+    "core": Group(("include/said_hip.h", "said_amd/csrc/said_hip_debug.h"), f"ABI version {ABI_VERSION}", {
+        "said_abi_version": (c_int, []),
+        "said_create": (c_int, [_c_void_pp, c_int, c_int, c_int, c_int, c_int]),
+        "said_destroy": (c_int, [c_void_p]),
+        "said_reserve": (c_int, [c_void_p, c_int, c_int]),
+        "said_capacity": (c_int, [c_void_p, _c_int_p, _c_int_p]),
+        "said_clone": (c_int, [c_void_p, _c_void_pp, c_int, c_int]),
+        "said_stream": (c_void_p, [c_void_p]),
+        "said_loop_prepare": (c_int, [c_void_p, POINTER(LoopParams), c_void_p]),
+        "said_last_error": (c_char_p, [c_void_p]),
+        "said_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, _c_ll_p, c_int]),
+        "said_finalize_weights": (c_int, [c_void_p, c_void_p]),
+        "said_set_timestep_freqs": (c_int, [c_void_p, c_void_p, c_int]),
+        "said_audio_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, _c_int_p, c_void_p]),
+        "said_unet_forward": (c_int, [c_void_p, c_void_p, _c_ll_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+        "said_denoise_loop": (c_int, [c_void_p, POINTER(LoopParams), c_void_p]),
+        "said_ddim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, _c_float_p, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+        "said_solver_step": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, _c_float_p, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+        "said_axpby": (c_int, [c_void_p, _c_float_p, c_void_p, _c_float_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+        "said_graph_num_nodes": (c_int, [c_void_p]),
+        "said_loop_progress": (c_int, [c_void_p, _c_int_p]),
+        "said_loop_progress_reset": (c_int, [c_void_p]),
+        "said_set_precision": (c_int, [c_void_p, c_int]),
+        "said_get_precision": (c_int, [c_void_p]),
+        "said_effective_precision": (c_int, [c_void_p]),
+        "said_precision_note": (c_char_p, [c_void_p]),
+        "said_numeric_status": (c_int, [c_void_p, c_void_p, _c_int_p, _c_int_p]),
+        "said_profile_unet": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, _c_int_p, c_void_p]),
+        "said_philox_normal": (c_int, [c_void_p, ctypes.c_uint64, c_int, c_int, c_int64, c_void_p, c_void_p]),
+        "said_debug_option": (c_int, [c_void_p, c_char_p, _c_ll]),
+        "said_debug_get": (_c_ll, [c_void_p, c_char_p]),
+        "said_debug_stop_after": (c_int, [c_void_p, c_int]),
+        "said_debug_clocks": (c_int, [c_void_p, c_int, c_void_p]),
+        "said_debug_read": (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),
+        "said_debug_ws_count": (c_int, [c_void_p]),
+        "said_debug_ws_info": (c_int, [c_void_p, c_int, _c_void_pp, _c_ll_p, POINTER(c_char_p)]),
+        "said_debug_ws_fill": (c_int, [c_void_p, c_int]),
+        "said_debug_ws_copy": (c_int, [c_void_p, c_int, c_void_p, _c_ll, c_void_p]),
+        "said_debug_audio_copy": (c_int, [c_void_p, c_char_p, c_void_p, _c_ll, c_void_p]),
+        "said_unet_algorithmic_bytes": (c_double, [c_int, c_int, c_int]),
+        "said_unet_algorithmic_flops": (c_double, [c_int, c_int]),
+        "said_vae_create": (c_int, [_c_void_pp, c_int, c_int, c_int, c_int]),
+        "said_vae_destroy": (c_int, [c_void_p]),
+        "said_vae_last_error": (c_char_p, [c_void_p]),
+        "said_vae_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, _c_ll_p, c_int]),
+        "said_vae_finalize_weights": (c_int, [c_void_p]),
+        "said_vae_encode": (c_int, [c_void_p, c_void_p, _c_ll, c_int, c_void_p, c_void_p, c_void_p]),
+        "said_vae_has_decoder": (c_int, [c_void_p]),
+        "said_vae_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    }, late={   # added to said_hip.h without an ABI version bump: load_library("vae_decoder") binds them
+        "vae_decoder": ("the VAE decoder", ("said_vae_has_decoder", "said_vae_decode")),
+    }),
+    "metrics": Group(("include/said_metrics.h",), "the metrics passes", {
+        "said_metrics_create": (c_int, [_c_void_pp, c_int, _c_ll]),
+        "said_metrics_destroy": (c_int, [c_void_p]),
+        "said_metrics_last_error": (c_char_p, [c_void_p]),
+        "said_metrics_max_points": (_c_ll, [c_void_p]),
+        "said_metrics_weighted_sums": (c_int, [c_void_p, c_void_p, _c_ll, c_int, c_int, _c_double_p, _c_double_p, c_void_p]),
+        "said_metrics_weighted_scatter": (c_int, [c_void_p, c_void_p, _c_ll, c_int, c_int, _c_double_p, _c_double_p, c_void_p]),
+        "said_metrics_gmm_estep": (c_int, [c_void_p, c_void_p, _c_ll, c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                           _c_double_p, c_void_p, c_void_p, c_void_p]),
+        "said_metrics_kmeans_assign": (c_int, [c_void_p, c_void_p, _c_ll, c_int, _c_double_p, c_int, _c_ll_p, _c_double_p, c_void_p]),
+        "said_metrics_kmeans_read": (c_int, [c_void_p, _c_ll, _c_int_p, _c_double_p, c_void_p]),
+        "said_metrics_kmeans_set_labels": (c_int, [c_void_p, _c_ll, c_int, _c_int_p, c_void_p]),
+        "said_metrics_kmeanspp_first": (c_int, [c_void_p, c_void_p, _c_ll, _c_ll, _c_double_p, c_void_p]),
+        "said_metrics_kmeanspp_step": (c_int, [c_void_p, c_void_p, _c_ll, _c_double_p, c_int, _c_ll_p, _c_double_p, c_void_p]),
+    }),
+    "optimize": Group(("include/said_optimize.h",), "the blendshape fit", {
+        "said_optimize_create": (c_int, [_c_void_pp, c_int]),
+        "said_optimize_destroy": (c_int, [c_void_p]),
+        "said_optimize_last_error": (c_char_p, [c_void_p]),
+        "said_optimize_set_bases": (c_int, [c_void_p, c_int, c_int, _c_ll, _c_double_p, _c_double_p, _c_double_p, c_void_p]),
+        "said_optimize_rhs": (c_int, [c_void_p, c_int, c_void_p, _c_ll, c_void_p, c_void_p]),
+        "said_optimize_solve": (c_int, [c_void_p, c_int, _c_ll_p, _c_int_p, c_void_p, c_double, c_int, c_int, c_double, c_void_p, c_void_p,
+                                        _c_int_p, _c_int_p, _c_double_p, c_void_p]),
+    }),
+    "train": Group(("include/said_train.h",), "the BCVAE trainer", {
+        "said_train_create": (c_int, [_c_void_pp, c_int, c_int]),
+        "said_train_destroy": (c_int, [c_void_p]),
+        "said_train_last_error": (c_char_p, [c_void_p]),
+        "said_train_tensor_name": (c_char_p, [c_int]),
+        "said_train_tensor_numel": (_c_ll, [c_int]),
+        "said_train_tensor_is_counter": (c_int, [c_int]),
+        "said_train_set_tensor": (c_int, [c_void_p, c_int, c_char_p, c_void_p, _c_ll]),
+        "said_train_get_tensor": (c_int, [c_void_p, c_int, c_char_p, c_void_p, _c_ll]),
+        "said_train_reset_optimizer": (c_int, [c_void_p]),
+        "said_train_set_data": (c_int, [c_void_p, c_int, _c_float_p, _c_ll, _c_ll_p, _c_int_p, c_int, _c_int_p]),
+        "said_train_gather": (c_int, [c_void_p, c_int, c_int, _c_int_p, _c_float_p]),
+        "said_train_step": (c_int, [c_void_p, c_int, _c_int_p, _c_float_p, _c_float_p, _c_float_p, c_int]),
+        "said_train_apply_update": (c_int, [c_void_p, _c_float_p]),
+        "said_train_eval_loss": (c_int, [c_void_p, c_int, c_int, _c_int_p, _c_float_p, _c_float_p, _c_float_p, c_int]),
+        "said_train_read_losses": (c_int, [c_void_p, c_int, _c_double_p, _c_int_p, c_int]),
+        "said_train_last_losses": (c_int, [c_void_p, _c_float_p]),
+        "said_train_bn_stats": (c_int, [c_void_p, c_int, _c_float_p]),
+        "said_train_graph_count": (c_int, [c_void_p]),
+    }),
+    "render": Group(("include/said_render.h",), "the renderer", {
+        "said_render_create": (c_int, [_c_void_pp, c_int]),
+        "said_render_destroy": (c_int, [c_void_p]),
+        "said_render_last_error": (c_char_p, [c_void_p]),
+        "said_render_set_mesh": (c_int, [c_void_p, c_int, c_int, c_int, _c_double_p, _c_int_p, _c_double_p, c_void_p]),
+        "said_render_set_scene": (c_int, [c_void_p, c_void_p]),
+        "said_render_set_colormap": (c_int, [c_void_p, _c_float_p, c_void_p]),
+        "said_render_render": (c_int, [c_void_p, c_void_p, c_void_p, _c_ll, c_int, c_float, _c_double_p, _c_double_p, c_void_p, c_void_p,
+                                       c_void_p]),
+        "said_render_read_vertices": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
+        "said_render_read_normals": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
+        "said_render_read_colors": (c_int, [c_void_p, c_int, _c_float_p, c_void_p]),
+    }),
+    # the sample count is an argument of this one call: the renderer's own header and scene keep their shape
+    "render_ms": Group(("include/said_render_ms.h",), "multisampled rendering", {
+        "said_render_render_ms": (c_int, [c_void_p, c_int, c_void_p, c_void_p, _c_ll, c_int, c_float, _c_double_p, _c_double_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
+    }),
+    "jpeg": Group(("include/said_jpeg.h",), "the JPEG encoder", {
+        "said_jpeg_create": (c_int, [_c_void_pp, c_int]),
+        "said_jpeg_destroy": (c_int, [c_void_p]),
+        "said_jpeg_last_error": (c_char_p, [c_void_p]),
+        "said_jpeg_configure": (c_int, [c_void_p, c_int, c_int, c_int]),
+        "said_jpeg_header": (c_int, [c_void_p, c_void_p, _c_ll, _c_ll_p]),
+        "said_jpeg_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, _c_ll, c_void_p, _c_ll_p, c_void_p]),
+        "said_jpeg_read_coefficients": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    }),
+    "unet_train": Group(("include/said_unet_train.h",), "the UNet trainer", {
+        "said_unet_train_create": (c_int, [_c_void_pp, c_int, c_int, c_int]),
+        "said_unet_train_create_dim": (c_int, [_c_void_pp, c_int, c_int, c_int, c_int]),
+        "said_unet_train_destroy": (c_int, [c_void_p]),
+        "said_unet_train_last_error": (c_char_p, [c_void_p]),
+        "said_unet_train_tensor_name": (c_char_p, [c_int]),
+        "said_unet_train_tensor_numel": (_c_ll, [c_int]),
+        "said_unet_train_table_size": (c_int, [c_int]),
+        "said_unet_train_table_name": (c_char_p, [c_int, c_int]),
+        "said_unet_train_table_numel": (_c_ll, [c_int, c_int]),
+        "said_unet_train_num_tensors": (c_int, [c_void_p]),
+        "said_unet_train_context_tensor_name": (c_char_p, [c_void_p, c_int]),
+        "said_unet_train_context_tensor_numel": (_c_ll, [c_void_p, c_int]),
+        "said_unet_train_feature_dim": (c_int, [c_void_p]),
+        "said_unet_train_set_tensor": (c_int, [c_void_p, c_int, c_char_p, _c_float_p, _c_ll]),
+        "said_unet_train_get_tensor": (c_int, [c_void_p, c_int, c_char_p, _c_float_p, _c_ll]),
+        "said_unet_train_reset_optimizer": (c_int, [c_void_p]),
+        "said_unet_train_copy": (c_int, [c_void_p, c_int, c_int]),
+        "said_unet_train_set_alphas": (c_int, [c_void_p, _c_float_p, c_int]),
+        "said_unet_train_step": (c_int, [c_void_p, c_int, c_int, _c_float_p, _c_float_p, _c_ll_p, _c_int_p, c_void_p, c_int, _c_ull, _c_float_p,
+                                         _c_float_p, _c_float_p, c_int]),
+        "said_unet_train_eval_loss": (c_int, [c_void_p, c_int, c_int, _c_float_p, _c_float_p, _c_ll_p, _c_int_p, c_void_p, c_int, _c_float_p,
+                                              _c_float_p, _c_float_p, c_int, c_int]),
+        "said_unet_train_forward_only": (c_int, [c_void_p, c_int, c_int, _c_float_p, _c_ll_p, _c_int_p, c_void_p, c_int, c_int, _c_float_p]),
+        "said_unet_train_apply_update": (c_int, [c_void_p, _c_float_p]),
+        "said_unet_train_read_losses": (c_int, [c_void_p, c_int, _c_double_p, _c_int_p, c_int]),
+        "said_unet_train_last_losses": (c_int, [c_void_p, _c_float_p]),
+    }),
+    "beat": Group(("include/said_beat.h",), "the beat-consistency passes", {
+        "said_beat_create": (c_int, [_c_void_pp, c_int]),
+        "said_beat_destroy": (c_int, [c_void_p]),
+        "said_beat_last_error": (c_char_p, [c_void_p]),
+        "said_beat_set_sampling_rate": (c_int, [c_void_p, c_int, _c_int_p]),
+        "said_beat_clips": (c_int, [c_void_p, c_void_p, c_int, _c_ll_p, c_void_p]),
+        "said_beat_coeffs": (c_int, [c_void_p, c_void_p, c_int, _c_ll_p, c_int, c_double, c_void_p]),
+        "said_beat_score": (c_int, [c_void_p, _c_int_p, c_double, c_double, _c_double_p, c_void_p]),
+        "said_beat_set_deltas": (c_int, [c_void_p, c_int, c_int, c_int, _c_double_p, c_void_p]),
+        "said_beat_vertex_error": (c_int, [c_void_p, c_void_p, _c_ll, c_int, _c_ll_p, _c_ll_p, _c_int_p, _c_int_p, _c_double_p, c_void_p]),
+        "said_beat_read_mel": (c_int, [c_void_p, _c_double_p, c_void_p]),
+        "said_beat_read_envelope": (c_int, [c_void_p, _c_double_p, c_void_p]),
+        "said_beat_read_onsets": (c_int, [c_void_p, _c_int_p, _c_int_p, c_void_p]),
+        "said_beat_read_rates": (c_int, [c_void_p, _c_double_p, c_void_p]),
+        "said_beat_read_minima": (c_int, [c_void_p, _c_int_p, _c_int_p, c_void_p]),
+    }),
+    "transfer": Group(("include/said_transfer.h",), "deformation transfer", {
+        "said_transfer_create": (c_int, [_c_void_pp, c_int]),
+        "said_transfer_destroy": (c_int, [c_void_p]),
+        "said_transfer_last_error": (c_char_p, [c_void_p]),
+        "said_transfer_set_source": (c_int, [c_void_p, c_int, c_int, c_int, _c_double_p, _c_int_p, _c_double_p, c_void_p]),
+        "said_transfer_set_target": (c_int, [c_void_p, c_int, c_int, _c_double_p, _c_int_p, c_void_p]),
+        "said_transfer_solve": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _c_int_p, _c_int_p, _c_double_p, _c_int_p, _c_int_p,
+                                        _c_double_p, _c_double_p, _c_double_p, c_double, c_int, c_int, _c_double_p, _c_int_p, _c_int_p,
+                                        _c_double_p, c_void_p]),
+        "said_transfer_register": (c_int, [c_void_p, c_void_p, c_int, _c_int_p, _c_double_p, c_double, c_double, c_int, _c_double_p, c_double, c_int,
+                                           _c_double_p, _c_int_p, _c_int_p, _c_int_p, _c_double_p, c_void_p]),
+        "said_transfer_correspond": (c_int, [c_void_p, _c_double_p, c_double, _c_int_p, _c_int_p, _c_double_p, _c_double_p, c_void_p]),
+        "said_transfer_transfer": (c_int, [c_void_p, c_void_p, c_double, c_int, _c_double_p, _c_int_p, _c_int_p, _c_double_p, c_void_p]),
+        "said_transfer_mesh": (c_int, [c_void_p, c_int, c_int, _c_double_p, _c_int_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                       c_void_p]),
+        "said_transfer_gradients": (c_int, [c_void_p, c_int, c_int, _c_double_p, _c_int_p, c_int, _c_double_p, _c_double_p, c_void_p]),
+        "said_transfer_closest": (c_int, [c_void_p, c_int, _c_double_p, _c_double_p, c_int, _c_double_p, _c_double_p, _c_int_p, _c_double_p, c_void_p]),
+    }),
+    # an entry point of the said_ctx context, added without an ABI version bump
+    "audio_train": Group(("include/said_audio_train.h",), "the audio encoder's train mode", {
+        "said_audio_encode_train": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(AudioTrainParams), c_void_p, _c_int_p, c_void_p]),
+    }),
 }
-_GROUPS = {**LAZY_EXPORTS, "render": ("the renderer", RENDER_EXPORTS), "render_ms": ("multisampled rendering", RENDER_MS_EXPORTS),
-           "jpeg": ("the JPEG encoder", JPEG_EXPORTS), "audio_train": ("the audio encoder's train mode", AUDIO_TRAIN_EXPORTS),
-           "unet_train": ("the UNet trainer", UNET_TRAIN_EXPORTS), "beat": ("the beat-consistency passes", BEAT_EXPORTS),
-           "transfer": ("deformation transfer", TRANSFER_EXPORTS)}
 _bound = set()   # the groups bound so far
 
 
@@ -272,15 +315,33 @@ def library_path() -> str:
     return _LIB_PATH
 
 
-def _bind(lib, table):
+def _group(group: str):
+    """(feature, table) of a group of ABI, without its late entries, or of a late part of one."""
+    if group in ABI:
+        g = ABI[group]
+        late = {name for _, names in g.late.values() for name in names}
+        return g.feature, {name: sig for name, sig in g.table.items() if name not in late}
+    for g in ABI.values():
+        if group in g.late:
+            feature, names = g.late[group]
+            return feature, {name: g.table[name] for name in names}
+    raise KeyError(group)
+
+
+def _bind(lib, group: str) -> None:
+    feature, table = _group(group)
+    for name in table:
+        if not hasattr(lib, name):
+            raise EngineError(f"{_LIB_PATH} predates {feature} ({name} is not exported): rebuild it with `python -m said_amd.build --force`")
     for name, (res, args) in table.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+        fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    _bound.add(group)
 
 
 def load_library(group: Optional[str] = None):
-    """dlopen the engine and bind EXPORTS but the VAE decoder (no compute); with `group`, also that group of LAZY_EXPORTS (or "render")."""
+    """dlopen the engine and bind the core group of ABI (no compute); with `group`, also that group."""
     global _lib
     if _lib is None:
         if not os.path.exists(_LIB_PATH):
@@ -288,41 +349,72 @@ def load_library(group: Optional[str] = None):
                 f"{_LIB_PATH} not found: build it with `python -m said_amd.build` (hipcc, gfx950). "
                 "said_amd has no CPU fallback.")
         lib = ctypes.CDLL(_LIB_PATH)
-        _bind(lib, {n: sig for n, sig in EXPORTS.items() if n not in LAZY_EXPORTS["vae_decoder"][1]})
+        _bind(lib, "core")
         got = lib.said_abi_version()
         if got != ABI_VERSION:
             raise EngineError(f"{_LIB_PATH} has ABI version {got}, this binding expects {ABI_VERSION}: rebuild it with "
                               "`python -m said_amd.build --force`")
         _lib = lib
     if group is not None and group not in _bound:
-        feature, table = _GROUPS[group]
-        for name in table:
-            if not hasattr(_lib, name):
-                raise EngineError(f"{_LIB_PATH} predates {feature} ({name} is not exported): rebuild it with `python -m said_amd.build --force`")
-        _bind(_lib, table)
-        _bound.add(group)
+        _bind(_lib, group)
     return _lib
+
+
+# ---- marshalling: host arrays, pointers to them, device tensors
+def _array_of(dtype):
+    """The helper of one element type: a C-contiguous host array of it (no copy of what already is one); None passes through."""
+    return lambda a: None if a is None else np.ascontiguousarray(a, dtype=dtype)
+
+
+def _pointer_to(ctype):
+    """The helper of one pointee type: a host array's memory as that ctypes pointer; None passes through."""
+    return lambda a: None if a is None else a.ctypes.data_as(ctype)
+
+
+_f32, _f64, _i32, _i64 = _array_of(np.float32), _array_of(np.float64), _array_of(np.int32), _array_of(np.int64)
+_fp, _dp, _ip, _lp, _vp = _pointer_to(_c_float_p), _pointer_to(_c_double_p), _pointer_to(_c_int_p), _pointer_to(_c_ll_p), _pointer_to(c_void_p)
+
+
+def host_f32(a) -> np.ndarray:
+    """A contiguous float32 host array of an array, a list or a tensor (on any device)."""
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return _f32(a)
 
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else c_void_p(t.data_ptr())
 
 
-def _check_dev(t: torch.Tensor, name: str) -> torch.Tensor:
-    if not t.is_cuda:
-        raise EngineError(f"{name} must live on the MI355X (got device {t.device}); said_amd has no CPU path")
-    if t.dtype != torch.float32:
-        raise EngineError(f"{name} must be float32, got {t.dtype}")
-    return t.contiguous()
-
-
 def _stream() -> c_void_p:
     return c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _dev(t: torch.Tensor, name: str, dtype=torch.float32, index: Optional[int] = None, trailing: Optional[tuple] = None, numel: int = 0,
+         strict: bool = False) -> torch.Tensor:
+    """`t` as a contiguous `dtype` tensor on the GPU; where given: on cuda:`index`, of shape (n, *trailing), of at least `numel` elements.
+    A tensor that is not contiguous is copied; with `strict` it is refused (an output, or an input whose owner promised the layout)."""
+    if not strict:
+        t = t.contiguous()
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and (index is None or t.device.index == index)
+            and (trailing is None or tuple(t.shape[1:]) == tuple(trailing)) and t.numel() >= numel):
+        shape = "" if trailing is None else f" of shape (n, {', '.join(str(n) for n in trailing)})"
+        raise EngineError(f"{name} must be a contiguous {dtype} tensor{shape} on " + ("the MI355X" if index is None else f"cuda:{index}")
+                          + (f" with at least {numel} elements" if numel else "") + f", got {tuple(t.shape)} {t.dtype} on {t.device}"
+                          + ("" if t.is_cuda else "; said_amd has no CPU path"))
+    return t
+
+
+def _w2v_frames(num_samples: int) -> int:
+    """Frames that Wav2Vec2's seven feature-extractor convolutions leave of `num_samples` samples."""
+    for k, s in zip((10, 3, 3, 3, 3, 2, 2), (5, 2, 2, 2, 2, 2, 2)):
+        num_samples = (num_samples - k) // s + 1
+    return num_samples
+
+
 class _Context:
     """One C context of the library on one GPU, created by <prefix>_create, released by <prefix>_destroy; <prefix>_last_error gives
-    the message of a failed call (NULL: of a failed create).  A subclass names its prefix, its LAZY_EXPORTS group and how it refuses a
+    the message of a failed call (NULL: of a failed create).  A subclass names its prefix, its group of ABI and how it refuses a
     device that is not a GPU."""
     prefix = ""
     group: Optional[str] = None
@@ -330,17 +422,19 @@ class _Context:
     cpu_message = "said_amd runs on MI355X only (device={}); there is no CPU fallback"
 
     def __init__(self, device: torch.device):
-        self.lib = load_library(self.group)
         device = torch.device(device)
-        if device.type != "cuda":
+        if device.type != "cuda":   # refused before the library is looked for: the answer does not depend on a build
             raise self.cpu_error(self.cpu_message.format(device))
+        self.lib = load_library(self.group)
         self.device = device
         self.index = device.index if device.index is not None else torch.cuda.current_device()
 
-    def _create(self, *args) -> None:
+    def _create(self, *args, entry: Optional[str] = None) -> None:
+        """<entry, default <prefix>_create>(&h, device index, *args)."""
+        entry = entry or self.prefix + "_create"
         h = c_void_p()
-        if getattr(self.lib, self.prefix + "_create")(ctypes.byref(h), self.index, *args) != 0:
-            raise EngineError(f"{self.prefix}_create: " + self._last_error(None))
+        if getattr(self.lib, entry)(ctypes.byref(h), self.index, *args) != 0:
+            raise EngineError(f"{entry}: " + self._last_error(None))
         self.h = h
 
     def _last_error(self, h) -> str:
@@ -361,6 +455,11 @@ class _Context:
         """name(h, *args); EngineError("<what or name>: <last error>") when it fails."""
         if getattr(self.lib, name)(self.h, *args) != 0:
             raise EngineError(f"{what or name}: " + self._last_error(self.h))
+
+    def _go(self, name: str, *args) -> None:
+        """_call with this context's GPU current and the current stream as the last argument: for the entries that end in a stream."""
+        with torch.cuda.device(self.index):
+            self._call(name, *args, _stream())
 
 
 class Engine(_Context):
@@ -414,36 +513,27 @@ class Engine(_Context):
         with torch.cuda.device(self.index):
             half = 96
             freqs = torch.exp(-np.log(10000) * torch.arange(start=0, end=half, dtype=torch.float32) / half)
-            fr = np.ascontiguousarray(freqs.numpy())
-            self._call("said_set_timestep_freqs", fr.ctypes.data_as(c_void_p), half)
+            self._call("said_set_timestep_freqs", _vp(_f32(freqs.numpy())), half)
             for k, v in state_dict.items():
-                a = np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy())
-                shape = (c_int64 * a.ndim)(*a.shape)
-                self._call("said_set_weight", k.encode(), a.ctypes.data_as(c_void_p), shape, a.ndim, what=f"said_set_weight({k})")
+                a = _f32(v.detach().to("cpu", torch.float32).numpy())
+                shape = (_c_ll * a.ndim)(*a.shape)
+                self._call("said_set_weight", k.encode(), _vp(a), shape, a.ndim, what=f"said_set_weight({k})")
             self._call("said_finalize_weights", _stream())
         self.has_audio = any(k.startswith("audio_encoder.") for k in state_dict)
 
     # ---- compute ----
     def audio_encode(self, waveform: torch.Tensor, num_frames: Optional[int], apply_proj: bool = False, _train=None) -> torch.Tensor:
-        waveform = _check_dev(waveform, "waveform")
+        waveform = _dev(waveform, "waveform")
         B, Ta = waveform.shape
-        out_dim = self.ctx_dim if apply_proj else 768
-        with torch.cuda.device(self.index):
-            # frame count without interpolation is decided by the library
-            nf = int(num_frames) if num_frames is not None else 0
-            if nf > 0:
-                out = torch.empty(B, nf, out_dim, device=waveform.device, dtype=torch.float32)
-            else:
-                L = Ta
-                for k, s in zip((10, 3, 3, 3, 3, 2, 2), (5, 2, 2, 2, 2, 2, 2)):
-                    L = (L - k) // s + 1
-                out = torch.empty(B, max(L, 1), out_dim, device=waveform.device, dtype=torch.float32)
-            got = c_int(0)
-            if _train is None:
-                self._call("said_audio_encode", _ptr(waveform), B, Ta, nf, int(apply_proj), _ptr(out), ctypes.byref(got), _stream())
-            else:
-                self._call("said_audio_encode_train", _ptr(waveform), B, Ta, nf, int(apply_proj), ctypes.byref(_train), _ptr(out), ctypes.byref(got), _stream())
-            assert got.value == out.shape[1], (got.value, out.shape)
+        nf = int(num_frames) if num_frames is not None else 0
+        # the frame count without interpolation is decided by the library
+        out = torch.empty(B, nf if nf > 0 else max(_w2v_frames(Ta), 1), self.ctx_dim if apply_proj else 768, device=waveform.device, dtype=torch.float32)
+        got = c_int(0)
+        if _train is None:
+            self._go("said_audio_encode", _ptr(waveform), B, Ta, nf, int(apply_proj), _ptr(out), ctypes.byref(got))
+        else:
+            self._go("said_audio_encode_train", _ptr(waveform), B, Ta, nf, int(apply_proj), ctypes.byref(_train), _ptr(out), ctypes.byref(got))
+        assert got.value == out.shape[1], (got.value, out.shape)
         return out
 
     def audio_encode_train(self, waveform: torch.Tensor, num_frames: Optional[int], draws, cfg, apply_proj: bool = False) -> torch.Tensor:
@@ -453,9 +543,7 @@ class Engine(_Context):
         cfg.check()
         B, frames = waveform.shape[0], int(num_frames or 0)
         if frames <= 0:   # no interpolation: the feature extractor's own frame count
-            frames = waveform.shape[1]
-            for k, s in zip((10, 3, 3, 3, 3, 2, 2), (5, 2, 2, 2, 2, 2, 2)):
-                frames = (frames - k) // s + 1
+            frames = _w2v_frames(waveform.shape[1])
         mask = None
         if draws.mask is not None:
             m = np.ascontiguousarray(np.asarray(draws.mask) != 0, dtype=np.uint8)
@@ -475,18 +563,16 @@ class Engine(_Context):
         return out
 
     def unet_forward(self, sample: torch.Tensor, timesteps: torch.Tensor, context: torch.Tensor) -> torch.Tensor:
-        sample = _check_dev(sample, "sample")
-        context = _check_dev(context, "encoder_hidden_states")
+        sample = _dev(sample, "sample")
+        context = _dev(context, "encoder_hidden_states")
         Be, T, C = sample.shape
         if context.shape[0] != Be or context.shape[2] != self.ctx_dim:
             raise EngineError(f"context shape {tuple(context.shape)} does not match batch {Be} / ctx_dim {self.ctx_dim}")
-        ts = np.ascontiguousarray(timesteps.detach().to("cpu", torch.int64).reshape(-1).numpy())
+        ts = _i64(timesteps.detach().to("cpu", torch.int64).reshape(-1).numpy())
         if ts.shape[0] != Be:
             raise EngineError(f"timesteps must have {Be} entries, got {ts.shape[0]}")
         out = torch.empty_like(sample)
-        with torch.cuda.device(self.index):
-            self._call("said_unet_forward", _ptr(sample), ts.ctypes.data_as(POINTER(c_int64)), _ptr(context), Be, T,
-                       context.shape[1], _ptr(out), _stream())
+        self._go("said_unet_forward", _ptr(sample), _lp(ts), _ptr(context), Be, T, context.shape[1], _ptr(out))
         return out
 
     def loop_job(self, *, latents: torch.Tensor, context: torch.Tensor, timesteps: np.ndarray, coef: np.ndarray,
@@ -497,12 +583,12 @@ class Engine(_Context):
         """Validates the arguments and allocates the outputs of one denoising loop (on the current stream): a job for
         prepare_loop / run_loop.  `noise_seed` (with step_noise None): the eta noise is generated inside the step's last
         kernel (Philox4x32-10 keyed by the seed) instead of being read from a tensor."""
-        latents = _check_dev(latents, "latents").clone()
-        context = _check_dev(context, "audio_embedding")
+        latents = _dev(latents, "latents").clone()
+        context = _dev(context, "audio_embedding")
         B, T, C = latents.shape
         N = int(len(timesteps))
-        ts = np.ascontiguousarray(np.asarray(timesteps, dtype=np.int64))
-        cf = np.ascontiguousarray(np.asarray(coef, dtype=np.float32).reshape(N, NCOEF))
+        ts = _i64(timesteps)
+        cf = _f32(coef).reshape(N, NCOEF)
         result = torch.empty_like(latents)
         inter = torch.empty(N, B, T, C, device=latents.device, dtype=torch.float32) if save_intermediate else None
         use_mask = mask is not None and init_latents is not None
@@ -514,12 +600,12 @@ class Engine(_Context):
         p.use_mask = int(use_mask)
         p.save_intermediate = int(save_intermediate)
         p.concurrent = int(bool(concurrent))
-        p.timesteps_host = ts.ctypes.data_as(POINTER(c_int64))
-        p.coef_host = cf.ctypes.data_as(POINTER(c_float))
+        p.timesteps_host = _lp(ts)
+        p.coef_host = _fp(cf)
         p.context_dev = context.data_ptr()
         p.latents_dev = latents.data_ptr()
         if step_noise is not None:
-            step_noise = _check_dev(step_noise, "step_noise")
+            step_noise = _dev(step_noise, "step_noise")
             assert tuple(step_noise.shape) == (N, B, T, C), step_noise.shape
             p.step_noise_dev = step_noise.data_ptr()
             keep.append(step_noise)
@@ -528,9 +614,9 @@ class Engine(_Context):
             p.noise_seed = int(noise_seed) & 0xFFFFFFFFFFFFFFFF
             p.noise_batch_offset = int(noise_batch_offset)
         if use_mask:
-            init_latents = _check_dev(init_latents, "init_latents")
-            edit_noise = _check_dev(edit_noise, "edit_noise")
-            mask = _check_dev(mask.expand_as(latents) if mask.shape != latents.shape else mask, "mask")
+            init_latents = _dev(init_latents, "init_latents")
+            edit_noise = _dev(edit_noise, "edit_noise")
+            mask = _dev(mask.expand_as(latents) if mask.shape != latents.shape else mask, "mask")
             p.init_latents_dev, p.edit_noise_dev, p.mask_dev = init_latents.data_ptr(), edit_noise.data_ptr(), mask.data_ptr()
             keep += [init_latents, edit_noise, mask]
         if inter is not None:
@@ -538,6 +624,7 @@ class Engine(_Context):
         p.result_dev = result.data_ptr()
         return p, keep, (result, latents, inter)
 
+    # prepare_loop and run_loop are the loop's path: they stay spelled out, one frame shallower than _go
     def prepare_loop(self, job):
         """Builds the job's step graph if this context does not hold it yet (said_loop_prepare); launches nothing of the loop."""
         with torch.cuda.device(self.index):
@@ -558,15 +645,13 @@ class Engine(_Context):
                   eps_uncond: Optional[torch.Tensor] = None, guidance_scale: float = 1.0,
                   step_noise: Optional[torch.Tensor] = None, init_latents: Optional[torch.Tensor] = None,
                   edit_noise: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        eps, sample = _check_dev(eps, "model_output"), _check_dev(sample, "sample")
+        eps, sample = _dev(eps, "model_output"), _dev(sample, "sample")
         out = torch.empty_like(sample)
-        cf = np.ascontiguousarray(np.asarray(coef_row, dtype=np.float32).reshape(NCOEF))
-        opt = [None if t is None else _check_dev(t, "tensor") for t in (eps_uncond, step_noise, init_latents, edit_noise, mask)]
-        with torch.cuda.device(self.index):
-            self._call("said_ddim_step", _ptr(eps), _ptr(opt[0]), float(guidance_scale), _ptr(sample),
-                       cf.ctypes.data_as(POINTER(c_float)), PRED[prediction_type], _ptr(opt[1]), _ptr(opt[2]),
-                       _ptr(opt[3]), _ptr(opt[4]), _ptr(out), sample.numel(), _stream())
-            torch.cuda.current_stream().synchronize()  # cf is a temporary
+        cf = _f32(coef_row).reshape(NCOEF)
+        opt = [None if t is None else _dev(t, "tensor") for t in (eps_uncond, step_noise, init_latents, edit_noise, mask)]
+        self._go("said_ddim_step", _ptr(eps), _ptr(opt[0]), float(guidance_scale), _ptr(sample), _fp(cf), PRED[prediction_type], _ptr(opt[1]),
+                 _ptr(opt[2]), _ptr(opt[3]), _ptr(opt[4]), _ptr(out), sample.numel())
+        torch.cuda.current_stream(self.index).synchronize()  # cf is a temporary
         return out
 
     def solver_step(self, model_output: torch.Tensor, sample: torch.Tensor, coef_row: np.ndarray, prediction_type: str,
@@ -574,34 +659,31 @@ class Engine(_Context):
                     step_noise: Optional[torch.Tensor] = None, init_latents: Optional[torch.Tensor] = None,
                     edit_noise: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One DDPM / DPM-Solver++ row (said_solver_step).  `x0_hist` (DPM rows): the previous step's x0 in, this step's out (updated in place)."""
-        model_output, sample = _check_dev(model_output, "model_output"), _check_dev(sample, "sample")
+        model_output, sample = _dev(model_output, "model_output"), _dev(sample, "sample")
         out = torch.empty_like(sample)
-        cf = np.ascontiguousarray(np.asarray(coef_row, dtype=np.float32).reshape(NCOEF))
-        opt = [None if t is None else _check_dev(t, "tensor") for t in (model_output_uncond, step_noise, init_latents, edit_noise, mask)]
+        cf = _f32(coef_row).reshape(NCOEF)
+        opt = [None if t is None else _dev(t, "tensor") for t in (model_output_uncond, step_noise, init_latents, edit_noise, mask)]
         for t in [x0_hist] + opt:
             if t is not None and t.numel() != sample.numel():
                 raise EngineError(f"solver_step: every tensor must hold {sample.numel()} values, got {t.numel()}")
-        if x0_hist is not None and (_check_dev(x0_hist, "x0_hist") is not x0_hist):
+        if x0_hist is not None and (_dev(x0_hist, "x0_hist") is not x0_hist):
             raise EngineError("x0_hist must be contiguous: it is updated in place")
-        with torch.cuda.device(self.index):
-            self._call("said_solver_step", _ptr(model_output), _ptr(opt[0]), float(guidance_scale), _ptr(sample),
-                       cf.ctypes.data_as(POINTER(c_float)), PRED[prediction_type], _ptr(x0_hist), _ptr(opt[1]),
-                       _ptr(opt[2]), _ptr(opt[3]), _ptr(opt[4]), _ptr(out), sample.numel(), _stream())
-            torch.cuda.current_stream().synchronize()  # cf is a temporary
+        self._go("said_solver_step", _ptr(model_output), _ptr(opt[0]), float(guidance_scale), _ptr(sample), _fp(cf), PRED[prediction_type],
+                 _ptr(x0_hist), _ptr(opt[1]), _ptr(opt[2]), _ptr(opt[3]), _ptr(opt[4]), _ptr(out), sample.numel())
+        torch.cuda.current_stream(self.index).synchronize()  # cf is a temporary
         return out
 
     def axpby(self, a: Sequence[float], x: torch.Tensor, c: Optional[Sequence[float]] = None, y: Optional[torch.Tensor] = None) -> torch.Tensor:
-        x = _check_dev(x, "x")
+        x = _dev(x, "x")
         B = x.shape[0]
         if len(a) != B or (c is not None and len(c) != B):
             raise EngineError(f"axpby: need one coefficient per sample ({B}), got {len(a)}" + (f" / {len(c)}" if c is not None else ""))
         av = (c_float * B)(*[float(v) for v in a])
         cv = (c_float * B)(*[float(v) for v in (c if c is not None else [0.0] * B)])
         if y is not None:
-            y = _check_dev(y, "y")
+            y = _dev(y, "y")
         out = torch.empty_like(x)
-        with torch.cuda.device(self.index):
-            self._call("said_axpby", av, _ptr(x), cv, _ptr(y), _ptr(out), B, x.numel() // B, _stream())
+        self._go("said_axpby", av, _ptr(x), cv, _ptr(y), _ptr(out), B, x.numel() // B)
         return out
 
     def profile_unet(self, batch_eff: int, frames: int, reps: int = 50, cfg_clips: int = 0):
@@ -610,10 +692,8 @@ class Engine(_Context):
         us = np.zeros(M, np.float32); by = np.zeros(M, np.float64); fl = np.zeros(M, np.float64)
         kind = np.zeros(M, np.int32); epi = np.zeros(M, np.int32); nb = np.zeros(M, np.int32); ks = np.zeros(M, np.int32)
         n = c_int(0)
-        vp = lambda a: a.ctypes.data_as(c_void_p)
-        with torch.cuda.device(self.index):
-            self._call("said_profile_unet", batch_eff, frames, cfg_clips, reps, M, vp(us), vp(by), vp(fl), vp(kind), vp(epi), vp(nb),
-                       vp(ks), ctypes.byref(n), _stream())
+        self._go("said_profile_unet", batch_eff, frames, cfg_clips, reps, M, _vp(us), _vp(by), _vp(fl), _vp(kind), _vp(epi), _vp(nb), _vp(ks),
+                 ctypes.byref(n))
         k = n.value
         return [dict(us=float(us[i]), bytes=float(by[i]), flops=float(fl[i]), kind=int(kind[i]), epi=int(epi[i]), NB=int(nb[i]), KS=int(ks[i]))
                 for i in range(k)]
@@ -622,8 +702,7 @@ class Engine(_Context):
         """(nsteps, *shape) standard normals: exactly what denoise_loop(noise_seed=seed) adds at steps step0 .. step0 + nsteps - 1."""
         n = int(np.prod(shape))
         out = torch.empty((nsteps,) + tuple(shape), device=self.device, dtype=torch.float32)
-        with torch.cuda.device(self.index):
-            self._call("said_philox_normal", int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), int(nsteps), n, _ptr(out), _stream())
+        self._go("said_philox_normal", int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), int(nsteps), n, _ptr(out))
         return out
 
     # ---- debugging aids (tests only) ----
@@ -638,19 +717,19 @@ class Engine(_Context):
 
     def debug_clocks(self, enable: bool, read: bool = False):
         out = np.zeros((64, 8, 16), dtype=np.int64) if read else None
-        self._call("said_debug_clocks", int(enable), out.ctypes.data_as(c_void_p) if read else None)
+        self._call("said_debug_clocks", int(enable), _vp(out))
         return out
 
     def debug_read(self, name: str, shape) -> np.ndarray:
         out = np.empty(shape, dtype=np.float32)
-        self._call("said_debug_read", name.encode(), out.ctypes.data_as(c_void_p), out.size)
+        self._call("said_debug_read", name.encode(), _vp(out), out.size)
         return out
 
     def ws_buffers(self):
         """[(index, name, bytes)] of the context's workspace buffers (said_debug_ws_info)."""
         out = []
         for i in range(int(self.lib.said_debug_ws_count(self.h))):
-            p, nb, nm = c_void_p(), ctypes.c_longlong(0), c_char_p()
+            p, nb, nm = c_void_p(), _c_ll(0), c_char_p()
             self._call("said_debug_ws_info", i, ctypes.byref(p), ctypes.byref(nb), ctypes.byref(nm))
             out.append((i, (nm.value or b"?").decode(), int(nb.value)))
         return out
@@ -661,15 +740,13 @@ class Engine(_Context):
     def ws_snapshot(self, idx: int, nbytes: int) -> torch.Tensor:
         """Device copy (uint8) of workspace buffer `idx`, enqueued on the current stream."""
         out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.index):
-            self._call("said_debug_ws_copy", idx, _ptr(out), nbytes, _stream())
+        self._go("said_debug_ws_copy", idx, _ptr(out), nbytes)
         return out
 
     def audio_snapshot(self, name: str, nbytes: int) -> torch.Tensor:
         """Device copy (uint8) of the first `nbytes` bytes of the audio encoder's buffer `name` (said_debug_audio_copy), enqueued on the current stream."""
         out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.index):
-            self._call("said_debug_audio_copy", name.encode(), _ptr(out), nbytes, _stream())
+        self._go("said_debug_audio_copy", name.encode(), _ptr(out), nbytes)
         return out
 
     def loop_progress(self) -> int:
@@ -729,23 +806,20 @@ class VaeEngine(_Context):
         for k, v in state_dict.items():
             if k.endswith("num_batches_tracked"):
                 continue   # a counter, not a weight
-            a = np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy())
-            shape = (c_int64 * max(a.ndim, 1))(*(a.shape if a.ndim else (1,)))
-            self._call("said_vae_set_weight", k.encode(), a.ctypes.data_as(c_void_p), shape, max(a.ndim, 1), what=f"said_vae_set_weight({k})")
+            a = _f32(v.detach().to("cpu", torch.float32).numpy())
+            shape = (_c_ll * max(a.ndim, 1))(*(a.shape if a.ndim else (1,)))
+            self._call("said_vae_set_weight", k.encode(), _vp(a), shape, max(a.ndim, 1), what=f"said_vae_set_weight({k})")
         self._call("said_vae_finalize_weights")
 
     def encode(self, coeffs: torch.Tensor, n_windows: int, window_stride: int, want_logvar: bool = True):
         """`coeffs`: contiguous fp32 device tensor holding the windows at `window_stride` floats apart."""
-        coeffs = _check_dev(coeffs, "coeffs")
-        if coeffs.device.index != self.index:
-            raise EngineError(f"coeffs live on cuda:{coeffs.device.index}, this VAE engine on cuda:{self.index}")
+        coeffs = _dev(coeffs, "coeffs", index=self.index)
         need = (n_windows - 1) * window_stride + self.seq_len * self.in_channels if n_windows > 0 else 0
         if coeffs.numel() < need:
             raise EngineError(f"coeffs holds {coeffs.numel()} floats, {n_windows} windows at stride {window_stride} need {need}")
         mean = torch.empty(n_windows, self.z_dim, device=coeffs.device, dtype=torch.float32)
         logvar = torch.empty_like(mean) if want_logvar else None
-        with torch.cuda.device(self.index):
-            self._call("said_vae_encode", _ptr(coeffs), int(window_stride), int(n_windows), _ptr(mean), _ptr(logvar), _stream())
+        self._go("said_vae_encode", _ptr(coeffs), int(window_stride), int(n_windows), _ptr(mean), _ptr(logvar))
         return mean, logvar
 
     @property
@@ -765,16 +839,13 @@ class VaeEngine(_Context):
                 continue
             if t.dim() != 2 or t.shape[1] != z or t.shape[0] != mean.shape[0]:
                 raise ValueError(f"{k} must be (n, {z}) like mean {tuple(mean.shape)}, got {tuple(t.shape)}")
-            args[k] = _check_dev(t, k)
-            if t.device.index != self.index:
-                raise EngineError(f"{k} lives on cuda:{t.device.index}, this VAE engine on cuda:{self.index}")
+            args[k] = _dev(t, k, index=self.index)
         n = int(mean.shape[0])
         out = torch.empty(n, self.seq_len, self.in_channels, device=self.device if n == 0 else args["mean"].device, dtype=torch.float32)
         if n == 0:
             return out
         lv = args["log_var"] if eps is not None else None
-        with torch.cuda.device(self.index):
-            self._call("said_vae_decode", _ptr(args["mean"]), _ptr(lv), _ptr(args["eps"]), n, _ptr(out), _stream())
+        self._go("said_vae_decode", _ptr(args["mean"]), _ptr(lv), _ptr(args["eps"]), n, _ptr(out))
         return out
 
 
@@ -784,15 +855,6 @@ def unet_algorithmic_bytes(batch_eff: int, frames: int, bytes_per_elem: int = 4)
 
 def unet_algorithmic_flops(batch_eff: int, frames: int) -> float:
     return float(load_library().said_unet_algorithmic_flops(batch_eff, frames))
-
-
-# ---- evaluation metrics (include/said_metrics.h)
-METRICS_DIM, METRICS_MAX_K = 64, 8
-W_UNIT, W_LABELS, W_RESP = 0, 1, 2   # SAID_METRICS_W_*
-
-
-def _dp(a: np.ndarray):
-    return a.ctypes.data_as(_c_double_p)
 
 
 class MetricsEngine(_Context):
@@ -806,10 +868,7 @@ class MetricsEngine(_Context):
         self.max_points = int(max_points)
 
     def _x(self, x: torch.Tensor) -> torch.Tensor:
-        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != METRICS_DIM or not x.is_contiguous():
-            raise EngineError(f"latents must be a contiguous (n, {METRICS_DIM}) float32 device tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
-        if x.device.index != self.index:
-            raise EngineError(f"latents live on cuda:{x.device.index}, this metrics context on cuda:{self.index}")
+        x = _dev(x, "latents", index=self.index, trailing=(METRICS_DIM,), strict=True)
         if x.shape[0] > self.max_points:
             raise EngineError(f"{x.shape[0]} latents exceed this context's max_points {self.max_points}")
         return x
@@ -818,17 +877,15 @@ class MetricsEngine(_Context):
         """(n_k (k,), sum r x (k, 64)) in float64."""
         x = self._x(x)
         nk, sx = np.zeros(k), np.zeros((k, METRICS_DIM))
-        with torch.cuda.device(self.index):
-            self._call("said_metrics_weighted_sums", _ptr(x), x.shape[0], k, wsrc, _dp(nk), _dp(sx), _stream())
+        self._go("said_metrics_weighted_sums", _ptr(x), x.shape[0], k, wsrc, _dp(nk), _dp(sx))
         return nk, sx
 
     def weighted_scatter(self, x: torch.Tensor, k: int, wsrc: int, means: np.ndarray) -> np.ndarray:
         """sum r (x - mu_k)(x - mu_k)^T, (k, 64, 64) float64."""
         x = self._x(x)
-        mu = np.ascontiguousarray(means, dtype=np.float64).reshape(k, METRICS_DIM)
+        mu = _f64(means).reshape(k, METRICS_DIM)
         out = np.zeros((k, METRICS_DIM, METRICS_DIM))
-        with torch.cuda.device(self.index):
-            self._call("said_metrics_weighted_scatter", _ptr(x), x.shape[0], k, wsrc, _dp(mu), _dp(out), _stream())
+        self._go("said_metrics_weighted_scatter", _ptr(x), x.shape[0], k, wsrc, _dp(mu), _dp(out))
         return out
 
     def gmm_estep(self, x: torch.Tensor, prec_chol: np.ndarray, mean_prec: np.ndarray, log_det: np.ndarray, log_weights: np.ndarray,
@@ -836,58 +893,46 @@ class MetricsEngine(_Context):
         """Mean log_prob_norm (the lower bound); with want_resp also the (n, k) log-responsibilities and (n,) log_prob_norm, float64 device tensors."""
         x = self._x(x)
         k = prec_chol.shape[0]
-        args = [np.ascontiguousarray(a, dtype=np.float64) for a in (prec_chol, mean_prec, log_det, log_weights)]
+        args = [_f64(a) for a in (prec_chol, mean_prec, log_det, log_weights)]
         lb = np.zeros(1)
         lr = lpn = None
         if want_resp:
             lr = torch.empty(x.shape[0], k, dtype=torch.float64, device=x.device)
             lpn = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
-        with torch.cuda.device(self.index):
-            self._call("said_metrics_gmm_estep", _ptr(x), x.shape[0], k, *[_dp(a) for a in args], _dp(lb), _ptr(lr), _ptr(lpn), _stream())
+        self._go("said_metrics_gmm_estep", _ptr(x), x.shape[0], k, *[_dp(a) for a in args], _dp(lb), _ptr(lr), _ptr(lpn))
         return (float(lb[0]), lr, lpn) if want_resp else float(lb[0])
 
     def kmeans_assign(self, x: torch.Tensor, centres: np.ndarray, compare: bool):
         """(labels changed since the previous assignment (n when not compared), inertia)."""
         x = self._x(x)
-        c = np.ascontiguousarray(centres, dtype=np.float64)
-        changed, inertia = ctypes.c_longlong(0), np.zeros(1)
-        with torch.cuda.device(self.index):
-            self._call("said_metrics_kmeans_assign", _ptr(x), x.shape[0], c.shape[0], _dp(c), int(bool(compare)), ctypes.byref(changed),
-                       _dp(inertia), _stream())
+        c = _f64(centres)
+        changed, inertia = _c_ll(0), np.zeros(1)
+        self._go("said_metrics_kmeans_assign", _ptr(x), x.shape[0], c.shape[0], _dp(c), int(bool(compare)), ctypes.byref(changed), _dp(inertia))
         return int(changed.value), float(inertia[0])
 
     def kmeans_read(self, n: int):
         """(labels int32 (n,), squared distance to the assigned centre float64 (n,)) of the last assignment."""
         lab, dist = np.zeros(n, dtype=np.int32), np.zeros(n)
-        with torch.cuda.device(self.index):
-            self._call("said_metrics_kmeans_read", n, lab.ctypes.data_as(POINTER(c_int)), _dp(dist), _stream())
+        self._go("said_metrics_kmeans_read", n, _ip(lab), _dp(dist))
         return lab, dist
 
     def kmeans_set_labels(self, labels: np.ndarray, k: int):
-        lab = np.ascontiguousarray(labels, dtype=np.int32)
-        with torch.cuda.device(self.index):
-            self._call("said_metrics_kmeans_set_labels", lab.shape[0], k, lab.ctypes.data_as(POINTER(c_int)), _stream())
+        lab = _i32(labels)
+        self._go("said_metrics_kmeans_set_labels", lab.shape[0], k, _ip(lab))
 
     def kmeanspp_first(self, x: torch.Tensor, centre_id: int) -> float:
         x = self._x(x)
         pot = np.zeros(1)
-        with torch.cuda.device(self.index):
-            self._call("said_metrics_kmeanspp_first", _ptr(x), x.shape[0], int(centre_id), _dp(pot), _stream())
+        self._go("said_metrics_kmeanspp_first", _ptr(x), x.shape[0], int(centre_id), _dp(pot))
         return float(pot[0])
 
     def kmeanspp_step(self, x: torch.Tensor, rand_vals: np.ndarray):
         """(chosen point index, its potential) for candidate values rand_vals (uniform * current potential)."""
         x = self._x(x)
-        r = np.ascontiguousarray(rand_vals, dtype=np.float64)
-        cid, pot = ctypes.c_longlong(0), np.zeros(1)
-        with torch.cuda.device(self.index):
-            self._call("said_metrics_kmeanspp_step", _ptr(x), x.shape[0], _dp(r), r.shape[0], ctypes.byref(cid), _dp(pot), _stream())
+        r = _f64(rand_vals)
+        cid, pot = _c_ll(0), np.zeros(1)
+        self._go("said_metrics_kmeanspp_step", _ptr(x), x.shape[0], _dp(r), r.shape[0], ctypes.byref(cid), _dp(pot))
         return int(cid.value), float(pot[0])
-
-
-# ---- blendshape-coefficient fit (include/said_optimize.h)
-OPTIMIZE_MAX_K = 64
-OPT_CONVERGED, OPT_MAX_ITER, OPT_NOT_FINITE = 0, 1, 2   # SAID_OPTIMIZE_*
 
 
 class OptimizeEngine(_Context):
@@ -904,31 +949,24 @@ class OptimizeEngine(_Context):
 
     def set_bases(self, neutrals: np.ndarray, bdeltas: np.ndarray, ps: np.ndarray):
         """neutrals (nb, 3V), bdeltas (nb, 3V, K) = B - n, ps (nb, K, K) = B_delta' B_delta, float64."""
-        n = np.ascontiguousarray(neutrals, dtype=np.float64)
-        b = np.ascontiguousarray(bdeltas, dtype=np.float64)
-        p = np.ascontiguousarray(ps, dtype=np.float64)
+        n, b, p = _f64(neutrals), _f64(bdeltas), _f64(ps)
         nb, n3v, k = b.shape
-        with torch.cuda.device(self.index):
-            self._call("said_optimize_set_bases", nb, k, n3v, _dp(n), _dp(b), _dp(p), _stream())
+        self._go("said_optimize_set_bases", nb, k, n3v, _dp(n), _dp(b), _dp(p))
         self.nbasis, self.n3v, self.k = nb, n3v, k
 
     def rhs(self, basis: int, verts: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """q (frames, K) float64 device tensor for verts, a contiguous (frames, 3V) float64 device tensor."""
-        if not verts.is_cuda or verts.dtype != torch.float64 or verts.dim() != 2 or verts.shape[1] != self.n3v or not verts.is_contiguous():
-            raise EngineError(f"vertices must be a contiguous (frames, {self.n3v}) float64 device tensor, got {tuple(verts.shape)} {verts.dtype}")
+        _dev(verts, "vertices", torch.float64, trailing=(self.n3v,), strict=True)
         if out is None:
             out = torch.empty(verts.shape[0], self.k, dtype=torch.float64, device=verts.device)
-        with torch.cuda.device(self.index):
-            self._call("said_optimize_rhs", int(basis), _ptr(verts), verts.shape[0], _ptr(out), _stream())
+        self._go("said_optimize_rhs", int(basis), _ptr(verts), verts.shape[0], _ptr(out))
         return out
 
     def solve(self, q: torch.Tensor, offsets: np.ndarray, basis: np.ndarray, delta: float, coupled: bool, max_iter: int, tol: float,
               want_duals: bool = False):
         """(w (frames, K), z (frames, 4, K) or None, status, iters, resid (nseq, 3)); w and z float64 device tensors."""
-        if not q.is_cuda or q.dtype != torch.float64 or q.dim() != 2 or q.shape[1] != self.k or not q.is_contiguous():
-            raise EngineError(f"q must be a contiguous (frames, {self.k}) float64 device tensor")
-        offs = np.ascontiguousarray(offsets, dtype=np.int64)
-        bas = np.ascontiguousarray(basis, dtype=np.int32)
+        _dev(q, "q", torch.float64, trailing=(self.k,), strict=True)
+        offs, bas = _i64(offsets), _i32(basis)
         nseq = bas.shape[0]
         if offs.shape != (nseq + 1,) or offs[-1] != q.shape[0]:
             raise EngineError(f"offsets must have nseq + 1 = {nseq + 1} entries ending at the {q.shape[0]} frames of q")
@@ -936,36 +974,15 @@ class OptimizeEngine(_Context):
         z = torch.empty(q.shape[0], 4, self.k, dtype=torch.float64, device=q.device) if want_duals else None
         st, it = np.zeros(nseq, dtype=np.int32), np.zeros(nseq, dtype=np.int32)
         res = np.zeros((nseq, 3))
-        ip = POINTER(c_int)
-        with torch.cuda.device(self.index):
-            self._call("said_optimize_solve", nseq, offs.ctypes.data_as(_c_ll_p), bas.ctypes.data_as(ip), _ptr(q), float(delta),
-                       int(bool(coupled)), int(max_iter), float(tol), _ptr(w), _ptr(z), st.ctypes.data_as(ip),
-                       it.ctypes.data_as(ip), _dp(res), _stream())
+        self._go("said_optimize_solve", nseq, _lp(offs), _ip(bas), _ptr(q), float(delta), int(bool(coupled)), int(max_iter), float(tol), _ptr(w),
+                 _ptr(z), _ip(st), _ip(it), _dp(res))
         return w, z, st, it, res
-
-
-# ---- BCVAE trainer (include/said_train.h)
-# SAID_TRAIN_* of include/said_train.h
-TRAIN_NSCAL, TRAIN_NACC, TRAIN_ITEM = 16, 8, 4
-(TRAIN_S_LR, TRAIN_S_WD_FACTOR, TRAIN_S_STEP_SIZE, TRAIN_S_BC2_SQRT, TRAIN_S_EMA_OMD, TRAIN_S_BETA, TRAIN_S_WVEL, TRAIN_S_OMB1, TRAIN_S_B2,
- TRAIN_S_OMB2, TRAIN_S_EPS, TRAIN_S_USE_EMA) = range(12)
-TRAIN_STATE, TRAIN_EMA, TRAIN_GRAD, TRAIN_EXP_AVG, TRAIN_EXP_AVG_SQ = range(5)
-TRAIN_OK, TRAIN_NOT_FINITE = 0, 1
-TRAIN_SET_TRAIN, TRAIN_SET_VAL = 0, 1
-
-
-def _f32(a) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.float32)
-
-
-def _i32(a) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 class _TrainContext(_Context):
     """What the two trainer contexts bind alike (<prefix>_set_tensor, _get_tensor, _reset_optimizer, _apply_update, _read_losses,
-    _last_losses); a subclass names how many values its _last_losses gives and the pointer type its tensor entries are bound with."""
-    n_last, _tensor_ptr = 0, _c_float_p
+    _last_losses); a subclass names how many values its _last_losses gives and the pointer helper of the type its tensor entries are bound with."""
+    n_last, _tensor_ptr = 0, staticmethod(_fp)
 
     @staticmethod
     def _dtype(name: str):
@@ -974,19 +991,18 @@ class _TrainContext(_Context):
 
     def set_tensor(self, which: int, name: str, value) -> None:
         a = np.ascontiguousarray(value, dtype=self._dtype(name)).reshape(-1)
-        self._call(self.prefix + "_set_tensor", which, name.encode(), a.ctypes.data_as(self._tensor_ptr), a.size)
+        self._call(self.prefix + "_set_tensor", which, name.encode(), self._tensor_ptr(a), a.size)
 
     def get_tensor(self, which: int, name: str, numel: int) -> np.ndarray:
         a = np.empty(numel, dtype=self._dtype(name))
-        self._call(self.prefix + "_get_tensor", which, name.encode(), a.ctypes.data_as(self._tensor_ptr), numel)
+        self._call(self.prefix + "_get_tensor", which, name.encode(), self._tensor_ptr(a), numel)
         return a
 
     def reset_optimizer(self) -> None:
         self._call(self.prefix + "_reset_optimizer")
 
     def apply_update(self, scalars: np.ndarray) -> None:
-        sc = _f32(scalars)
-        self._call(self.prefix + "_apply_update", sc.ctypes.data_as(_c_float_p))
+        self._call(self.prefix + "_apply_update", _fp(_f32(scalars)))
 
     def read_losses(self, val: bool, reset: bool = True):
         acc = np.zeros(TRAIN_NACC, dtype=np.float64)   # SAID_UT_NACC is the same
@@ -996,7 +1012,7 @@ class _TrainContext(_Context):
 
     def last_losses(self) -> np.ndarray:
         out = np.zeros(self.n_last, dtype=np.float32)
-        self._call(self.prefix + "_last_losses", out.ctypes.data_as(_c_float_p))
+        self._call(self.prefix + "_last_losses", _fp(out))
         return out
 
 
@@ -1005,6 +1021,7 @@ class TrainEngine(_TrainContext):
     window sets, and the captured training step.  Host arrays in and out (numpy); the context keeps its own stream."""
     prefix, group, n_last = "said_train", "train", 4   # last_losses: reconst, regularize, velocity, total
     cpu_error, cpu_message = NoCpuPathError, "said_amd trains the BCVAE on MI355X only (device={}); there is no CPU path"
+    _tensor_ptr = staticmethod(_vp)   # float32, or the int64 of a num_batches_tracked
 
     def __init__(self, device: torch.device, max_batch: int):
         super().__init__(device)
@@ -1013,51 +1030,35 @@ class TrainEngine(_TrainContext):
         self.tensors = [(self.lib.said_train_tensor_name(i).decode(), int(self.lib.said_train_tensor_numel(i)),
                          bool(self.lib.said_train_tensor_is_counter(i))) for i in range(70)]
 
-    _tensor_ptr = c_void_p   # float32, or the int64 of a num_batches_tracked
-
     @staticmethod
     def _dtype(name: str):
         return np.int64 if name.endswith("num_batches_tracked") else np.float32
 
     def set_data(self, which_set: int, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, mirror: np.ndarray) -> None:
-        fr, off, ln, mi = _f32(frames), np.ascontiguousarray(offsets, dtype=np.int64), _i32(lengths), _i32(mirror)
-        self._call("said_train_set_data", which_set, fr.ctypes.data_as(_c_float_p), fr.shape[0], off.ctypes.data_as(_c_ll_p),
-                   ln.ctypes.data_as(POINTER(c_int)), ln.size, mi.ctypes.data_as(POINTER(c_int)))
+        fr, off, ln, mi = _f32(frames), _i64(offsets), _i32(lengths), _i32(mirror)
+        self._call("said_train_set_data", which_set, _fp(fr), fr.shape[0], _lp(off), _ip(ln), ln.size, _ip(mi))
 
     def gather(self, which_set: int, items: np.ndarray) -> np.ndarray:
         it = _i32(items)
         x = np.empty((it.shape[0], 120, 32), dtype=np.float32)
-        self._call("said_train_gather", which_set, it.shape[0], it.ctypes.data_as(POINTER(c_int)), x.ctypes.data_as(_c_float_p))
+        self._call("said_train_gather", which_set, it.shape[0], _ip(it), _fp(x))
         return x
 
-    @staticmethod
-    def _opt_f32(a):
-        return None if a is None else _f32(a)
-
     def step(self, items: np.ndarray, eps: np.ndarray, scalars: np.ndarray, std: Optional[np.ndarray], use_graph: bool = True) -> None:
-        it, ep, sc, sd = _i32(items), _f32(eps), _f32(scalars), self._opt_f32(std)
-        self._call("said_train_step", it.shape[0], it.ctypes.data_as(POINTER(c_int)), ep.ctypes.data_as(_c_float_p),
-                   sc.ctypes.data_as(_c_float_p), None if sd is None else sd.ctypes.data_as(_c_float_p), int(bool(use_graph)))
+        it, ep, sc, sd = _i32(items), _f32(eps), _f32(scalars), _f32(std)
+        self._call("said_train_step", it.shape[0], _ip(it), _fp(ep), _fp(sc), _fp(sd), int(bool(use_graph)))
 
     def eval_loss(self, which_set: int, items: np.ndarray, eps: np.ndarray, scalars: np.ndarray, std: Optional[np.ndarray], ema: bool) -> None:
-        it, ep, sc, sd = _i32(items), _f32(eps), _f32(scalars), self._opt_f32(std)
-        self._call("said_train_eval_loss", which_set, it.shape[0], it.ctypes.data_as(POINTER(c_int)), ep.ctypes.data_as(_c_float_p),
-                   sc.ctypes.data_as(_c_float_p), None if sd is None else sd.ctypes.data_as(_c_float_p), int(bool(ema)))
+        it, ep, sc, sd = _i32(items), _f32(eps), _f32(scalars), _f32(std)
+        self._call("said_train_eval_loss", which_set, it.shape[0], _ip(it), _fp(ep), _fp(sc), _fp(sd), int(bool(ema)))
 
     def bn_stats(self, bn: int, channels: int) -> np.ndarray:
         out = np.zeros(2 * channels, dtype=np.float32)
-        self._call("said_train_bn_stats", bn, out.ctypes.data_as(_c_float_p))
+        self._call("said_train_bn_stats", bn, _fp(out))
         return out.reshape(2, channels)
 
     def graph_count(self) -> int:
         return int(self.lib.said_train_graph_count(self.h))
-
-
-# ---- UNet denoiser trainer (include/said_unet_train.h)
-UT_NSCAL, UT_NACC, UT_NUM_TENSORS = 16, 8, 161   # SAID_UT_*
-(UT_S_LR, UT_S_WD_FACTOR, UT_S_STEP_SIZE, UT_S_BC2_SQRT, UT_S_EMA_OMD, UT_S_WVEL, UT_S_WVERTEX, UT_S_OMB1, UT_S_B2, UT_S_OMB2, UT_S_EPS,
- UT_S_USE_EMA, UT_S_PRED_TYPE, UT_S_DROPOUT) = range(14)
-UT_STATE, UT_EMA, UT_GRAD, UT_EXP_AVG, UT_EXP_AVG_SQ, UT_STASH = range(6)
 
 
 class UNetTrainEngine(_TrainContext):
@@ -1071,10 +1072,7 @@ class UNetTrainEngine(_TrainContext):
         if feature_dim is None:   # the entry point without a feature_dim: the default context, as feature_dim=-1 is
             self._create(int(max_batch), int(max_frames))
         else:
-            h = c_void_p()
-            if self.lib.said_unet_train_create_dim(ctypes.byref(h), self.index, int(max_batch), int(max_frames), int(feature_dim)) != 0:
-                raise EngineError("said_unet_train_create_dim: " + self._last_error(None))
-            self.h = h
+            self._create(int(max_batch), int(max_frames), int(feature_dim), entry="said_unet_train_create_dim")
         self.max_batch, self.max_frames = int(max_batch), int(max_frames)
         self.feature_dim = int(self.lib.said_unet_train_feature_dim(self.h))   # -1: no audio_proj_layer
         self.tensors = [(self.lib.said_unet_train_context_tensor_name(self.h, i).decode(), int(self.lib.said_unet_train_context_tensor_numel(self.h, i)))
@@ -1085,68 +1083,43 @@ class UNetTrainEngine(_TrainContext):
 
     def set_alphas(self, alphas_cumprod) -> None:
         a = _f32(alphas_cumprod).reshape(-1)
-        self._call("said_unet_train_set_alphas", a.ctypes.data_as(_c_float_p), a.size)
+        self._call("said_unet_train_set_alphas", _fp(a), a.size)
 
     def _batch(self, x, timesteps, cond, audio):
-        """(B, T, pointers) of a batch; keeps the converted arrays alive in the returned tuple."""
+        """(B, T, x, timesteps, cond, the audio embedding, its pointer, whether that is a device pointer) of a batch, as arrays of the bound types."""
         x = _f32(x)
         B, T = x.shape[0], x.shape[1]
-        ts = np.ascontiguousarray(timesteps, dtype=np.int64).reshape(-1)
+        ts = _i64(timesteps).reshape(-1)
         cd = _i32(np.asarray(cond).astype(np.int32)).reshape(-1)
         if isinstance(audio, torch.Tensor) and audio.is_cuda:
-            au = _check_dev(audio, "audio_embedding")
+            au = _dev(audio, "audio_embedding")
             torch.cuda.current_stream(au.device).synchronize()   # the context copies it on its own stream
-            ap, on_dev = c_void_p(au.data_ptr()), 1
+            ap, on_dev = _ptr(au), 1
         else:
-            au = _f32(audio.cpu().numpy() if isinstance(audio, torch.Tensor) else audio)
-            ap, on_dev = au.ctypes.data_as(c_void_p), 0
+            au = host_f32(audio)
+            ap, on_dev = _vp(au), 0
         if x.shape != (B, T, 32) or ts.size != B or cd.size != B or tuple(au.shape) != (B, T, 768):
             raise EngineError(f"batch shapes: x {x.shape}, timesteps {ts.shape}, cond {cd.shape}, audio embedding {tuple(au.shape)}")
         return B, T, x, ts, cd, au, ap, on_dev
 
-    @staticmethod
-    def _opt(a):
-        return (None, None) if a is None else (lambda v: (v, v.ctypes.data_as(_c_float_p)))(_f32(a))
-
     def step(self, coeffs, noise, timesteps, cond, audio, dropout_seed: int, scalars, std=None, deltas=None) -> None:
         B, T, x, ts, cd, au, ap, on_dev = self._batch(coeffs, timesteps, cond, audio)
-        nz, sc = _f32(noise), _f32(scalars)
-        (sd, sdp), (dl, dlp) = self._opt(std), self._opt(deltas)
+        nz, sc, sd, dl = _f32(noise), _f32(scalars), _f32(std), _f32(deltas)
         V = 0 if dl is None else dl.shape[-1] // 3
-        self._call("said_unet_train_step", B, T, x.ctypes.data_as(_c_float_p), nz.ctypes.data_as(_c_float_p), ts.ctypes.data_as(_c_ll_p),
-                   cd.ctypes.data_as(POINTER(c_int)), ap, on_dev, _c_ull(int(dropout_seed) & (2 ** 64 - 1)), sc.ctypes.data_as(_c_float_p), sdp, dlp, V)
+        self._call("said_unet_train_step", B, T, _fp(x), _fp(nz), _lp(ts), _ip(cd), ap, on_dev, _c_ull(int(dropout_seed) & (2 ** 64 - 1)), _fp(sc),
+                   _fp(sd), _fp(dl), V)
 
     def eval_loss(self, coeffs, noise, timesteps, cond, audio, scalars, std=None, deltas=None, ema: bool = False) -> None:
         B, T, x, ts, cd, au, ap, on_dev = self._batch(coeffs, timesteps, cond, audio)
-        nz, sc = _f32(noise), _f32(scalars)
-        (sd, sdp), (dl, dlp) = self._opt(std), self._opt(deltas)
+        nz, sc, sd, dl = _f32(noise), _f32(scalars), _f32(std), _f32(deltas)
         V = 0 if dl is None else dl.shape[-1] // 3
-        self._call("said_unet_train_eval_loss", B, T, x.ctypes.data_as(_c_float_p), nz.ctypes.data_as(_c_float_p), ts.ctypes.data_as(_c_ll_p),
-                   cd.ctypes.data_as(POINTER(c_int)), ap, on_dev, sc.ctypes.data_as(_c_float_p), sdp, dlp, V, int(bool(ema)))
+        self._call("said_unet_train_eval_loss", B, T, _fp(x), _fp(nz), _lp(ts), _ip(cd), ap, on_dev, _fp(sc), _fp(sd), _fp(dl), V, int(bool(ema)))
 
     def forward_only(self, sample, timesteps, cond, audio, ema: bool = False) -> np.ndarray:
         B, T, x, ts, cd, au, ap, on_dev = self._batch(sample, timesteps, cond, audio)
         out = np.empty((B, T, 32), dtype=np.float32)
-        self._call("said_unet_train_forward_only", B, T, x.ctypes.data_as(_c_float_p), ts.ctypes.data_as(_c_ll_p), cd.ctypes.data_as(POINTER(c_int)),
-                   ap, on_dev, int(bool(ema)), out.ctypes.data_as(_c_float_p))
+        self._call("said_unet_train_forward_only", B, T, _fp(x), _lp(ts), _ip(cd), ap, on_dev, int(bool(ema)), _fp(out))
         return out
-
-
-
-# ---- renderer (include/said_render.h)
-RENDER_MAX_K, RENDER_MAX_LIGHTS, RENDER_LUT = 64, 4, 256   # SAID_RENDER_*
-
-
-class RenderScene(ctypes.Structure):
-    """said_render_scene."""
-    _fields_ = [
-        ("width", c_int), ("height", c_int),
-        ("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float), ("znear", c_float), ("zfar", c_float),
-        ("cam_pos", c_float * 3), ("n_lights", c_int),
-        ("light_pos", (c_float * 3) * RENDER_MAX_LIGHTS), ("light_intensity", c_float * RENDER_MAX_LIGHTS),
-        ("ambient", c_float), ("base_color", c_float * 3),
-        ("metallic", c_float), ("roughness", c_float), ("vc_metallic", c_float), ("vc_roughness", c_float),
-    ]
 
 
 class RenderEngine(_Context):
@@ -1162,19 +1135,18 @@ class RenderEngine(_Context):
 
     def set_mesh(self, neutral: np.ndarray, faces: np.ndarray, blendshapes_matrix: np.ndarray) -> None:
         """neutral (V, 3), faces (F, 3) vertex indices, blendshapes_matrix (3V, K) = [b_1 | ... | b_K] (not deltas)."""
-        n = np.ascontiguousarray(neutral, dtype=np.float64).reshape(-1, 3)
+        n = _f64(neutral).reshape(-1, 3)
         fa = np.asarray(faces)
         if fa.ndim != 2 or fa.shape[1] != 3 or fa.dtype.kind not in "iu":
             raise EngineError(f"faces must be an (F, 3) integer array, got {fa.shape} {fa.dtype}")
         if fa.size and (fa.min() < -2**31 or fa.max() >= 2**31):
             raise EngineError("faces hold indices outside int32")
-        fa = np.ascontiguousarray(fa, dtype=np.int32)
-        b = np.ascontiguousarray(blendshapes_matrix, dtype=np.float64)
+        fa = _i32(fa)
+        b = _f64(blendshapes_matrix)
         if b.ndim != 2 or b.shape[0] != n.size:
             raise EngineError(f"blendshapes_matrix must be (3V, K) = ({n.size}, K), got {b.shape}")
         self.nv = self.nf = self.k = 0
-        with torch.cuda.device(self.index):
-            self._call("said_render_set_mesh", n.shape[0], fa.shape[0], b.shape[1], _dp(n), fa.ctypes.data_as(POINTER(c_int)), _dp(b), _stream())
+        self._go("said_render_set_mesh", n.shape[0], fa.shape[0], b.shape[1], _dp(n), _ip(fa), _dp(b))
         self.nv, self.nf, self.k = n.shape[0], fa.shape[0], b.shape[1]
 
     def set_scene(self, scene: RenderScene) -> None:
@@ -1186,8 +1158,7 @@ class RenderEngine(_Context):
         a = _f32(lut)
         if a.shape != (RENDER_LUT, 3):
             raise EngineError(f"the colour table must be ({RENDER_LUT}, 3), got {a.shape}")
-        with torch.cuda.device(self.index):
-            self._call("said_render_set_colormap", a.ctypes.data_as(_c_float_p), _stream())
+        self._go("said_render_set_colormap", _fp(a))
 
     def render(self, coeffs: torch.Tensor, t0: int, n_frames: int, out: torch.Tensor, target: Optional[torch.Tensor] = None, max_diff: float = 0.001,
                rot=None, t_center=None, face_ids: Optional[torch.Tensor] = None, samples: int = 1, sample_ids: Optional[torch.Tensor] = None) -> None:
@@ -1197,39 +1168,31 @@ class RenderEngine(_Context):
         contiguous (>= n_frames, H, W, 4) int32 device tensor: the face of each of a pixel's four samples."""
         if self.nf == 0:
             raise EngineError(("said_render_render" if samples == 1 and sample_ids is None else "said_render_render_ms") + ": no mesh set (set_mesh)")
-        coeffs = _check_dev(coeffs, "blendshape_coeffs")
+        coeffs = _dev(coeffs, "blendshape_coeffs", index=self.index)
         if coeffs.dim() != 2 or coeffs.shape[1] != self.k:
             raise EngineError(f"blendshape_coeffs must be (T, {self.k}), got {tuple(coeffs.shape)}")
         if t0 < 0 or n_frames < 1 or t0 + n_frames > coeffs.shape[0]:
             raise EngineError(f"frames [{t0}, {t0 + n_frames}) lie outside the {coeffs.shape[0]} frames of blendshape_coeffs")
         if target is not None:
-            target = _check_dev(target, "target_blendshape_coeffs")
+            target = _dev(target, "target_blendshape_coeffs")
             if target.shape != coeffs.shape:
                 raise EngineError(f"target_blendshape_coeffs must have the shape of blendshape_coeffs {tuple(coeffs.shape)}, got {tuple(target.shape)}")
-        need = n_frames * self.height * self.width
+        need = n_frames * self.height * self.width   # room for n_frames frames of height x width
         for t, name, dt, per in ((out, "out", torch.uint8, 3), (face_ids, "face_ids", torch.int32, 1), (sample_ids, "sample_ids", torch.int32, 4)):
-            if t is None:
-                continue
-            if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() < need * per or t.device.index != self.index:
-                raise EngineError(f"{name} must be a contiguous {dt} tensor on cuda:{self.index} with room for {n_frames} frames of {self.height} x {self.width}")
-        if coeffs.device.index != self.index:
-            raise EngineError(f"blendshape_coeffs live on cuda:{coeffs.device.index}, this renderer on cuda:{self.index}")
-        r = None if rot is None else np.ascontiguousarray(rot, dtype=np.float64).reshape(3)
-        c = None if t_center is None else np.ascontiguousarray(t_center, dtype=np.float64).reshape(3)
-        with torch.cuda.device(self.index):
-            if samples == 1 and sample_ids is None:
-                self._call("said_render_render", _ptr(coeffs), _ptr(target), int(t0), int(n_frames), float(max_diff), None if r is None else _dp(r),
-                           None if c is None else _dp(c), _ptr(out), _ptr(face_ids), _stream())
-            else:   # what goes with which sample count is said_render_render_ms's to refuse
-                load_library("render_ms")
-                self._call("said_render_render_ms", int(samples), _ptr(coeffs), _ptr(target), int(t0), int(n_frames), float(max_diff),
-                           None if r is None else _dp(r), None if c is None else _dp(c), _ptr(out), _ptr(face_ids), _ptr(sample_ids), _stream())
+            if t is not None:
+                _dev(t, name, dt, self.index, numel=need * per, strict=True)
+        r, c = (None if a is None else _f64(a).reshape(3) for a in (rot, t_center))
+        if samples == 1 and sample_ids is None:
+            self._go("said_render_render", _ptr(coeffs), _ptr(target), int(t0), int(n_frames), float(max_diff), _dp(r), _dp(c), _ptr(out), _ptr(face_ids))
+        else:   # what goes with which sample count is said_render_render_ms's to refuse
+            load_library("render_ms")
+            self._go("said_render_render_ms", int(samples), _ptr(coeffs), _ptr(target), int(t0), int(n_frames), float(max_diff), _dp(r), _dp(c),
+                     _ptr(out), _ptr(face_ids), _ptr(sample_ids))
         self._keep = (coeffs, target)   # alive until the next call: the kernels may still be reading them
 
     def _read(self, name: str, n_frames: int) -> np.ndarray:
         out = np.empty((n_frames, self.nv, 3), dtype=np.float32)
-        with torch.cuda.device(self.index):
-            self._call(name, int(n_frames), out.ctypes.data_as(_c_float_p), _stream())
+        self._go(name, int(n_frames), _fp(out))
         return out
 
     def read_vertices(self, n_frames: int) -> np.ndarray:
@@ -1242,10 +1205,6 @@ class RenderEngine(_Context):
     def read_colors(self, n_frames: int) -> np.ndarray:
         """(n_frames, V, 3) difference colours (R, G, B) of the last render's chunk."""
         return self._read("said_render_read_colors", n_frames)
-
-
-# ---- JPEG encoder (include/said_jpeg.h)
-JPEG_OVERFLOW = 1   # SAID_JPEG_OVERFLOW
 
 
 class JpegEngine(_Context):
@@ -1266,7 +1225,7 @@ class JpegEngine(_Context):
             self._call("said_jpeg_configure", int(width), int(height), int(quality))
         self.width, self.height, self.quality = int(width), int(height), int(quality)
         self.blocks = ((self.width + 15) // 16) * ((self.height + 15) // 16) * 6
-        buf, size = ctypes.create_string_buffer(1024), ctypes.c_longlong(0)
+        buf, size = ctypes.create_string_buffer(1024), _c_ll(0)
         self._call("said_jpeg_header", buf, 1024, ctypes.byref(size))
         self.header = buf.raw[:size.value]   # SOI .. SOS: the same for every frame
 
@@ -1275,19 +1234,18 @@ class JpegEngine(_Context):
         """The first n_frames of frames, a contiguous (>= n_frames, H, W, 3) uint8 device tensor, into out (uint8, device): each frame's scan and
         EOI, back to back; offsets, a contiguous int64 device tensor of at least n_frames + 1 elements, receives where each starts and the
         total.  `capacity` (default: all of out) bounds what may be written.  Returns (fits, bytes required); synchronises the current stream."""
-        need = n_frames * self.height * self.width * 3
-        if n_frames < 1 or not frames.is_cuda or frames.dtype != torch.uint8 or not frames.is_contiguous() or frames.numel() < need or frames.device.index != self.index:
-            raise EngineError(f"frames must be a contiguous uint8 tensor on cuda:{self.index} holding {n_frames} >= 1 frames of {self.height} x {self.width} x 3")
-        if not offsets.is_cuda or offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.numel() < n_frames + 1 or offsets.device.index != self.index:
-            raise EngineError(f"offsets must be a contiguous int64 tensor on cuda:{self.index} with at least {n_frames + 1} elements")
-        if out is not None and (not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.device.index != self.index):
-            raise EngineError(f"out must be a contiguous uint8 tensor on cuda:{self.index}")
+        if n_frames < 1:
+            raise EngineError(f"n_frames must be at least 1, got {n_frames}")
+        _dev(frames, "frames", torch.uint8, self.index, numel=n_frames * self.height * self.width * 3, strict=True)   # n_frames of height x width x 3
+        _dev(offsets, "offsets", torch.int64, self.index, numel=n_frames + 1, strict=True)
+        if out is not None:
+            _dev(out, "out", torch.uint8, self.index, strict=True)
         room = 0 if out is None else out.numel()
         cap = room if capacity is None else int(capacity)
         if cap < 0 or cap > room:
             raise EngineError(f"capacity {cap} lies outside the {room} bytes of out")
-        required = ctypes.c_longlong(0)
-        with torch.cuda.device(self.index):
+        required = _c_ll(0)
+        with torch.cuda.device(self.index):   # (1, SAID_JPEG_OVERFLOW, is an answer, not an error: no _go)
             rc = self.lib.said_jpeg_encode(self.h, _ptr(frames), int(n_frames), 1 if bgr else 0, _ptr(out), cap, _ptr(offsets), ctypes.byref(required), _stream())
         if rc not in (0, JPEG_OVERFLOW):
             raise EngineError("said_jpeg_encode: " + self._last_error(self.h))
@@ -1296,24 +1254,8 @@ class JpegEngine(_Context):
     def read_coefficients(self, n_frames: int) -> np.ndarray:
         """(n_frames, blocks, 64) int16: the last encode's quantised coefficients, blocks in scan order, each in zigzag order."""
         out = np.empty((n_frames, self.blocks, 64), dtype=np.int16)
-        with torch.cuda.device(self.index):
-            self._call("said_jpeg_read_coefficients", int(n_frames), out.ctypes.data_as(c_void_p), _stream())
+        self._go("said_jpeg_read_coefficients", int(n_frames), _vp(out))
         return out
-
-
-# ---- beat consistency and vertex error (include/said_beat.h)
-BEAT_N_FFT, BEAT_HOP, BEAT_N_MELS = 2048, 512, 128   # SAID_BEAT_*
-
-
-def _i64(a) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.int64)
-
-
-def host_f32(a) -> np.ndarray:
-    """A contiguous float32 host array of an array, a list or a tensor (on any device)."""
-    if isinstance(a, torch.Tensor):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(a, dtype=np.float32)
 
 
 class BeatEngine(_Context):
@@ -1330,11 +1272,6 @@ class BeatEngine(_Context):
         if sampling_rate is not None:
             self.set_sampling_rate(sampling_rate)
 
-    def _f32_dev(self, t: torch.Tensor, name: str) -> torch.Tensor:
-        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.device.index != self.index:
-            raise EngineError(f"{name} must be a contiguous float32 tensor on cuda:{self.index}, got {t.dtype} on {t.device}")
-        return t
-
     def set_sampling_rate(self, sampling_rate: int):
         """Forms the mel bank of the rate; returns librosa's peak-pick windows in frames (pre_max, post_max, pre_avg, post_avg, wait)."""
         pick = (c_int * 5)()
@@ -1346,23 +1283,21 @@ class BeatEngine(_Context):
 
     def clips(self, wave: torch.Tensor, offsets) -> np.ndarray:
         """Analyse the clips wave[offsets[i]:offsets[i + 1]] (one float32 device vector); returns the first frame number of each clip, (n + 1)."""
-        wave, offs = self._f32_dev(wave, "the waveforms"), _i64(offsets)
+        wave, offs = _dev(wave, "the waveforms", index=self.index, strict=True), _i64(offsets)
         if wave.dim() != 1 or offs.ndim != 1 or offs.shape[0] < 2 or offs[-1] != wave.shape[0]:
             raise EngineError(f"offsets must have n + 1 >= 2 entries ending at the {wave.numel()} samples of the waveforms")
         self.frame_start = None
-        with torch.cuda.device(self.index):
-            self._call("said_beat_clips", _ptr(wave), offs.shape[0] - 1, offs.ctypes.data_as(_c_ll_p), _stream())
+        self._go("said_beat_clips", _ptr(wave), offs.shape[0] - 1, _lp(offs))
         self.frame_start = np.concatenate([[0], np.cumsum(1 + np.diff(offs) // BEAT_HOP)]).astype(np.int64)
         return self.frame_start
 
     def coeffs(self, coeffs: torch.Tensor, offsets, threshold: float) -> None:
         """Change rates and their minima of the sequences coeffs[offsets[i]:offsets[i + 1]], a (frames, channels) float32 device tensor."""
-        coeffs, offs = self._f32_dev(coeffs, "the coefficients"), _i64(offsets)
+        coeffs, offs = _dev(coeffs, "the coefficients", index=self.index, strict=True), _i64(offsets)
         if coeffs.dim() != 2 or offs.ndim != 1 or offs.shape[0] < 2 or offs[-1] != coeffs.shape[0]:
             raise EngineError(f"offsets must have n + 1 >= 2 entries ending at the {coeffs.shape[0]} frames of the coefficients")
         self.seq_off = None
-        with torch.cuda.device(self.index):
-            self._call("said_beat_coeffs", _ptr(coeffs), offs.shape[0] - 1, offs.ctypes.data_as(_c_ll_p), coeffs.shape[1], float(threshold), _stream())
+        self._go("said_beat_coeffs", _ptr(coeffs), offs.shape[0] - 1, _lp(offs), coeffs.shape[1], float(threshold))
         self.seq_off = offs
 
     def score(self, clip_index, fps: float, sigma: float) -> np.ndarray:
@@ -1373,44 +1308,38 @@ class BeatEngine(_Context):
         if idx.shape != (self.seq_off.shape[0] - 1,):
             raise EngineError(f"clip_index must name one clip for each of the {self.seq_off.shape[0] - 1} sequences")
         out = np.empty(idx.shape[0])
-        with torch.cuda.device(self.index):
-            self._call("said_beat_score", idx.ctypes.data_as(_c_int_p), float(fps), float(sigma), _dp(out), _stream())
+        self._go("said_beat_score", _ip(idx), float(fps), float(sigma), _dp(out))
         return out
 
     def set_deltas(self, deltas: np.ndarray) -> None:
         """deltas (persons, channels, 3V) float64."""
-        d = np.ascontiguousarray(deltas, dtype=np.float64)
+        d = _f64(deltas)
         if d.ndim != 3:
             raise EngineError(f"deltas must be (persons, channels, 3V), got {d.shape}")
         self.delta_shape = None
-        with torch.cuda.device(self.index):
-            self._call("said_beat_set_deltas", d.shape[0], d.shape[1], d.shape[2], _dp(d), _stream())
+        self._go("said_beat_set_deltas", d.shape[0], d.shape[1], d.shape[2], _dp(d))
         self.delta_shape = d.shape
 
     def vertex_error(self, coeffs: torch.Tensor, real_off, eval_off, length, person) -> np.ndarray:
         """(n_pairs,) float64: max over t < length[p] of |(coeffs[real_off[p] + t] - coeffs[eval_off[p] + t]) @ deltas[person[p]]|."""
         if self.delta_shape is None:
             raise EngineError("vertex_error() needs set_deltas() first")
-        coeffs = self._f32_dev(coeffs, "the coefficients")
+        coeffs = _dev(coeffs, "the coefficients", index=self.index, strict=True)
         ro, eo, ln, pe = _i64(real_off), _i64(eval_off), _i32(length), _i32(person)
         if coeffs.dim() != 2 or coeffs.shape[1] != self.delta_shape[1] or not (ro.shape == eo.shape == ln.shape == pe.shape) or ro.ndim != 1:
             raise EngineError(f"coefficients must be (frames, {self.delta_shape[1]}) and the four pair tables of one length")
         out = np.empty(ro.shape[0])
-        with torch.cuda.device(self.index):
-            self._call("said_beat_vertex_error", _ptr(coeffs), coeffs.shape[0], ro.shape[0], ro.ctypes.data_as(_c_ll_p), eo.ctypes.data_as(_c_ll_p),
-                       ln.ctypes.data_as(_c_int_p), pe.ctypes.data_as(_c_int_p), _dp(out), _stream())
+        self._go("said_beat_vertex_error", _ptr(coeffs), coeffs.shape[0], ro.shape[0], _lp(ro), _lp(eo), _ip(ln), _ip(pe), _dp(out))
         return out
 
     def _lists(self, name: str, start: np.ndarray):
         counts, flat = np.zeros(start.shape[0] - 1, dtype=np.int32), np.zeros(int(start[-1]), dtype=np.int32)
-        with torch.cuda.device(self.index):
-            self._call(name, counts.ctypes.data_as(_c_int_p), flat.ctypes.data_as(_c_int_p), _stream())
+        self._go(name, _ip(counts), _ip(flat))
         return [flat[int(s):int(s) + int(n)].copy() for s, n in zip(start[:-1], counts)]
 
     def _array(self, name: str, shape) -> np.ndarray:
         out = np.empty(shape)
-        with torch.cuda.device(self.index):
-            self._call(name, _dp(out), _stream())
+        self._go(name, _dp(out))
         return out
 
     def read_mel(self) -> np.ndarray:
@@ -1435,30 +1364,6 @@ class BeatEngine(_Context):
         return self._lists("said_beat_read_minima", self.seq_off)
 
 
-# ---- deformation transfer (include/said_transfer.h)
-TRANSFER_CONVERGED, TRANSFER_MAX_ITER, TRANSFER_NOT_FINITE = 0, 1, 2   # SAID_TRANSFER_*
-TRANSFER_ROW_SMOOTH, TRANSFER_ROW_IDENTITY, TRANSFER_ROW_CLOSEST, TRANSFER_ROW_UNIT = range(4)
-TRANSFER_RHS_PAIR, TRANSFER_RHS_IDENTITY, TRANSFER_RHS_ANCHOR = range(3)
-_TRANSFER_ARRAYS = ("rowptr", "col", "c0", "c1", "rowclass", "rowaux", "rhsclass", "at_rowptr", "at_col", "at_src")
-
-
-class TransferSystem(ctypes.Structure):
-    """said_transfer_system: the host-built index structure of a system."""
-    _fields_ = [("m", c_int), ("n", c_int), ("nnz", c_int)] + [(name, POINTER(c_int)) for name in _TRANSFER_ARRAYS]
-
-
-def _ip(a: Optional[np.ndarray]):
-    return None if a is None else a.ctypes.data_as(POINTER(c_int))
-
-
-def _odp(a: Optional[np.ndarray]):
-    return None if a is None else _dp(a)
-
-
-def _f64(a) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.float64)
-
-
 class TransferEngine(_Context):
     """said_transfer context on one GPU (include/said_transfer.h): the mesh passes, the three stages and the solver
     alone; float64 host arrays in and out."""
@@ -1470,14 +1375,10 @@ class TransferEngine(_Context):
         self._create()
         self.source = self.target = None   # (V, F, K) and (V, F)
 
-    def _go(self, name: str, *args) -> None:
-        with torch.cuda.device(self.index):
-            self._call(name, *args, _stream())
-
     @staticmethod
     def _system(structure: dict):
         """(TransferSystem, the arrays it points into) of a structure from said_amd.optimize.deformation_transfer."""
-        keep = {name: (None if structure.get(name) is None else _i32(structure[name])) for name in _TRANSFER_ARRAYS}
+        keep = {name: _i32(structure.get(name)) for name in _TRANSFER_ARRAYS}
         sys_ = TransferSystem(int(structure["m"]), int(structure["n"]), int(keep["col"].shape[0]), *[_ip(keep[name]) for name in _TRANSFER_ARRAYS])
         return sys_, keep
 
@@ -1487,7 +1388,7 @@ class TransferEngine(_Context):
         if sh is not None and sh.shape[1:] != v.shape:
             raise EngineError(f"shapes must be (K, {v.shape[0]}, 3), got {sh.shape}")
         k = 0 if sh is None else sh.shape[0]
-        self._go("said_transfer_set_source", v.shape[0], f.shape[0], k, _dp(v), _ip(f), _odp(sh))
+        self._go("said_transfer_set_source", v.shape[0], f.shape[0], k, _dp(v), _ip(f), _dp(sh))
         self.source = (v.shape[0], f.shape[0], k)
 
     def set_target(self, neutral, faces) -> None:
@@ -1503,12 +1404,12 @@ class TransferEngine(_Context):
         arp, ac, av, trp, tc, tv = _i32(a_rowptr), _i32(a_col), _f64(a_val), _i32(at_rowptr), _i32(at_col), _f64(at_val)
         if arp.shape[0] != m + 1 or ac.shape != av.shape or tc.shape != tv.shape or ac.shape != tc.shape:
             raise EngineError("the CSR arrays of A and A' do not fit the right-hand side")
-        x0 = None if x0 is None else _f64(x0)
+        x0 = _f64(x0)
         if x0 is not None and x0.shape != (n, r):
             raise EngineError(f"x0 must be ({n}, {r}), got {x0.shape}")
         x = np.empty((n, r))
         st, it, res = np.zeros(r, dtype=np.int32), np.zeros(r, dtype=np.int32), np.zeros(r)
-        self._go("said_transfer_solve", m, n, ac.shape[0], r, _ip(arp), _ip(ac), _dp(av), _ip(trp), _ip(tc), _dp(tv), _dp(b), _odp(x0), float(tol),
+        self._go("said_transfer_solve", m, n, ac.shape[0], r, _ip(arp), _ip(ac), _dp(av), _ip(trp), _ip(tc), _dp(tv), _dp(b), _dp(x0), float(tol),
                  int(max_iter), int(check_every), _dp(x), _ip(st), _ip(it), _dp(res))
         return x, st, it, res
 
@@ -1527,12 +1428,12 @@ class TransferEngine(_Context):
 
     def correspond(self, threshold: float, registered=None):
         """(t2s (F_t), s2t (F_s), their squared centroid distances): -1 where a triangle has no partner within the threshold."""
-        reg = None if registered is None else _f64(registered)
+        reg = _f64(registered)
         if reg is not None and reg.shape != (self.source[0], 3):
             raise EngineError(f"the registered source must be ({self.source[0]}, 3), got {reg.shape}")
         t2s, s2t = np.empty(self.target[1], dtype=np.int32), np.empty(self.source[1], dtype=np.int32)
         dt, ds = np.empty(self.target[1]), np.empty(self.source[1])
-        self._go("said_transfer_correspond", _odp(reg), float(threshold), _ip(t2s), _ip(s2t), _dp(dt), _dp(ds))
+        self._go("said_transfer_correspond", _dp(reg), float(threshold), _ip(t2s), _ip(s2t), _dp(dt), _dp(ds))
         return t2s, s2t, dt, ds
 
     def transfer(self, structure: dict, tol: float, max_iter: int):
@@ -1567,5 +1468,5 @@ class TransferEngine(_Context):
         qp, tp = _f64(qpos), _f64(tpos)
         qn, tn = (None, None) if qnrm is None else (_f64(qnrm), _f64(tnrm))
         idx, d2 = np.empty(qp.shape[0], dtype=np.int32), np.empty(qp.shape[0])
-        self._go("said_transfer_closest", qp.shape[0], _dp(qp), _odp(qn), tp.shape[0], _dp(tp), _odp(tn), _ip(idx), _dp(d2))
+        self._go("said_transfer_closest", qp.shape[0], _dp(qp), _dp(qn), tp.shape[0], _dp(tp), _dp(tn), _ip(idx), _dp(d2))
         return idx, d2

@@ -5,9 +5,7 @@ tests/golden/spec_masks.npz holds the masks of transformers 5.15.0's ``_compute_
 ``np.random.seed(1000 + i)`` for shape i of SHAPES (keys ``mask_<i>``), recorded once, so the comparison also runs where transformers is
 not installed.
 """
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -148,21 +146,3 @@ def test_masking_and_layerdrop_against_transformers_in_train_mode():
         got = ref.forward(sd, wave, None, skip=(0, 1))
         assert float((got - want).abs().max()) <= 1e-10 * max(1.0, float(want.abs().max()))
         assert torch.equal(got, ref.forward(sd, wave, None, skip=(True, True)))
-
-
-# ------------------------------------------------------------------------------------------------ the C ABI
-def test_header_matches_its_binding_table():
-    from said_amd import _engine
-    from said_amd.build import build_library
-    build_library()
-    lib = _engine.load_library("audio_train")
-    code = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, "include", "said_audio_train.h")).read(), flags=re.S)
-    decl = {name: params.count(",") + 1 for name, params in re.findall(r"\b(said_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code)}
-    assert set(decl) == set(_engine.AUDIO_TRAIN_EXPORTS) == {"said_audio_encode_train"}
-    for name, n in decl.items():
-        assert hasattr(lib, name) and len(_engine.AUDIO_TRAIN_EXPORTS[name][1]) == n
-    fields = re.search(r"typedef struct \{(.*?)\} said_audio_train_params;", code, re.S).group(1)
-    names = [n for d in fields.split(";") if d.strip() for n in re.findall(r"(\w+)\s*(?:,|$)", d.strip())]
-    assert names == [f[0] for f in _engine.AudioTrainParams._fields_]
-    assert ctypes.sizeof(_engine.AudioTrainParams) == 40 and _engine.AudioTrainParams.seed.offset == 16
-    assert lib.said_abi_version() == 9

@@ -1,9 +1,7 @@
 """CPU checks of deformation transfer: the host-built index structures of said_amd/optimize/deformation_transfer.py
-and get_submesh against the restatement (tests/deform_transfer_ref.py), the binding table against include/said_transfer.h, the landmark
-fixture, the residuals pickle's layout and script/preprocess_blendvoca.py's round trip."""
+and get_submesh against the restatement (tests/deform_transfer_ref.py), the landmark fixture, the residuals pickle's layout and script/preprocess_blendvoca.py's round trip."""
 import os
 import pickle
-import re
 
 import numpy as np
 import pytest
@@ -110,20 +108,6 @@ def test_split_mesh_keeps_the_original_vertices():
     tv, tf = R.split_in_four(verts, faces)
     assert tv.shape == (4746, 3) and tf.shape == (9216, 3) and np.array_equal(tv[:1220], verts)
     assert R.edge_pairs(tf).shape[0] > 0   # still manifold
-
-
-def test_binding_table_matches_the_header():
-    text = open(os.path.join(ROOT, "include", "said_transfer.h")).read()
-    declared = set(re.findall(r"^(?:int|const char\*)\s+(said_transfer_\w+)\(", text, flags=re.M))
-    table = _engine.TRANSFER_EXPORTS
-    assert declared == set(table) and len(declared) == 12
-    for name, (_, args) in table.items():
-        proto = re.search(r"^(?:int|const char\*)\s+" + name + r"\((.*?)\);", text, flags=re.S | re.M).group(1)
-        assert len(args) == proto.count(",") + 1, name
-    fields = re.search(r"typedef struct said_transfer_system \{(.*?)\}", text, flags=re.S).group(1)
-    assert [f for f, _ in _engine.TransferSystem._fields_] == re.findall(r"\*?(\w+)[,;]", fields)
-    for name in ("CONVERGED", "MAX_ITER", "NOT_FINITE", "ROW_SMOOTH", "ROW_IDENTITY", "ROW_CLOSEST", "ROW_UNIT", "RHS_PAIR", "RHS_IDENTITY", "RHS_ANCHOR"):
-        assert int(re.search(r"SAID_TRANSFER_" + name + r" = (\d+)", text).group(1)) == getattr(_engine, "TRANSFER_" + name)
 
 
 def test_no_cpu_path():

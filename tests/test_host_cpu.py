@@ -25,39 +25,154 @@ def test_library_exports_every_declared_symbol():
     assert declared, "no declarations parsed"
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/said_hip.h but not exported"
-    assert declared == set(_engine.EXPORTS), (declared ^ set(_engine.EXPORTS))
+    core = set(_engine.ABI["core"].table)
+    assert declared == core, (declared ^ core)
     assert lib.said_abi_version() == _engine.ABI_VERSION == 9
 
 
-def _declarations(path):
-    """{said_* entry point: parameter count} of the declarations in a header."""
-    code = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, path)).read(), flags=re.S)
-    return {name: 0 if params.strip() in ("", "void") else params.count(",") + 1
-            for name, params in re.findall(r"\b(said_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code)}
+# ---------------------------------------------------------------- the headers against the one binding table, _engine.ABI
+GROUP_DECLARATIONS = {"core": 48, "metrics": 12, "optimize": 6, "train": 18, "render": 10, "render_ms": 1, "jpeg": 7, "unet_train": 24, "beat": 14, "transfer": 12, "audio_train": 1}   # 153
+_C_SCALARS = {"int": ("int", 4), "unsigned": ("int", 4), "unsigned int": ("int", 4), "uint32_t": ("int", 4), "long long": ("int", 8), "unsigned long long": ("int", 8), "int64_t": ("int", 8),
+              "uint64_t": ("int", 8), "char": ("int", 1), "uint8_t": ("int", 1), "short": ("int", 2), "float": ("float", 4), "double": ("float", 8), "void": ("void", 0)}
+_POINTER = ("pointer", ctypes.sizeof(ctypes.c_void_p))
+_c_kind = lambda base, stars: _POINTER if stars else _C_SCALARS[base]   # (kind, size in bytes) of a C type: pointer, int, float or void
+_code = lambda text: re.sub(r"^[ \t]*#.*$", "", re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S), flags=re.M)   # C text without comments and preprocessor lines
+_header = lambda path: _code(open(os.path.join(ROOT, path)).read())
+_TYPE_WORD = re.compile(r"unsigned|long|int|short|char|float|double|void|\w+_t|said_\w+")
 
 
-def test_every_header_matches_its_binding_table():
-    """Every header's declarations are its ctypes table (one argtypes entry per parameter) and are exported by the built library."""
+def _c_type(text):
+    """(base type, pointer depth) of a C parameter or return type; `const` and the parameter's name are dropped."""
+    words = [w for w in text.replace("*", " ").split() if w != "const"]
+    n = next((i for i, w in enumerate(words) if not _TYPE_WORD.fullmatch(w)), len(words))
+    assert n and len(words) - n <= 1, f"cannot read the C type of {text!r}"
+    return " ".join(words[:n]), text.count("*")
+
+
+def _py_kind(t):
+    """The same of a ctypes type: c_void_p, c_char_p, POINTER(...) and arrays are pointers."""
+    if t is None or t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, (ctypes._Pointer, ctypes.Array)):
+        return _POINTER if t else ("void", 0)
+    return ("float" if t._type_ in "fd" else "int", ctypes.sizeof(t))
+
+
+def _declarations(code):
+    """{said_* entry point: (return type, [parameter types])} of the declarations in a header's code, types as _c_type gives them."""
+    return {name: (_c_type(ret), [] if params.strip() in ("", "void") else [_c_type(p) for p in params.split(",")])
+            for ret, name, params in re.findall(r"([\w \t\*]+?)\b(said_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code)}
+
+
+def _mismatches(declared, table):
+    """What disagrees between declarations and their {name: (restype, argtypes)} table, one sentence each: a parameter count; the kind
+    and size of a parameter or of the return value; the pointee of a POINTER(x) whose C pointee is neither void nor a struct."""
+    bad = []
+    for name, (ret, params) in declared.items():
+        res, args = table[name]
+        if len(args) != len(params):
+            bad.append(f"{name}: {len(params)} parameters declared, {len(args)} argtypes bound")
+            continue
+        for i, ((base, stars), t) in enumerate(zip([ret] + params, [res] + list(args))):
+            what = f"{name}: " + (f"parameter {i}" if i else "the return value") + f" is {base + '*' * stars}, bound as {getattr(t, '__name__', t)}"
+            if _py_kind(t) != _c_kind(base, stars):
+                bad.append(what)
+            elif stars and issubclass(t, ctypes._Pointer) and base != "void" and not base.startswith("said_") and _py_kind(t._type_) != _c_kind(base, stars - 1):
+                bad.append(what + ": another pointee")
+    return bad
+
+
+def _enums(code):
+    """{name: value} of every enum { ... } in a header's code: implicit increments, and values that are expressions (1 << 20, 3 * 256)."""
+    values = {}
+    for body in re.findall(r"\benum\s*\{(.*?)\}", code, flags=re.S):
+        following = 0
+        for item in filter(str.strip, body.split(",")):
+            name, _, expr = (part.strip() for part in item.partition("="))
+            if expr:
+                assert re.fullmatch(r"[\w\s<*+()-]+", expr), expr
+                following = eval(expr, {"__builtins__": {}}, dict(values))
+            values[name], following = following, following + 1
+    return values
+
+
+def _struct(code, name, enums):
+    """[(field, base type, pointer depth, elements)] of `typedef struct ... { ... } name;`, array extents resolved with `enums`."""
+    fields = []
+    for decl in filter(str.strip, re.search(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*" + name + r"\s*;", code).group(1).split(";")):
+        declarators = [re.fullmatch(r"\s*(.*?)(\w+)\s*((?:\[\w+\])*)\s*", d, flags=re.S).groups() for d in decl.split(",")]
+        for prefix, field, dims in declarators:
+            extents = [int(enums.get(d, d)) for d in re.findall(r"\[(\w+)\]", dims)]
+            fields.append((field, _c_type(declarators[0][0])[0], prefix.count("*"), int(np.prod(extents, dtype=np.int64))))
+    return fields
+
+
+@pytest.mark.parametrize("group", sorted(GROUP_DECLARATIONS))
+def test_group_matches_its_headers(group):
+    """A group's headers declare its table's names and no other group's, the library exports them, every parameter and return value is bound in kind and size."""
     from said_amd import _engine
-    lib = _engine.load_library()
-    lazy = {group: table for group, (_, table) in _engine.LAZY_EXPORTS.items()}
-    decoder = lazy.pop("vae_decoder")
-    assert decoder.items() <= _engine.EXPORTS.items(), "the decoder group is part of said_hip.h's table"
-    tables = {("include/said_hip.h", "said_amd/csrc/said_hip_debug.h"): _engine.EXPORTS,
-              ("include/said_metrics.h",): lazy.pop("metrics"), ("include/said_optimize.h",): lazy.pop("optimize"),
-              ("include/said_train.h",): lazy.pop("train")}
-    assert not lazy, f"binding groups without a header here: {sorted(lazy)}"
-    declared, bound = {}, {}
-    for headers, table in tables.items():
-        decl = {name: n for h in headers for name, n in _declarations(h).items()}
-        assert decl, f"no declarations parsed in {headers}"
-        assert set(decl) == set(table), (headers, set(decl) ^ set(table))
-        declared.update(decl)
-        bound.update(table)
-    assert set(declared) == set(bound) and len(declared) == 84
-    for name, nparams in declared.items():
-        assert hasattr(lib, name), f"{name} is declared but not exported"
-        assert len(bound[name][1]) == nparams, f"{name}: {nparams} parameters declared, {len(bound[name][1])} argtypes bound"
+    lib, g = _engine.load_library(), _engine.ABI[group]
+    declared = {name: sig for h in g.headers for name, sig in _declarations(_header(h)).items()}
+    assert set(declared) == set(g.table), (g.headers, set(declared) ^ set(g.table))
+    assert len(declared) == GROUP_DECLARATIONS[group] and set(_engine.ABI) == set(GROUP_DECLARATIONS)
+    assert not [name for other, o in _engine.ABI.items() if other != group for name in o.table if name in declared], "bound by two groups"
+    assert [name for name in declared if not hasattr(lib, name)] == [], "declared but not exported"
+    assert _mismatches(declared, g.table) == []
+    assert list(g.late) == (["vae_decoder"] if group == "core" else [])
+    for late, (feature, names) in g.late.items():   # declared here, bound as a group of its own: load_library(late) knows it
+        assert late not in _engine.ABI and feature and all(getattr(_engine.load_library(late), name).argtypes == g.table[name][1] for name in names)
+
+
+def test_the_header_check_can_fail():
+    """_mismatches on a synthetic header: each of three wrong bindings is reported, the right one is not."""
+    from ctypes import POINTER, c_double, c_float, c_int, c_longlong, c_void_p
+    declared = _declarations(_code("typedef struct said_x said_x;\nint said_x_run(said_x* x, long long n, const double* v_host, /* why */ void* stream);\n"))
+    assert declared == {"said_x_run": (("int", 0), [("said_x", 1), ("long long", 0), ("double", 1), ("void", 1)])}
+    good = [c_void_p, c_longlong, POINTER(c_double), c_void_p]
+    assert _mismatches(declared, {"said_x_run": (c_int, good)}) == []
+    for args, said in (([c_void_p, c_int, POINTER(c_double), c_void_p], "parameter 2 is long long, bound as c_int"),
+                       ([c_void_p, c_longlong, POINTER(c_float), c_void_p], "parameter 3 is double*, bound as LP_c_float: another pointee"),
+                       (good + [c_int], "4 parameters declared, 5 argtypes bound")):
+        assert _mismatches(declared, {"said_x_run": (c_int, args)}) == ["said_x_run: " + said]
+    assert _mismatches(declared, {"said_x_run": (c_longlong, good)}) == ["said_x_run: the return value is int, bound as " + c_longlong.__name__]
+
+
+def test_struct_mirrors_match_their_c_structs():
+    """Field names in order, each field's kind, size and offset, and the size of the whole under natural alignment."""
+    from said_amd import _engine
+    for mirror, header, name, size in ((_engine.LoopParams, "include/said_hip.h", "said_loop_params", 136), (_engine.RenderScene, "include/said_render.h", "said_render_scene", 144),
+                                       (_engine.AudioTrainParams, "include/said_audio_train.h", "said_audio_train_params", 40), (_engine.TransferSystem, "include/said_transfer.h", "said_transfer_system", 96)):
+        fields = _struct(_header(header), name, _enums(_header(header)))
+        assert [f[0] for f in fields] == [f[0] for f in mirror._fields_], name
+        offset = align = 0
+        for (field, base, stars, count), (_, t) in zip(fields, mirror._fields_):
+            kind, width = _c_kind(base, stars)
+            while issubclass(t, ctypes.Array):
+                t = t._type_
+            offset = -(-offset // width) * width
+            assert (_py_kind(t), getattr(mirror, field).offset, getattr(mirror, field).size) == ((kind, width), offset, width * count), (name, field)
+            offset, align = offset + width * count, max(align, width)
+        assert ctypes.sizeof(mirror) == -(-offset // align) * align == size, name
+    assert _engine.AudioTrainParams.seed.offset == 16
+
+
+def test_mirrored_constants_equal_the_headers():
+    """Every public integer constant of _engine, and PRED and PRECISIONS, has its header's value; a new one must be checked here or exempted."""
+    from said_amd import _engine
+    headers = [h for g in _engine.ABI.values() for h in g.headers]
+    assert sorted(headers) == sorted(["include/" + f for f in os.listdir(os.path.join(ROOT, "include"))] + ["said_amd/csrc/said_hip_debug.h"])
+    enums = {name: value for h in headers for name, value in _enums(_header(h)).items()}
+    assert enums["SAID_BEAT_MAX_FRAMES"] == 1 << 20 and enums["SAID_TRANSFER_MAX_COLUMNS"] == 768 and enums["SAID_TRAIN_S_USE_EMA"] == 11
+    alias = {**{"OPT_" + n: "SAID_OPTIMIZE_" + n for n in ("CONVERGED", "MAX_ITER", "NOT_FINITE")}, **{"W_" + n: "SAID_METRICS_W_" + n for n in ("UNIT", "LABELS", "RESP")}}
+    exempt = {"ABI_VERSION", "SOLVER", "ABI"}   # no enum: said_abi_version() of the built library; the codes that SAID_COEF_SOLVER's comment gives; the table itself
+    consts = {n: v for n, v in vars(_engine).items() if n.isupper() and n[0] != "_" and n not in exempt and isinstance(v, (int, dict)) and not isinstance(v, bool)}
+    assert len(consts) == 77   # 75 integers and the two dicts
+    for name, value in consts.items():
+        if name == "PRED":
+            assert value == {"epsilon": enums["SAID_PRED_EPSILON"], "sample": enums["SAID_PRED_SAMPLE"], "v_prediction": enums["SAID_PRED_V"]}
+        elif name == "PRECISIONS":
+            assert value == {mode: enums["SAID_PREC_" + mode.upper()] for mode in ("fp32", "bf16", "fp32_strict")}
+        else:
+            assert isinstance(value, int) and value == enums[alias.get(name, "SAID_" + name)], name
+    assert (_engine.JPEG_OVERFLOW, _engine.BEAT_N_FFT, _engine.BEAT_HOP, _engine.BEAT_N_MELS, _engine.ABI_VERSION) == (1, 2048, 512, 128, 9)
 
 
 def test_no_gpu_means_loud_failure_not_fallback():

@@ -1,7 +1,6 @@
 """CPU checks of the JPEG restatement (tests/jpeg_ref.py): its tables are the ones PIL writes, PIL reads its files, its
-quality matches PIL's own encoder, fp32 can reproduce its rounding almost everywhere, and the binding table matches include/said_jpeg.h."""
+quality matches PIL's own encoder, and fp32 can reproduce its rounding almost everywhere."""
 import os
-import re
 import struct
 
 import numpy as np
@@ -106,21 +105,6 @@ def test_entropy_coder_is_exact_on_arbitrary_coefficients():
             y0, x0 = (m // 2) * 16 + (k // 2) * 8, (m % 2) * 16 + (k % 2) * 8
             want = np.clip(pix[m * 6 + k], 0.0, 255.0)
             assert np.abs(got[y0:y0 + 8, x0:x0 + 8, 1] - want).max() <= 1.0, (m, k)
-
-
-def test_export_table_matches_the_header():
-    """include/said_jpeg.h's declarations are JPEG_EXPORTS, one argtypes entry per parameter, and the built library exports them."""
-    from said_amd import _engine
-    code = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, "include", "said_jpeg.h")).read(), flags=re.S)
-    decl = {name: 0 if params.strip() in ("", "void") else params.count(",") + 1
-            for name, params in re.findall(r"\b(said_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code)}
-    assert set(decl) == set(_engine.JPEG_EXPORTS) and len(decl) == 7
-    assert _engine._GROUPS["jpeg"][1] is _engine.JPEG_EXPORTS
-    lib = _engine.load_library()
-    for name, n in decl.items():
-        assert hasattr(lib, name), f"{name} is declared but not exported"
-        assert len(_engine.JPEG_EXPORTS[name][1]) == n, f"{name}: {n} parameters declared, {len(_engine.JPEG_EXPORTS[name][1])} argtypes bound"
-    assert _engine.JPEG_OVERFLOW == 1 and re.search(r"SAID_JPEG_OVERFLOW\s*=\s*1\b", code)
 
 
 def test_write_video_takes_encoded_chunks(tmp_path):

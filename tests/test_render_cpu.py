@@ -237,22 +237,6 @@ def test_normals_of_a_pyramid_and_a_flat_fan():
     assert np.array_equal(rr.vertex_normals(v, np.array([[0, 1, 1]])), np.zeros((4, 3)))   # no area, no normal
 
 
-def test_header_matches_its_binding_table():
-    """include/said_render.h's declarations are RENDER_EXPORTS, one argtypes entry per parameter, and the built library exports them."""
-    import re
-    from said_amd import _engine
-    code = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, "include", "said_render.h")).read(), flags=re.S)
-    decl = {name: 0 if params.strip() in ("", "void") else params.count(",") + 1
-            for name, params in re.findall(r"\b(said_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code)}
-    assert set(decl) == set(_engine.RENDER_EXPORTS) and len(decl) == 10
-    lib = _engine.load_library()
-    for name, n in decl.items():
-        assert hasattr(lib, name), f"{name} is declared but not exported"
-        assert len(_engine.RENDER_EXPORTS[name][1]) == n, f"{name}: {n} parameters declared, {len(_engine.RENDER_EXPORTS[name][1])} argtypes bound"
-    import ctypes
-    assert ctypes.sizeof(_engine.RenderScene) == 144   # said_render_scene: 2 int, 6 float, 3 float, int, 12 float, 4 float, float, 3 float, 4 float
-
-
 def load_script(name):
     spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "script", name + ".py"))
     mod = importlib.util.module_from_spec(spec)

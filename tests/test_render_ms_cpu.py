@@ -1,8 +1,7 @@
 """The host side of rendering with 4 samples per pixel: the restatement's own ambiguity cap on the scenes the GPU
-test renders, include/said_render_ms.h against its binding table, the CLIs' --samples flag and the resolve rule."""
+test renders, the CLIs' --samples flag and the resolve rule."""
 import importlib.util
 import os
-import re
 
 import numpy as np
 
@@ -28,22 +27,6 @@ def test_ambiguous_pixels_stay_under_the_cap():
         assert covered > 100000 and mixed > 10000
         assert out["max_b"] <= ms.MAX_BARY   # the |b| rule flags nothing on these scenes
         assert ambiguous < 1e-3 * covered
-
-
-def test_header_matches_its_binding_table():
-    """include/said_render_ms.h's declarations are RENDER_MS_EXPORTS, one argtypes entry per parameter, and the built library exports them."""
-    from said_amd import _engine
-    code = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, "include", "said_render_ms.h")).read(), flags=re.S)
-    decl = {name: 0 if params.strip() in ("", "void") else params.count(",") + 1
-            for name, params in re.findall(r"\b(said_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code)}
-    assert set(decl) == set(_engine.RENDER_MS_EXPORTS) == {"said_render_render_ms"}
-    assert _engine._GROUPS["render_ms"][1] is _engine.RENDER_MS_EXPORTS
-    lib = _engine.load_library()
-    for name, n in decl.items():
-        assert hasattr(lib, name), f"{name} is declared but not exported"
-        assert len(_engine.RENDER_MS_EXPORTS[name][1]) == n, f"{name}: {n} parameters declared, {len(_engine.RENDER_MS_EXPORTS[name][1])} argtypes bound"
-    # the sample count is an argument of the call: the renderer's own header and scene keep their shape
-    assert len(_engine.RENDER_EXPORTS) == 10 and not set(_engine.RENDER_EXPORTS) & set(_engine.RENDER_MS_EXPORTS)
 
 
 def load_script(name):

@@ -1,6 +1,5 @@
 """CPU checks of the denoiser trainer's host side and of its float64-capable restatement (tests/unet_train_ref.py)."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,17 +13,6 @@ import unet_train_ref as ref
 from oracle import unet as oracle_unet
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def test_header_matches_binding_table():
-    code = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, "include", "said_unet_train.h")).read(), flags=re.S)
-    decl = {name: 0 if params.strip() in ("", "void") else params.count(",") + 1
-            for name, params in re.findall(r"\b(said_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code)}
-    assert set(decl) == set(_engine.UNET_TRAIN_EXPORTS)
-    lib = _engine.load_library()
-    for name, n in decl.items():
-        assert hasattr(lib, name), name
-        assert len(_engine.UNET_TRAIN_EXPORTS[name][1]) == n, name
 
 
 def test_tensor_table_is_the_trainable_state_dict():
