@@ -308,6 +308,33 @@ ABI = {
         "said_audio_encode_train": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(AudioTrainParams), c_void_p, _c_int_p, c_void_p]),
     }),
 }
+# Groups added since: entry points of existing contexts, declared in headers of their own and bound on first use, outside the ABI version
+_ABI_ADDED = {
+    "unet_finetune": Group(("said_amd/csrc/said_unet_finetune.h",), "fine-tuning the audio encoder in the UNet trainer", {
+        "said_unet_train_create_ft": (c_int, [_c_void_pp, c_int, c_int, c_int, c_int, c_int]),
+        "said_unet_train_table_size_ft": (c_int, [c_int, c_int]),
+        "said_unet_train_table_name_ft": (c_char_p, [c_int, c_int, c_int]),
+        "said_unet_train_table_numel_ft": (_c_ll, [c_int, c_int, c_int]),
+        "said_unet_train_finetune_layers": (c_int, [c_void_p]),
+        "said_unet_train_step_ft": (c_int, [c_void_p, c_int, c_int, _c_float_p, _c_float_p, _c_ll_p, _c_int_p, c_void_p, c_int, POINTER(AudioTrainParams),
+                                            _c_ull, _c_float_p, _c_float_p, _c_float_p, c_int]),
+        "said_unet_train_eval_loss_ft": (c_int, [c_void_p, c_int, c_int, _c_float_p, _c_float_p, _c_ll_p, _c_int_p, c_void_p, c_int,
+                                                 POINTER(AudioTrainParams), _c_float_p, _c_float_p, _c_float_p, c_int, c_int]),
+        "said_unet_train_forward_only_ft": (c_int, [c_void_p, c_int, c_int, _c_float_p, _c_ll_p, _c_int_p, c_void_p, c_int, POINTER(AudioTrainParams),
+                                                    c_int, _c_float_p]),
+        "said_unet_train_last_conditioning": (c_int, [c_void_p, c_int, c_int, _c_float_p]),
+    }),
+    "audio_features": Group(("said_amd/csrc/said_audio_features.h",), "the audio encoder's front end as a callable", {
+        "said_audio_extract_features": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, _c_int_p, c_void_p]),
+    }),
+}
+
+
+def added_groups() -> dict:
+    """{group: Group} of the groups added beside ABI."""
+    return dict(_ABI_ADDED)
+
+
 _bound = set()   # the groups bound so far
 
 
@@ -317,8 +344,8 @@ def library_path() -> str:
 
 def _group(group: str):
     """(feature, table) of a group of ABI, without its late entries, or of a late part of one."""
-    if group in ABI:
-        g = ABI[group]
+    if group in ABI or group in _ABI_ADDED:
+        g = ABI[group] if group in ABI else _ABI_ADDED[group]
         late = {name for _, names in g.late.values() for name in names}
         return g.feature, {name: sig for name, sig in g.table.items() if name not in late}
     for g in ABI.values():
@@ -462,6 +489,24 @@ class _Context:
             self._call(name, *args, _stream())
 
 
+def audio_train_params(draws, cfg, B: int, frames: int, device):
+    """(said_audio_train_params, the device tensor its mask pointer refers to or None) of an AudioTrainDraws and an AudioTrainConfig
+    (said_amd.model.wav2vec2) for B clips of `frames` frames."""
+    mask = None
+    if draws.mask is not None:
+        m = np.ascontiguousarray(np.asarray(draws.mask) != 0, dtype=np.uint8)
+        if m.shape != (B, frames):
+            raise EngineError(f"time mask of shape {m.shape} does not match {B} clips of {frames} frames")
+        mask = torch.from_numpy(m).to(device)
+    skip = 0
+    for l, sk in enumerate(draws.skip):
+        skip |= int(bool(sk)) << l
+    if skip >> 32:
+        raise EngineError("skip list longer than 32 layers")
+    return AudioTrainParams(cfg.feat_proj_dropout, cfg.hidden_dropout, cfg.attention_dropout, cfg.activation_dropout,
+                            int(draws.seed) & 0xFFFFFFFFFFFFFFFF, _ptr(mask), skip), mask
+
+
 class Engine(_Context):
     """One engine context on one GPU (one process per GPU)."""
     prefix = "said"
@@ -536,6 +581,19 @@ class Engine(_Context):
         assert got.value == out.shape[1], (got.value, out.shape)
         return out
 
+    def extract_features(self, waveform: torch.Tensor, num_frames: Optional[int]) -> torch.Tensor:
+        """(B, frames, 512): the frozen feature extractor's output after the interpolation, token-major (said_audio_extract_features):
+        what a fine-tuning UNetTrainEngine takes as `features`."""
+        load_library("audio_features")
+        waveform = _dev(waveform, "waveform")
+        B, Ta = waveform.shape
+        nf = int(num_frames) if num_frames is not None else 0
+        out = torch.empty(B, nf if nf > 0 else max(_w2v_frames(Ta), 1), 512, device=waveform.device, dtype=torch.float32)
+        got = c_int(0)
+        self._go("said_audio_extract_features", _ptr(waveform), B, Ta, nf, _ptr(out), ctypes.byref(got))
+        assert got.value == out.shape[1], (got.value, out.shape)
+        return out
+
     def audio_encode_train(self, waveform: torch.Tensor, num_frames: Optional[int], draws, cfg, apply_proj: bool = False) -> torch.Tensor:
         """audio_encode in Wav2Vec2's train mode (include/said_audio_train.h): `draws` is an AudioTrainDraws (time mask, skipped layers,
         dropout seed), `cfg` an AudioTrainConfig (the dropout probabilities) — said_amd.model.wav2vec2."""
@@ -544,19 +602,7 @@ class Engine(_Context):
         B, frames = waveform.shape[0], int(num_frames or 0)
         if frames <= 0:   # no interpolation: the feature extractor's own frame count
             frames = _w2v_frames(waveform.shape[1])
-        mask = None
-        if draws.mask is not None:
-            m = np.ascontiguousarray(np.asarray(draws.mask) != 0, dtype=np.uint8)
-            if m.shape != (B, frames):
-                raise EngineError(f"time mask of shape {m.shape} does not match {B} clips of {frames} frames")
-            mask = torch.from_numpy(m).to(waveform.device)
-        skip = 0
-        for l, sk in enumerate(draws.skip):
-            skip |= int(bool(sk)) << l
-        if skip >> 32:
-            raise EngineError("skip list longer than 32 layers")
-        p = AudioTrainParams(cfg.feat_proj_dropout, cfg.hidden_dropout, cfg.attention_dropout, cfg.activation_dropout,
-                             int(draws.seed) & 0xFFFFFFFFFFFFFFFF, _ptr(mask), skip)
+        p, mask = audio_train_params(draws, cfg, B, frames, waveform.device)
         out = self.audio_encode(waveform, num_frames, apply_proj, _train=p)
         if mask is not None:
             mask.record_stream(torch.cuda.current_stream(waveform.device))
@@ -1067,9 +1113,14 @@ class UNetTrainEngine(_TrainContext):
     prefix, group, n_last = "said_unet_train", "unet_train", 6   # last_losses: predict, velocity, vertex, total, clip factor, gradient norm
     cpu_error, cpu_message = NoCpuPathError, "said_amd trains the denoiser on MI355X only (device={}); there is no CPU path"
 
-    def __init__(self, device: torch.device, max_batch: int, max_frames: int, feature_dim: Optional[int] = -1):
+    def __init__(self, device: torch.device, max_batch: int, max_frames: int, feature_dim: Optional[int] = -1, finetune_layers: int = 0):
         super().__init__(device)
-        if feature_dim is None:   # the entry point without a feature_dim: the default context, as feature_dim=-1 is
+        self.finetune_layers = max(int(finetune_layers), 0)
+        if self.finetune_layers > 0:   # the Wav2Vec2 transformer trains with the denoiser: the batch's input is the conv features
+            load_library("unet_finetune")
+            self._create(int(max_batch), int(max_frames), -1 if feature_dim is None else int(feature_dim), self.finetune_layers,
+                         entry="said_unet_train_create_ft")
+        elif feature_dim is None:   # the entry point without a feature_dim: the default context, as feature_dim=-1 is
             self._create(int(max_batch), int(max_frames))
         else:
             self._create(int(max_batch), int(max_frames), int(feature_dim), entry="said_unet_train_create_dim")
@@ -1098,14 +1149,33 @@ class UNetTrainEngine(_TrainContext):
         else:
             au = host_f32(audio)
             ap, on_dev = _vp(au), 0
-        if x.shape != (B, T, 32) or ts.size != B or cd.size != B or tuple(au.shape) != (B, T, 768):
-            raise EngineError(f"batch shapes: x {x.shape}, timesteps {ts.shape}, cond {cd.shape}, audio embedding {tuple(au.shape)}")
+        width = 512 if self.finetune_layers > 0 else 768
+        if x.shape != (B, T, 32) or ts.size != B or cd.size != B or tuple(au.shape) != (B, T, width):
+            raise EngineError(f"batch shapes: x {x.shape}, timesteps {ts.shape}, cond {cd.shape}, "
+                              f"{'features' if self.finetune_layers > 0 else 'audio embedding'} {tuple(au.shape)}")
         return B, T, x, ts, cd, au, ap, on_dev
 
-    def step(self, coeffs, noise, timesteps, cond, audio, dropout_seed: int, scalars, std=None, deltas=None) -> None:
+    def _audio_params(self, draws, cfg, B: int, T: int):
+        """(pointer to said_audio_train_params or None, what it must keep alive) for the _ft entry points; draws None: eval mode."""
+        if draws is None:
+            return None, None
+        cfg.check()
+        p, mask = audio_train_params(draws, cfg, B, T, self.device)
+        if mask is not None:
+            torch.cuda.current_stream(self.device).synchronize()   # the context copies the mask on its own stream
+        return ctypes.byref(p), (p, mask)
+
+    def step(self, coeffs, noise, timesteps, cond, audio, dropout_seed: int, scalars, std=None, deltas=None, audio_draws=None, audio_cfg=None) -> None:
+        """`audio`: the audio embedding (B, T, 768), or with finetune_layers > 0 the conv features (B, T, 512); there audio_draws /
+        audio_cfg (AudioTrainDraws / AudioTrainConfig) put the encoder in train mode, None leaves it in eval mode."""
         B, T, x, ts, cd, au, ap, on_dev = self._batch(coeffs, timesteps, cond, audio)
         nz, sc, sd, dl = _f32(noise), _f32(scalars), _f32(std), _f32(deltas)
         V = 0 if dl is None else dl.shape[-1] // 3
+        if self.finetune_layers > 0:
+            pp, keep = self._audio_params(audio_draws, audio_cfg, B, T)
+            self._call("said_unet_train_step_ft", B, T, _fp(x), _fp(nz), _lp(ts), _ip(cd), ap, on_dev, pp, _c_ull(int(dropout_seed) & (2 ** 64 - 1)),
+                       _fp(sc), _fp(sd), _fp(dl), V)
+            return
         self._call("said_unet_train_step", B, T, _fp(x), _fp(nz), _lp(ts), _ip(cd), ap, on_dev, _c_ull(int(dropout_seed) & (2 ** 64 - 1)), _fp(sc),
                    _fp(sd), _fp(dl), V)
 
@@ -1113,12 +1183,25 @@ class UNetTrainEngine(_TrainContext):
         B, T, x, ts, cd, au, ap, on_dev = self._batch(coeffs, timesteps, cond, audio)
         nz, sc, sd, dl = _f32(noise), _f32(scalars), _f32(std), _f32(deltas)
         V = 0 if dl is None else dl.shape[-1] // 3
+        if self.finetune_layers > 0:
+            self._call("said_unet_train_eval_loss_ft", B, T, _fp(x), _fp(nz), _lp(ts), _ip(cd), ap, on_dev, None, _fp(sc), _fp(sd), _fp(dl), V,
+                       int(bool(ema)))
+            return
         self._call("said_unet_train_eval_loss", B, T, _fp(x), _fp(nz), _lp(ts), _ip(cd), ap, on_dev, _fp(sc), _fp(sd), _fp(dl), V, int(bool(ema)))
 
     def forward_only(self, sample, timesteps, cond, audio, ema: bool = False) -> np.ndarray:
         B, T, x, ts, cd, au, ap, on_dev = self._batch(sample, timesteps, cond, audio)
         out = np.empty((B, T, 32), dtype=np.float32)
-        self._call("said_unet_train_forward_only", B, T, _fp(x), _lp(ts), _ip(cd), ap, on_dev, int(bool(ema)), _fp(out))
+        if self.finetune_layers > 0:
+            self._call("said_unet_train_forward_only_ft", B, T, _fp(x), _lp(ts), _ip(cd), ap, on_dev, None, int(bool(ema)), _fp(out))
+        else:
+            self._call("said_unet_train_forward_only", B, T, _fp(x), _lp(ts), _ip(cd), ap, on_dev, int(bool(ema)), _fp(out))
+        return out
+
+    def last_conditioning(self, B: int, T: int) -> np.ndarray:
+        """(B, T, context width): what the denoiser saw in the last call of that shape on a fine-tuning context."""
+        out = np.empty((B, T, self.feature_dim if self.feature_dim > 0 else 768), dtype=np.float32)
+        self._call("said_unet_train_last_conditioning", B, T, _fp(out))
         return out
 
 

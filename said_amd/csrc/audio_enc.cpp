@@ -3,14 +3,16 @@
 // (include/said_audio_train.h; kernels: audio_train.hip).
 #include "../../include/said_audio_train.h"
 #include "audio_train.h"
+#include "said_audio_features.h"
 #include "engine_internal.h"
 
 namespace {
 
 // Both entry points.  tp == nullptr: said_audio_encode, launch for launch what it always issued.  tp != nullptr (validated by
 // said_audio_encode_train; fp32 route only): SpecAugment span replacement, the four dropouts and LayerDrop of the train-mode forward.
+// features_only: stop behind the interpolation and store the conv features token-major, (B, frames, 512) (said_audio_extract_features).
 int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_frames, int apply_proj, const said_audio_train_params* tp,
-                 float* out_dev, int* out_frames, void* stream) {
+                 float* out_dev, int* out_frames, void* stream, bool features_only = false) {
     if (check_ready(ctx)) return -1;
     if (!ctx->has_audio) return fail(ctx, "audio_encoder.* weights were not loaded");
     hipStream_t s = (hipStream_t)stream;
@@ -258,6 +260,10 @@ int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_fra
             launch_interp_linear(src, ctx->aX, nb, W2V_CONV, L[6], Fr, pitch, Fp, bs, xs, s);
             feat = ctx->aX; feat_bs = xs; feat_pitch = Fp;
         }
+        if (features_only) {
+            launch_cm_to_tm(feat, out_dev + (long long)b0 * Fr * W2V_CONV, nb, Fr, W2V_CONV, feat_pitch, feat_bs, s);
+            continue;
+        }
         const long long tt = (long long)nb * ((Fr + 31) / 32);
         {   // feature_projection: LayerNorm(512) -> Linear(512, 768)
             GemmArgs a = mkargs(Fr, W2V_H);
@@ -389,6 +395,13 @@ int said_audio_encode_train(said_ctx* ctx, const float* wav_dev, int B, int Ta, 
         return fail(ctx, "said_audio_encode_train: a time mask needs audio_encoder.masked_spec_embed, which was not loaded");
     if (ctx->w2v_layers > 32) return fail(ctx, "said_audio_encode_train: skip_layers holds 32 layers, the encoder has %d", ctx->w2v_layers);
     return audio_encode(ctx, wav_dev, B, Ta, num_frames, apply_proj, tp, out_dev, out_frames, stream);
+}
+
+int said_audio_extract_features(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_frames, float* out_dev, int* out_frames, void* stream) {
+    if (check_ready(ctx)) return -1;
+    if (ctx->bf16_mode)
+        return fail(ctx, "said_audio_extract_features: the context is in bf16 mode; the features come from the fp32 route only (said_set_precision)");
+    return audio_encode(ctx, wav_dev, B, Ta, num_frames, 0, nullptr, out_dev, out_frames, stream, true);
 }
 
 }  // extern "C"

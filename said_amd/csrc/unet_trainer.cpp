@@ -2,8 +2,11 @@
 // parameters and of the optimizer, the activation arena, and the step: add_noise, forward, objective, backward, clip, AdamW, EMA, launched in that
 // order on the context's stream (unet_train.hip).  T is a run-time value, so nothing is captured into a graph.  A context made with
 // feature_dim = F > 0 also holds and trains audio_proj_layer (768 -> F) and runs the context at width F; F <= 0 leaves every launch as it is.
-#include "../../include/said_unet_train.h"
+// A context made with finetune_layers = L > 0 (said_unet_finetune.h) also holds and trains the Wav2Vec2 transformer in the same store: its
+// forward runs in front of the UNet's and its backward behind it (kernels: audio_ft.hip); L <= 0 leaves every launch as it is.
+#include "said_unet_finetune.h"
 
+#include "audio_ft.h"
 #include "engine_internal.h"
 #include "train_store.h"
 #include "unet_train.h"
@@ -24,7 +27,31 @@ constexpr int AUD = SAID_UT_CTX_DIM;   // width of the frozen encoder's output, 
 
 // null_cond_emb, (F > 0: audio_proj_layer,) then UNet1DConditionModel.state_dict() under "denoiser.", in the reference's registration order.
 // F <= 0: the context is the encoder's output itself (SAID_UNet1D(feature_dim = -1))
-std::vector<TDesc> make_table(int F) {
+// audio_encoder.* of an L-layer wav2vec2-base encoder without its feature extractor, in state-dict order (transformers 4.30.2 key layout)
+constexpr int EH = 768, ECONV = 512, EFFN = 3072, ENH = 12, EHD = 64, EPK = 128, EPG = 16, EPC = EH / EPG, MAXL = 32;
+const char* const kEnc = "audio_encoder.";
+std::string enc_layer(int l) { return std::string(kEnc) + "encoder.layers." + std::to_string(l); }
+void add_encoder(std::vector<TDesc>& v, int L) {
+    auto add = [&](const std::string& n, long long k) { v.push_back({kEnc + n, k}); };
+    auto wb = [&](const std::string& n, long long no, long long ni) { add(n + ".weight", no * ni); add(n + ".bias", no); };
+    add("masked_spec_embed", EH);
+    wb("feature_projection.layer_norm", ECONV, 1);
+    wb("feature_projection.projection", EH, ECONV);
+    add("encoder.pos_conv_embed.conv.bias", EH);
+    add("encoder.pos_conv_embed.conv.weight_g", EPK);
+    add("encoder.pos_conv_embed.conv.weight_v", (long long)EH * EPC * EPK);
+    wb("encoder.layer_norm", EH, 1);
+    for (int l = 0; l < L; ++l) {
+        const std::string p = "encoder.layers." + std::to_string(l);
+        for (const char* n : {"k_proj", "v_proj", "q_proj", "out_proj"}) wb(p + ".attention." + n, EH, EH);
+        wb(p + ".layer_norm", EH, 1);
+        wb(p + ".feed_forward.intermediate_dense", EFFN, EH);
+        wb(p + ".feed_forward.output_dense", EH, EFFN);
+        wb(p + ".final_layer_norm", EH, 1);
+    }
+}
+
+std::vector<TDesc> make_table(int F, int L) {
     std::vector<TDesc> v;
     auto add = [&](const std::string& n, long long k) { v.push_back({n, k}); };
     const int CTX = F > 0 ? F : AUD;
@@ -65,16 +92,18 @@ std::vector<TDesc> make_table(int F) {
     res(m + "output_blocks.1.0", 2 * CH); st(m + "output_blocks.1.1");
     add(m + "out.0.weight", CH); add(m + "out.0.bias", CH);
     add(m + "out.2.weight", XC * CH * 3); add(m + "out.2.bias", XC);
+    if (L > 0) add_encoder(v, L);
     return v;
 }
-// the table of feature_dim F (<= 0: the default one), built once; a std::map's nodes stay where they are
-const std::vector<TDesc>& table(int F = 0) {
+// the table of feature_dim F (<= 0: the default one) and L fine-tuned encoder layers (<= 0: a frozen encoder), built once; a std::map's
+// nodes stay where they are
+const std::vector<TDesc>& table(int F = 0, int L = 0) {
     static std::mutex mu;
-    static std::map<int, std::vector<TDesc>> tabs;
-    const int key = F > 0 ? F : 0;
+    static std::map<std::pair<int, int>, std::vector<TDesc>> tabs;
+    const std::pair<int, int> key(F > 0 ? F : 0, L > 0 ? L : 0);
     std::lock_guard<std::mutex> lock(mu);
     auto it = tabs.find(key);
-    if (it == tabs.end()) it = tabs.emplace(key, make_table(key)).first;
+    if (it == tabs.end()) it = tabs.emplace(key, make_table(key.first, key.second)).first;
     return it->second;
 }
 const char* kRes[5] = {"denoiser.model.input_blocks.1.0", "denoiser.model.middle_block.0", "denoiser.model.middle_block.2",
@@ -99,6 +128,16 @@ struct Acts {
     // feature_dim > 0: the projected audio (B T, F) and the conditional samples' rows of dctx
     float *proj, *dcond;
 };
+// what the fine-tuned encoder keeps from its forward: per layer the input, q, k, v, the undropped probabilities, the attention output, both
+// LayerNorms' xhat / rstd, the FFN's pre-activation and its dropped GELU, the layer's output
+struct EncLayer { const float* x; float *q, *k, *v, *P, *o, *xh1, *rs1, *x1, *u, *gd, *xh2, *rs2, *out; };
+struct EncActs {
+    float *xh0, *rs0, *y0, *hp, *h0, *wnorm, *w, *pospre, *pos, *xhf, *rsf, *x0;
+    EncLayer l[MAXL];
+    const float* out;   // the last hidden state (B T, 768)
+    // scratch of the forward and the backward
+    float *t768, *Pd, *PB, *d, *g1, *g2, *g3, *big, *dw, *wnpart, *wndot, *dy0;
+};
 
 }  // namespace
 
@@ -106,6 +145,12 @@ struct said_unet_train {
     HostCtx c;
     int maxB = 0, maxT = 0;
     int F = 0, CTX = AUD;     // feature_dim (0: no audio_proj_layer) and the context width, F or 768
+    int L = 0;                // fine-tuned encoder layers (0: the encoder is frozen and its output an input)
+    float* feat = nullptr;    // L > 0: the batch's conv features (B T, 512)
+    unsigned char* mask = nullptr;   // L > 0: the step's time mask (B T)
+    long long enc_off = 0, enc_n = 0;   // L > 0: the encoder's tensors in the store
+    size_t gpart_n = 0;
+    EncActs e;
     const std::vector<TDesc>* tb = nullptr;
     hipStream_t s = nullptr;
     TrainStore st;            // the parameters (with the stash of EMAModel.store) and the optimizer's state
@@ -125,7 +170,7 @@ struct said_unet_train {
 
 namespace {
 
-size_t layout(Acts& a, float* base, int B, int T, int F) {
+size_t layout(Acts& a, float* base, int B, int T, int F, int L = 0, EncActs* e = nullptr) {
     size_t pos = 0;
     const size_t M = (size_t)B * T, CTX = F > 0 ? F : AUD;
     auto take = [&](size_t n) { float* p = base ? base + pos : nullptr; pos += (n + 63) / 64 * 64; return p; };
@@ -153,6 +198,21 @@ size_t layout(Acts& a, float* base, int B, int T, int F) {
     a.R = take(M * XC); a.dpred = take(M * XC); a.GV = take(M * XC);
     a.proj = a.dcond = nullptr;
     if (F > 0) { a.proj = take(M * F); a.dcond = take(M * F); }
+    if (L > 0) {
+        if (F <= 0) a.dcond = take(M * CTX);
+        const size_t PP = (size_t)B * ENH * T * T, WN = (size_t)EH * EPC * EPK;
+        e->xh0 = take(M * ECONV); e->rs0 = take(M); e->y0 = take(M * ECONV); e->hp = take(M * EH); e->h0 = take(M * EH); e->wnorm = take(EPK);
+        e->w = take(WN); e->pospre = take(M * EH); e->pos = take(M * EH); e->xhf = take(M * EH); e->rsf = take(M); e->x0 = take(M * EH);
+        for (int l = 0; l < L; ++l) {
+            EncLayer& z = e->l[l];
+            float** f[] = {&z.q, &z.k, &z.v, &z.o, &z.xh1, &z.x1, &z.xh2, &z.out};
+            for (float** p : f) *p = take(M * EH);
+            z.rs1 = take(M); z.rs2 = take(M); z.P = take(PP); z.u = take(M * EFFN); z.gd = take(M * EFFN);
+        }
+        e->t768 = take(M * EH); e->Pd = take(PP); e->PB = take(PP); e->d = take(M * EH); e->g1 = take(M * EH); e->g2 = take(M * EH);
+        e->g3 = take(M * EH); e->big = take(M * EFFN); e->dw = take(WN); e->wnpart = take((size_t)aft::WN_SEG * EPK); e->wndot = take(EPK);
+        e->dy0 = take(M * ECONV);
+    }
     return pos;
 }
 
@@ -236,12 +296,13 @@ void enqueue_forward(said_unet_train* t, int B, int T, const float* base, float 
     auto w = [&](const std::string& n) { return par(t, base, n); };
     const std::string m = "denoiser.model.";
     const int CTX = t->CTX;
+    const float* audio = t->L > 0 ? t->e.out : t->audio;   // the fine-tuned encoder's output of this call (enqueue_enc_forward), or the input
     if (t->F > 0) {
         // get_audio_embedding projects, then the trainer selects (script/train.py:86-94)
-        gm.lin(t->audio, AUD, w("audio_proj_layer.weight"), w("audio_proj_layer.bias"), a.proj, CTX, M, CTX, AUD);
+        gm.lin(audio, AUD, w("audio_proj_layer.weight"), w("audio_proj_layer.bias"), a.proj, CTX, M, CTX, AUD);
         select_ctx(s, B, T, CTX, a.proj, w("null_cond_emb"), t->cond, a.ctx);
     } else {
-        select_ctx(s, B, T, CTX, t->audio, w("null_cond_emb"), t->cond, a.ctx);
+        select_ctx(s, B, T, CTX, audio, w("null_cond_emb"), t->cond, a.ctx);
     }
     timestep_embedding(s, B, CH, t->tsf, a.temb);
     gm.lin(a.temb, CH, w(m + "time_embed.0.weight"), w(m + "time_embed.0.bias"), a.e1, TEd, B, TEd, CH);
@@ -459,11 +520,180 @@ void enqueue_backward(said_unet_train* t, int B, int T, float p, unsigned long l
         // the conditional samples' rows go to the projection (nothing flows into the frozen encoder's output)
         split_cond_rows(s, B, T, CTX, t->cond, a.dctx, a.dcond);
         colsum(s, a.dctx, CTX, nullptr, 0, M, 1, CTX, gw("null_cond_emb"), 0);
-        gm.lin_wgrad(a.dcond, t->audio, AUD, gw("audio_proj_layer.weight"), gw("audio_proj_layer.bias"), M, CTX, AUD);
+        gm.lin_wgrad(a.dcond, t->L > 0 ? t->e.out : t->audio, AUD, gw("audio_proj_layer.weight"), gw("audio_proj_layer.bias"), M, CTX, AUD);
+    } else if (t->L > 0) {
+        // the conditional samples' rows are the gradient at the fine-tuned encoder's output (enqueue_enc_backward)
+        split_cond_rows(s, B, T, CTX, t->cond, a.dctx, a.dcond);
+        colsum(s, a.dctx, CTX, nullptr, 0, M, 1, CTX, gw("null_cond_emb"), 0);
     } else {
         mask_cond_rows(s, B, T, CTX, t->cond, a.dctx);
         colsum(s, a.dctx, CTX, nullptr, 0, M, 1, CTX, gw("null_cond_emb"), 0);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the fine-tuned encoder
+// The Wav2Vec2 transformer behind the frozen feature extractor (include/said_unet_train.h), fp32 token-major.  tp == nullptr: eval mode.
+struct EncGm {
+    said_unet_train* t;
+    int B, T;
+    UOp rows(const float* p) const { return plain(p, EH, 1, (long long)T * EH, EHD); }     // (t, d) of head h
+    UOp cols(const float* p) const { return plain(p, 1, EH, (long long)T * EH, EHD); }     // (d, t)
+    UOp prow(const float* p) const { return plain(p, T, 1, (long long)ENH * T * T, (long long)T * T); }
+    UOp pcol(const float* p) const { return plain(p, 1, T, (long long)ENH * T * T, (long long)T * T); }
+    void heads(UOp A, UOp Bo, float* C, long long czb, long long czh, int ldc, int M, int N, int K) const {
+        UGemm g = Gm{t}.base(A, Bo, C, ldc, M, N, K);
+        g.Z = B * ENH; g.ZH = ENH; g.czb = czb; g.czh = czh;
+        gemm(t->s, g);
+    }
+    void scores(const float* q, const float* k, float* S) const { heads(rows(q), rows(k), S, (long long)ENH * T * T, (long long)T * T, T, T, T, EHD); }
+    void apply(UOp Pm, const float* v, float* o) const { heads(Pm, cols(v), o, (long long)T * EH, EHD, EH, T, EHD, T); }
+    // the grouped positional convolution (k = 128, padding 64, the last output dropped) as shifted-operand GEMMs, the group as batch index;
+    // a short batch splits K = 128 x 48 so that more than 16 workgroups run
+    void split_small(UGemm& g) const {
+        const int ks = 8;
+        if (g.M <= 256 && (size_t)ks * g.Z * g.M * g.N <= t->gpart_n) { g.KS = ks; g.kchunk = rup((g.K + ks - 1) / ks, 16); }
+    }
+    void pos_fwd(const float* h, const float* w, float* y) const {   // without the bias: the epilogue's bias[n] counts columns inside a group
+        UOp A{h, 0, EPC, 0, T, EH, 0, 1, 0, EPC, EPK, 0, -EPK / 2, 1};
+        UOp W{w, 0, (long long)EPC * EPC * EPK, 0, 1, 0, EPC * EPK, EPK, 1, EPC, EPK, 0, 0, 0};
+        UGemm g = Gm{t}.base(A, W, y, EH, B * T, EPC, EPK * EPC);
+        g.Z = EPG; g.ZH = EPG; g.czh = EPC;
+        split_small(g);
+        gemm(t->s, g);
+    }
+    void pos_dgrad(const float* dy, const float* w, float* dh) const {   // dh += ...
+        UOp A{dy, 0, EPC, 0, T, EH, 0, 1, 0, EPC, EPK, 0, EPK / 2, -1};
+        UOp W{w, 0, (long long)EPC * EPC * EPK, 0, 1, 0, EPK, EPC * EPK, 1, EPC, EPK, 0, 0, 0};
+        UGemm g = Gm{t}.base(A, W, dh, EH, B * T, EPC, EPK * EPC);
+        g.Z = EPG; g.ZH = EPG; g.czh = EPC; g.accumulate = 1;
+        split_small(g);
+        gemm(t->s, g);
+    }
+    void pos_wgrad(const float* dy, const float* h, float* dw) const {   // dw (768, 48, 128)
+        UOp A = plain(dy, 1, EH, 0, EPC);
+        UOp X{h, 0, EPC, 1, T, EH, 0, 1, 0, EPC, EPK, 1, -EPK / 2, 1};
+        UGemm g = Gm{t}.base(A, X, dw, EPC * EPK, EPC, EPC * EPK, B * T);
+        g.Z = EPG; g.ZH = EPG; g.czh = (long long)EPC * EPC * EPK;
+        Gm{t}.ksplit(g);
+        gemm(t->s, g);
+    }
+};
+
+void enqueue_enc_forward(said_unet_train* t, int B, int T, const float* base, const said_audio_train_params* tp) {
+    hipStream_t s = t->s;
+    EncActs& e = t->e;
+    const Gm gm{t};
+    const EncGm eg{t, B, T};
+    const int M = B * T;
+    auto w = [&](const std::string& n) { return par(t, base, kEnc + n); };
+    auto site = [&](int id, float p) { return aft::drop(tp ? tp->seed : 0, id, tp ? p : 0.f); };
+    const aft::Drop none = aft::drop(0, 0, 0.f);
+    const unsigned char* mask = (tp && tp->time_mask_dev) ? t->mask : nullptr;
+    aft::ln_fwd(s, M, ECONV, t->feat, nullptr, w("feature_projection.layer_norm.weight"), w("feature_projection.layer_norm.bias"), none, none, e.xh0,
+                e.rs0, e.y0);
+    gm.lin(e.y0, ECONV, w("feature_projection.projection.weight"), w("feature_projection.projection.bias"), e.hp, EH, M, EH, ECONV);
+    aft::mask_drop_fwd(s, M, EH, e.hp, mask, w("masked_spec_embed"), site(0, tp ? tp->p_feat_proj : 0.f), e.h0);
+    aft::weight_norm_fwd(s, EH * EPC, EPK, w("encoder.pos_conv_embed.conv.weight_g"), w("encoder.pos_conv_embed.conv.weight_v"), e.wnpart, e.wnorm, e.w);
+    eg.pos_fwd(e.h0, e.w, e.pospre);
+    aft::add_bias(s, M, EH, w("encoder.pos_conv_embed.conv.bias"), e.pospre);
+    aft::gelu_drop_fwd(s, (long long)M * EH, e.pospre, none, e.pos);
+    aft::ln_fwd(s, M, EH, e.pos, e.h0, w("encoder.layer_norm.weight"), w("encoder.layer_norm.bias"), none, site(1, tp ? tp->p_hidden : 0.f), e.xhf, e.rsf,
+                e.x0);
+    const float* x = e.x0;
+    for (int l = 0; l < t->L; ++l) {
+        if (tp && (tp->skip_layers >> l & 1u)) continue;   // LayerDrop: the layer is the identity for the whole batch
+        EncLayer& z = e.l[l];
+        const std::string p = "encoder.layers." + std::to_string(l);
+        z.x = x;
+        gm.lin(x, EH, w(p + ".attention.q_proj.weight"), w(p + ".attention.q_proj.bias"), z.q, EH, M, EH, EH);
+        gm.lin(x, EH, w(p + ".attention.k_proj.weight"), w(p + ".attention.k_proj.bias"), z.k, EH, M, EH, EH);
+        gm.lin(x, EH, w(p + ".attention.v_proj.weight"), w(p + ".attention.v_proj.bias"), z.v, EH, M, EH, EH);
+        eg.scores(z.q, z.k, z.P);
+        softmax_fwd(s, (long long)B * ENH * T, T, T, 0.125f, nullptr, nullptr, z.P);
+        const aft::Drop pd = site(16 + 4 * l, tp ? tp->p_attention : 0.f);
+        const float* Pd = z.P;   // the denominator summed the undropped terms; the mask goes on the normalised probabilities
+        if (pd.p > 0.f) { aft::prob_drop(s, (long long)B * ENH * T, T, z.P, pd, e.Pd); Pd = e.Pd; }
+        eg.apply(eg.prow(Pd), z.v, z.o);
+        gm.lin(z.o, EH, w(p + ".attention.out_proj.weight"), w(p + ".attention.out_proj.bias"), e.t768, EH, M, EH, EH);
+        aft::ln_fwd(s, M, EH, e.t768, x, w(p + ".layer_norm.weight"), w(p + ".layer_norm.bias"), site(16 + 4 * l + 1, tp ? tp->p_hidden : 0.f), none, z.xh1,
+                    z.rs1, z.x1);
+        gm.lin(z.x1, EH, w(p + ".feed_forward.intermediate_dense.weight"), w(p + ".feed_forward.intermediate_dense.bias"), z.u, EFFN, M, EFFN, EH);
+        aft::gelu_drop_fwd(s, (long long)M * EFFN, z.u, site(16 + 4 * l + 2, tp ? tp->p_activation : 0.f), z.gd);
+        gm.lin(z.gd, EFFN, w(p + ".feed_forward.output_dense.weight"), w(p + ".feed_forward.output_dense.bias"), e.t768, EH, M, EH, EFFN);
+        aft::ln_fwd(s, M, EH, e.t768, z.x1, w(p + ".final_layer_norm.weight"), w(p + ".final_layer_norm.bias"), site(16 + 4 * l + 3, tp ? tp->p_hidden : 0.f),
+                    none, z.xh2, z.rs2, z.out);
+        x = z.out;
+    }
+    e.out = x;
+}
+
+// dE (B T, 768): the gradient at the encoder's output, exact zeros in the unconditional samples' rows; it is overwritten.  The caller has
+// zeroed the encoder's gradients: a skipped layer's, and masked_spec_embed's without a mask, stay exact zeros.
+void enqueue_enc_backward(said_unet_train* t, int B, int T, const said_audio_train_params* tp, float* dE) {
+    hipStream_t s = t->s;
+    EncActs& e = t->e;
+    const Gm gm{t};
+    const EncGm eg{t, B, T};
+    const int M = B * T;
+    const float* P = t->st.P;
+    auto w = [&](const std::string& n) { return par(t, P, kEnc + n); };
+    auto gw = [&](const std::string& n) { return par(t, t->st.G, kEnc + n); };
+    auto site = [&](int id, float p) { return aft::drop(tp ? tp->seed : 0, id, tp ? p : 0.f); };
+    const aft::Drop none = aft::drop(0, 0, 0.f);
+    const unsigned char* mask = (tp && tp->time_mask_dev) ? t->mask : nullptr;
+    auto norm_grads = [&](const float* du, const float* xh, int C, const std::string& name) {
+        colsum(s, du, C, xh, C, M, 1, C, gw(name + ".weight"), 0);
+        colsum(s, du, C, nullptr, 0, M, 1, C, gw(name + ".bias"), 0);
+    };
+    float* d = dE;
+    for (int l = t->L - 1; l >= 0; --l) {
+        if (tp && (tp->skip_layers >> l & 1u)) continue;
+        EncLayer& z = e.l[l];
+        const std::string p = "encoder.layers." + std::to_string(l);
+        // final_layer_norm over x1 + dropout(f): g1 = d x1 (so far), g2 = d f
+        norm_grads(d, z.xh2, EH, p + ".final_layer_norm");
+        aft::ln_bwd(s, M, EH, d, z.xh2, z.rs2, w(p + ".final_layer_norm.weight"), site(16 + 4 * l + 3, tp ? tp->p_hidden : 0.f), none, nullptr, e.g1, 0, e.g2);
+        gm.lin_wgrad(e.g2, z.gd, EFFN, gw(p + ".feed_forward.output_dense.weight"), gw(p + ".feed_forward.output_dense.bias"), M, EH, EFFN);
+        gm.lin_dgrad(e.g2, w(p + ".feed_forward.output_dense.weight"), e.big, EFFN, M, EH, EFFN, 0);
+        aft::gelu_drop_bwd(s, (long long)M * EFFN, z.u, e.big, site(16 + 4 * l + 2, tp ? tp->p_activation : 0.f), e.big);
+        gm.lin_wgrad(e.big, z.x1, EH, gw(p + ".feed_forward.intermediate_dense.weight"), gw(p + ".feed_forward.intermediate_dense.bias"), M, EFFN, EH);
+        gm.lin_dgrad(e.big, w(p + ".feed_forward.intermediate_dense.weight"), e.g1, EH, M, EFFN, EH, 1);
+        // layer_norm over x + dropout(a): d = d x (so far), g2 = d a
+        norm_grads(e.g1, z.xh1, EH, p + ".layer_norm");
+        aft::ln_bwd(s, M, EH, e.g1, z.xh1, z.rs1, w(p + ".layer_norm.weight"), site(16 + 4 * l + 1, tp ? tp->p_hidden : 0.f), none, nullptr, d, 0, e.g2);
+        gm.lin_wgrad(e.g2, z.o, EH, gw(p + ".attention.out_proj.weight"), gw(p + ".attention.out_proj.bias"), M, EH, EH);
+        gm.lin_dgrad(e.g2, w(p + ".attention.out_proj.weight"), e.g3, EH, M, EH, EH, 0);                    // g3 = d o
+        const aft::Drop pd = site(16 + 4 * l, tp ? tp->p_attention : 0.f);
+        const float* Pd = z.P;
+        if (pd.p > 0.f) { aft::prob_drop(s, (long long)B * ENH * T, T, z.P, pd, e.Pd); Pd = e.Pd; }
+        eg.scores(e.g3, z.v, e.PB);                                                                           // d Pd = do v^T
+        eg.apply(eg.pcol(Pd), e.g3, e.g2);                                                                    // g2 = d v = Pd^T do
+        if (pd.p > 0.f) aft::prob_drop(s, (long long)B * ENH * T, T, e.PB, pd, e.PB);                         // d P: masked and scaled
+        softmax_bwd(s, (long long)B * ENH * T, T, 0.125f, z.P, e.PB);
+        eg.apply(eg.prow(e.PB), z.k, e.g1);                                                                   // g1 = d q = dS k
+        eg.apply(eg.pcol(e.PB), z.q, e.g3);                                                                   // g3 = d k = dS^T q
+        gm.lin_wgrad(e.g1, z.x, EH, gw(p + ".attention.q_proj.weight"), gw(p + ".attention.q_proj.bias"), M, EH, EH);
+        gm.lin_wgrad(e.g3, z.x, EH, gw(p + ".attention.k_proj.weight"), gw(p + ".attention.k_proj.bias"), M, EH, EH);
+        gm.lin_wgrad(e.g2, z.x, EH, gw(p + ".attention.v_proj.weight"), gw(p + ".attention.v_proj.bias"), M, EH, EH);
+        gm.lin_dgrad(e.g1, w(p + ".attention.q_proj.weight"), d, EH, M, EH, EH, 1);
+        gm.lin_dgrad(e.g3, w(p + ".attention.k_proj.weight"), d, EH, M, EH, EH, 1);
+        gm.lin_dgrad(e.g2, w(p + ".attention.v_proj.weight"), d, EH, M, EH, EH, 1);
+    }
+    // the front: x0 = dropout(LN(h0 + gelu(pos_conv(h0)))): g2 = the gradient behind the dropout, g1 = d (h0 + pos)
+    aft::ln_bwd(s, M, EH, d, e.xhf, e.rsf, w("encoder.layer_norm.weight"), none, site(1, tp ? tp->p_hidden : 0.f), e.g2, e.g1, 0, nullptr);
+    norm_grads(e.g2, e.xhf, EH, "encoder.layer_norm");
+    aft::gelu_drop_bwd(s, (long long)M * EH, e.pospre, e.g1, none, e.g3);                                     // g3 = d pos_conv output
+    colsum(s, e.g3, EH, nullptr, 0, M, 1, EH, gw("encoder.pos_conv_embed.conv.bias"), 0);
+    eg.pos_wgrad(e.g3, e.h0, e.dw);
+    aft::weight_norm_bwd(s, EH * EPC, EPK, w("encoder.pos_conv_embed.conv.weight_g"), w("encoder.pos_conv_embed.conv.weight_v"), e.wnorm, e.dw, e.wnpart,
+                         e.wndot, gw("encoder.pos_conv_embed.conv.weight_g"), gw("encoder.pos_conv_embed.conv.weight_v"));
+    eg.pos_dgrad(e.g3, e.w, e.g1);                                                                            // g1 = d h0
+    // masked rows give their gradient to masked_spec_embed and none to the projection
+    aft::mask_drop_bwd(s, M, EH, e.g1, mask, site(0, tp ? tp->p_feat_proj : 0.f), e.g2, mask ? e.g3 : nullptr);
+    if (mask) colsum(s, e.g3, EH, nullptr, 0, M, 1, EH, gw("masked_spec_embed"), 0);
+    gm.lin_wgrad(e.g2, e.y0, ECONV, gw("feature_projection.projection.weight"), gw("feature_projection.projection.bias"), M, EH, ECONV);
+    gm.lin_dgrad(e.g2, w("feature_projection.projection.weight"), e.dy0, ECONV, M, EH, ECONV, 0);
+    norm_grads(e.dy0, e.xh0, ECONV, "feature_projection.layer_norm");   // nothing flows into the features
 }
 
 int put_record(said_unet_train* t, const float* scalars, const float* std_) {
@@ -479,8 +709,11 @@ int put_record(said_unet_train* t, const float* scalars, const float* std_) {
 
 // shape checks and the upload of a batch's inputs; x0 / noise may be null (forward_only passes the sample as x0)
 int put_inputs(said_unet_train* t, const char* what, int B, int T, const float* x0, const float* noise, const long long* ts, const int* cond,
-               const void* audio, int audio_on_device, bool need_alphas) {
+               const void* audio, int audio_on_device, bool need_alphas, bool ft = false) {
     HostCtx* ctx = &t->c;
+    if (ft && t->L <= 0) return fail(ctx, "%s: the context has no fine-tuned encoder (said_unet_train_create_ft with finetune_layers >= 1)", what);
+    if (!ft && t->L > 0) return fail(ctx, "%s: the context fine-tunes its encoder and takes conv features: call the _ft entry point", what);
+    if (ft && (unsigned long long)B * T * EFFN >= (1ull << 32)) return fail(ctx, "%s: %d windows of %d frames need a dropout index of 2^32 or more", what, B, T);
     if (B < 1 || B > t->maxB) return fail(ctx, "%s: batch %d outside [1, %d] (the context's max_batch)", what, B, t->maxB);
     if (T < 2 || T > t->maxT) return fail(ctx, "%s: %d frames outside [2, %d] (the context's max_frames)", what, T, t->maxT);
     if (!x0 || !ts || !cond || !audio) return fail(ctx, "%s: null input", what);
@@ -510,7 +743,8 @@ int put_inputs(said_unet_train* t, const char* what, int B, int T, const float* 
     HIPCHK(hipMemcpyAsync(t->sasb, ab.data(), 2 * B * sizeof(float), hipMemcpyHostToDevice, t->s));
     HIPCHK(hipMemcpyAsync(t->cond, cond, B * sizeof(int), hipMemcpyHostToDevice, t->s));
     HIPCHK(hipMemcpyAsync(t->band, band.data(), band.size() * sizeof(int), hipMemcpyHostToDevice, t->s));
-    HIPCHK(hipMemcpyAsync(t->audio, audio, (size_t)B * T * AUD * sizeof(float), audio_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, t->s));
+    HIPCHK(hipMemcpyAsync(ft ? t->feat : t->audio, audio, (size_t)B * T * (ft ? ECONV : AUD) * sizeof(float),
+                          audio_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, t->s));
     HIPCHK(hipStreamSynchronize(t->s));   // the host vectors above end with this call
     return 0;
 }
@@ -549,17 +783,23 @@ extern "C" {
 const char* said_unet_train_tensor_name(int i) { return said_unet_train_table_name(0, i); }
 long long said_unet_train_tensor_numel(int i) { return said_unet_train_table_numel(0, i); }
 
-int said_unet_train_table_size(int feature_dim) { return feature_dim > SAID_UT_MAX_FEATURE_DIM ? -1 : (int)table(feature_dim).size(); }
-const char* said_unet_train_table_name(int feature_dim, int i) {
-    if (feature_dim > SAID_UT_MAX_FEATURE_DIM) return nullptr;
-    const auto& tb = table(feature_dim);
+int said_unet_train_table_size(int feature_dim) { return said_unet_train_table_size_ft(feature_dim, 0); }
+const char* said_unet_train_table_name(int feature_dim, int i) { return said_unet_train_table_name_ft(feature_dim, 0, i); }
+long long said_unet_train_table_numel(int feature_dim, int i) { return said_unet_train_table_numel_ft(feature_dim, 0, i); }
+int said_unet_train_table_size_ft(int feature_dim, int finetune_layers) {
+    return (feature_dim > SAID_UT_MAX_FEATURE_DIM || finetune_layers > SAID_UT_MAX_FINETUNE_LAYERS) ? -1 : (int)table(feature_dim, finetune_layers).size();
+}
+const char* said_unet_train_table_name_ft(int feature_dim, int finetune_layers, int i) {
+    if (feature_dim > SAID_UT_MAX_FEATURE_DIM || finetune_layers > SAID_UT_MAX_FINETUNE_LAYERS) return nullptr;
+    const auto& tb = table(feature_dim, finetune_layers);
     return (i >= 0 && i < (int)tb.size()) ? tb[i].name.c_str() : nullptr;
 }
-long long said_unet_train_table_numel(int feature_dim, int i) {
-    if (feature_dim > SAID_UT_MAX_FEATURE_DIM) return -1;
-    const auto& tb = table(feature_dim);
+long long said_unet_train_table_numel_ft(int feature_dim, int finetune_layers, int i) {
+    if (feature_dim > SAID_UT_MAX_FEATURE_DIM || finetune_layers > SAID_UT_MAX_FINETUNE_LAYERS) return -1;
+    const auto& tb = table(feature_dim, finetune_layers);
     return (i >= 0 && i < (int)tb.size()) ? tb[i].numel : -1;
 }
+int said_unet_train_finetune_layers(const said_unet_train* t) { return t ? t->L : -1; }
 int said_unet_train_num_tensors(const said_unet_train* t) { return t ? (int)t->tb->size() : -1; }
 int said_unet_train_feature_dim(const said_unet_train* t) { return (t && t->F > 0) ? t->F : -1; }
 const char* said_unet_train_context_tensor_name(const said_unet_train* t, int i) {
@@ -574,7 +814,14 @@ int said_unet_train_create(said_unet_train** out, int device, int max_batch, int
 }
 
 int said_unet_train_create_dim(said_unet_train** out, int device, int max_batch, int max_frames, int feature_dim) {
+    return said_unet_train_create_ft(out, device, max_batch, max_frames, feature_dim, 0);
+}
+
+int said_unet_train_create_ft(said_unet_train** out, int device, int max_batch, int max_frames, int feature_dim, int finetune_layers) {
     DeviceRestore restore_device;
+    static_assert(SAID_UT_MAX_FINETUNE_LAYERS == MAXL, "said_unet_train.h and the encoder's activation table disagree");
+    if (finetune_layers > SAID_UT_MAX_FINETUNE_LAYERS)
+        return fail(nullptr, "said_unet_train_create_ft: finetune_layers %d above %d (SAID_UT_MAX_FINETUNE_LAYERS)", finetune_layers, SAID_UT_MAX_FINETUNE_LAYERS);
     if (feature_dim > SAID_UT_MAX_FEATURE_DIM)
         return fail(nullptr, "said_unet_train_create_dim: feature_dim %d above %d (SAID_UT_MAX_FEATURE_DIM)", feature_dim, SAID_UT_MAX_FEATURE_DIM);
     said_unet_train* t = new_ctx("said_unet_train_create", out, device);
@@ -586,21 +833,33 @@ int said_unet_train_create_dim(said_unet_train** out, int device, int max_batch,
     t->maxT = max_frames;
     t->F = feature_dim > 0 ? feature_dim : 0;
     t->CTX = t->F > 0 ? t->F : AUD;
-    t->tb = &table(t->F);
+    t->L = finetune_layers > 0 ? finetune_layers : 0;
+    t->tb = &table(t->F, t->L);
     const auto& tb = *t->tb;
     std::vector<long long> sizes, off;
     for (const TDesc& d : tb) sizes.push_back(d.numel);
     Acts tmp;
-    t->arena_n = layout(tmp, nullptr, max_batch, max_frames, t->F);
+    EncActs etmp;
+    t->arena_n = layout(tmp, nullptr, max_batch, max_frames, t->F, t->L, &etmp);
+    // K-split partial tiles: the UNet's weight gradients; with a fine-tuned encoder its FFN's and the positional convolution's (768 x 48 x 128)
+    t->gpart_n = (size_t)MAXKS * std::max(TEd, t->F) * TEd;
+    if (t->L > 0) t->gpart_n = (size_t)MAXKS * EH * EPC * EPK;
     const size_t Mx = (size_t)max_batch * max_frames;
     int rc = 0;
     rc = rc || hipStreamCreateWithFlags(&t->s, hipStreamNonBlocking) != hipSuccess;
     rc = rc || dalloc(ctx, &t->rec, NSCAL + XC) || dalloc(ctx, &t->coeffs, Mx * XC) ||
          dalloc(ctx, &t->noise, Mx * XC) || dalloc(ctx, &t->tsf, max_batch) || dalloc(ctx, &t->sasb, (size_t)2 * max_batch) ||
          dalloc(ctx, &t->audio, Mx * AUD) || dalloc(ctx, &t->cond, max_batch) || dalloc(ctx, &t->band, (size_t)2 * max_frames) ||
-         dalloc(ctx, &t->arena, t->arena_n) || dalloc(ctx, &t->gpart, (size_t)MAXKS * std::max(TEd, t->F) * TEd) || dalloc(ctx, &t->vpart, VBLK);
+         dalloc(ctx, &t->arena, t->arena_n) || dalloc(ctx, &t->gpart, t->gpart_n) || dalloc(ctx, &t->vpart, VBLK);
+    if (t->L > 0) rc = rc || dalloc(ctx, &t->feat, Mx * ECONV) || dalloc(ctx, &t->mask, Mx);
     rc = rc || store_build(&t->st, ctx, sizes, true, &off);   // last: it ends with a synchronous copy, after every allocation's memset
-    for (size_t i = 0; i < tb.size() && !rc; ++i) t->off[tb[i].name] = off[i];
+    for (size_t i = 0; i < tb.size() && !rc; ++i) {
+        t->off[tb[i].name] = off[i];
+        if (tb[i].name.compare(0, strlen(kEnc), kEnc) == 0) {
+            if (t->enc_n == 0) t->enc_off = off[i];
+            t->enc_n += tb[i].numel;
+        }
+    }
     if (rc) {
         g_create_err = ctx->err.empty() ? std::string("said_unet_train_create: allocation failed") : ctx->err;
         said_unet_train_destroy(t);
@@ -734,6 +993,112 @@ int said_unet_train_forward_only(said_unet_train* t, int B, int T, const float* 
     enqueue_forward(t, B, T, ema ? t->st.E : t->st.P, 0.f, 0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, t->a.pred, (size_t)B * T * XC * sizeof(float), hipMemcpyDeviceToHost, t->s));
+    HIPCHK(hipStreamSynchronize(t->s));
+    return 0;
+}
+
+// the _ft entry points' own checks and the upload of the step's time mask; tp may be null (eval mode)
+static int put_audio_params(said_unet_train* t, const char* what, int B, int T, const said_audio_train_params* tp) {
+    HostCtx* ctx = &t->c;
+    if (!tp) return 0;
+    for (const float p : {tp->p_feat_proj, tp->p_hidden, tp->p_attention, tp->p_activation})
+        if (!(p >= 0.f && p < 1.f)) return fail(ctx, "%s: dropout probability %g is outside [0, 1)", what, (double)p);
+    if (tp->time_mask_dev) {
+        HIPCHK(hipMemcpyAsync(t->mask, tp->time_mask_dev, (size_t)B * T, hipMemcpyDeviceToDevice, t->s));
+        HIPCHK(hipStreamSynchronize(t->s));   // the caller's mask may go away after the call
+    }
+    return 0;
+}
+
+int said_unet_train_step_ft(said_unet_train* t, int B, int T, const float* coeffs, const float* noise, const long long* ts, const int* cond,
+                            const void* features, int features_on_device, const said_audio_train_params* tp, unsigned long long seed,
+                            const float* scalars, const float* std_, const float* deltas, int V) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    const char* what = "said_unet_train_step_ft";
+    if (!noise || !scalars) return fail(ctx, "%s: null noise or scalars", what);
+    const float p = scalars[SAID_UT_S_DROPOUT];
+    if (!(p >= 0.f && p < 1.f)) return fail(ctx, "%s: dropout probability %g outside [0, 1)", what, (double)p);
+    if (check_std(t, std_, what)) return -1;
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (put_inputs(t, what, B, T, coeffs, noise, ts, cond, features, features_on_device, true, true) || put_audio_params(t, what, B, T, tp) ||
+        put_deltas(t, what, B, T, deltas, V) || put_record(t, scalars, std_))
+        return -1;
+    layout(t->a, t->arena, B, T, t->F, t->L, &t->e);
+    const size_t M = (size_t)B * T;
+    add_noise(t->s, B, T, t->coeffs, t->noise, t->sasb, t->rec, t->a.noisy, t->a.answer);
+    enqueue_enc_forward(t, B, T, t->st.P, tp);
+    enqueue_forward(t, B, T, t->st.P, p, seed);
+    enqueue_loss(t, B, T, deltas ? V : 0, true, t->st.acc);
+    HIPCHK(hipMemsetAsync(t->a.dembs, 0, (size_t)B * TEd * sizeof(float), t->s));
+    HIPCHK(hipMemsetAsync(t->a.dctx, 0, M * t->CTX * sizeof(float), t->s));
+    HIPCHK(hipMemsetAsync(t->st.G + t->enc_off, 0, (size_t)t->enc_n * sizeof(float), t->s));
+    enqueue_backward(t, B, T, p, seed);
+    // a.dcond: the conditional samples' rows of the context gradient; through W_proj when there is a projection
+    float* dE = t->a.dcond;
+    if (t->F > 0) {
+        Gm{t}.lin_dgrad(t->a.dcond, par(t, t->st.P, "audio_proj_layer.weight"), t->e.d, AUD, (int)M, t->CTX, AUD, 0);
+        dE = t->e.d;
+    }
+    enqueue_enc_backward(t, B, T, tp, dE);
+    store_enqueue_update(&t->st, t->s, t->rec);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int said_unet_train_eval_loss_ft(said_unet_train* t, int B, int T, const float* coeffs, const float* noise, const long long* ts, const int* cond,
+                                 const void* features, int features_on_device, const said_audio_train_params* tp, const float* scalars,
+                                 const float* std_, const float* deltas, int V, int ema) {
+    if (!t) return -1;
+    (void)tp;   // validation runs the encoder in eval mode
+    HostCtx* ctx = &t->c;
+    const char* what = "said_unet_train_eval_loss_ft";
+    if (!noise || !scalars) return fail(ctx, "%s: null noise or scalars", what);
+    if (check_std(t, std_, what)) return -1;
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (put_inputs(t, what, B, T, coeffs, noise, ts, cond, features, features_on_device, true, true) || put_deltas(t, what, B, T, deltas, V) ||
+        put_record(t, scalars, std_))
+        return -1;
+    layout(t->a, t->arena, B, T, t->F, t->L, &t->e);
+    add_noise(t->s, B, T, t->coeffs, t->noise, t->sasb, t->rec, t->a.noisy, t->a.answer);
+    enqueue_enc_forward(t, B, T, ema ? t->st.E : t->st.P, nullptr);
+    enqueue_forward(t, B, T, ema ? t->st.E : t->st.P, 0.f, 0);
+    enqueue_loss(t, B, T, deltas ? V : 0, false, t->st.acc + NACC);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int said_unet_train_forward_only_ft(said_unet_train* t, int B, int T, const float* sample, const long long* ts, const int* cond, const void* features,
+                                    int features_on_device, const said_audio_train_params* tp, int ema, float* out) {
+    if (!t) return -1;
+    (void)tp;   // the forward runs the encoder in eval mode
+    HostCtx* ctx = &t->c;
+    const char* what = "said_unet_train_forward_only_ft";
+    if (!out) return fail(ctx, "%s: null output", what);
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (put_inputs(t, what, B, T, sample, nullptr, ts, cond, features, features_on_device, false, true)) return -1;
+    layout(t->a, t->arena, B, T, t->F, t->L, &t->e);
+    HIPCHK(hipMemcpyAsync(t->a.noisy, t->coeffs, (size_t)B * T * XC * sizeof(float), hipMemcpyDeviceToDevice, t->s));
+    enqueue_enc_forward(t, B, T, ema ? t->st.E : t->st.P, nullptr);
+    enqueue_forward(t, B, T, ema ? t->st.E : t->st.P, 0.f, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, t->a.pred, (size_t)B * T * XC * sizeof(float), hipMemcpyDeviceToHost, t->s));
+    HIPCHK(hipStreamSynchronize(t->s));
+    return 0;
+}
+
+int said_unet_train_last_conditioning(said_unet_train* t, int B, int T, float* out) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    if (t->L <= 0 || !out || B < 1 || B > t->maxB || T < 2 || T > t->maxT)
+        return fail(ctx, "said_unet_train_last_conditioning: needs a fine-tuning context, an output and the last call's shape");
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    layout(t->a, t->arena, B, T, t->F, t->L, &t->e);
+    HIPCHK(hipMemcpyAsync(out, t->a.ctx, (size_t)B * T * t->CTX * sizeof(float), hipMemcpyDeviceToHost, t->s));
     HIPCHK(hipStreamSynchronize(t->s));
     return 0;
 }

@@ -266,6 +266,11 @@ class SAID(ABC, nn.Module):
         return e.audio_encode_train(waveform, num_frames, train_draws, train_cfg if train_cfg is not None else AudioTrainConfig(),
                                     apply_proj=apply_proj)
 
+    def get_audio_features(self, waveform: torch.FloatTensor, num_frames: Optional[int]) -> torch.FloatTensor:
+        """(B, T_a) -> (B, num_frames, 512): the frozen feature extractor's output after the interpolation (not part of the reference
+        surface): the input of a denoiser trainer that fine-tunes the Wav2Vec2 transformer."""
+        return self._get_engine(1, num_frames or 1).extract_features(waveform, num_frames)
+
     def _encode_distinct(self, waveform: torch.FloatTensor, num_frames: int) -> torch.FloatTensor:
         """get_audio_embedding with byte-identical rows encoded once.  Candidates are found from two cheap per-row checksums (two passes over
         the batch: a sort of whole 160,000-sample rows would cost more than it saves on a batch of distinct clips) and then compared exactly."""

@@ -6,7 +6,9 @@ trainable nn.Linear(768, feature_dim) behind the frozen encoder), their AdamW mo
 ``random_noise_loss``, backward, ``clip_grad_norm_(1.0)``, ``torch.optim.AdamW`` and diffusers' ``EMAModel.step``.  The host draws what the
 reference draws on the host (noise and timesteps on torch's CPU generator, plus one 64-bit dropout seed per step) and writes the per-step
 scalars.  The audio encoder is frozen; its embedding of the batch is an input of the step.  It runs as in inference, or, with
-``train_epoch(..., audio_train=AudioTrainConfig())``, in Wav2Vec2's train mode as the reference's does.
+``train_epoch(..., audio_train=AudioTrainConfig())``, in Wav2Vec2's train mode as the reference's does.  With
+``finetune_audio_layers > 0`` the Wav2Vec2 transformer is not frozen: it trains in the same step, behind the frozen feature extractor
+(DESIGN.md 16.9).
 """
 from __future__ import annotations
 
@@ -56,10 +58,12 @@ class UNetLossEpochOutput:
     lr: Optional[float] = None
 
 
-def trainable_shapes(feature_dim: int = -1) -> "OrderedDict[str, Tuple[int, ...]]":
+def trainable_shapes(feature_dim: int = -1, finetune_layers: int = 0) -> "OrderedDict[str, Tuple[int, ...]]":
     """Names and shapes of the trainable tensors of SAID_UNet1D(feature_dim=feature_dim) in state_dict() order: null_cond_emb, with
     feature_dim > 0 audio_proj_layer.weight / .bias, then denoiser.model.* as the reference registers them (BasicTransformerBlock: attn1,
-    ff, attn2, norm1..3).  The context width (null_cond_emb, attn2.to_k / to_v) is feature_dim when > 0, else 768."""
+    ff, attn2, norm1..3).  The context width (null_cond_emb, attn2.to_k / to_v) is feature_dim when > 0, else 768.  finetune_layers = L > 0
+    appends the Wav2Vec2 transformer of an L-layer encoder: audio_encoder.* without audio_encoder.feature_extractor.*, in the encoder's
+    state-dict order (said_amd.util.synth.w2v_param_shapes)."""
     C, E = 192, 768
     X = feature_dim if feature_dim > 0 else 768
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict([("null_cond_emb", (1, 1, X))])
@@ -104,6 +108,11 @@ def trainable_shapes(feature_dim: int = -1) -> "OrderedDict[str, Tuple[int, ...]
     res(m + "output_blocks.1.0", 2 * C); st(m + "output_blocks.1.1")
     s[m + "out.0.weight"], s[m + "out.0.bias"] = (C,), (C,)
     wb(m + "out.2", 32, C, 3)
+    if finetune_layers > 0:
+        from ..util.synth import w2v_param_shapes
+        for k, shp in w2v_param_shapes(finetune_layers).items():
+            if not k.startswith("feature_extractor."):
+                s["audio_encoder." + k] = tuple(shp)
     return s
 
 
@@ -160,16 +169,22 @@ class UNetTrainer(TrainerBase):
     feature_dim = F > 0 trains SAID_UNet1D(feature_dim=F): audio_proj_layer.* of `state_dict` is the trainable projection's initial value,
     the context is F wide, and the audio embedding given to step / eval_loss / forward_only stays the encoder's (B, T, 768) output, before
     the projection (batch_audio_embedding asks the model for that).
+
+    finetune_audio_layers = L > 0 trains the Wav2Vec2 transformer of `state_dict`'s L-layer encoder with the denoiser (the reference's
+    `said_model.audio_encoder.freeze_feature_encoder()` variant): audio_encoder.* except audio_encoder.feature_extractor.*
+    join the trainable tensors, and step / eval_loss / forward_only take the frozen extractor's features (B, T, 512) (batch_audio_features)
+    in place of the audio embedding.  step's audio_draws / audio_cfg put the encoder in Wav2Vec2's train mode.
     """
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", max_batch: int = 8, max_frames: int = 512, learning_rate: float = 1e-5,
                  num_warmup_steps: float = 0, ema: bool = True, ema_decay: float = 0.9999, std=None, prediction_type: str = "epsilon",
                  dropout: float = 0.1, weight_decay: float = 0.01, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 num_train_timesteps: int = 1000, feature_dim: int = -1):
+                 num_train_timesteps: int = 1000, feature_dim: int = -1, finetune_audio_layers: int = 0):
         if prediction_type not in PREDICTION_TYPES:
             raise ValueError(f"prediction_type must be one of {sorted(PREDICTION_TYPES)}, got {prediction_type!r}")
-        self.eng = _engine.UNetTrainEngine(torch.device(device), max_batch, max_frames, feature_dim)
+        self.eng = _engine.UNetTrainEngine(torch.device(device), max_batch, max_frames, feature_dim, finetune_audio_layers)
         self.feature_dim = self.eng.feature_dim
+        self.finetune_audio_layers = self.eng.finetune_layers
         self.device = self.eng.device
         self.max_batch, self.max_frames = int(max_batch), int(max_frames)
         self._set_optimizer(learning_rate, num_warmup_steps, weight_decay, betas, eps, ema, ema_decay)
@@ -178,7 +193,7 @@ class UNetTrainer(TrainerBase):
         self.alphas_cumprod = DDIMScheduler(num_train_timesteps=num_train_timesteps, beta_schedule="squaredcos_cap_v2").alphas_cumprod.float()
         self.eng.set_alphas(self.alphas_cumprod.numpy())
         self.std = parse_std(std)
-        self._shapes = trainable_shapes(self.feature_dim)
+        self._shapes = trainable_shapes(self.feature_dim, self.finetune_audio_layers)
         self._stored = False
         self.load_state_dict(state_dict)
 
@@ -195,6 +210,7 @@ class UNetTrainer(TrainerBase):
                 raise ValueError(f"{name}: shape {tuple(v.shape)}, expected {self._shapes[name]} (feature_dim={self.feature_dim})")
             self.eng.set_tensor(_engine.UT_STATE, name, v.numpy())
         self._frozen = OrderedDict((k, v.detach().cpu().clone()) for k, v in state_dict.items() if k not in self._shapes)
+        self._given_order = list(state_dict)
         self.eng.reset_optimizer()
         self.step_count = 0
 
@@ -204,8 +220,13 @@ class UNetTrainer(TrainerBase):
         out = OrderedDict()
         tr = self.parameters_of(_engine.UT_EMA if (ema and self.ema) else _engine.UT_STATE)
         out["null_cond_emb"] = tr["null_cond_emb"]   # SAID registers audio_encoder, (audio_proj_layer,) null_cond_emb's parameter first, denoiser
-        out.update(self._frozen)
-        out.update((k, v) for k, v in tr.items() if k != "null_cond_emb")
+        if self.finetune_audio_layers > 0:
+            # the trained transformer over the frozen feature extractor, in the order the encoder's keys were given in
+            out.update((k, tr[k] if k in tr else self._frozen[k]) for k in self._given_order if k.startswith("audio_encoder."))
+            out.update((k, v) for k, v in self._frozen.items() if k not in out)
+        else:
+            out.update(self._frozen)
+        out.update((k, v) for k, v in tr.items() if k != "null_cond_emb" and k not in out)
         return out
 
     # ---- EMAModel.store / copy_to / restore
@@ -243,13 +264,17 @@ class UNetTrainer(TrainerBase):
         return x.numpy(), torch.as_tensor(noise, dtype=torch.float32).cpu().numpy(), torch.as_tensor(timesteps).cpu().numpy()
 
     def enqueue_step(self, coeffs, cond, audio_embedding, noise=None, timesteps=None, dropout_seed: Optional[int] = None, weight_vel: float = 1.0,
-                     weight_vertex: float = 0.02, deltas=None) -> None:
-        """One optimizer step; nothing is read back."""
+                     weight_vertex: float = 0.02, deltas=None, audio_draws=None, audio_cfg: Optional[AudioTrainConfig] = None) -> None:
+        """One optimizer step; nothing is read back.  With finetune_audio_layers > 0, `audio_embedding` holds the conv features and
+        audio_draws (an AudioTrainDraws) / audio_cfg run the encoder in train mode."""
+        if audio_draws is not None and self.finetune_audio_layers <= 0:
+            raise ValueError("audio_draws: the encoder is frozen here; it runs in train mode where its embedding is computed (batch_audio_embedding)")
         x, nz, ts = self._draws(coeffs, noise, timesteps)
         if dropout_seed is None:
             dropout_seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.dropout > 0 else 0
         self.eng.step(x, nz, ts, cond, audio_embedding, dropout_seed, self._scalars(weight_vel, weight_vertex, self.step_count, self.dropout),
-                      self.std, None if deltas is None else np.asarray(deltas, dtype=np.float32))
+                      self.std, None if deltas is None else np.asarray(deltas, dtype=np.float32), audio_draws=audio_draws,
+                      audio_cfg=(audio_cfg or AudioTrainConfig()) if audio_draws is not None else None)
         self.step_count += 1
 
     def step(self, coeffs, cond, audio_embedding, **kw) -> UNetLossStepOutput:
@@ -283,6 +308,14 @@ class UNetTrainer(TrainerBase):
         losses read once at the end; lr is the LR after the last step.  audio_train: the encoder in Wav2Vec2's train mode (the reference
         calls said_model.train() before its epoch); None: as in inference."""
         for data in train_dataloader:
+            if self.finetune_audio_layers > 0:
+                # the draws come where batch_audio_embedding draws them: before the step's own
+                feats = batch_audio_features(model, data)
+                draws = None if audio_train is None else draw_audio_train(audio_train, feats.shape[0], feats.shape[1], self.finetune_audio_layers)
+                self.enqueue_step(data.blendshape_coeffs, data.cond, feats, weight_vel=weight_vel, weight_vertex=weight_vertex,
+                                  deltas=None if data.blendshape_delta is None else normalize_deltas(data.blendshape_delta), audio_draws=draws,
+                                  audio_cfg=audio_train)
+                continue
             self.enqueue_step(data.blendshape_coeffs, data.cond, batch_audio_embedding(model, data, audio_train, self.feature_dim > 0), weight_vel=weight_vel,
                               weight_vertex=weight_vertex, deltas=None if data.blendshape_delta is None else normalize_deltas(data.blendshape_delta))
         return self.epoch_output(False, self.lr_at(self.step_count))
@@ -293,7 +326,8 @@ class UNetTrainer(TrainerBase):
         reference does) or, with use_ema, directly on the EMA copy."""
         for _ in range(num_repeat):
             for data in val_dataloader:
-                self.eval_loss(data.blendshape_coeffs, data.cond, batch_audio_embedding(model, data, before_proj=self.feature_dim > 0), weight_vel=weight_vel, weight_vertex=weight_vertex,
+                audio = batch_audio_features(model, data) if self.finetune_audio_layers > 0 else batch_audio_embedding(model, data, before_proj=self.feature_dim > 0)
+                self.eval_loss(data.blendshape_coeffs, data.cond, audio, weight_vel=weight_vel, weight_vertex=weight_vertex,
                                deltas=None if data.blendshape_delta is None else normalize_deltas(data.blendshape_delta), use_ema=use_ema)
         return self.epoch_output(True)
 
@@ -310,6 +344,13 @@ def batch_audio_embedding(model, data, audio_train: Optional[AudioTrainConfig] =
         return model.get_audio_embedding(wave, frames, before_proj=before_proj).float()
     draws = draw_audio_train(audio_train, wave.shape[0], frames, model.audio_config.num_hidden_layers)
     return model.get_audio_embedding(wave, frames, train_draws=draws, train_cfg=audio_train, before_proj=before_proj).float()
+
+
+def batch_audio_features(model, data) -> torch.Tensor:
+    """(B, T, 512) conv features of a batch's waveforms by the model's frozen feature extractor, interpolated to the batch's frames: what a
+    trainer with finetune_audio_layers > 0 takes in place of the audio embedding."""
+    wave = model.process_audio(data.waveform).to(next(model.parameters()).device)
+    return model.get_audio_features(wave, data.blendshape_coeffs.shape[1]).float()
 
 
 # ---------------------------------------------------------------------------------------------------------------- data sets

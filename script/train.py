@@ -10,6 +10,11 @@ Command-line compatible with the reference (same flags, names and defaults; `--e
 - --unet_feature_dim F > 0 trains the extra audio_proj_layer = nn.Linear(768, F) inside the HIP step, with the rest: the
   model built here serves only as the frozen encoder, its own audio_proj_layer is never read.  F must be a multiple of 16, at most 1024:
   the inference engine, which runs that encoder and later the checkpoint, takes such context widths only.
+- --finetune_audio_encoder trains the Wav2Vec2 transformer (feature projection, positional convolution, every transformer layer of the
+  loaded encoder) together with the denoiser in the same HIP step, with the convolutional feature extractor frozen: the reference's
+  commented `said_model.audio_encoder.freeze_feature_encoder()` variant, the paper's "finetune_wav2vec" ablation.
+  --audio_encoder_mode keeps its meaning: 'train' gives the encoder its masks, dropouts and LayerDrop, 'eval' none.  <epoch>.pth then holds
+  the trained audio_encoder.* tensors.  Off by default; without it nothing changes.
 - New flags: --seed, --device.  Logs go to stdout and to <output_dir>/log.csv (the reference's TensorBoard keys as columns).
 - <output_dir>/<epoch>.pth is SAID_UNet1D's state dict, written between EMA copy_to and restore as in the reference.
 """
@@ -63,6 +68,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="state dict holding audio_encoder.* (the frozen Wav2Vec2), or 'synthetic' for the seeded test weights")
     ap.add_argument("--audio_encoder_mode", type=str, default="eval", choices=["eval", "train"],
                     help="the frozen audio encoder during training: 'eval' as in inference, 'train' as the reference leaves it (SpecAugment, dropout, LayerDrop)")
+    ap.add_argument("--finetune_audio_encoder", action="store_true",
+                    help="train the Wav2Vec2 transformer with the denoiser (the feature extractor stays frozen)")
     ap.add_argument("--seed", type=int, default=None, help="seed of Python's random, numpy and torch (unseeded by default)")
     ap.add_argument("--device", type=str, default="cuda:0", help="MI355X to train on (there is no CPU path)")
     return ap
@@ -102,7 +109,8 @@ def main(argv=None):
     max_frames = max([c.shape[0] for _, c, _ in train_dataset.data + val_dataset.data])
     trainer = UNetTrainer(state, args.device, max_batch=args.batch_size, max_frames=max_frames, learning_rate=args.learning_rate,
                           num_warmup_steps=len(train_dataloader) * args.num_warmup_epochs, ema=args.ema, ema_decay=args.ema_decay, std=coeffs_std,
-                          prediction_type=args.prediction_type, feature_dim=args.unet_feature_dim)
+                          prediction_type=args.prediction_type, feature_dim=args.unet_feature_dim,
+                          finetune_audio_layers=model.audio_config.num_hidden_layers if args.finetune_audio_encoder else 0)
 
     audio_train = AudioTrainConfig() if args.audio_encoder_mode == "train" else None
     with open(os.path.join(args.output_dir, "log.csv"), "a", newline="") as f:
