@@ -10,6 +10,7 @@
 #include "engine_internal.h"
 #include "train_store.h"
 #include "unet_train.h"
+#include "ut_gemm_plan.h"
 
 #include <map>
 #include <mutex>
@@ -29,6 +30,7 @@ constexpr int AUD = SAID_UT_CTX_DIM;   // width of the frozen encoder's output, 
 // F <= 0: the context is the encoder's output itself (SAID_UNet1D(feature_dim = -1))
 // audio_encoder.* of an L-layer wav2vec2-base encoder without its feature extractor, in state-dict order (transformers 4.30.2 key layout)
 constexpr int EH = 768, ECONV = 512, EFFN = 3072, ENH = 12, EHD = 64, EPK = 128, EPG = 16, EPC = EH / EPG, MAXL = 32;
+static_assert(TEd == UT_TED && EH == UT_EH && EPG == UT_EPG && EPC == UT_EPC && EPK == UT_EPK, "ut_gemm_plan.h sizes gpart for these widths");
 const char* const kEnc = "audio_encoder.";
 std::string enc_layer(int l) { return std::string(kEnc) + "encoder.layers." + std::to_string(l); }
 void add_encoder(std::vector<TDesc>& v, int L) {
@@ -111,7 +113,7 @@ const char* kRes[5] = {"denoiser.model.input_blocks.1.0", "denoiser.model.middle
 const int kResCin[5] = {CH, CH, CH, 2 * CH, 2 * CH};
 const char* kST[4] = {"denoiser.model.input_blocks.1.1", "denoiser.model.middle_block.1", "denoiser.model.output_blocks.0.1",
                       "denoiser.model.output_blocks.1.1"};
-constexpr int MAXKS = 16, VBLK = 256;
+constexpr int VBLK = 256;
 
 // what a ResBlock / SpatialTransformer keeps from the forward
 struct ResAct { const float* x; int ldx; float *xh1, *rs1, *a1, *ee, *c1, *xh2, *rs2, *a2, *out; };
@@ -222,14 +224,13 @@ struct Gm {
     said_unet_train* t;
     UGemm base(UOp A, UOp B, float* C, int ldc, int M, int N, int K) const {
         UGemm g{};
-        g.A = A; g.B = B; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.Z = 1; g.ZH = 1; g.alpha = 1.f; g.rbT = 1; g.KS = 1; g.kchunk = rup(std::max(K, 1), 16);
+        g.A = A; g.B = B; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.Z = 1; g.ZH = 1; g.alpha = 1.f; g.rbT = 1; g.KS = 1; g.kchunk = ut_unsplit(K).kchunk;
         g.part = t->gpart;
         return g;
     }
     void ksplit(UGemm& g) const {   // the weight gradients: few tiles, long K
-        const int ks = std::min(MAXKS, std::max(1, g.K / 128));
-        g.KS = ks;
-        g.kchunk = rup((g.K + ks - 1) / ks, 16);
+        const UtSplit p = ut_ksplit(g.K, g.M, g.N, g.Z, t->gpart_n);
+        g.KS = p.KS; g.kchunk = p.kchunk;
     }
     // y (M, N) = x (M, K; ldx) W^T (W: N x K) + bias (+ rowb) (+ res)
     void lin(const float* x, int ldx, const float* W, const float* bias, float* y, int ldy, int M, int N, int K, const float* res = nullptr, int ldr = 0,
@@ -550,8 +551,8 @@ struct EncGm {
     // the grouped positional convolution (k = 128, padding 64, the last output dropped) as shifted-operand GEMMs, the group as batch index;
     // a short batch splits K = 128 x 48 so that more than 16 workgroups run
     void split_small(UGemm& g) const {
-        const int ks = 8;
-        if (g.M <= 256 && (size_t)ks * g.Z * g.M * g.N <= t->gpart_n) { g.KS = ks; g.kchunk = rup((g.K + ks - 1) / ks, 16); }
+        const UtSplit p = ut_split_small(g.K, g.M, g.N, g.Z, t->gpart_n);
+        g.KS = p.KS; g.kchunk = p.kchunk;
     }
     void pos_fwd(const float* h, const float* w, float* y) const {   // without the bias: the epilogue's bias[n] counts columns inside a group
         UOp A{h, 0, EPC, 0, T, EH, 0, 1, 0, EPC, EPK, 0, -EPK / 2, 1};
@@ -842,8 +843,7 @@ int said_unet_train_create_ft(said_unet_train** out, int device, int max_batch, 
     EncActs etmp;
     t->arena_n = layout(tmp, nullptr, max_batch, max_frames, t->F, t->L, &etmp);
     // K-split partial tiles: the UNet's weight gradients; with a fine-tuned encoder its FFN's and the positional convolution's (768 x 48 x 128)
-    t->gpart_n = (size_t)MAXKS * std::max(TEd, t->F) * TEd;
-    if (t->L > 0) t->gpart_n = (size_t)MAXKS * EH * EPC * EPK;
+    t->gpart_n = ut_gpart_n(t->F, t->L);
     const size_t Mx = (size_t)max_batch * max_frames;
     int rc = 0;
     rc = rc || hipStreamCreateWithFlags(&t->s, hipStreamNonBlocking) != hipSuccess;
