@@ -2,7 +2,7 @@
 
 fp32 mode with its default options — nothing switched off — is stopped behind every launch of the channel-major schedule (said_debug_stop_after), the launch's
 inputs and outputs are read back AS STORED (the workspace list: Engine.ws_buffers / ws_snapshot), and the output is compared with tests/unet_f32_ref.py's evaluation
-of those inputs in float64 (tests/test_unet_f32_ref_cpu.py ties that restatement to the oracle and shows that fourteen ways of being wrong exceed the bound 70 x
+of those inputs in float64 (tests/test_unet_f32_ref_cpu.py ties that restatement to the oracle and shows that twenty ways of being wrong exceed the bound 70 x
 at least).  The rule is the project's (audio_bf16_ref.check_f32):
     max |got - ref64| / max |ref64| <= 4 max(e32, 1e-6),   e32 the same figure of the torch fp32 CPU evaluation of the identical inputs,
 over all samples, channels and tokens [0, T).  Per launch: conv_in_kernel / the generic convolution (H0); ugemm_kernel with ugemm_body or kconv_body (the ResBlock
@@ -37,6 +37,8 @@ inconsistent (one element in ~2000 has a remainder of exactly half a step); KVT,
 and bit-identical.
 Largest e per shape: S 3.1e-7, M1 2.7e-7, M2 3.2e-7, L 4.3e-7, S trained-like 9.7e-7, G 2.9e-7, G-eta 3.0e-7, F 3.3e-7.  pytest --durations: L 1.1 s,
 S trained-like 0.8 s, S 0.5 s, M2 0.3 s, M1 0.2 s, F 0.14 s, G / G-eta 0.1 s, each of the five fill tests <= 0.03 s (the module's model 2 s once).
+The schedules, the stop-and-read loop (Stops) and the per-launch checks live in tests/unet_f32_stops.py, shared with tests/test_gpu_unet_f32_strict_kernels.py (strict
+fp32, the five-launch tail, attn_kernel<QW 4>, the one-slice chain).
 """
 import numpy as np
 import pytest
@@ -46,26 +48,18 @@ import unet_f32_ref as R
 from audio_bf16_ref import check_exact, check_f32
 from oracle import pipeline as op
 from said_amd.util import synth
+# the schedules, the stop-and-read loop and the per-launch checks: shared with tests/test_gpu_unet_f32_strict_kernels.py
+from unet_f32_stops import (F32, F64, GS, MC, Stops, _check_launch, _check_launch_f, _kv_checks, _model, _partials, _poison, _schedule, _schedule_f,  # noqa: F401
+                            _summary)
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
-F64, F32 = torch.float64, torch.float32
-MC = R.MC
-GS = 2.0
 
 
 @pytest.fixture(scope="module")
 def dev():
     assert torch.cuda.is_available(), "gpu tests need the MI355X"
     return torch.device("cuda:0")
-
-
-def _model(dev, sd):
-    from said_amd.model.diffusion import SAID_UNet1D
-    from said_amd.model.wav2vec2 import AudioConfig
-    m = SAID_UNet1D(audio_config=AudioConfig(num_hidden_layers=1))
-    m.load_state_dict(sd, strict=True)
-    return m.to(dev).eval()
 
 
 @pytest.fixture(scope="module")
@@ -75,62 +69,7 @@ def plain(dev):
     return _model(dev, sd), sd_u, null
 
 
-# ---------------------------------------------------------------- the schedule (unet_sched.cpp run_unet) and what each launch reads and writes
-def _schedule(guided):
-    L = [("conv_in",)]
-
-    def res(i, in0, in1, out, shared=False):
-        L.append(("conv1", i, in0, in1, shared))
-        L.append(("conv2", i, in0, in1, out, shared))
-
-    def st(j, inn, out, shared=False):
-        L.append(("qkv", j, inn, shared))
-        L.append(("attn", j, shared))
-        L.append(("chain", j, inn, out, shared))
-
-    res(0, "H0", None, "P", guided); st(0, "P", "H1", guided)
-    res(1, "H1", None, "P"); st(1, "P", "Q")
-    res(2, "Q", None, "P")
-    res(3, "P", "H1", "Q"); st(2, "Q", "P")
-    res(4, "P", "H0", "Q"); st(3, "Q", "P")
-    L.append(("out_sched",) if guided else ("out",))
-    return L
-
-
-def _io(launch):
-    """(buffers read, buffers written) of a launch, by workspace name."""
-    k = launch[0]
-    if k == "conv_in":
-        return ["x"], ["H0", "stH0"]
-    if k == "conv1":
-        srcs = [s for s in launch[2:4] if s]
-        return srcs + ["st" + s for s in srcs] + ["EO"], ["M", "stM"]
-    if k == "conv2":
-        srcs = [s for s in launch[2:4] if s]
-        return ["M", "stM"] + srcs, [launch[4], "st" + launch[4]]
-    if k == "qkv":
-        return [launch[2], "st" + launch[2]], ["QK", "VT", "gn_coef"]
-    if k == "attn":
-        return ["QK", "VT"], ["O"]
-    if k == "chain":
-        return ["O", launch[2], "gn_coef", "KV"], [launch[3], "st" + launch[3]]
-    if k == "out":
-        return ["P", "stP"], ["eps"]
-    if k == "prep0":     # operand of a ResBlock convolution from source `src` into columns [off, off + 192) of uPA (and its raw copy into uPB)
-        _, i, src, off, cin, raw = launch
-        return [src, "st" + src], [f"uPA:{cin}"] + ([f"uPB:{2 * MC}"] if raw else [])
-    if k == "fconv1":
-        return [f"uPA:{launch[2]}", "EO"], ["M", "stM"]
-    if k == "fconv2":
-        _, i, in0, in1, out = launch
-        return [f"uPA:{MC}"] + ([f"uPB:{2 * MC}"] if in1 else [in0]), [out, "st" + out]
-    if k == "prep1":
-        return [launch[2], "st" + launch[2]], [f"uPL:{MC}", "gn_coef"]
-    if k == "fqkv":
-        return [f"uPL:{MC}"], ["QK", "VT"]
-    return ["P", "stP"], []   # out_sched: its output is the loop's result
-
-
+# ---------------------------------------------------------------- the schedule's stage log
 def _expected_stages(guided, nb_in, nb, nb_cat, nb_qkv, ks):
     """(kind, epi, NB, KS) per launch as unet_sched.cpp logs them: 0 the generic GEMM, 2 ugemm_kernel, 1 attention (NB = head_dim / 32; KS 34 = attn2q_kernel),
     10 stchain_kernel, 11 conv_in_kernel, 12 the out convolution.  profile_unet never logs out_sched_kernel: its stage list ends with the out convolution."""
@@ -150,143 +89,6 @@ def _expected_stages(guided, nb_in, nb, nb_cat, nb_qkv, ks):
         else:
             out.append((12, 0, 1, 8))
     return out
-
-
-class Stops:
-    """One shape's stopped runs: `run` makes the call (forward pass or loop step), stop(k, launch) makes it with the first k launches and reads the launch's buffers."""
-
-    def __init__(self, eng, Be, T, S, run):
-        self.eng, self.Be, self.T, self.S, self.run = eng, Be, T, S, run
-        self.Tp, self.Sp, self.np = R.rup(T, 32), R.rup(S, 32), (T + 31) // 32
-        self.sizes = {nm: nb for _, nm, nb in eng.ws_buffers()}
-        self.index = {nm: i for i, nm, _ in eng.ws_buffers()}
-        self.cur = {}
-
-    def raw(self, name, nfloat):
-        assert 4 * nfloat <= self.sizes[name], (name, nfloat, self.sizes[name])
-        t = self.eng.ws_snapshot(self.index[name], 4 * nfloat)
-        torch.cuda.synchronize()
-        return t.cpu().view(torch.float32)
-
-    def read(self, name):
-        """The buffer as stored, pad tokens removed."""
-        Be, T, Tp = self.Be, self.T, self.Tp
-        if name in ("H0", "H1", "P", "Q", "M"):
-            return self.raw(name, Be * MC * Tp).view(Be, MC, Tp)[:, :, :T].clone()
-        if name.startswith("st"):
-            return self.raw(name, Be * self.np * MC * 2).view(Be, self.np, MC, 2).clone()
-        if name in ("x", "eps"):
-            return self.raw(name, Be * 32 * Tp).view(Be, 32, Tp)[:, :, :T].clone()
-        if name == "O":
-            return self.raw(name, Be * 2 * MC * Tp).view(Be, 2 * MC, Tp)[:, :MC, :T].clone()
-        if name == "QK":
-            return self.raw(name, Be * 12 * Tp * 32).view(Be, 12, Tp, 32)[:, :, :T].clone()
-        if name == "VT":
-            return self.raw(name, Be * MC * Tp).view(Be, MC, Tp)[:, :, :T].clone()
-        if name == "gn_coef":
-            return self.raw(name, Be * MC * 2).view(Be, MC, 2).clone()
-        if name == "EO":
-            n = self.sizes["EO"] // 4
-            return self.raw(name, n).view(5, MC, n // (5 * MC))[:, :, :max(Be, 1)].clone()
-        if name == "KV":
-            return self.raw(name, Be * R.NST * 2 * MC * self.Sp).view(Be, R.NST * 2 * MC, self.Sp)[:, :, :self.S].clone()
-        if name == "KVT":
-            return self.raw(name, Be * self.S * R.NST * 2 * MC).view(Be, self.S, R.NST * 2 * MC).clone()
-        if name.startswith("uP"):   # token-major operands of the large-batch route: [sample][rup(T + 2, 32) rows][columns] dwords
-            cols = int(name.split(":")[1])
-            rows = R.rup(T + 2, 32)
-            return self.raw(name.split(":")[0], Be * rows * cols).view(Be, rows, cols).clone()
-        raise KeyError(name)
-
-    def stop(self, k, launch):
-        """Runs the first k launches; re-reads the launch's inputs (bit-equal to what an earlier stop saw) and reads its outputs."""
-        self.eng.debug_stop_after(k)
-        self.run()
-        ins, outs = _io(launch)
-        for name in ins:
-            v = self.read(name)
-            if name in self.cur:
-                assert torch.equal(v.view(torch.int32), self.cur[name].view(torch.int32)), f"launch {k} {launch}: {name} differs from what the earlier stop saw"
-            self.cur[name] = v
-        for name in outs:
-            self.cur[name] = self.read(name)
-        return self.cur
-
-
-def _partials(tag, y, st):
-    """The normalised tensor the stored partials imply against the float64 GroupNorm of the stored output (32 groups of 6 channels, eps 1e-5)."""
-    got = R.norm_from_partials(y, st)
-    return check_f32(f"{tag}: GroupNorm from the stored partials", got, R.group_norm(y, 32, None, None, 1e-5, F64), R.group_norm(y, 32, None, None, 1e-5, F32))
-
-
-def _split(tag, packed):
-    val, h, lo = R.decode_split(packed)
-    bad, ties = R.split_is_consistent(h, lo)
-    print(f"{tag}: {bad} of {h.numel()} packed pairs inconsistent ({ties} with a remainder of exactly half a step)")
-    assert bad == 0, f"{tag}: the low plane of {bad} elements is no rounded remainder of the stored high plane"
-    return val
-
-
-def _check_launch(tag, sd, null, la, c, Be, Bc, rec):
-    """One launch on its own stored inputs.  c: buffer name -> tensor as stored; Bc > 0: the guided step's sample layout (unconditional half first)."""
-    k = la[0]
-    shared = bool(la[-1]) if k in ("conv1", "conv2", "qkv", "attn", "chain") else False
-    ns = Bc if shared else Be                     # samples this launch computes
-    f = lambda name, fn, got: rec.append((name,) + check_f32(f"{tag} {name}", got, fn(F64), fn(F32)))
-    if k == "conv_in":
-        x = c["x"][:Bc] if Bc else c["x"]
-        f("conv_in", lambda dt: R.conv_in(sd, x, dt), c["H0"][:x.shape[0]])
-        if Bc:
-            check_exact(f"{tag} conv_in: the second copy", c["H0"][Bc:], c["H0"][:Bc])
-            assert torch.equal(c["stH0"][Bc:], c["stH0"][:Bc])
-        rec.append(("stH0",) + _partials(f"{tag} conv_in", c["H0"], c["stH0"]))
-    elif k == "conv1":
-        _, i, in0, in1, _ = la
-        xs = [c[s][:ns] for s in (in0, in1) if s]
-        e_row = c["EO"][i][:, :1].t().expand(ns, -1) if Bc else c["EO"][i][:, :ns].t()
-        f(f"res{i} conv 1 ({len(xs)} segment{'s' if len(xs) > 1 else ''})", lambda dt: R.res_conv1(sd, i, xs, e_row, dt), c["M"][:ns])
-        rec.append(("stM",) + _partials(f"{tag} res{i} conv 1", c["M"][:ns], c["stM"][:ns]))
-    elif k == "conv2":
-        _, i, in0, in1, out, _ = la
-        xs = [c[s][:ns] for s in (in0, in1) if s]
-        f(f"res{i} conv 2 ({'1x1 skip segments' if in1 else 'residual'})", lambda dt: R.res_conv2(sd, i, c["M"][:ns], xs, dt)[0], c[out][:ns])
-        rec.append(("st" + out,) + _partials(f"{tag} res{i} conv 2", c[out][:ns], c["st" + out][:ns]))
-        if shared:
-            check_exact(f"{tag} res{i} conv 2: the duplicate store y2", c[out][Bc:], c[out][:Bc])
-    elif k == "qkv":
-        _, j, inn, _ = la
-        x = c[inn][:ns]
-        kd, vd = _split(f"{tag} st{j} k", c["QK"][:ns, 6:]), _split(f"{tag} st{j} v", c["VT"][:ns])
-        c["k_dec"], c["v_dec"] = kd, vd
-        for n, idx, got in (("q", 0, c["QK"][:ns, :6]), ("k", 1, kd), ("v", 2, vd)):
-            f(f"st{j} q/k/v: {n}", lambda dt: R.qkv(sd, j, x, dt)[idx], got)
-        for n, idx in (("a", 0), ("b", 1)):
-            f(f"st{j} gn_coef {n}", lambda dt: R.gn_coef(sd, j, x, dt)[..., idx], c["gn_coef"][:ns, :, idx])
-    elif k == "attn":
-        _, j, _ = la
-        f(f"st{j} self-attention", lambda dt: R.self_attention(c["QK"][:ns, :6], c["k_dec"][:ns], c["v_dec"][:ns], dt), c["O"][:ns])
-    elif k == "chain":
-        _, j, inn, out, _ = la
-        kv = c["KV"][:, j * 2 * MC:(j + 1) * 2 * MC].clone()
-        kv[:Bc] = 0   # (the unconditional half's rows are never written, and never read)
-        f(f"st{j} chain", lambda dt: R.chain(sd, j, c["O"][:ns], c[inn][:ns], c["gn_coef"][:ns], kv[:, :MC], kv[:, MC:], dt, nsamp=Be, in_mod=Bc if shared else 0,
-                                            n_uncond=Bc, null=null), c[out])
-        rec.append(("st" + out,) + _partials(f"{tag} st{j} chain", c[out], c["st" + out]))
-    elif k == "out":
-        f("out convolution", lambda dt: R.out_conv(sd, c["P"], dt), c["eps"])
-    else:
-        raise KeyError(k)
-
-
-def _kv_checks(tag, sd, s, ctx, b0, rec):
-    """KV of samples [b0, Be) against the float64 projection of their context; KVT its exact transpose."""
-    kv, kvt = s.read("KV"), s.read("KVT")
-    rec.append(("KV",) + check_f32(f"{tag} KV", kv[b0:], R.kv_all(sd, ctx, F64), R.kv_all(sd, ctx, F32)))
-    check_exact(f"{tag} KVT (key-major copy)", kvt[b0:], kv[b0:].transpose(1, 2))
-
-
-def _summary(tag, rec):
-    print(f"{tag}: {len(rec)} comparisons, largest e {max(e for _, e, _ in rec):.2e}, largest e / bound {max(e / b for _, e, b in rec):.3f}")
 
 
 # ---------------------------------------------------------------- forward shapes
@@ -326,42 +128,6 @@ def _forward_case(model, sd, dev, tag, B, T, seed, stages):
     print(f"{tag}: stage log {log}")
     assert stages is None or log == stages, f"{tag}: the launches are not the ones this shape is here for"
     _summary(tag, rec)
-
-
-def _poison(model, dev, B, T, seed, opts=None):
-    """Forward pass and one guided step (eta = 1 noise, initial latents, edit noise and a mask across the tile boundary at 64: everything out_sched_kernel<CFG> reads)
-    with the workspace filled with 0x00, 0xFF (NaN) and 0x7F (3.4e38) first: finite and bit-identical.  opts: said_debug_option settings, restored afterwards."""
-    x = synth.synth_latents(seed, (B, T, 32)).to(dev)
-    ctx = synth.synth_latents(seed + 1, (B, T, 768)).to(dev)
-    ts = (torch.arange(B) * 137 + 500) % 1000
-    sch = model.noise_scheduler
-    sch.set_timesteps(50)
-    tsl = sch.timesteps.numpy()
-    coef = sch.coef_table(tsl[24:26], 1.0)[:1]   # (the blend's pair is the next timestep's)
-    mask = torch.zeros(B, T, 32)
-    mask[:, 60:68] = 1
-    mask[:, :, :5] = 1
-    kw = dict(step_noise=synth.synth_latents(seed + 2, (1, B, T, 32)).to(dev), init_latents=synth.synth_latents(seed + 3, (B, T, 32)).abs().clamp(0, 1).to(dev),
-              edit_noise=synth.synth_latents(seed + 4, (B, T, 32)).to(dev), mask=mask.to(dev))
-    eng = model._get_engine(2 * B, max(T, 64))
-    ref = None
-    try:
-        for k, v in (opts or {}).items():
-            eng.debug_option(k, v)
-        for fill in (0x00, 0xFF, 0x7F):
-            eng.ws_fill(fill)
-            o1 = eng.unet_forward(x, ts, ctx).cpu()
-            eng.ws_fill(fill)
-            o2 = eng.denoise_loop(latents=x, context=ctx, timesteps=tsl[24:25], coef=coef, prediction_type="epsilon", guidance_scale=GS, guidance_rescale=0.0,
-                                  latent_scale=1.0, **kw)[1].cpu()
-            assert torch.isfinite(o1).all() and torch.isfinite(o2).all(), f"fill 0x{fill:02X}: a result is not finite"
-            if ref is None:
-                ref = (o1, o2)
-            assert torch.equal(o1, ref[0]) and torch.equal(o2, ref[1]), f"fill 0x{fill:02X}: a result depends on memory nobody wrote"
-    finally:
-        for k in (opts or {}):
-            eng.debug_option(k, -1)
-    return eng
 
 
 #        tag   B  T    conv_in NB, 192-wide NB, concatenated NB, q/k/v NB, attention KS
@@ -473,87 +239,6 @@ def test_guided_step_launches_on_their_own_inputs(plain, dev, case):
 
 
 # ---------------------------------------------------------------- shape F: the large-batch route (prep_kernel + fgemm_kernel) at toy size
-def _schedule_f():
-    L = [("conv_in",)]
-
-    def res(i, in0, in1, out):
-        cin = 2 * MC if in1 else MC
-        for off, src in enumerate(s for s in (in0, in1) if s):
-            L.append(("prep0", i, src, off * MC, cin, bool(in1)))
-        L.append(("fconv1", i, cin))
-        L.append(("prep0", i, "M", 0, MC, False))
-        L.append(("fconv2", i, in0, in1, out))
-
-    def st(j, inn, out):
-        L.extend([("prep1", j, inn), ("fqkv", j), ("attn", j, False), ("chain", j, inn, out, False)])
-
-    res(0, "H0", None, "P"); st(0, "P", "H1")
-    res(1, "H1", None, "P"); st(1, "P", "Q")
-    res(2, "Q", None, "P")
-    res(3, "P", "H1", "Q"); st(2, "Q", "P")
-    res(4, "P", "H0", "Q"); st(3, "Q", "P")
-    L.append(("out",))
-    return L
-
-
-def _packed_operand(tag, buf, T, row_off):
-    """A packed operand buffer (B, rows, columns): the T token rows decoded, the Conv1d padding rows (row_off = 1: rows 0 and T + 1) all-zero bits."""
-    if row_off:
-        assert int(buf[:, 0].view(torch.int32).abs().sum()) == 0 and int(buf[:, T + 1].view(torch.int32).abs().sum()) == 0, f"{tag}: a padding row is not zero"
-    return _split(tag, buf[:, row_off:row_off + T])
-
-
-def _check_launch_f(tag, sd, la, c, B, T, rec):
-    k = la[0]
-    f = lambda name, fn, got: rec.append((name,) + check_f32(f"{tag} {name}", got, fn(F64), fn(F32)))
-    if k == "prep0":
-        _, i, src, off, cin, raw = la
-        op_ = _packed_operand(f"{tag} res{i} uPA columns [{off}, {off + MC})", c[f"uPA:{cin}"][:, :, off:off + MC], T, 1)
-        if src == "M":
-            f(f"res{i} prep_kernel, conv 2's operand", lambda dt: R.res_operand2(sd, i, c["M"], dt).transpose(1, 2), op_)
-        else:
-            c.setdefault(("srcs", i), []).append(c[src])
-            if off == 0 and raw:
-                return   # (GroupNorm spans both sources: checked behind the second preparation launch)
-            xs = c.pop(("srcs", i))
-            full = _packed_operand(f"{tag} res{i} uPA", c[f"uPA:{cin}"], T, 1)
-            f(f"res{i} prep_kernel, conv 1's operand ({len(xs)} source{'s' if len(xs) > 1 else ''})", lambda dt: R.res_operand1(sd, i, xs, dt).transpose(1, 2), full)
-            if raw:   # the raw copy: the same values, packed (h + 2^-11 l holds 22 significand bits)
-                rawv = _packed_operand(f"{tag} res{i} uPB", c[f"uPB:{2 * MC}"], T, 0)
-                want = torch.cat(xs, dim=1).transpose(1, 2).double()
-                assert bool(((rawv - want).abs() <= 2.0 ** -21 * want.abs() + 2.0 ** -36).all()), f"{tag} res{i}: the raw copy for the 1x1 skip is not the input"
-    elif k == "fconv1":
-        _, i, cin = la
-        op_ = _packed_operand(f"{tag} res{i} uPA", c[f"uPA:{cin}"], T, 1).transpose(1, 2)
-        f(f"res{i} conv 1 on fgemm_kernel ({cin // MC} source{'s' if cin > MC else ''})", lambda dt: R.res_conv1(sd, i, None, c["EO"][i][:, :B].t(), dt, operand=op_), c["M"])
-        rec.append(("stM",) + _partials(f"{tag} res{i} conv 1", c["M"], c["stM"]))
-    elif k == "fconv2":
-        _, i, in0, in1, out = la
-        op_ = _packed_operand(f"{tag} res{i} uPA", c[f"uPA:{MC}"], T, 1).transpose(1, 2)
-        if in1:
-            rawv = _packed_operand(f"{tag} res{i} uPB", c[f"uPB:{2 * MC}"], T, 0).transpose(1, 2)
-            xs = [rawv[:, :MC], rawv[:, MC:]]
-        else:
-            xs = [c[in0]]
-        f(f"res{i} conv 2 on fgemm_kernel ({'1x1 skip segment' if in1 else 'residual'})", lambda dt: R.res_conv2(sd, i, None, xs, dt, operand=op_)[0], c[out])
-        rec.append(("st" + out,) + _partials(f"{tag} res{i} conv 2", c[out], c["st" + out]))
-    elif k == "prep1":
-        _, j, inn = la
-        op_ = _packed_operand(f"{tag} st{j} uPL", c[f"uPL:{MC}"], T, 0)
-        f(f"st{j} prep_kernel, q/k/v's operand", lambda dt: R.qkv_operand(sd, j, c[inn], dt), op_)
-        for n, idx in (("a", 0), ("b", 1)):
-            f(f"st{j} gn_coef {n}", lambda dt: R.gn_coef(sd, j, c[inn], dt)[..., idx], c["gn_coef"][:, :, idx])
-    elif k == "fqkv":
-        _, j = la
-        op_ = _packed_operand(f"{tag} st{j} uPL", c[f"uPL:{MC}"], T, 0)
-        kd, vd = _split(f"{tag} st{j} k", c["QK"][:, 6:]), _split(f"{tag} st{j} v", c["VT"])
-        c["k_dec"], c["v_dec"] = kd, vd
-        for n, idx, got in (("q", 0, c["QK"][:, :6]), ("k", 1, kd), ("v", 2, vd)):
-            f(f"st{j} q/k/v on fgemm_kernel: {n}", lambda dt: R.qkv(sd, j, None, dt, operand=op_)[idx], got)
-    else:
-        _check_launch(tag, sd, None, la, c, B, 0, rec)
-
-
 def test_large_batch_route_at_toy_size(plain, dev):
     """Shape F: prep_kernel in pack mode and fgemm_kernel<SP, PK> on their own stored inputs, then attention and the chain behind them."""
     model, sd, _ = plain

@@ -92,9 +92,9 @@ def test_presplit_term_is_the_plan_s(planner):
     assert n > 50
 
 
-def _plan(planner, batch, T):
-    """{case: "kernel/NB/KS/tt body"} at one batch and frame count, fp32 mode's default switches."""
-    return dict(ln.split(" ", 1) for ln in planner("plan", str(batch), str(T)).splitlines())
+def _plan(planner, batch, T, split=True):
+    """{case: "kernel/NB/KS/tt body"} at one batch and frame count, fp32 mode's default switches (split = False: ugemm_split off, what strict fp32 plans with)."""
+    return dict(ln.split(" ", 1) for ln in planner("plan", str(batch), str(T), *([] if split else ["0"])).splitlines())
 
 
 def test_shapes_of_the_fp32_kernel_test_reach_what_they_are_named_for(planner):
@@ -127,6 +127,67 @@ def test_shapes_of_the_fp32_kernel_test_reach_what_they_are_named_for(planner):
     slices = lambda B, T: 3 if B * ((T + 31) // 32) <= c3 else (2 if B * ((T + 31) // 32) <= c2 else 1)
     assert {t: slices(*K.SHAPES[t][:2]) for t in K.SHAPES} == {"S": 3, "M1": 3, "M2": 3, "L": 2}
     assert slices(2, 70) == 3 and slices(3, 70) == 3   # G (both halves), F
+
+
+def test_shapes_of_the_strict_fp32_kernel_test_reach_what_they_are_named_for(planner):
+    """tests/test_gpu_unet_f32_strict_kernels.py's twin of the test above: with ugemm_split off (strict fp32's plan switches) every ugemm_kernel launch of S*, M1*,
+    M2* and L* lands on an fp32-MFMA row — none on a split-fp16 row or on kconv_body — at the NB the GPU test expects in the stage log; and the two band shapes are
+    what set_band's rule, restated in Python, says they are."""
+    import test_gpu_unet_f32_strict_kernels as K
+    import unet_f32_stops as H
+    names = ("in_layers", "out_layers", "in_layers_cat", "out_layers_skip", "qkv", "to_out1", "q2_band", "to_out2", "geglu", "proj_out", "out_conv")
+    F = lambda nb, tt=1: f"f32/{nb}/8/{tt} block"
+    want = {   # in the order of `names`
+        "S*": (F(1), F(1), F(1), F(1), F(1), F(1), F(1), F(1), F(1), F(1), F(1)),
+        "M1*": (F(1), F(1), F(1), F(1), F(3), F(1), F(1), F(1), F(2), F(1), F(1)),                 # q/k/v NB = 3
+        "M2*": (F(2), F(2), F(2), F(2), F(2), F(1), F(1), F(2), F(4), F(2), F(1)),                 # NB = 2 throughout
+        "L*": (F(3), F(3), F(2), F(2), F(3, 2), F(1, 2), F(1), F(3), F(4), F(3), F(1)),            # NB = 3; q/k/v (and to_out1) two token tiles per workgroup
+    }
+    for tag, (B, T, nb_in, nb, nb_cat, nb_qkv, _, nb_out2, nb_geglu) in K.SHAPES.items():
+        p = _plan(planner, B, T, split=False)
+        assert tuple(p[n] for n in names) == want[tag], (tag, p)
+        assert p["conv_in"] == f"cgemm/{nb_in}/8/1 block", (tag, p["conv_in"])   # (sample aliasing keeps the forward pass's conv_in on the generic kernel in every mode)
+        assert all(v.split("/")[0] in ("f32", "cgemm") and v.endswith("block") for v in p.values()), (tag, p)   # nothing on `sp`, nothing on kconv_body
+        assert [int(p[n].split("/")[1]) for n in ("in_layers", "in_layers_cat", "qkv", "to_out2", "geglu", "proj_out")] == [nb, nb_cat, nb_qkv, nb_out2, nb_geglu, nb], tag
+    # L*: q/k/v is multi-tile, and does NOT pre-split: run_transformer's presplit term needs split products (sp_on(attn_split)), which strict fp32 switches off —
+    # the GPU test sees plain k and v and attn_kernel with KS 4 in the log (attn2q_kernel, KS 34, needs pre-split operands)
+    assert int(_plan(planner, 7, 417, split=False)["qkv"].split("/")[3].split()[0]) > 1
+    with open(os.path.join(CSRC, "unet_sched.cpp")) as f:
+        sched = f.read()
+    assert re.search(r"presplit = !c->bf16_mode && sp_on\(c, c->attn_split\) && c->attn_presplit != 0 && key_split", sched)
+    assert re.search(r"if \(presplit && ks_run == 4 && a\.o_mode == 0 && .*\) ks_run = 34;", sched)
+    with open(os.path.join(CSRC, "engine_internal.h")) as f:
+        assert "inline bool sp_on(const said_ctx* c, int opt) { return opt != 0 && !strict_f32(c); }" in f.read()
+    # G*: the shared first block on the clip alone (to_out1 with the duplicate store), F*: what stays channel-major at 3 x 70
+    p1, p3 = _plan(planner, 1, 70, split=False), _plan(planner, 3, 70, split=False)
+    assert (p1["in_layers"], p1["out_layers_dup"], p1["qkv"], p1["to_out1_dup"], p1["q2_band"], p1["to_out2"]) == (F(1),) * 6
+    assert (p3["to_out1"], p3["q2_band"], p3["to_out2"], p3["out_conv"]) == (F(1),) * 4
+    # W, N in the default mode: the tail's GEMMs on split-fp16 operands, but for GEGLU (no one-tile split-fp16 shape) and the plain to_q projection (the generic kernel)
+    for T in (10, 37):
+        p = _plan(planner, 2, T)
+        assert (p["to_out1"], p["q2_band"], p["to_out2"], p["proj_out"]) == ("sp/1/8/1 block",) * 4 and p["geglu"] == F(1) and p["q2_plain"] == "cgemm/1/8/1 block", p
+        ps = _plan(planner, 2, T, split=False)
+        assert (ps["to_out1"], ps["q2_band"], ps["to_out2"], ps["geglu"], ps["proj_out"]) == (F(1),) * 5 and ps["q2_plain"] == "cgemm/1/8/1 block", ps
+    # the band shapes by set_band's rule: wmax, and max(hi) - lo[t0] <= CHAIN_KW per 32-token tile
+    with open(os.path.join(CSRC, "stchain.h")) as f:
+        kw = int(re.search(r"constexpr int CHAIN_KW = (\d+);", f.read()).group(1))
+    assert kw == K.CHAIN_KW == 56
+    assert re.search(r"ok = hmax - lo\[t0\] <= CHAIN_KW;", sched) and re.search(r"bool ok = wmax <= 8;", sched)
+    for (T, S), wmax in zip(K.W_SHAPES, (12, 13)):
+        assert H.band_facts(T, S, kw) == (wmax, False) and wmax > 8, (T, S, H.band_facts(T, S, kw))
+    T, S = K.N_SHAPE
+    wmax, ok = H.band_facts(T, S, kw)
+    lo, hi = H.band_tables(T, S)
+    assert (T, S) == (10, 57) and wmax == 8 and not ok
+    assert all(lo[i] >= lo[i - 1] for i in range(1, T)) and max(hi) - lo[0] == 57 > kw, "N fails the tile rule, not the ordering or the width"
+    assert H.band_facts(T, S - 1, kw)[1] and all(H.band_facts(t, S, kw)[0] > 8 for t in range(1, T)), "one key fewer fits; fewer tokens widen the windows past 8"
+    assert H.band_facts(70, 70, kw) == (3, True) and H.band_facts(33, 33, kw) == (3, True)   # S*, Q: the fused tail's band
+    # Q: 2064 (sample, head, tile) triples, and more tiles than a sliced fused tail may have
+    B, T = K.Q_SHAPE
+    c2 = int(re.search(r"constexpr int CHAIN2_MAX_TILES = (\d+);", open(os.path.join(CSRC, "stchain.h")).read()).group(1))
+    assert B * ((T + 31) // 32) > c2 and B * ((T + 31) // 32) * 6 >= 2048
+    pq = _plan(planner, B, T)
+    assert (pq["conv_in"], pq["in_layers"], pq["out_layers"], pq["qkv"]) == ("cgemm/2/8/1 block", F(2, 2), F(2, 2), F(3, 2))
 
 
 def _calls(src, name):

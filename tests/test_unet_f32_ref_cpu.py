@@ -5,6 +5,9 @@
   bound of 1e-9 of range is three orders below any fp32 bound the GPU test applies.
 * Teeth: every mutant of unet_f32_ref.MUTANTS, applied to the reference of the launch it belongs to and compared with the unmutated float64 reference of the same
   stored inputs, must exceed that launch's bound 4 max(e32, 1e-6) (tests/test_gpu_unet_f32_kernels.py's rule) at least ten times.  The ratios are printed.
+  The six mutants of the seams between the five launches of the unfused tail (and band_shifted / geglu_swapped again) are applied at the launch's own output, on
+  CPU-made stored inputs at the shapes tests/test_gpu_unet_f32_strict_kernels.py runs: the guided step's second block at 1 clip x 70 (x_off = kv_off = 1) and the
+  wide-band shapes W; to_out1's two forms (merged partials, coefficient rows) are shown to agree.
 """
 from unittest import mock
 
@@ -131,16 +134,69 @@ def _mutant_cases(sd_u, null, inputs, tr):
         "y2_not_written": ("res0.conv2, duplicate store", lambda dt: R.res_conv2(sd_u, 0, M, [H0], dt)[1]),
         "last_key_tile_missing": ("st0.attn", lambda dt: R.self_attention(q, k, v, dt)),
         "band_shifted": chain, "geglu_swapped": chain, "uncond_runs_cross_attention": guided, "mask_blend_order": upd,
-    }
+    }   # (the mutants of the five-launch tail's seams: _tail_mutant_cases)
+
+
+def _tail_inputs(sd_u, T, S, seed):
+    """CPU-made stored inputs of block 0's five-launch tail at 2 x (T, S): (o, xin, k2, v2) in fp32, from the launches chained in float64."""
+    x = synth.synth_latents(seed, (2, T, 32))
+    c = synth.synth_latents(seed + 1, (2, S, 768))
+    tr = []
+    R.forward(sd_u, x.transpose(1, 2), (torch.arange(2) * 137 + 500) % 1000, c, F64, trace=tr)
+    tr = dict(tr)
+    kv = R.kv_all(sd_u, c, F64).float()
+    return _stored(tr["st0.attn"]), _stored(tr["res0.conv2"]), kv[:, :R.MC], kv[:, R.MC:2 * R.MC]
+
+
+# the band shapes of tests/test_gpu_unet_f32_strict_kernels.py: W (windows wider than 8 keys), N (narrow windows the fused tail's window tile cannot hold)
+W_SHAPES = ((10, 100), (37, 400))
+
+
+def _tail_mutant_cases(sd_u, null, inputs, tr):
+    """[(mutant, launch name, fn(dtype))] for the seams between the five launches of the unfused tail, each at the launch's own output: shape S, the guided step's
+    second block at 1 clip x 70 (sample 0 unconditional, sample 1 conditional: x_off = kv_off = 1), and the wide-band shapes W."""
+    _, ts, c = inputs
+    Pm, O1 = _stored(tr["res1.conv2"]), _stored(tr["st1.attn"])
+    st = R.partials_of(Pm)
+    kv = R.kv_all(sd_u, c, F64).float()
+    kb, vb = kv[:, 2 * R.MC:3 * R.MC], kv[:, 3 * R.MC:4 * R.MC]
+    x1, y2 = (t.float() for t in R.to_out1(sd_u, 1, O1, Pm, st, F64, null=null))
+    o2 = R.q_band(sd_u, 1, x1[1:], kb[1:], vb[1:], T, T, F64).float()
+    O = torch.cat([O1[:1], o2])   # (the band overwrites the attention output's slots in place)
+    x2 = R.to_out2(sd_u, 1, O[1:], x1, F64, x_off=1, kv_off=1, x2=y2).float()
+    h = R.geglu(sd_u, 1, x2, F64).float()
+    out = [
+        ("y2_without_c2", "st1 to_out1, y2 (guided)", lambda dt: R.to_out1(sd_u, 1, O1, Pm, st, dt, null=null)[1]),
+        ("x1_of_wrong_sample_under_x_off", "st1 to_out2 (guided)", lambda dt: R.to_out2(sd_u, 1, O[1:], x1, dt, x_off=1, kv_off=1, x2=y2)),
+        ("to_out2_writes_uncond_slot", "st1 to_out2 (guided)", lambda dt: R.to_out2(sd_u, 1, O[1:], x1, dt, x_off=1, kv_off=1, x2=y2)),
+        ("geglu_swapped", "st1 geglu", lambda dt: R.geglu(sd_u, 1, x2, dt)),
+        ("ffproj_second_segment_dropped", "st1 ffproj", lambda dt: R.ffproj(sd_u, 1, h, x2, Pm, dt)),
+        ("band_shifted", "st1 q_band", lambda dt: R.q_band(sd_u, 1, x1, kb, vb, T, T, dt)),
+    ]
+    for Tw, Sw in W_SHAPES:
+        o, xin, k2, v2 = _tail_inputs(sd_u, Tw, Sw, 330 + Tw)
+        xw = R.to_out1(sd_u, 0, o, xin, R.partials_of(xin), F64)[0].float()
+        qw = R.q2(sd_u, 0, xw, F64).float()
+        out.append(("band_truncated_to_8_keys", f"st0 q_band, W {Tw} x {Sw}", lambda dt, a=(xw, k2, v2, Tw, Sw): R.q_band(sd_u, 0, *a, dt)))
+        out.append(("wide_band_off_by_one", f"st0 band_wide, W {Tw} x {Sw}", lambda dt, a=(qw, k2, v2, Tw, Sw): R.band(*a, dt)))
+    return out
+
+
+def test_partials_made_on_the_cpu_give_the_coefficient_rows(sd_null, trace):
+    """to_out1's two forms agree: the (a, b) rows from merged partials (the RES_GN epilogue) are gn_coef's rows from the values (what fgemm_kernel reads)."""
+    sd_u, _ = sd_null
+    P = _stored(trace[1]["res0.conv2"])
+    e = rel_max(R.coef_from_partials(sd_u, 0, R.partials_of(P), T, F64), R.gn_coef(sd_u, 0, P, F64))
+    print(f"GroupNorm rows from CPU-made partials vs from the values: {e:.2e}")
+    assert e <= 1e-6   # (the partials are stored in fp32)
 
 
 def test_every_mutant_exceeds_its_launch_bound_tenfold(sd_null, inputs, trace):
     sd_u, null = sd_null
-    cases = _mutant_cases(sd_u, null, inputs, trace[1])
-    assert set(cases) == set(R.MUTANTS)
+    cases = [(n, *v) for n, v in _mutant_cases(sd_u, null, inputs, trace[1]).items()] + _tail_mutant_cases(sd_u, null, inputs, trace[1])
+    assert {n for n, _, _ in cases} == set(R.MUTANTS)
     worst = np.inf
-    for name in R.MUTANTS:
-        launch, fn = cases[name]
+    for name, launch, fn in cases:
         assert R.MUTANT is None
         ref64, ref32 = fn(F64), fn(F32)
         e32, bound = f32_bound(ref32, ref64)
@@ -150,7 +206,7 @@ def test_every_mutant_exceeds_its_launch_bound_tenfold(sd_null, inputs, trace):
         finally:
             R.MUTANT = None
         e = rel_max(mut, ref64)
-        print(f"mutant {name:30s} on {launch:28s}: {e:.2e} of max |ref|, bound {bound:.2e} (fp32 CPU evaluation {e32:.2e}): ratio {e / bound:.3g}")
+        print(f"mutant {name:32s} on {launch:30s}: {e:.2e} of max |ref|, bound {bound:.2e} (fp32 CPU evaluation {e32:.2e}): ratio {e / bound:.3g}")
         worst = min(worst, e / bound)
         assert e >= 10 * bound, f"{name}: only {e / bound:.2f} x the bound of {launch}"
     print(f"smallest ratio {worst:.3g}")

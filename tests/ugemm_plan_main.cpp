@@ -4,8 +4,9 @@
 //   (no arguments)  -> one line per (case, T, distinct result): `case T=<T> <switch codes> : b<first batch>=<plan> ...`, a plan printed where it changes along the scan.
 //                      switch code: f|b (fp32 | bf16 mode), ugemm_split, kconv, concurrent, clk.  plan: kernel/NB/KS/tt, for q/k/v also /p<run_transformer's old presplit term>
 //   rows            -> checks that every split-fp16 and multi-tile row of the table is also a base row; prints the row counts
-//   plan <batch> <T> -> one line per case at that batch and frame count with fp32 mode's default switches (ugemm_split on, kconv -1, no clip groups, no clocks):
-//                      `case kernel/NB/KS/tt body`, body = kconv for launches that run kconv_body, else block
+//   plan <batch> <T> [<split>] -> one line per case at that batch and frame count with fp32 mode's default switches (ugemm_split on, kconv -1, no clip groups, no
+//                      clocks), or with ugemm_split as given (0: what strict fp32 plans with): `case kernel/NB/KS/tt body`, body = kconv for launches that run
+//                      kconv_body, else block
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -202,7 +203,7 @@ int main(int argc, char** argv) {
 #ifdef SAID_UGEMM_ROWS
     if (argc > 3 && !strcmp(argv[1], "plan")) {
         const int batch = atoi(argv[2]), T = atoi(argv[3]);
-        const PlanSwitches sw = {false, true, -1, false, false};
+        const PlanSwitches sw = {false, argc > 4 ? atoi(argv[4]) != 0 : true, -1, false, false};
         for (const Case& cs : CASES) {
             const GemmArgs a = cs.make(T, batch);
             const GemmPlan p = plan_gemm(sw, a, cs.epi, batch, cs.nb((long long)batch * ((T + 31) / 32)), 8);

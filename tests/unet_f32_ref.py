@@ -1,6 +1,7 @@
 """Launch-by-launch restatement of the channel-major fp32 denoise step (said_amd/csrc/unet_sched.cpp: run_unet / run_resblock / run_transformer) — TEST INFRASTRUCTURE.
 
-One function per launch of the default (fp32, split-fp16) schedule.  Each takes the launch's inputs AS THE ENGINE STORES THEM (channel-major (B, C, T) without the pad
+One function per launch of the default (fp32, split-fp16) schedule, and one per launch of the five-launch tail behind a block's self-attention (to_out1, q_band,
+to_out2, geglu, ffproj: strict fp32, and the default mode where the fused tail's window tile cannot hold the band); chain() is their composition.  Each takes the launch's inputs AS THE ENGINE STORES THEM (channel-major (B, C, T) without the pad
 tokens [T, Tp); q / k token-major per head; k / v decoded from their packed split pairs) plus the UNet state dict (`model.*` keys) and `dtype`, and returns what the
 launch stores.  Operands are NOT rounded: split-fp16 represents an operand to 2^-22, so the float64 evaluation is the yardstick and the float32 one (torch CPU)
 measures how far a correct fp32 evaluation of the same inputs may sit from it (audio_bf16_ref.check_f32).  GroupNorm is evaluated from the stored values, not from
@@ -22,7 +23,10 @@ SCALE = HD ** -0.5
 
 MUTANTS = ("fp16_operands", "k_block_dropped", "tap_shifted", "pad_tap_nonzero", "residual_of_neighbour_sample", "gn_neighbour_group", "gn_over_tp",
            "emb_row_of_other_sample", "last_key_tile_missing", "band_shifted", "geglu_swapped", "uncond_runs_cross_attention", "y2_not_written",
-           "mask_blend_order")
+           "mask_blend_order",
+           # the seams between the five launches of the unfused tail
+           "x1_of_wrong_sample_under_x_off", "y2_without_c2", "to_out2_writes_uncond_slot", "band_truncated_to_8_keys", "wide_band_off_by_one",
+           "ffproj_second_segment_dropped")
 MUTANT = None
 
 
@@ -95,6 +99,13 @@ def merge_partials(st: torch.Tensor, T: int, cpg: int):
     gm_c = gm.repeat_interleave(cpg, dim=1).view(B, 1, C)
     m2 = (m2_pc + cnt * (mean_pc - gm_c) ** 2).view(B, npart, G, cpg).sum(dim=(1, 3))
     return gm, m2 / (cpg * T)
+
+
+def partials_of(y: torch.Tensor) -> torch.Tensor:
+    """What a producer stores beside y (B, C, T): per 32-token tile and channel (mean, M2) -> (B, np, C, 2) fp32 (CPU-made stand-in for the self-check)."""
+    T = y.shape[-1]
+    parts = [y[..., t0:min(T, t0 + 32)].double() for t0 in range(0, T, 32)]
+    return torch.stack([torch.stack([p.mean(-1), ((p - p.mean(-1, keepdim=True)) ** 2).sum(-1)], dim=-1) for p in parts], dim=1).float()
 
 
 def norm_from_partials(y: torch.Tensor, st: torch.Tensor, cpg: int = 6, eps: float = 1e-5) -> torch.Tensor:
@@ -263,39 +274,129 @@ def folded_proj_out(sd, j):
     return P @ sd[tb + ".ff.net.2.weight"].double(), P, P @ sd[tb + ".ff.net.2.bias"].double() + sd[p + ".proj_out.bias"].double()
 
 
-def chain(sd, j, o, xin, coef, k2, v2, dt, nsamp=None, in_mod=0, n_uncond=0, null=None):
-    """stchain_kernel's whole tail of SpatialTransformer j.  o, xin (n_in, 192, T): the self-attention output and the block input; coef (n_in, 192, 2): the
-    GroupNorm (a, b) rows as stored; k2, v2 (nsamp, 192, S): block j's rows of the stored KV (those of unconditional samples are never read).  Output sample s reads
-    input sample s % in_mod (in_mod > 0: the guidance-shared block), samples [0, n_uncond) are unconditional: x2 = x1 + c2 instead of the cross-attention.
-    -> the block's output (nsamp, 192, T)."""
-    tb = ST[j] + ".transformer_blocks.0"
-    W = lambda n: sd[tb + n]
-    n_in, _, T = o.shape
-    nsamp = n_in if nsamp is None else nsamp
-    idx = torch.arange(nsamp) % in_mod if in_mod else torch.arange(nsamp)
-    xin_t = xin.to(dt).transpose(1, 2)
-    g = xin_t * coef[..., 0].to(dt)[:, None] + coef[..., 1].to(dt)[:, None]
-    x1 = (_lin(o.to(dt).transpose(1, 2), W(".attn1.to_out.0.weight"), W(".attn1.to_out.0.bias"), dt) + g)[idx]          # (nsamp, T, 192)
-    # attn2: to_q(norm2(x1)), banded softmax over the stored K / V, to_out + x1
-    S = k2.shape[-1]
-    q = _lin(_ln(x1, W(".norm2.weight"), W(".norm2.bias"), dt), W(".attn2.to_q.weight"), None, dt).reshape(nsamp, T, HEADS, HD).permute(0, 2, 1, 3)
-    kh = k2.to(dt).reshape(nsamp, HEADS, HD, S)
-    vh = v2.to(dt).reshape(nsamp, HEADS, HD, S)
+def _tb(sd, j):
+    return lambda n: sd[ST[j] + ".transformer_blocks.0" + n]
+
+
+def coef_from_partials(sd, j, st, T, dt):
+    """The block input's GroupNorm (32 groups, eps 1e-6) as (a, b) rows from its producer's stored partials (n, np, 192, 2), merged as the RES_GN epilogue merges
+    them -> (n, 192, 2)."""
+    mean, var = merge_partials(st, T, MC // 32)
+    rstd = (1.0 / torch.sqrt(var + 1e-6)).repeat_interleave(MC // 32, dim=1)
+    a = sd[ST[j] + ".norm.weight"].double()[None] * rstd
+    b = sd[ST[j] + ".norm.bias"].double()[None] - mean.repeat_interleave(MC // 32, dim=1) * a
+    return torch.stack([a, b], dim=-1).to(dt)
+
+
+def to_out1(sd, j, o, xin, gn, dt, null=None):
+    """Launch 1 of the five-launch tail: x1 = attn1.to_out(o) + GroupNorm(xin).  o, xin (n, 192, T) channel-major as stored; gn: the (a, b) rows (n, 192, 2) that
+    fgemm_kernel reads (and stchain_kernel), or the producer's partials (n, np, 192, 2) that ugemm_kernel's RES_GN epilogue merges itself.
+    -> (x1, y2): y2 = x1 + c2, the duplicate the guided step stores into X2 for every sample of the launch (null given), else None."""
+    W = _tb(sd, j)
+    T = o.shape[-1]
+    coef = coef_from_partials(sd, j, gn, T, dt) if gn.dim() == 4 else gn.to(dt)
+    g = xin.to(dt) * coef[..., 0, None] + coef[..., 1, None]
+    x1 = _lin(o.to(dt).transpose(1, 2), W(".attn1.to_out.0.weight"), W(".attn1.to_out.0.bias"), dt).transpose(1, 2) + g
+    if null is None:
+        return x1, None
+    return x1, (x1.clone() if _m("y2_without_c2") else x1 + c2_const(sd, j, null, dt)[None, :, None])
+
+
+def q2(sd, j, x1, dt):
+    """attn2.to_q(norm2(x1)); x1 (n, 192, T) -> (n, 192, T) channel-major: what the plain projection in front of band_wide_kernel stores."""
+    W = _tb(sd, j)
+    return _lin(_ln(x1.to(dt).transpose(1, 2), W(".norm2.weight"), W(".norm2.bias"), dt), W(".attn2.to_q.weight"), None, dt).transpose(1, 2)
+
+
+def band_mask(T: int, S: int) -> torch.Tensor:
+    """alignment_mask(T, S) (True: masked) with the mutants of the band's seams."""
     mask = alignment_mask(T, S)
     if _m("band_shifted"):
         mask = mask.roll(1, 1)
-    s = (q @ kh * SCALE).masked_fill(mask[None, None], -torch.finfo(dt).max)
-    o2 = (torch.softmax(s, dim=-1) @ vh.transpose(2, 3)).permute(0, 2, 1, 3).reshape(nsamp, T, MC)
-    x2 = _lin(o2, W(".attn2.to_out.0.weight"), W(".attn2.to_out.0.bias"), dt) + x1
-    if n_uncond and not _m("uncond_runs_cross_attention"):
-        x2 = torch.cat([x1[:n_uncond] + c2_const(sd, j, null, dt), x2[n_uncond:]])
-    hv = _lin(_ln(x2, W(".norm3.weight"), W(".norm3.bias"), dt), W(".ff.net.0.proj.weight"), W(".ff.net.0.proj.bias"), dt)
+    width = (~mask).sum(1)
+    if int(width.max()) > 8:
+        lo = (~mask).int().argmax(1)
+        if _m("band_truncated_to_8_keys"):   # the fused epilogue's eight keys where the window is wider
+            mask = mask | (torch.arange(S)[None] >= (lo + 8)[:, None])
+        if _m("wide_band_off_by_one"):       # band_wide_kernel's window one key further: [lo + 1, hi + 1)
+            mask = mask.roll(1, 1)
+            mask[:, 0] = True
+    return mask
+
+
+def band(q, k2, v2, T, S, dt):
+    """The banded softmax over the stored K / V of the context: q (n, 192, T) channel-major, k2, v2 (n, 192, S) -> (n, 192, T).  band_wide_kernel in place, or
+    the second half of the EPI_BAND epilogue."""
+    n = q.shape[0]
+    qh = q.to(dt).reshape(n, HEADS, HD, T).transpose(2, 3)
+    kh = k2.to(dt).reshape(n, HEADS, HD, S)
+    vh = v2.to(dt).reshape(n, HEADS, HD, S)
+    s = (qh @ kh * SCALE).masked_fill(band_mask(T, S)[None, None], -torch.finfo(dt).max)
+    return (torch.softmax(s, dim=-1) @ vh.transpose(2, 3)).permute(0, 1, 3, 2).reshape(n, MC, T)
+
+
+def q_band(sd, j, x1, k2, v2, T, S, dt):
+    """Launch 2: to_q(norm2(x1)) and the banded softmax at any window width — the fused EPI_BAND epilogue, or the plain projection followed by band_wide_kernel."""
+    return band(q2(sd, j, x1, dt), k2, v2, T, S, dt)
+
+
+def to_out2(sd, j, o2, x1, dt, x_off=0, kv_off=0, x2=None):
+    """Launch 3: x2 = attn2.to_out(o2) + x1 for the n samples of o2 (the cross-attention range).  x1: the whole stored X1, read from sample x_off on; x2: the stored
+    X2 before the launch (the guided step: y2 of launch 1 in every slot) — then the result is that buffer with slots [kv_off, kv_off + n) alone replaced."""
+    W = _tb(sd, j)
+    n = o2.shape[0]
+    r = x1[0:n] if (_m("x1_of_wrong_sample_under_x_off") and x_off) else x1[x_off:x_off + n]
+    y = _lin(o2.to(dt).transpose(1, 2), W(".attn2.to_out.0.weight"), W(".attn2.to_out.0.bias"), dt).transpose(1, 2) + r.to(dt)
+    if x2 is None:
+        return y
+    out = x2.to(dt).clone()
+    out[kv_off:kv_off + n] = y
+    if _m("to_out2_writes_uncond_slot") and kv_off:
+        out[0:n] = y
+    return out
+
+
+def geglu_operand(sd, j, x2, dt):
+    """norm3(x2) token-major (n, T, 192): what the third preparation launch of the large-batch route stores for fgemm_kernel."""
+    W = _tb(sd, j)
+    return _ln(x2.to(dt).transpose(1, 2), W(".norm3.weight"), W(".norm3.bias"), dt)
+
+
+def geglu(sd, j, x2, dt, operand=None):
+    """Launch 4: ff.net.0 over norm3(x2), value x gelu(gate); x2 (n, 192, T) -> F (n, 768, T).  operand: the stored operand (geglu_operand) instead of x2."""
+    W = _tb(sd, j)
+    y = geglu_operand(sd, j, x2, dt) if operand is None else operand.to(dt)
+    hv = _lin(y, W(".ff.net.0.proj.weight"), W(".ff.net.0.proj.bias"), dt)
     a, gate = hv.chunk(2, dim=-1)
     if _m("geglu_swapped"):
         a, gate = gate, a
+    return (a * _gelu(gate)).transpose(1, 2)
+
+
+def ffproj(sd, j, h, x2, xin, dt):
+    """Launch 5: the folded proj_out over the K segments [h ; x2] (weights folded in float64, weights.cpp fold_ffproj) + bias + x_in; h (n, 768, T), x2, xin
+    (n, 192, T) -> the block's output (n, 192, T).  (Its GroupNorm partials are held to the stored output on their own: norm_from_partials.)"""
     PF, P, PB = folded_proj_out(sd, j)
-    y = _lin(a * _gelu(gate), PF, None, dt) + _lin(x2, P, None, dt) + PB.to(dt) + xin_t[idx]
-    return y.transpose(1, 2)
+    y = _lin(h.to(dt).transpose(1, 2), PF, None, dt)
+    if not _m("ffproj_second_segment_dropped"):
+        y = y + _lin(x2.to(dt).transpose(1, 2), P, None, dt)
+    return (y + PB.to(dt)).transpose(1, 2) + xin.to(dt)
+
+
+def chain(sd, j, o, xin, coef, k2, v2, dt, nsamp=None, in_mod=0, n_uncond=0, null=None):
+    """stchain_kernel's whole tail of SpatialTransformer j: the five launches composed.  o, xin (n_in, 192, T): the self-attention output and the block input; coef
+    (n_in, 192, 2): the GroupNorm (a, b) rows as stored; k2, v2 (nsamp, 192, S): block j's rows of the stored KV (those of unconditional samples are never read).
+    Output sample s reads input sample s % in_mod (in_mod > 0: the guidance-shared block), samples [0, n_uncond) are unconditional: x2 = x1 + c2 instead of the
+    cross-attention.  -> the block's output (nsamp, 192, T)."""
+    n_in, _, T = o.shape
+    nsamp = n_in if nsamp is None else nsamp
+    idx = torch.arange(nsamp) % in_mod if in_mod else torch.arange(nsamp)
+    x1, y2 = to_out1(sd, j, o, xin, coef, dt, null=null if n_uncond else None)
+    x1 = x1[idx]
+    x2 = to_out2(sd, j, q_band(sd, j, x1, k2, v2, T, k2.shape[-1], dt), x1, dt)
+    if n_uncond and not _m("uncond_runs_cross_attention"):
+        x2 = torch.cat([y2[idx][:n_uncond], x2[n_uncond:]])
+    return ffproj(sd, j, geglu(sd, j, x2, dt), x2, xin[idx], dt)
 
 
 def out_conv(sd, h, dt):
