@@ -157,6 +157,7 @@ ABI = {
         "said_debug_ws_fill": (c_int, [c_void_p, c_int]),
         "said_debug_ws_copy": (c_int, [c_void_p, c_int, c_void_p, _c_ll, c_void_p]),
         "said_debug_audio_copy": (c_int, [c_void_p, c_char_p, c_void_p, _c_ll, c_void_p]),
+        "said_debug_audio_fill": (c_int, [c_void_p, c_int]),
         "said_unet_algorithmic_bytes": (c_double, [c_int, c_int, c_int]),
         "said_unet_algorithmic_flops": (c_double, [c_int, c_int]),
         "said_vae_create": (c_int, [_c_void_pp, c_int, c_int, c_int, c_int]),
@@ -794,6 +795,10 @@ class Engine(_Context):
         out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._go("said_debug_audio_copy", name.encode(), _ptr(out), nbytes)
         return out
+
+    def audio_fill(self, byte_value: int) -> None:
+        """Every byte of every allocated audio-encoder buffer set to `byte_value` (said_debug_audio_fill); synchronises the device."""
+        self._call("said_debug_audio_fill", int(byte_value) & 0xFF)
 
     def loop_progress(self) -> int:
         """Denoise steps started so far by the loop running (or last run) on this context; never blocks the loop's stream."""

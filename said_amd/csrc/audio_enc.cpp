@@ -153,7 +153,8 @@ int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_fra
                 a.bias = ctx->posconv.bias; a.act = ACT_GELU;
                 a.y = ctx->aPOS; a.y_bstride = hs; a.y_pitch = Fp;
                 if (on()) {
-                    launch_gemm(a, EPI_STORE, nb, tt * 32 <= 2048 ? 1 : 2, 8, s);
+                    const LaunchCfg lc = audio_plan::posconv(tt);
+                    launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
                     launch_cm_to_tm(ctx->aPOS, ctx->bPosT, nb, Fr, W2V_H, Fp, hs, s);
                 }
             }
@@ -233,11 +234,15 @@ int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_fra
     }
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = std::min(chunk, B - b0);
+        // said_debug_option "audio_stop_after" (said_audio_encode and said_audio_extract_features; train mode ignores it): a stage is one launch call site
+        // below, numbered per pass in the order documented in said_hip_debug.h; on() is asked once per site, whether or not the site launches
+        int stage = 0;
+        auto on = [&]() { return tp || ctx->audio_stop_after < 0 || stage++ < ctx->audio_stop_after; };
         // ---- feature extractor ----
         int pitch = rup(L[0], 32);
         long long bs = (long long)W2V_CONV * pitch;
-        launch_conv0(wav_dev + (long long)b0 * Ta, ctx->c0_w, ctx->abufA, nb, Ta, W2V_CONV, ctx->w2v_kernel[0], ctx->w2v_stride[0], L[0], pitch, bs, s);
-        launch_rownorm_gelu(ctx->abufA, ctx->c0_g, ctx->c0_b, W2V_CONV, nb, L[0], pitch, bs, 1e-5f, s);
+        if (on()) launch_conv0(wav_dev + (long long)b0 * Ta, ctx->c0_w, ctx->abufA, nb, Ta, W2V_CONV, ctx->w2v_kernel[0], ctx->w2v_stride[0], L[0], pitch, bs, s);
+        if (on()) launch_rownorm_gelu(ctx->abufA, ctx->c0_g, ctx->c0_b, W2V_CONV, nb, L[0], pitch, bs, 1e-5f, s);
         float* src = ctx->abufA;
         float* dst = ctx->abufB;
         for (int i = 1; i < 7; ++i) {
@@ -248,23 +253,24 @@ int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_fra
             a.seg[0] = mkseg(src, bs, pitch, W2V_CONV, ctx->w2v_kernel[i], 0, ctx->w2v_stride[i], L[i - 1], XF_NONE, ctx->aconv[i].w[0]);
             a.act = ACT_GELU;
             a.y = dst; a.y_bstride = bo; a.y_pitch = po;
-            const LaunchCfg lc = pick_cfg((long long)nb * ((L[i] + 31) / 32), W2V_CONV / 32, false);
-            launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
+            const LaunchCfg lc = audio_plan::conv(audio_plan::token_tiles(nb, L[i]));
+            if (on()) launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
             std::swap(src, dst);
             pitch = po; bs = bo;
         }
         // ---- interpolation to the frame count (wav2vec2.py:41-44) ----
         const long long xs = (long long)W2V_CONV * Fp, hs = (long long)W2V_H * Fp;
         const float* feat = src; long long feat_bs = bs; int feat_pitch = pitch;
+        const bool interp_on = on();
         if (num_frames > 0) {
-            launch_interp_linear(src, ctx->aX, nb, W2V_CONV, L[6], Fr, pitch, Fp, bs, xs, s);
+            if (interp_on) launch_interp_linear(src, ctx->aX, nb, W2V_CONV, L[6], Fr, pitch, Fp, bs, xs, s);
             feat = ctx->aX; feat_bs = xs; feat_pitch = Fp;
         }
         if (features_only) {
-            launch_cm_to_tm(feat, out_dev + (long long)b0 * Fr * W2V_CONV, nb, Fr, W2V_CONV, feat_pitch, feat_bs, s);
+            if (on()) launch_cm_to_tm(feat, out_dev + (long long)b0 * Fr * W2V_CONV, nb, Fr, W2V_CONV, feat_pitch, feat_bs, s);
             continue;
         }
-        const long long tt = (long long)nb * ((Fr + 31) / 32);
+        const long long tt = audio_plan::token_tiles(nb, Fr);
         {   // feature_projection: LayerNorm(512) -> Linear(512, 768)
             GemmArgs a = mkargs(Fr, W2V_H);
             a.nseg = 1;
@@ -272,8 +278,8 @@ int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_fra
             a.seg[0].ln_gamma = ctx->fp_lng; a.seg[0].ln_beta = ctx->fp_lnb; a.seg[0].ln_eps = 1e-5f;
             a.bias = ctx->fproj.bias;
             a.y = ctx->aH; a.y_bstride = hs; a.y_pitch = Fp;
-            const LaunchCfg lc = pick_cfg(tt, W2V_H / 32);
-            launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
+            const LaunchCfg lc = audio_plan::hidden(tt);
+            if (on()) launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
         }
         // train mode: every mask is indexed from the call's first clip (b0 + the launch's clip), so the result does not depend on `chunk`
         const unsigned long long seed = tp ? tp->seed : 0;
@@ -291,10 +297,11 @@ int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_fra
             a.seg[0].c_group_stride = W2V_H / 16;
             a.bias = ctx->posconv.bias; a.act = ACT_GELU;
             a.y = ctx->aPOS; a.y_bstride = hs; a.y_pitch = Fp;
-            launch_gemm(a, EPI_STORE, nb, tt * 32 <= 2048 ? 1 : 2, 8, s);
+            const LaunchCfg lc = audio_plan::posconv(tt);
+            if (on()) launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
         }
         if (tp) launch_ln_drop_cm(ctx->aH, ctx->aPOS, ctx->aH, ctx->enc_lng, ctx->enc_lnb, nb, W2V_H, Fr, Fp, hs, 1e-5f, b0, none, site(AT_SITE_FRONT, tp->p_hidden, 2), s);
-        else launch_layernorm_cm(ctx->aH, ctx->aPOS, ctx->aH, ctx->enc_lng, ctx->enc_lnb, nb, W2V_H, Fr, Fp, hs, 1e-5f, s);
+        else if (on()) launch_layernorm_cm(ctx->aH, ctx->aPOS, ctx->aH, ctx->enc_lng, ctx->enc_lnb, nb, W2V_H, Fr, Fp, hs, 1e-5f, s);
         const int vt_rows = Fp;
         for (int l = 0; l < ctx->w2v_layers; ++l) {
             if (tp && (tp->skip_layers >> l & 1u)) continue;   // LayerDrop: the layer is the identity for the whole batch
@@ -307,8 +314,8 @@ int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_fra
                 a.tm_tiles = 2 * W2V_H / 32;
                 a.vt = ctx->aQK; a.vt_heads = 2 * W2V_HEADS; a.vt_dim = W2V_HD; a.vt_rows = vt_rows;
                 a.y = ctx->aVT - (long long)a.tm_tiles * 32 * Fp; a.y_bstride = hs; a.y_pitch = Fp;
-                const bool big = tt * 72 > 4096;
-                launch_gemm(a, EPI_QKV, nb, big ? 6 : 2, big ? 4 : 8, s);
+                const LaunchCfg lc = audio_plan::qkv(tt);
+                if (on()) launch_gemm(a, EPI_QKV, nb, lc.NB, lc.KS, s);
             }
             {
                 AttnArgs a;
@@ -317,10 +324,13 @@ int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_fra
                 a.pitch = Fp; a.T = Fr; a.heads = W2V_HEADS; a.rows = vt_rows; a.scale = 0.125f;
                 const int mode = sp_on(ctx, ctx->attn_split) ? 2 : 0;
                 const DropSite pd = site(at_site_layer(l, 0), tp ? tp->p_attention : 0.f, 4);
-                if (pd.p > 0.f)   // (training batches are small: the key split stays on, eight waves or four)
-                    launch_attn_drop(a, nb, tt * W2V_HEADS <= 2048 ? 8 : 4, s, mode, b0, pd);
-                else
-                    launch_attn(a, nb, W2V_HD, tt * W2V_HEADS <= 2048 ? 8 : (tt * W2V_HEADS <= 8192 ? 4 : 1), s, mode);
+                if (pd.p > 0.f) {   // (training batches are small: the key split stays on, eight waves or four)
+                    launch_attn_drop(a, nb, audio_plan::attn_slices(tt, true), s, mode, b0, pd);
+                } else if (on()) {
+                    const int ks = audio_plan::attn_slices(tt);
+                    launch_attn(a, nb, W2V_HD, ks, s, mode);
+                    ++ctx->n_audio_attn_f32[ks == 8 ? 0 : (ks == 4 ? 1 : 2)];
+                }
             }
             {
                 GemmArgs a = mkargs(Fr, W2V_H);
@@ -329,19 +339,19 @@ int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_fra
                 a.bias = ly.out.bias;
                 if (!tp) { a.res_kind = RES_PLAIN; a.res = ctx->aH; a.res_bstride = hs; a.res_pitch = Fp; }   // train mode: the LayerNorm kernel adds the residual, behind the dropout
                 a.y = ctx->aT; a.y_bstride = hs; a.y_pitch = Fp;
-                const LaunchCfg lc = pick_cfg(tt, W2V_H / 32);
-                launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
+                const LaunchCfg lc = audio_plan::hidden(tt);
+                if (on()) launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
             }
             if (tp) launch_ln_drop_cm(ctx->aT, ctx->aH, ctx->aH, ly.ln1g, ly.ln1b, nb, W2V_H, Fr, Fp, hs, 1e-5f, b0, site(at_site_layer(l, 1), tp->p_hidden, 8), none, s);
-            else launch_layernorm_cm(ctx->aT, nullptr, ctx->aH, ly.ln1g, ly.ln1b, nb, W2V_H, Fr, Fp, hs, 1e-5f, s);
+            else if (on()) launch_layernorm_cm(ctx->aT, nullptr, ctx->aH, ly.ln1g, ly.ln1b, nb, W2V_H, Fr, Fp, hs, 1e-5f, s);
             {
                 GemmArgs a = mkargs(Fr, W2V_FFN);
                 a.nseg = 1;
                 a.seg[0] = mkseg(ctx->aH, hs, Fp, W2V_H, 1, 0, 1, Fr, XF_NONE, ly.ff1.w[0]);
                 a.bias = ly.ff1.bias; a.act = ACT_GELU;
                 a.y = ctx->aF; a.y_bstride = (long long)W2V_FFN * Fp; a.y_pitch = Fp;
-                const LaunchCfg lc = pick_cfg(tt, W2V_FFN / 32);
-                launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
+                const LaunchCfg lc = audio_plan::ffn(tt);
+                if (on()) launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
             }
             if (tp) launch_drop_cm(ctx->aF, nb, W2V_FFN, Fr, Fp, (long long)W2V_FFN * Fp, b0, site(at_site_layer(l, 2), tp->p_activation, 16), nullptr, nullptr, s);
             {
@@ -351,11 +361,11 @@ int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_fra
                 a.bias = ly.ff2.bias;
                 if (!tp) { a.res_kind = RES_PLAIN; a.res = ctx->aH; a.res_bstride = hs; a.res_pitch = Fp; }   // train mode: the LayerNorm kernel adds the residual, behind the dropout
                 a.y = ctx->aT; a.y_bstride = hs; a.y_pitch = Fp;
-                const LaunchCfg lc = pick_cfg(tt, W2V_H / 32);
-                launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
+                const LaunchCfg lc = audio_plan::hidden(tt);
+                if (on()) launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
             }
             if (tp) launch_ln_drop_cm(ctx->aT, ctx->aH, ctx->aH, ly.ln2g, ly.ln2b, nb, W2V_H, Fr, Fp, hs, 1e-5f, b0, site(at_site_layer(l, 3), tp->p_hidden, 32), none, s);
-            else launch_layernorm_cm(ctx->aT, nullptr, ctx->aH, ly.ln2g, ly.ln2b, nb, W2V_H, Fr, Fp, hs, 1e-5f, s);
+            else if (on()) launch_layernorm_cm(ctx->aT, nullptr, ctx->aH, ly.ln2g, ly.ln2b, nb, W2V_H, Fr, Fp, hs, 1e-5f, s);
         }
         const float* fin = ctx->aH; long long fin_bs = hs;
         if (apply_proj) {  // diffusion.py:228-229
@@ -364,10 +374,11 @@ int audio_encode(said_ctx* ctx, const float* wav_dev, int B, int Ta, int num_fra
             a.seg[0] = mkseg(ctx->aH, hs, Fp, W2V_H, 1, 0, 1, Fr, XF_NONE, ctx->aproj.w[0]);
             a.bias = ctx->aproj.bias;
             a.y = ctx->aT; a.y_bstride = (long long)out_dim * Fp; a.y_pitch = Fp;
-            launch_gemm(a, EPI_STORE, nb, 1, 8, s);
+            const LaunchCfg lc = audio_plan::proj(tt);
+            if (on()) launch_gemm(a, EPI_STORE, nb, lc.NB, lc.KS, s);
             fin = ctx->aT; fin_bs = (long long)out_dim * Fp;
         }
-        launch_cm_to_tm(fin, out_dev + (long long)b0 * Fr * out_dim, nb, Fr, out_dim, Fp, fin_bs, s);
+        if (on()) launch_cm_to_tm(fin, out_dev + (long long)b0 * Fr * out_dim, nb, Fr, out_dim, Fp, fin_bs, s);
     }
     LAUNCHCHK();
     HIPCHK(hipGetLastError());

@@ -717,6 +717,9 @@ long long said_debug_get(const said_ctx* ctx, const char* name) {
     if (k == "n_tgemm_256d") return ctx->n_tgemm[TG_256D];
     if (k == "n_audio_attn_ks8") return ctx->n_audio_attn[0];
     if (k == "n_audio_attn_tm") return ctx->n_audio_attn[1];
+    if (k == "n_audio_attn_f32_ks8") return ctx->n_audio_attn_f32[0];
+    if (k == "n_audio_attn_f32_ks4") return ctx->n_audio_attn_f32[1];
+    if (k == "n_audio_attn_f32_ks1") return ctx->n_audio_attn_f32[2];
     if (k == "steps_per_graph") return ctx->spg_limit;
     if (k == "tm_acts") return ctx->tm_acts;
     if (k == "gemm_split") return (!ctx->bf16_mode && sp_on(ctx, ctx->gemm_split)) ? 1 : 0;
@@ -812,22 +815,37 @@ int said_debug_ws_copy(said_ctx* ctx, int idx, void* dst_dev, long long bytes, v
     HIPCHK(hipMemcpyAsync(dst_dev, ctx->ws_allocs[idx], (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
-// the audio encoder's lazily sized buffers by name (they are not part of the workspace list): bf16 mode's token-major set and the attention operands it shares with fp32 mode
+// the audio encoder's lazily sized buffers by name (they are not part of the workspace list): bf16 mode's token-major set, fp32 mode's channel-major set and the
+// attention operands both share
+struct AudioBuf { const char* name; void* p; };
+static std::vector<AudioBuf> audio_bufs(const said_ctx* ctx) {
+    return {{"bA0", ctx->bA0}, {"bA1", ctx->bA1}, {"bX", ctx->bX}, {"bXg", ctx->bXg}, {"bH", ctx->bH}, {"bHb", ctx->bHb}, {"bT", ctx->bT}, {"bF", ctx->bF},
+            {"bO", ctx->bO}, {"bPosT", ctx->bPosT}, {"aQK", ctx->aQK}, {"aVT", ctx->aVT}, {"aO", ctx->aO},
+            {"abufA", ctx->abufA}, {"abufB", ctx->abufB}, {"aX", ctx->aX}, {"aH", ctx->aH}, {"aT", ctx->aT}, {"aF", ctx->aF}, {"aPOS", ctx->aPOS}};
+}
 int said_debug_audio_copy(said_ctx* ctx, const char* name, void* dst_dev, long long bytes, void* stream) {
     if (!ctx) return -1;
     if (!name || !dst_dev || bytes < 0) return fail(ctx, "said_debug_audio_copy: bad arguments");
-    const std::pair<const char*, const void*> t[] = {
-        {"bA0", ctx->bA0}, {"bA1", ctx->bA1}, {"bX", ctx->bX}, {"bXg", ctx->bXg}, {"bH", ctx->bH}, {"bHb", ctx->bHb}, {"bT", ctx->bT}, {"bF", ctx->bF},
-        {"bO", ctx->bO}, {"bPosT", ctx->bPosT}, {"aQK", ctx->aQK}, {"aVT", ctx->aVT}, {"aO", ctx->aO}};
     const void* p = nullptr;
     bool known = false;
-    for (const auto& e : t) if (!strcmp(e.first, name)) { known = true; p = e.second; }
+    for (const AudioBuf& e : audio_bufs(ctx)) if (!strcmp(e.name, name)) { known = true; p = e.p; }
     if (!known) return fail(ctx, "said_debug_audio_copy: unknown buffer %s", name);
     auto it = p ? ctx->alloc_bytes.find(const_cast<void*>(p)) : ctx->alloc_bytes.end();
     if (it == ctx->alloc_bytes.end()) return fail(ctx, "said_debug_audio_copy: buffer %s is not allocated", name);
     if ((size_t)bytes > it->second) return fail(ctx, "said_debug_audio_copy: %lld bytes asked of %s, %zu allocated", bytes, name, it->second);
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipMemcpyAsync(dst_dev, p, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+int said_debug_audio_fill(said_ctx* ctx, int byte_value) {
+    if (!ctx) return -1;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipDeviceSynchronize());
+    for (const AudioBuf& e : audio_bufs(ctx)) {
+        auto it = e.p ? ctx->alloc_bytes.find(e.p) : ctx->alloc_bytes.end();
+        if (it != ctx->alloc_bytes.end()) HIPCHK(hipMemset(e.p, byte_value, it->second));
+    }
+    HIPCHK(hipDeviceSynchronize());
     return 0;
 }
 

@@ -16,6 +16,7 @@
 #include "../../include/said_hip.h"
 #include "said_hip_debug.h"
 #include "kernels.h"
+#include "audio_plan.h"
 #include "stchain.h"
 #include "tgemm.h"
 
@@ -172,7 +173,7 @@ struct Switches {
     int audio_chunk = 32;    // clips per audio-encoder pass
     int audio_train_sites = -1;  // said_audio_encode_train: which kinds of dropout site draw a mask — bits 1 feature projection, 2 encoder front, 4 probabilities, 8 attention output,
                                  // 16 activation, 32 FFN output; -1: all (said_debug_option "audio_train_sites": tests isolate the three sites that share p_hidden)
-    int audio_stop_after = -1;   // bf16 encoder: issue only the first n stages of each pass (said_debug_option "audio_stop_after"; < 0: all) — host side only
+    int audio_stop_after = -1;   // audio encoder (bf16 branch and fp32 branch outside train mode): issue only the first n stages of each pass (said_debug_option "audio_stop_after"; < 0: all) — host side only
 };
 
 // The fixed-size device cells: allocated once by alloc_cells (said_create and said_clone), written by the entry points and kernels of their own context only.
@@ -254,6 +255,7 @@ struct DebugState {
     long long n_xgemm = 0;    // launches issued through round 3's xgemm_kernel (said_debug_get; n_rgemm: through rgemm_kernel)
     long long n_tgemm[TG_NVARIANTS] = {0};   // the bf16 encoder's launch_tgemm calls per kernel (tgemm.h TGemmVariant; said_debug_get "n_tgemm_*")
     long long n_audio_attn[2] = {0, 0};      // ... and its attention launches: [0] eight key slices + cm_to_tm_bf16, [1] no key split, token-major bf16 store
+    long long n_audio_attn_f32[3] = {0, 0, 0};   // the fp32 encoder's attention launches (attn_kernel<2, KS, PM 2 / PM 0>) with [0] eight, [1] four key slices, [2] no key split
     long long n_audio_clips = 0;   // clips encoded by said_audio_encode so far (tests: identical rows of a batch are encoded once)
 };
 
@@ -378,8 +380,7 @@ int make_pw(HostCtx* ctx, PW* pw, const std::string& wname, const std::string& b
 int check_ready(said_ctx* ctx);   // 0 once said_finalize_weights has run, else -1 with the error set
 
 // ---- UNet launch schedules (unet_sched.cpp) ----
-struct LaunchCfg { int NB, KS; };
-LaunchCfg pick_cfg(long long t_tiles_total, int ntiles, bool allow6 = true);
+// (LaunchCfg and pick_cfg: audio_plan.h)
 Seg mkseg(const float* x, long long bstride, int pitch, int C, int taps, int pad, int stride, int Tin, int xform, const float* w);
 GemmArgs mkargs(int T, int N);
 // geometry of one UNet evaluation

@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "audio_plan.h"
 #include "gemm_common.h"
 
 namespace said {
@@ -662,12 +663,7 @@ static void configure_one() {
                               hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);
 }
 
-#define SAID_GEMM_CONFIGS(X)                                                                   \
-    X(EPI_STORE, 1, 8) X(EPI_STORE, 2, 8) X(EPI_STORE, 3, 4) X(EPI_STORE, 6, 4) X(EPI_STORE, 4, 4) \
-    X(EPI_QKV, 1, 8) X(EPI_QKV, 2, 8) X(EPI_QKV, 3, 4) X(EPI_QKV, 6, 4)                        \
-    X(EPI_GEGLU, 1, 8) X(EPI_GEGLU, 3, 4)                                                      \
-    X(EPI_BAND, 1, 8) X(EPI_BAND, 1, 4)
-
+// (SAID_GEMM_CONFIGS, the list of instantiations: audio_plan.h)
 void configure_gemm_kernels() {
 #define X(E, nb, ks) configure_one<nb, ks, E>();
     SAID_GEMM_CONFIGS(X)
@@ -675,14 +671,12 @@ void configure_gemm_kernels() {
 }
 
 void launch_gemm(const GemmArgs& a, int epi, int batch, int NB, int KS, hipStream_t s) {
+    // a tile shape that is not instantiated runs on one tile x 8 waves (cgemm_resolve, audio_plan.h)
+    const LaunchCfg r = cgemm_resolve(epi, NB, KS);
 #define X(E, nb, ks) \
-    if (epi == E && NB == nb && KS == ks) { launch_one<nb, ks, E>(a, batch, s); return; }
+    if (epi == E && r.NB == nb && r.KS == ks) { launch_one<nb, ks, E>(a, batch, s); return; }
     SAID_GEMM_CONFIGS(X)
 #undef X
-    // A tile shape chosen for the LDS-staged kernel that this kernel does not instantiate (the launch was not eligible
-    // there after all): every epilogue exists as one tile x 8 waves, and the q/k/v token-major split needs
-    // tm_tiles % NB == 0, which NB = 1 always satisfies.
-    if (!(NB == 1 && KS == 8)) { launch_gemm(a, epi, batch, 1, 8, s); return; }
     launch_fault("unsupported gemm config epi=%d NB=%d KS=%d", epi, NB, KS);
 }
 

@@ -18,12 +18,18 @@ extern "C" {
  *   "audio_chunk"            clips per audio-encoder pass (default 32)
  *   "audio_train_sites"      said_audio_encode_train: bit mask of the kinds of dropout site that draw a mask (1 feature projection, 2 encoder front, 4 attention probabilities,
  *                            8 attention output, 16 activation, 32 FFN output); the others run with p = 0.  < 0 (default): all.  The three sites of p_hidden can be told apart this way.
- *   "audio_stop_after"       bf16 mode: n >= 0 makes said_audio_encode issue only the first n stages of each pass and return 0 (the output is then undefined; the buffers hold
- *                            the intermediates: said_debug_audio_copy); < 0 (default): everything.  Host side only.  A stage is one launch site of the bf16 branch, in order:
+ *   "audio_stop_after"       n >= 0 makes said_audio_encode (and said_audio_extract_features) issue only the first n stages of each pass and return 0 (the output is then
+ *                            undefined; the buffers hold the intermediates: said_debug_audio_copy); < 0 (default): everything.  Host side only; said_audio_encode_train ignores
+ *                            it.  A stage is one launch site, asked whether or not it launches.  bf16 mode, the bf16 branch's sites in order:
  *                              0 conv0 + GroupNorm + GELU, 1-6 the strided convolutions, 7 interpolation + LayerNorm, 8 feature projection, 9 tm_to_group_bf16,
  *                              10 positional convolution, 11 encoder LayerNorm; layer l from 12 + 8 l: +0 q/k/v, +1 attention, +2 cm_to_tm_bf16 (a stage of its own also where the
  *                              key-split-free attention stores token-major itself and nothing is launched), +3 out_proj, +4 LayerNorm, +5 ff1, +6 ff2, +7 final LayerNorm;
  *                              then audio_proj_layer.  (Without the packed positional weights: 9 tm_to_cm, 10 the grouped fp32 convolution + cm_to_tm, 11 LayerNorm.)
+ *                            fp32 modes, the fp32 branch's sites in order:
+ *                              0 conv0, 1 per-channel GroupNorm + GELU, 2-7 the strided convolutions, 8 interpolation (a stage of its own also where no frame count is given and
+ *                              nothing is launched), 9 feature projection (LayerNorm in its operand transform), 10 positional convolution, 11 encoder LayerNorm; layer l from
+ *                              12 + 7 l: +0 q/k/v, +1 attention, +2 out_proj + residual, +3 LayerNorm, +4 ff1, +5 ff2 + residual, +6 final LayerNorm; then audio_proj_layer (only
+ *                              with apply_proj), then the final cm_to_tm.  said_audio_extract_features: its cm_to_tm store is stage 9, and the last.
  *   "steps_per_graph"        denoise steps captured per hipGraph in loops of >= 400 steps (default 50; until round 6: 10); shorter loops: min(this, 10)
  *   "tm_acts"                bf16 mode, large batches: token-major bf16 activations between the UNet kernels, GroupNorm / LayerNorm applied inside the consuming
  *                            GEMMs (-1 / 1, default); 0: channel-major fp32 activations with preparation kernels (round 2).  (The fp32 twin of the schedule, measured
@@ -55,7 +61,9 @@ extern "C" {
  * said_debug_get additionally knows "n_set_weight" (said_set_weight calls so far), "n_stchain" / "n_rgemm" / "n_xgemm" (launches issued through those kernels)
  * and "n_out_sched" / "n_out_sched_tm" / "n_sched_step" (the same for the step's last kernel: out_sched_kernel, out_sched_tm_kernel, sched_step_kernel);
  * of the bf16 audio encoder: "n_tgemm_128" / "n_tgemm_128sb" / "n_tgemm_128x64" / "n_tgemm_256" / "n_tgemm_256x192" / "n_tgemm_256d" (its GEMM launches per kernel: tgemm.h
- * TGemmVariant) and "n_audio_attn_ks8" / "n_audio_attn_tm" (attention launches with eight key slices / without key split and with the token-major bf16 store). */
+ * TGemmVariant) and "n_audio_attn_ks8" / "n_audio_attn_tm" (attention launches with eight key slices / without key split and with the token-major bf16 store);
+ * of the fp32 audio encoder: "n_audio_attn_f32_ks8" / "n_audio_attn_f32_ks4" / "n_audio_attn_f32_ks1" (attention launches with eight / four key slices / without key split:
+ * audio_plan.h attn_slices). */
 int said_debug_option(said_ctx* ctx, const char* name, long long value);
 long long said_debug_get(const said_ctx* ctx, const char* name);
 /* Stop the UNet schedule after `n_launches` kernel launches, counted from the start of each said_unet_forward / said_denoise_loop call (< 0: run
@@ -81,8 +89,13 @@ int said_debug_ws_copy(said_ctx* ctx, int idx, void* dst_dev, long long bytes, v
 /* The audio encoder's lazily sized buffers are not in that list.  Enqueues a device-to-device copy of the first `bytes` bytes of the named one — bf16 mode's token-major
  * buffers "bA0" "bA1" (feature-extractor ping-pong, bf16) "bX" (interpolated + normalised features, bf16) "bXg" (per-group positional-conv operand, bf16) "bH" (hidden state, fp32)
  * "bHb" (its bf16 copy) "bT" (GEMM results before LayerNorm, fp32) "bF" (feed-forward activation, bf16) "bO" (attention output, bf16) "bPosT", and the attention buffers "aQK"
- * "aVT" "aO" (fp32) — to `dst_dev` on `stream`.  Fails on an unknown name, a buffer no call has allocated yet, or more bytes than it holds. */
+ * "aVT" "aO" (fp32), and fp32 mode's channel-major buffers (fp32, [clip][channel][pitch], pitch = frames rounded up to 32): "abufA" "abufB" (feature-extractor ping-pong) "aX"
+ * (interpolated features) "aH" (hidden state) "aT" (GEMM results before LayerNorm; the audio_proj_layer output) "aF" (feed-forward activation) "aPOS" (positional convolution) — to
+ * `dst_dev` on `stream`.  Fails on an unknown name, a buffer no call has allocated yet, or more bytes than it holds. */
 int said_debug_audio_copy(said_ctx* ctx, const char* name, void* dst_dev, long long bytes, void* stream);
+/* Synchronises the device and sets EVERY byte of every allocated audio-encoder buffer (all the names above, fp32 and bf16 set alike) to `byte_value`: what said_debug_ws_fill
+ * is for the workspace.  An encode whose result changes with the fill value reads memory nobody wrote (pad rows frames .. pitch, or what an earlier, larger encode left). */
+int said_debug_audio_fill(said_ctx* ctx, int byte_value);
 
 #ifdef __cplusplus
 }

@@ -7,17 +7,6 @@
 namespace said {
 namespace host {
 
-LaunchCfg pick_cfg(long long t_tiles_total, int ntiles, bool allow6) {
-    // small problems: maximise workgroups (split K over 8 waves, one tile each);
-    // large problems: amortise the operand transform over more tiles per workgroup.
-    if (t_tiles_total * ntiles <= 1536 || ntiles % 2) return {1, 8};
-    if (t_tiles_total * ntiles <= 4096) return {2, 8};
-    if (allow6 && ntiles % 6 == 0) return {6, 4};
-    if (ntiles % 4 == 0) return {4, 4};
-    if (ntiles % 3 == 0) return {3, 4};
-    return {2, 8};
-}
-
 namespace {
 
 constexpr float ATTN_SCALE = 0.17677669529663687f;   // dim_head ** -0.5 = 32 ** -0.5 (attention.py:101)

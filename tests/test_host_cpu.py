@@ -31,7 +31,7 @@ def test_library_exports_every_declared_symbol():
 
 
 # ---------------------------------------------------------------- the headers against the one binding table, _engine.ABI
-GROUP_DECLARATIONS = {"core": 48, "metrics": 12, "optimize": 6, "train": 18, "render": 10, "render_ms": 1, "jpeg": 7, "unet_train": 24, "beat": 14, "transfer": 12, "audio_train": 1}   # 153
+GROUP_DECLARATIONS = {"core": 49, "metrics": 12, "optimize": 6, "train": 18, "render": 10, "render_ms": 1, "jpeg": 7, "unet_train": 24, "beat": 14, "transfer": 12, "audio_train": 1}   # 154
 _C_SCALARS = {"int": ("int", 4), "unsigned": ("int", 4), "unsigned int": ("int", 4), "uint32_t": ("int", 4), "long long": ("int", 8), "unsigned long long": ("int", 8), "int64_t": ("int", 8),
               "uint64_t": ("int", 8), "char": ("int", 1), "uint8_t": ("int", 1), "short": ("int", 2), "float": ("float", 4), "double": ("float", 8), "void": ("void", 0)}
 _POINTER = ("pointer", ctypes.sizeof(ctypes.c_void_p))
