@@ -325,6 +325,12 @@ _ABI_ADDED = {
                                                     c_int, _c_float_p]),
         "said_unet_train_last_conditioning": (c_int, [c_void_p, c_int, c_int, _c_float_p]),
     }),
+    "unet_products": Group(("said_amd/csrc/said_unet_train_products.h",), "split-fp16 products of the fine-tuned audio encoder", {
+        "said_unet_train_set_encoder_products": (c_int, [c_void_p, c_int]),
+        "said_unet_train_encoder_products": (c_int, [c_void_p]),
+        "said_unet_train_dense_product": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _c_float_p, _c_float_p, _c_float_p, _c_float_p, c_int, c_int,
+                                                  _c_float_p]),
+    }),
     "audio_features": Group(("said_amd/csrc/said_audio_features.h",), "the audio encoder's front end as a callable", {
         "said_audio_extract_features": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, _c_int_p, c_void_p]),
     }),
@@ -1112,6 +1118,9 @@ class TrainEngine(_TrainContext):
         return int(self.lib.said_train_graph_count(self.h))
 
 
+ENCODER_PRODUCTS = ("fp32", "split_fp16")   # a mode's index is its SAID_UT_PRODUCTS_* value
+
+
 class UNetTrainEngine(_TrainContext):
     """said_unet_train context on one GPU (include/said_unet_train.h): the denoiser's parameters, gradients, Adam moments and EMA shadow, and
     the training step.  Host arrays in and out (numpy); the audio embedding may be a device tensor.  The context keeps its own stream."""
@@ -1136,6 +1145,43 @@ class UNetTrainEngine(_TrainContext):
 
     def copy(self, dst: int, src: int) -> None:
         self._call("said_unet_train_copy", dst, src)
+
+    # ---- the arithmetic of the fine-tuned encoder's dense products (said_amd/csrc/said_unet_train_products.h)
+    def set_encoder_products(self, mode: str) -> None:
+        """"fp32" or "split_fp16", from the next call on; refused on a context without a fine-tuned encoder."""
+        if mode not in ENCODER_PRODUCTS:
+            raise ValueError(f"encoder_products must be one of {sorted(ENCODER_PRODUCTS)}, got {mode!r}")
+        load_library("unet_products")
+        self._call("said_unet_train_set_encoder_products", ENCODER_PRODUCTS.index(mode))
+
+    def encoder_products(self) -> str:
+        load_library("unet_products")
+        return ENCODER_PRODUCTS[int(self.lib.said_unet_train_encoder_products(self.h))]
+
+    def dense_product(self, layout: str, a, b, bias=None, res=None, out=None, mode: str = "fp32") -> np.ndarray:
+        """One dense product of a linear layer with weight W (n, k), by the route the encoder's products take in `mode`:
+        "forward": a = x (rows, k), b = W -> x W^T + bias (+ res) (+ out);  "dgrad": a = dy (rows, n), b = W -> dy W (+ out);
+        "wgrad": a = dy (rows, n), b = x (rows, k) -> dy^T x.  `out`: the destination's value before the call, added to."""
+        load_library("unet_products")
+        a, b, bias, res = _f32(a), _f32(b), _f32(bias), _f32(res)
+        rows = a.shape[0]
+        if layout == "forward":
+            n, k, shape = b.shape[0], b.shape[1], (rows, b.shape[0])
+        elif layout == "dgrad":
+            n, k, shape = b.shape[0], b.shape[1], (rows, b.shape[1])
+        elif layout == "wgrad":
+            n, k, shape = a.shape[1], b.shape[1], (a.shape[1], b.shape[1])
+        else:
+            raise ValueError(f"layout must be forward, dgrad or wgrad, got {layout!r}")
+        want_a, want_b = ((rows, k), (n, k)) if layout == "forward" else ((rows, n), (n, k)) if layout == "dgrad" else ((rows, n), (rows, k))
+        if a.shape != want_a or b.shape != want_b or (bias is not None and bias.shape != (n,)) or (res is not None and res.shape != shape) \
+                or (out is not None and tuple(np.shape(out)) != shape):
+            raise EngineError(f"dense_product {layout}: a {a.shape}, b {b.shape}, bias {None if bias is None else bias.shape}, "
+                              f"res {None if res is None else res.shape}, out {None if out is None else np.shape(out)}")
+        y = np.empty(shape, dtype=np.float32) if out is None else np.array(out, dtype=np.float32, order="C")
+        self._call("said_unet_train_dense_product", ("forward", "dgrad", "wgrad").index(layout), rows, n, k, _fp(a), _fp(b), _fp(bias), _fp(res),
+                   int(out is not None), ENCODER_PRODUCTS.index(mode), _fp(y))
+        return y
 
     def set_alphas(self, alphas_cumprod) -> None:
         a = _f32(alphas_cumprod).reshape(-1)

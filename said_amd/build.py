@@ -19,7 +19,7 @@ LIB = os.path.join(LIBDIR, "libsaid_hip.so")
 # gfx950 only.  SAID_OFFLOAD_ARCH may narrow the target ID for experiments (e.g. "gfx950:xnack-"; several, comma-separated,
 # give a fat binary from which the runtime picks the one matching the device).
 ARCHS = os.environ.get("SAID_OFFLOAD_ARCH", "gfx950").split(",")
-SOURCES = ["gemm.hip", "gemm_lds.hip", "attn.hip", "attn2q.hip", "audio_train.hip", "audio_ft.hip", "misc.hip", "out_sched.hip", "conv_in.hip", "tgemm.hip", "fgemm.hip", "xgemm.hip", "tm_kernels.hip", "rgemm.hip", "stchain.hip",
+SOURCES = ["gemm.hip", "gemm_lds.hip", "attn.hip", "attn2q.hip", "audio_train.hip", "audio_ft.hip", "enc_gemm.hip", "misc.hip", "out_sched.hip", "conv_in.hip", "tgemm.hip", "fgemm.hip", "xgemm.hip", "tm_kernels.hip", "rgemm.hip", "stchain.hip",
            "vae_dec.hip", "metrics.hip", "blendshape_qp.hip", "vae_train.hip", "unet_train.hip", "train_opt.hip", "render.hip", "jpeg.hip", "beat.hip", "deform_transfer.hip", "engine.cpp", "weights.cpp", "unet_sched.cpp", "audio_enc.cpp", "vae.cpp", "vae_trainer.cpp", "unet_trainer.cpp", "renderer.cpp", "jpeg_enc.cpp", "beat_ctx.cpp", "deform_transfer_ctx.cpp"]
 FLAGS = [*[f"--offload-arch={a}" for a in ARCHS], "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result"]
 # Round 5 (profiles/r05a_pk_fma_hazard.txt): on gfx950 a packed-fp32 VALU instruction (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) whose LOW half
@@ -27,7 +27,7 @@ FLAGS = [*[f"--offload-arch={a}" for a in ARCHS], "-O3", "-std=c++17", "-fPIC", 
 # MFMAs — the silent, concurrency-only corruption round 4 chased as "split-fp16 non-determinism".  hipcc's SLP vectoriser produces exactly that form whenever it
 # broadcasts the odd element of a loaded pair ((a, b) coefficients: x * a + b).  These sources are built without SLP vectorisation (bit-identical results: an
 # unpacked fma is the same fma), and EVERY object's ISA is scanned: a crossed packed-fp32 operand anywhere fails the build (check_packed_f32 below).
-NO_SLP = {"audio_train.hip", "audio_ft.hip", "render.hip", "jpeg.hip", "gemm_lds.hip", "misc.hip", "out_sched.hip", "tgemm.hip", "fgemm.hip", "xgemm.hip", "tm_kernels.hip", "stchain.hip", "vae_dec.hip", "vae_train.hip", "vae_trainer.cpp", "unet_train.hip", "unet_trainer.cpp", "train_opt.hip"}
+NO_SLP = {"audio_train.hip", "audio_ft.hip", "enc_gemm.hip", "render.hip", "jpeg.hip", "gemm_lds.hip", "misc.hip", "out_sched.hip", "tgemm.hip", "fgemm.hip", "xgemm.hip", "tm_kernels.hip", "stchain.hip", "vae_dec.hip", "vae_train.hip", "vae_trainer.cpp", "unet_train.hip", "unet_trainer.cpp", "train_opt.hip"}
 
 
 def _hipcc() -> str:

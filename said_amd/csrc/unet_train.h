@@ -43,6 +43,9 @@ struct UGemm {
     float* part;
 };
 void gemm(hipStream_t s, const UGemm& g);
+// the second launch of a K-split gemm alone: C = epilogue(sum over ks of part[ks]) in ascending chunk order; for a kernel that wrote the
+// partial tiles itself (enc_gemm.hip)
+void gemm_reduce(hipStream_t s, const UGemm& g);
 
 // out[seg][n] (+)= sum over the rows r of segment seg (rows seg * rows .. seg * rows + rows - 1) of x[r ld + n] (* mul[r ldm + n])
 void colsum(hipStream_t s, const float* x, int ld, const float* mul, int ldm, int rows, int nseg, int N, float* out, int accumulate);

@@ -452,8 +452,9 @@ __global__ void __launch_bounds__(NT) loss_final_kernel(int B, int T, const floa
 void gemm(hipStream_t s, const UGemm& g) {
     dim3 grid((g.M + BM - 1) / BM, (g.N + BN - 1) / BN, g.Z * g.KS);
     gemm_kernel<<<grid, NT, 0, s>>>(g);
-    if (g.KS > 1) gemm_reduce_kernel<<<nblk((long long)g.M * g.N * g.Z), NT, 0, s>>>(g);
+    if (g.KS > 1) gemm_reduce(s, g);
 }
+void gemm_reduce(hipStream_t s, const UGemm& g) { gemm_reduce_kernel<<<nblk((long long)g.M * g.N * g.Z), NT, 0, s>>>(g); }
 void colsum(hipStream_t s, const float* x, int ld, const float* mul, int ldm, int rows, int nseg, int N, float* out, int accumulate) {
     colsum_kernel<<<dim3((N + 15) / 16, nseg), NT, 0, s>>>(x, ld, mul, ldm, rows, N, out, accumulate);
 }

@@ -3,10 +3,13 @@
 // order on the context's stream (unet_train.hip).  T is a run-time value, so nothing is captured into a graph.  A context made with
 // feature_dim = F > 0 also holds and trains audio_proj_layer (768 -> F) and runs the context at width F; F <= 0 leaves every launch as it is.
 // A context made with finetune_layers = L > 0 (said_unet_finetune.h) also holds and trains the Wav2Vec2 transformer in the same store: its
-// forward runs in front of the UNet's and its backward behind it (kernels: audio_ft.hip); L <= 0 leaves every launch as it is.
-#include "said_unet_finetune.h"
+// forward runs in front of the UNet's and its backward behind it (kernels: audio_ft.hip); L <= 0 leaves every launch as it is.  Such a context
+// can run the encoder's dense products on split-fp16 operands (said_unet_train_products.h; kernel: enc_gemm.hip); the default leaves every
+// launch as it is.
+#include "said_unet_train_products.h"
 
 #include "audio_ft.h"
+#include "enc_gemm.h"
 #include "engine_internal.h"
 #include "train_store.h"
 #include "unet_train.h"
@@ -152,6 +155,8 @@ struct said_unet_train {
     unsigned char* mask = nullptr;   // L > 0: the step's time mask (B T)
     long long enc_off = 0, enc_n = 0;   // L > 0: the encoder's tensors in the store
     size_t gpart_n = 0;
+    int products = SAID_UT_PRODUCTS_FP32;   // L > 0: the arithmetic of the encoder's dense products (said_unet_train_products.h)
+    unsigned* amax = nullptr;               // split products: the partial maxima of a gradient operand, allocated when the mode is first asked for
     EncActs e;
     const std::vector<TDesc>* tb = nullptr;
     hipStream_t s = nullptr;
@@ -222,6 +227,14 @@ UOp plain(const float* p, int sr, int sc, long long zb = 0, long long zh = 0) { 
 
 struct Gm {
     said_unet_train* t;
+    int products = SAID_UT_PRODUCTS_FP32;   // of lin / lin_dgrad / lin_wgrad: the encoder's dense products are made with the context's mode
+    bool split() const { return products == SAID_UT_PRODUCTS_SPLIT_F16; }
+    eg::EncGemm split_base(int layout, const float* a, int lda, const float* b, int ldb, float* c, int ldc, int M, int N, int K) const {
+        eg::EncGemm g{};
+        g.layout = layout; g.a = a; g.lda = lda; g.b = b; g.ldb = ldb; g.c = c; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.KS = 1; g.kchunk = M;
+        g.part = t->gpart; g.amax = t->amax;
+        return g;
+    }
     UGemm base(UOp A, UOp B, float* C, int ldc, int M, int N, int K) const {
         UGemm g{};
         g.A = A; g.B = B; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.Z = 1; g.ZH = 1; g.alpha = 1.f; g.rbT = 1; g.KS = 1; g.kchunk = ut_unsplit(K).kchunk;
@@ -235,21 +248,38 @@ struct Gm {
     // y (M, N) = x (M, K; ldx) W^T (W: N x K) + bias (+ rowb) (+ res)
     void lin(const float* x, int ldx, const float* W, const float* bias, float* y, int ldy, int M, int N, int K, const float* res = nullptr, int ldr = 0,
              int accumulate = 0) const {
+        if (split()) {
+            eg::EncGemm e = split_base(eg::EG_FWD, x, ldx, W, K, y, ldy, M, N, K);
+            e.bias = bias; e.res = res; e.ldr = ldr; e.accumulate = accumulate;
+            return eg::enc_gemm(t->s, e);
+        }
         UGemm g = base(plain(x, ldx, 1), plain(W, K, 1), y, ldy, M, N, K);
         g.bias = bias; g.res = res; g.ldr = ldr; g.accumulate = accumulate;
         gemm(t->s, g);
     }
     // dx (M, K; lddx) (+)= dy (M, N) W
     void lin_dgrad(const float* dy, const float* W, float* dx, int lddx, int M, int N, int K, int accumulate) const {
+        if (split()) {
+            eg::EncGemm e = split_base(eg::EG_DGRAD, dy, N, W, K, dx, lddx, M, N, K);
+            e.accumulate = accumulate;
+            return eg::enc_gemm(t->s, e);
+        }
         UGemm g = base(plain(dy, N, 1), plain(W, 1, K), dx, lddx, M, K, N);
         g.accumulate = accumulate;
         gemm(t->s, g);
     }
     // dW (N, K) = dy^T (rows x N) x (rows x K; ldx); dbias = column sums of dy
     void lin_wgrad(const float* dy, const float* x, int ldx, float* dW, float* dbias, int rows, int N, int K) const {
-        UGemm g = base(plain(dy, 1, N), plain(x, 1, ldx), dW, K, N, K, rows);
-        ksplit(g);
-        gemm(t->s, g);
+        if (split()) {
+            eg::EncGemm e = split_base(eg::EG_WGRAD, dy, N, x, ldx, dW, K, rows, N, K);
+            const UtSplit p = ut_ksplit(rows, N, K, 1, t->gpart_n);
+            e.KS = p.KS; e.kchunk = p.kchunk;
+            eg::enc_gemm(t->s, e);
+        } else {
+            UGemm g = base(plain(dy, 1, N), plain(x, 1, ldx), dW, K, N, K, rows);
+            ksplit(g);
+            gemm(t->s, g);
+        }
         if (dbias) colsum(t->s, dy, N, nullptr, 0, rows, 1, N, dbias, 0);
     }
     // Conv1d(k = 3, padding 1) over (B, T): y (M, Co) = sum_j x[t + j - 1] W[:, :, j]^T
@@ -583,7 +613,7 @@ struct EncGm {
 void enqueue_enc_forward(said_unet_train* t, int B, int T, const float* base, const said_audio_train_params* tp) {
     hipStream_t s = t->s;
     EncActs& e = t->e;
-    const Gm gm{t};
+    const Gm gm{t, t->products};
     const EncGm eg{t, B, T};
     const int M = B * T;
     auto w = [&](const std::string& n) { return par(t, base, kEnc + n); };
@@ -633,7 +663,7 @@ void enqueue_enc_forward(said_unet_train* t, int B, int T, const float* base, co
 void enqueue_enc_backward(said_unet_train* t, int B, int T, const said_audio_train_params* tp, float* dE) {
     hipStream_t s = t->s;
     EncActs& e = t->e;
-    const Gm gm{t};
+    const Gm gm{t, t->products};
     const EncGm eg{t, B, T};
     const int M = B * T;
     const float* P = t->st.P;
@@ -1100,6 +1130,76 @@ int said_unet_train_last_conditioning(said_unet_train* t, int B, int T, float* o
     layout(t->a, t->arena, B, T, t->F, t->L, &t->e);
     HIPCHK(hipMemcpyAsync(out, t->a.ctx, (size_t)B * T * t->CTX * sizeof(float), hipMemcpyDeviceToHost, t->s));
     HIPCHK(hipStreamSynchronize(t->s));
+    return 0;
+}
+
+// the split products' scratch exists only in a context that was asked for them
+static int need_split_scratch(said_unet_train* t) {
+    if (t->amax) return 0;
+    return dalloc(&t->c, &t->amax, eg::EG_AMAX_BLOCKS);
+}
+
+int said_unet_train_set_encoder_products(said_unet_train* t, int mode) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    const char* what = "said_unet_train_set_encoder_products";
+    if (t->L <= 0) return fail(ctx, "%s: the context has no fine-tuned encoder (said_unet_train_create_ft with finetune_layers >= 1)", what);
+    if (mode != SAID_UT_PRODUCTS_FP32 && mode != SAID_UT_PRODUCTS_SPLIT_F16)
+        return fail(ctx, "%s: unknown mode %d (SAID_UT_PRODUCTS_FP32 = 0, SAID_UT_PRODUCTS_SPLIT_F16 = 1)", what, mode);
+    static_assert(eg::enc_gemm_takes(EH, EH) && eg::enc_gemm_takes(EH, ECONV) && eg::enc_gemm_takes(EFFN, EH), "enc_gemm.hip's tile and the encoder's widths");
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (mode == SAID_UT_PRODUCTS_SPLIT_F16 && need_split_scratch(t)) return -1;
+    t->products = mode;
+    return 0;
+}
+
+int said_unet_train_encoder_products(const said_unet_train* t) { return t ? t->products : -1; }
+
+int said_unet_train_dense_product(said_unet_train* t, int layout, int rows, int n, int k, const float* a_host, const float* b_host,
+                                  const float* bias_host, const float* res_host, int accumulate, int mode, float* out_host) {
+    if (!t) return -1;
+    HostCtx* ctx = &t->c;
+    const char* what = "said_unet_train_dense_product";
+    const bool fwd = layout == SAID_UT_PRODUCT_FORWARD, dg = layout == SAID_UT_PRODUCT_DGRAD, wg = layout == SAID_UT_PRODUCT_WGRAD;
+    if (!fwd && !dg && !wg) return fail(ctx, "%s: unknown layout %d", what, layout);
+    if (mode != SAID_UT_PRODUCTS_FP32 && mode != SAID_UT_PRODUCTS_SPLIT_F16) return fail(ctx, "%s: unknown mode %d", what, mode);
+    if (rows < 1 || n < 1 || k < 1 || (long long)rows * std::max(n, k) >= (1ll << 31) || (long long)n * k >= (1ll << 31))
+        return fail(ctx, "%s: %d rows, widths (%d, %d)", what, rows, n, k);
+    if (!a_host || !b_host || !out_host) return fail(ctx, "%s: null operand or output", what);
+    if (!fwd && (bias_host || res_host)) return fail(ctx, "%s: only the forward layout has a bias and a residual", what);
+    if (wg && accumulate) return fail(ctx, "%s: the weight gradient does not accumulate", what);
+    if (mode == SAID_UT_PRODUCTS_SPLIT_F16) {
+        if (t->L <= 0) return fail(ctx, "%s: split products need a context with a fine-tuned encoder", what);
+        if (!eg::enc_gemm_takes(n, k)) return fail(ctx, "%s: split products take widths that are multiples of %d, got (%d, %d)", what, eg::EG_TILE, n, k);
+    }
+    DeviceRestore restore_device;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (mode == SAID_UT_PRODUCTS_SPLIT_F16 && need_split_scratch(t)) return -1;
+    const size_t na = (size_t)rows * (fwd ? k : n), nb = wg ? (size_t)rows * k : (size_t)n * k;
+    const size_t no = fwd ? (size_t)rows * n : dg ? (size_t)rows * k : (size_t)n * k;
+    // one allocation for the call: a, b, out, bias, res, each from a 256-byte boundary
+    auto up = [](size_t v) { return (v + 63) / 64 * 64; };
+    const size_t oa = 0, ob = oa + up(na), oo = ob + up(nb), obias = oo + up(no), ores = obias + up((size_t)n), total = ores + up(no);
+    float* buf = nullptr;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&buf), total * sizeof(float)));
+    int rc = 0;
+    auto put = [&](size_t off, const float* h, size_t cnt) {
+        if (!rc && h && hipMemcpyAsync(buf + off, h, cnt * sizeof(float), hipMemcpyHostToDevice, t->s) != hipSuccess) rc = -1;
+    };
+    put(oa, a_host, na); put(ob, b_host, nb); put(obias, bias_host, (size_t)n); put(ores, res_host, no);
+    if (accumulate) put(oo, out_host, no);
+    else if (!rc && hipMemsetAsync(buf + oo, 0xff, no * sizeof(float), t->s) != hipSuccess) rc = -1;   // NaNs: the product must write every element
+    if (!rc) {
+        const Gm gm{t, mode};
+        if (fwd) gm.lin(buf + oa, k, buf + ob, bias_host ? buf + obias : nullptr, buf + oo, n, rows, n, k, res_host ? buf + ores : nullptr, n, accumulate);
+        else if (dg) gm.lin_dgrad(buf + oa, buf + ob, buf + oo, k, rows, n, k, accumulate);
+        else gm.lin_wgrad(buf + oa, buf + ob, k, buf + oo, nullptr, rows, n, k);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out_host, buf + oo, no * sizeof(float), hipMemcpyDeviceToHost, t->s) != hipSuccess) rc = -1;
+    }
+    const hipError_t se = hipStreamSynchronize(t->s);
+    (void)hipFree(buf);
+    if (rc || se != hipSuccess) return fail(ctx, "%s: a copy or a launch failed: %s", what, hipGetErrorString(se));
     return 0;
 }
 

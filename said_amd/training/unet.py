@@ -173,18 +173,27 @@ class UNetTrainer(TrainerBase):
     finetune_audio_layers = L > 0 trains the Wav2Vec2 transformer of `state_dict`'s L-layer encoder with the denoiser (the reference's
     `said_model.audio_encoder.freeze_feature_encoder()` variant): audio_encoder.* except audio_encoder.feature_extractor.*
     join the trainable tensors, and step / eval_loss / forward_only take the frozen extractor's features (B, T, 512) (batch_audio_features)
-    in place of the audio embedding.  step's audio_draws / audio_cfg put the encoder in Wav2Vec2's train mode.
+    in place of the audio embedding.  step's audio_draws / audio_cfg put the encoder in Wav2Vec2's train mode.  There
+    encoder_products = "split_fp16" runs the encoder's dense products on split-fp16 operands (22 significand bits, fp32 accumulation; DESIGN.md
+    16.10) in step, eval_loss and forward_only; "fp32", the default, leaves every launch as it is.  Given without fine-tuning it is refused.
     """
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", max_batch: int = 8, max_frames: int = 512, learning_rate: float = 1e-5,
                  num_warmup_steps: float = 0, ema: bool = True, ema_decay: float = 0.9999, std=None, prediction_type: str = "epsilon",
                  dropout: float = 0.1, weight_decay: float = 0.01, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 num_train_timesteps: int = 1000, feature_dim: int = -1, finetune_audio_layers: int = 0):
+                 num_train_timesteps: int = 1000, feature_dim: int = -1, finetune_audio_layers: int = 0, encoder_products: Optional[str] = None):
         if prediction_type not in PREDICTION_TYPES:
             raise ValueError(f"prediction_type must be one of {sorted(PREDICTION_TYPES)}, got {prediction_type!r}")
+        if encoder_products is not None and encoder_products not in _engine.ENCODER_PRODUCTS:
+            raise ValueError(f"encoder_products must be one of {sorted(_engine.ENCODER_PRODUCTS)}, got {encoder_products!r}")
+        if encoder_products is not None and finetune_audio_layers <= 0:
+            raise ValueError("encoder_products: the encoder is frozen here; its products are the trainer's only with finetune_audio_layers > 0")
         self.eng = _engine.UNetTrainEngine(torch.device(device), max_batch, max_frames, feature_dim, finetune_audio_layers)
         self.feature_dim = self.eng.feature_dim
         self.finetune_audio_layers = self.eng.finetune_layers
+        self.encoder_products = encoder_products or "fp32"
+        if encoder_products is not None:
+            self.eng.set_encoder_products(encoder_products)
         self.device = self.eng.device
         self.max_batch, self.max_frames = int(max_batch), int(max_frames)
         self._set_optimizer(learning_rate, num_warmup_steps, weight_decay, betas, eps, ema, ema_decay)

@@ -70,6 +70,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="the frozen audio encoder during training: 'eval' as in inference, 'train' as the reference leaves it (SpecAugment, dropout, LayerDrop)")
     ap.add_argument("--finetune_audio_encoder", action="store_true",
                     help="train the Wav2Vec2 transformer with the denoiser (the feature extractor stays frozen)")
+    ap.add_argument("--encoder_products", type=str, default=None, choices=["fp32", "split_fp16"],
+                    help="with --finetune_audio_encoder: the arithmetic of the encoder's dense products: 'fp32' (the default) or 'split_fp16' "
+                         "(split-fp16 operands, 22 significand bits, fp32 accumulation: faster)")
     ap.add_argument("--seed", type=int, default=None, help="seed of Python's random, numpy and torch (unseeded by default)")
     ap.add_argument("--device", type=str, default="cuda:0", help="MI355X to train on (there is no CPU path)")
     return ap
@@ -79,6 +82,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.unet_feature_dim > 0 and (args.unet_feature_dim % 16 or args.unet_feature_dim > 1024):
         raise SystemExit(f"--unet_feature_dim {args.unet_feature_dim}: must be a multiple of 16 up to 1024 (the context widths SAID_UNet1D's engine and the trainer take)")
+    if args.encoder_products is not None and not args.finetune_audio_encoder:
+        raise SystemExit("--encoder_products: needs --finetune_audio_encoder (the frozen encoder's products are not the trainer's)")
     if args.seed is not None:
         random.seed(args.seed)
         np.random.seed(args.seed)
@@ -110,7 +115,8 @@ def main(argv=None):
     trainer = UNetTrainer(state, args.device, max_batch=args.batch_size, max_frames=max_frames, learning_rate=args.learning_rate,
                           num_warmup_steps=len(train_dataloader) * args.num_warmup_epochs, ema=args.ema, ema_decay=args.ema_decay, std=coeffs_std,
                           prediction_type=args.prediction_type, feature_dim=args.unet_feature_dim,
-                          finetune_audio_layers=model.audio_config.num_hidden_layers if args.finetune_audio_encoder else 0)
+                          finetune_audio_layers=model.audio_config.num_hidden_layers if args.finetune_audio_encoder else 0,
+                          encoder_products=args.encoder_products)
 
     audio_train = AudioTrainConfig() if args.audio_encoder_mode == "train" else None
     with open(os.path.join(args.output_dir, "log.csv"), "a", newline="") as f:

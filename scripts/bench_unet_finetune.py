@@ -8,11 +8,17 @@
   restatement draws them with numpy on the host, which is no part of a step's GPU time): fewer operations than the HIP side runs.
 
     python scripts/bench_unet_finetune.py [--batch 8] [--frames 120 240] [--windows 5] [--steps 10] [--warmup 5] [--layers 12]
+                                          [--products fp32 split_fp16] [--baseline_lib PATH]
+
+--products: the arithmetic of the encoder's dense products (UNetTrainer(encoder_products=...)) that the fine-tuning step is
+timed in: finetune_step_ms is the fp32 one, finetune_step_split_fp16_ms the split-fp16 one, on one context switched between the windows.
+--baseline_lib: a libsaid_hip.so built from another commit; its fine-tuning step (fp32) is timed beside as baseline_finetune_step_ms.
 
 Every figure is the median over --windows timed windows of --steps steps each (host clock around work that ends in a device synchronise),
-the three sides alternating window by window.  One JSON line per frame count.
+the sides alternating window by window.  One JSON line per frame count.
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -24,12 +30,25 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+from said_amd import _engine  # noqa: E402
 from said_amd.model.diffusion import SAID_UNet1D  # noqa: E402
 from said_amd.model.wav2vec2 import AudioConfig, AudioTrainConfig, draw_audio_train  # noqa: E402
 from said_amd.training import UNetTrainer, trainable_shapes  # noqa: E402
 from said_amd.util.synth import said_state_dict, synth_waveform  # noqa: E402
 import audio_ft_ref as aft  # noqa: E402
 import unet_train_ref as ref  # noqa: E402
+
+
+def trainer_on_library(path, *args, **kw):
+    """A UNetTrainer whose context lives in another build of the library; this build's groups must be bound already."""
+    lib = ctypes.CDLL(path)
+    for group in ("core", "unet_train", "unet_finetune"):
+        _engine._bind(lib, group)
+    mine, _engine._lib = _engine._lib, lib
+    try:
+        return UNetTrainer(*args, **kw)
+    finally:
+        _engine._lib = mine
 
 
 def main():
@@ -40,6 +59,8 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--products", nargs="+", default=["fp32", "split_fp16"], choices=sorted(_engine.ENCODER_PRODUCTS))
+    ap.add_argument("--baseline_lib", default=None)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     dev = torch.device(a.device)
@@ -47,6 +68,10 @@ def main():
     sd = said_state_dict(num_w2v_layers=L)
     ft = UNetTrainer(sd, dev, max_batch=B, max_frames=max(a.frames), learning_rate=1e-5, num_warmup_steps=10, finetune_audio_layers=L)
     frozen = UNetTrainer(sd, dev, max_batch=B, max_frames=max(a.frames), learning_rate=1e-5, num_warmup_steps=10)
+    base = None
+    if a.baseline_lib:
+        base = trainer_on_library(a.baseline_lib, sd, dev, max_batch=B, max_frames=max(a.frames), learning_rate=1e-5, num_warmup_steps=10,
+                                  finetune_audio_layers=L)
     model = SAID_UNet1D(audio_config=AudioConfig(num_hidden_layers=L))
     model.load_state_dict(sd, strict=True)
     model.to(dev)
@@ -63,9 +88,11 @@ def main():
         c_d, n_d, ts_d, ac, cond_d = coeffs.to(dev), noise.to(dev), ts.to(dev), ft.alphas_cumprod.to(dev), torch.tensor(cond, device=dev)
         count = [0]
 
-        def ft_step():
+        def ft_step(tr=ft, products="fp32"):
             count[0] += 1
-            ft.step(coeffs, cond, feats, noise=noise, timesteps=ts, dropout_seed=count[0], audio_draws=draw_audio_train(cfg, B, T, L), audio_cfg=cfg)
+            if tr is ft and ft.eng.encoder_products() != products:
+                ft.eng.set_encoder_products(products)
+            tr.step(coeffs, cond, feats, noise=noise, timesteps=ts, dropout_seed=count[0], audio_draws=draw_audio_train(cfg, B, T, L), audio_cfg=cfg)
 
         def frozen_step():
             count[0] += 1
@@ -85,7 +112,12 @@ def main():
             opt.zero_grad()
             float(losses[0])
 
-        sides = {"finetune_step_ms": ft_step, "frozen_step_ms": frozen_step, "frozen_step_with_encode_ms": frozen_encode_step, "torch_eager_step_ms": eager_step}
+        sides = {}
+        if base is not None:
+            sides["baseline_finetune_step_ms"] = lambda: ft_step(base)
+        for mode in a.products:
+            sides["finetune_step_ms" if mode == "fp32" else f"finetune_step_{mode}_ms"] = lambda mode=mode: ft_step(ft, mode)
+        sides.update({"frozen_step_ms": frozen_step, "frozen_step_with_encode_ms": frozen_encode_step, "torch_eager_step_ms": eager_step})
         for f in sides.values():
             for _ in range(a.warmup):
                 f()
